@@ -16,8 +16,15 @@ GPUs (weak scaling, no data-path collective).
 * ``--workload``: c2 (default, the headline), c3 = the train_sequential step with its gradient all-reduce (the only
   collective of the path), c4 = the 60 fps / d_model 512 / window 512 shape, c5 = streaming ticks (128 streams per GPU,
   hipGraph replay).
-* extra objects on the line: ``roofline`` (dominant kernel; executed FLOPs / launch time measured live with HIP events
-  on the launch stream, km_enable_stage_timing) and ``cpu_baseline`` (the CPU oracle on this host, N = 1 only).
+* A plain run sets up, warms up, times the K steps and prints the line (``value``, ``ms_per_step`` and the workload's
+  configuration).  ``--full`` adds everything else, each measured in runs of its own after the timed steps: ``roofline``
+  (dominant kernel; executed FLOPs / launch time measured live with HIP events on the launch stream,
+  km_enable_stage_timing), ``cpu_baseline`` (the CPU oracle on this host, N = 1 only), ``ms_per_step_cached_input``,
+  the split-bf16 variant (C2), ``ms_per_step_no_spinup`` (the W + K steps timed once more before the spin-up, on a
+  cold chip) and, for N > 1, the ``collective`` object.
+* ``--dump-outputs DIR`` (c2, c4): after the timed steps, what the last timed step returned is written as float32
+  ``DIR/<name>.npy`` (rank r > 0: ``<name>.rank<r>.npy``).  The timed pass starts a fresh stream from the first input
+  batch after the spin-up, so that with the same arguments the written arrays are the same from run to run.
 """
 from __future__ import annotations
 
@@ -54,6 +61,8 @@ PEAK_F32_MFMA_TFLOPS = 157.3              # /opt/skills/guides/MI355X_MICROARCH.
 PEAK_HBM_GBS = 8000.0
 
 METRIC = "blendshape frames/sec (52-coef, 256-win, d_model=256)"
+DUMP_WORKLOADS = ("c2", "c4")            # workloads whose timed pass can be restarted from a fixed state (--dump-outputs)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def parse_args():
@@ -70,7 +79,14 @@ def parse_args():
     ap.add_argument("--cpu-seconds", type=float, default=18.0, help="CPU-baseline time budget (0 = skip)")
     ap.add_argument("--cpu-windows", type=int, default=None, help="deprecated: 0 skips the CPU baseline")
     ap.add_argument("--no-split", action="store_true", help="skip the experimental split-bf16 timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / per-kernel times, CPU baseline, "
+                         "no-spin-up and cached-input timings, split-bf16 variant, collective (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (c2, c4)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in DUMP_WORKLOADS:
+        ap.error(f"--dump-outputs supports the workloads {', '.join(DUMP_WORKLOADS)}")
     defaults = {"c2": (200, 20, 256), "c3": (100, 10, 8), "c4": (50, 5, 256), "c5": (300, 20, 128), "rendezvous": (3, 1, 1)}[args.workload]
     if args.steps is None:
         args.steps = defaults[0]
@@ -226,15 +242,20 @@ def _timed_once(rk: Ranks, step, steps: int, warmup: int, flush=None) -> float:
     return rk.max_over_ranks(time.perf_counter() - t0)
 
 
-def timed(rk: Ranks, step, steps: int, warmup: int, flush=None, spin: bool = True) -> float:
-    """W untimed steps, then EXACTLY K steps between barrier + synchronize on both sides; MAX over ranks (seconds).
-    The workload's FIRST measurement is taken twice: once exactly as the command line says (W warmup steps on a chip that
-    has done nothing yet -> rk.no_spinup_ms, printed as ``ms_per_step_no_spinup``), then again behind SPINUP_SECONDS of
-    untimed load (the steady-state figure every line reports as ``ms_per_step`` / ``value``)."""
+def timed(rk: Ranks, step, steps: int, warmup: int, flush=None, spin: bool = True, restart=None,
+          no_spinup: bool = False) -> float:
+    """W untimed steps, then EXACTLY K steps between barrier + synchronize on both sides, behind SPINUP_SECONDS of
+    untimed load (the steady-state figure every line reports as ``ms_per_step`` / ``value``); MAX over ranks (seconds).
+    ``no_spinup`` (the workload's headline measurement under --full): the same W + K steps are first taken exactly as
+    the command line says, before the spin-up, on a chip that has done nothing yet -> rk.no_spinup_ms, printed as
+    ``ms_per_step_no_spinup``.  ``restart`` runs after the spin-up, before the W warmup steps: it puts the workload back
+    to a fixed state so that what the last timed step computes depends on W and K only (--dump-outputs)."""
     use_spin = spin and not os.environ.get("KM_BENCH_NO_SPINUP")
-    if use_spin and getattr(rk, "no_spinup_ms", None) is None:
+    if use_spin and no_spinup:
         rk.no_spinup_ms = _timed_once(rk, step, steps, warmup, flush) / steps * 1e3
     spin_up(rk, step, SPINUP_SECONDS if use_spin else 0.0)
+    if restart is not None:
+        restart()
     return _timed_once(rk, step, steps, warmup, flush)
 
 
@@ -370,19 +391,44 @@ def run_c2(args, rk: Ranks):
     # of a step come from HBM, not from the Infinity Cache a single replayed 139.7 MB batch would sit in
     bufs, rot_bytes = rotating_inputs(torch, audio)
     it = [0]
+    first = [True]
 
-    def step(first=False):
+    def step():
         a = bufs[it[0] % len(bufs)]
         it[0] += 1
-        eng.forward_audio(a, emo, state=state, first=first, out=out)
+        eng.forward_audio(a, emo, state=state, first=first[0], out=out)
+        first[0] = False
+
+    def restart():          # a fresh stream from batch 0: the EMA state of the last timed step no longer depends on the spin-up
+        it[0] = 0
+        first[0] = True
 
     def step_cached():
         eng.forward_audio(audio, emo, state=state, first=False, out=out)
 
-    step(first=True)
-    dt = timed(rk, step, args.steps, args.warmup)
+    step()
+    dt = timed(rk, step, args.steps, args.warmup, restart=restart, no_spinup=args.full)
     ms_per_step = dt / args.steps * 1e3
     value = B * rk.world * args.steps / dt
+    if args.dump_outputs:
+        rk.outputs = {"blendshapes": out.cpu().numpy(), "ema_state": state.cpu().numpy()}
+    line = {
+        "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": rk.world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "rtf_30fps": round(30.0 / (value / rk.world), 8), "rccl_ranks": rk.rccl_ranks,
+        # K distinct audio batches used round-robin (together past the 256 MiB Infinity Cache): `value` / `ms_per_step` /
+        # kernel_ms / roofline are measured on them; ms_per_step_cached_input (--full) = the same step replaying ONE batch
+        # (what rounds 1-3 reported: its 139.7 MB stay on-die)
+        "input_rotation": {"buffers": len(bufs), "bytes_total": rot_bytes, "infinity_cache_bytes": INFINITY_CACHE_BYTES},
+        "config": {"workload": "C2: 256 windows/GPU x 136448 samples (8.5 s @16 kHz) -> 1024-pt STFT, hop 533, "
+                               "80-bin log-mel (257 frames) -> dual-stream attention d_model=256, 8 heads, "
+                               "window 256 -> 52 coefficients + EMA; from audio resident in HBM (rotating batches)",
+                   "windows_per_gpu": B, "samples_per_window": L, "parallelism": f"window-sharded x{rk.world}, no collective",
+                   },
+    }
+    if not args.full:
+        return line
     ms_cached = _timed_once(rk, step_cached, args.steps, args.warmup) / args.steps * 1e3      # ONE batch replayed (rounds 1-3)
 
     # ---- per-kernel timing, live: HIP events recorded by the library on the launch stream(s) around the kernels of
@@ -470,24 +516,11 @@ def run_c2(args, rk: Ranks):
     if rk.rank == 0 and rk.world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline_c2(args, params, audio_np, emo_np, eng, audio, emo)
 
-    line = {
-        "metric": METRIC, "value": round(value, 1), "unit": "frames/s", "n_gpus": rk.world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "rtf_30fps": round(30.0 / (value / rk.world), 8), "rccl_ranks": rk.rccl_ranks,
-        # K distinct audio batches used round-robin (together past the 256 MiB Infinity Cache): `value` / `ms_per_step` /
-        # kernel_ms / roofline are measured on them; ms_per_step_cached_input = the same step replaying ONE batch (what
-        # rounds 1-3 reported: its 139.7 MB stay on-die)
-        "input_rotation": {"buffers": len(bufs), "bytes_total": rot_bytes, "infinity_cache_bytes": INFINITY_CACHE_BYTES},
+    line.update({
         "ms_per_step_cached_input": round(ms_cached, 4),
-        "config": {"workload": "C2: 256 windows/GPU x 136448 samples (8.5 s @16 kHz) -> 1024-pt STFT, hop 533, "
-                               "80-bin log-mel (257 frames) -> dual-stream attention d_model=256, 8 heads, "
-                               "window 256 -> 52 coefficients + EMA; from audio resident in HBM (rotating batches)",
-                   "windows_per_gpu": B, "samples_per_window": L, "parallelism": f"window-sharded x{rk.world}, no collective",
-                   },
         "roofline": roofline, "roofline_other_kernel": other, "step_roofline": step_roof, "kernel_ms": stage_ms,
         "cpu_baseline": cpu, "experimental_split_bf16": split,
-    }
+    })
     if rk.world > 1:
         line["collective"] = measure_collective(args, rk)
     return line
@@ -789,17 +822,17 @@ def run_c3(args, rk: Ranks):
         for _ in range(3):
             tr.step(audio, emo, target)
         tr.capture(B, L)
-        dt = timed(rk, lambda: tr.step_graph(audio, emo, target), args.steps, args.warmup)
+        dt = timed(rk, lambda: tr.step_graph(audio, emo, target), args.steps, args.warmup, no_spinup=args.full)
     else:
-        dt = timed(rk, lambda: tr.step(audio, emo, target), args.steps, args.warmup)
+        dt = timed(rk, lambda: tr.step(audio, emo, target), args.steps, args.warmup, no_spinup=args.full)
     ms = dt / args.steps * 1e3
     value = B * rk.world * args.steps / dt
     tf = TRAIN_FLOPS_PER_WINDOW * B / (ms * 1e-3) / 1e12
     final_loss = float(tr.loss.item())
     cpu = None
-    if rk.rank == 0 and rk.world == 1 and args.cpu_seconds > 0:
+    if args.full and rk.rank == 0 and rk.world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline_c3(args, params, audio_np, emo_np, target_np, kw.get("dropout", 0.0))
-    return {
+    line = {
         "metric": "training windows/sec (train_sequential step, window 256, d_model=256)", "value": round(value, 1),
         "unit": "windows/s", "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -812,8 +845,11 @@ def run_c3(args, rk: Ranks):
                                "tile loop: DESIGN 3.6, profiles/r04_train_trace_*.txt)", "bound": "mfma", "achieved": round(tf, 3),
                      "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / PEAK_F32_MFMA_TFLOPS, 5), "traffic": None,
                      "flops_per_window": TRAIN_FLOPS_PER_WINDOW},
-        "cpu_baseline": cpu, "final_loss": final_loss,
+        "final_loss": final_loss,
     }
+    if args.full:
+        line["cpu_baseline"] = cpu
+    return line
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -843,10 +879,17 @@ def run_c4(args, rk: Ranks):
         it[0] += 1
         eng.forward_audio(a, emo, out=out)
 
-    dt = timed(rk, step, args.steps, args.warmup)
-    ms_cached = _timed_once(rk, lambda: eng.forward_audio(audio, emo, out=out), args.steps, args.warmup) / args.steps * 1e3
+    def restart():          # the last timed step's batch depends on W and K only
+        it[0] = 0
+
+    dt = timed(rk, step, args.steps, args.warmup, restart=restart, no_spinup=args.full)
+    if args.dump_outputs:
+        rk.outputs = {"blendshapes": out.cpu().numpy()}
+    ms_cached = None
+    if args.full:
+        ms_cached = _timed_once(rk, lambda: eng.forward_audio(audio, emo, out=out), args.steps, args.warmup) / args.steps * 1e3
     cpu = None
-    if rk.rank == 0 and rk.world == 1 and args.cpu_seconds > 0:
+    if args.full and rk.rank == 0 and rk.world == 1 and args.cpu_seconds > 0:
         import numpy as np
         cpu, ref = cpu_baseline_c4(args, params, audio_np, emo_np, H)
         got = eng.forward_audio(audio[:ref.shape[0]], emo[:ref.shape[0]]).cpu().numpy()
@@ -855,13 +898,12 @@ def run_c4(args, rk: Ranks):
     value = B * rk.world * args.steps / dt
     exe = executed_flops_per_frame_c4(H) * B / (ms * 1e-3) / 1e12
     alg = ALGORITHMIC_FLOPS_PER_FRAME_C4 * B / (ms * 1e-3) / 1e12
-    return {
+    line = {
         "metric": "blendshape frames/sec (52-coef, 512-win, d_model=512, 60 fps)", "value": round(value, 1), "unit": "frames/s",
         "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "rtf_60fps": round(60.0 / (value / rk.world), 8),
         "rccl_ranks": rk.rccl_ranks,
         "input_rotation": {"buffers": len(bufs), "bytes_total": rot_bytes, "infinity_cache_bytes": INFINITY_CACHE_BYTES},
-        "ms_per_step_cached_input": round(ms_cached, 4),
         "config": {"workload": f"C4: {B} windows/GPU x {L} samples, hop 266, 513 frames -> dual-stream attention d_model=512, "
                                f"{H} heads, window 512 -> 52 coefficients; from audio resident in HBM (rotating batches)", "windows_per_gpu": B,
                    "parallelism": f"window-sharded x{rk.world}, no collective"},
@@ -871,8 +913,11 @@ def run_c4(args, rk: Ranks):
                      "traffic": None, "executed_flops_per_window": executed_flops_per_frame_c4(H),
                      "note": "MFMA FLOPs the three core stages issue (bench.py header; one launch, core512_kernel, since round 4) over the WHOLE step incl. the VALU "
                              "front end; per stage as separate kernels (KM_BENCH_OPTIONS=no_core_merge=1): profiles/r04_c4_kernel_stats.txt, r02_c4_harness.txt"},
-        "cpu_baseline": cpu,
     }
+    if args.full:
+        line["ms_per_step_cached_input"] = round(ms_cached, 4)
+        line["cpu_baseline"] = cpu
+    return line
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -908,14 +953,14 @@ def run_c5(args, rk: Ranks):
         torch.cuda.synchronize(rk.dev)
         lat.append(time.perf_counter() - t0)
 
-    dt = timed(rk, tick, args.steps, args.warmup)
+    dt = timed(rk, tick, args.steps, args.warmup, no_spinup=args.full)
     cpu = None
-    if rk.rank == 0 and rk.world == 1 and args.cpu_seconds > 0:
+    if args.full and rk.rank == 0 and rk.world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline_c5(args, synth.make_core_params(0), frames.cpu().numpy(), emo.cpu().numpy())
     lat_ms = np.array(lat[args.warmup:]) * 1e3
     ms = dt / args.steps * 1e3
     value = S * rk.world * args.steps / dt
-    return {
+    line = {
         "metric": "streaming blendshape frames/sec (per-tick decode, 52-coef, 256-win, d_model=256)", "value": round(value, 1),
         "unit": "frames/s", "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -929,8 +974,10 @@ def run_c5(args, rk: Ranks):
                      "achieved": round(EXECUTED_MFMA_FLOPS_PER_FRAME * S / (ms * 1e-3) / 1e12, 3), "peak": PEAK_F32_MFMA_TFLOPS,
                      "unit": "TFLOP/s", "frac": round(EXECUTED_MFMA_FLOPS_PER_FRAME * S / (ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
                      "traffic": None},
-        "cpu_baseline": cpu,
     }
+    if args.full:
+        line["cpu_baseline"] = cpu
+    return line
 
 
 def run_rendezvous(args, rk: Ranks):
@@ -940,7 +987,23 @@ def run_rendezvous(args, rk: Ranks):
             "n_gpus": rk.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "none", "data": "synthetic",
             "rccl_ranks": rk.rccl_ranks, "config": {"workload": "rendezvous"}, "roofline": None, "cpu_baseline": None,
-            "collective": measure_collective(args, rk, steps=3) if rk.world > 1 else None}
+            "collective": measure_collective(args, rk, steps=3) if args.full and rk.world > 1 else None}
+
+
+def dump_outputs(path: str, arrays: dict, rank: int) -> list:
+    """--dump-outputs: the arrays of the last timed step as float32 <path>/<name>.npy (<name>.rank<r>.npy on rank r > 0)."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    names = []
+    for k, v in arrays.items():
+        name = k if rank == 0 else f"{k}.rank{rank}"
+        np.save(os.path.join(path, name + ".npy"), v)
+        names.append(name)
+    return names
 
 
 def main():
@@ -959,7 +1022,11 @@ def main():
     if args.workload != "rendezvous":      # disclosed: untimed sustained load ahead of the W warmup steps (see SPINUP_SECONDS)
         line["spinup_s"] = 0.0 if os.environ.get("KM_BENCH_NO_SPINUP") else SPINUP_SECONDS
         # the same K steps behind the W warmup steps alone (the command line's literal protocol, on the clock ramp)
-        line["ms_per_step_no_spinup"] = None if getattr(rk, "no_spinup_ms", None) is None else round(rk.no_spinup_ms, 4)
+        if args.full:
+            line["ms_per_step_no_spinup"] = None if getattr(rk, "no_spinup_ms", None) is None else round(rk.no_spinup_ms, 4)
+    line["full"] = args.full
+    if args.dump_outputs:
+        line["dumped_outputs"] = dump_outputs(args.dump_outputs, rk.outputs, rk.rank)
     if rk.rank == 0:
         print(json.dumps(line), flush=True)
     rk.finish()

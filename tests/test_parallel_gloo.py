@@ -95,7 +95,7 @@ def test_bench_starts_its_own_ranks(n):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--workload", "rendezvous", "--steps", "4",
-                          "--warmup", "1"], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+                          "--warmup", "1", "--full"], cwd=root, env=env, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
