@@ -35,8 +35,8 @@ __device__ __forceinline__ float db_finish(const LogParams& p, float dbs, float 
     v = clamp_lo(v, floor_db);
     return (v + p.db_add) * p.db_scale;
 }
-// The same in two instructions, for top_db == db_add (the floor then maps to exactly 0): max(t, -A) + A == max(t + A, 0) and the
-// positive scale commutes with the max, so x = max(dbs * scale + (A - ref_db) * scale, 0) -- one fma + one max per value, within
+// The same in two instructions, for top_db == db_add and db_scale > 0 ONLY (mel_packs checks both): max(t, -A) + A == max(t + A, 0)
+// and a positive scale commutes with the max (a negative one would make it a min), so x = max(dbs * scale + (A - ref_db) * scale, 0) -- one fma + one max per value, within
 // an ulp or two of db_finish (the front end's own log is good to 3e-7 of the feature range).  c1 = db_fast_c1().
 __device__ __forceinline__ float db_fast_c1(const LogParams& p, float ref_db) { return (p.db_add - ref_db) * p.db_scale; }
 __device__ __forceinline__ float db_finish_fast(float dbs, float scale, float c1) { return fmaxf(fmaf(dbs, scale, c1), 0.f); }

@@ -1228,11 +1228,13 @@ bool mel_fuses_emotion(Context* c, MelPlan* p) {
 }
 
 // true when launch_mel_power can write the training step's packed input itself (MelPack): the 1024-point kernel with a grouped
-// filter image, librosa's dB conversion with top_db == db_add (the floor maps to exactly 0), and at least T frames (every slot
-// of a row is then written by the launch: short clips take the conversion operation of phase 0)
+// filter image, librosa's dB conversion with top_db == db_add and db_scale > 0 (the floor then maps to exactly 0 and the scale
+// commutes with the max: db_finish_fast; under a negative scale the floor becomes a ceiling, min(x scale, 0)), and at
+// least T frames (every slot of a row is then written by the launch: short clips take the conversion operation of phase 0)
 bool mel_packs(Context* c, MelPlan* p, int64_t n_frames, int64_t T) {
     const km_mel_config& m = p->cfg;
     return m.n_fft == 1024 && !c->opt.mel_two_frame && p->d_fbg_gid != nullptr && m.log_mode == KM_LOG_DB_MAX && m.top_db == m.db_add &&
+           m.db_scale > 0.f &&
            n_frames >= T && n_frames >= 3;
 }
 

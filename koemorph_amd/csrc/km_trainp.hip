@@ -979,8 +979,22 @@ int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64
     // prologue per tile, which the launch it saves outweighs up to ~40 windows (8 windows 0.1288-0.1301 -> 0.125 ms, 24: 0.1647 ->
     // 0.1606, 32: 0.1717 -> 0.1683, 48: 0.2079 -> 0.2105, 64: 0.229 -> 0.238: there the K / V product is bound by the matrix pipe and the
     // LayerNorm phase is cheap beside it)
+    // The products it rides on are the producers of Y0 / E0 (they leave the statistic parts) and their readers (K | V, the emotion
+    // value projection); Program::gemm refuses LayerNorm on a product that misses the LDS-DMA tile with k-contiguous operands, so
+    // each is checked here first: E0's operand is the CALLER's emotion pointer, and one that is not 16-byte aligned (a view at an
+    // odd float offset) rules the tile out -- the step then keeps the LayerNorm phase instead of failing.
+    GemmArgs gY0 = NT(X, KP, WceP, KP, Y0, d, NKk, d, P("mel_channel_encoder.bias"), 0);
+    gY0.a_bs1 = KP * NKk; gY0.c_bs1 = NKk * d;
+    const GemmArgs gE0 = NT(emo, ED, P("emotion_encoder.weight"), ED, E0, d, B, d, P("emotion_encoder.bias"), 0);
+    auto dma_nt = [](const GemmArgs& g) { int ma = -1, mb = -1; return gemm_dma_ok(g, &ma, &mb) && ma == 0 && mb == 0; };
+    auto ln_ok = [&](const GemmArgs& g) { return dma_nt(g) && g.N % 32 == 0; };
+    // the operand transform has no fallback (the front end has already written 10 log10(power)): its operand is the aligned workspace
+    if (xf && !dma_nt(gY0))
+        return fail(KM_ERR_UNSUPPORTED, "training program: the front end packed the encoder input, but the channel encoder product misses the LDS-DMA tile");
     const int ln_fuse_rows = c->opt.train_ln_fuse_rows > 0 ? c->opt.train_ln_fuse_rows : 3200;
-    const bool fuse_ln = pg.use_dma && !c->opt.train_no_ln_fuse && d % 32 == 0 && ED % 32 == 0 && R <= ln_fuse_rows;
+    const bool fuse_ln = pg.use_dma && !c->opt.train_no_ln_fuse && d % 32 == 0 && ED % 32 == 0 && R <= ln_fuse_rows &&
+                         ln_ok(gY0) && ln_ok(gE0) && ln_ok(NT(Y0, d, inw + d * d, d, KV, 2 * d, R, 2 * d, inb + d, 0)) &&
+                         ln_ok(NT(E0, d, einw + 2 * d * d, d, Ve, d, B, d, einb + 2 * d, 0));
     if (fuse_ln) {
         pg.ln[0] = LnXform{statsY, P("mel_norm.weight"), P("mel_norm.bias"), (int)(d / 32), 1e-5f};
         pg.ln[1] = LnXform{statsE, P("emotion_norm.weight"), P("emotion_norm.bias"), (int)(d / 32), 1e-5f};
@@ -998,16 +1012,14 @@ int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64
     {   // Y0[b] (NK x d) = XT_b (NK x KP) WceP^T + b: both operands k-contiguous with K = KP a multiple of 32 (zeros beyond KT on
         // both sides): the LDS-DMA tile.  Round 3 read X (B, KP, NK) as a row-contiguous operand against Wce's rows of 259
         // floats on the register tile (scalar loads): 12 us of the 8-window step
-        GemmArgs g = NT(X, KP, WceP, KP, Y0, d, NKk, d, P("mel_channel_encoder.bias"), 0);
-        g.a_bs1 = KP * NKk; g.c_bs1 = NKk * d;
-        pg.gemm(g, (int)B, xf, fuse_ln ? 1 : 0);       // xf: X holds 10 log10(power), finished on the fragments; fuse_ln: LayerNorm parts of Y0's rows
+        pg.gemm(gY0, (int)B, xf, fuse_ln ? 1 : 0);     // xf: X holds 10 log10(power), finished on the fragments; fuse_ln: LayerNorm parts of Y0's rows
     }
     pg.gemm(NT(P("mouth_queries"), d, inw, d, Qb, d, 28, d, inb, 0), 1);                                  // Q = mq Wq^T + bq
     pg.gemm(NN(Wmo, d, Wo, d, T1m, d, d, d, d), 1);                                                        // T1 = Wmo Wo
     pg.gemm(NN(Weo, d, Woe, d, T1e, d, d, d, d), 1);
     { GemmArgs g = G(Wmo, d, 1, bo, 1, 0, t1m, 1, d, 1, d); g.bias = bmo; g.bias_mode = 2; pg.gemm(g, 1); }   // t1 = Wmo bo + bmo
     { GemmArgs g = G(Weo, d, 1, boe, 1, 0, t1e, 1, d, 1, d); g.bias = beo; g.bias_mode = 2; pg.gemm(g, 1); }
-    pg.gemm(NT(emo, ED, P("emotion_encoder.weight"), ED, E0, d, B, d, P("emotion_encoder.bias"), 0), 1, false, fuse_ln ? 2 : 0);
+    pg.gemm(gE0, 1, false, fuse_ln ? 2 : 0);
     RUN(pg.end_phase(st));
     // The folds Wf = W1 T1 (operands of P5) and the finished features x2 (operand of P12): with fuse_ln they ride in P3
     auto folds = [&]() {

@@ -158,18 +158,26 @@ def power_to_db(S: np.ndarray, ref_max: bool = True, amin: float = 1e-10,
 # ---------------------------------------------------------------------------
 def mel_batch_window(y: np.ndarray, sample_rate: int = 16000, n_fft: int = 1024,
                      hop: int = 533, n_mels: int = 80, fmin: float = 80.0, fmax: float = 8000.0,
-                     precision: str = "ref") -> Tuple[np.ndarray, np.ndarray]:
+                     precision: str = "ref", top_db: float = 80.0, db_add: float = 80.0,
+                     db_scale: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray]:
     """One window: librosa.feature.melspectrogram (defaults: hann, center, pad_mode
     'constant', power 2, slaney) :188-196 -> power_to_db(ref=np.max) :199 -> (x+80)/80 :200
-    -> transpose :202 -> (long (T_mel,80), short = last 3 frames (3,80)) :206-214."""
+    -> transpose :202 -> (long (T_mel,80), short = last 3 frames (3,80)) :206-214.
+
+    ``top_db`` / ``db_add`` / ``db_scale``: the dB constants of km_mel_config,
+    (max(db, max - top_db) + db_add) * db_scale.  ``db_scale=None`` divides by 80 as the
+    reference does (:200) -- the defaults reproduce (x+80)/80 bit for bit."""
     fb = mel_filterbank_librosa(sample_rate, n_fft, n_mels, fmin, fmax)
     P = stft_power(y, n_fft, hop, center=True, pad_mode="constant", precision=precision)
     if precision == "ref":
         mel = (P.astype(np.float32) @ fb.T.astype(np.float32)).astype(np.float32)   # (T,80)
     else:
         mel = P @ fb.T.astype(np.float64)
-    db = power_to_db(mel)
-    db = (db + db.dtype.type(80)) / db.dtype.type(80)
+    db = power_to_db(mel, top_db=top_db)
+    if db_scale is None:
+        db = (db + db.dtype.type(db_add)) / db.dtype.type(80)
+    else:
+        db = (db + db.dtype.type(db_add)) * db.dtype.type(db_scale)
     long = db
     if long.shape[0] >= 3:
         short = long[-3:]

@@ -161,17 +161,22 @@ def test_training_loop_matches_torch_adamw_with_ema_and_l1():
 
 
 def test_train_step_from_audio_and_schedule():
-    """BASELINE config 3 shape on one rank: 8 windows of 136448 samples, window 256, d_model 256."""
+    """BASELINE config 3 shape on one rank: 8 windows of 136448 samples, window 256, d_model 256.  The first step's loss (the EMA
+    starts there, so the output is the forward's) against the float64 oracle fed by the numpy front end (oracle.mel): 1e-4
+    relative."""
+    from oracle import mel as omel
     params = synth.make_core_params(72, style="init")
     e = Engine()
     e.load_state_dict(params)
     e.finalize()
     tr = Trainer(e, max_windows=8)
-    audio = dev(synth.make_audio(73, 8, 136448))
-    emo = dev(synth.normal(74, (8, 256)))
-    target = dev(synth.uniform(75, (8, 52), 0, 1))
+    audio_np, emo_np, target_np = synth.make_audio(73, 8, 136448), synth.normal(74, (8, 256)), synth.uniform(75, (8, 52), 0, 1)
+    audio, emo, target = dev(audio_np), dev(emo_np), dev(target_np)
     losses = [float(tr.step(audio, emo, target).item()) for _ in range(6)]
     assert all(np.isfinite(losses)) and losses[-1] < losses[0]           # it learns the (fixed) batch
+    long, short = omel.mel_batch(audio_np)
+    want = core.core_loss_and_grads(params, long, short, emo_np, target_np, dtype=torch.float64)[0]
+    assert abs(losses[0] - want) <= 1e-4 * abs(want), (losses[0], want)
     assert tr.n_params >= 837738 and tr.step_count == 6
     # CosineAnnealingWarmRestarts(T_0=10, T_mult=2, eta_min=1e-6) against torch
     p = torch.nn.Parameter(torch.zeros(1))

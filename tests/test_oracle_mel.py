@@ -68,3 +68,32 @@ def test_ref_precision_close_to_f64():
     a, _ = mel.mel_batch_window(y, precision="ref")
     b, _ = mel.mel_batch_window(y, precision="f64")
     assert np.max(np.abs(a - b)) < 5e-5
+
+
+def test_batch_window_db_constants():
+    """mel_batch_window's top_db / db_add / db_scale (km_mel_config's dB constants): the defaults are today's (db + 80) / 80 bit for
+    bit, and other values follow (max(db, max - top_db) + db_add) * db_scale -- the oracle of the training tests' MelConfig cases."""
+    y = synth.make_audio(11, 1, 136448)[0]
+    y[60000:] *= 1e-3                                                      # a quiet half: more than 80 dB below the loud frames
+    fb = mel.mel_filterbank_librosa(16000, 1024, 80, 80.0, 8000.0)
+    P = mel.stft_power(y, 1024, 533, center=True, pad_mode="constant")
+    m = (P.astype(np.float32) @ fb.T.astype(np.float32)).astype(np.float32)
+    raw = mel.power_to_db(m, top_db=None)                                  # 10 log10(S / max S), no clamp
+    base = (mel.power_to_db(m) + np.float32(80)) / np.float32(80)
+    for kw in ({}, dict(top_db=80.0, db_add=80.0)):
+        long, short = mel.mel_batch_window(y, **kw)
+        assert long.dtype == np.float32 and np.array_equal(long, base) and np.array_equal(short, base[-3:])
+    assert raw.min() < -80.0                                               # the clamps below are exercised
+    for top_db, db_add, db_scale in ((60.0, 80.0, 1.0 / 80.0), (80.0, 80.0, -1.0 / 80.0), (60.0, 80.0, -1.0 / 80.0), (50.0, 0.0, 1.0)):
+        long, short = mel.mel_batch_window(y, top_db=top_db, db_add=db_add, db_scale=db_scale)
+        want = (np.maximum(raw.astype(np.float64), -top_db) + db_add) * db_scale
+        np.testing.assert_allclose(long, want, rtol=1e-6, atol=1e-6 * abs(db_add * db_scale) + 1e-7)
+        assert np.array_equal(short, long[-3:])
+        lim = (db_add - top_db) * db_scale                                 # the clamped value: a floor for db_scale > 0, a ceiling below
+        assert (long.min() if db_scale > 0 else long.max()) == pytest.approx(lim, abs=1e-6)
+    # a short clip: fewer than 3 frames, the short rows are zero-filled after the frames there are (as with the defaults)
+    long, short = mel.mel_batch_window(y[:533], top_db=60.0, db_scale=-1.0 / 80.0)
+    assert long.shape == (2, 80) and np.array_equal(short[:2], long) and not short[2].any()
+    # mel_batch passes them on
+    lb, sb = mel.mel_batch(synth.make_audio(12, 2, 20000), top_db=60.0)
+    assert lb.min() == pytest.approx(0.25, abs=1e-6) and sb.shape == (2, 3, 80)
