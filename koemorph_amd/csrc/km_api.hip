@@ -15,7 +15,10 @@ using namespace km;
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) {                                                                                                        \
+            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
+            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
+        }                                                                                                                              \
     } while (0)
 
 static int free_streams(Context* c);

@@ -14,7 +14,10 @@ namespace km {
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) {                                                                                                        \
+            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
+            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
+        }                                                                                                                              \
     } while (0)
 
 // dst[t, k] = float32(np.interp(np.linspace(0, n_src - 1, n_dst)[t], np.arange(n_src), src[:, k]))

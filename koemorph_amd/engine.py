@@ -172,7 +172,11 @@ class Engine:
         torch = _torch()
         with torch.cuda.device(self.device):
             torch.cuda.synchronize(self.device)        # the old workspace may still be in use
-            check(self._lib.km_reserve(self._h, max_windows, max_samples))
+            try:
+                check(self._lib.km_reserve(self._h, max_windows, max_samples))
+            except KoeMorphError:
+                self._reserved = (0, 0)                # a failed regrow leaves the handle without a workspace
+                raise
         self._reserved = (max(max_windows, self._reserved[0]), max(max_samples, self._reserved[1]))
 
     # ---- forward path -----------------------------------------------------------------------

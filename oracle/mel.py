@@ -18,7 +18,10 @@ algorithms of ``librosa.feature.melspectrogram`` / ``librosa.power_to_db`` /
 Precision model: librosa multiplies the float32 frames by a float64 window, so the rFFT
 runs in float64 and is then stored as complex64; |.|^2, the mel product and the dB
 conversion run in float32.  ``precision="ref"`` mirrors that; ``precision="f64"`` keeps
-everything in float64 (used to bound rounding noise).
+everything in float64 (used to bound rounding noise); ``precision="f32"`` is a plain float32
+pipeline (float32 window, numpy's float32 rFFT, float32 power and filter product): not a
+restatement of anything in the reference, but the yardstick that says how far an honest
+float32 implementation is from the float64 truth (``mel_power`` / ``mel_power_error``).
 """
 
 from __future__ import annotations
@@ -129,6 +132,14 @@ def stft_power(y: np.ndarray, n_fft: int, hop: int, win_length: Optional[int] = 
         y = np.pad(y, n_fft // 2, mode=mode)
     n_frames = 1 + (len(y) - n_fft) // hop
     idx = np.arange(n_fft)[None, :] + hop * np.arange(n_frames)[:, None]
+    if precision == "f32":                              # the plain float32 pipeline (not librosa's)
+        frames = y[idx].astype(np.float32) * w.astype(np.float32)[None, :]
+        spec = np.fft.rfft(frames, axis=1)
+        assert spec.dtype == np.complex64, f"numpy's rfft of float32 input gave {spec.dtype}, not complex64"
+        if window_norm:
+            spec = spec / np.float32(np.sqrt(np.sum(w * w)))
+        assert spec.dtype == np.complex64
+        return spec.real * spec.real + spec.imag * spec.imag
     frames = y[idx].astype(np.float64) * w[None, :]     # float32 frame x float64 window
     spec = np.fft.rfft(frames, axis=1)
     if window_norm:
@@ -151,6 +162,63 @@ def power_to_db(S: np.ndarray, ref_max: bool = True, amin: float = 1e-10,
     if top_db is not None:
         log_spec = np.maximum(log_spec, log_spec.max() - S.dtype.type(top_db))
     return log_spec
+
+
+# ---------------------------------------------------------------------------
+# linear mel power for any km_mel_config, and the error measure of the linear-power tests
+# ---------------------------------------------------------------------------
+def mel_power(y: np.ndarray, sample_rate: int = 16000, n_fft: int = 1024, hop: int = 533, n_mels: int = 80,
+              f_min: float = 80.0, f_max: Optional[float] = 8000.0, mel_scale: str = "slaney",
+              slaney_norm: bool = True, pad_mode: str = "constant", window_norm: bool = False,
+              precision: str = "f64", fb: Optional[np.ndarray] = None, return_aux: bool = False):
+    """Linear mel power (n_frames, n_mels) of one clip: centred STFT (periodic Hann of n_fft points), |.|^2,
+    triangular filters of librosa.filters.mel (``mel_scale`` "slaney" / "htk", ``slaney_norm``) -- every
+    configuration km_mel_config expresses, before any logarithm.
+
+    precision "f64": everything in float64 (the truth).  "ref": librosa's chain (float64 rFFT rounded to complex64,
+    float32 power and product) -- power_to_db of it IS mel_batch_window / mel_sliding_window / mel_torchaudio.
+    "f32": the plain float32 pipeline of stft_power(precision="f32") with a float32 product.
+
+    ``fb`` (n_mels, 1 + n_fft//2) replaces the filters (mel_torchaudio's come from mel_filterbank_torchaudio).
+    ``return_aux``: also return {"fb": the filters, "spec_peak": max_k |X64[t, k]|^2 per frame (float64)},
+    the two ingredients of mel_power_error's scale."""
+    if fb is None:
+        fb = mel_filterbank_librosa(sample_rate, n_fft, n_mels, f_min, f_max, htk=(mel_scale == "htk"),
+                                    norm="slaney" if slaney_norm else None)
+    P = stft_power(y, n_fft, hop, center=True, pad_mode=pad_mode, precision=precision, window_norm=window_norm)
+    mel = (P @ fb.T.astype(P.dtype)).astype(P.dtype)
+    if not return_aux:
+        return mel
+    P64 = P if precision == "f64" else stft_power(y, n_fft, hop, center=True, pad_mode=pad_mode, precision="f64",
+                                                  window_norm=window_norm)
+    return mel, {"fb": fb, "spec_peak": P64.max(axis=1)}
+
+
+MEL_POWER_U = 2.0 ** -23
+
+
+def mel_power_error(P: np.ndarray, P64: np.ndarray, spec_peak: np.ndarray, fb: np.ndarray) -> Tuple[np.ndarray, int]:
+    """Error of a mel power image P against the float64 one, per (frame t, filter m), in units in which an absolute
+    error of u |X|max on every spectrum bin is about u = 2^-23:
+
+        S = max_k |X64[t, k]|^2 * max_k fb[m, k]         (peak of the WHOLE spectrum of the frame, not of the mel row)
+        e[t, m] = |P - P64| / (sqrt(P64 S) + u S)
+
+    first- and second-order effect of such an error; the second term keeps e finite where the true power is zero.
+    Frames whose float64 spectrum is identically zero (spec_peak == 0) must come back as exactly zero power: their
+    e is 0 where P == 0 and inf elsewhere.  Returns (e, number of such frames)."""
+    P = np.asarray(P, np.float64)
+    P64 = np.asarray(P64, np.float64)
+    peak = np.asarray(spec_peak, np.float64)
+    assert P.shape == P64.shape and peak.shape == P.shape[:-1] and fb.shape[0] == P.shape[-1]
+    S = peak[..., None] * fb.max(axis=1).astype(np.float64)
+    den = np.sqrt(P64 * S) + MEL_POWER_U * S
+    dead = peak == 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = np.abs(P - P64) / den
+    # a filter without any weight (max fb == 0: narrower than a bin) has S == 0 and true power 0 in every frame
+    e = np.where(den == 0.0, np.where(P == 0.0, 0.0, np.inf), e)
+    return e, int(np.count_nonzero(dead))
 
 
 # ---------------------------------------------------------------------------
