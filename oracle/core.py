@@ -62,14 +62,15 @@ def core_forward(params: Dict[str, "np.ndarray | torch.Tensor"],
                  num_heads: int = 8, mel_sequence_length: int = 256,
                  temperature: float = 1.0, return_attention: bool = False,
                  dtype=torch.float32, return_intermediates: bool = False,
-                 dropout_p: float = 0.0, drop_masks: Optional[Dict[str, "np.ndarray | torch.Tensor"]] = None
-                 ) -> Dict[str, torch.Tensor]:
+                 dropout_p: float = 0.0, drop_masks: Optional[Dict[str, "np.ndarray | torch.Tensor"]] = None,
+                 ln_eps: float = 1e-5) -> Dict[str, torch.Tensor]:
     """DualStreamCrossAttention.forward (dual_stream_attention.py:162-280).
 
     Training mode: the module holds three dropouts (p = ``dropout``, :106, :115, :153) -- on the attention weights of
     both nn.MultiheadAttention modules (after the softmax, before P V) and on the decoder's hidden layer (after the
     ReLU).  ``drop_masks`` = {"mel": (B,H,28,80), "emo": (B,H,24,1), "dec": (B,52,d/2)} of 0/1 keep flags makes them
-    explicit; kept values are scaled by 1/(1-p) as torch.nn.functional.dropout does."""
+    explicit; kept values are scaled by 1/(1-p) as torch.nn.functional.dropout does.
+    ``ln_eps`` is the epsilon of both LayerNorms (the reference's is 1e-5; the tests plant another value as a fault)."""
     P = {k: _t(v, dtype) for k, v in params.items()}
     mel = _t(mel_features, dtype)
     short = _t(mel_temporal_features, dtype)
@@ -88,10 +89,10 @@ def core_forward(params: Dict[str, "np.ndarray | torch.Tensor"],
     x = torch.cat([x, short.transpose(1, 2)], dim=2)
     # :211-212  per-channel encoder + LayerNorm(eps=1e-5)
     y = F.linear(x, P["mel_channel_encoder.weight"], P["mel_channel_encoder.bias"])
-    y = F.layer_norm(y, (d,), P["mel_norm.weight"], P["mel_norm.bias"], 1e-5)
+    y = F.layer_norm(y, (d,), P["mel_norm.weight"], P["mel_norm.bias"], ln_eps)
     # :216-218  emotion vector -> one token
     e = F.linear(emo, P["emotion_encoder.weight"], P["emotion_encoder.bias"]).unsqueeze(1)
-    e = F.layer_norm(e, (d,), P["emotion_norm.weight"], P["emotion_norm.bias"], 1e-5)
+    e = F.layer_norm(e, (d,), P["emotion_norm.weight"], P["emotion_norm.bias"], ln_eps)
     # :221-222
     qm = P["mouth_queries"].unsqueeze(0).expand(B, -1, -1)
     qe = P["expression_queries"].unsqueeze(0).expand(B, -1, -1)
@@ -144,6 +145,104 @@ def core_forward_np(params, mel, short, emo, **kw) -> Dict[str, np.ndarray]:
     with torch.no_grad():
         o = core_forward(params, mel, short, emo, **kw)
     return {k: v.detach().cpu().numpy() for k, v in o.items()}
+
+
+# ---- the logit-space measure (tests/test_gpu_core_logit.py, tests/test_oracle_core.py) ---------------------------------------
+# blendshapes = clamp(c_i * sigmoid(z)), c_i = (softmax(mel_weights)_i + softmax(emotion_weights)_i) / 2 ~ 1/52, and the sigmoid's
+# slope is at most 1/4: an error in the decoder logit z reaches the output ~200 times smaller.  The measure undoes both factors.
+LOGIT_U = 2.0 ** -24                 # half an ulp of a float32 in [1, 2): the relative error of storing a value in float32
+LOGIT_FLOOR = 2.0 ** -23             # the yardstick is never taken smaller than one float32 ulp at 1.0
+LOGIT_Z_MAX = 8.0                    # the cases keep |z| below this, so that 1 / (s (1 - s)) stays below ~3000
+
+
+def stream_coefficients(params, temperature: float = 1.0) -> np.ndarray:
+    """c_i of the output's last line, float64 (52,).  c_i <= 1/2 (two softmax entries halved), so the clamp never binds."""
+    wm = torch.softmax(_t(params["mel_weights"], torch.float64) / temperature, dim=0)
+    we = torch.softmax(_t(params["emotion_weights"], torch.float64) / temperature, dim=0)
+    return (0.5 * (wm + we)).numpy()
+
+
+def recover_sigmoid(blendshapes, params, temperature: float = 1.0) -> np.ndarray:
+    """s = blendshapes / c_i in float64: the sigmoid value of every coefficient from the float32 output."""
+    return np.asarray(blendshapes, dtype=np.float64) / stream_coefficients(params, temperature)
+
+
+def undo_ema(out, prev, smoothing_alpha: float = 0.8) -> np.ndarray:
+    """x of y = alpha x + (1 - alpha) prev in float64, alpha = sigmoid(smoothing_alpha): the unsmoothed output of a call whose
+    smoothed result is ``out`` and whose state before the call was ``prev`` (both read back from the device)."""
+    alpha = 1.0 / (1.0 + math.exp(-float(smoothing_alpha)))
+    return (np.asarray(out, dtype=np.float64) - (1.0 - alpha) * np.asarray(prev, dtype=np.float64)) / alpha
+
+
+def logit_error(s, s64) -> np.ndarray:
+    """First-order error of the logit behind a sigmoid value: |s - s64| / (s64 (1 - s64)), entry by entry.  NaN stays NaN."""
+    s, s64 = np.asarray(s, dtype=np.float64), np.asarray(s64, dtype=np.float64)
+    return np.abs(s - s64) / (s64 * (1.0 - s64))
+
+
+def logit_storage_term(s64) -> np.ndarray:
+    """What storing s (or c_i s) in float32 adds to logit_error at most: s 2^-24 / (s (1 - s)) = 2^-24 / (1 - s64)."""
+    return LOGIT_U / (1.0 - np.asarray(s64, dtype=np.float64))
+
+
+def attention_error(a, a64) -> np.ndarray:
+    """|a - a64| / max_k a64 per (window, query) row of the head-averaged attention map (B, Lq, Lk)."""
+    a, a64 = np.asarray(a, dtype=np.float64), np.asarray(a64, dtype=np.float64)
+    return np.abs(a - a64) / a64.max(axis=-1, keepdims=True)
+
+
+def logit_reference(params, mel, short, emo, num_heads: int = 8, mel_sequence_length: int = 256,
+                    temperature: float = 1.0) -> Dict[str, np.ndarray]:
+    """The float64 oracle of one case and the yardstick: the same measure applied to the float32 oracle on the same parameters
+    and inputs.  Keys: s64 (B,52) sigmoid values, z64 (B,52) logits (the 24 expression columns hold the emotion-stream logit),
+    a64 (B,28,80), s32 / a32 the float32 oracle's, yard_e / yard_a = max logit_error / attention_error of the float32 oracle."""
+    kw = dict(num_heads=num_heads, mel_sequence_length=mel_sequence_length, temperature=temperature, return_attention=True,
+              return_intermediates=True)
+    with torch.no_grad():
+        r64 = core_forward(params, mel, short, emo, dtype=torch.float64, **kw)
+        r32 = core_forward(params, mel, short, emo, dtype=torch.float32, **kw)
+    ref = {"s64": r64["_bs"].numpy(), "z64": r64["_z"].numpy(), "a64": r64["mel_attention_weights"].numpy(),
+           "out64": r64["blendshapes"].numpy(), "s32": r32["_bs"].numpy(), "out32": r32["blendshapes"].numpy(),
+           "a32": r32["mel_attention_weights"].numpy()}
+    ref["yard_e"] = float(logit_error(ref["s32"], ref["s64"]).max())
+    ref["yard_a"] = float(attention_error(ref["a32"], ref["a64"]).max())
+    return ref
+
+
+def logit_bound(ref, K: float, roundings: int = 1, extra=None) -> np.ndarray:
+    """Per-entry bound on logit_error: K x max(yardstick, floor) + `roundings` storage terms of that entry (+ `extra`, a derived
+    per-entry term of the caller's).  roundings = 1 for a sigmoid value stored in float32 (`raw`); OUT_OVER_C_ROUNDINGS = 3 for
+    s recovered as out / c_i, because out = fl(c32 * s32) carries the rounding of s, the float32 representation of c_i and the
+    rounding of the product, each of relative size 2^-24 and each worth 2^-24 / (1 - s64) in the measure."""
+    b = K * max(ref["yard_e"], LOGIT_FLOOR) + roundings * logit_storage_term(ref["s64"])
+    return b if extra is None else b + extra
+
+
+OUT_OVER_C_ROUNDINGS = 3
+
+
+def attention_bound(ref, K: float) -> float:
+    """Bound on attention_error: K x max(yardstick, floor) + 2^-24 (float32 storage of an entry no larger than the row's maximum)."""
+    return K * max(ref["yard_a"], LOGIT_FLOOR) + LOGIT_U
+
+
+def logit_verdict(s, ref, K: float, roundings: int = 1, extra=None):
+    """(largest logit_error, largest error / bound) over EVERY entry; a NaN or infinity in ``s``, or another shape, gives (inf, inf)."""
+    if np.shape(s) != ref["s64"].shape:
+        return float("inf"), float("inf")
+    e = logit_error(s, ref["s64"])
+    if not np.isfinite(e).all():
+        return float("inf"), float("inf")
+    return float(e.max()), float((e / logit_bound(ref, K, roundings, extra)).max())
+
+
+def attention_verdict(a, ref, K: float):
+    if np.shape(a) != ref["a64"].shape:
+        return float("inf"), float("inf")
+    e = attention_error(a, ref["a64"])
+    if not np.isfinite(e).all():
+        return float("inf"), float("inf")
+    return float(e.max()), float(e.max() / attention_bound(ref, K))
 
 
 # perceptual groups and weights of PerceptualBlendshapeLoss (src/model/losses.py:306-330)

@@ -144,3 +144,92 @@ def test_dual_stream_loss_restatement_known_values():
     assert len(ocore.MOUTH_INDICES) == 28 and len(ocore.EXPRESSION_INDICES) == 24
     # without the attention maps the reference skips the separation term
     assert abs(float(ocore.dual_stream_loss(pred, target, velocity_weight=0.0, with_attention=False)) - base) < 1e-7
+
+
+# ---- the logit-space measure of oracle/core.py (tests/test_gpu_core_logit.py asserts it on the kernels) ------------------------
+def _standin(params, mel, short, emo, fault="none", H=8, T=256):
+    """A stand-in kernel: the float32 oracle with a planted fault.  (out (B,52), raw, attention map) as the C ABI returns them."""
+    import core_logit_cases as cc
+    p2, m2, s2, e2, kw = cc.apply_fault(fault, params, mel, short, emo, T)
+    with torch.no_grad():
+        r = core.core_forward(p2, m2, s2, e2, num_heads=H, mel_sequence_length=T, return_attention=True,
+                              return_intermediates=True, **kw)
+    return r["blendshapes"].numpy(), r["_bs"].numpy(), r["mel_attention_weights"].numpy()
+
+
+@pytest.mark.parametrize("pk", ["init", "trained", "sharp", "bias0", "offset"])
+def test_logit_measure_of_the_float64_oracle_against_itself_is_zero(pk):
+    import core_logit_cases as cc
+    params = cc.make_params(pk, 77)
+    mel, short, emo = cc.make_inputs("mel01", 937, 3, 257)
+    ref = core.logit_reference(params, mel, short, emo)
+    assert np.abs(ref["z64"]).max() <= core.LOGIT_Z_MAX
+    assert core.logit_error(ref["s64"], ref["s64"]).max() == 0.0 and core.attention_error(ref["a64"], ref["a64"]).max() == 0.0
+    assert core.logit_verdict(ref["s64"], ref, cc.K) == (0.0, 0.0)
+    # c_i <= 1/2, so the clamp never binds and out / c_i is the sigmoid value: in float64 to float64 rounding
+    c = core.stream_coefficients(params)
+    assert c.shape == (52,) and c.max() <= 0.5 and abs(c.sum() - 1.0) < 1e-12
+    assert np.abs(core.recover_sigmoid(ref["out64"], params) - ref["s64"]).max() < 1e-15
+    # a NaN anywhere, or a missing row, is the worst verdict and not a silently ignored entry
+    bad = ref["s64"].copy()
+    bad[1, 7] = np.nan
+    assert core.logit_verdict(bad, ref, cc.K)[1] == float("inf") and core.logit_verdict(ref["s64"][:2], ref, cc.K)[1] == float("inf")
+
+
+@pytest.mark.parametrize("pk", ["init", "trained"])
+def test_recovery_from_the_float32_output_agrees_with_raw_to_the_storage_term(pk):
+    import core_logit_cases as cc
+    params = cc.make_params(pk, 77)
+    mel, short, emo = cc.make_inputs("randn", 5, 4, 300)
+    ref = core.logit_reference(params, mel, short, emo)
+    out, raw, _ = _standin(params, mel, short, emo)
+    s = core.recover_sigmoid(out, params)
+    # out = fl(fl(fl(wm s) / 2) + fl(fl(we s) / 2)) with float32 softmax weights: a handful of roundings of relative size 2^-24
+    assert (np.abs(s - raw.astype(np.float64)) <= 6 * core.LOGIT_U * ref["s64"]).all()
+    assert (np.abs(core.logit_error(s, ref["s64"]) - core.logit_error(raw, ref["s64"])) <= 6 * core.logit_storage_term(ref["s64"])).all()
+    # undoing an EMA in float64 returns the unsmoothed value
+    alpha = 1.0 / (1.0 + np.exp(-0.8))
+    prev = ref["out64"][::-1]
+    assert np.abs(core.undo_ema(alpha * ref["out64"] + (1 - alpha) * prev, prev) - ref["out64"]).max() < 1e-15
+
+
+FAULT_CASES = [(f, pk, ik) for pk in ("init", "trained") for f, ik in (
+    ("short_reversed", "mel01"), ("last_long_row", "mel01"), ("ln_eps", "zeroch"), ("softmax_scale", "randn"),
+    ("value_column", "mel01" if pk == "init" else "randn"), ("emotion_last_column", "mel01"))] + [("one_query", "trained", "mel01"), ("one_query", "sharp", "mel01")]
+
+
+@pytest.mark.parametrize("fault,pk,ik", FAULT_CASES)
+def test_planted_faults_break_the_bound_on_a_stand_in_kernel(fault, pk, ik):
+    """The float32 oracle passes the bound of tests/test_gpu_core_logit.py; with each planted fault it does not (through the
+    logit error or the attention map), at `init` and at `trained` weights.  The one fault the measure cannot see at `init`
+    weights -- one mouth query x 1.001, 3.6e-8 in z -- is planted at `trained` and `sharp`."""
+    import core_logit_cases as cc
+    params = cc.make_params(pk, 77)
+    mel, short, emo = cc.make_inputs(ik, 937, 4, 257)
+    ref = core.logit_reference(params, mel, short, emo)
+    out, raw, attn = _standin(params, mel, short, emo)
+    assert core.logit_verdict(raw, ref, cc.K)[1] <= 1.0
+    assert core.logit_verdict(core.recover_sigmoid(out, params), ref, cc.K, core.OUT_OVER_C_ROUNDINGS)[1] <= 1.0
+    assert core.attention_verdict(attn, ref, cc.K)[1] <= 1.0
+    out, raw, attn = _standin(params, mel, short, emo, fault)
+    worst = max(core.logit_verdict(core.recover_sigmoid(out, params), ref, cc.K, core.OUT_OVER_C_ROUNDINGS)[1],
+                core.logit_verdict(raw, ref, cc.K)[1], core.attention_verdict(attn, ref, cc.K)[1])
+    print(f"fault {fault} {pk} {ik}: {worst:.2f} x the bound")
+    assert worst > 1.0, worst
+
+
+@pytest.mark.parametrize("name", CORE_CASES_D256 + CORE_CASES_OTHER)
+def test_goldens_are_within_the_storage_term_of_the_float32_oracle_in_logit_space(name):
+    """The committed `blendshapes` (the reference module's float32 output) against the float32 oracle, so far compared at
+    1e-6 absolute: in the logit measure they differ by a few roundings of the stored values, and both meet the float64 bound."""
+    import core_logit_cases as cc
+    c, params, (mel, short, emo), g = golden_case(name)
+    ref = core.logit_reference(params, mel, short, emo, num_heads=c["H"], mel_sequence_length=c["T"])
+    sg, s32 = core.recover_sigmoid(g["blendshapes"], params), core.recover_sigmoid(ref["out32"], params)
+    d = np.abs(sg - s32) / (ref["s64"] * (1.0 - ref["s64"]))
+    print(f"golden {name}: max {d.max():.3e}, yardstick {ref['yard_e']:.3e}, |z| <= {np.abs(ref['z64']).max():.2f}")
+    assert (d <= 2 * max(ref["yard_e"], core.LOGIT_FLOOR) + 4 * core.logit_storage_term(ref["s64"])).all(), float(d.max())
+    # against the float64 oracle: the sigmoid values the goldens hold directly, and out / c_i with its three storage terms
+    assert core.logit_verdict(g["mel_blendshapes"] + g["emotion_blendshapes"], ref, cc.K)[1] <= 1.0
+    assert core.logit_verdict(sg, ref, cc.K, core.OUT_OVER_C_ROUNDINGS)[1] <= 1.0
+    assert core.attention_verdict(g["mel_attention_weights"], ref, cc.K)[1] <= 1.0
