@@ -446,6 +446,39 @@ int km_egemaps_records(const float* work_dev, int64_t B, int64_t L, float* rec_h
  * eGeMAPS windows (OpenSMILEeGeMAPSExtractor.get_concatenated_features, opensmile_extractor.py:575-590).  b may be NULL. */
 int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev, void* stream);
 
+/* ---- evaluation metrics: a streaming accumulator in device memory ------------------------------------------------
+ * Replaces BlendshapeMetrics (src/model/losses.py:421-521) and compute_lip_sync_metrics (:524-583).  The reference
+ * copies every batch to the host, concatenates the epoch and reduces it there; here (N, 52) rows are folded into a
+ * float64 / integer state on the device (first-row-shifted moments per column, absolute and squared errors, frame-to-frame
+ * differences carried ACROSS updates as torch.diff over the concatenation sees them, activity counts against float32(0.1),
+ * moments of the mouth activity = sum of columns 12..31, and of an optional per-row audio energy).  Fixed-order
+ * reductions: the same rows in the same calls give the same bits.
+ *   km_metrics_create / _destroy   state + a workspace of partial records on the current device; the state starts empty
+ *   km_metrics_reset               BlendshapeMetrics.reset (:432-436)
+ *   km_metrics_update              BlendshapeMetrics.update (:438-449): pred_dev, target_dev (N, 52); audio_energy_dev (N)
+ *                                  (km_audio_energy of the batch's audio features) or NULL.  Any N >= 0; N = 0 does nothing,
+ *                                  calls beyond 2^24 rows are cut into pieces inside
+ *   km_metrics_compute             BlendshapeMetrics.compute (:451-521) + compute_lip_sync_metrics (:540-583) over
+ *                                  everything since the last reset: out_dev[KM_METRICS_COUNT] float32, finalised in
+ *                                  float64 and rounded once.  The state is left as it is (compute, update, compute works)
+ * reset / update / compute launch on `stream`, neither allocate nor synchronise nor read back, and can be captured.
+ * out_dev, in the reference's key order:
+ *    0 mae                   1 mse                 2 rmse                 3 max_bs_mae         4 min_bs_mae
+ *    5 std_bs_mae            6 mean_correlation    7 min_correlation      8 temporal_consistency
+ *    9 pred_smoothness      10 target_smoothness  11 pred_activity       12 target_activity   13 precision
+ *   14 recall               15 f1_score
+ *   16 mouth_mae            17 mouth_correlation  18 audiovisual_sync (0 unless an energy was given)
+ *   19 rows (exact below 2^24)   20 valid_correlations (columns that passed the std() > 1e-6 gate of :479)
+ *   21 has_energy (1 when any update came with an energy, else 0)
+ * 8..10 are 0 while fewer than two rows were seen (the reference leaves the keys out, :492); before any row every entry
+ * is 0 (the reference returns {}, :453-454). */
+#define KM_METRICS_COUNT 22
+int km_metrics_create(void** acc_out);
+int km_metrics_destroy(void* acc);
+int km_metrics_reset(void* acc, void* stream);
+int km_metrics_update(void* acc, const float* pred_dev, const float* target_dev, const float* audio_energy_dev, int64_t N, void* stream);
+int km_metrics_compute(void* acc, float* out_dev, void* stream);
+
 /* ---- run-time switches ---------------------------------------------------------------------------
  * Replaces what would be module attributes / environment switches on the reference side (the reference has none on
  * this path: every switch selects between two implementations of the SAME arithmetic, for A/B timing and for the

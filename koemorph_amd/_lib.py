@@ -63,6 +63,13 @@ KM_OK = 0
 KM_ERR_INVALID_ARG, KM_ERR_UNSUPPORTED, KM_ERR_NOT_FINALIZED = -1, -2, -3
 KM_ERR_WORKSPACE, KM_ERR_HIP, KM_ERR_NOT_READY = -4, -5, -6
 
+# km_metrics_compute's output vector (include/koemorph.h: KM_METRICS_COUNT and the index of every entry)
+KM_METRICS_COUNT = 22
+KM_METRICS_NAMES = ("mae", "mse", "rmse", "max_bs_mae", "min_bs_mae", "std_bs_mae", "mean_correlation", "min_correlation",
+                    "temporal_consistency", "pred_smoothness", "target_smoothness", "pred_activity", "target_activity",
+                    "precision", "recall", "f1_score", "mouth_mae", "mouth_correlation", "audiovisual_sync", "rows",
+                    "valid_correlations", "has_energy")
+
 _p = C.c_void_p
 _i64 = C.c_int64
 _i32 = C.c_int32
@@ -135,6 +142,11 @@ SIGNATURES = {
     "km_egemaps_workspace_floats": (_i64, [_i64, _i64]),
     "km_egemaps_functionals": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p, _p]),
     "km_egemaps_records": (C.c_int, [_p, _i64, _i64, _p, _p]),
+    "km_metrics_create": (C.c_int, [C.POINTER(_p)]),
+    "km_metrics_destroy": (C.c_int, [_p]),
+    "km_metrics_reset": (C.c_int, [_p, _p]),
+    "km_metrics_update": (C.c_int, [_p, _p, _p, _p, _i64, _p]),
+    "km_metrics_compute": (C.c_int, [_p, _p, _p]),
     "km_linear": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
     "km_enable_stage_timing": (C.c_int, [_h, _i32]),
     "km_stage_times": (C.c_int, [_h, C.POINTER(C.c_float)]),

@@ -1,0 +1,248 @@
+"""Evaluation metrics -- mirror of the reference's ``BlendshapeMetrics`` (src/model/losses.py:421-521) and
+``compute_lip_sync_metrics`` (:524-583).
+
+The reference copies every batch to the host, concatenates the epoch and reduces it with torch on the CPU.  Here device
+tensors are folded into a float64 accumulator in device memory by the HIP kernels behind ``km_metrics_*``
+(koemorph_amd/csrc/km_metrics.hip): ``update`` enqueues one call on the current stream and returns, ``compute`` enqueues
+the finalisation and does the only readback.  CPU tensors run ``metrics_f64`` below, the float64 NumPy restatement of
+both reference functions; it is also the yardstick of the GPU tests.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional
+
+import numpy as np
+
+from ._lib import KM_METRICS_COUNT, KM_METRICS_NAMES, check, load
+
+REFERENCE_KEYS = KM_METRICS_NAMES[:16]           # BlendshapeMetrics.compute(), in the reference's order
+TEMPORAL_KEYS = ("temporal_consistency", "pred_smoothness", "target_smoothness")   # absent when one row was seen (:492)
+LIP_SYNC_KEYS = KM_METRICS_NAMES[16:19]          # compute_lip_sync_metrics()
+DIAGNOSTIC_KEYS = ("rows", "valid_correlations")  # ours: rows folded, columns that passed the std() > 1e-6 gate
+MOUTH = slice(12, 32)                            # losses.py:543
+ACTIVITY_THRESHOLD = np.float32(0.1)             # `tensor_f32 > 0.1` compares against 0.1 rounded to float32 (:501-503)
+
+
+def _corr(x: np.ndarray, y: np.ndarray, gate_x: bool = True, gate_y: bool = True) -> Optional[float]:
+    """torch.corrcoef(...)[0, 1] behind the reference's gates: unbiased std() > 1e-6 where gated, NaN -> None."""
+    n = x.shape[0]
+    if n < 2:
+        return None                                          # std() of one value is NaN: the gate is closed
+    x, y = x - x[0], y - y[0]                                # exact for constant input: its variance is exactly 0
+    xc, yc = x - x.mean(), y - y.mean()
+    vx, vy = float((xc * xc).sum()), float((yc * yc).sum())
+    if gate_x and not np.sqrt(vx / (n - 1)) > 1e-6:
+        return None
+    if gate_y and not np.sqrt(vy / (n - 1)) > 1e-6:
+        return None
+    den = np.sqrt(vx) * np.sqrt(vy)
+    if not den > 0.0:
+        return None                                          # 0 / 0 in corrcoef
+    return float(np.clip(float((xc * yc).sum()) / den, -1.0, 1.0))
+
+
+def metrics_f64(pred, target, energy=None) -> Dict[str, float]:
+    """Both reference functions over (N, 52) float32 rows, evaluated in float64: every key of
+    ``BlendshapeMetrics.compute()`` (the three temporal keys only when N > 1), ``mouth_mae`` / ``mouth_correlation`` of
+    ``compute_lip_sync_metrics``, ``audiovisual_sync`` when a per-row ``energy`` (N) is given, and DIAGNOSTIC_KEYS."""
+    p32 = np.ascontiguousarray(np.asarray(pred, np.float32).reshape(-1, 52))
+    t32 = np.ascontiguousarray(np.asarray(target, np.float32).reshape(-1, 52))
+    if p32.shape != t32.shape:
+        raise ValueError(f"pred {p32.shape} and target {t32.shape} differ")
+    n = p32.shape[0]
+    if n == 0:
+        return {}
+    p, t = p32.astype(np.float64), t32.astype(np.float64)
+    m: Dict[str, float] = {}
+    ad = np.abs(p - t)
+    m["mae"] = float(ad.mean())
+    m["mse"] = float(((p - t) ** 2).mean())
+    m["rmse"] = float(np.sqrt(m["mse"]))
+    per = ad.mean(axis=0)
+    m["max_bs_mae"], m["min_bs_mae"], m["std_bs_mae"] = float(per.max()), float(per.min()), float(per.std(ddof=1))
+    corrs = [c for c in (_corr(p[:, i], t[:, i]) for i in range(52)) if c is not None]
+    m["mean_correlation"] = sum(corrs) / len(corrs) if corrs else 0.0
+    m["min_correlation"] = min(corrs) if corrs else 0.0
+    if n > 1:
+        dp, dt = np.diff(p, axis=0), np.diff(t, axis=0)
+        m["temporal_consistency"] = float(np.abs(dp - dt).mean())
+        m["pred_smoothness"] = float(np.abs(dp).mean())
+        m["target_smoothness"] = float(np.abs(dt).mean())
+    pa, ta = p32 > ACTIVITY_THRESHOLD, t32 > ACTIVITY_THRESHOLD
+    m["pred_activity"], m["target_activity"] = float(pa.sum()) / pa.size, float(ta.sum()) / ta.size
+    tp, fp, fn = float((pa & ta).sum()), float((pa & ~ta).sum()), float((~pa & ta).sum())
+    precision, recall = tp / (tp + fp + 1e-8), tp / (tp + fn + 1e-8)
+    m["precision"], m["recall"] = precision, recall
+    m["f1_score"] = 2 * precision * recall / (precision + recall + 1e-8)
+    # compute_lip_sync_metrics
+    m["mouth_mae"] = float(ad[:, MOUTH].mean())
+    ap, at = p[:, MOUTH].sum(axis=1), t[:, MOUTH].sum(axis=1)
+    c = _corr(ap, at)
+    m["mouth_correlation"] = 0.0 if c is None else c
+    if energy is not None:
+        e = np.asarray(energy, np.float32).astype(np.float64).reshape(-1)
+        if e.shape[0] != n:
+            raise ValueError(f"energy has {e.shape[0]} rows, pred {n}")
+        c = _corr(ap, e, gate_x=False)
+        m["audiovisual_sync"] = 0.0 if c is None else c
+    m["rows"] = float(n)
+    m["valid_correlations"] = float(len(corrs))
+    return m
+
+
+def _energy_host(features) -> np.ndarray:
+    """Per-row energy as compute_lip_sync_metrics reduces its features (losses.py:567-570), float64 -> float32."""
+    f = np.asarray(features, np.float32).astype(np.float64)
+    if f.ndim == 3:
+        return np.sqrt((f * f).sum(-1)).mean(-1).astype(np.float32)
+    if f.ndim == 2:
+        return np.sqrt((f * f).sum(-1)).astype(np.float32)
+    raise ValueError(f"audio_features must be 2-D or 3-D, got {f.ndim}-D")
+
+
+def _rows(pred, target):
+    if pred.shape[-1] != 52 or target.shape[-1] != 52:
+        raise ValueError(f"last dimension must be 52 blendshapes, got pred {tuple(pred.shape)} target {tuple(target.shape)}")
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} differ")
+    return pred.reshape(-1, 52), target.reshape(-1, 52)
+
+
+class BlendshapeMetrics:
+    """``reset()``, ``update(pred, target, audio_features=None)``, ``compute() -> Dict[str, float]`` as the reference's
+    class.  The first ``update`` after a reset decides where the epoch lives: device tensors go to the HIP accumulator of
+    their device, CPU tensors / arrays are kept and reduced by ``metrics_f64``."""
+
+    def __init__(self):
+        self._acc = C.c_void_p()
+        self._device = None
+        self._lib = None
+        self.reset()
+
+    # ---- device plumbing --------------------------------------------------------------------------------
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self._device).cuda_stream
+
+    def _open(self, device):
+        import torch
+        if self._acc and self._device != device:
+            self.close()
+        if not self._acc:
+            self._lib = load()
+            self._device = device
+            with torch.cuda.device(device):
+                check(self._lib.km_metrics_create(C.byref(self._acc)))
+
+    def close(self):
+        if self._acc:
+            import torch
+            torch.cuda.synchronize(self._device)
+            self._lib.km_metrics_destroy(self._acc)
+            self._acc = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- reference interface ----------------------------------------------------------------------------
+    def reset(self):
+        """Reset accumulated metrics (losses.py:432-436)."""
+        self.rows = 0
+        self._where: Optional[str] = None            # "device" | "host" after the first update
+        self._host: List = []
+        self._has_energy = False
+        if self._acc:
+            import torch
+            with torch.cuda.device(self._device):
+                check(self._lib.km_metrics_reset(self._acc, self._stream()))
+
+    def update(self, pred_blendshapes, target_blendshapes, audio_features=None):
+        """Fold a batch in (losses.py:438-449).  Any leading shape over 52 columns; ``audio_features`` (rows, D) or
+        (rows, T, D) gives the per-row energy of ``audiovisual_sync``."""
+        pred, target = _rows(pred_blendshapes, target_blendshapes)
+        n = int(pred.shape[0])
+        on_device = bool(getattr(pred, "is_cuda", False))
+        where = "device" if on_device else "host"
+        if self._where is not None and where != self._where:
+            raise ValueError("one epoch mixes device and host tensors; reset() first")
+        if audio_features is not None and int(audio_features.shape[0]) != n:
+            raise ValueError(f"audio_features has {int(audio_features.shape[0])} rows, pred {n}")
+        if audio_features is not None and audio_features.ndim not in (2, 3):
+            raise ValueError(f"audio_features must be 2-D or 3-D, got {audio_features.ndim}-D")
+        if n == 0:
+            return
+        self._where = where
+        if not on_device:
+            as_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+            self._host.append((np.array(as_np(pred), np.float32), np.array(as_np(target), np.float32),
+                               None if audio_features is None else _energy_host(as_np(audio_features))))
+            self.rows += n
+            return
+        import torch
+        if target.device != pred.device:
+            raise ValueError("pred and target are on different devices")
+        self._open(pred.device)
+        pred = pred.detach().to(torch.float32).contiguous()
+        target = target.detach().to(torch.float32).contiguous()
+        with torch.cuda.device(self._device):
+            energy = None
+            if audio_features is not None:
+                af = audio_features.detach().to(self._device, torch.float32).contiguous()
+                if af.dim() == 2:
+                    af = af.unsqueeze(1)
+                energy = torch.empty(n, device=self._device)
+                check(self._lib.km_audio_energy(af.data_ptr(), n, af.shape[1], af.shape[2], energy.data_ptr(), self._stream()))
+                self._has_energy = True
+            check(self._lib.km_metrics_update(self._acc, pred.data_ptr(), target.data_ptr(),
+                                              0 if energy is None else energy.data_ptr(), n, self._stream()))
+        self.rows += n
+
+    def _vector(self) -> np.ndarray:
+        """km_metrics_compute on the current stream + the one readback: KM_METRICS_COUNT float32."""
+        import torch
+        with torch.cuda.device(self._device):
+            out = torch.empty(KM_METRICS_COUNT, device=self._device)
+            check(self._lib.km_metrics_compute(self._acc, out.data_ptr(), self._stream()))
+            return out.cpu().numpy()
+
+    def _all(self) -> Dict[str, float]:
+        if self._where == "host":
+            p = np.concatenate([h[0] for h in self._host])
+            t = np.concatenate([h[1] for h in self._host])
+            with_e = [h[2] is not None for h in self._host]
+            if any(with_e) and not all(with_e):
+                raise ValueError("audio_features were given for some host batches only")
+            return metrics_f64(p, t, np.concatenate([h[2] for h in self._host]) if all(with_e) else None)
+        v = self._vector()
+        m = {k: float(v[i]) for i, k in enumerate(KM_METRICS_NAMES)}
+        if m.pop("has_energy") == 0.0:
+            del m["audiovisual_sync"]
+        if self.rows < 2:
+            for k in TEMPORAL_KEYS:
+                del m[k]
+        return m
+
+    def compute(self, lip_sync: bool = False) -> Dict[str, float]:
+        """Accumulated metrics (losses.py:451-521): the reference's keys in its order; ``{}`` before any update.
+        ``lip_sync=True`` adds the keys of ``compute_lip_sync_metrics`` over the same rows and DIAGNOSTIC_KEYS."""
+        if self.rows == 0:
+            return {}
+        m = self._all()
+        keys = REFERENCE_KEYS + ((LIP_SYNC_KEYS + DIAGNOSTIC_KEYS) if lip_sync else ())
+        return {k: m[k] for k in keys if k in m}
+
+
+def compute_lip_sync_metrics(pred_blendshapes, target_blendshapes, audio_features=None) -> Dict[str, float]:
+    """``mouth_mae``, ``mouth_correlation`` and, with ``audio_features``, ``audiovisual_sync`` (losses.py:524-583), on a
+    fresh accumulator."""
+    acc = BlendshapeMetrics()
+    try:
+        acc.update(pred_blendshapes, target_blendshapes, audio_features)
+        m = acc.compute(lip_sync=True)
+    finally:
+        acc.close()
+    return {k: m[k] for k in LIP_SYNC_KEYS if k in m}

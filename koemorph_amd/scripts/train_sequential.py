@@ -28,6 +28,7 @@ import torch
 from .. import parallel, synth
 from ..data import SequentialKoeMorphDataset
 from ..engine import Engine
+from ..metrics import BlendshapeMetrics
 from ..training import Trainer
 
 logger = logging.getLogger(__name__)
@@ -72,8 +73,12 @@ class SequentialTrainer:
         return {k: (v[lo:hi] if isinstance(v, (torch.Tensor, list)) else v) for k, v in batch.items()}, hi - lo
 
     # ---- reference API ----------------------------------------------------------------------------------
-    def train_epoch(self) -> Dict[str, float]:
+    def train_epoch(self, metrics: bool = False) -> Dict[str, float]:
+        """``metrics=True``: every step's output (``Trainer.out``) and target also go into a ``BlendshapeMetrics`` on the
+        device (src/train.py:214: the reference's trainer feeds its train_metrics the same way); its ``compute()`` is merged
+        into the result.  The loss and the weights are what they are without it."""
         total, n = 0.0, 0
+        bm = BlendshapeMetrics() if metrics else None
         t0 = time.time()
         for batch in self.train_data:
             file_idx = int(batch["file_indices"][0])
@@ -89,18 +94,27 @@ class SequentialTrainer:
             # every rank's gradient is weighted by its share of the GLOBAL batch (shares differ by one window when the
             # batch does not divide, and the last batch of a clip is short): the sum is the full-batch gradient
             loss = self.trainer.step(share["audio"], self._emotion(share), share["target"], global_batch=B_global)
+            if bm is not None:
+                bm.update(self.trainer.out[:nb], share["target"])
             total += float(loss.item())
             n += 1
             self.global_step += 1
         self.trainer.end_epoch()                             # CosineAnnealingWarmRestarts(T_0=10, T_mult=2, eta_min=1e-6)
         self.epoch += 1
-        return {"total": total / max(n, 1), "batches": n, "lr": self.trainer.lr, "seconds": time.time() - t0}
+        out = {"total": total / max(n, 1), "batches": n, "lr": self.trainer.lr, "seconds": time.time() - t0}
+        if bm is not None:
+            out.update(bm.compute())
+            bm.close()
+        return out
 
-    def validate(self) -> Dict[str, float]:
+    def validate(self, metrics: bool = False) -> Dict[str, float]:
+        """``metrics=True``: the reference's validation metrics (src/train.py:239, :260-298) over every window of the pass,
+        accumulated on the device with no host round trip per batch and merged into the result; "total" is unchanged."""
         if self.val_data is None:
             return {}
         self.trainer.sync_inference_weights()
         total, n = 0.0, 0
+        bm = BlendshapeMetrics() if metrics else None
         state = None
         current = None
         with torch.no_grad():
@@ -111,9 +125,15 @@ class SequentialTrainer:
                 if first:
                     current, state = file_idx, torch.zeros(B, 52, device=self.device)
                 pred = self.engine.forward_audio(batch["audio"], self._emotion(batch), state=state, first=first)
+                if bm is not None:
+                    bm.update(pred, batch["target"])
                 total += float(torch.nn.functional.mse_loss(pred, batch["target"]).item())
                 n += 1
-        return {"total": total / max(n, 1), "batches": n}
+        out = {"total": total / max(n, 1), "batches": n}
+        if bm is not None:
+            out.update(bm.compute())
+            bm.close()
+        return out
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         """The reference model's state dict (keys of SimplifiedDualStreamModel: dual_stream_attention.* + smoothing_alpha)."""
@@ -173,6 +193,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--checkpoint_dir", default="checkpoints")
     p.add_argument("--resume", help="checkpoint to resume from")
     p.add_argument("--max_files", type=int)
+    p.add_argument("--metrics", action="store_true", help="log mae / rmse / mean_correlation / f1_score of every epoch (BlendshapeMetrics)")
     return p
 
 
@@ -194,14 +215,19 @@ def main(argv=None):
     if args.resume:
         st.load_checkpoint(args.resume)
     for _ in range(st.epoch, args.epochs):
-        m = st.train_epoch()
-        v = st.validate()
+        m = st.train_epoch(metrics=args.metrics)
+        v = st.validate(metrics=args.metrics)
         is_best = bool(v) and v["total"] < st.best_val_loss
         if is_best:
             st.best_val_loss = v["total"]
         if rank == 0:
             logger.info(f"epoch {st.epoch}: train {m['total']:.6f} ({m['batches']} steps, {m['seconds']:.1f} s, lr {m['lr']:.2e})"
                         + (f", val {v['total']:.6f}" if v else ""))
+            if args.metrics:                                 # the reference logs these four per epoch (src/train.py:368-373)
+                for tag, d in (("train", m), ("val", v)):
+                    if "mae" in d:
+                        logger.info(f"  {tag} metrics: mae {d['mae']:.6f}, rmse {d['rmse']:.6f}, "
+                                    f"mean_correlation {d['mean_correlation']:.4f}, f1_score {d['f1_score']:.4f}")
         st.save_checkpoint(Path(args.checkpoint_dir) / f"checkpoint_epoch_{st.epoch}.pth", is_best=is_best)
 
 

@@ -336,3 +336,57 @@ def make_vowel(seed: int, f0: float, seconds: float, formants=((700.0, 90.0), (1
         x = y
     x = x + noise * np.abs(x).max() * normal(seed + 1, (n,)).astype(np.float64)
     return (x / np.abs(x).max()).astype(np.float32)
+
+
+# ---- inputs of the evaluation-metrics fixtures (tests/golden/metrics_*.npz, tools/gen_metrics_golden.py) -------------------
+METRICS_STYLES = ("plain", "closed_cols", "all_closed", "threshold", "inactive")
+
+
+def make_metrics_inputs(seed: int, N: int, style: str = "plain"):
+    """(pred, target), each (N, 52) float32 in [0, 1], for BlendshapeMetrics (src/model/losses.py:421-521).
+
+    plain        target uniform in [0, 1], pred = target + 0.1-std noise, clipped: every column correlates
+    closed_cols  plain with pred column 5 constant and target column 9 all zero: two correlation gates closed (:479)
+    all_closed   every pred column constant: no correlation passes the gate, the 0.0 fallbacks apply (:484-489, :562-563)
+    threshold    plain with every 7th entry AT float32(0.1) (not active) and every 7th, offset 3, at the next float32
+                 above it (active) (:501-503)
+    inactive     both below the activity threshold everywhere: precision = recall = F1 = 0 through the 1e-8 terms
+    """
+    assert style in METRICS_STYLES, style
+    lo, hi = (0.0, 0.09) if style == "inactive" else (0.0, 1.0)
+    target = uniform(seed * 5 + 1, (N, 52), lo, hi)
+    pred = np.clip(target.astype(np.float64) + 0.1 * (hi - lo) * normal(seed * 5 + 2, (N, 52)), lo, hi).astype(np.float32)
+    if style == "closed_cols":
+        pred[:, 5] = np.float32(0.25)
+        target[:, 9] = 0.0
+    elif style == "all_closed":
+        pred[:] = (0.05 + 0.01 * np.arange(52)).astype(np.float32)[None, :]
+    elif style == "threshold":
+        at, above = np.float32(0.1), np.nextafter(np.float32(0.1), np.float32(1.0))
+        pred.reshape(-1)[0::7] = at
+        pred.reshape(-1)[3::7] = above
+        target.reshape(-1)[1::7] = at
+        target.reshape(-1)[3::7] = above
+    return pred, target
+
+
+def make_metrics_features(seed: int, N: int, kind: str, pred: np.ndarray):
+    """audio_features for compute_lip_sync_metrics (losses.py:566-581): "3d" (N, 12, 80) and "2d" (N, 80) mel-like rows whose
+    level follows the mouth activity of `pred` (a louder frame opens the mouth: audiovisual_sync is O(1), not a
+    difference of rounding errors around 0); "const" (N, 80) identical rows (constant energy: audiovisual_sync = 0.0)."""
+    if kind == "const":
+        return np.ascontiguousarray(np.broadcast_to(uniform(seed * 3 + 9, (1, 80), 0.0, 1.0), (N, 80)))
+    level = 0.2 + 0.1 * pred[:, 12:32].astype(np.float64).sum(axis=1)
+    if kind == "3d":
+        return (uniform(seed * 3 + 7, (N, 12, 80), 0.0, 1.0) * level[:, None, None]).astype(np.float32)
+    if kind == "2d":
+        return (uniform(seed * 3 + 7, (N, 80), 0.0, 1.0) * level[:, None]).astype(np.float32)
+    raise ValueError(kind)
+
+
+def metrics_inputs_checksum(pred: np.ndarray, target: np.ndarray, features=None) -> float:
+    acc = 0.0
+    for i, a in enumerate((pred, target) if features is None else (pred, target, features)):
+        a = np.asarray(a, np.float64).ravel()
+        acc += (i + 1) * float(np.sum(a * (1.0 + (np.arange(a.size) % 7)))) + float(np.sum(np.abs(a)))
+    return acc
