@@ -223,6 +223,26 @@ int km_sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t 
  *                        NULL applies the model's temporal smoothing inside the forward as the reference does
  *   km_train_step_audio  same from audio_dev (B, L): runs the log-mel front end first (no gradient flows into
  *                        it in the reference either: NumPy round trip, simplified_dual_stream_model.py:184-229)
+ *   km_train_step_clip   same for B windows of ONE clip resident in HBM: window b is samples [start_frames[b] * hop,
+ *                        + T * hop) of clip_dev (clip_len samples, zero beyond), exactly what km_gather_windows would have
+ *                        copied; the start frames may come in any order and may repeat.  Replaces the per-window slicing
+ *                        (src/data/sequential_dataset.py:156-209) + the per-window log-mel
+ *                        (src/model/simplified_dual_stream_model.py:184-229) under the step (src/train_sequential.py:158)
+ *                        without materialising the (B, T * hop) windows: the STFT frames the windows share are computed
+ *                        once -- max - min + T + 1 clip frames + 2 zero-padded boundary frames per window instead of
+ *                        B * (T + 1) -- and everything behind the front end is km_train_step_audio's program, so loss,
+ *                        out and flat_grad are bit-identical to km_gather_windows + km_train_step_audio.
+ *                        min_start_frame / max_start_frame are HOST copies of the extremes of start_frames_dev (they size
+ *                        the launches; nothing is read back from the device, so the step can be captured into a hipGraph).
+ *                        A span wider than any earlier call's (km_train_init allocates max_windows + T + 1 frames) grows a
+ *                        buffer: capture only after a warm-up call with that span.  Needs km_reserve(B, T * hop) like the
+ *                        from-audio step.
+ *   km_train_clip_supported   1 when km_train_step_clip runs on this handle (after km_train_init), else 0: the 1024-point
+ *                        front end (not mel_two_frame) that writes the packed encoder input (where km_train_step_audio
+ *                        packs in the front-end launch), pad_mode constant, and hop_length >= n_fft / 2 -- only then are
+ *                        frames 0 and T the only frames of a window that see its zero padding (hop 533: frame 1 spans
+ *                        samples 21 .. 1044; at the 60 fps shape, hop 266, frames 1 and T - 1 reach into it too).
+ *                        km_train_step_clip on an unsupported handle returns KM_ERR_UNSUPPORTED, never another result.
  *   km_train_adamw       grad-norm clipping (max_grad_norm <= 0 disables) + AdamW on the flat vectors; `step`
  *                        is the 1-based optimizer step for the bias correction
  *   km_train_get_params / km_train_set_params   flat master copy <-> host
@@ -238,6 +258,11 @@ int km_train_step(km_handle h, const float* mel_dev, int64_t B, int64_t T_in, co
 int km_train_step_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
                         const float* target_dev, float mse_weight, float l1_weight, float* flat_grad_dev,
                         float* loss_dev, float* out_dev, float* ema_state_dev, int32_t ema_first, void* stream);
+int km_train_clip_supported(km_handle h);
+int km_train_step_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
+                       int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev, const float* target_dev,
+                       float mse_weight, float l1_weight, float* flat_grad_dev, float* loss_dev, float* out_dev,
+                       float* ema_state_dev, int32_t ema_first, void* stream);
 int km_train_adamw(km_handle h, const float* flat_grad_dev, float lr, float beta1, float beta2, float eps,
                    float weight_decay, float max_grad_norm, int64_t step, void* stream);
 int km_train_get_params(km_handle h, float* flat_host, int64_t n);

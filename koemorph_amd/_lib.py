@@ -106,6 +106,8 @@ SIGNATURES = {
     "km_train_param_offset": (_i64, [_h, C.c_char_p]),
     "km_train_step": (C.c_int, [_h, _p, _i64, _i64, _p, _p, _p, C.c_float, C.c_float, _p, _p, _p, _p, _i32, _p]),
     "km_train_step_audio": (C.c_int, [_h, _p, _i64, _i64, _p, _p, C.c_float, C.c_float, _p, _p, _p, _p, _i32, _p]),
+    "km_train_clip_supported": (C.c_int, [_h]),
+    "km_train_step_clip": (C.c_int, [_h, _p, _i64, _p, _i64, _i32, _i32, _p, _p, C.c_float, C.c_float, _p, _p, _p, _p, _i32, _p]),
     "km_train_adamw": (C.c_int, [_h, _p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i64, _p]),
     "km_train_get_params": (C.c_int, [_h, _p, _i64]),
     "km_train_set_params": (C.c_int, [_h, _p, _i64]),

@@ -223,6 +223,7 @@ static int free_train(Context* c) {
     c->tr_params = c->tr_m = c->tr_v = c->tr_act = c->tr_q = c->tr_dq = c->tr_part = c->tr_gnorm = c->tr_loss = c->tr_red = nullptr;
     c->tr_steps = nullptr;
     if (c->tr_red2) { HIP_TRY(hipFree(c->tr_red2)); c->tr_red2 = nullptr; }
+    if (c->clip_span) { HIP_TRY(hipFree(c->clip_span)); c->clip_span = c->clip_edge = nullptr; c->clip_span_cap = c->clip_edge_cap = 0; }
     if (c->trp_act) { HIP_TRY(hipFree(c->trp_act)); c->trp_act = nullptr; c->trp_act_floats = 0; }
     if (c->trp_split) { HIP_TRY(hipFree(c->trp_split)); c->trp_split = nullptr; c->trp_split_floats = 0; }
     if (c->trp_wcep) { HIP_TRY(hipFree(c->trp_wcep)); c->trp_wcep = nullptr; }
@@ -246,6 +247,32 @@ static int upload_train_params(Context* c, void* stream) {
     HIP_TRY(hipMemcpyAsync(c->tr_params, flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream));
     if (int rc = train_refresh_padded_weights(c, stream)) return rc;
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return KM_OK;
+}
+
+// km_train_step_clip shares STFT frames between the windows of a batch.  That needs (a) the front end that writes the packed
+// encoder input (where km_train_step_audio takes its fe_packs branch at a window of T hop samples), (b) zero padding -- a
+// reflected boundary frame is not a clip frame either, but the two images below are built for zeros -- and (c) hop >= n_fft / 2:
+// frame f of a window spans its samples [f hop - n_fft / 2, f hop + n_fft / 2), so only then are frames 1 .. T - 1 free of
+// the window's padding and equal to the clip's own frames (hop 533: frame 1 starts at sample 21; hop 266: frames 1 and T - 1
+// reach into the padding too).
+static bool train_clip_ok(Context* c) {
+    if (c->mel_plans.empty()) return false;
+    MelPlan* p = c->mel_plans[0];
+    const km_mel_config& m = p->cfg;
+    return !c->opt.train_chain && !c->opt.train_no_fe_pack && !c->opt.train_no_dma && mel_packs(c, p, c->T + 1, c->T) &&
+           m.n_mels == c->NK && c->NK % 4 == 0 && m.pad_mode == KM_PAD_CONSTANT && 2 * m.hop_length >= m.n_fft;
+}
+
+// span image (span_rows, NK) and edge image (tr_windows, 2, NK) of km_train_step_clip in ONE allocation: the pack kernel
+// addresses both with 32-bit offsets from one base
+static int alloc_clip_images(Context* c, int64_t span_rows) {
+    if (c->clip_span) HIP_TRY(hipFree(c->clip_span));
+    c->clip_span = c->clip_edge = nullptr; c->clip_span_cap = c->clip_edge_cap = 0;
+    if ((span_rows + 2 * c->tr_windows) * c->NK >= (1ll << 31)) return fail(KM_ERR_WORKSPACE, "km_train_step_clip: span of %lld frames is too wide", (long long)span_rows);
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->clip_span), (size_t)(span_rows + 2 * c->tr_windows) * c->NK * sizeof(float)));
+    c->clip_edge = c->clip_span + span_rows * c->NK;
+    c->clip_span_cap = span_rows; c->clip_edge_cap = c->tr_windows;
     return KM_OK;
 }
 
@@ -321,6 +348,8 @@ int km_train_init(km_handle h, int64_t max_windows, void* stream) {
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->trp_drop_ctr), sizeof(int)));
         HIP_TRY(hipMemsetAsync(c->trp_drop_ctr, 0, sizeof(int), (hipStream_t)stream));
     }
+    if (train_clip_ok(c))       // km_train_step_clip: the span of a dense (stride 1) batch; a wider span grows the image on first use
+        if (int rc = alloc_clip_images(c, max_windows + c->T + 1)) return rc;
     return upload_train_params(c, stream);
 }
 
@@ -384,6 +413,53 @@ int km_train_step_audio(km_handle h, const float* audio_dev, int64_t B, int64_t 
     if (int rc = launch_mel(c, c->mel_plans[0], audio_dev, B, L, 0, c->ws_mel, c->ws_short, stream)) return rc;
     return train_forward_backward(c, c->ws_mel, B, n_frames, c->ws_short, emotion_dev, target_dev, mse_weight, l1_weight,
                                   flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream);
+}
+
+int km_train_clip_supported(km_handle h) {
+    if (!h || !h->dev_finalized || h->kind != 0 || !h->tr_params) return 0;
+    return train_clip_ok(h) ? 1 : 0;
+}
+
+int km_train_step_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
+                       int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev, const float* target_dev,
+                       float mse_weight, float l1_weight, float* flat_grad_dev, float* loss_dev, float* out_dev,
+                       float* ema_state_dev, int32_t ema_first, void* stream) {
+    if (int rc = need_train(h, B)) return rc;
+    Context* c = h;
+    if (!clip_dev || !start_frames_dev || !emotion_dev || !target_dev || !flat_grad_dev || !loss_dev || clip_len <= 0 ||
+        min_start_frame < 0 || max_start_frame < min_start_frame)
+        return fail(KM_ERR_INVALID_ARG, "km_train_step_clip: bad argument");
+    const km_mel_config& m = c->mel_plans[0]->cfg;
+    if (!train_clip_ok(c))
+        return fail(KM_ERR_UNSUPPORTED, "km_train_step_clip: windows share STFT frames only with the packing 1024-point front end, constant "
+                    "padding and hop >= n_fft / 2 (hop %d, n_fft %d): gather the windows (km_gather_windows) and call km_train_step_audio",
+                    m.hop_length, m.n_fft);
+    const int64_t T = c->T, hop = m.hop_length;
+    const int64_t n_span = (int64_t)(max_start_frame - min_start_frame) + T + 1;
+    if (clip_len >= (1ll << 31) || ((int64_t)max_start_frame + T + 2) * hop >= (1ll << 31))
+        return fail(KM_ERR_INVALID_ARG, "km_train_step_clip: clip or start frame beyond 2^31 samples");
+    if (B > c->ws_windows)
+        return fail(KM_ERR_WORKSPACE, "workspace holds %lld windows, need %lld: call km_reserve", (long long)c->ws_windows, (long long)B);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_span > c->clip_span_cap || B > c->clip_edge_cap) {            // grow-only; allocates, so not inside a stream capture
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+            return fail(KM_ERR_WORKSPACE, "km_train_step_clip: a span of %lld frames exceeds the %lld allocated during a stream capture: "
+                        "run one step with this span first", (long long)n_span, (long long)c->clip_span_cap);
+        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = alloc_clip_images(c, n_span > c->clip_span_cap ? n_span : c->clip_span_cap)) return rc;
+    }
+    // (the pack kernel STORES the maxima of windows 0 .. B - 1: no zeroed slots needed, no memset whatever ran before)
+    const int KP = (int)trainp_kp(c);
+    if (int rc = launch_mel_clip_span(c, c->mel_plans[0], clip_dev, clip_len, start_frames_dev, B, min_start_frame, n_span, (int)T,
+                                      c->clip_span, c->clip_edge, stream)) return rc;
+    if (int rc = launch_train_clip_pack(c, c->mel_plans[0], c->clip_span, c->clip_edge, start_frames_dev, B, min_start_frame, n_span,
+                                        (int)T, KP, c->trp_act, stream)) return rc;
+    c->melmax_dirty = true;      // until phase 3 / 4 has re-zeroed the maxima
+    const LogParams lp = plan_log_params(c->mel_plans[0]);
+    const TrainAudioSrc asrc{c->ws_melpow, c->ws_melmax, (int)(T + 1), &lp, true};
+    return train_forward_backward_phased(c, nullptr, B, T + 1, nullptr, c->trp_act, &asrc, emotion_dev, target_dev, mse_weight,
+                                         l1_weight, flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream);
 }
 
 int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev, void* stream) {

@@ -180,6 +180,10 @@ struct Context {
     // shared-frame sequence mode buffers (grow-only, allocated by km_sequence_forward)
     float* seq_pow = nullptr; unsigned* seq_fmax = nullptr; float* seq_edge = nullptr; unsigned* seq_emax = nullptr;
     int64_t seq_pow_cap = 0, seq_edge_cap = 0;
+    // training from a resident clip (km_train_step_clip): power-mel of the clip span the batch touches (rows, NK) and of every
+    // window's two zero-padded boundary frames (windows, 2, NK); sized by km_train_init, the span image grow-only afterwards
+    float* clip_span = nullptr; float* clip_edge = nullptr;
+    int64_t clip_span_cap = 0, clip_edge_cap = 0;
     int64_t tr_alpha_steps = 0;
     bool stage_timing = false;
     void* stage_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // hipEvent_t: emo b/e, mel e, core b/e
@@ -284,6 +288,15 @@ int launch_mel_power(Context* c, MelPlan* p, const float* audio, int64_t B, int6
                      const float* emotion = nullptr, float* zemo = nullptr, const SeqFrames* seq = nullptr,
                      const MelPack* pack = nullptr);
 bool mel_packs(Context* c, MelPlan* p, int64_t n_frames, int64_t T);
+// Training from a resident clip (km_train_step_clip).  Window b of the batch is samples [start[b] hop, + T hop) of the clip.
+// launch_mel_clip_span: ONE front-end launch writes `span` (n_span, n_mels) = the power-mel of clip frames min_start ..
+// min_start + n_span - 1 (frame f of window b is row start[b] - min_start + f for f = 1 .. T - 1) and `edge` (B, 2, n_mels) =
+// frames 0 and T of every window, the two that see its zero padding.  launch_train_clip_pack: from both images the packed
+// encoder input xt (B, n_mels, KP) as MelPack leaves it and the window maxima into ws_melmax.
+int launch_mel_clip_span(Context* c, MelPlan* p, const float* clip, int64_t clip_len, const int* start_frames, int64_t B,
+                         int min_start, int64_t n_span, int T, float* span, float* edge, void* stream);
+int launch_train_clip_pack(Context* c, MelPlan* p, const float* span, const float* edge, const int* start_frames, int64_t B,
+                           int min_start, int64_t n_span, int T, int KP, float* xt, void* stream);
 bool mel_fuses_emotion(Context* c, MelPlan* p);
 int ensure_chunk_counters(Context* c, int64_t windows, void* stream);
 int launch_ring_push(Context* c, const float* samples, int64_t n_per_stream, void* stream);

@@ -140,6 +140,13 @@ struct MelArgs {
     float* pack_xt;
     int pack_T, pack_KP;
     float pack_amin;
+    // training from a resident clip (km_train_step_clip; TAB instantiation of mel_power_rp_kernel): one launch, in which "window" 0
+    // is the clip span -- n_frames frames from clip frame tab_min on, written to melpow -- and "window" 1 + w is batch window w,
+    // which starts at clip frame tab_start[w] and contributes its frames 0 and tab_T (the two that see its zero padding) to
+    // tab_edge (w, 2, n_mels).  The grid is one-dimensional: tab_span_wgs workgroups for the span, then one per batch window.
+    const int* tab_start;
+    float* tab_edge;
+    int tab_min, tab_T, tab_span_wgs;
 };
 
 // raw samples of the frame pair (fa, fa+1) into z[i] = (x_a[lane + 64 i], x_b[lane + 64 i]); wave-uniform fa
@@ -740,7 +747,7 @@ __device__ __forceinline__ int mel_lane_of(int slot, int frame) {
     return 32 * (slot >> 1) + m;
 }
 
-template <bool RING, bool PACK = false>
+template <bool RING, bool PACK = false, bool TAB = false>
 __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
     using namespace melrp;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -759,18 +766,27 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
     // one window are gridDim.y ids apart instead of adjacent (tools/micro: which workgroups share a CU / an XCD's L2).
 #if KM_MEL_REMAP
     const unsigned lin_ = blockIdx.x + gridDim.x * blockIdx.y;
-    const int b = (int)(lin_ % gridDim.y), bx = (int)(lin_ / gridDim.y);
+    const int b = TAB ? ((int)blockIdx.x < a.tab_span_wgs ? 0 : 1 + (int)blockIdx.x - a.tab_span_wgs) : (int)(lin_ % gridDim.y);
+    const int bx = TAB ? (b == 0 ? (int)blockIdx.x : 0) : (int)(lin_ / gridDim.y);
 #else
     const int b = blockIdx.y, bx = (int)blockIdx.x;
+    static_assert(!TAB, "the clip-span launch is laid out for KM_MEL_REMAP");
 #endif
+    const unsigned gx = TAB ? (b == 0 ? (unsigned)a.tab_span_wgs : 1u) : gridDim.x;      // workgroups of this window
+    const int n_frames = TAB && b > 0 ? 2 : a.n_frames;
     const int64_t gw = a.win0 + b;
-    const int64_t clip = gw / a.wins_per_clip, woff = (gw - clip * a.wins_per_clip) * a.win_step;
-    const float* x = a.audio + clip * a.clip_len + woff;
-    const int Lv = (int)((a.clip_len - woff) < a.L ? (a.clip_len - woff) : a.L);
+    const int64_t clip = TAB ? 0 : gw / a.wins_per_clip;
+    int tab_f0 = 0;
+    if constexpr (TAB) { tab_f0 = b == 0 ? a.tab_min : a.tab_start[b - 1]; tab_f0 = tab_f0 < 0 ? 0 : tab_f0; }
+    const int64_t woff = TAB ? (int64_t)tab_f0 * a.hop : (gw - clip * a.wins_per_clip) * a.win_step;
+    const int64_t Lw = TAB ? (int64_t)(b == 0 ? a.n_frames - 1 : a.tab_T) * a.hop : a.L;
+    // (TAB: a window that starts beyond the clip reads as zeros -- Lv <= 0 -- and keeps its pointer inside the clip)
+    const float* x = a.audio + clip * a.clip_len + (TAB && woff >= a.clip_len ? 0 : woff);
+    const int Lv = (int)((a.clip_len - woff) < Lw ? (a.clip_len - woff) : Lw);
     if (a.ready && !a.ready[b]) return;                        // workgroup-uniform: stream still filling
     const int rs = RING ? a.ring_start[b] : -1;
     v2f* buf = reinterpret_cast<v2f*>(fbuf + wave * FFT_BUF);
-    const int n_chunks = (a.n_frames + FPB - 1) / FPB;
+    const int n_chunks = (n_frames + FPB - 1) / FPB;
     const unsigned rd2 = lds_offset(buf + (lane >> 3) * 72 + (lane & 7)), rd3 = lds_offset(buf + lane * 9);
     const unsigned wr3 = lds_offset(buf + fft_lane_k0(lane) * 9 + (lane & 7));
     const int cbin = fft_lane_bin(lane);                       // this lane finishes the bins cbin + 64 i and 512 - cbin - 64 i
@@ -781,18 +797,18 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
     // frame is requested here, ahead of everything else the prologue loads (tables through L2; these come from HBM).
     v2f zn[8];
     bool zn_ok = false;                                                  // wave-uniform: zn holds the next frame
-    const int fmul = a.frame_mul;
+    const int fmul = TAB ? (b == 0 ? 1 : a.tab_T) : a.frame_mul;
     auto first_frame = [&]() {
         if (KM_MEL_SKIP & 8) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) zn[i] = v2f{0.001f * lane, 0.5f + i};
             zn_ok = true;
-        } else if (bx * FPB + wave < a.n_frames) zn_ok = load_frame_rp_fast<RING>(x, Lv, rs, a.hop, (bx * FPB + wave) * fmul, lane, zn);
+        } else if (bx * FPB + wave < n_frames) zn_ok = load_frame_rp_fast<RING>(x, Lv, rs, a.hop, (bx * FPB + wave) * fmul, lane, zn);
     };
     // The emotion stream of this window (0.2 MFLOP, latency bound, independent of the audio) rides in the last workgroup of
     // the window: no separate launch, and the chunk hand-out below lets that workgroup take correspondingly fewer chunks.
     // (It requests its first frame after the rider: the rider's weight loads need the registers.)
-    if (!(KM_MEL_SKIP & 16) && a.emo.emo && bx == (int)gridDim.x - 1) {
+    if (!(KM_MEL_SKIP & 16) && a.emo.emo && bx == (int)gx - 1) {
         if (a.emo.d == 256 && a.emo.DH == 128) emotion_window_d256(a.emo, gw, pw);
         else emotion_window_generic(a.emo, EmoShape{a.emo.d, a.emo.DH}, gw, pw);
         first_frame();
@@ -840,7 +856,7 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
     for (int i = 0; i < NGW; ++i) asm volatile("" ::"s"(my_gid[i]));
 
     float vmax = 0.f;
-    int chunk = bx, chunk_next = bx + (int)gridDim.x;
+    int chunk = bx, chunk_next = bx + (int)gx;
 #if defined(KM_MEL_DELAY)          /* timing experiment: hold the odd workgroups of a window back by KM_MEL_DELAY x 64 cycles */
     if (bx & 1) { for (int i = 0; i < KM_MEL_DELAY; i += 16) __builtin_amdgcn_s_sleep(16); }
 #endif
@@ -857,7 +873,7 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
         for (int pi = 0; pi < FPB / WAVES; ++pi) {
             const int fl = wave + WAVES * pi;
             const int f = f0 + fl;
-            if (f < a.n_frames) {   // wave-uniform
+            if (f < n_frames) {   // wave-uniform
                 if (!zn_ok) {       // edge frame (padding / ring wrap): 2 of 257 in the batch shape
                     load_frame_rp_slow(x, Lv, rs, RING ? 1 : 0, a.hop, a.pad_mode == KM_PAD_REFLECT ? 1 : 0, f * fmul, lane,
                                        reinterpret_cast<float2*>(buf));
@@ -885,7 +901,7 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
                 }
                 {
                     const int fnext = pi + 1 < FPB / WAVES ? f + WAVES : chunk_next * FPB + wave;
-                    if (!(KM_MEL_SKIP & 8)) zn_ok = fnext < a.n_frames && load_frame_rp_fast<RING>(x, Lv, rs, a.hop, fnext * fmul, lane, zn);
+                    if (!(KM_MEL_SKIP & 8)) zn_ok = fnext < n_frames && load_frame_rp_fast<RING>(x, Lv, rs, a.hop, fnext * fmul, lane, zn);
                 }
                 // ---- pass 2: radix-8 over n1 (lane = 8 n1 + n2); this lane: n2 = lane & 7, digit k0 = fft_lane_k0(lane) ----
                 if (!(KM_MEL_XCHG & 1) && !(KM_MEL_SKIP & 2)) {
@@ -957,7 +973,7 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
         for (int i = 0; i < NGW; ++i) my_desc[i] = my_desc_p[4 * i];
         if (tid == 0) {
             if (req == ctr_last) a.chunk_ctr[b] = 0u;
-            sched[0] = (int)(req + 2u * gridDim.x);
+            sched[0] = (int)(req + 2u * gx);
         }
         __syncthreads();
         KM_STAMP(9);                                                      // waiting at the barrier ahead of the mel stage
@@ -977,13 +993,14 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
             // busy cycles.  No cross-lane reduction, no per-filter descriptor traffic.  Results go straight to HBM (the 80 filters of a
             // frame are written by 8 waves within one chunk, L2 merges the lines).
             const int slot = mel_slot_of_lane(lane), flm = mel_frame_of_lane(lane);
-            const bool fvalid = f0 + flm < a.n_frames;
+            const bool fvalid = f0 + flm < n_frames;
             const float4* prow = reinterpret_cast<const float4*>(pw + flm * NFS);
             const float4* wbase = reinterpret_cast<const float4*>(fbw);
-            float* dst = a.melpow + ((int64_t)b * a.n_frames + f0 + flm) * a.n_mels + slot;
+            float* dst = TAB ? (b == 0 ? a.melpow : a.tab_edge + (int64_t)(b - 1) * 2 * a.n_mels) + (int64_t)(f0 + flm) * a.n_mels + slot
+                             : a.melpow + ((int64_t)b * n_frames + f0 + flm) * a.n_mels + slot;
             // PACK: filter m of frame f is element (m, f) of the window's packed rows -- the 16 frame lanes of a filter write 64
             // contiguous bytes -- and the last three computed frames are stored a second time behind the T long ones
-            const int fr = f0 + flm, qs = a.n_frames >= 3 ? fr - (a.n_frames - 3) : fr;
+            const int fr = f0 + flm, qs = n_frames >= 3 ? fr - (n_frames - 3) : fr;
             const bool st_long = fvalid && fr < a.pack_T, st_short = fvalid && qs >= 0 && qs < 3;
             float* dst_long = nullptr; float* dst_short = nullptr;
             if constexpr (PACK) {
@@ -1058,12 +1075,12 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
                 store_mel(my_gid[i], r);
             }
 #endif
-            if (a.frame_max) {                                             // this wave's filters of frame f0 + flm
+            if (!TAB && a.frame_max) {                                     // this wave's filters of frame f0 + flm
                 float fall = fmx;
 #pragma unroll
                 for (int s2 = 0; s2 < 4; ++s2) fall = fmaxf(fall, __shfl(fmx, mel_lane_of(s2, flm)));
                 fmx = fall;
-                if (slot == 0 && fvalid) atomicMax(a.frame_max + (int64_t)b * a.n_frames + f0 + flm, __float_as_uint(fmx));
+                if (slot == 0 && fvalid) atomicMax(a.frame_max + (int64_t)b * n_frames + f0 + flm, __float_as_uint(fmx));
             }
         }
         if (KM_MEL_PRIO) __builtin_amdgcn_s_setprio(0);
@@ -1088,7 +1105,7 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
     for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
     if (lane == 0) redmax[wave] = vmax;
     __syncthreads();
-    if (tid == 0 && !a.frame_max) {
+    if (!TAB && tid == 0 && !a.frame_max) {      // (TAB: train_clip_pack_kernel takes the window maxima from the images)
         float mx = redmax[0];
 #pragma unroll
         for (int w = 1; w < WAVES; ++w) mx = fmaxf(mx, redmax[w]);
@@ -1294,6 +1311,7 @@ int launch_mel_power(Context* c, MelPlan* p, const float* audio, int64_t B, int6
     a.melpow = c->ws_melpow; a.melmax = c->ws_melmax;
     a.frame_mul = 1; a.frame_max = nullptr; a.chunk_ctr = c->ws_chunkctr;
     a.pack_xt = nullptr; a.pack_T = a.pack_KP = 0; a.pack_amin = m.amin;
+    a.tab_start = nullptr; a.tab_edge = nullptr; a.tab_min = a.tab_T = a.tab_span_wgs = 0;
     if (pack) {
         if (!mel_packs(c, p, n_frames, pack->T) || seq || ring_start || wins_per_clip > 1 || pack->KP < pack->T + 3)
             return fail(KM_ERR_UNSUPPORTED, "launch_mel_power: packed output requested for an unsupported configuration");
@@ -1330,6 +1348,165 @@ int launch_mel_power(Context* c, MelPlan* p, const float* audio, int64_t B, int6
     else if (m.n_fft == 1024) hipLaunchKernelGGL((mel_power_kernel<1024, true>), grid, dim3(256), lds, st, a);
     else if (!ring_start) hipLaunchKernelGGL((mel_power_kernel<512, false>), grid, dim3(256), lds, st, a);
     else hipLaunchKernelGGL((mel_power_kernel<512, true>), grid, dim3(256), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Training from a resident clip (km_train_step_clip).  The windows of a dense batch start at multiples of the hop inside ONE
+// clip, so with hop >= n_fft / 2 frame f = 1 .. T - 1 of a window IS clip frame start + f; only frames 0 and T see the window's
+// zero padding (km_sequence_forward uses the same fact for inference).  Two launches replace the per-window front end:
+//   launch_mel_clip_span    mel_power_rp_kernel<false, false, true>: the span's frames once + 2 boundary frames per window
+//   launch_train_clip_pack  train_clip_pack_kernel: per window the packed, transposed rows the PACK instantiation would have
+//                           written (same db10 of the same powers: bit-identical) and the window maximum
+// ---------------------------------------------------------------------------------------------------------
+struct ClipPackArgs {
+    const float* span;      // (n_span, n_mels): row r = clip frame min_start + r
+    int edge_off;           // the edge image (B, 2, n_mels: frames 0 and T of every window) begins at span + edge_off
+    const int* start;       // (B) start frames
+    int min_start, n_span, T, KP, n_mels, row_stride, tile_cols;
+    float amin;
+    float* xt;              // (B, n_mels, KP)
+    unsigned* melmax;       // (B) float bits
+};
+namespace clippack {
+constexpr int NT = 1024, MAXI = 24, LDS_FLOATS = 24 * 1024;      // a thread holds up to MAXI powers of a tile; 96 KB of LDS
+// LDS row stride of the [column][mel] tile: 18 (mod 64) dwords, so that the transposed read of a wave -- lanes 0-31 are 32
+// columns of mel m, lanes 32-63 the same columns of mel m + 1 -- meets 64 different banks (18 c mod 64 are the 32 even banks)
+inline int row_stride(int n_mels) { return (n_mels + 45) / 64 * 64 + 18; }
+// columns per tile: a multiple of 32 within the register and LDS budgets (the C3 shape: all KP = 288 columns at once)
+inline int tile_cols(int n_mels, int KP) {
+    int c = NT * MAXI / n_mels;
+    const int l = LDS_FLOATS / row_stride(n_mels);
+    c = (c < l ? c : l) / 32 * 32;
+    return c < KP ? c : KP;
+}
+}  // namespace clippack
+
+// One 1024-thread workgroup per window.  Column j < T of the window's packed rows is window frame j, columns T .. T + 2 are
+// frames T - 2 .. T (the last three computed frames, as the PACK store of mel_power_rp_kernel places them), the rest up to KP is
+// zero.  A tile of columns is read frame-major (n_mels contiguous floats per frame: the span rows of consecutive frames are
+// one contiguous run) with every load in flight before the first is used, and written mel-major (32 contiguous floats per
+// half-wave), transposed through LDS.  The workgroup sees all T + 1 frames, so the window maximum is a plain store: no atomics
+// (one atomicMax per wave of a (tile, window) grid sent 2304 of them to two cache lines at 64 windows: 16.7 us for the
+// kernel), no zeroed slots needed.
+__global__ __launch_bounds__(clippack::NT) void train_clip_pack_kernel(ClipPackArgs a) {
+    using namespace clippack;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ float redmax[NT / 64];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    int s = a.start[b];
+    s = s < 0 ? 0 : s;
+    const int row0 = s - a.min_start;
+    const int e0 = a.edge_off + b * 2 * a.n_mels;               // 32-bit offsets from a.span: one address register per load
+    const int dq = NT / a.n_mels, dr = NT % a.n_mels;
+    const int cl0 = tid / a.n_mels, m0 = tid - cl0 * a.n_mels;
+    float vmax = 0.f;
+    for (int c0 = 0; c0 < a.KP; c0 += a.tile_cols) {
+        const int ncol = a.KP - c0 < a.tile_cols ? a.KP - c0 : a.tile_cols;
+        const int total = ncol * a.n_mels;
+        float pwv[MAXI];
+        int cl = cl0, m = m0;
+#pragma unroll
+        for (int k = 0; k < MAXI; ++k) {
+            const int col = c0 + cl;
+            const int f = col < a.T ? col : col - 2;
+            pwv[k] = -1.f;                                     // no frame behind this column (powers are >= 0)
+            if (tid + k * NT < total && col < a.T + 3) {
+                int r = row0 + f;                              // inside the span whenever min_start / n_span are the batch's extremes
+                r = r < 0 ? 0 : (r >= a.n_span ? a.n_span - 1 : r);
+                pwv[k] = a.span[(f == 0 ? e0 : (f == a.T ? e0 + a.n_mels : r * a.n_mels)) + m];
+            }
+            cl += dq; m += dr;
+            if (m >= a.n_mels) { m -= a.n_mels; ++cl; }
+        }
+        if (c0 > 0) __syncthreads();                           // the previous tile has been written out
+        cl = cl0; m = m0;
+#pragma unroll
+        for (int k = 0; k < MAXI; ++k) {
+            if (tid + k * NT < total) {
+                const float pw = pwv[k];
+                vmax = fmaxf(vmax, pw);
+                smem[cl * a.row_stride + m] = pw >= 0.f ? db10(pw, a.amin) : 0.f;
+            }
+            cl += dq; m += dr;
+            if (m >= a.n_mels) { m -= a.n_mels; ++cl; }
+        }
+        __syncthreads();
+        // half-wave h of the workgroup owns mel rows h, h + 32, ...; its 32 lanes walk the tile's columns 32 at a time
+        const int lane32 = tid & 31;
+        for (int m2 = tid >> 5; m2 < a.n_mels; m2 += NT / 32) {
+            float* dst = a.xt + ((int64_t)b * a.n_mels + m2) * a.KP + c0;
+            for (int c = lane32; c < ncol; c += 32) dst[c] = smem[c * a.row_stride + m2];
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
+    if ((tid & 63) == 0) redmax[tid >> 6] = vmax;
+    __syncthreads();
+    if (tid == 0) {
+        float mx = redmax[0];
+#pragma unroll
+        for (int w = 1; w < NT / 64; ++w) mx = fmaxf(mx, redmax[w]);
+        a.melmax[b] = __float_as_uint(mx);                     // the maximum over all T + 1 frames of the window
+    }
+}
+
+static void mel_plan_args(MelPlan* p, MelArgs& a) {
+    const km_mel_config& m = p->cfg;
+    a.hop = m.hop_length; a.pad_mode = m.pad_mode;
+    a.n_mels = m.n_mels; a.window = p->d_window; a.twiddle = reinterpret_cast<const float2*>(p->d_twiddle);
+    a.fb_start = p->d_fb_start; a.fb_count = p->d_fb_count; a.fb_offset = p->d_fb_offset; a.fb_weight = p->d_fb_weight;
+    a.fb_nnz = (int)p->fb_weight.size();
+    a.fbg_gid = p->d_fbg_gid; a.fbg_desc = p->d_fbg_desc; a.fbg_weight = p->d_fbg_weight; a.fbg_nw = (int)p->fbg_weight.size();
+}
+
+int launch_mel_clip_span(Context* c, MelPlan* p, const float* clip, int64_t clip_len, const int* start_frames, int64_t B,
+                         int min_start, int64_t n_span, int T, float* span, float* edge, void* stream) {
+    const km_mel_config& m = p->cfg;
+    if (!(m.n_fft == 1024 && !c->opt.mel_two_frame && p->d_fbg_gid) || m.pad_mode != KM_PAD_CONSTANT || 2 * m.hop_length < m.n_fft)
+        return fail(KM_ERR_UNSUPPORTED, "clip-span front end: needs the 1024-point kernel, constant padding and hop >= n_fft / 2");
+    if (!p->uploaded) return fail(KM_ERR_NOT_FINALIZED, "mel plan not uploaded (km_finalize / km_reserve first)");
+    if (!clip || !start_frames || !span || !edge || B <= 0 || n_span < T + 1 || min_start < 0)
+        return fail(KM_ERR_INVALID_ARG, "clip-span front end: bad argument");
+    static PerDeviceOnce once;
+    if (once.first(c->device))
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_power_rp_kernel<false, false, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (int rc = ensure_chunk_counters(c, B + 1, stream)) return rc;
+    MelArgs a{};
+    mel_plan_args(p, a);
+    a.audio = clip; a.L = 0; a.clip_len = clip_len; a.win_step = 0; a.win0 = 0; a.wins_per_clip = 1; a.n_frames = (int)n_span;
+    a.ring_start = nullptr; a.ready = nullptr;
+    a.melpow = span; a.melmax = nullptr; a.frame_mul = 1; a.frame_max = nullptr; a.chunk_ctr = c->ws_chunkctr;
+    a.pack_xt = nullptr; a.pack_T = a.pack_KP = 0; a.pack_amin = m.amin;
+    a.tab_start = start_frames; a.tab_edge = edge; a.tab_min = min_start; a.tab_T = T;
+    // one workgroup per 16-frame chunk of the span (a dense batch: 17 at 8 windows, 21 at 64), persistent beyond 512
+    const int n_chunks = (int)((n_span + mel::FPB - 1) / mel::FPB);
+    a.tab_span_wgs = n_chunks < 512 ? n_chunks : 512;
+    hipLaunchKernelGGL((mel_power_rp_kernel<false, false, true>), dim3((unsigned)(a.tab_span_wgs + B)), dim3(melrp::NT),
+                       melrp_lds_bytes(a.fbg_nw), (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+int launch_train_clip_pack(Context* c, MelPlan* p, const float* span, const float* edge, const int* start_frames, int64_t B,
+                           int min_start, int64_t n_span, int T, int KP, float* xt, void* stream) {
+    const km_mel_config& m = p->cfg;
+    if (!span || !edge || !start_frames || !xt || B <= 0 || B > 65535 || T < 2 || KP < T + 3 || n_span < T + 1 || m.n_mels > 128 || m.n_mels < 1)
+        return fail(KM_ERR_INVALID_ARG, "clip pack: bad argument");
+    ClipPackArgs a;
+    if (edge - span < 0 || edge - span + (int64_t)2 * B * m.n_mels >= (1ll << 31))
+        return fail(KM_ERR_INVALID_ARG, "clip pack: the edge image has to follow the span image in one allocation");
+    a.span = span; a.edge_off = (int)(edge - span); a.start = start_frames; a.min_start = min_start; a.n_span = (int)n_span; a.T = T; a.KP = KP;
+    a.n_mels = m.n_mels; a.row_stride = clippack::row_stride(m.n_mels); a.tile_cols = clippack::tile_cols(m.n_mels, KP);
+    a.amin = m.amin; a.xt = xt; a.melmax = c->ws_melmax;
+    const size_t lds = (size_t)a.tile_cols * a.row_stride * sizeof(float);
+    static PerDeviceOnce once;
+    if (once.first(c->device))
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&train_clip_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(clippack::LDS_FLOATS * sizeof(float))));
+    hipLaunchKernelGGL(train_clip_pack_kernel, dim3((unsigned)B), dim3(clippack::NT), lds, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

@@ -76,7 +76,11 @@ class _Clip:
 class SequentialKoeMorphDataset:
     def __init__(self, data_dir: Union[str, Path], window_frames: int = 256, stride_frames: int = 1,
                  sample_rate: int = 16000, target_fps: int = 30, shuffle_files: bool = True, loop_dataset: bool = True,
-                 max_files: Optional[int] = None, batch_size: int = 8, device: Union[str, torch.device] = "cuda"):
+                 max_files: Optional[int] = None, batch_size: int = 8, device: Union[str, torch.device] = "cuda",
+                 resident_windows: bool = False):
+        """``resident_windows``: iterate ``index_batch`` instead of ``gather`` -- batches name their windows inside the resident
+        clip (for ``Trainer.step_clip``) instead of carrying a copy of their audio."""
+        self.resident_windows = resident_windows
         self.data_dir = Path(data_dir)
         self.window_frames, self.stride_frames = window_frames, stride_frames
         self.sample_rate, self.target_fps = sample_rate, target_fps
@@ -157,6 +161,24 @@ class SequentialKoeMorphDataset:
                 "file_indices": torch.full((B,), file_idx, dtype=torch.int64), "window_indices": wi.to(torch.int64),
                 "start_frames": (wi * self.stride_frames).to(torch.int64), "file_names": [c.name] * B}
 
+    def index_batch(self, file_idx: int, window_indices) -> Dict[str, object]:
+        """``gather`` without the audio copy: ``clip_audio`` is the resident clip itself (no copy), ``start_frames_dev`` the
+        windows' start frames as a device int32 tensor (``start_frames`` is its host copy: the step takes the extremes from it);
+        labels and targets are gathered as before."""
+        c = self.clip(file_idx)
+        wi = torch.as_tensor(window_indices, dtype=torch.int32)
+        starts = (wi * self.stride_frames).to(self.device)
+        B = int(wi.numel())
+        bs = torch.empty(B, self.window_frames, c.labels.shape[1], device=self.device)
+        target = torch.empty(B, c.labels.shape[1], device=self.device)
+        with torch.cuda.device(self.device):
+            check(self._lib.km_gather_windows(None, 0, starts.data_ptr(), B, self.hop_length, self.window_samples, None,
+                                              c.labels.data_ptr(), c.labels.shape[0], self.window_frames, c.labels.shape[1],
+                                              bs.data_ptr(), target.data_ptr(), self._stream()))
+        return {"clip_audio": c.audio, "start_frames_dev": starts, "blendshapes": bs, "target": target,
+                "file_indices": torch.full((B,), file_idx, dtype=torch.int64), "window_indices": wi.to(torch.int64),
+                "start_frames": (wi * self.stride_frames).to(torch.int64), "file_names": [c.name] * B}
+
     # ---- iteration: the reference's order (files, then windows in time order), already batched --------------
     def __iter__(self) -> Iterator[Dict[str, object]]:
         while True:
@@ -167,7 +189,8 @@ class SequentialKoeMorphDataset:
                 n = self.clip(fi).num_windows
                 # a window is valid only when both slices are full (:191); with aligned lengths that is every i < n
                 for w0 in range(0, n, self.batch_size):
-                    yield self.gather(fi, list(range(w0, min(n, w0 + self.batch_size))))
+                    make = self.index_batch if self.resident_windows else self.gather
+                    yield make(fi, list(range(w0, min(n, w0 + self.batch_size))))
             if not self.loop_dataset:
                 break
 

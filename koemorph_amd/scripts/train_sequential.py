@@ -38,14 +38,20 @@ class SequentialTrainer:
     def __init__(self, engine: Engine, train_data: SequentialKoeMorphDataset, val_data: Optional[SequentialKoeMorphDataset] = None,
                  device: str = "cuda", learning_rate: float = 1e-4, weight_decay: float = 1e-5, gradient_clip: float = 1.0,
                  mse_weight: float = 1.0, l1_weight: float = 0.0, extra_loss_terms: Optional[Dict[str, float]] = None,
-                 emotion_provider: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, dropout: float = 0.1, seed: int = 0):
-        """``dropout``: the reference trains under ``model.train()`` (src/train_sequential.py:118) on a model built with
+                 emotion_provider: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, dropout: float = 0.1, seed: int = 0,
+                 from_clip: bool = False):
+        """``from_clip``: batches that name their windows inside the resident clip (``resident_windows=True`` data sets) go
+        through ``Trainer.step_clip`` -- no window copy, shared STFT frames; same losses and weights, bit for bit.  An
+        ``emotion_provider`` is handed window audio, so with one installed the trainer stays on the gathered path.
+        ``dropout``: the reference trains under ``model.train()`` (src/train_sequential.py:118) on a model built with
         dropout 0.1 (simplified_dual_stream_model.py:155): the attention weights of both streams and the decoder's hidden
         layer are dropped per step; ``validate()`` runs the eval-mode inference kernels.  Every rank draws its own masks
         (generator seed = ``seed`` + rank); the generator's step counter is part of the checkpoint."""
         self.engine, self.device = engine, torch.device(device)
         self.train_data, self.val_data = train_data, val_data
         self.emotion_provider = emotion_provider
+        self.from_clip = from_clip
+        self._from_clip_logged = False
         self.rank, self.world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) \
             if torch.distributed.is_initialized() else (0, 1)
         self.trainer = Trainer(engine, max_windows=train_data.batch_size, lr=learning_rate, weight_decay=weight_decay,
@@ -68,9 +74,24 @@ class SequentialTrainer:
 
     def _my_share(self, batch):
         """This rank's contiguous share of the batch (windows shard embarrassingly; only the gradient is reduced)."""
-        B = batch["audio"].shape[0]
+        B = batch["target"].shape[0]
         lo, hi = parallel.shard_range(B, self.rank, self.world)
-        return {k: (v[lo:hi] if isinstance(v, (torch.Tensor, list)) else v) for k, v in batch.items()}, hi - lo
+        return {k: (v[lo:hi] if isinstance(v, (torch.Tensor, list)) and k != "clip_audio" else v) for k, v in batch.items()}, hi - lo
+
+    def _with_audio(self, batch):
+        """A resident-window batch with its windows gathered (validation, an emotion provider): the keys ``gather`` gives."""
+        if "audio" in batch:
+            return batch
+        ds = self.train_data
+        B = batch["target"].shape[0]
+        audio = torch.empty(B, ds.window_samples, device=self.device)
+        clip = batch["clip_audio"]
+        from .._lib import check
+        with torch.cuda.device(self.device):
+            check(ds._lib.km_gather_windows(clip.data_ptr(), clip.shape[0], batch["start_frames_dev"].data_ptr(), B, ds.hop_length,
+                                            ds.window_samples, audio.data_ptr(), None, 0, 0, 0, None, None,
+                                            torch.cuda.current_stream(self.device).cuda_stream))
+        return {**batch, "audio": audio}
 
     # ---- reference API ----------------------------------------------------------------------------------
     def train_epoch(self, metrics: bool = False) -> Dict[str, float]:
@@ -86,14 +107,24 @@ class SequentialTrainer:
                 self.current_file_idx = file_idx
                 self.trainer.reset_temporal_state()
             share, nb = self._my_share(batch)
-            B_global = batch["audio"].shape[0]
+            B_global = batch["target"].shape[0]
             if nb == 0:                                      # fewer windows than ranks: weight 0 in the global mean
                 self.trainer.flat_grad.zero_()
                 self.trainer.optimizer_step(weight=0.0)
                 continue
             # every rank's gradient is weighted by its share of the GLOBAL batch (shares differ by one window when the
             # batch does not divide, and the last batch of a clip is short): the sum is the full-batch gradient
-            loss = self.trainer.step(share["audio"], self._emotion(share), share["target"], global_batch=B_global)
+            if "clip_audio" in share and self.from_clip and self.emotion_provider is None:
+                sf = share["start_frames"]
+                loss = self.trainer.step_clip(share["clip_audio"], share["start_frames_dev"], self._emotion(share), share["target"],
+                                              global_batch=B_global, extremes=(int(sf.min()), int(sf.max())))
+            else:
+                if "clip_audio" in share and not self._from_clip_logged:
+                    self._from_clip_logged = True
+                    logger.info("resident-window batches are gathered before the step (%s)",
+                                "the emotion provider reads window audio" if self.emotion_provider is not None else "from_clip is off")
+                share = self._with_audio(share)
+                loss = self.trainer.step(share["audio"], self._emotion(share), share["target"], global_batch=B_global)
             if bm is not None:
                 bm.update(self.trainer.out[:nb], share["target"])
             total += float(loss.item())
@@ -119,6 +150,7 @@ class SequentialTrainer:
         current = None
         with torch.no_grad():
             for batch in self.val_data:
+                batch = self._with_audio(batch)
                 file_idx = int(batch["file_indices"][0])
                 B = batch["audio"].shape[0]
                 first = current != file_idx or state is None or state.shape[0] != B
@@ -193,6 +225,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--checkpoint_dir", default="checkpoints")
     p.add_argument("--resume", help="checkpoint to resume from")
     p.add_argument("--max_files", type=int)
+    p.add_argument("--resident-clip", dest="resident_clip", action="store_true",
+                   help="train from the clips resident in GPU memory (Trainer.step_clip): no window copies, the STFT frames the "
+                        "windows of a batch share are computed once; same losses and weights")
     p.add_argument("--metrics", action="store_true", help="log mae / rmse / mean_correlation / f1_score of every epoch (BlendshapeMetrics)")
     return p
 
@@ -208,10 +243,11 @@ def main(argv=None):
     eng.finalize(device)
     kw = dict(window_frames=args.window_frames, stride_frames=args.stride_frames, shuffle_files=False, loop_dataset=False,
               batch_size=args.batch_size, device=device, max_files=args.max_files)
-    train = SequentialKoeMorphDataset(args.data_dir, **kw)
+    train = SequentialKoeMorphDataset(args.data_dir, resident_windows=args.resident_clip, **kw)
     val = SequentialKoeMorphDataset(args.val_dir, **kw) if args.val_dir else None
     st = SequentialTrainer(eng, train, val, device=device, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
-                           gradient_clip=args.gradient_clip, l1_weight=args.l1_weight, dropout=args.dropout, seed=args.seed)
+                           gradient_clip=args.gradient_clip, l1_weight=args.l1_weight, dropout=args.dropout, seed=args.seed,
+                           from_clip=args.resident_clip)
     if args.resume:
         st.load_checkpoint(args.resume)
     for _ in range(st.epoch, args.epochs):

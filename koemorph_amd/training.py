@@ -246,6 +246,104 @@ class Trainer:
         self._last_was_step = True
         return self.loss
 
+    # ---- the step from a clip resident in HBM (km_train_step_clip) -------------------------------------------------
+    def clip_supported(self) -> bool:
+        """km_train_clip_supported: the windows of a batch can share the clip's STFT frames on this engine."""
+        return bool(self._lib.km_train_clip_supported(self._h))
+
+    def _window_samples(self) -> int:
+        return self.engine.mel_sequence_length * self.engine.mel.hop_length
+
+    def _start_frames(self, start_frames, extremes):
+        """(device int32 tensor, min, max).  A host sequence / CPU tensor is uploaded and its extremes taken here; a device
+        tensor comes with ``extremes`` = (min, max) from the host copy its producer has (the window indices are Python ints in
+        the data set): nothing is read back from the device on the way to the launch."""
+        if isinstance(start_frames, torch.Tensor) and start_frames.is_cuda:
+            if extremes is None:
+                raise ValueError("device start frames need extremes=(min, max) from their host copy")
+            if start_frames.dtype != torch.int32 or not start_frames.is_contiguous():
+                raise ValueError("start_frames must be a contiguous int32 tensor")
+            return start_frames, int(extremes[0]), int(extremes[1])
+        host = np.ascontiguousarray(np.asarray(start_frames), np.int32).ravel()
+        lo, hi = (int(host.min()), int(host.max())) if extremes is None else (int(extremes[0]), int(extremes[1]))
+        return torch.from_numpy(host).to(self.device), lo, hi
+
+    def _gather_clip(self, clip, starts, B):
+        """The windows as km_gather_windows copies them, into a buffer kept across steps (unsupported shapes)."""
+        W = self._window_samples()
+        buf = getattr(self, "_clip_windows", None)
+        if buf is None or buf.shape[1] != W or buf.shape[0] < B:
+            buf = self._clip_windows = torch.empty(max(B, self.max_windows), W, device=self.device)
+        check(self._lib.km_gather_windows(_ptr(clip), clip.shape[0], _ptr(starts), B, self.engine.mel.hop_length, W, _ptr(buf),
+                                          None, 0, 0, 0, None, None, _stream_ptr(self.device)))
+        return buf[:B]
+
+    def forward_backward_clip(self, clip, start_frames, emotion, target, extremes=None):
+        """``forward_backward`` on the windows of ONE clip (a 1-D device tensor) that start at ``start_frames`` (in frames of
+        hop samples; any order, repeats allowed): same loss, output and gradient bits as gathering the windows first, without
+        the (B, window) copy and with the STFT frames the windows share computed once.  Where the engine's shape does not
+        allow that (``clip_supported()`` is False) the windows are gathered into a cached buffer and take the from-audio step."""
+        clip = clip.contiguous()
+        starts, lo, hi = self._start_frames(start_frames, extremes)
+        B = int(starts.numel())
+        self.engine.reserve(B, self._window_samples())
+        if not self.clip_supported():
+            return self.forward_backward(self._gather_clip(clip, starts, B), emotion, target)
+        st, first = self._ema_args(B)
+        check(self._lib.km_train_step_clip(self._h, _ptr(clip), clip.shape[0], _ptr(starts), B, lo, hi, _ptr(emotion.contiguous()),
+                                           _ptr(target.contiguous()), self.mse_weight, self.l1_weight, _ptr(self.flat_grad),
+                                           _ptr(self.loss), _ptr(self.out), st, first, _stream_ptr(self.device)))
+        self._last_was_step = True
+        return self.loss
+
+    def step_clip(self, clip, start_frames, emotion, target, global_batch: Optional[int] = None, extremes=None) -> torch.Tensor:
+        """``step`` from a resident clip: forward_backward_clip + all-reduce + clip + AdamW."""
+        self.forward_backward_clip(clip, start_frames, emotion, target, extremes)
+        B = int(start_frames.numel()) if isinstance(start_frames, torch.Tensor) else len(start_frames)
+        self.optimizer_step(None if global_batch is None else B / float(global_batch))
+        return self.loss
+
+    def capture_clip(self, clip, B: int, min_start: int, max_start: int) -> None:
+        """Record ``forward_backward_clip`` on ``clip`` with static start-frame / emotion / target buffers into a hipGraph.
+        The extremes are host arguments of the launches, so they are part of the recording: the graph computes the span
+        ``min_start .. max_start + T`` of the clip on every replay and is right for any B start frames inside
+        [min_start, max_start] (``replay_clip`` checks that on the host).  Call after one eager clip step with this batch size
+        and a span at least as wide (EMA first-call branch; the span image may have to grow, which a capture cannot do)."""
+        dev = self.device
+        self._gc_clip = clip.contiguous()
+        self._gc_range = (int(min_start), int(max_start))
+        self._gc_starts = torch.full((B,), int(min_start), dtype=torch.int32, device=dev)
+        self._gc_emo = torch.zeros(B, self.engine.emotion_dim, device=dev)
+        self._gc_target = torch.zeros(B, 52, device=dev)
+        self.engine.reserve(B, self._window_samples())
+        if self.use_smoothing and self._ema_batch != B:
+            raise RuntimeError("run one eager step with this batch size before capture_clip()")
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.forward_backward_clip(self._gc_clip, self._gc_starts, self._gc_emo, self._gc_target, extremes=self._gc_range)
+        self._gc_graph = g
+        self._last_was_step = False      # see capture(): no side-stream overlap behind a replay
+
+    def replay_clip(self, start_frames, emotion, target) -> torch.Tensor:
+        """Replay the recorded clip step on new start frames (a host sequence: they are checked against the recorded span)."""
+        host = np.ascontiguousarray(np.asarray(start_frames), np.int32).ravel()
+        lo, hi = self._gc_range
+        if host.size != self._gc_starts.numel() or int(host.min()) < lo or int(host.max()) > hi:
+            raise ValueError(f"replay_clip: {host.size} start frames in [{int(host.min())}, {int(host.max())}], recorded "
+                             f"{self._gc_starts.numel()} in [{lo}, {hi}]")
+        self._gc_starts.copy_(torch.from_numpy(host), non_blocking=False)
+        self._gc_emo.copy_(emotion, non_blocking=True)
+        self._gc_target.copy_(target, non_blocking=True)
+        self._gc_graph.replay()
+        self._last_was_step = False
+        return self.loss
+
+    def step_clip_graph(self, start_frames, emotion, target, weight: Optional[float] = None) -> torch.Tensor:
+        self.replay_clip(start_frames, emotion, target)
+        self.optimizer_step(weight)
+        return self.loss
+
     def _allreduce_two_piece(self, weight: Optional[float], overlap: bool) -> None:
         """The step's one gradient exchange, issued as two pieces: floats [0, E) of the bucket (83 %: everything but the
         tensors the backward pass finishes last, km_train_grad_split) are reduced on a side stream that waits only for
