@@ -509,7 +509,7 @@ int km_metrics_compute(void* acc, float* out_dev, void* stream);
  * this path: every switch selects between two implementations of the SAME arithmetic, for A/B timing and for the
  * tests that pin one path against the other).  Names: "core_split" (0 | 3 | 6, experimental split-bf16 core),
  * "seq_per_window", "generic_staged", "mel_two_frame", "emotion_separate", "no_ln_fusion", "no_db_fusion",
- * "no_score_fusion", "no_out_fusion", "no_v_fusion", "train_chain" (training step as the launch-per-op chain),
+ * "no_score_fusion", "no_out_fusion", "no_v_fusion",
  * "kmm_no_fuse" (km_koemorph_forward as the launch-per-step GEMM chain even at the width of the two fused kernels),
  * "legacy_no_enc_fusion" / "legacy_no_attn_fusion" / "legacy_no_tail_fusion" (km_legacy_forward's three fused kernels back to GEMM-chain launches), "train_op_per_launch" (timing aid:
  * every operation of the training program as its own launch), "train_bm32_below", "train_tail_groups", "train_split_min_k",

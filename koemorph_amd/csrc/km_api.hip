@@ -217,12 +217,11 @@ int km_core_forward_z(km_handle h, const float* mel_dev, int64_t B, int64_t T_in
 }
 
 static int free_train(Context* c) {
-    void* ptrs[] = {c->tr_params, c->tr_m, c->tr_v, c->tr_act, c->tr_q, c->tr_dq, c->tr_part, c->tr_gnorm, c->tr_loss, c->tr_red, c->tr_steps};
+    void* ptrs[] = {c->tr_params, c->tr_m, c->tr_v, c->tr_part, c->tr_gnorm, c->tr_loss, c->tr_steps};
     for (void* p : ptrs)
         if (p) HIP_TRY(hipFree(p));
-    c->tr_params = c->tr_m = c->tr_v = c->tr_act = c->tr_q = c->tr_dq = c->tr_part = c->tr_gnorm = c->tr_loss = c->tr_red = nullptr;
+    c->tr_params = c->tr_m = c->tr_v = c->tr_part = c->tr_gnorm = c->tr_loss = nullptr;
     c->tr_steps = nullptr;
-    if (c->tr_red2) { HIP_TRY(hipFree(c->tr_red2)); c->tr_red2 = nullptr; }
     if (c->clip_span) { HIP_TRY(hipFree(c->clip_span)); c->clip_span = c->clip_edge = nullptr; c->clip_span_cap = c->clip_edge_cap = 0; }
     if (c->trp_act) { HIP_TRY(hipFree(c->trp_act)); c->trp_act = nullptr; c->trp_act_floats = 0; }
     if (c->trp_split) { HIP_TRY(hipFree(c->trp_split)); c->trp_split = nullptr; c->trp_split_floats = 0; }
@@ -231,9 +230,7 @@ static int free_train(Context* c) {
     if (c->trp_tail_ctr) { HIP_TRY(hipFree(c->trp_tail_ctr)); c->trp_tail_ctr = nullptr; }
     if (c->trp_masks) { HIP_TRY(hipFree(c->trp_masks)); c->trp_masks = nullptr; }
     if (c->trp_drop_ctr) { HIP_TRY(hipFree(c->trp_drop_ctr)); c->trp_drop_ctr = nullptr; }
-    if (c->tr_s2) { (void)hipStreamDestroy((hipStream_t)c->tr_s2); c->tr_s2 = nullptr; }
-    for (auto& e : c->tr_ev)
-        if (e) { (void)hipEventDestroy((hipEvent_t)e); e = nullptr; }
+    if (c->tr_early_ev) { (void)hipEventDestroy((hipEvent_t)c->tr_early_ev); c->tr_early_ev = nullptr; }
     c->tr_windows = 0;
     return KM_OK;
 }
@@ -260,7 +257,7 @@ static bool train_clip_ok(Context* c) {
     if (c->mel_plans.empty()) return false;
     MelPlan* p = c->mel_plans[0];
     const km_mel_config& m = p->cfg;
-    return !c->opt.train_chain && !c->opt.train_no_fe_pack && !c->opt.train_no_dma && mel_packs(c, p, c->T + 1, c->T) &&
+    return !c->opt.train_no_fe_pack && !c->opt.train_no_dma && mel_packs(c, p, c->T + 1, c->T) &&
            m.n_mels == c->NK && c->NK % 4 == 0 && m.pad_mode == KM_PAD_CONSTANT && 2 * m.hop_length >= m.n_fft;
 }
 
@@ -307,28 +304,18 @@ int km_train_init(km_handle h, int64_t max_windows, void* stream) {
     HIP_TRY(hipMemsetAsync(c->tr_params, 0, nb, (hipStream_t)stream));
     HIP_TRY(hipMemsetAsync(c->tr_m, 0, nb, (hipStream_t)stream));
     HIP_TRY(hipMemsetAsync(c->tr_v, 0, nb, (hipStream_t)stream));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_act), (size_t)max_windows * train_act_floats(c) * sizeof(float)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_q), (size_t)28 * c->d * sizeof(float)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_dq), (size_t)28 * c->d * sizeof(float)));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_part), 256 * sizeof(float)));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_gnorm), sizeof(float)));
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_loss), sizeof(float)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_red), (size_t)32 * 2 * 2 * c->d * sizeof(float)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_red2), (size_t)32 * 2 * 2 * c->d * sizeof(float)));
     {
-        hipStream_t s2;
-        HIP_TRY(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-        c->tr_s2 = s2;
-        for (auto& e : c->tr_ev) {
-            hipEvent_t ev;
-            HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            e = ev;
-        }
+        hipEvent_t ev;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        c->tr_early_ev = ev;
     }
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_steps), 2 * sizeof(int)));
     HIP_TRY(hipMemsetAsync(c->tr_steps, 0, 2 * sizeof(int), (hipStream_t)stream));
     c->tr_windows = max_windows;
-    {   // phased step (km_trainp.hip): packed input first, then a fixed part, then per-window activations; dropout masks
+    {   // the step's workspace (km_trainp.hip): packed input first, then a fixed part, then per-window activations; dropout masks
         int64_t fixed = 0;
         const int64_t per = trainp_act_floats(c, &fixed);
         const int64_t KP = trainp_kp(c);
@@ -376,12 +363,8 @@ int km_train_step(km_handle h, const float* mel_dev, int64_t B, int64_t T_in, co
     if (int rc = need_train(h, B)) return rc;
     if (!mel_dev || !mel_short_dev || !emotion_dev || !target_dev || !flat_grad_dev || !loss_dev || T_in <= 0)
         return fail(KM_ERR_INVALID_ARG, "km_train_step: bad argument");
-    if (!h->opt.train_chain)
-        return train_forward_backward_phased(h, mel_dev, B, T_in, mel_short_dev, nullptr, nullptr, emotion_dev, target_dev, mse_weight,
-                                             l1_weight, flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream);
-    if (h->tr_dropout_p > 0.f) return fail(KM_ERR_UNSUPPORTED, "the launch-per-op training chain has no dropout: unset train_chain");
-    return train_forward_backward(h, mel_dev, B, T_in, mel_short_dev, emotion_dev, target_dev, mse_weight, l1_weight,
-                                  flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream);
+    const TrainStepArgs sa{emotion_dev, target_dev, mse_weight, l1_weight, flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream};
+    return train_forward_backward(h, mel_dev, B, T_in, mel_short_dev, nullptr, nullptr, sa);
 }
 
 int km_train_step_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
@@ -394,25 +377,19 @@ int km_train_step_audio(km_handle h, const float* audio_dev, int64_t B, int64_t 
     const int64_t n_frames = 1 + L / c->cfg.mel.hop_length;
     if (B > c->ws_windows || n_frames > c->ws_frames)
         return fail(KM_ERR_WORKSPACE, "workspace too small for %lld windows x %lld samples: call km_reserve", (long long)B, (long long)L);
-    if (!c->opt.train_chain) {
-        // front end -> power-mel; phase 0 of the program converts and packs it into the encoder input (B, KP, n_mels) at the
-        // head of the phased workspace
-        // (round 4: the front end writes the packed dB input itself -- MelPack -- where it can; option train_no_fe_pack)
-        const bool fe_packs = !c->opt.train_no_fe_pack && !c->opt.train_no_dma &&
-                              mel_packs(c, c->mel_plans[0], n_frames, c->T) && c->mel_plans[0]->cfg.n_mels == c->NK;
-        const MelPack pack{c->trp_act, (int)c->T, (int)trainp_kp(c)};
-        if (int rc = launch_mel_power(c, c->mel_plans[0], audio_dev, B, L, stream, 0, 0, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                      fe_packs ? &pack : nullptr)) return rc;
-        c->melmax_dirty = true;      // until phase 1 / 2 has re-zeroed the maxima
-        const LogParams lp = plan_log_params(c->mel_plans[0]);
-        const TrainAudioSrc asrc{c->ws_melpow, c->ws_melmax, (int)n_frames, &lp, fe_packs};
-        return train_forward_backward_phased(c, nullptr, B, n_frames, nullptr, c->trp_act, &asrc, emotion_dev, target_dev, mse_weight,
-                                             l1_weight, flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream);
-    }
-    if (c->tr_dropout_p > 0.f) return fail(KM_ERR_UNSUPPORTED, "the launch-per-op training chain has no dropout: unset train_chain");
-    if (int rc = launch_mel(c, c->mel_plans[0], audio_dev, B, L, 0, c->ws_mel, c->ws_short, stream)) return rc;
-    return train_forward_backward(c, c->ws_mel, B, n_frames, c->ws_short, emotion_dev, target_dev, mse_weight, l1_weight,
-                                  flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream);
+    // front end -> power-mel; phase 0 of the program converts and packs it into the encoder input (B, KP, n_mels) at the
+    // head of the step's workspace
+    // (round 4: the front end writes the packed dB input itself -- MelPack -- where it can; option train_no_fe_pack)
+    const bool fe_packs = !c->opt.train_no_fe_pack && !c->opt.train_no_dma &&
+                          mel_packs(c, c->mel_plans[0], n_frames, c->T) && c->mel_plans[0]->cfg.n_mels == c->NK;
+    const MelPack pack{c->trp_act, (int)c->T, (int)trainp_kp(c)};
+    if (int rc = launch_mel_power(c, c->mel_plans[0], audio_dev, B, L, stream, 0, 0, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  fe_packs ? &pack : nullptr)) return rc;
+    c->melmax_dirty = true;      // until phase 1 / 2 has re-zeroed the maxima
+    const LogParams lp = plan_log_params(c->mel_plans[0]);
+    const TrainAudioSrc asrc{c->ws_melpow, c->ws_melmax, (int)n_frames, &lp, fe_packs};
+    const TrainStepArgs sa{emotion_dev, target_dev, mse_weight, l1_weight, flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream};
+    return train_forward_backward(c, nullptr, B, n_frames, nullptr, c->trp_act, &asrc, sa);
 }
 
 int km_train_clip_supported(km_handle h) {
@@ -458,8 +435,8 @@ int km_train_step_clip(km_handle h, const float* clip_dev, int64_t clip_len, con
     c->melmax_dirty = true;      // until phase 3 / 4 has re-zeroed the maxima
     const LogParams lp = plan_log_params(c->mel_plans[0]);
     const TrainAudioSrc asrc{c->ws_melpow, c->ws_melmax, (int)(T + 1), &lp, true};
-    return train_forward_backward_phased(c, nullptr, B, T + 1, nullptr, c->trp_act, &asrc, emotion_dev, target_dev, mse_weight,
-                                         l1_weight, flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream);
+    const TrainStepArgs sa{emotion_dev, target_dev, mse_weight, l1_weight, flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream};
+    return train_forward_backward(c, nullptr, B, T + 1, nullptr, c->trp_act, &asrc, sa);
 }
 
 int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev, void* stream) {
@@ -474,14 +451,14 @@ int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_
 int km_train_grad_split(km_handle h, int64_t* early_floats) {
     if (int rc = need_train(h, 1)) return rc;
     if (!early_floats) return fail(KM_ERR_INVALID_ARG, "km_train_grad_split: NULL argument");
-    *early_floats = h->opt.train_chain ? h->tr_nparams : h->tr_early;      // the chain finishes everything at its last join
+    *early_floats = h->tr_early;
     return KM_OK;
 }
 
 int km_train_wait_early(km_handle h, void* stream) {
     if (int rc = need_train(h, 1)) return rc;
-    if (!h->tr_early_recorded) return fail(KM_ERR_NOT_READY, "km_train_wait_early: no phased training step has run yet");
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)h->tr_ev[0], 0));
+    if (!h->tr_early_recorded) return fail(KM_ERR_NOT_READY, "km_train_wait_early: no training step has run yet");
+    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)h->tr_early_ev, 0));
     return KM_OK;
 }
 

@@ -76,9 +76,7 @@ struct Options {
     int legacy_no_enc_fusion = 0;  // 1: SimplifiedKoeMorphModel audio encoder + key / value projections as four GEMM launches (A/B, tests)
     int legacy_no_attn_fusion = 0; // 1: SimplifiedKoeMorphModel attention as two batched strided products + a row softmax (A/B, tests)
     int kmm_no_fuse = 0;           // 1: KoeMorphModel as the launch-per-step chain even at the fused kernels' width (A/B, tests)
-    int train_chain = 0;           // 1: training step as the round-1 launch-per-op chain (A/B reference; no dropout)
-    int train_no_split = 0;        // 1: no split-K of the long gradient products of the phased training step (A/B)
-    int train_dwce_parts = 0;      // > 0: partial sums of the channel-encoder gradient per step (a divisor of the batch; A/B)
+    int train_no_split = 0;        // 1: no split-K of the long gradient products of the training step (A/B)
     int train_split_min_k = 0;     // > 0: split gradient products longer than this many rows into chains of about this length (A/B; default 1024 / 640)
     int train_alone_max = 0;       // > 0: a phase of up to this many workgroups gives its 32-row LDS-DMA tiles the 8-stage ring (default 256)
     int train_no_dy_split = 0;     // 1: dY = dKV Wkv as one product at every batch size (A/B of the two K halves summed by the LayerNorm backward); 2: two halves at every batch size (measured: 16 windows 0.1401 -> 0.1422 ms, 64: 0.2299 -> 0.2327)
@@ -155,18 +153,17 @@ struct Context {
     int64_t stream_out_frames = 0;
     // training state (km_train_*): flat fp32 master parameters + AdamW moments on the device, in state-dict order
     int64_t tr_nparams = 0, tr_windows = 0;
-    int64_t tr_early = 0;            // floats [0, tr_early) of the gradient bucket are final when tr_ev[0] fires (phased step)
+    int64_t tr_early = 0;            // floats [0, tr_early) of the gradient bucket are final when tr_early_ev fires
+    void* tr_early_ev = nullptr;     // hipEvent_t, recorded by the step after the last phase that writes an early gradient
     bool tr_early_recorded = false;
     std::map<std::string, int64_t> tr_offset;
     float* tr_params = nullptr; float* tr_m = nullptr; float* tr_v = nullptr;
     float* trp_wcep = nullptr;     // (d, KP) the channel encoder weight with rows padded to KP floats (zeros): written with tr_params (upload, AdamW)
-    float* tr_act = nullptr; float* tr_q = nullptr; float* tr_dq = nullptr; float* tr_part = nullptr; float* tr_gnorm = nullptr;
-    float* tr_loss = nullptr;
-    float* tr_red = nullptr;         // split-reduction partials
+    float* tr_part = nullptr; float* tr_gnorm = nullptr; float* tr_loss = nullptr;
     int* tr_steps = nullptr;         // device-side AdamW step counters (graph replay safe)
     bool tr_alpha_live = false;      // smoothing_alpha was in the last step's graph (see adamw_kernel)
     km_loss_config tr_loss_cfg{};    // extra KoeMorphLoss terms (all weights 0 = off)
-    // phased training step (km_trainp.hip): its own activation workspace, dropout masks and per-step mask counter
+    // training step (km_trainp.hip): activation workspace, dropout masks and per-step mask counter
     float* trp_act = nullptr; int64_t trp_act_floats = 0;
     float* trp_split = nullptr; int64_t trp_split_floats = 0;   // partial outputs of the split-K gradient products of one step
     float* trp_tail_part = nullptr; unsigned* trp_tail_ctr = nullptr;   // per-workgroup sums of the loss tail + its arrival counter
@@ -175,8 +172,6 @@ struct Context {
     float tr_dropout_p = 0.f;        // training-mode dropout probability (0 = eval-mode arithmetic)
     int tr_dropout_mode = 0;         // 0: masks drawn per step (Philox), 1: masks supplied by the caller (km_train_set_dropout_masks)
     unsigned long long tr_dropout_seed = 0;
-    // side stream of the training step (emotion stream + decoder weight gradients run beside the mel chain)
-    void* tr_s2 = nullptr; void* tr_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float* tr_red2 = nullptr;
     // shared-frame sequence mode buffers (grow-only, allocated by km_sequence_forward)
     float* seq_pow = nullptr; unsigned* seq_fmax = nullptr; float* seq_edge = nullptr; unsigned* seq_emax = nullptr;
     int64_t seq_pow_cap = 0, seq_edge_cap = 0;
@@ -226,10 +221,6 @@ int launch_ema_scan(Context* c, float* x, int64_t B, int64_t N, void* stream);
 int launch_smooth(Context* c, float* x, float* state, int64_t B, int first, void* stream);
 
 // km_train.hip
-int64_t train_act_floats(Context* c);
-int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in, const float* mel_short, const float* emo,
-                           const float* target, float mse_w, float l1_w, float* flat_grad, float* loss_dev, float* out_dev,
-                           float* ema_state, int ema_first, void* stream);
 int train_refresh_padded_weights(Context* c, void* stream);
 int train_adamw(Context* c, const float* flat_grad, float lr, float b1, float b2, float eps, float wd, float max_norm,
                 int64_t step, void* stream);
@@ -244,10 +235,13 @@ int trainp_copy_masks(Context* c, int64_t B, unsigned char* mel, unsigned char* 
 struct LogParams;
 // packed: the front end wrote 10 log10(power) into the packed input itself (MelPack); the readers finish the dB conversion
 struct TrainAudioSrc { const float* melpow; const unsigned* melmax; int n_frames; const LogParams* lp; bool packed; };
-int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64_t T_in, const float* mel_short, const float* xp_dev,
-                                  const TrainAudioSrc* asrc,
-                                  const float* emo, const float* target, float mse_w, float l1_w, float* flat_grad, float* loss_dev,
-                                  float* out_dev, float* ema_state, int ema_first, void* stream);
+// what km_train_step, km_train_step_audio and km_train_step_clip hand through unchanged from their own arguments
+struct TrainStepArgs {
+    const float* emo; const float* target; float mse_w, l1_w; float* flat_grad; float* loss_dev; float* out_dev;
+    float* ema_state; int ema_first; void* stream;
+};
+int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in, const float* mel_short, const float* xp_dev,
+                           const TrainAudioSrc* asrc, const TrainStepArgs& a);
 int launch_audio_energy(const float* feats, int64_t B, int64_t T, int64_t D, float* out, void* stream);
 
 // km_generic.hip

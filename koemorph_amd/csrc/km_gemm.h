@@ -1,5 +1,5 @@
 // Strided-batched exact-fp32 MFMA GEMM shared by km_generic.hip (inference on generic shapes, legacy model)
-// and km_train.hip (training forward / backward).
+// and km_trainp.hip (training forward / backward).
 #pragma once
 
 #include <cstdint>

@@ -1,5 +1,5 @@
-// Loss tail of the training step (decoder output -> prediction -> KoeMorphLoss -> dL/dz), shared by the launch-per-op
-// chain (km_train.hip) and the phased step (km_trainp.hip).  Included inside namespace km of a .hip translation unit.
+// Loss tail of the training step (decoder output -> prediction -> KoeMorphLoss -> dL/dz), included by the
+// training step (km_trainp.hip).  Included inside namespace km of a .hip translation unit.
 #pragma once
 #include "km_gridsync.h"
 

@@ -1,10 +1,14 @@
-// Phased training step of the dual-stream core for gfx950 (BASELINE config C3).
+// Training step of the dual-stream core for gfx950 (BASELINE config C3): forward, loss and
+// backward.  Clipping and AdamW are km_train.hip.
 //
-// Same arithmetic as km_train.hip (unfolded forward with saved activations, KoeMorphLoss tail, backward into ONE flat
-// gradient bucket), restructured for the shape the reference trains at: 8 windows per GPU.  There every product is a
-// handful of 64 x 64 tiles, so the launch-per-op chain (~70 launches over two streams) was bound by launches and by the
-// load -> LDS -> MFMA latency of each tiny kernel, not by arithmetic (round 1: 0.69 ms, 1 % of the MFMA peak).  Here the
-// step is a PROGRAM of ~19 phases; a phase is ONE launch (phase_kernel) that runs every operation whose inputs are ready
+// Replaces, per rank, the body of SequentialTrainer.train_epoch (reference src/train_sequential.py:158-181):
+//   outputs = model(audio); loss = criterion(...); loss.backward()
+// for the 28 tensors of DualStreamCrossAttention + smoothing_alpha.  The mel and emotion features carry no gradient in the
+// reference (NumPy round trip), so backward stops at the core inputs: unfolded forward with saved activations, KoeMorphLoss
+// tail, backward into ONE flat caller-owned gradient bucket in state-dict order.  Built for the shape the reference trains
+// at, 8 windows per GPU: there every product is a handful of 64 x 64 tiles, and a launch per operation (~70 launches, the
+// form this step had in round 1) is bound by launches and by the load -> LDS -> MFMA latency of each tiny kernel, not by
+// arithmetic (0.69 ms, 1 % of the MFMA peak).  Here the step is a PROGRAM of phases; a phase is ONE launch (phase_kernel) that runs every operation whose inputs are ready
 // -- GEMM tiles, LayerNorm / softmax rows, column reductions -- side by side on different workgroups.  No side stream,
 // no events, no atomics: every reduction is a fixed-order two-stage sum, so a step is bit-reproducible and capturable.
 //
@@ -255,7 +259,7 @@ __device__ __forceinline__ void op_elem(const Op& op, int vb, int tid, float* sm
         break;
     }
     case OP_PACKX: {        // xt (B, NK, KP) <- mel (B, t_in, NK) rows [0, tv), zeros to T, 3 short rows, zeros to KP -- TRANSPOSED:
-        // channel rows of KP frames (see train_forward_backward_phased: both products that read it then run on the LDS-DMA tile)
+        // channel rows of KP frames (see train_forward_backward: both products that read it then run on the LDS-DMA tile)
         const int64_t i = (int64_t)vb * 256 + tid;           // one float4 of channels each
         const int nk4 = a.i0 / 4, KP = a.i1, T = a.i2, t_in = a.i3;
         if (i >= a.n0 * KP * nk4) break;
@@ -859,19 +863,17 @@ int64_t trainp_mask_alloc_bytes(Context* c) {
 
 // xp_dev: packed encoder input (B, KP, NK) when the caller (the from-audio step) produced it, else null and it is packed
 // here from mel / mel_short.
-int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64_t T_in, const float* mel_short, const float* xp_dev,
-                                  const TrainAudioSrc* asrc,
-                                  const float* emo, const float* target, float mse_w, float l1_w, float* flat_grad, float* loss_dev,
-                                  float* out_dev, float* ema_state, int ema_first, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
+int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in, const float* mel_short, const float* xp_dev,
+                           const TrainAudioSrc* asrc, const TrainStepArgs& sa) {
+    hipStream_t st = (hipStream_t)sa.stream;
     const int64_t d = c->d, H = c->H, hd = c->hd, T = c->T, KT = c->KT, DH = c->DH, NKk = c->NK, ED = c->ED;
     const int64_t KP = trainp_kp(c);
     const int64_t R = B * NKk, Rm = B * 28, Re = B * 24;
     if (NKk % 4 != 0 || NKk > 16 * kAttnMaxKT)
         return fail(KM_ERR_UNSUPPORTED, "phased training step needs num_mel_channels <= %d, a multiple of 4 (got %lld)", 16 * kAttnMaxKT, (long long)NKk);
-    c->tr_alpha_live = ema_state != nullptr && !ema_first;
+    c->tr_alpha_live = sa.ema_state != nullptr && !sa.ema_first;
     auto P = [&](const char* k) -> const float* { return c->tr_params + c->tr_offset.at(k); };
-    auto Gd = [&](const char* k) -> float* { return flat_grad + c->tr_offset.at(k); };
+    auto Gd = [&](const char* k) -> float* { return sa.flat_grad + c->tr_offset.at(k); };
     float* w = c->trp_act;
     auto take = [&](int64_t n) { float* p = w; w += (n + 3) / 4 * 4; return p; };
     float* xp = take(c->tr_windows * KP * NKk);            // first: km_train_step_audio writes the packed input here
@@ -933,7 +935,7 @@ int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64
     Program pg;
     pg.scratch = c->trp_split; pg.scratch_left = c->trp_split_floats;
     pg.allow_split = !c->opt.train_no_split;
-    pg.leaf_lo = flat_grad; pg.leaf_hi = flat_grad + c->tr_nparams;
+    pg.leaf_lo = sa.flat_grad; pg.leaf_hi = sa.flat_grad + c->tr_nparams;
     if (c->opt.train_bm32_below > 0) pg.bm32_below = c->opt.train_bm32_below;
     pg.op_per_launch = c->opt.train_op_per_launch != 0; pg.dbg_stream = st;
     pg.use_dma = !c->opt.train_no_dma;
@@ -988,7 +990,7 @@ int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64
     // odd float offset) rules the tile out -- the step then keeps the LayerNorm phase instead of failing.
     GemmArgs gY0 = NT(X, KP, WceP, KP, Y0, d, NKk, d, P("mel_channel_encoder.bias"), 0);
     gY0.a_bs1 = KP * NKk; gY0.c_bs1 = NKk * d;
-    const GemmArgs gE0 = NT(emo, ED, P("emotion_encoder.weight"), ED, E0, d, B, d, P("emotion_encoder.bias"), 0);
+    const GemmArgs gE0 = NT(sa.emo, ED, P("emotion_encoder.weight"), ED, E0, d, B, d, P("emotion_encoder.bias"), 0);
     auto dma_nt = [](const GemmArgs& g) { int ma = -1, mb = -1; return gemm_dma_ok(g, &ma, &mb) && ma == 0 && mb == 0; };
     auto ln_ok = [&](const GemmArgs& g) { return dma_nt(g) && g.N % 32 == 0; };
     // the operand transform has no fallback (the front end has already written 10 log10(power)): its operand is the aligned workspace
@@ -1122,7 +1124,7 @@ int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64
     // clean gradient bucket and the ones vector (first touched in P8): they ride under the attention blocks
     {
         ElemArgs e{};
-        e.q0 = flat_grad; e.n0 = c->tr_nparams;
+        e.q0 = sa.flat_grad; e.n0 = c->tr_nparams;
         pg.elem(OP_ZERO, e, (c->tr_nparams + 4095) / 4096);
         ElemArgs f{};
         f.q0 = ones; f.n0 = R; f.f0 = 1.0f;
@@ -1139,11 +1141,11 @@ int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64
     {
         TailArgs t{};
         t.zrows = zrows; t.zrows_out = zrows; t.grow = grow; t.h1 = H1; t.he = He; t.w2 = w2; t.b2 = b2;
-        t.mel_w = P("mel_weights"); t.emo_w = P("emotion_weights"); t.temperature = c->cfg.temperature; t.target = target;
-        t.bs = bs; t.out = outb; t.dz = dz; t.ema_state = ema_state; t.ema_first = ema_first; t.alpha_p = P("smoothing_alpha");
-        t.mse_w = mse_w; t.l1_w = l1_w; t.lc = c->tr_loss_cfg; t.fac = tfac; t.xp = txp; t.loss = loss_dev;
+        t.mel_w = P("mel_weights"); t.emo_w = P("emotion_weights"); t.temperature = c->cfg.temperature; t.target = sa.target;
+        t.bs = bs; t.out = outb; t.dz = dz; t.ema_state = sa.ema_state; t.ema_first = sa.ema_first; t.alpha_p = P("smoothing_alpha");
+        t.mse_w = sa.mse_w; t.l1_w = sa.l1_w; t.lc = c->tr_loss_cfg; t.fac = tfac; t.xp = txp; t.loss = sa.loss_dev;
         t.d_melw = Gd("mel_weights"); t.d_emow = Gd("emotion_weights"); t.d_alpha = Gd("smoothing_alpha");
-        t.B = (int)B; t.DH = (int)DH; t.expr_rows = 24; t.audio_energy = c->tr_loss_cfg.audio_energy_dev; t.out2 = out_dev;
+        t.B = (int)B; t.DH = (int)DH; t.expr_rows = 24; t.audio_energy = c->tr_loss_cfg.audio_energy_dev; t.out2 = sa.out_dev;
         t.d_b2 = Gd("blendshape_decoder.3.bias"); t.drop_ctr = (drop && c->tr_dropout_mode == 0) ? c->trp_drop_ctr : nullptr;
         t.part = c->trp_tail_part; t.ctr = c->trp_tail_ctr;
         t.dh1 = dH1; t.dhe = dHe; t.keep_scale = keep_scale;
@@ -1254,7 +1256,7 @@ int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64
     RUN(pg.end_phase(st));
     if (!pg.pend_prev.empty()) return fail(KM_ERR_UNSUPPORTED, "training program: a reduction is still pending behind phase 11 (internal)");
     // everything but the "late" group of the bucket (km_train_init) is final: a side stream may start its all-reduce
-    HIP_TRY(hipEventRecord((hipEvent_t)c->tr_ev[0], st));
+    HIP_TRY(hipEventRecord((hipEvent_t)c->tr_early_ev, st));
     c->tr_early_recorded = true;
     // ================= P12: channel encoder gradients; LayerNorm parameters; emotion encoder =================
     // dWce (d x KT) = dY0^T XT over ALL rows (window, channel) of the batch: with the transposed input it is ONE product with a
@@ -1270,7 +1272,7 @@ int train_forward_backward_phased(Context* c, const float* mel, int64_t B, int64
     colsum(dY, R, d, d, Gd("mel_norm.bias"), 0, ones);
     colsum(Te, B, d, d, Gd("emotion_norm.weight"), 0, ones);
     colsum(dE, B, d, d, Gd("emotion_norm.bias"), 0, ones);
-    pg.gemm(TN(dE0, d, emo, ED, Gd("emotion_encoder.weight"), ED, d, ED, B), 1);
+    pg.gemm(TN(dE0, d, sa.emo, ED, Gd("emotion_encoder.weight"), ED, d, ED, B), 1);
     colsum(dE0, B, d, d, Gd("emotion_encoder.bias"), 0, ones);
     pg.min_k = min_k_saved;
     RUN(pg.end_phase(st));
