@@ -174,6 +174,29 @@ int km_forward_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L,
                      const float* emotion_dev, float* out_dev, float* state_dev, int32_t first,
                      void* stream);
 
+/* km_forward_audio for B windows of ONE clip resident in HBM -- the eval-mode twin of km_train_step_clip, for the validation
+ * pass between epochs.  Replaces the per-window slicing (src/data/sequential_dataset.py:156-209) + the per-window log-mel
+ * (src/model/simplified_dual_stream_model.py:184-229) under the validation forward (src/train_sequential.py:257-259) without
+ * materialising the (B, T * hop) windows.  Window b is samples [start_frames[b] * hop, + T * hop) of clip_dev (clip_len samples,
+ * zero beyond), exactly what km_gather_windows would have copied; the start frames may come in any order and may repeat.
+ * emotion_dev is (B, emotion_dim), one vector per window; state_dev / first as in km_forward_audio (the caller carries the
+ * (B, 52) EMA state from batch to batch -- km_sequence_forward smooths along the frame axis of a clip instead and takes one
+ * emotion vector per clip, so it cannot stand in).  The STFT frames the windows share are computed once -- max - min + T + 1 clip
+ * frames + 2 zero-padded boundary frames per window instead of B * (T + 1) -- the dB reference of a window is the maximum over
+ * its own T + 1 frames, and the fused core reads its rows through the start-frame table: out_dev and state_dev are
+ * bit-identical to km_gather_windows + km_forward_audio.  min_start_frame / max_start_frame are HOST copies of the extremes of
+ * start_frames_dev (they size the launches; nothing is read back, so the call can be captured into a hipGraph).  The span and
+ * edge images belong to the inference context (no km_train_init needed) and only grow: a span wider, or a batch larger, than
+ * any earlier call's allocates, so capture only after a warm-up call with that span.  Needs km_reserve(B, 0).
+ *   km_forward_clip_supported   1 when km_forward_clip runs on this handle (after km_finalize), else 0: the fused core
+ *                        (d_model 256, window 256, 8 heads) behind the 1024-point front end (not mel_two_frame), pad_mode
+ *                        constant and hop_length >= n_fft / 2 (see km_train_clip_supported).  On any other handle
+ *                        km_forward_clip returns KM_ERR_UNSUPPORTED, never another result. */
+int km_forward_clip_supported(km_handle h);
+int km_forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
+                    int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev,
+                    float* out_dev, float* state_dev, int32_t first, void* stream);
+
 /* Throughput mode of km_forward_audio: a two-deep software pipeline ACROSS calls.  The front end (VALU/LDS bound
  * FFT) of call i runs on an internal stream concurrently with the fused core (fp32-MFMA bound) of call i-1, which
  * the hardware co-schedules on the same CUs (separate matrix and vector pipes); the power-mel workspace is double
@@ -503,6 +526,37 @@ int km_metrics_destroy(void* acc);
 int km_metrics_reset(void* acc, void* stream);
 int km_metrics_update(void* acc, const float* pred_dev, const float* target_dev, const float* audio_energy_dev, int64_t N, void* stream);
 int km_metrics_compute(void* acc, float* out_dev, void* stream);
+
+/* ---- the loss by component: a streaming accumulator in device memory ------------------------------------------------
+ * Replaces the `metrics` dict of KoeMorphLoss.forward (src/model/losses.py:111-183: one .item() per term and batch), the
+ * per-batch criterion call + .item() reads of the reference's validate() (src/train_sequential.py:257-271) and the
+ * per-sequence loss / smoothness lists it keeps (:273-290).  One update takes one batch (N, 52), N >= 1, and evaluates in
+ * float64 the eval-mode value of every term km_train_step* adds (KoeMorphLoss's eight, perceptual with the audio-visual part
+ * when cfg->audio_energy_dev is set, and DualStreamLoss's two), their weighted total
+ * mse_weight * mse + l1_weight * l1 + sum cfg weight * term, and the rows' smoothness mean_j |pred[b, j+1] - pred[b, j]|.
+ * The skip rules are km_loss_config's: temporal and velocity need prev_pred_dev and prev_target_dev, landmark landmark_w_dev,
+ * ds_velocity ds_prev_pred_dev, ds_separation a weight > 0; a skipped term reports 0 and its update does not count in its
+ * mean.  cfg = NULL evaluates mse and l1 only; cfg->abi_version is checked as in km_train_set_loss.  cfg is read during the
+ * call (its device pointers on the stream).  Fixed-order float64 reductions, no floating-point atomics: the same rows in the
+ * same calls give the same bits.  reset / update / compute launch on `stream`, neither allocate nor synchronise nor read
+ * back, and can be captured.
+ *   km_loss_terms_update    terms_dev (KM_LOSS_TERMS) or NULL: this batch's values, float32, indexed by KM_LOSS_TERM_*
+ *   km_loss_terms_compute   out_dev (KM_LOSS_TERMS + 2): per term (and for the total) the mean over the UPDATES since the last
+ *                           reset in which it was evaluated -- the reference averages per-batch losses (:286-287) -- then
+ *                           [KM_LOSS_TERMS] the number of updates and [KM_LOSS_TERMS + 1] the mean over all ROWS of their
+ *                           smoothness; all 0 before any update.  The state is left as it is */
+enum {
+    KM_LOSS_TERM_MSE = 0, KM_LOSS_TERM_L1 = 1, KM_LOSS_TERM_PERCEPTUAL = 2, KM_LOSS_TERM_TEMPORAL = 3, KM_LOSS_TERM_VELOCITY = 4,
+    KM_LOSS_TERM_SPARSITY = 5, KM_LOSS_TERM_SMOOTHNESS = 6, KM_LOSS_TERM_LANDMARK = 7, KM_LOSS_TERM_DS_VELOCITY = 8,
+    KM_LOSS_TERM_DS_SEPARATION = 9, KM_LOSS_TERM_TOTAL = 10
+};
+#define KM_LOSS_TERMS 11
+int km_loss_terms_create(void** acc_out);
+int km_loss_terms_destroy(void* acc);
+int km_loss_terms_reset(void* acc, void* stream);
+int km_loss_terms_update(void* acc, const km_loss_config* cfg, float mse_weight, float l1_weight,
+                         const float* pred_dev, const float* target_dev, int64_t N, float* terms_dev, void* stream);
+int km_loss_terms_compute(void* acc, float* out_dev, void* stream);
 
 /* ---- run-time switches ---------------------------------------------------------------------------
  * Replaces what would be module attributes / environment switches on the reference side (the reference has none on

@@ -70,6 +70,11 @@ KM_METRICS_NAMES = ("mae", "mse", "rmse", "max_bs_mae", "min_bs_mae", "std_bs_ma
                     "precision", "recall", "f1_score", "mouth_mae", "mouth_correlation", "audiovisual_sync", "rows",
                     "valid_correlations", "has_energy")
 
+# km_loss_terms_update's terms_dev / the first KM_LOSS_TERMS entries of km_loss_terms_compute (include/koemorph.h: KM_LOSS_TERM_*)
+KM_LOSS_TERMS = 11
+KM_LOSS_TERM_NAMES = ("mse", "l1", "perceptual", "temporal", "velocity", "sparsity", "smoothness", "landmark", "ds_velocity",
+                      "ds_separation", "total")
+
 _p = C.c_void_p
 _i64 = C.c_int64
 _i32 = C.c_int32
@@ -96,6 +101,8 @@ SIGNATURES = {
     "km_core_forward_z": (C.c_int, [_h, _p, _i64, _i64, _p, _p, _p, _p, _p, _p]),
     "km_smooth": (C.c_int, [_h, _p, _p, _i64, _i32, _p]),
     "km_forward_audio": (C.c_int, [_h, _p, _i64, _i64, _p, _p, _p, _i32, _p]),
+    "km_forward_clip_supported": (C.c_int, [_h]),
+    "km_forward_clip": (C.c_int, [_h, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _i32, _p]),
     "km_forward_audio_pipelined": (C.c_int, [_h, _p, _i64, _i64, _p, _p, _p, _i32, _p]),
     "km_pipeline_flush": (C.c_int, [_h, _p]),
     "km_sequence_num_outputs": (_i64, [_h, _i64, _i32]),
@@ -149,6 +156,11 @@ SIGNATURES = {
     "km_metrics_reset": (C.c_int, [_p, _p]),
     "km_metrics_update": (C.c_int, [_p, _p, _p, _p, _i64, _p]),
     "km_metrics_compute": (C.c_int, [_p, _p, _p]),
+    "km_loss_terms_create": (C.c_int, [C.POINTER(_p)]),
+    "km_loss_terms_destroy": (C.c_int, [_p]),
+    "km_loss_terms_reset": (C.c_int, [_p, _p]),
+    "km_loss_terms_update": (C.c_int, [_p, C.POINTER(KMLossConfig), C.c_float, C.c_float, _p, _p, _i64, _p, _p]),
+    "km_loss_terms_compute": (C.c_int, [_p, _p, _p]),
     "km_linear": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
     "km_enable_stage_timing": (C.c_int, [_h, _i32]),
     "km_stage_times": (C.c_int, [_h, C.POINTER(C.c_float)]),

@@ -126,7 +126,7 @@ int km_destroy(km_handle h) {
     (void)free_streams(c);
     (void)free_train(c);
     (void)free_pipeline(c);
-    for (void* q : {(void*)c->seq_pow, (void*)c->seq_fmax, (void*)c->seq_edge, (void*)c->seq_emax})
+    for (void* q : {(void*)c->seq_pow, (void*)c->seq_fmax, (void*)c->seq_edge, (void*)c->seq_emax, (void*)c->fwd_span, (void*)c->fwd_edge})
         if (q) (void)hipFree(q);
     if (c->pipe_s1) {
         (void)hipStreamDestroy((hipStream_t)c->pipe_s1); (void)hipStreamDestroy((hipStream_t)c->pipe_s2);
@@ -700,6 +700,75 @@ int km_forward_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, 
     if (int rc = launch_core_fused_db(c, c->mel_plans[0], B, n_frames, c->ws_zemo, out_dev, state_dev, first, stream)) return rc;
     if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[4], st));
     return KM_OK;
+}
+
+// km_forward_clip shares STFT frames between the windows of a batch exactly as km_train_step_clip does, so the front-end half of
+// train_clip_ok applies (the 1024-point kernel with its grouped filter image, zero padding, hop >= n_fft / 2: only then are
+// frames 0 and T the only frames of a window that see its padding); behind it runs the fused core's table variant.  The
+// experimental split-bf16 core has no table variant: with it switched on km_forward_audio computes something else.
+static bool forward_clip_ok(Context* c) {
+    if (c->mel_plans.empty() || !c->fused_ok || c->opt.core_split == 3 || c->opt.core_split == 6) return false;
+    MelPlan* p = c->mel_plans[0];
+    const km_mel_config& m = p->cfg;
+    return m.n_fft == 1024 && !c->opt.mel_two_frame && p->d_fbg_gid != nullptr && m.n_mels == c->NK && c->NK % 4 == 0 &&
+           m.pad_mode == KM_PAD_CONSTANT && 2 * m.hop_length >= m.n_fft;
+}
+
+int km_forward_clip_supported(km_handle h) {
+    if (!h || !h->dev_finalized || h->kind != 0) return 0;
+    return forward_clip_ok(h) ? 1 : 0;
+}
+
+int km_forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
+                    int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev, float* out_dev,
+                    float* state_dev, int32_t first, void* stream) {
+    if (int rc = need_dual(h)) return rc;
+    Context* c = h;
+    if (!clip_dev || !start_frames_dev || !emotion_dev || !out_dev || B <= 0 || clip_len <= 0 || min_start_frame < 0 ||
+        max_start_frame < min_start_frame)
+        return fail(KM_ERR_INVALID_ARG, "km_forward_clip: bad argument");
+    const km_mel_config& m = c->mel_plans[0]->cfg;
+    if (!forward_clip_ok(c))
+        return fail(KM_ERR_UNSUPPORTED, "km_forward_clip: needs the fused core (d_model 256, window 256, 8 heads) behind the 1024-point "
+                    "front end with constant padding and hop >= n_fft / 2 (hop %d, n_fft %d): gather the windows (km_gather_windows) "
+                    "and call km_forward_audio", m.hop_length, m.n_fft);
+    const int64_t T = c->T, hop = m.hop_length;
+    const int64_t n_span = (int64_t)(max_start_frame - min_start_frame) + T + 1;
+    if (clip_len >= (1ll << 31) || ((int64_t)max_start_frame + T + 2) * hop >= (1ll << 31) || n_span * c->NK >= (1ll << 31))
+        return fail(KM_ERR_INVALID_ARG, "km_forward_clip: clip or start frame beyond 2^31 samples");
+    if (B > c->ws_windows)
+        return fail(KM_ERR_WORKSPACE, "workspace holds %lld windows, need %lld: call km_reserve", (long long)c->ws_windows, (long long)B);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_span > c->fwd_span_cap || B > c->fwd_edge_cap) {            // grow-only; allocates, so not inside a stream capture
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+            return fail(KM_ERR_WORKSPACE, "km_forward_clip: a span of %lld frames / %lld windows exceeds the %lld / %lld allocated during a "
+                        "stream capture: run one call with this span first", (long long)n_span, (long long)B, (long long)c->fwd_span_cap,
+                        (long long)c->fwd_edge_cap);
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_span > c->fwd_span_cap) {
+            if (c->fwd_span) HIP_TRY(hipFree(c->fwd_span));
+            c->fwd_span = nullptr; c->fwd_span_cap = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->fwd_span), (size_t)n_span * c->NK * sizeof(float)));
+            c->fwd_span_cap = n_span;
+        }
+        if (B > c->fwd_edge_cap) {
+            if (c->fwd_edge) HIP_TRY(hipFree(c->fwd_edge));
+            c->fwd_edge = nullptr; c->fwd_edge_cap = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->fwd_edge), (size_t)B * 2 * c->NK * sizeof(float)));
+            c->fwd_edge_cap = B;
+        }
+    }
+    // four launches: emotion logits (emotion_kernel_d256: bit-identical to the rider inside km_forward_audio's front end), the
+    // span + edge images, the window maxima, the fused core reading its rows through the table
+    if (int rc = launch_emotion(c, emotion_dev, B, c->ws_zemo, stream)) return rc;
+    if (int rc = launch_mel_clip_span(c, c->mel_plans[0], clip_dev, clip_len, start_frames_dev, B, min_start_frame, n_span, (int)T,
+                                      c->fwd_span, c->fwd_edge, stream)) return rc;
+    if (int rc = launch_clip_window_max(c, c->fwd_span, c->fwd_edge, start_frames_dev, B, min_start_frame, n_span, (int)(T + 1),
+                                        stream)) return rc;
+    SeqCore sc{c->fwd_span, c->fwd_edge, (int)n_span, 0, 1};
+    sc.start = start_frames_dev; sc.min_start = min_start_frame;
+    return launch_core_fused_db(c, c->mel_plans[0], B, T + 1, c->ws_zemo, out_dev, state_dev, first, stream, 0, 1, 0, nullptr, nullptr, &sc);
 }
 
 static int free_streams(Context* c) {

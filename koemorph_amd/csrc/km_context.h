@@ -175,6 +175,10 @@ struct Context {
     // shared-frame sequence mode buffers (grow-only, allocated by km_sequence_forward)
     float* seq_pow = nullptr; unsigned* seq_fmax = nullptr; float* seq_edge = nullptr; unsigned* seq_emax = nullptr;
     int64_t seq_pow_cap = 0, seq_edge_cap = 0;
+    // eval-mode forward from a resident clip (km_forward_clip): the span image (rows, NK) and the edge image (windows, 2, NK) of
+    // launch_mel_clip_span, owned by the inference context (no km_train_init needed), grow-only
+    float* fwd_span = nullptr; float* fwd_edge = nullptr;
+    int64_t fwd_span_cap = 0, fwd_edge_cap = 0;
     // training from a resident clip (km_train_step_clip): power-mel of the clip span the batch touches (rows, NK) and of every
     // window's two zero-padded boundary frames (windows, 2, NK); sized by km_train_init, the span image grow-only afterwards
     float* clip_span = nullptr; float* clip_edge = nullptr;
@@ -210,6 +214,10 @@ struct SeqCore {
     const float* pow;     // (clips, nfc, 80) clip-level power-mel
     const float* edge;    // (clips * n_per_clip, 2, 80) first / last frame of every window
     int nfc, stride, n_per_clip;
+    // km_forward_clip: rows addressed by a start-frame table instead of a stride.  `pow` is then ONE span image (nfc rows, row r =
+    // clip frame min_start + r), window b begins at row start[b] - min_start, `edge` is (windows, 2, 80); stride / n_per_clip unused
+    const int* start = nullptr;
+    int min_start = 0;
 };
 int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, const float* zemo, float* out,
                          float* state, int first, void* stream, int64_t win0 = 0, int zemo_div = 1, int64_t n_use = 0,
@@ -217,6 +225,9 @@ int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, co
                          const struct SeqCore* seq = nullptr);
 int launch_seq_window_max(Context* c, const unsigned* fmax, const unsigned* emax, int64_t nw, int64_t win0, int nfc, int stride,
                           int n_per_clip, int n_frames, void* stream);
+// km_forward_clip: the maximum over each window's OWN n_frames rows of the span / edge images (found through the table) -> ws_melmax
+int launch_clip_window_max(Context* c, const float* span, const float* edge, const int* start, int64_t B, int min_start,
+                           int64_t n_span, int n_frames, void* stream);
 int launch_ema_scan(Context* c, float* x, int64_t B, int64_t N, void* stream);
 int launch_smooth(Context* c, float* x, float* state, int64_t B, int first, void* stream);
 

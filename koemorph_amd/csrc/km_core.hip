@@ -101,6 +101,11 @@ struct CoreArgs {
     int seq_nfc, seq_stride, seq_n;
     const unsigned char* ready;   // (B) or null: windows with ready[b] == 0 are skipped entirely
     unsigned char* started;       // (B) or null: first = !started[b], then started[b] = 1
+    // TAB variant (km_forward_clip): seq_pow is one span image of seq_nfc rows (row r = clip frame seq_min + r), window b begins
+    // at row seq_start[b] - seq_min, seq_edge is (B, 2, 80).  Last, so that
+    // the kernel arguments of every other instantiation stay where they were
+    const int* seq_start;
+    int seq_min;
 };
 
 // blendshape index -> mouth query slot (MOUTH_INDICES = 14..40, 51; dual_stream_attention.py:14-45)
@@ -110,7 +115,8 @@ __device__ __forceinline__ int mouth_slot_of(int i) { return (i >= 14 && i <= 40
 // NP > 0 (experimental, opt-in: KM_CORE_SPLIT = 3 or 6 terms): phases 2+3 on the bf16 matrix pipe with every
 // fp32 operand split into NP bf16 pieces and the products of weight >= 2^-16 (NP 2: three) or >= 2^-24 (NP 3: six)
 // accumulated in fp32.  Everything else is unchanged.
-template <bool ATTN, bool FUSE_DB, int NP = 0>
+// TAB (km_forward_clip): the rows of a window are found through a start-frame table; every other instantiation is untouched.
+template <bool ATTN, bool FUSE_DB, int NP = 0, bool TAB = false>
 __global__ __launch_bounds__(512) void core_fused_kernel(CoreArgs a) {
     using namespace fused;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -155,7 +161,15 @@ __global__ __launch_bounds__(512) void core_fused_kernel(CoreArgs a) {
         const int tv = U < T ? U : T;
         const float4* src = reinterpret_cast<const float4*>(a.melpow + (int64_t)b * F * NK);
         const float4 *seq_rows = nullptr, *seq_e = nullptr;
-        if (a.seq_pow) {
+        if constexpr (TAB) {
+            // frame f = 1 .. F - 2 of window b is span row start[b] - min_start + f; the row is kept inside the image whatever
+            // the table holds (the extremes are the caller's host copies)
+            int r0 = a.seq_start[b];
+            r0 = (r0 < 0 ? 0 : r0) - a.seq_min;
+            r0 = r0 < 0 ? 0 : (r0 > a.seq_nfc - F ? a.seq_nfc - F : r0);
+            seq_rows = reinterpret_cast<const float4*>(a.seq_pow + (int64_t)r0 * NK);
+            seq_e = reinterpret_cast<const float4*>(a.seq_edge + (int64_t)b * 2 * NK);
+        } else if (a.seq_pow) {
             const int64_t gw = a.win0 + b, clip = gw / a.seq_n, wi = gw - clip * a.seq_n;
             seq_rows = reinterpret_cast<const float4*>(a.seq_pow + (clip * a.seq_nfc + wi * a.seq_stride) * NK);
             seq_e = reinterpret_cast<const float4*>(a.seq_edge + gw * 2 * NK);
@@ -926,6 +940,8 @@ static int core_attrs(Context* c) {
                                     hipFuncAttributeMaxDynamicSharedMemorySize, fused::lds_bytes(2)));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core_fused_kernel<false, true, 3>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, fused::lds_bytes(3)));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core_fused_kernel<false, true, 0, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, fused::LDS_BYTES));
     }
     return KM_OK;
 }
@@ -979,6 +995,50 @@ int launch_seq_window_max(Context* c, const unsigned* fmax, const unsigned* emax
     return KM_OK;
 }
 
+// Per-window maximum for km_forward_clip: launch_mel_clip_span keeps no per-frame maxima, so the maximum is taken over the
+// powers themselves -- rows 1 .. n_frames - 2 of the window in the span image (one contiguous run, read as float4) and its two
+// edge rows.  One workgroup per window; a maximum does not depend on the order, so the bits are those of the front end's own
+// window maximum.  Plain store: no zeroed slot needed.
+constexpr int CWM_NT = 256;
+__global__ __launch_bounds__(CWM_NT) void clip_window_max_kernel(const float* __restrict__ span, const float* __restrict__ edge,
+                                                                 const int* __restrict__ start, unsigned* __restrict__ melmax,
+                                                                 int min_start, int n_span, int n_frames, int nk4) {
+    __shared__ float red[CWM_NT / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int r0 = start[b];
+    r0 = (r0 < 0 ? 0 : r0) - min_start;
+    r0 = r0 < 0 ? 0 : (r0 > n_span - n_frames ? n_span - n_frames : r0);      // as the core clamps it
+    const float4* rows = reinterpret_cast<const float4*>(span) + (int64_t)(r0 + 1) * nk4;
+    const float4* e = reinterpret_cast<const float4*>(edge) + (int64_t)b * 2 * nk4;
+    float m = 0.f;
+    auto take = [&](const float4 v) { m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w))); };
+    const int n_in = (n_frames - 2) * nk4;
+    for (int i = tid; i < n_in; i += CWM_NT) take(rows[i]);
+    for (int i = tid; i < 2 * nk4; i += CWM_NT) take(e[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((tid & 63) == 0) red[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) {
+        float mx = red[0];
+#pragma unroll
+        for (int w = 1; w < CWM_NT / 64; ++w) mx = fmaxf(mx, red[w]);
+        melmax[b] = __float_as_uint(mx);
+    }
+}
+
+int launch_clip_window_max(Context* c, const float* span, const float* edge, const int* start, int64_t B, int min_start,
+                           int64_t n_span, int n_frames, void* stream) {
+    if (!span || !edge || !start || B <= 0 || n_frames < 3 || n_span < n_frames || c->NK % 4 != 0)
+        return fail(KM_ERR_INVALID_ARG, "clip window maximum: bad argument");
+    hipLaunchKernelGGL(clip_window_max_kernel, dim3((unsigned)B), dim3(CWM_NT), 0, (hipStream_t)stream, span, edge, start, c->ws_melmax,
+                       min_start, (int)n_span, n_frames, c->NK / 4);
+    HIP_TRY(hipGetLastError());
+    // melmax_dirty stays as it is: slots 0 .. B - 1 were just stored and are re-zeroed by the core launch that follows, the
+    // slots beyond B are as clean or as dirty as they were
+    return KM_OK;
+}
+
 int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, const float* zemo, float* out,
                          float* state, int first, void* stream, int64_t win0, int zemo_div, int64_t n_use,
                          const unsigned char* ready, unsigned char* started, const SeqCore* seq) {
@@ -990,6 +1050,12 @@ int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, co
     a.melpow = c->ws_melpow; a.melmax = c->ws_melmax; a.n_frames = (int)n_frames; a.lp = plan_log_params(p);
     a.n_use = (int)(n_use > 0 ? n_use : n_frames); a.ready = ready; a.started = started;
     if (seq) { a.seq_pow = seq->pow; a.seq_edge = seq->edge; a.seq_nfc = seq->nfc; a.seq_stride = seq->stride; a.seq_n = seq->n_per_clip; }
+    if (seq && seq->start) {     // km_forward_clip: rows by table (never with the experimental split core: km_forward_clip refuses it)
+        a.seq_start = seq->start; a.seq_min = seq->min_start;
+        hipLaunchKernelGGL((core_fused_kernel<false, true, 0, true>), dim3((unsigned)B), dim3(fused::NT), fused::LDS_BYTES, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+        return KM_OK;
+    }
     // experimental, off by default: option core_split = 3 / 6 runs phases 1 and 2+3 as split-bf16 products
     const int terms = c->opt.core_split;
     if (terms == 3) {

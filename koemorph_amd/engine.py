@@ -285,6 +285,42 @@ class Engine:
                                              1 if first else 0, _stream_ptr(audio.device)))
         return out
 
+    def forward_clip_supported(self) -> bool:
+        """km_forward_clip_supported: ``forward_clip`` runs on this engine (fused core, windows share the clip's STFT frames)."""
+        return bool(self._lib.km_forward_clip_supported(self._h))
+
+    def forward_clip(self, clip, start_frames, emotion, state=None, first: bool = True, extremes=None, out=None):
+        """``forward_audio`` on the windows of ONE clip (a 1-D device tensor) that start at ``start_frames`` (in frames of hop
+        samples; any order, repeats allowed), without the (B, window) copy and with the STFT frames the windows share computed
+        once (km_forward_clip): same ``out`` and ``state`` bits as gathering the windows first.  ``emotion`` is (B, emotion_dim).
+        A host sequence / CPU tensor of start frames is uploaded and its extremes taken here; a device int32 tensor comes with
+        ``extremes`` = (min, max) from the host copy its producer has, so nothing is read back on the way to the launch."""
+        torch = _torch()
+        clip = self._chk(clip, "clip", 1)
+        emotion = self._chk(emotion, "emotion_features", 2)
+        if isinstance(start_frames, torch.Tensor) and start_frames.is_cuda:
+            if extremes is None:
+                raise ValueError("device start frames need extremes=(min, max) from their host copy")
+            if start_frames.dtype != torch.int32 or not start_frames.is_contiguous():
+                raise ValueError("start_frames must be a contiguous int32 tensor")
+            starts, lo, hi = start_frames, int(extremes[0]), int(extremes[1])
+        else:
+            host = np.ascontiguousarray(np.asarray(start_frames), np.int32).ravel()
+            if host.size == 0:
+                raise ValueError("start_frames is empty")
+            lo, hi = (int(host.min()), int(host.max())) if extremes is None else (int(extremes[0]), int(extremes[1]))
+            starts = torch.from_numpy(host).to(clip.device)
+        B = int(starts.numel())
+        if tuple(emotion.shape) != (B, self.emotion_dim):
+            raise ValueError(f"shape mismatch: {B} start frames, emotion {tuple(emotion.shape)}")
+        self.reserve(B, 0)
+        if out is None:
+            out = torch.empty(B, self.num_blendshapes, device=clip.device, dtype=torch.float32)
+        with torch.cuda.device(clip.device):
+            check(self._lib.km_forward_clip(self._h, _ptr(clip), clip.shape[0], _ptr(starts), B, lo, hi, _ptr(emotion), _ptr(out),
+                                            _ptr(state), 1 if first else 0, _stream_ptr(clip.device)))
+        return out
+
     def set_option(self, name: str, value: int) -> None:
         """Run-time switch of this handle (km_set_option): e.g. ("seq_per_window", 1), ("core_split", 3)."""
         check(self._lib.km_set_option(self._h, name.encode(), int(value)))

@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._lib import KM_METRICS_COUNT, KM_METRICS_NAMES, check, load
+from ._lib import KM_LOSS_TERM_NAMES, KM_LOSS_TERMS, KM_METRICS_COUNT, KM_METRICS_NAMES, check, load
 
 REFERENCE_KEYS = KM_METRICS_NAMES[:16]           # BlendshapeMetrics.compute(), in the reference's order
 TEMPORAL_KEYS = ("temporal_consistency", "pred_smoothness", "target_smoothness")   # absent when one row was seen (:492)
@@ -234,6 +234,143 @@ class BlendshapeMetrics:
         m = self._all()
         keys = REFERENCE_KEYS + ((LIP_SYNC_KEYS + DIAGNOSTIC_KEYS) if lip_sync else ())
         return {k: m[k] for k in keys if k in m}
+
+
+# KoeMorphLoss's default weights (src/model/losses.py:36-47); the two DualStreamLoss terms are off unless asked for
+LOSS_TERM_DEFAULT_WEIGHTS = {"mse_weight": 1.0, "l1_weight": 0.1, "perceptual_weight": 0.5, "temporal_weight": 0.2,
+                             "sparsity_weight": 0.01, "smoothness_weight": 0.1, "landmark_weight": 0.3, "velocity_weight": 0.05,
+                             "ds_velocity_weight": 0.0, "ds_separation_weight": 0.0}
+
+
+class LossTerms:
+    """The loss by component, accumulated on the device (``km_loss_terms_*``, koemorph_amd/csrc/km_loss_terms.hip): what
+    the reference reads back per batch as the ``metrics`` dict of ``KoeMorphLoss.forward`` (src/model/losses.py:111-183) and
+    averages over the batches of a validation pass (src/train_sequential.py:262-290).
+
+    ``update`` enqueues one call on the current stream and returns the batch's ``KM_LOSS_TERM_NAMES`` values as a device
+    tensor (float32, nothing is read back); ``compute`` enqueues the finalisation and does the only readback.  Weights given
+    to the constructor are the defaults of every ``update`` (``KoeMorphLoss``'s own where not given)."""
+
+    def __init__(self, **weights):
+        self._check_weights(weights)
+        self.weights = {**LOSS_TERM_DEFAULT_WEIGHTS, **weights}
+        self._acc = C.c_void_p()
+        self._device = None
+        self._lib = None
+        self.updates = 0
+
+    @staticmethod
+    def _check_weights(weights):
+        unknown = sorted(set(weights) - set(LOSS_TERM_DEFAULT_WEIGHTS))
+        if unknown:
+            raise TypeError(f"unknown loss weights {unknown}; known: {sorted(LOSS_TERM_DEFAULT_WEIGHTS)}")
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self._device).cuda_stream
+
+    def _open(self, device):
+        import torch
+        if self._acc and self._device != device:
+            self.close()
+        if not self._acc:
+            self._lib = load()
+            self._device = device
+            with torch.cuda.device(device):
+                check(self._lib.km_loss_terms_create(C.byref(self._acc)))
+
+    def close(self):
+        if self._acc:
+            import torch
+            torch.cuda.synchronize(self._device)
+            self._lib.km_loss_terms_destroy(self._acc)
+            self._acc = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self.updates = 0
+        if self._acc:
+            import torch
+            with torch.cuda.device(self._device):
+                check(self._lib.km_loss_terms_reset(self._acc, self._stream()))
+
+    def update(self, pred, target, prev_pred=None, prev_target=None, landmark_w=None, audio_energy=None, ds_prev_pred=None,
+               extra_terms: bool = True, **weights):
+        """Fold one batch in.  ``pred`` / ``target``: device tensors, any leading shape over 52 columns.  ``prev_pred`` /
+        ``prev_target`` (same shape) switch the temporal and velocity terms on, ``landmark_w`` (136, 52) the landmark term,
+        ``ds_prev_pred`` DualStreamLoss's velocity, ``ds_separation_weight`` > 0 its separation term; ``audio_energy`` (rows)
+        -- or audio features (rows, D) / (rows, T, D), reduced by ``km_audio_energy`` -- adds the audio-visual part to
+        ``perceptual``.  A term whose input is missing reports 0 and does not count in its mean.  ``extra_terms=False``
+        evaluates mse and l1 only (the C call with cfg = NULL)."""
+        import torch
+        from ._lib import KM_ABI_VERSION, KMLossConfig
+        self._check_weights(weights)
+        w = {**self.weights, **weights}
+        pred, target = _rows(pred, target)
+        if not bool(getattr(pred, "is_cuda", False)):
+            raise ValueError("LossTerms takes device tensors (the float64 restatement for host data is oracle.core.koemorph_loss)")
+        n = int(pred.shape[0])
+        if n == 0:
+            raise ValueError("LossTerms.update needs at least one row")
+        self._open(pred.device)
+        keep = []
+
+        def dev(t, shape):
+            if t is None:
+                return None
+            t = t.detach().to(self._device, torch.float32).reshape(shape).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+
+        pred = pred.detach().to(torch.float32).contiguous()
+        target = target.detach().to(self._device, torch.float32).contiguous()
+        with torch.cuda.device(self._device):
+            energy = None
+            if audio_energy is not None:
+                if audio_energy.dim() == 1:
+                    energy = dev(audio_energy, (n,))
+                else:
+                    af = audio_energy.detach().to(self._device, torch.float32).contiguous()
+                    if af.dim() == 2:
+                        af = af.unsqueeze(1)
+                    if af.dim() != 3 or int(af.shape[0]) != n:
+                        raise ValueError(f"audio features must be (rows, D) or (rows, T, D) with {n} rows, got {tuple(af.shape)}")
+                    e = torch.empty(n, device=self._device)
+                    check(self._lib.km_audio_energy(af.data_ptr(), n, af.shape[1], af.shape[2], e.data_ptr(), self._stream()))
+                    keep.append(e)
+                    energy = e.data_ptr()
+            cfg = None
+            if extra_terms:
+                cfg = KMLossConfig(KM_ABI_VERSION, w["perceptual_weight"], w["temporal_weight"], w["sparsity_weight"],
+                                   w["smoothness_weight"], w["landmark_weight"], w["velocity_weight"], dev(prev_pred, (n, 52)),
+                                   dev(prev_target, (n, 52)), dev(landmark_w, (136, 52)), energy, w["ds_velocity_weight"],
+                                   w["ds_separation_weight"], dev(ds_prev_pred, (n, 52)))
+            terms = torch.empty(KM_LOSS_TERMS, device=self._device)
+            check(self._lib.km_loss_terms_update(self._acc, None if cfg is None else C.byref(cfg), w["mse_weight"], w["l1_weight"],
+                                                 pred.data_ptr(), target.data_ptr(), n, terms.data_ptr(), self._stream()))
+        self.updates += 1
+        return terms
+
+    def compute(self) -> Dict[str, float]:
+        """Means over the updates since the last reset: one key per ``KM_LOSS_TERM_NAMES`` entry (a term's mean runs over the
+        updates that evaluated it; 0.0 if none did), ``updates``, and ``row_smoothness`` = the mean over all rows of
+        mean_j |pred[b, j + 1] - pred[b, j]|.  ``{}`` before any update.  One readback."""
+        if self.updates == 0:
+            return {}
+        import torch
+        with torch.cuda.device(self._device):
+            out = torch.empty(KM_LOSS_TERMS + 2, device=self._device)
+            check(self._lib.km_loss_terms_compute(self._acc, out.data_ptr(), self._stream()))
+            v = out.cpu().numpy()
+        m = {k: float(v[i]) for i, k in enumerate(KM_LOSS_TERM_NAMES)}
+        m["updates"] = float(v[KM_LOSS_TERMS])
+        m["row_smoothness"] = float(v[KM_LOSS_TERMS + 1])
+        return m
 
 
 def compute_lip_sync_metrics(pred_blendshapes, target_blendshapes, audio_features=None) -> Dict[str, float]:

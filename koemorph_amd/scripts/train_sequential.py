@@ -28,7 +28,7 @@ import torch
 from .. import parallel, synth
 from ..data import SequentialKoeMorphDataset
 from ..engine import Engine
-from ..metrics import BlendshapeMetrics
+from ..metrics import BlendshapeMetrics, LossTerms
 from ..training import Trainer
 
 logger = logging.getLogger(__name__)
@@ -59,6 +59,9 @@ class SequentialTrainer:
                                dropout=dropout, seed=seed + self.rank)
         if extra_loss_terms:
             self.trainer.set_loss_terms(**extra_loss_terms)
+        self.mse_weight, self.l1_weight = mse_weight, l1_weight
+        self.extra_loss_terms = dict(extra_loss_terms or {})
+        self._val_clip_logged = False
         self.epoch = 0
         self.global_step = 0
         self.best_val_loss = float("inf")
@@ -138,11 +141,15 @@ class SequentialTrainer:
             bm.close()
         return out
 
-    def validate(self, metrics: bool = False) -> Dict[str, float]:
+    def validate(self, metrics: bool = False, components: bool = False) -> Dict[str, float]:
         """``metrics=True``: the reference's validation metrics (src/train.py:239, :260-298) over every window of the pass,
-        accumulated on the device with no host round trip per batch and merged into the result; "total" is unchanged."""
+        accumulated on the device with no host round trip per batch and merged into the result; "total" is unchanged.
+        ``components=True``: the loss by component and per-sequence statistics, as the reference's validate() reports them
+        (src/train_sequential.py:213-295), see ``_validate_components``."""
         if self.val_data is None:
             return {}
+        if components:
+            return self._validate_components(metrics)
         self.trainer.sync_inference_weights()
         total, n = 0.0, 0
         bm = BlendshapeMetrics() if metrics else None
@@ -162,6 +169,91 @@ class SequentialTrainer:
                 total += float(torch.nn.functional.mse_loss(pred, batch["target"]).item())
                 n += 1
         out = {"total": total / max(n, 1), "batches": n}
+        if bm is not None:
+            out.update(bm.compute())
+            bm.close()
+        return out
+
+    def _loss_term_inputs(self):
+        """The trainer's own weights and the static inputs of its extra terms, as ``LossTerms.update`` takes them; the
+        per-batch inputs (prev_pred / prev_target / ds_prev_pred / audio features) are validation's own."""
+        ex = self.extra_loss_terms
+        weights = {"mse_weight": self.mse_weight, "l1_weight": self.l1_weight}
+        for k in ("perceptual_weight", "temporal_weight", "sparsity_weight", "smoothness_weight", "landmark_weight", "velocity_weight",
+                  "ds_velocity_weight", "ds_separation_weight"):
+            weights[k] = float(ex.get(k, 0.0))
+        return weights, ex.get("landmark_weights")
+
+    def _validate_components(self, metrics: bool) -> Dict[str, float]:
+        """The validation pass with the loss summed by component on the device (``LossTerms``): no ``.item()`` per batch.
+        Batches that name their windows inside the resident clip go through ``Engine.forward_clip`` -- no window copy, the
+        STFT frames the windows share computed once, same bits -- under the conditions ``train_epoch`` applies to
+        ``step_clip`` (``from_clip``, no emotion provider) and where ``forward_clip_supported()``; every other batch is
+        gathered.  ``prev_pred`` / ``prev_target`` of a batch are the previous batch's prediction and target of the same
+        file (absent on a file's first batch and when the batch size changes: the EMA state's own ``first`` rule).
+        Returns "total" (mean per-batch MSE), "batches", one key per loss term, "weighted_total", and "sequence_stats":
+        ``{file name or index: {"loss", "smoothness", "batches"}}``, read back once per file."""
+        self.trainer.sync_inference_weights()
+        weights, landmark_w = self._loss_term_inputs()
+        clip_ok = self.from_clip and self.emotion_provider is None and self.engine.forward_clip_supported()
+        lt_all, lt_file = LossTerms(**weights), LossTerms(**weights)
+        bm = BlendshapeMetrics() if metrics else None
+        stats: Dict[object, Dict[str, float]] = {}
+        state = prev_pred = prev_target = None
+        current = current_name = None
+        n = 0
+
+        def close_file():
+            m = lt_file.compute()                            # the one readback per file
+            if m:
+                stats[current_name] = {"loss": m["total"], "smoothness": m["row_smoothness"], "batches": int(m["updates"])}
+            lt_file.reset()
+
+        with torch.no_grad():
+            for batch in self.val_data:
+                file_idx = int(batch["file_indices"][0])
+                B = batch["target"].shape[0]
+                new_file = current != file_idx
+                first = new_file or state is None or state.shape[0] != B
+                if new_file:
+                    if current is not None:
+                        close_file()
+                    names = batch.get("file_names")
+                    current, current_name = file_idx, (names[0] if names else file_idx)
+                if first:
+                    state, prev_pred, prev_target = torch.zeros(B, 52, device=self.device), None, None
+                if "clip_audio" in batch and "audio" not in batch and clip_ok:
+                    sf = batch["start_frames"]
+                    pred = self.engine.forward_clip(batch["clip_audio"], batch["start_frames_dev"], self._emotion(batch), state=state,
+                                                    first=first, extremes=(int(sf.min()), int(sf.max())))
+                else:
+                    if "clip_audio" in batch and "audio" not in batch and not self._val_clip_logged:
+                        self._val_clip_logged = True
+                        logger.info("resident-window validation batches are gathered before the forward (%s)",
+                                    "the emotion provider reads window audio" if self.emotion_provider is not None else
+                                    ("from_clip is off" if not self.from_clip else "forward_clip is not supported at this shape"))
+                    batch = self._with_audio(batch)
+                    pred = self.engine.forward_audio(batch["audio"], self._emotion(batch), state=state, first=first)
+                target = batch["target"]
+                kw = dict(prev_pred=prev_pred, prev_target=prev_target, landmark_w=landmark_w,
+                          ds_prev_pred=prev_pred if weights["ds_velocity_weight"] > 0 else None)
+                lt_all.update(pred, target, **kw)
+                lt_file.update(pred, target, **kw)
+                if bm is not None:
+                    bm.update(pred, target)
+                prev_pred, prev_target = pred, target
+                n += 1
+        if current is not None:
+            close_file()
+        m = lt_all.compute()
+        out = {"total": m.get("mse", 0.0), "batches": n}
+        for k, v in m.items():
+            if k == "total":
+                out["weighted_total"] = v
+            elif k not in ("updates", "row_smoothness"):
+                out[k] = v
+        out["sequence_stats"] = stats
+        lt_all.close(); lt_file.close()
         if bm is not None:
             out.update(bm.compute())
             bm.close()
@@ -228,6 +320,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resident-clip", dest="resident_clip", action="store_true",
                    help="train from the clips resident in GPU memory (Trainer.step_clip): no window copies, the STFT frames the "
                         "windows of a batch share are computed once; same losses and weights")
+    p.add_argument("--loss-components", dest="loss_components", action="store_true",
+                   help="validation reports the loss by component (LossTerms) and per-sequence loss / smoothness; with "
+                        "--resident-clip the validation forward runs from the resident clip (Engine.forward_clip)")
     p.add_argument("--metrics", action="store_true", help="log mae / rmse / mean_correlation / f1_score of every epoch (BlendshapeMetrics)")
     return p
 
@@ -244,7 +339,7 @@ def main(argv=None):
     kw = dict(window_frames=args.window_frames, stride_frames=args.stride_frames, shuffle_files=False, loop_dataset=False,
               batch_size=args.batch_size, device=device, max_files=args.max_files)
     train = SequentialKoeMorphDataset(args.data_dir, resident_windows=args.resident_clip, **kw)
-    val = SequentialKoeMorphDataset(args.val_dir, **kw) if args.val_dir else None
+    val = SequentialKoeMorphDataset(args.val_dir, resident_windows=args.resident_clip and args.loss_components, **kw) if args.val_dir else None
     st = SequentialTrainer(eng, train, val, device=device, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
                            gradient_clip=args.gradient_clip, l1_weight=args.l1_weight, dropout=args.dropout, seed=args.seed,
                            from_clip=args.resident_clip)
@@ -252,13 +347,17 @@ def main(argv=None):
         st.load_checkpoint(args.resume)
     for _ in range(st.epoch, args.epochs):
         m = st.train_epoch(metrics=args.metrics)
-        v = st.validate(metrics=args.metrics)
+        v = st.validate(metrics=args.metrics, components=args.loss_components)
         is_best = bool(v) and v["total"] < st.best_val_loss
         if is_best:
             st.best_val_loss = v["total"]
         if rank == 0:
             logger.info(f"epoch {st.epoch}: train {m['total']:.6f} ({m['batches']} steps, {m['seconds']:.1f} s, lr {m['lr']:.2e})"
                         + (f", val {v['total']:.6f}" if v else ""))
+            if args.loss_components and v:
+                logger.info("  val terms: " + ", ".join(f"{k} {v[k]:.6f}" for k in ("mse", "l1", "perceptual", "temporal", "velocity",
+                                                                                    "sparsity", "smoothness", "landmark") if k in v)
+                            + f"; {len(v['sequence_stats'])} sequences")
             if args.metrics:                                 # the reference logs these four per epoch (src/train.py:368-373)
                 for tag, d in (("train", m), ("val", v)):
                     if "mae" in d:
