@@ -384,6 +384,62 @@ int km_legacy_create(const km_legacy_config* cfg, km_handle* out);
 int km_legacy_forward(km_handle h, const float* audio_dev, int64_t B, int64_t L, float* out_dev, void* stream);
 int km_legacy_forward_mel(km_handle h, const float* mel_dev, int64_t B, int64_t T_mel, float* out_dev, void* stream);
 
+/* ---- training step of the legacy single-stream variant -------------------------------------------------------
+ * What the reference's main trainer does to SimplifiedKoeMorphModel (src/train.py:82-96 builds it, :165-249 is the loop): the
+ * model under .train() (src/model/simplified_model.py:44-72, :114-149), KoeMorphLoss (src/model/losses.py:89-178), backward,
+ * clip_grad_norm_ and AdamW.  Default width only: d_model 256, 8 heads, decoder hidden 128, 52 blendshapes, 80 mel bins, any
+ * number of frames; km_legacy_train_init on any other legacy handle returns KM_ERR_UNSUPPORTED, never another result.  The
+ * km_train_* family keeps refusing legacy handles, this one refuses dual-stream handles.  Parameters, AdamW moments and the
+ * gradient are FLAT fp32 vectors in state-dict order with 16-byte-aligned offsets, the gradient caller-owned.
+ *   km_legacy_train_init         allocate the training state and the step's workspace for up to max_windows windows of up to
+ *                                max_frames mel frames and upload the loaded parameters (allocates; call after km_finalize)
+ *   km_legacy_train_num_params / km_legacy_train_param_offset   size of the flat vectors / offset of a state-dict key (-1: unknown)
+ *   km_legacy_train_step_mel     mel_dev (B, T, 80), target_dev (B, 52) -> flat_grad_dev (all of it is written, nothing is
+ *                                accumulated), loss_dev (1), out_dev (B, 52) or NULL: forward (simplified_model.py:129-147), loss =
+ *                                mse_weight * MSE + l1_weight * L1 (losses.py:112-121) + the terms of km_legacy_train_set_loss,
+ *                                backward (train.py:190-193).  Two calls with the same inputs and dropout step give the same bits;
+ *                                no allocation, so the call can be captured into a hipGraph after one eager call
+ *   km_legacy_train_step_audio   the same from audio_dev (B, L): km_mel_batch's front end (extract_mel_features, :79-112; no
+ *                                gradient flows into it: a NumPy round trip in the reference), then the step from mel -- bit-identical
+ *                                to km_mel_batch followed by km_legacy_train_step_mel.  Needs km_reserve(B, L)
+ *   km_legacy_train_set_loss     the remaining KoeMorphLoss terms as km_train_set_loss takes them (perceptual, temporal, velocity,
+ *                                sparsity, smoothness, landmark); the audio-visual and ds_* terms are KM_ERR_UNSUPPORTED here
+ *   km_legacy_train_adamw        clip_grad_norm_ + AdamW.step (train.py:195-203); contract and implementation of km_train_adamw
+ *   km_legacy_train_get_params / _set_params / _get_optimizer_state / _set_optimizer_state   as their km_train_* twins
+ *                                (checkpoints, train.py:262-283)
+ *   km_legacy_train_sync         km_legacy_forward* and the state dict (km_get_param) see the trained weights, as km_train_sync
+ *   km_legacy_train_set_dropout  training-mode dropout of the five sites of the model (simplified_model.py:44-72): p in [0, 1),
+ *                                masks drawn per step by the Philox4x32-10 generator of km_train_set_dropout, or given by the
+ *                                caller (external_masks != 0); p = 0 (the state after init) is eval-mode arithmetic
+ *   km_legacy_train_get_dropout_masks / _set_dropout_masks   keep flags (1 = kept) of a (B, T) step as bytes on the host:
+ *                                enc1 (B, T, 256), enc2 (B, T, 256) behind the encoder's two ReLUs, attn (B, 8, 52, T) on the
+ *                                softmaxed attention weights (as nn.MultiheadAttention applies its dropout), dec1 (B, 52, 128),
+ *                                dec2 (B, 52, 128) behind the decoder's two ReLUs
+ *   km_legacy_train_get_dropout_step / _set_dropout_step   the generator's device-side step counter (advanced by every step) */
+int km_legacy_train_init(km_handle h, int64_t max_windows, int64_t max_frames, void* stream);
+int64_t km_legacy_train_num_params(km_handle h);
+int64_t km_legacy_train_param_offset(km_handle h, const char* key);
+int km_legacy_train_step_mel(km_handle h, const float* mel_dev, int64_t B, int64_t T, const float* target_dev, float mse_weight,
+                             float l1_weight, float* flat_grad_dev, float* loss_dev, float* out_dev, void* stream);
+int km_legacy_train_step_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* target_dev, float mse_weight,
+                               float l1_weight, float* flat_grad_dev, float* loss_dev, float* out_dev, void* stream);
+int km_legacy_train_set_loss(km_handle h, const km_loss_config* cfg);
+int km_legacy_train_adamw(km_handle h, const float* flat_grad_dev, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, float max_grad_norm, int64_t step, void* stream);
+int km_legacy_train_get_params(km_handle h, float* flat_host, int64_t n);
+int km_legacy_train_set_params(km_handle h, const float* flat_host, int64_t n);
+int km_legacy_train_get_optimizer_state(km_handle h, float* exp_avg_host, float* exp_avg_sq_host, int64_t n, int32_t* steps2_host);
+int km_legacy_train_set_optimizer_state(km_handle h, const float* exp_avg_host, const float* exp_avg_sq_host, int64_t n,
+                                        const int32_t* steps2_host);
+int km_legacy_train_sync(km_handle h, void* stream);
+int km_legacy_train_set_dropout(km_handle h, float p, uint64_t seed, int32_t external_masks);
+int km_legacy_train_get_dropout_step(km_handle h, int64_t* step);
+int km_legacy_train_set_dropout_step(km_handle h, int64_t step);
+int km_legacy_train_get_dropout_masks(km_handle h, int64_t B, int64_t T, uint8_t* enc1_host, uint8_t* enc2_host, uint8_t* attn_host,
+                                      uint8_t* dec1_host, uint8_t* dec2_host, void* stream);
+int km_legacy_train_set_dropout_masks(km_handle h, int64_t B, int64_t T, const uint8_t* enc1_host, const uint8_t* enc2_host,
+                                      const uint8_t* attn_host, const uint8_t* dec1_host, const uint8_t* dec2_host, void* stream);
+
 /* ---- legacy multi-layer model: KoeMorphModel (src/model/gaussian_face.py:29-268) -----------------------
  * The model behind create_koemorph_model / scripts/rt.py:283-304, eval mode: DualStreamEncoder on both feature streams
  * (Linear + ReLU + LayerNorm, then num_encoder_layers post-norm nn.TransformerEncoderLayer with 8 heads, 4 d feed-forward,

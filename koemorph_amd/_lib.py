@@ -137,6 +137,23 @@ SIGNATURES = {
     "km_legacy_create": (C.c_int, [C.POINTER(KMLegacyConfig), C.POINTER(_h)]),
     "km_legacy_forward": (C.c_int, [_h, _p, _i64, _i64, _p, _p]),
     "km_legacy_forward_mel": (C.c_int, [_h, _p, _i64, _i64, _p, _p]),
+    "km_legacy_train_init": (C.c_int, [_h, _i64, _i64, _p]),
+    "km_legacy_train_num_params": (_i64, [_h]),
+    "km_legacy_train_param_offset": (_i64, [_h, C.c_char_p]),
+    "km_legacy_train_step_mel": (C.c_int, [_h, _p, _i64, _i64, _p, C.c_float, C.c_float, _p, _p, _p, _p]),
+    "km_legacy_train_step_audio": (C.c_int, [_h, _p, _i64, _i64, _p, C.c_float, C.c_float, _p, _p, _p, _p]),
+    "km_legacy_train_set_loss": (C.c_int, [_h, C.POINTER(KMLossConfig)]),
+    "km_legacy_train_adamw": (C.c_int, [_h, _p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _i64, _p]),
+    "km_legacy_train_get_params": (C.c_int, [_h, _p, _i64]),
+    "km_legacy_train_set_params": (C.c_int, [_h, _p, _i64]),
+    "km_legacy_train_get_optimizer_state": (C.c_int, [_h, _p, _p, _i64, _p]),
+    "km_legacy_train_set_optimizer_state": (C.c_int, [_h, _p, _p, _i64, _p]),
+    "km_legacy_train_sync": (C.c_int, [_h, _p]),
+    "km_legacy_train_set_dropout": (C.c_int, [_h, C.c_float, C.c_uint64, _i32]),
+    "km_legacy_train_get_dropout_step": (C.c_int, [_h, C.POINTER(_i64)]),
+    "km_legacy_train_set_dropout_step": (C.c_int, [_h, _i64]),
+    "km_legacy_train_get_dropout_masks": (C.c_int, [_h, _i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "km_legacy_train_set_dropout_masks": (C.c_int, [_h, _i64, _i64, _p, _p, _p, _p, _p, _p]),
     "km_koemorph_create": (C.c_int, [C.POINTER(KMKoeMorphConfig), C.POINTER(_h)]),
     "km_koemorph_reserve": (C.c_int, [_h, _i64, _i64]),
     "km_koemorph_forward": (C.c_int, [_h, _p, _p, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p, _p]),

@@ -39,6 +39,15 @@ static int need_dual(Context* c) {
     return KM_OK;
 }
 
+static int need_legacy_train(Context* c, int64_t B) {
+    if (int rc = need_ready(c)) return rc;
+    if (c->kind != 1) return fail(KM_ERR_INVALID_ARG, "this entry point needs a legacy handle (km_legacy_create)");
+    if (!c->tr_params || !c->ltr_ws) return fail(KM_ERR_NOT_FINALIZED, "call km_legacy_train_init first");
+    if (B <= 0 || B > c->tr_windows) return fail(KM_ERR_WORKSPACE, "km_legacy_train_init sized the step for %lld windows, got %lld",
+                                                 (long long)c->tr_windows, (long long)B);
+    return KM_OK;
+}
+
 namespace km { LogParams plan_log_params(MelPlan* p); }
 
 extern "C" {
@@ -230,6 +239,9 @@ static int free_train(Context* c) {
     if (c->trp_tail_ctr) { HIP_TRY(hipFree(c->trp_tail_ctr)); c->trp_tail_ctr = nullptr; }
     if (c->trp_masks) { HIP_TRY(hipFree(c->trp_masks)); c->trp_masks = nullptr; }
     if (c->trp_drop_ctr) { HIP_TRY(hipFree(c->trp_drop_ctr)); c->trp_drop_ctr = nullptr; }
+    if (c->ltr_ws) { HIP_TRY(hipFree(c->ltr_ws)); c->ltr_ws = nullptr; c->ltr_ws_floats = 0; }
+    if (c->ltr_part) { HIP_TRY(hipFree(c->ltr_part)); c->ltr_part = nullptr; }
+    if (c->ltr_masks) { HIP_TRY(hipFree(c->ltr_masks)); c->ltr_masks = nullptr; c->ltr_mask_bytes = 0; }
     if (c->tr_early_ev) { (void)hipEventDestroy((hipEvent_t)c->tr_early_ev); c->tr_early_ev = nullptr; }
     c->tr_windows = 0;
     return KM_OK;
@@ -462,16 +474,22 @@ int km_train_wait_early(km_handle h, void* stream) {
     return KM_OK;
 }
 
-int km_train_set_dropout(km_handle h, float p, uint64_t seed, int32_t external_masks) {
-    if (int rc = need_train(h, 1)) return rc;
+static int train_set_dropout_impl(km_handle h, float p, uint64_t seed, int32_t external_masks) {
     if (!(p >= 0.f && p < 1.f)) return fail(KM_ERR_INVALID_ARG, "dropout probability has to be in [0, 1), but got %g", (double)p);
     h->tr_dropout_p = p; h->tr_dropout_seed = seed; h->tr_dropout_mode = external_masks ? 1 : 0;
     return KM_OK;
 }
-
-int km_train_get_dropout_step(km_handle h, int64_t* step) {
+int km_train_set_dropout(km_handle h, float p, uint64_t seed, int32_t external_masks) {
     if (int rc = need_train(h, 1)) return rc;
-    if (!step) return fail(KM_ERR_INVALID_ARG, "km_train_get_dropout_step: NULL argument");
+    return train_set_dropout_impl(h, p, seed, external_masks);
+}
+int km_legacy_train_set_dropout(km_handle h, float p, uint64_t seed, int32_t external_masks) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    return train_set_dropout_impl(h, p, seed, external_masks);
+}
+
+static int train_get_dropout_step_impl(const char* fn, km_handle h, int64_t* step) {
+    if (!step) return fail(KM_ERR_INVALID_ARG, "%s: NULL argument", fn);
     int v = 0;
     if (h->trp_drop_ctr) {
         HIP_TRY(hipDeviceSynchronize());
@@ -480,15 +498,30 @@ int km_train_get_dropout_step(km_handle h, int64_t* step) {
     *step = v;
     return KM_OK;
 }
-
-int km_train_set_dropout_step(km_handle h, int64_t step) {
+int km_train_get_dropout_step(km_handle h, int64_t* step) {
     if (int rc = need_train(h, 1)) return rc;
-    if (step < 0 || step > 0x7fffffff) return fail(KM_ERR_INVALID_ARG, "km_train_set_dropout_step: step out of range");
-    if (!h->trp_drop_ctr) return fail(KM_ERR_NOT_READY, "km_train_set_dropout_step: the phased training step is not initialised");
+    return train_get_dropout_step_impl("km_train_get_dropout_step", h, step);
+}
+int km_legacy_train_get_dropout_step(km_handle h, int64_t* step) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    return train_get_dropout_step_impl("km_legacy_train_get_dropout_step", h, step);
+}
+
+static int train_set_dropout_step_impl(const char* fn, km_handle h, int64_t step) {
+    if (step < 0 || step > 0x7fffffff) return fail(KM_ERR_INVALID_ARG, "%s: step out of range", fn);
+    if (!h->trp_drop_ctr) return fail(KM_ERR_NOT_READY, "%s: the training step is not initialised", fn);
     const int v = (int)step;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h->trp_drop_ctr, &v, sizeof(int), hipMemcpyHostToDevice));
     return KM_OK;
+}
+int km_train_set_dropout_step(km_handle h, int64_t step) {
+    if (int rc = need_train(h, 1)) return rc;
+    return train_set_dropout_step_impl("km_train_set_dropout_step", h, step);
+}
+int km_legacy_train_set_dropout_step(km_handle h, int64_t step) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    return train_set_dropout_step_impl("km_legacy_train_set_dropout_step", h, step);
 }
 
 int km_train_get_dropout_masks(km_handle h, int64_t B, uint8_t* mel_host, uint8_t* emo_host, uint8_t* dec_host, void* stream) {
@@ -509,8 +542,7 @@ int km_audio_energy(const float* features_dev, int64_t B, int64_t T, int64_t D, 
     return launch_audio_energy(features_dev, B, T, D, energy_dev, stream);
 }
 
-int km_train_set_loss(km_handle h, const km_loss_config* cfg) {
-    if (int rc = need_train(h, 1)) return rc;
+static int train_set_loss_impl(km_handle h, const km_loss_config* cfg) {
     Context* c = h;
     // the struct has grown since ABI version 1 and holds device pointers the loss tail dereferences: a caller built against
     // an older header must be refused, not read past
@@ -519,55 +551,103 @@ int km_train_set_loss(km_handle h, const km_loss_config* cfg) {
     if (cfg) c->tr_loss_cfg = *cfg; else c->tr_loss_cfg = km_loss_config{};
     return KM_OK;
 }
+int km_train_set_loss(km_handle h, const km_loss_config* cfg) {
+    if (int rc = need_train(h, 1)) return rc;
+    return train_set_loss_impl(h, cfg);
+}
+int km_legacy_train_set_loss(km_handle h, const km_loss_config* cfg) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    if (cfg && (cfg->audio_energy_dev || cfg->ds_velocity_weight != 0.f || cfg->ds_separation_weight != 0.f))
+        return fail(KM_ERR_UNSUPPORTED, "km_legacy_train_set_loss: the audio-visual and DualStreamLoss terms belong to the dual-stream step");
+    return train_set_loss_impl(h, cfg);
+}
 
+static int train_adamw_impl(const char* fn, km_handle h, const float* flat_grad_dev, float lr, float beta1, float beta2, float eps,
+                   float weight_decay, float max_grad_norm, int64_t step, void* stream) {
+    if (!flat_grad_dev || step < 1) return fail(KM_ERR_INVALID_ARG, "%s: bad argument", fn);
+    return train_adamw(h, flat_grad_dev, lr, beta1, beta2, eps, weight_decay, max_grad_norm, step, stream);
+}
 int km_train_adamw(km_handle h, const float* flat_grad_dev, float lr, float beta1, float beta2, float eps,
                    float weight_decay, float max_grad_norm, int64_t step, void* stream) {
     if (int rc = need_train(h, 1)) return rc;
-    if (!flat_grad_dev || step < 1) return fail(KM_ERR_INVALID_ARG, "km_train_adamw: bad argument");
-    return train_adamw(h, flat_grad_dev, lr, beta1, beta2, eps, weight_decay, max_grad_norm, step, stream);
+    return train_adamw_impl("km_train_adamw", h, flat_grad_dev, lr, beta1, beta2, eps, weight_decay, max_grad_norm, step, stream);
+}
+int km_legacy_train_adamw(km_handle h, const float* flat_grad_dev, float lr, float beta1, float beta2, float eps,
+                   float weight_decay, float max_grad_norm, int64_t step, void* stream) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    return train_adamw_impl("km_legacy_train_adamw", h, flat_grad_dev, lr, beta1, beta2, eps, weight_decay, max_grad_norm, step, stream);
 }
 
-int km_train_get_params(km_handle h, float* flat_host, int64_t n) {
-    if (int rc = need_train(h, 1)) return rc;
-    if (!flat_host || n != h->tr_nparams) return fail(KM_ERR_INVALID_ARG, "km_train_get_params: size mismatch");
+static int train_get_params_impl(const char* fn, km_handle h, float* flat_host, int64_t n) {
+    if (!flat_host || n != h->tr_nparams) return fail(KM_ERR_INVALID_ARG, "%s: size mismatch", fn);
     HIP_TRY(hipMemcpy(flat_host, h->tr_params, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return KM_OK;
 }
-
-int km_train_set_params(km_handle h, const float* flat_host, int64_t n) {
+int km_train_get_params(km_handle h, float* flat_host, int64_t n) {
     if (int rc = need_train(h, 1)) return rc;
-    if (!flat_host || n != h->tr_nparams) return fail(KM_ERR_INVALID_ARG, "km_train_set_params: size mismatch");
+    return train_get_params_impl("km_train_get_params", h, flat_host, n);
+}
+int km_legacy_train_get_params(km_handle h, float* flat_host, int64_t n) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    return train_get_params_impl("km_legacy_train_get_params", h, flat_host, n);
+}
+
+static int train_set_params_impl(const char* fn, km_handle h, const float* flat_host, int64_t n) {
+    if (!flat_host || n != h->tr_nparams) return fail(KM_ERR_INVALID_ARG, "%s: size mismatch", fn);
     HIP_TRY(hipMemcpy(h->tr_params, flat_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     if (int rc = train_refresh_padded_weights(h, nullptr)) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return KM_OK;
 }
-
-int km_train_get_optimizer_state(km_handle h, float* exp_avg_host, float* exp_avg_sq_host, int64_t n, int32_t* steps2_host) {
+int km_train_set_params(km_handle h, const float* flat_host, int64_t n) {
     if (int rc = need_train(h, 1)) return rc;
+    return train_set_params_impl("km_train_set_params", h, flat_host, n);
+}
+int km_legacy_train_set_params(km_handle h, const float* flat_host, int64_t n) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    return train_set_params_impl("km_legacy_train_set_params", h, flat_host, n);
+}
+
+static int train_get_optimizer_state_impl(const char* fn, km_handle h, float* exp_avg_host, float* exp_avg_sq_host, int64_t n, int32_t* steps2_host) {
     if (!exp_avg_host || !exp_avg_sq_host || !steps2_host || n != h->tr_nparams)
-        return fail(KM_ERR_INVALID_ARG, "km_train_get_optimizer_state: bad argument");
+        return fail(KM_ERR_INVALID_ARG, "%s: bad argument", fn);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(exp_avg_host, h->tr_m, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(exp_avg_sq_host, h->tr_v, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(steps2_host, h->tr_steps, 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
     return KM_OK;
 }
-
-int km_train_set_optimizer_state(km_handle h, const float* exp_avg_host, const float* exp_avg_sq_host, int64_t n,
-                                 const int32_t* steps2_host) {
+int km_train_get_optimizer_state(km_handle h, float* exp_avg_host, float* exp_avg_sq_host, int64_t n, int32_t* steps2_host) {
     if (int rc = need_train(h, 1)) return rc;
+    return train_get_optimizer_state_impl("km_train_get_optimizer_state", h, exp_avg_host, exp_avg_sq_host, n, steps2_host);
+}
+int km_legacy_train_get_optimizer_state(km_handle h, float* exp_avg_host, float* exp_avg_sq_host, int64_t n, int32_t* steps2_host) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    return train_get_optimizer_state_impl("km_legacy_train_get_optimizer_state", h, exp_avg_host, exp_avg_sq_host, n, steps2_host);
+}
+
+static int train_set_optimizer_state_impl(const char* fn, km_handle h, const float* exp_avg_host, const float* exp_avg_sq_host, int64_t n,
+                                 const int32_t* steps2_host) {
     if (!exp_avg_host || !exp_avg_sq_host || !steps2_host || n != h->tr_nparams)
-        return fail(KM_ERR_INVALID_ARG, "km_train_set_optimizer_state: bad argument");
+        return fail(KM_ERR_INVALID_ARG, "%s: bad argument", fn);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h->tr_m, exp_avg_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->tr_v, exp_avg_sq_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->tr_steps, steps2_host, 2 * sizeof(int32_t), hipMemcpyHostToDevice));
     return KM_OK;
 }
-
-int km_train_sync(km_handle h, void* stream) {
+int km_train_set_optimizer_state(km_handle h, const float* exp_avg_host, const float* exp_avg_sq_host, int64_t n,
+                                 const int32_t* steps2_host) {
     if (int rc = need_train(h, 1)) return rc;
+    return train_set_optimizer_state_impl("km_train_set_optimizer_state", h, exp_avg_host, exp_avg_sq_host, n, steps2_host);
+}
+int km_legacy_train_set_optimizer_state(km_handle h, const float* exp_avg_host, const float* exp_avg_sq_host, int64_t n,
+                                 const int32_t* steps2_host) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    return train_set_optimizer_state_impl("km_legacy_train_set_optimizer_state", h, exp_avg_host, exp_avg_sq_host, n, steps2_host);
+}
+
+static int train_sync_impl(km_handle h, void* stream) {
     Context* c = h;
     std::vector<float> flat((size_t)c->tr_nparams);
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -578,6 +658,80 @@ int km_train_sync(km_handle h, void* stream) {
     }
     c->host_finalized = false;
     return km_finalize(h, stream);
+}
+int km_train_sync(km_handle h, void* stream) {
+    if (int rc = need_train(h, 1)) return rc;
+    return train_sync_impl(h, stream);
+}
+int km_legacy_train_sync(km_handle h, void* stream) {
+    if (int rc = need_legacy_train(h, 1)) return rc;
+    return train_sync_impl(h, stream);
+}
+
+// ---- training step of the legacy model (kernels: km_legacy_train.hip; optimizer, parameter and state transfers: the
+// implementations of the km_train_* twins above) ----
+int km_legacy_train_init(km_handle h, int64_t max_windows, int64_t max_frames, void* stream) {
+    if (int rc = need_ready(h)) return rc;
+    Context* c = h;
+    if (c->kind != 1) return fail(KM_ERR_INVALID_ARG, "km_legacy_train_init needs a legacy handle (km_legacy_create)");
+    if (!legacy_train_supported(c))
+        return fail(KM_ERR_UNSUPPORTED, "km_legacy_train_init: the training step exists for d_model 256, 8 heads, decoder hidden 128, "
+                    "52 blendshapes and 80 mel bins only (got d_model %d, %d heads, hidden %d)", (int)c->d, (int)c->H, c->legacy_hidden);
+    if (max_windows <= 0 || max_frames <= 0) return fail(KM_ERR_INVALID_ARG, "km_legacy_train_init: bad argument");
+    if (int rc = free_train(c)) return rc;
+    return legacy_train_init(c, max_windows, max_frames, stream);
+}
+
+int64_t km_legacy_train_num_params(km_handle h) { return h && h->kind == 1 ? h->tr_nparams : -1; }
+
+int64_t km_legacy_train_param_offset(km_handle h, const char* key) {
+    if (!h || !key || h->kind != 1) return -1;
+    auto it = h->tr_offset.find(key);
+    return it == h->tr_offset.end() ? -1 : it->second;
+}
+
+int km_legacy_train_step_mel(km_handle h, const float* mel_dev, int64_t B, int64_t T, const float* target_dev, float mse_weight,
+                             float l1_weight, float* flat_grad_dev, float* loss_dev, float* out_dev, void* stream) {
+    if (int rc = need_legacy_train(h, B)) return rc;
+    if (!mel_dev || !target_dev || !flat_grad_dev || !loss_dev || T <= 0) return fail(KM_ERR_INVALID_ARG, "km_legacy_train_step_mel: bad argument");
+    if (T > h->ltr_frames) return fail(KM_ERR_WORKSPACE, "km_legacy_train_init sized the step for %lld frames, got %lld",
+                                       (long long)h->ltr_frames, (long long)T);
+    return legacy_train_step(h, mel_dev, B, T, target_dev, mse_weight, l1_weight, flat_grad_dev, loss_dev, out_dev, stream);
+}
+
+int km_legacy_train_step_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* target_dev, float mse_weight,
+                               float l1_weight, float* flat_grad_dev, float* loss_dev, float* out_dev, void* stream) {
+    if (int rc = need_legacy_train(h, B)) return rc;
+    Context* c = h;
+    if (!audio_dev || !target_dev || !flat_grad_dev || !loss_dev || L <= 0) return fail(KM_ERR_INVALID_ARG, "km_legacy_train_step_audio: bad argument");
+    const int64_t T = 1 + L / c->cfg.mel.hop_length;
+    if (T > c->ltr_frames) return fail(KM_ERR_WORKSPACE, "km_legacy_train_init sized the step for %lld frames, got %lld",
+                                       (long long)c->ltr_frames, (long long)T);
+    if (B > c->ws_windows || T > c->ws_frames)
+        return fail(KM_ERR_WORKSPACE, "workspace too small for %lld windows x %lld samples: call km_reserve", (long long)B, (long long)L);
+    // km_mel_batch into the step's own mel image, then the step from mel: the same launches, the same bits
+    float* mel = legacy_train_mel_buffer(c);
+    if (int rc = launch_mel(c, c->mel_plans[0], audio_dev, B, L, 0, mel, nullptr, stream)) return rc;
+    return legacy_train_step(c, mel, B, T, target_dev, mse_weight, l1_weight, flat_grad_dev, loss_dev, out_dev, stream);
+}
+
+int km_legacy_train_get_dropout_masks(km_handle h, int64_t B, int64_t T, uint8_t* enc1_host, uint8_t* enc2_host, uint8_t* attn_host,
+                                      uint8_t* dec1_host, uint8_t* dec2_host, void* stream) {
+    if (int rc = need_legacy_train(h, B)) return rc;
+    if (!enc1_host || !enc2_host || !attn_host || !dec1_host || !dec2_host || T <= 0 || T > h->ltr_frames)
+        return fail(KM_ERR_INVALID_ARG, "km_legacy_train_get_dropout_masks: bad argument");
+    unsigned char* const hp[5] = {enc1_host, enc2_host, attn_host, dec1_host, dec2_host};
+    return legacy_train_copy_masks(h, B, T, hp, 0, stream);
+}
+
+int km_legacy_train_set_dropout_masks(km_handle h, int64_t B, int64_t T, const uint8_t* enc1_host, const uint8_t* enc2_host,
+                                      const uint8_t* attn_host, const uint8_t* dec1_host, const uint8_t* dec2_host, void* stream) {
+    if (int rc = need_legacy_train(h, B)) return rc;
+    if (!enc1_host || !enc2_host || !attn_host || !dec1_host || !dec2_host || T <= 0 || T > h->ltr_frames)
+        return fail(KM_ERR_INVALID_ARG, "km_legacy_train_set_dropout_masks: bad argument");
+    unsigned char* const hp[5] = {const_cast<uint8_t*>(enc1_host), const_cast<uint8_t*>(enc2_host), const_cast<uint8_t*>(attn_host),
+                                  const_cast<uint8_t*>(dec1_host), const_cast<uint8_t*>(dec2_host)};
+    return legacy_train_copy_masks(h, B, T, hp, 1, stream);
 }
 
 int km_legacy_forward_mel(km_handle h, const float* mel_dev, int64_t B, int64_t T_mel, float* out_dev, void* stream) {

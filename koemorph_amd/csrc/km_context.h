@@ -172,6 +172,12 @@ struct Context {
     float tr_dropout_p = 0.f;        // training-mode dropout probability (0 = eval-mode arithmetic)
     int tr_dropout_mode = 0;         // 0: masks drawn per step (Philox), 1: masks supplied by the caller (km_train_set_dropout_masks)
     unsigned long long tr_dropout_seed = 0;
+    // training step of the legacy model (km_legacy_train.hip); parameters, moments, counters and dropout settings are the tr_* above
+    float* ltr_ws = nullptr; int64_t ltr_ws_floats = 0;   // activations and their gradients, carved for (tr_windows, ltr_frames)
+    int64_t ltr_frames = 0;
+    float* ltr_part = nullptr;       // split-K partials of one weight gradient, then of its bias gradient
+    unsigned char* ltr_masks = nullptr; int64_t ltr_mask_bytes = 0;   // keep flags: enc1 | enc2 | attn | dec1 | dec2, packed for the step's (B, T)
+    int64_t ltr_mask_B = 0, ltr_mask_T = 0;               // the (B, T) the masks on the device belong to
     // shared-frame sequence mode buffers (grow-only, allocated by km_sequence_forward)
     float* seq_pow = nullptr; unsigned* seq_fmax = nullptr; float* seq_edge = nullptr; unsigned* seq_emax = nullptr;
     int64_t seq_pow_cap = 0, seq_edge_cap = 0;
@@ -254,6 +260,14 @@ struct TrainStepArgs {
 int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in, const float* mel_short, const float* xp_dev,
                            const TrainAudioSrc* asrc, const TrainStepArgs& a);
 int launch_audio_energy(const float* feats, int64_t B, int64_t T, int64_t D, float* out, void* stream);
+
+// km_legacy_train.hip
+bool legacy_train_supported(Context* c);
+int legacy_train_init(Context* c, int64_t max_windows, int64_t max_frames, void* stream);
+float* legacy_train_mel_buffer(Context* c);
+int legacy_train_step(Context* c, const float* mel, int64_t B, int64_t T, const float* target, float mse_w, float l1_w, float* grad,
+                      float* loss_dev, float* out_dev, void* stream);
+int legacy_train_copy_masks(Context* c, int64_t B, int64_t T, unsigned char* const host[5], int to_device, void* stream);
 
 // km_generic.hip
 int64_t generic_ws_floats(Context* c);

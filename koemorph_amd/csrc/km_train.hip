@@ -162,10 +162,13 @@ int train_adamw(Context* c, const float* flat_grad, float lr, float b1, float b2
     // two launches: partial sums of squares (+ the step counters), then norm + clip + AdamW in one kernel
     hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, st, flat_grad, n, c->tr_part, c->tr_steps, c->tr_alpha_live ? 1 : 0);
     (void)step;
+    // the legacy model (km_legacy_train_*) has neither a smoothing_alpha nor a padded channel-encoder copy
+    const auto alpha_it = c->tr_offset.find("smoothing_alpha");
+    const int64_t alpha_idx = alpha_it == c->tr_offset.end() ? -1 : alpha_it->second;
+    const PaddedCopy pc = c->trp_wcep ? PaddedCopy{c->trp_wcep, c->tr_offset.at("mel_channel_encoder.weight"), (int64_t)c->d * c->KT, (int)c->KT, (int)trainp_kp(c)}
+                                      : PaddedCopy{nullptr, 0, 0, 1, 1};
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, st, c->tr_params, c->tr_m, c->tr_v, flat_grad, n,
-                       c->tr_part, c->tr_gnorm, max_norm, lr, b1, b2, eps, wd, c->tr_steps, c->tr_offset.at("smoothing_alpha"),
-                       c->tr_alpha_live ? 1 : 0,
-                       PaddedCopy{c->trp_wcep, c->tr_offset.at("mel_channel_encoder.weight"), (int64_t)c->d * c->KT, (int)c->KT, (int)trainp_kp(c)});
+                       c->tr_part, c->tr_gnorm, max_norm, lr, b1, b2, eps, wd, c->tr_steps, alpha_idx, c->tr_alpha_live ? 1 : 0, pc);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

@@ -52,6 +52,72 @@ struct TailArgs {
 // dL/dy -- the smoothness and landmark terms need the whole row of y, hence two passes.
 __device__ __forceinline__ float sgnf(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }   // torch: d|x|/dx = sign(x)
 
+// The terms of KoeMorphLoss that act on ONE coefficient of one row (losses.py:112-178: mse, l1, perceptual groups, temporal,
+// velocity, sparsity, smoothness; train_dual_stream.py:489-495 for the DualStreamLoss velocity).  One statement of them for every
+// tail: train_tail_dev, train_tail_window_dev and the legacy step's loss kernel (km_legacy_train.hip).  Lane i < 52 holds its
+// prediction y and target, its row neighbours y_left / y_right (read only where they exist) and, where the term is on, the
+// previous prediction / target (t_on, v_on), the DualStreamLoss previous prediction (dsv_on) and the audio-visual gradient of
+// its window (av_on).  The terms are added to loss_acc; e = y - target is left for the landmark term; returns dL/dy.
+struct TailCoef {
+    float y, tgt, y_left, y_right;
+    float pp_t, pt_t, pp_ds, av_g;
+    bool t_on, v_on, dsv_on, av_on;
+};
+
+__device__ __forceinline__ float tail_coef_terms(const km_loss_config& lc, float mse_w, float l1_w, int B, int i, const TailCoef& c, float& e_out,
+                                                 float& loss_acc) {
+    const float inv_n = 1.0f / (float)(B * 52);
+    // perceptual groups (losses.py:306-338): weight / group size
+    const float pg = i < 12 ? 1.0f / 12.f : (i < 32 ? 2.0f / 20.f : (i < 44 ? 1.0f / 12.f : 1.5f / 8.f));
+    const float y = c.y, e = y - c.tgt;
+    loss_acc += (mse_w * e * e + l1_w * fabsf(e)) * inv_n;
+    float dy = (mse_w * 2.0f * e + l1_w * sgnf(e)) * inv_n;
+    if (lc.perceptual_weight > 0.f) {
+        const float wgt = lc.perceptual_weight * pg / (float)B;
+        loss_acc += wgt * e * e;
+        dy += wgt * 2.0f * e;
+        if (c.av_on && i >= 12 && i < 32) dy += c.av_g;
+    }
+    if (c.t_on || c.v_on) {
+        const float dd = (y - c.pp_t) - (c.tgt - c.pt_t);
+        if (c.t_on) { loss_acc += lc.temporal_weight * dd * dd * inv_n; dy += lc.temporal_weight * 2.0f * dd * inv_n; }
+        if (c.v_on) { loss_acc += lc.velocity_weight * fabsf(dd) * inv_n; dy += lc.velocity_weight * sgnf(dd) * inv_n; }
+    }
+    if (c.dsv_on) {   // both differences against the SAME previous prediction
+        const float dd = (y - c.pp_ds) - (c.tgt - c.pp_ds);
+        loss_acc += lc.ds_velocity_weight * dd * dd * inv_n;
+        dy += lc.ds_velocity_weight * 2.0f * dd * inv_n;
+    }
+    if (lc.sparsity_weight > 0.f) { loss_acc += lc.sparsity_weight * fabsf(y) * inv_n; dy += lc.sparsity_weight * sgnf(y) * inv_n; }
+    if (lc.smoothness_weight > 0.f) {   // torch.diff along the 52 coefficients: 51 pairs per row
+        const float wgt = lc.smoothness_weight / (float)(B * 51);
+        if (i > 0) { const float dl = y - c.y_left; loss_acc += wgt * fabsf(dl); dy += wgt * sgnf(dl); }
+        if (i < 51) { const float dr = c.y_right - y; dy -= wgt * sgnf(dr); }
+    }
+    e_out = e;
+    return dy;
+}
+
+// The landmark term of one row, by the wave that owns the row: u = e W^T (136), loss = mean u^2, dL/de = 2 / (B 136) u W.  e_s (52)
+// holds the row's e, u_s (136) is scratch; only this wave touches them.  Adds to loss_acc (lane 0) and to dy (lanes i < 52).
+__device__ __forceinline__ void tail_landmark_term(const km_loss_config& lc, int B, int i, const float* e_s, float* u_s, float& dy, float& loss_acc) {
+    __builtin_amdgcn_wave_barrier();
+    for (int k = i; k < 136; k += 64) {
+        float u = 0.f;
+        for (int jj = 0; jj < 52; ++jj) u += e_s[jj] * lc.landmark_w_dev[k * 52 + jj];
+        u_s[k] = u;
+    }
+    __builtin_amdgcn_wave_barrier();
+    const float wgt = lc.landmark_weight / (float)(B * 136);
+    if (i < 52) {
+        float gsum = 0.f;
+        for (int k = 0; k < 136; ++k) gsum += u_s[k] * lc.landmark_w_dev[k * 52 + i];
+        dy += wgt * 2.0f * gsum;
+    }
+    if (i == 0) { float q = 0.f; for (int k = 0; k < 136; ++k) q += u_s[k] * u_s[k]; loss_acc += wgt * q; }
+    __builtin_amdgcn_wave_barrier();
+}
+
 // 8 waves: wave w owns windows w, w + 8, ...; lane i < 52 owns coefficient i (lanes up to 63 help with the landmark
 // products).  Per-thread partial sums run over a wave's windows in order and are combined across waves in wave order,
 // so the result does not depend on timing.
@@ -125,7 +191,6 @@ __device__ __forceinline__ void train_tail_dev(const TailArgs& a) {
     }
     __syncthreads();
     const float alpha = 1.0f / (1.0f + expf(-alpha_raw));
-    const float inv_n = 1.0f / (float)(a.B * 52);
     const bool ema_on = a.ema_state && !a.ema_first;
     // ---- pass A: y = EMA(clamp(wsum * sigmoid(z))) ----
     if (i < 52) {
@@ -197,41 +262,19 @@ __device__ __forceinline__ void train_tail_dev(const TailArgs& a) {
     const bool t_on = lc.temporal_weight > 0.f && have_prev, v_on = lc.velocity_weight > 0.f && have_prev;
     const bool lm_on = lc.landmark_weight > 0.f && lc.landmark_w_dev;
     const bool dsv_on = lc.ds_velocity_weight > 0.f && lc.ds_prev_pred_dev;
-    // perceptual groups (losses.py:306-338): weight / group size
-    float pg = 0.f;
-    if (i < 52) pg = i < 12 ? 1.0f / 12.f : (i < 32 ? 2.0f / 20.f : (i < 44 ? 1.0f / 12.f : 1.5f / 8.f));
     float loss_acc = 0.f, dws = 0.f, dal = 0.f, db2 = 0.f;
     for (int b = wg + G * w; b < a.B; b += G * NW) {
         float y = 0.f, e = 0.f, dy = 0.f;
         if (i < 52) {
-            y = a.out[(int64_t)b * 52 + i];
-            e = y - a.target[(int64_t)b * 52 + i];
-            loss_acc += (a.mse_w * e * e + a.l1_w * fabsf(e)) * inv_n;
-            dy = (a.mse_w * 2.0f * e + a.l1_w * sgnf(e)) * inv_n;
-            if (lc.perceptual_weight > 0.f) {
-                const float wgt = lc.perceptual_weight * pg / (float)a.B;
-                loss_acc += wgt * e * e;
-                dy += wgt * 2.0f * e;
-                if (av_on && i >= 12 && i < 32) dy += av_g[b];
-            }
-            if (t_on || v_on) {
-                const float dd = (y - lc.prev_pred_dev[(int64_t)b * 52 + i]) -
-                                 (a.target[(int64_t)b * 52 + i] - lc.prev_target_dev[(int64_t)b * 52 + i]);
-                if (t_on) { loss_acc += lc.temporal_weight * dd * dd * inv_n; dy += lc.temporal_weight * 2.0f * dd * inv_n; }
-                if (v_on) { loss_acc += lc.velocity_weight * fabsf(dd) * inv_n; dy += lc.velocity_weight * sgnf(dd) * inv_n; }
-            }
-            if (dsv_on) {   // DualStreamLoss velocity (train_dual_stream.py:489-495): both differences against the SAME previous prediction
-                const float pp = lc.ds_prev_pred_dev[(int64_t)b * 52 + i];
-                const float dd = (y - pp) - (a.target[(int64_t)b * 52 + i] - pp);
-                loss_acc += lc.ds_velocity_weight * dd * dd * inv_n;
-                dy += lc.ds_velocity_weight * 2.0f * dd * inv_n;
-            }
-            if (lc.sparsity_weight > 0.f) { loss_acc += lc.sparsity_weight * fabsf(y) * inv_n; dy += lc.sparsity_weight * sgnf(y) * inv_n; }
-            if (lc.smoothness_weight > 0.f) {   // torch.diff along the 52 coefficients: 51 pairs per row
-                const float wgt = lc.smoothness_weight / (float)(a.B * 51);
-                if (i > 0) { const float dl = y - a.out[(int64_t)b * 52 + i - 1]; loss_acc += wgt * fabsf(dl); dy += wgt * sgnf(dl); }
-                if (i < 51) { const float dr = a.out[(int64_t)b * 52 + i + 1] - y; dy -= wgt * sgnf(dr); }
-            }
+            const int64_t o = (int64_t)b * 52 + i;
+            TailCoef tc{};
+            y = tc.y = a.out[o]; tc.tgt = a.target[o];
+            if (lc.smoothness_weight > 0.f) { tc.y_left = i > 0 ? a.out[o - 1] : 0.f; tc.y_right = i < 51 ? a.out[o + 1] : 0.f; }
+            tc.t_on = t_on; tc.v_on = v_on; tc.dsv_on = dsv_on; tc.av_on = av_on;
+            if (t_on || v_on) { tc.pp_t = lc.prev_pred_dev[o]; tc.pt_t = lc.prev_target_dev[o]; }
+            if (dsv_on) tc.pp_ds = lc.ds_prev_pred_dev[o];
+            if (av_on) tc.av_g = av_g[b];
+            dy = tail_coef_terms(lc, a.mse_w, a.l1_w, a.B, i, tc, e, loss_acc);
             e_s[w][i] = e;
         }
         if (lc.ds_separation_weight > 0.f) {   // DualStreamLoss separation (train_dual_stream.py:498-514), one value per window
@@ -242,23 +285,7 @@ __device__ __forceinline__ void train_tail_dev(const TailArgs& a) {
             if (i == 0) loss_acc += wgt * fabsf(diff);
             if (i < 52) dy += wgt * sgnf(diff) * (mouth ? 1.0f / 28.0f : -1.0f / 24.0f);
         }
-        if (lm_on) {   // u = e W^T (136), loss = mean u^2, dL/de = 2/(B 136) u W; only this wave touches e_s[w], u_s[w]
-            __builtin_amdgcn_wave_barrier();
-            for (int k = i; k < 136; k += 64) {
-                float u = 0.f;
-                for (int jj = 0; jj < 52; ++jj) u += e_s[w][jj] * lc.landmark_w_dev[k * 52 + jj];
-                u_s[w][k] = u;
-            }
-            __builtin_amdgcn_wave_barrier();
-            const float wgt = lc.landmark_weight / (float)(a.B * 136);
-            if (i < 52) {
-                float gsum = 0.f;
-                for (int k = 0; k < 136; ++k) gsum += u_s[w][k] * lc.landmark_w_dev[k * 52 + i];
-                dy += wgt * 2.0f * gsum;
-            }
-            if (i == 0) { float q = 0.f; for (int k = 0; k < 136; ++k) q += u_s[w][k] * u_s[w][k]; loss_acc += wgt * q; }
-            __builtin_amdgcn_wave_barrier();
-        }
+        if (lm_on) tail_landmark_term(lc, a.B, i, e_s[w], u_s[w], dy, loss_acc);
         if (i < 52) {
             if (ema_on) dal += dy * a.xp[(int64_t)b * 52 + i] * alpha * (1.0f - alpha);
             const float df = dy * a.fac[(int64_t)b * 52 + i];
@@ -452,7 +479,6 @@ __device__ __forceinline__ void train_tail_window_dev(const TailArgs& a, float* 
         wm_i = i < 52 ? em / sm : 0.f; we_i = i < 52 ? ee / se : 0.f;
         const float wsum_i = 0.5f * wm_i + 0.5f * we_i;
         const float alpha = 1.0f / (1.0f + expf(-alpha_raw));
-        const float inv_n = 1.0f / (float)(a.B * 52);
         // ---- pass A: y = EMA(clamp(wsum * sigmoid(z))) ----
         float y = 0.f, bsig = 0.f, fac = 0.f, xp = 0.f;
         if (i < 52) {
@@ -475,35 +501,14 @@ __device__ __forceinline__ void train_tail_window_dev(const TailArgs& a, float* 
             a.xp[(int64_t)b * 52 + i] = xp;
         }
         // ---- pass B: loss terms and dL/dy ----
-        float pg = 0.f;
-        if (i < 52) pg = i < 12 ? 1.0f / 12.f : (i < 32 ? 2.0f / 20.f : (i < 44 ? 1.0f / 12.f : 1.5f / 8.f));
         const float y_left = __shfl_up(y, 1), y_right = __shfl_down(y, 1);
         float e = 0.f, dy = 0.f;
         if (i < 52) {
-            e = y - tgt;
-            loss_acc += (a.mse_w * e * e + a.l1_w * fabsf(e)) * inv_n;
-            dy = (a.mse_w * 2.0f * e + a.l1_w * sgnf(e)) * inv_n;
-            if (lc.perceptual_weight > 0.f) {
-                const float wgt = lc.perceptual_weight * pg / (float)a.B;
-                loss_acc += wgt * e * e;
-                dy += wgt * 2.0f * e;
-            }
-            if (t_on || v_on) {
-                const float dd = (y - pp_t) - (tgt - pt_t);
-                if (t_on) { loss_acc += lc.temporal_weight * dd * dd * inv_n; dy += lc.temporal_weight * 2.0f * dd * inv_n; }
-                if (v_on) { loss_acc += lc.velocity_weight * fabsf(dd) * inv_n; dy += lc.velocity_weight * sgnf(dd) * inv_n; }
-            }
-            if (dsv_on) {
-                const float dd = (y - pp_ds) - (tgt - pp_ds);
-                loss_acc += lc.ds_velocity_weight * dd * dd * inv_n;
-                dy += lc.ds_velocity_weight * 2.0f * dd * inv_n;
-            }
-            if (lc.sparsity_weight > 0.f) { loss_acc += lc.sparsity_weight * fabsf(y) * inv_n; dy += lc.sparsity_weight * sgnf(y) * inv_n; }
-            if (lc.smoothness_weight > 0.f) {
-                const float wgt = lc.smoothness_weight / (float)(a.B * 51);
-                if (i > 0) { const float dl = y - y_left; loss_acc += wgt * fabsf(dl); dy += wgt * sgnf(dl); }
-                if (i < 51) { const float dr = y_right - y; dy -= wgt * sgnf(dr); }
-            }
+            TailCoef tc{};
+            tc.y = y; tc.tgt = tgt; tc.y_left = y_left; tc.y_right = y_right;
+            tc.t_on = t_on; tc.v_on = v_on; tc.dsv_on = dsv_on;
+            tc.pp_t = pp_t; tc.pt_t = pt_t; tc.pp_ds = pp_ds;
+            dy = tail_coef_terms(lc, a.mse_w, a.l1_w, a.B, i, tc, e, loss_acc);
             e_s[i] = e;
         }
         if (lc.ds_separation_weight > 0.f) {
@@ -514,23 +519,7 @@ __device__ __forceinline__ void train_tail_window_dev(const TailArgs& a, float* 
             if (i == 0) loss_acc += wgt * fabsf(diff);
             if (i < 52) dy += wgt * sgnf(diff) * (mouth ? 1.0f / 28.0f : -1.0f / 24.0f);
         }
-        if (lm_on) {
-            __builtin_amdgcn_wave_barrier();
-            for (int k = i; k < 136; k += 64) {
-                float u = 0.f;
-                for (int jj = 0; jj < 52; ++jj) u += e_s[jj] * lc.landmark_w_dev[k * 52 + jj];
-                u_s[k] = u;
-            }
-            __builtin_amdgcn_wave_barrier();
-            const float wgt = lc.landmark_weight / (float)(a.B * 136);
-            if (i < 52) {
-                float gsum = 0.f;
-                for (int k = 0; k < 136; ++k) gsum += u_s[k] * lc.landmark_w_dev[k * 52 + i];
-                dy += wgt * 2.0f * gsum;
-            }
-            if (i == 0) { float q = 0.f; for (int k = 0; k < 136; ++k) q += u_s[k] * u_s[k]; loss_acc += wgt * q; }
-            __builtin_amdgcn_wave_barrier();
-        }
+        if (lm_on) tail_landmark_term(lc, a.B, i, e_s, u_s, dy, loss_acc);
         if (i < 52) {
             if (ema_on) dal += dy * xp * alpha * (1.0f - alpha);
             const float df = dy * fac;

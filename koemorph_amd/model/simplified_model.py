@@ -67,12 +67,21 @@ class SimplifiedKoeMorphModel(nn.Module):
         self._reserved = (0, 0)
 
     # ---- handle plumbing ------------------------------------------------------------------------
+    def _signature(self):
+        """What the library's copy of the weights was made from: device, and storage address and version of every tensor."""
+        return (str(self.blendshape_queries.device),) + tuple((k, v.data_ptr(), v._version) for k, v in self.state_dict().items())
+
+    def _mark_uploaded(self):
+        """The library already holds the module's present tensors (LegacyTrainer.sync_inference_weights wrote both): the next
+        call must not upload them again."""
+        self._sig = self._signature()
+
     def _handle(self):
         dev = self.blendshape_queries.device
         if dev.type != "cuda":
             raise RuntimeError("SimplifiedKoeMorphModel runs on the GPU only (there is no CPU fallback by design)")
         lib = _lib.load()
-        sig = (str(dev),) + tuple((k, v.data_ptr(), v._version) for k, v in self.state_dict().items())
+        sig = self._signature()
         if self._h is None:
             mel = MelConfig.model_batch(self.sample_rate, self.target_fps, self.n_fft)
             mel.hop_length = self.hop_length

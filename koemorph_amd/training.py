@@ -430,3 +430,229 @@ class Trainer:
         """Fold + pack the trained master weights so the inference kernels see them (km_train_sync)."""
         with torch.cuda.device(self.device):
             check(self._lib.km_train_sync(self._h, _stream_ptr(self.device)))
+
+
+def cosine_annealing_lr(epoch: int, base_lr: float, T_max: int = 100, eta_min: float = 1e-6) -> float:
+    """torch.optim.lr_scheduler.CosineAnnealingLR (closed form), evaluated at an integer epoch."""
+    return eta_min + (base_lr - eta_min) * (1 + math.cos(math.pi * epoch / T_max)) / 2
+
+
+class LegacyTrainer:
+    """Training step of ``SimplifiedKoeMorphModel`` on the GPU (km_legacy_train_*): what the reference's main trainer does
+    per batch (src/train.py:165-249) -- the model under ``.train()``, ``KoeMorphLoss``, backward, ``clip_grad_norm_``, AdamW --
+    with the conventions of ``Trainer``.  The module itself keeps refusing training-mode forwards; the trainer owns fp32
+    master weights on the device, and ``sync_inference_weights`` hands them back to the module."""
+
+    SITES = ("enc1", "enc2", "attn", "dec1", "dec2")
+
+    def __init__(self, model, max_windows: int = 16, max_frames: int = 301, lr: float = 1e-4, weight_decay: float = 1e-5,
+                 betas=(0.9, 0.999), eps: float = 1e-8, grad_clip: float = 1.0, mse_weight: float = 1.0, l1_weight: float = 0.1,
+                 dropout: float = 0.0, seed: int = 0):
+        self.model = model
+        self._lib, self._h, self.device = model._handle()
+        self.base_lr = self.lr = lr
+        self.weight_decay, self.betas, self.eps, self.grad_clip = weight_decay, betas, eps, grad_clip
+        self.mse_weight, self.l1_weight = mse_weight, l1_weight
+        self.max_windows, self.max_frames = int(max_windows), int(max_frames)
+        with torch.cuda.device(self.device):
+            check(self._lib.km_legacy_train_init(self._h, self.max_windows, self.max_frames, _stream_ptr(self.device)))
+        self.n_params = int(self._lib.km_legacy_train_num_params(self._h))
+        self.shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+        self.flat_grad = torch.zeros(self.n_params, device=self.device)
+        self.loss = torch.zeros(1, device=self.device)
+        self.out = torch.zeros(self.max_windows, 52, device=self.device)
+        self.dropout = 0.0
+        if dropout > 0:
+            self.set_dropout(dropout, seed)
+        self._last_bt = None
+        self.step_count = 0
+        self.epoch = 0
+
+    # ---- introspection --------------------------------------------------------------------------
+    def offset(self, key: str) -> int:
+        off = int(self._lib.km_legacy_train_param_offset(self._h, key.encode()))
+        if off < 0:
+            raise KeyError(key)
+        return off
+
+    def _split(self, flat: np.ndarray) -> Dict[str, np.ndarray]:
+        return {k: flat[self.offset(k):self.offset(k) + int(np.prod(s, dtype=np.int64))].reshape(s).copy() for k, s in self.shapes.items()}
+
+    def grads(self) -> Dict[str, np.ndarray]:
+        return self._split(self.flat_grad.cpu().numpy())
+
+    def params(self) -> Dict[str, np.ndarray]:
+        flat = np.empty(self.n_params, np.float32)
+        check(self._lib.km_legacy_train_get_params(self._h, flat.ctypes.data, self.n_params))
+        return self._split(flat)
+
+    def load_params(self, state: Dict[str, np.ndarray]) -> None:
+        """Overwrite the fp32 master weights (e.g. from a checkpoint); moments and step counters are kept."""
+        flat = np.empty(self.n_params, np.float32)
+        check(self._lib.km_legacy_train_get_params(self._h, flat.ctypes.data, self.n_params))
+        for k, v in state.items():
+            a = (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float32).ravel()
+            off = self.offset(k)
+            flat[off:off + a.size] = a
+        check(self._lib.km_legacy_train_set_params(self._h, flat.ctypes.data, self.n_params))
+
+    def optimizer_state(self) -> Dict[str, object]:
+        """AdamW moments per state-dict key + step counters (host copies) for a checkpoint, in ``Trainer``'s layout."""
+        import ctypes
+        m, v = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.float32)
+        steps = np.zeros(2, np.int32)
+        check(self._lib.km_legacy_train_get_optimizer_state(self._h, m.ctypes.data, v.ctypes.data, self.n_params, steps.ctypes.data))
+        drop_step = ctypes.c_int64(0)
+        check(self._lib.km_legacy_train_get_dropout_step(self._h, ctypes.byref(drop_step)))
+        return {"layout": "per-key-v1", "exp_avg": {k: torch.from_numpy(a) for k, a in self._split(m).items()},
+                "exp_avg_sq": {k: torch.from_numpy(a) for k, a in self._split(v).items()}, "steps": torch.from_numpy(steps),
+                "step_count": self.step_count, "epoch": self.epoch, "dropout_step": int(drop_step.value)}
+
+    def load_optimizer_state(self, st: Dict[str, object]) -> None:
+        if st.get("layout") != "per-key-v1":
+            raise ValueError("optimizer state without a per-key layout")
+        m, v = np.zeros(self.n_params, np.float32), np.zeros(self.n_params, np.float32)
+        for k, s in self.shapes.items():
+            o, n = self.offset(k), int(np.prod(s, dtype=np.int64))
+            a, b = st["exp_avg"][k].numpy().ravel(), st["exp_avg_sq"][k].numpy().ravel()
+            if a.size != n or b.size != n:
+                raise ValueError(f"optimizer state of {k}: {a.size} values, the model has {n}")
+            m[o:o + n] = a; v[o:o + n] = b
+        steps = np.ascontiguousarray(st["steps"].numpy(), np.int32)
+        check(self._lib.km_legacy_train_set_optimizer_state(self._h, m.ctypes.data, v.ctypes.data, self.n_params, steps.ctypes.data))
+        self.step_count = int(st["step_count"]); self.epoch = int(st["epoch"])
+        if "dropout_step" in st:
+            self.set_dropout_step(int(st["dropout_step"]))
+
+    # ---- training-mode dropout -------------------------------------------------------------------
+    def set_dropout(self, p: float, seed: int = 0, external_masks: bool = False) -> None:
+        check(self._lib.km_legacy_train_set_dropout(self._h, float(p), int(seed) & (2 ** 64 - 1), 1 if external_masks else 0))
+        self.dropout = float(p)
+
+    def dropout_step(self) -> int:
+        import ctypes
+        v = ctypes.c_int64(0)
+        check(self._lib.km_legacy_train_get_dropout_step(self._h, ctypes.byref(v)))
+        return int(v.value)
+
+    def set_dropout_step(self, step: int) -> None:
+        check(self._lib.km_legacy_train_set_dropout_step(self._h, int(step)))
+
+    @staticmethod
+    def mask_shapes(B: int, T: int):
+        return {"enc1": (B, T, 256), "enc2": (B, T, 256), "attn": (B, 8, 52, T), "dec1": (B, 52, 128), "dec2": (B, 52, 128)}
+
+    def dropout_masks(self, B: Optional[int] = None, T: Optional[int] = None) -> Dict[str, np.ndarray]:
+        """Keep masks of the most recent step (boolean arrays at the five sites, the layout of the float64 restatement)."""
+        if B is None:
+            B, T = self._last_bt
+        bufs = {k: np.empty(s, np.uint8) for k, s in self.mask_shapes(B, T).items()}
+        with torch.cuda.device(self.device):
+            check(self._lib.km_legacy_train_get_dropout_masks(self._h, B, T, *[bufs[k].ctypes.data for k in self.SITES], _stream_ptr(self.device)))
+        return {k: b.astype(bool) for k, b in bufs.items()}
+
+    def set_dropout_masks(self, masks: Dict[str, np.ndarray]) -> None:
+        B, T = int(masks["enc1"].shape[0]), int(masks["enc1"].shape[1])
+        bufs = [np.ascontiguousarray(np.asarray(masks[k]).reshape(s), np.uint8) for k, s in self.mask_shapes(B, T).items()]
+        with torch.cuda.device(self.device):
+            check(self._lib.km_legacy_train_set_dropout_masks(self._h, B, T, *[b.ctypes.data for b in bufs], _stream_ptr(self.device)))
+
+    def set_loss_terms(self, perceptual_weight: float = 0.0, temporal_weight: float = 0.0, sparsity_weight: float = 0.0,
+                       smoothness_weight: float = 0.0, landmark_weight: float = 0.0, velocity_weight: float = 0.0,
+                       prev_pred: Optional[torch.Tensor] = None, prev_target: Optional[torch.Tensor] = None,
+                       landmark_weights: Optional[torch.Tensor] = None) -> None:
+        """The remaining terms of KoeMorphLoss (src/model/losses.py:29-178), added to mse / l1; no arguments = off."""
+        import ctypes
+        from ._lib import KM_ABI_VERSION, KMLossConfig
+        keep = []
+        def dev(t, shape_tail):
+            if t is None:
+                return None
+            t = t.to(self.device, torch.float32).contiguous()
+            assert tuple(t.shape[-len(shape_tail):]) == shape_tail, (t.shape, shape_tail)
+            keep.append(t)
+            return _ptr(t)
+        cfg = KMLossConfig(KM_ABI_VERSION, perceptual_weight, temporal_weight, sparsity_weight, smoothness_weight, landmark_weight,
+                           velocity_weight, dev(prev_pred, (52,)), dev(prev_target, (52,)), dev(landmark_weights, (136, 52)),
+                           None, 0.0, 0.0, None)
+        self._loss_tensors = keep
+        check(self._lib.km_legacy_train_set_loss(self._h, ctypes.byref(cfg)))
+
+    # ---- one optimisation step ------------------------------------------------------------------
+    def forward_backward_mel(self, mel, target):
+        mel = mel.float().contiguous()
+        B, T, _ = mel.shape
+        check(self._lib.km_legacy_train_step_mel(self._h, _ptr(mel), B, T, _ptr(target.float().contiguous()), self.mse_weight,
+                                                 self.l1_weight, _ptr(self.flat_grad), _ptr(self.loss), _ptr(self.out),
+                                                 _stream_ptr(self.device)))
+        self._last_bt = (B, T)
+        return self.loss
+
+    def forward_backward(self, audio, target):
+        audio = audio.float().contiguous()
+        B, L = audio.shape
+        self.model._reserve(self._lib, self._h, self.device, B, L)
+        check(self._lib.km_legacy_train_step_audio(self._h, _ptr(audio), B, L, _ptr(target.float().contiguous()), self.mse_weight,
+                                                   self.l1_weight, _ptr(self.flat_grad), _ptr(self.loss), _ptr(self.out),
+                                                   _stream_ptr(self.device)))
+        self._last_bt = (B, 1 + L // self.model.hop_length)
+        return self.loss
+
+    def optimizer_step(self):
+        """clip_grad_norm_ + AdamW.step on the flat vectors (src/train.py:195-203)."""
+        self.step_count += 1
+        check(self._lib.km_legacy_train_adamw(self._h, _ptr(self.flat_grad), self.lr, self.betas[0], self.betas[1], self.eps,
+                                              self.weight_decay, self.grad_clip if self.grad_clip else 0.0, self.step_count,
+                                              _stream_ptr(self.device)))
+
+    def step(self, audio, target) -> torch.Tensor:
+        """forward + loss + backward + clip + AdamW; returns the loss (device)."""
+        self.forward_backward(audio, target)
+        self.optimizer_step()
+        return self.loss
+
+    def step_mel(self, mel, target) -> torch.Tensor:
+        self.forward_backward_mel(mel, target)
+        self.optimizer_step()
+        return self.loss
+
+    # ---- hipGraph replay of the step's launches ---------------------------------------------------
+    def capture(self, B: int, L: int) -> None:
+        """Record ``forward_backward`` on static input buffers into a hipGraph; call after one eager step at this (B, L)."""
+        dev = self.device
+        self._g_audio = torch.zeros(B, L, device=dev)
+        self._g_target = torch.zeros(B, 52, device=dev)
+        self.model._reserve(self._lib, self._h, dev, B, L)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.forward_backward(self._g_audio, self._g_target)
+        self._graph = g
+
+    def replay(self, audio, target) -> torch.Tensor:
+        self._g_audio.copy_(audio, non_blocking=True)
+        self._g_target.copy_(target, non_blocking=True)
+        self._graph.replay()
+        return self.loss
+
+    def step_graph(self, audio, target) -> torch.Tensor:
+        self.replay(audio, target)
+        self.optimizer_step()
+        return self.loss
+
+    def end_epoch(self, T_max: int = 100, eta_min: float = 1e-6):
+        """scheduler.step() of the reference (CosineAnnealingLR, src/train.py:118-123, :305)."""
+        self.epoch += 1
+        self.lr = cosine_annealing_lr(self.epoch, self.base_lr, T_max, eta_min)
+
+    def sync_inference_weights(self):
+        """km_legacy_train_sync, and the trained tensors copied back into the module's parameters: ``model.eval()(audio)``
+        and ``torch.save(model.state_dict())`` then see them."""
+        with torch.cuda.device(self.device):
+            check(self._lib.km_legacy_train_sync(self._h, _stream_ptr(self.device)))
+        trained = self.params()
+        sd = self.model.state_dict()
+        with torch.no_grad():
+            for k, v in sd.items():
+                v.copy_(torch.from_numpy(trained[k]).to(v.device))
+        self.model._mark_uploaded()
