@@ -508,7 +508,11 @@ int km_koemorph_forward(km_handle h, const float* mel_dev, const float* emotion_
  *                     is full; ready_dev (n_streams) u8 mirrors MelAudioBuffer.is_full (rows of not-ready streams
  *                     are left untouched).  Per-stream EMA state lives in the handle.  The short-term rows are
  *                     the last three kept frames.  push + tick never allocate or synchronise: capture them in a
- *                     hipGraph and replay it per 33 ms tick.
+ *                     hipGraph and replay it per tick.  Two model shapes have a streaming core: d_model 256 /
+ *                     8 heads / mel_sequence_length 256 (30 fps: update_interval 0.0333 s, front end hop 533) and
+ *                     d_model 512 / 8 or 16 heads / mel_sequence_length 512 (60 fps long context: update_interval
+ *                     1/60 s, ring hop 266, front end hop 266, 512 frames per 8.5 s ring of which 510 are kept);
+ *                     any other shape returns KM_ERR_UNSUPPORTED ("no kernel for d_model=...").
  *   km_stream_reset   clear rings, readiness and EMA state (MelSlidingWindowExtractor.reset :373-383). */
 int km_stream_create(km_handle h, int64_t n_streams, double context_window_s, double update_interval_s,
                      const km_mel_config* mel_cfg);

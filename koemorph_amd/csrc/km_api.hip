@@ -994,7 +994,8 @@ int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_
     Context* c = h;
     if (c->n_streams <= 0) return fail(KM_ERR_INVALID_ARG, "km_stream_tick: no streams (km_stream_create first)");
     if (!emotion_dev || !out_dev) return fail(KM_ERR_INVALID_ARG, "km_stream_tick: NULL argument");
-    if (!c->fused_ok)
+    // two shapes have a streaming core: the fused one (d_model 256, 8 heads, window 256) and core512's (512, 8 or 16 heads, window 512)
+    if (!c->fused_ok && !core512_stream_ok(c))
         return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
     const int64_t S = c->n_streams, L = c->ring_len;
     const int64_t n_frames = 1 + L / c->stream_plan->cfg.hop_length;
@@ -1004,8 +1005,12 @@ int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_
         if (int rc = launch_emotion(c, emotion_dev, S, c->ws_zemo, stream)) return rc;
     if (int rc = launch_mel_power(c, c->stream_plan, c->ring, S, L, stream, L, 0, 0, 1, c->ring_wptr, c->ring_ready,
                                   fuse_emo ? emotion_dev : nullptr, fuse_emo ? c->ws_zemo : nullptr)) return rc;
-    if (int rc = launch_core_fused_db(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, c->ring_state, 0, stream, 0, 1,
-                                      c->stream_out_frames, c->ring_ready, c->ring_started)) return rc;
+    if (c->fused_ok) {
+        if (int rc = launch_core_fused_db(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, c->ring_state, 0, stream, 0, 1,
+                                          c->stream_out_frames, c->ring_ready, c->ring_started)) return rc;
+    } else {
+        if (int rc = launch_core512_stream(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream)) return rc;
+    }
     if (ready_dev)
         HIP_TRY(hipMemcpyAsync(ready_dev, c->ring_ready, (size_t)S, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return KM_OK;

@@ -357,13 +357,14 @@ __global__ __launch_bounds__(512) void attn_out_kernel(const float* __restrict__
 #endif
 
 // window b of the launch; gsm: the workgroup's dynamic LDS
-template <int D, int HPW>
+// STREAM (km_stream_tick): the per-stream EMA of the fused d = 256 core's tail (StreamSrc, km_encoder_dev.h)
+template <int D, int HPW, bool STREAM = false>
 __device__ __forceinline__ void attn_out_vr_body(const float* __restrict__ S, const float* __restrict__ Y,
                                                  const float* __restrict__ wv_bg, const float* __restrict__ wf_pg,
                                                  const float* __restrict__ bf, const float* __restrict__ w2,
                                                  const float* __restrict__ b2, const float* __restrict__ zemo,
                                                  const float* __restrict__ wsum, float* __restrict__ out,
-                                                 float* __restrict__ raw, int b, float* gsm) {
+                                                 float* __restrict__ raw, int b, float* gsm, const StreamSrc& ss = StreamSrc{}) {
     constexpr int NKc = 80, KB = D / 16, CH = 4, NCH = KB / CH, QS = NKc + 1, OS = D + 8, NWv = 8, H = NWv * HPW;
     constexpr int TPH = 4 / HPW;                               // column tiles per head
     static_assert(D == 64 * NWv && KB % CH == 0 && CH % 2 == 0, "one wave per 64 columns; k blocks in chunks of four");
@@ -547,7 +548,17 @@ __device__ __forceinline__ void attn_out_vr_body(const float* __restrict__ S, co
         }
         const float bs = 1.0f / (1.0f + expf(-z));
         if (raw) raw[(int64_t)b * 52 + tid] = bs;
-        out[(int64_t)b * 52 + tid] = fminf(fmaxf(wsum[tid] * bs, 0.f), 1.f);
+        float val = fminf(fmaxf(wsum[tid] * bs, 0.f), 1.f);
+        if constexpr (STREAM) {                                         // EMA (simplified_dual_stream_model.py:357-366)
+            float* st = ss.state + (int64_t)b * 52 + tid;
+            if (ss.started[b]) val = ss.alpha * val + (1.0f - ss.alpha) * (*st);
+            *st = val;
+        }
+        out[(int64_t)b * 52 + tid] = val;
+    }
+    if constexpr (STREAM) {
+        __syncthreads();                                                // the 52 threads above have read started[b]
+        if (tid == 0) ss.started[b] = 1;
     }
 }
 

@@ -289,6 +289,9 @@ int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_fr
                               float* raw, float* attn, void* stream);
 int launch_core_generic(Context* c, const float* mel, int64_t B, int64_t T_in, const float* mel_short, const float* zemo,
                         float* out, float* raw, float* attn, void* stream);
+// km_stream_tick on the d_model 512 shapes (8 or 16 heads, window 512): core512's streaming kernel over the rings' power-mel
+bool core512_stream_ok(Context* c);
+int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream);
 
 // km_mel.hip
 // Shared-frame sequence mode: the front end writes n_rows rows per window (row r = STFT frame r * frame_mul) into

@@ -32,6 +32,17 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct EncSrc {
     const float* melpow; unsigned* melmax; int n_frames, T; LogParams lp;   // melmax[b] is re-zeroed once every thread has read it
 };
+// STREAM (km_stream_tick at d_model 512; needs FUSE_DB): window b is stream b's ring, as the fused d = 256 core reads it.
+//  * rows: the front end computed n_frames frames (the dB reference melmax[b] spans all of them); the streaming extractor keeps
+//    the first n_use of them -- truncated, or extended by repeating the last frame (mel_sliding_window.py:300-307).  Long rows =
+//    the first min(n_use, T) kept rows, zero rows up to T; short rows = the last three kept rows;
+//  * ready[b] == 0 (ring still filling): the workgroup returns before it touches anything;
+//  * per-stream EMA in the tail of attn_out_vr_body: first = !started[b], state (n_streams, 52) updated in place.
+// A struct of its own, handed to the bodies next to their other arguments: the kernel arguments of every other instantiation stay
+// where they are.
+struct StreamSrc {
+    int n_use; const unsigned char* ready; unsigned char* started; float* state; float alpha;
+};
 
 // NW waves of CT column tiles each: D = 16 CT NW columns (d = 512 -> 8 waves x 64 columns, two waves per SIMD with 20
 // accumulators each; d = 256 -> 8 x 32; d = 64 -> 2 x 32).  What the timing harness showed about the first version
@@ -54,12 +65,13 @@ struct EncLds {
 };
 
 // window b of the launch; every thread of the workgroup runs the whole body (barriers inside)
-template <int NW, int CT, bool FUSE_DB>
+template <int NW, int CT, bool FUSE_DB, bool STREAM = false>
 __device__ __forceinline__ void encoder_ln_body(const float* __restrict__ xp, const float* __restrict__ wpg,
                                                 const float* __restrict__ bias, const float* __restrict__ gam,
                                                 const float* __restrict__ bet, float* __restrict__ Y, int KP,
-                                                const EncSrc& src, int b, EncLds<NW>& L) {
+                                                const EncSrc& src, int b, EncLds<NW>& L, const StreamSrc& ss = StreamSrc{}) {
     constexpr int NKc = 80, NTHR = 64 * NW, D = 16 * CT * NW;
+    static_assert(!STREAM || FUSE_DB, "a stream's rows come from the front end's power-mel");
     static_assert(NKc % NW == 0, "rows must divide evenly among the waves");
     static_assert(CT == 2 || CT == 4, "a lane's columns are stored as one 8- or 16-byte vector");
     constexpr int ABUF = 4 * NKc * 4;                 // floats of one A tile image [k / 4][row][k % 4]
@@ -92,7 +104,16 @@ __device__ __forceinline__ void encoder_ln_body(const float* __restrict__ xp, co
             const int idx = tid + NTHR * i, fr = idx / 20, c4 = idx - fr * 20;
             const int r = 32 * sb + fr;                               // packed row of this load
             int f = r < KP ? r : -1;
-            if constexpr (FUSE_DB) {                                  // packed row -> frame (mel_log_packed_kernel's mapping)
+            if constexpr (STREAM) {                                   // packed row -> frame under the streaming row policy (km_core.hip, phase 0)
+                const int F = src.n_frames, U = ss.n_use, tv = U < src.T ? U : src.T;
+                f = -1;
+                if (r < src.T) { if (r < tv) f = r < F ? r : F - 1; }
+                else if (r < src.T + 3) {
+                    const int q = r - src.T;
+                    if (U >= 3) f = U - 3 + q; else if (q < U) f = q;
+                    if (f >= F) f = F - 1;
+                }
+            } else if constexpr (FUSE_DB) {                           // packed row -> frame (mel_log_packed_kernel's mapping)
                 f = -1;
                 if (r < src.T) f = r < src.n_frames ? r : -1;
                 else if (r < src.T + 3) {

@@ -573,11 +573,32 @@ __global__ __launch_bounds__(512) void core512_kernel(Core512Args a) {
     attn_out_vr_body<512, HPW>(a.S, a.Y, a.wv_bg, a.wf_pg, a.bf, a.w2, a.b2, a.zemo, a.wsum, a.out, a.raw, b, gsm);
 }
 
+// The streaming instantiation (km_stream_tick): window b is stream b.  A stream whose ring is still filling returns before the
+// first barrier and leaves its out row, EMA state and window maximum as they were; the encoder reads its rows under the streaming
+// row policy and the tail applies the per-stream EMA (StreamSrc, km_encoder_dev.h).  A kernel of its own around the same three
+// bodies, so that core512_kernel's instantiations and their arguments are what they were.  No LDS beyond theirs.
+struct Core512StreamArgs { Core512Args c; StreamSrc st; };
+template <int TPW, int HPW>
+__global__ __launch_bounds__(512) void core512_stream_kernel(Core512StreamArgs sa) {
+    __shared__ EncLds<8> el;
+    extern __shared__ __attribute__((aligned(16))) float gsm[];
+    const Core512Args& a = sa.c;
+    const int b = (int)blockIdx.x;
+    if (!sa.st.ready[b]) return;     // workgroup-uniform
+    encoder_ln_body<8, 4, true, true>(a.xp, a.wce_pg, a.bce, a.ln_g, a.ln_b, a.Y, a.KP, a.src, b, el, sa.st);
+    __syncthreads();
+    scores_softmax_body<512, TPW>(a.Y, a.qk_pg, a.S, a.rows, b, *reinterpret_cast<float (*)[2][kScoresYsFloats]>(gsm));
+    __syncthreads();
+    attn_out_vr_body<512, HPW, true>(a.S, a.Y, a.wv_bg, a.wf_pg, a.bf, a.w2, a.b2, a.zemo, a.wsum, a.out, a.raw, b, gsm, sa.st);
+}
+
 static bool core512_merge_ok(Context* c, const float* attn) {
     return c->d == 512 && c->NK == 80 && c->DH == 256 && (c->H == 8 || c->H == 16) && !attn && !c->opt.no_ln_fusion &&
            !c->opt.no_score_fusion && !c->opt.no_out_fusion && !c->opt.no_v_fusion && !c->opt.no_core_merge && c->packed.count("qk_pg") &&
            c->packed.count("wf_pg") && c->packed.count("wv_bg");
 }
+
+constexpr int kCore512Lds = (2 * 16 * 81 * 4 + 32 * (512 + 8) + 8 * 32) * (int)sizeof(float);   // dynamic LDS of the last stage
 
 template <bool FUSE_DB>
 static int launch_core512(Context* c, int64_t B, const float* xp, int KP, const EncSrc& src, const float* zemo, float* out, float* raw,
@@ -587,7 +608,7 @@ static int launch_core512(Context* c, int64_t B, const float* xp, int KP, const 
     float* S = Y + 2 * B * NKk * d;
     Core512Args a{xp, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), S, H * 28,
                   dv(c, "wv_bg"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw};
-    constexpr int lds = (2 * 16 * 81 * 4 + 32 * (512 + 8) + 8 * 32) * (int)sizeof(float);
+    constexpr int lds = kCore512Lds;
     static PerDeviceOnce once;
     if (once.first(c->device)) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_kernel<2, 1, FUSE_DB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -656,6 +677,32 @@ int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_fr
     if (int rc = launch_encoder_ln_for<true>(c, B, st, nullptr, KP, src)) return rc;
     c->melmax_dirty = false;     // every slot the encoder read was just written by the front end and is re-zeroed by the encoder
     return core_generic_after_encoder(c, B, zemo, out, raw, attn, stream, true);
+}
+
+// km_stream_tick on the d_model 512 shapes: the front end has written the power-mel of every ready stream's ring
+bool core512_stream_ok(Context* c) { return core512_merge_ok(c, nullptr) && generic_core_takes_power(c); }
+
+int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream) {
+    if (!core512_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
+    if (!c->ws_generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
+    const int d = c->d, H = c->H, NKk = c->NK, KP = (c->KT + 15) / 16 * 16;
+    float* Y = c->ws_generic;
+    float* Sc = Y + 2 * S * NKk * d;
+    const EncSrc src{c->ws_melpow, c->ws_melmax, (int)n_frames, c->T, plan_log_params(plan)};
+    Core512StreamArgs sa{{nullptr, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), Sc, H * 28,
+                          dv(c, "wv_bg"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, nullptr},
+                         {(int)(c->stream_out_frames > 0 ? c->stream_out_frames : n_frames), c->ring_ready, c->ring_started,
+                          c->ring_state, c->alpha}};
+    static PerDeviceOnce once;
+    if (once.first(c->device)) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_stream_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_stream_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
+    }
+    if (H == 8) hipLaunchKernelGGL((core512_stream_kernel<2, 1>), dim3((unsigned)S), dim3(512), kCore512Lds, (hipStream_t)stream, sa);
+    else hipLaunchKernelGGL((core512_stream_kernel<4, 2>), dim3((unsigned)S), dim3(512), kCore512Lds, (hipStream_t)stream, sa);
+    HIP_TRY(hipGetLastError());
+    c->melmax_dirty = false;     // as in launch_core_generic_power: the slots the front end wrote are re-zeroed by the encoder stage
+    return KM_OK;
 }
 
 float* generic_packed_x(Context* c, int64_t B) {     // the packed-X slot behind the other intermediates of B windows

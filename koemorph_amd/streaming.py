@@ -1,5 +1,9 @@
 """Many concurrent speaker streams with device-resident state (BASELINE config 5: 1024 streams, 128 per GPU).
 
+Two model shapes have a streaming core: d_model 256 / 8 heads / window 256 (the 30 fps configuration: 8.5 s ring, hop 532)
+and d_model 512 / 8 or 16 heads / window 512 (the 60 fps long-context configuration: ``update_interval=1/60``, ring hop 266,
+front end at hop 266).  Any other shape raises ``KoeMorphError`` from ``tick``.
+
 Each stream owns an 8.5 s audio ring (``MelAudioBuffer`` semantics, reference
 src/features/mel_sliding_window.py:28-140), and an EMA state; both live in the km_handle on the GPU and never
 move.  A tick is ``push`` (one ~hop-sized frame per stream, the only host->device traffic: n_streams x 533
@@ -19,6 +23,14 @@ from ._lib import check
 from .engine import Engine, MelConfig, _ptr, _stream_ptr
 
 
+def stream_shape(context_window: float, update_interval: float, mel_hop: int, sample_rate: int = 16000) -> dict:
+    """The reference's stream arithmetic (mel_sliding_window.py:46-50, 300), which km_stream_create follows as well: the ring's
+    length and hop in samples, the frames a front end of hop ``mel_hop`` computes over a full ring and the rows the extractor keeps."""
+    ring_len = int(context_window * sample_rate)
+    return dict(ring_len=ring_len, ring_hop=int(sample_rate / (1.0 / update_interval)), n_frames=1 + ring_len // mel_hop,
+                stream_out_frames=int(context_window / update_interval))
+
+
 class StreamEngine:
     def __init__(self, engine: Engine, n_streams: int, context_window: float = 8.5, update_interval: float = 0.0333,
                  mel: Optional[MelConfig] = None):
@@ -31,7 +43,8 @@ class StreamEngine:
         cfg = self.mel.to_c()
         with torch.cuda.device(engine.device):
             check(self._lib.km_stream_create(engine._h, n_streams, context_window, update_interval, C.byref(cfg)))
-        self.ring_hop = int(self.mel.sample_rate / (1.0 / update_interval))
+        self.shape = stream_shape(context_window, update_interval, self.mel.hop_length, self.mel.sample_rate)
+        self.ring_hop = self.shape["ring_hop"]
         dev = engine.device
         self.out = torch.zeros(n_streams, engine.num_blendshapes, device=dev)
         self.ready = torch.zeros(n_streams, dtype=torch.uint8, device=dev)
@@ -58,11 +71,15 @@ class StreamEngine:
         self.ready.zero_()
 
     # ---- hipGraph replay ------------------------------------------------------------------------
-    def capture(self, n_per_stream: int = 533, host_out: Optional[torch.Tensor] = None) -> None:
+    def capture(self, n_per_stream: Optional[int] = None, host_out: Optional[torch.Tensor] = None) -> None:
         """Record push + tick on static input buffers into a hipGraph (torch.cuda.CUDAGraph drives
-        hipStreamBeginCapture on the current stream; the kernels are launched by libkoemorph_hip).  ``host_out``: a pinned
+        hipStreamBeginCapture on the current stream; the kernels are launched by libkoemorph_hip).  ``n_per_stream``: the
+        frame size every replay() will bring, within +/-1 of ``ring_hop``; default 533 wherever push accepts it (ring hop 532
+        or 533: every 30 fps engine, as before), otherwise ``ring_hop + 1`` (267 at 60 fps).  ``host_out``: a pinned
         (n_streams, 52) host tensor -- the tick's result readback becomes the graph's last node instead of a call per tick."""
         dev = self.engine.device
+        if n_per_stream is None:
+            n_per_stream = 533 if abs(533 - self.ring_hop) <= 1 else self.ring_hop + 1
         if host_out is not None and (not host_out.is_pinned() or tuple(host_out.shape) != tuple(self.out.shape)):
             raise ValueError("host_out must be a pinned host tensor of the shape of the result")
         self._g_samples = torch.zeros(self.n_streams, n_per_stream, device=dev)
