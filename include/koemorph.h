@@ -219,7 +219,9 @@ int km_pipeline_flush(km_handle h, void* stream);
  * start at multiples of the hop, the clip's STFT is computed ONCE ((N-1)*stride + T+1 frames) plus the two
  * zero-padded boundary frames of each window, and the core reads rows from both images -- bit-identical to the
  * per-window evaluation (KM_SEQ_PER_WINDOW=1 selects that for comparison).  This entry point may allocate (grow-only
- * clip-level buffers sized B*L) on first use, so capture it in a hipGraph only after a warm-up call. */
+ * clip-level buffers sized B*L) on first use, so capture it in a hipGraph only after a warm-up call of the same shape:
+ * inside a stream capture a call that would have to grow them returns KM_ERR_WORKSPACE before it launches anything, as
+ * km_forward_clip and km_train_step_clip do. */
 int64_t km_sequence_num_outputs(km_handle h, int64_t L, int32_t stride_frames);
 /* The temporal smoothing of a whole sequence, in place: x_dev (B, N, 52), y[0] = x[0], y[n] = alpha x[n] + (1 - alpha) y[n - 1]
  * along the frame axis with alpha = sigmoid(smoothing_alpha) -- what SequentialDualStreamModel.forward's per-position calls of

@@ -160,7 +160,7 @@ int km_mel_batch(km_handle h, const float* audio_dev, int64_t B, int64_t L, floa
                  float* mel_short_dev, void* stream) {
     if (int rc = need_ready(h)) return rc;
     if (!audio_dev || !mel_long_dev || B <= 0 || L <= 0) return fail(KM_ERR_INVALID_ARG, "km_mel_batch: bad argument");
-    return launch_mel(h, h->mel_plans[0], audio_dev, B, L, 0, mel_long_dev, mel_short_dev, stream);
+    return launch_mel(h, h->mel_plans[0], mel_windows(audio_dev, B, L), 0, mel_long_dev, mel_short_dev, stream);
 }
 
 int km_mel_extract(km_handle h, const km_mel_config* cfg, const float* audio_dev, int64_t B, int64_t L,
@@ -182,7 +182,7 @@ int km_mel_extract(km_handle h, const km_mel_config* cfg, const float* audio_dev
             if (int rc = km_reserve(h, h->ws_windows, h->ws_samples)) return rc;
         }
     }
-    return launch_mel(h, p, audio_dev, B, L, out_frames, mel_dev, nullptr, stream);
+    return launch_mel(h, p, mel_windows(audio_dev, B, L), out_frames, mel_dev, nullptr, stream);
 }
 
 int km_core_forward(km_handle h, const float* mel_dev, int64_t B, int64_t T_in, const float* mel_short_dev,
@@ -259,18 +259,16 @@ static int upload_train_params(Context* c, void* stream) {
     return KM_OK;
 }
 
-// km_train_step_clip shares STFT frames between the windows of a batch.  That needs (a) the front end that writes the packed
-// encoder input (where km_train_step_audio takes its fe_packs branch at a window of T hop samples), (b) zero padding -- a
-// reflected boundary frame is not a clip frame either, but the two images below are built for zeros -- and (c) hop >= n_fft / 2:
-// frame f of a window spans its samples [f hop - n_fft / 2, f hop + n_fft / 2), so only then are frames 1 .. T - 1 free of
-// the window's padding and equal to the clip's own frames (hop 533: frame 1 starts at sample 21; hop 266: frames 1 and T - 1
-// reach into the padding too).
-static bool train_clip_ok(Context* c) {
-    if (c->mel_plans.empty()) return false;
+// where km_train_step_audio lets the front end write the packed encoder input itself (MelPack) for windows of n_frames frames
+static bool train_fe_packs(Context* c, int64_t n_frames) {
     MelPlan* p = c->mel_plans[0];
-    const km_mel_config& m = p->cfg;
-    return !c->opt.train_no_fe_pack && !c->opt.train_no_dma && mel_packs(c, p, c->T + 1, c->T) &&
-           m.n_mels == c->NK && c->NK % 4 == 0 && m.pad_mode == KM_PAD_CONSTANT && 2 * m.hop_length >= m.n_fft;
+    return !c->opt.train_no_fe_pack && !c->opt.train_no_dma && mel_packs(c, p, n_frames, c->T) && p->cfg.n_mels == c->NK;
+}
+
+// km_train_step_clip: the windows share the clip's STFT frames, and the step behind them is km_train_step_audio's packing
+// branch at a window of T hop samples
+static bool train_clip_ok(Context* c) {
+    return !c->mel_plans.empty() && clip_frames_shared(c, c->mel_plans[0]) && train_fe_packs(c, c->T + 1);
 }
 
 // span image (span_rows, NK) and edge image (tr_windows, 2, NK) of km_train_step_clip in ONE allocation: the pack kernel
@@ -392,11 +390,9 @@ int km_train_step_audio(km_handle h, const float* audio_dev, int64_t B, int64_t 
     // front end -> power-mel; phase 0 of the program converts and packs it into the encoder input (B, KP, n_mels) at the
     // head of the step's workspace
     // (round 4: the front end writes the packed dB input itself -- MelPack -- where it can; option train_no_fe_pack)
-    const bool fe_packs = !c->opt.train_no_fe_pack && !c->opt.train_no_dma &&
-                          mel_packs(c, c->mel_plans[0], n_frames, c->T) && c->mel_plans[0]->cfg.n_mels == c->NK;
+    const bool fe_packs = train_fe_packs(c, n_frames);
     const MelPack pack{c->trp_act, (int)c->T, (int)trainp_kp(c)};
-    if (int rc = launch_mel_power(c, c->mel_plans[0], audio_dev, B, L, stream, 0, 0, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  fe_packs ? &pack : nullptr)) return rc;
+    if (int rc = launch_mel_power(c, c->mel_plans[0], mel_windows(audio_dev, B, L), stream, fe_packs ? mel_to_pack(&pack) : MelCarry{})) return rc;
     c->melmax_dirty = true;      // until phase 1 / 2 has re-zeroed the maxima
     const LogParams lp = plan_log_params(c->mel_plans[0]);
     const TrainAudioSrc asrc{c->ws_melpow, c->ws_melmax, (int)n_frames, &lp, fe_packs};
@@ -429,14 +425,10 @@ int km_train_step_clip(km_handle h, const float* clip_dev, int64_t clip_len, con
         return fail(KM_ERR_INVALID_ARG, "km_train_step_clip: clip or start frame beyond 2^31 samples");
     if (B > c->ws_windows)
         return fail(KM_ERR_WORKSPACE, "workspace holds %lld windows, need %lld: call km_reserve", (long long)c->ws_windows, (long long)B);
-    hipStream_t st = (hipStream_t)stream;
-    if (n_span > c->clip_span_cap || B > c->clip_edge_cap) {            // grow-only; allocates, so not inside a stream capture
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-            return fail(KM_ERR_WORKSPACE, "km_train_step_clip: a span of %lld frames exceeds the %lld allocated during a stream capture: "
-                        "run one step with this span first", (long long)n_span, (long long)c->clip_span_cap);
-        HIP_TRY(hipStreamSynchronize(st));
-        if (int rc = alloc_clip_images(c, n_span > c->clip_span_cap ? n_span : c->clip_span_cap)) return rc;
+    if (n_span > c->clip_span_cap) {     // grow-only, both images in one allocation (the edge image holds tr_windows >= B windows)
+        if (int rc = growth_refused(stream, "km_train_step_clip: span frames", n_span, c->clip_span_cap)) return rc;
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        if (int rc = alloc_clip_images(c, n_span)) return rc;
     }
     // (the pack kernel STORES the maxima of windows 0 .. B - 1: no zeroed slots needed, no memset whatever ran before)
     const int KP = (int)trainp_kp(c);
@@ -711,7 +703,7 @@ int km_legacy_train_step_audio(km_handle h, const float* audio_dev, int64_t B, i
         return fail(KM_ERR_WORKSPACE, "workspace too small for %lld windows x %lld samples: call km_reserve", (long long)B, (long long)L);
     // km_mel_batch into the step's own mel image, then the step from mel: the same launches, the same bits
     float* mel = legacy_train_mel_buffer(c);
-    if (int rc = launch_mel(c, c->mel_plans[0], audio_dev, B, L, 0, mel, nullptr, stream)) return rc;
+    if (int rc = launch_mel(c, c->mel_plans[0], mel_windows(audio_dev, B, L), 0, mel, nullptr, stream)) return rc;
     return legacy_train_step(c, mel, B, T, target_dev, mse_weight, l1_weight, flat_grad_dev, loss_dev, out_dev, stream);
 }
 
@@ -784,12 +776,12 @@ int km_legacy_forward(km_handle h, const float* audio_dev, int64_t B, int64_t L,
     if (legacy_pow_ok(c)) {
         // front end -> power-mel + window maxima; the fused encoder converts to dB while it stages its rows and the attention
         // kernel re-zeroes the maxima: no mel_log_kernel launch, no memset (round 4; 18 us of the 460 per 256 windows)
-        if (int rc = launch_mel_power(c, c->mel_plans[0], audio_dev, B, L, stream)) return rc;
+        if (int rc = launch_mel_power(c, c->mel_plans[0], mel_windows(audio_dev, B, L), stream)) return rc;
         const LogParams lp = plan_log_params(c->mel_plans[0]);
         const LegacyPowSrc src{c->ws_melpow, c->ws_melmax, &lp};
         return launch_legacy(c, nullptr, B, n_frames, out_dev, stream, &src);
     }
-    if (int rc = launch_mel(c, c->mel_plans[0], audio_dev, B, L, 0, c->ws_mel, nullptr, stream)) return rc;
+    if (int rc = launch_mel(c, c->mel_plans[0], mel_windows(audio_dev, B, L), 0, c->ws_mel, nullptr, stream)) return rc;
     return launch_legacy(c, c->ws_mel, B, n_frames, out_dev, stream);
 }
 
@@ -816,25 +808,25 @@ int km_forward_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, 
     if (B > c->ws_windows || n_frames > c->ws_frames)
         return fail(KM_ERR_WORKSPACE, "workspace too small for %lld windows x %lld samples: call km_reserve",
                     (long long)B, (long long)L);
+    MelPlan* plan = c->mel_plans[0];
+    const MelSrc src = mel_windows(audio_dev, B, L);
     if (!c->fused_ok) {     // generic shapes: staged front end, GEMM-chain core, stand-alone EMA
         if (!c->ws_generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
         const bool power_path = generic_core_takes_power(c) && !c->opt.generic_staged;
-        const bool fuse_emo = power_path && mel_fuses_emotion(c, c->mel_plans[0]);   // emotion logits inside the front-end kernel
+        const bool fuse_emo = power_path && mel_fuses_emotion(c, plan);   // emotion logits inside the front-end kernel
         if (!fuse_emo)
             if (int rc = launch_emotion(c, emotion_dev, B, c->ws_zemo, stream)) return rc;
         if (power_path) {
             // power-mel -> dB conversion inside the encoder's tile staging: no log-mel image at all
-            if (int rc = launch_mel_power(c, c->mel_plans[0], audio_dev, B, L, stream, 0, 0, 0, 1, nullptr, nullptr,
-                                          fuse_emo ? emotion_dev : nullptr, fuse_emo ? c->ws_zemo : nullptr)) return rc;
-            if (int rc = launch_core_generic_power(c, c->mel_plans[0], B, n_frames, c->ws_zemo, out_dev, nullptr,
-                                                   nullptr, stream)) return rc;
+            if (int rc = launch_mel_power(c, plan, src, stream, fuse_emo ? mel_emotion(emotion_dev, c->ws_zemo) : MelCarry{})) return rc;
+            if (int rc = launch_core_generic_power(c, plan, B, n_frames, c->ws_zemo, out_dev, nullptr, nullptr, stream)) return rc;
         } else if (c->NK == 80 && !c->opt.generic_staged) {
             // log-mel written straight into the packed encoder input; long + short-term rows in one contraction
             float* xp = generic_packed_x(c, B);
-            if (int rc = launch_mel_packed(c, c->mel_plans[0], audio_dev, B, L, xp, c->T, (c->KT + 15) / 16 * 16, stream)) return rc;
+            if (int rc = launch_mel_packed(c, plan, src, xp, c->T, (c->KT + 15) / 16 * 16, stream)) return rc;
             if (int rc = launch_core_generic_packed(c, xp, B, c->ws_zemo, out_dev, nullptr, nullptr, stream)) return rc;
         } else {
-            if (int rc = launch_mel(c, c->mel_plans[0], audio_dev, B, L, 0, c->ws_mel, c->ws_short, stream)) return rc;
+            if (int rc = launch_mel(c, plan, src, 0, c->ws_mel, c->ws_short, stream)) return rc;
             if (int rc = launch_core_generic(c, c->ws_mel, B, n_frames, c->ws_short, c->ws_zemo, out_dev, nullptr, nullptr, stream)) return rc;
         }
         if (state_dev) return launch_smooth(c, out_dev, state_dev, B, first, stream);
@@ -843,29 +835,24 @@ int km_forward_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, 
     // three launches: emotion logits, power-mel + window maxima, fused core (dB conversion on load)
     hipStream_t st = (hipStream_t)stream;
     const bool tm = c->stage_timing;
-    const bool fuse_emo = mel_fuses_emotion(c, c->mel_plans[0]);   // emotion logits computed inside the front-end kernel
+    const bool fuse_emo = mel_fuses_emotion(c, plan);   // emotion logits computed inside the front-end kernel
     if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[0], st));
     if (!fuse_emo)
         if (int rc = launch_emotion(c, emotion_dev, B, c->ws_zemo, stream)) return rc;
     if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[1], st));
-    if (int rc = launch_mel_power(c, c->mel_plans[0], audio_dev, B, L, stream, 0, 0, 0, 1, nullptr, nullptr,
-                                  fuse_emo ? emotion_dev : nullptr, fuse_emo ? c->ws_zemo : nullptr)) return rc;
+    if (int rc = launch_mel_power(c, plan, src, stream, fuse_emo ? mel_emotion(emotion_dev, c->ws_zemo) : MelCarry{})) return rc;
     if (tm) { HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[2], st)); HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[3], st)); }
-    if (int rc = launch_core_fused_db(c, c->mel_plans[0], B, n_frames, c->ws_zemo, out_dev, state_dev, first, stream)) return rc;
+    if (int rc = launch_core_fused_db(c, plan, B, n_frames, c->ws_zemo, out_dev, stream, core_workspace(state_dev, first))) return rc;
     if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[4], st));
     return KM_OK;
 }
 
-// km_forward_clip shares STFT frames between the windows of a batch exactly as km_train_step_clip does, so the front-end half of
-// train_clip_ok applies (the 1024-point kernel with its grouped filter image, zero padding, hop >= n_fft / 2: only then are
-// frames 0 and T the only frames of a window that see its padding); behind it runs the fused core's table variant.  The
-// experimental split-bf16 core has no table variant: with it switched on km_forward_audio computes something else.
+// km_forward_clip shares STFT frames between the windows of a batch exactly as km_train_step_clip does; behind the span
+// front end runs the fused core's table variant.  The experimental split-bf16 core has no table variant: with it switched on
+// km_forward_audio computes something else.
 static bool forward_clip_ok(Context* c) {
     if (c->mel_plans.empty() || !c->fused_ok || c->opt.core_split == 3 || c->opt.core_split == 6) return false;
-    MelPlan* p = c->mel_plans[0];
-    const km_mel_config& m = p->cfg;
-    return m.n_fft == 1024 && !c->opt.mel_two_frame && p->d_fbg_gid != nullptr && m.n_mels == c->NK && c->NK % 4 == 0 &&
-           m.pad_mode == KM_PAD_CONSTANT && 2 * m.hop_length >= m.n_fft;
+    return mel_rp_ok(c, c->mel_plans[0]) && clip_frames_shared(c, c->mel_plans[0]);
 }
 
 int km_forward_clip_supported(km_handle h) {
@@ -892,27 +879,9 @@ int km_forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const 
         return fail(KM_ERR_INVALID_ARG, "km_forward_clip: clip or start frame beyond 2^31 samples");
     if (B > c->ws_windows)
         return fail(KM_ERR_WORKSPACE, "workspace holds %lld windows, need %lld: call km_reserve", (long long)c->ws_windows, (long long)B);
-    hipStream_t st = (hipStream_t)stream;
-    if (n_span > c->fwd_span_cap || B > c->fwd_edge_cap) {            // grow-only; allocates, so not inside a stream capture
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-            return fail(KM_ERR_WORKSPACE, "km_forward_clip: a span of %lld frames / %lld windows exceeds the %lld / %lld allocated during a "
-                        "stream capture: run one call with this span first", (long long)n_span, (long long)B, (long long)c->fwd_span_cap,
-                        (long long)c->fwd_edge_cap);
-        HIP_TRY(hipStreamSynchronize(st));
-        if (n_span > c->fwd_span_cap) {
-            if (c->fwd_span) HIP_TRY(hipFree(c->fwd_span));
-            c->fwd_span = nullptr; c->fwd_span_cap = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->fwd_span), (size_t)n_span * c->NK * sizeof(float)));
-            c->fwd_span_cap = n_span;
-        }
-        if (B > c->fwd_edge_cap) {
-            if (c->fwd_edge) HIP_TRY(hipFree(c->fwd_edge));
-            c->fwd_edge = nullptr; c->fwd_edge_cap = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->fwd_edge), (size_t)B * 2 * c->NK * sizeof(float)));
-            c->fwd_edge_cap = B;
-        }
-    }
+    // grow-only; allocates, so not inside a stream capture
+    if (int rc = grow_buffer(&c->fwd_span, &c->fwd_span_cap, n_span, c->NK * sizeof(float), stream, "km_forward_clip: span frames")) return rc;
+    if (int rc = grow_buffer(&c->fwd_edge, &c->fwd_edge_cap, B, 2 * c->NK * sizeof(float), stream, "km_forward_clip: windows")) return rc;
     // four launches: emotion logits (emotion_kernel_d256: bit-identical to the rider inside km_forward_audio's front end), the
     // span + edge images, the window maxima, the fused core reading its rows through the table
     if (int rc = launch_emotion(c, emotion_dev, B, c->ws_zemo, stream)) return rc;
@@ -920,9 +889,8 @@ int km_forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const 
                                       c->fwd_span, c->fwd_edge, stream)) return rc;
     if (int rc = launch_clip_window_max(c, c->fwd_span, c->fwd_edge, start_frames_dev, B, min_start_frame, n_span, (int)(T + 1),
                                         stream)) return rc;
-    SeqCore sc{c->fwd_span, c->fwd_edge, (int)n_span, 0, 1};
-    sc.start = start_frames_dev; sc.min_start = min_start_frame;
-    return launch_core_fused_db(c, c->mel_plans[0], B, T + 1, c->ws_zemo, out_dev, state_dev, first, stream, 0, 1, 0, nullptr, nullptr, &sc);
+    const ClipTable tab{c->fwd_span, c->fwd_edge, (int)n_span, start_frames_dev, min_start_frame};
+    return launch_core_fused_db(c, c->mel_plans[0], B, T + 1, c->ws_zemo, out_dev, stream, core_table(&tab, state_dev, first));
 }
 
 static int free_streams(Context* c) {
@@ -1003,11 +971,9 @@ int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_
     const bool fuse_emo = mel_fuses_emotion(c, c->stream_plan);
     if (!fuse_emo)
         if (int rc = launch_emotion(c, emotion_dev, S, c->ws_zemo, stream)) return rc;
-    if (int rc = launch_mel_power(c, c->stream_plan, c->ring, S, L, stream, L, 0, 0, 1, c->ring_wptr, c->ring_ready,
-                                  fuse_emo ? emotion_dev : nullptr, fuse_emo ? c->ws_zemo : nullptr)) return rc;
+    if (int rc = launch_mel_power(c, c->stream_plan, mel_rings(c), stream, fuse_emo ? mel_emotion(emotion_dev, c->ws_zemo) : MelCarry{})) return rc;
     if (c->fused_ok) {
-        if (int rc = launch_core_fused_db(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, c->ring_state, 0, stream, 0, 1,
-                                          c->stream_out_frames, c->ring_ready, c->ring_started)) return rc;
+        if (int rc = launch_core_fused_db(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream, core_stream(c))) return rc;
     } else {
         if (int rc = launch_core512_stream(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream)) return rc;
     }
@@ -1102,13 +1068,12 @@ int km_forward_audio_pipelined(km_handle h, const float* audio_dev, int64_t B, i
         const bool fuse_emo = mel_fuses_emotion(c, c->mel_plans[0]);
         if (!fuse_emo && (rc = launch_emotion(c, emotion_dev, B, c->ws_zemo, s1))) break;
         if (tm) (void)hipEventRecord((hipEvent_t)c->stage_ev[1], s1);
-        if ((rc = launch_mel_power(c, c->mel_plans[0], audio_dev, B, L, s1, 0, 0, 0, 1, nullptr, nullptr,
-                                   fuse_emo ? emotion_dev : nullptr, fuse_emo ? c->ws_zemo : nullptr))) break;
+        if ((rc = launch_mel_power(c, c->mel_plans[0], mel_windows(audio_dev, B, L), s1, fuse_emo ? mel_emotion(emotion_dev, c->ws_zemo) : MelCarry{}))) break;
         if (tm) (void)hipEventRecord((hipEvent_t)c->stage_ev[2], s1);
         (void)hipEventRecord((hipEvent_t)c->pipe_ev_mel[slot], s1);
         (void)hipStreamWaitEvent(s2, (hipEvent_t)c->pipe_ev_mel[slot], 0);
         if (tm) (void)hipEventRecord((hipEvent_t)c->stage_ev[3], s2);
-        if ((rc = launch_core_fused_db(c, c->mel_plans[0], B, n_frames, c->ws_zemo, out_dev, state_dev, first, s2))) break;
+        if ((rc = launch_core_fused_db(c, c->mel_plans[0], B, n_frames, c->ws_zemo, out_dev, s2, core_workspace(state_dev, first)))) break;
         if (tm) (void)hipEventRecord((hipEvent_t)c->stage_ev[4], s2);
         (void)hipEventRecord((hipEvent_t)c->pipe_ev_core[slot], s2);
         // stream-order visibility of the PREVIOUS call's result (and release of its slot for the next call)
@@ -1153,60 +1118,54 @@ int km_sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t 
         return fail(KM_ERR_WORKSPACE, "workspace too small for %lld clips / %lld-frame windows: call km_reserve",
                     (long long)B, (long long)n_frames);
     if (N > 0x7fffffff) return fail(KM_ERR_INVALID_ARG, "too many output frames");
-    // emotion features ONCE for the entire audio (:88): one logit per clip
-    if (int rc = launch_emotion(c, emotion_dev, B, c->ws_zemo, stream)) return rc;
     const int64_t total = B * N, tile = c->ws_windows;
     // Shared-frame path.  Windows start at multiples of the hop (:101-117), so frame f of window i IS clip frame
     // i*stride + f for f = 1 .. T-1; only frame 0 and frame T see the zero padding at the window boundary.  The STFT
     // of the clip is computed once (N-1)*stride + T + 1 frames instead of N * (T+1)), the two edge frames per window
     // separately, and the core reads its rows from both images.  Results are bit-identical to the per-window path.
     const bool dedup = !c->opt.seq_per_window;       // km_set_option: tests compare both paths
-    if (c->fused_ok && dedup && c->cfg.mel.n_fft == 1024 && !c->opt.mel_two_frame && N < (1 << 24)) {
+    MelPlan* plan = c->mel_plans[0];
+    const bool shared = c->fused_ok && dedup && mel_rp_ok(c, plan) && N < (1 << 24);
+    const int64_t nfc = (N - 1) * stride_frames + n_frames;                     // clip frames any window touches
+    if (shared) {     // grow-only images and their per-row maxima; allocates, so refused inside a stream capture, before any launch
+        const char* what = "km_sequence_forward: clip frames / windows";
+        if (int rc = grow_buffer(&c->seq_pow, &c->seq_pow_cap, B * nfc, c->NK * sizeof(float), stream, what)) return rc;
+        if (int rc = grow_buffer(&c->seq_fmax, &c->seq_fmax_cap, B * nfc, sizeof(unsigned), stream, what)) return rc;
+        if (int rc = grow_buffer(&c->seq_edge, &c->seq_edge_cap, total, 2 * c->NK * sizeof(float), stream, what)) return rc;
+        if (int rc = grow_buffer(&c->seq_emax, &c->seq_emax_cap, total, 2 * sizeof(unsigned), stream, what)) return rc;
+    }
+    // emotion features ONCE for the entire audio (:88): one logit per clip
+    if (int rc = launch_emotion(c, emotion_dev, B, c->ws_zemo, stream)) return rc;
+    if (shared) {
         hipStream_t st = (hipStream_t)stream;
-        const int64_t nfc = (N - 1) * stride_frames + n_frames;                 // clip frames any window touches
-        if (B * nfc > c->seq_pow_cap) {                                           // grow-only; may allocate (not capturable)
-            if (c->seq_pow) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(c->seq_pow)); HIP_TRY(hipFree(c->seq_fmax)); }
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->seq_pow), (size_t)B * nfc * c->NK * sizeof(float)));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->seq_fmax), (size_t)B * nfc * sizeof(unsigned)));
-            c->seq_pow_cap = B * nfc;
-        }
-        if (total > c->seq_edge_cap) {
-            if (c->seq_edge) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(c->seq_edge)); HIP_TRY(hipFree(c->seq_emax)); }
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->seq_edge), (size_t)total * 2 * c->NK * sizeof(float)));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->seq_emax), (size_t)total * 2 * sizeof(unsigned)));
-            c->seq_edge_cap = total;
-        }
         HIP_TRY(hipMemsetAsync(c->seq_fmax, 0, (size_t)B * nfc * sizeof(unsigned), st));
         HIP_TRY(hipMemsetAsync(c->seq_emax, 0, (size_t)total * 2 * sizeof(unsigned), st));
         // (1) every clip as one long "window" of nfc frames, zero beyond the clip end
-        SeqFrames clip_img{c->seq_pow, c->seq_fmax, nfc, 1};
-        if (int rc = launch_mel_power(c, c->mel_plans[0], audio_dev, B, (nfc - 1) * hop, stream, L, 0, 0, 1, nullptr, nullptr,
-                                      nullptr, nullptr, &clip_img)) return rc;
+        const SeqFrames clip_img{c->seq_pow, c->seq_fmax, nfc, 1};
+        if (int rc = launch_mel_power(c, plan, mel_clip_windows(audio_dev, L, B, (nfc - 1) * hop, 0, 0, 1), stream, mel_to_frames(&clip_img))) return rc;
         // (2) the first and last frame of every window (rows 0 and 1 = frames 0 and T of the window)
-        SeqFrames edge_img{c->seq_edge, c->seq_emax, 2, (int)(n_frames - 1)};
-        if (int rc = launch_mel_power(c, c->mel_plans[0], audio_dev, total, W, stream, L, step, 0, (int)N, nullptr, nullptr,
-                                      nullptr, nullptr, &edge_img)) return rc;
+        const SeqFrames edge_img{c->seq_edge, c->seq_emax, 2, (int)(n_frames - 1)};
+        if (int rc = launch_mel_power(c, plan, mel_clip_windows(audio_dev, L, total, W, step, 0, (int)N), stream, mel_to_frames(&edge_img))) return rc;
         // (3) per tile: window maxima, then the fused core reading rows from both images
-        SeqCore sc{c->seq_pow, c->seq_edge, (int)nfc, (int)stride_frames, (int)N};
+        const SeqCore sc{c->seq_pow, c->seq_edge, (int)nfc, (int)stride_frames, (int)N};
         for (int64_t w0 = 0; w0 < total; w0 += tile) {
             const int64_t nw = (total - w0) < tile ? (total - w0) : tile;
             if (int rc = launch_seq_window_max(c, c->seq_fmax, c->seq_emax, nw, w0, (int)nfc, (int)stride_frames, (int)N,
                                                (int)n_frames, stream)) return rc;
-            if (int rc = launch_core_fused_db(c, c->mel_plans[0], nw, n_frames, c->ws_zemo, out_dev + w0 * c->NB, nullptr, 1,
-                                              stream, w0, (int)N, 0, nullptr, nullptr, &sc)) return rc;
+            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, c->ws_zemo, out_dev + w0 * c->NB, stream, core_strided(&sc, w0))) return rc;
         }
         if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
         return KM_OK;
     }
     for (int64_t w0 = 0; w0 < total; w0 += tile) {
         const int64_t nw = (total - w0) < tile ? (total - w0) : tile;
+        const MelSrc src = mel_clip_windows(audio_dev, L, nw, W, step, w0, (int)N);
         if (c->fused_ok) {
-            if (int rc = launch_mel_power(c, c->mel_plans[0], audio_dev, nw, W, stream, L, step, w0, (int)N)) return rc;
-            if (int rc = launch_core_fused_db(c, c->mel_plans[0], nw, n_frames, c->ws_zemo, out_dev + w0 * c->NB, nullptr, 1,
-                                              stream, w0, (int)N)) return rc;
+            if (int rc = launch_mel_power(c, plan, src, stream)) return rc;
+            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, c->ws_zemo, out_dev + w0 * c->NB, stream, core_workspace_seq(w0, (int)N))) return rc;
         } else {
             // generic shapes: staged log-mel, per-window logits gathered from the per-clip ones, GEMM-chain core
-            if (int rc = launch_mel(c, c->mel_plans[0], audio_dev, nw, W, 0, c->ws_mel, c->ws_short, stream, L, step, w0, (int)N)) return rc;
+            if (int rc = launch_mel(c, plan, src, 0, c->ws_mel, c->ws_short, stream)) return rc;
             if (int rc = launch_gather_clip_logits(c, c->ws_zemo, c->ws_zemo_win, nw, w0, (int)N, stream)) return rc;
             if (int rc = launch_core_generic(c, c->ws_mel, nw, n_frames, c->ws_short, c->ws_zemo_win, out_dev + w0 * c->NB,
                                              nullptr, nullptr, stream)) return rc;

@@ -180,7 +180,7 @@ struct Context {
     int64_t ltr_mask_B = 0, ltr_mask_T = 0;               // the (B, T) the masks on the device belong to
     // shared-frame sequence mode buffers (grow-only, allocated by km_sequence_forward)
     float* seq_pow = nullptr; unsigned* seq_fmax = nullptr; float* seq_edge = nullptr; unsigned* seq_emax = nullptr;
-    int64_t seq_pow_cap = 0, seq_edge_cap = 0;
+    int64_t seq_pow_cap = 0, seq_fmax_cap = 0, seq_edge_cap = 0, seq_emax_cap = 0;
     // eval-mode forward from a resident clip (km_forward_clip): the span image (rows, NK) and the edge image (windows, 2, NK) of
     // launch_mel_clip_span, owned by the inference context (no km_train_init needed), grow-only
     float* fwd_span = nullptr; float* fwd_edge = nullptr;
@@ -214,21 +214,37 @@ int launch_emotion(Context* c, const float* emo, int64_t B, float* zemo, void* s
 int launch_core_fused(Context* c, const float* mel, int64_t B, int64_t T_in, const float* mel_short,
                       const float* zemo, float* out, float* raw, float* attn, float* state, int first,
                       void* stream);
-// fused variant: reads the workspace power-mel + window maxima, applies the log/dB conversion on load
-// Shared-frame sequence mode, core side (see CoreArgs in km_core.hip)
-struct SeqCore {
+// fused variant: reads the workspace power-mel + window maxima, applies the log/dB conversion on load.  CoreSrc says where
+// the B windows' rows and their EMA come from (CoreArgs in km_core.hip): build one with the functions below it
+struct SeqCore {          // shared-frame sequence mode: frame f of window i of a clip is row i stride + f of the clip's image
     const float* pow;     // (clips, nfc, 80) clip-level power-mel
     const float* edge;    // (clips * n_per_clip, 2, 80) first / last frame of every window
     int nfc, stride, n_per_clip;
-    // km_forward_clip: rows addressed by a start-frame table instead of a stride.  `pow` is then ONE span image (nfc rows, row r =
-    // clip frame min_start + r), window b begins at row start[b] - min_start, `edge` is (windows, 2, 80); stride / n_per_clip unused
-    const int* start = nullptr;
-    int min_start = 0;
 };
-int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, const float* zemo, float* out,
-                         float* state, int first, void* stream, int64_t win0 = 0, int zemo_div = 1, int64_t n_use = 0,
-                         const unsigned char* ready = nullptr, unsigned char* started = nullptr,
-                         const struct SeqCore* seq = nullptr);
+struct ClipTable {        // km_forward_clip: rows addressed by a start-frame table
+    const float* span;    // (n_span, 80) ONE span image, row r = clip frame min_start + r
+    const float* edge;    // (windows, 2, 80)
+    int n_span;
+    const int* start; int min_start;   // (windows) window b begins at row start[b] - min_start
+};
+struct CoreSrc {
+    float* state; int first;                 // EMA state (B, 52) or null
+    int64_t win0; int zemo_div;              // sequence mode: window b of the launch takes the logit zemo[(win0 + b) / zemo_div]
+    int64_t n_use;                           // streams: frames kept by the truncate / repeat-last policy (0: all)
+    const unsigned char* ready; unsigned char* started;   // streams: windows with ready[b] == 0 are skipped, first = !started[b]
+    const SeqCore* seq;                      // rows of the strided images instead of the workspace, or null
+    const ClipTable* tab;                    // ... of the span image through the table, or null
+};
+// rows of the workspace (launch_mel_power wrote them), the caller's EMA state
+inline CoreSrc core_workspace(float* state, int first) { return {state, first, 0, 1, 0, nullptr, nullptr, nullptr, nullptr}; }
+// ... for windows win0 .. of a sequence, n_per_clip of them sharing a clip's logit; no EMA here (launch_ema_scan follows)
+inline CoreSrc core_workspace_seq(int64_t win0, int n_per_clip) { return {nullptr, 1, win0, n_per_clip, 0, nullptr, nullptr, nullptr, nullptr}; }
+inline CoreSrc core_strided(const SeqCore* s, int64_t win0) { return {nullptr, 1, win0, s->n_per_clip, 0, nullptr, nullptr, s, nullptr}; }
+inline CoreSrc core_table(const ClipTable* t, float* state, int first) { return {state, first, 0, 1, 0, nullptr, nullptr, nullptr, t}; }
+// the handle's streams: rows of the workspace, EMA state and flags of the rings
+inline CoreSrc core_stream(Context* c) { return {c->ring_state, 0, 0, 1, c->stream_out_frames, c->ring_ready, c->ring_started, nullptr, nullptr}; }
+int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, const float* zemo, float* out, void* stream,
+                         const CoreSrc& src);
 int launch_seq_window_max(Context* c, const unsigned* fmax, const unsigned* emax, int64_t nw, int64_t win0, int nfc, int stride,
                           int n_per_clip, int n_frames, void* stream);
 // km_forward_clip: the maximum over each window's OWN n_frames rows of the span / edge images (found through the table) -> ws_melmax
@@ -304,11 +320,28 @@ struct SeqFrames {
 };
 // packed training input written by the front end itself (MelArgs::pack_*): xt (B, n_mels, KP), T long frames per row
 struct MelPack { float* xt; int T, KP; };
-int launch_mel_power(Context* c, MelPlan* p, const float* audio, int64_t B, int64_t L, void* stream,
-                     int64_t clip_len = 0, int64_t win_step = 0, int64_t win0 = 0, int wins_per_clip = 1,
-                     const int* ring_start = nullptr, const unsigned char* ready = nullptr,
-                     const float* emotion = nullptr, float* zemo = nullptr, const SeqFrames* seq = nullptr,
-                     const MelPack* pack = nullptr);
+// Where a front-end launch takes its B windows of L samples from; build one with the functions below.
+struct MelSrc {
+    const float* audio; int64_t B, L;
+    int64_t clip_len, win_step, win0; int wins_per_clip;      // window w is global window g = win0 + w: clip g / wins_per_clip, offset (g % wins_per_clip) win_step
+    const int* ring_start; const unsigned char* ready;        // rings: window b is read from ring_start[b] (mod L), skipped while ready[b] == 0
+};
+inline MelSrc mel_windows(const float* audio, int64_t B, int64_t L) { return {audio, B, L, L, 0, 0, 1, nullptr, nullptr}; }   // audio (B, L)
+// windows win0 .. win0 + B - 1 of L samples cut from clips (n, clip_len), wins_per_clip per clip, win_step samples apart (zero past the clip's end)
+inline MelSrc mel_clip_windows(const float* clips, int64_t clip_len, int64_t B, int64_t L, int64_t win_step, int64_t win0, int wins_per_clip) {
+    return {clips, B, L, clip_len, win_step, win0, wins_per_clip, nullptr, nullptr};
+}
+inline MelSrc mel_rings(Context* c) { return {c->ring, c->n_streams, c->ring_len, c->ring_len, 0, 0, 1, c->ring_wptr, c->ring_ready}; }
+// What a launch may carry, at most one of: the emotion rider (the windows' logits from the same kernel: mel_fuses_emotion, one window
+// per clip), rows into a SeqFrames image instead of the workspace (mel_rp_ok, no rings), the packed training input (mel_packs, a plain batch)
+struct MelCarry { const float* emotion = nullptr; float* zemo = nullptr; const SeqFrames* seq = nullptr; const MelPack* pack = nullptr; };
+inline MelCarry mel_emotion(const float* emotion, float* zemo) { return {emotion, zemo, nullptr, nullptr}; }
+inline MelCarry mel_to_frames(const SeqFrames* seq) { return {nullptr, nullptr, seq, nullptr}; }
+inline MelCarry mel_to_pack(const MelPack* pack) { return {nullptr, nullptr, nullptr, pack}; }
+int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, const MelCarry& carry = {});
+// true when launch_mel_power launches mel_power_rp_kernel, the row-parallel 1024-point kernel
+bool mel_rp_ok(Context* c, MelPlan* p);
+bool clip_frames_shared(Context* c, MelPlan* p);   // windows at multiples of the hop share the clip's STFT frames (km_mel.hip)
 bool mel_packs(Context* c, MelPlan* p, int64_t n_frames, int64_t T);
 // Training from a resident clip (km_train_step_clip).  Window b of the batch is samples [start[b] hop, + T hop) of the clip.
 // launch_mel_clip_span: ONE front-end launch writes `span` (n_span, n_mels) = the power-mel of clip frames min_start ..
@@ -321,11 +354,15 @@ int launch_train_clip_pack(Context* c, MelPlan* p, const float* span, const floa
                            int min_start, int64_t n_span, int T, int KP, float* xt, void* stream);
 bool mel_fuses_emotion(Context* c, MelPlan* p);
 int ensure_chunk_counters(Context* c, int64_t windows, void* stream);
+// Grow-only device buffers.  grow_buffer(&ptr, &cap, ...): ptr holds cap units of unit_bytes; when `need` exceeds that it is replaced,
+// once the stream has drained, by one of `need` units (contents undefined).  An allocation cannot be captured: inside a stream
+// capture growth_refused fails with KM_ERR_WORKSPACE, before any HIP call of the entry point.
+int growth_refused(void* stream, const char* what, int64_t need, int64_t cap);
+int grow_buffer(void* ptr_addr, int64_t* cap, int64_t need, size_t unit_bytes, void* stream, const char* what);
 int launch_ring_push(Context* c, const float* samples, int64_t n_per_stream, void* stream);
-int launch_mel(Context* c, MelPlan* p, const float* audio, int64_t B, int64_t L, int64_t out_frames,
-               float* mel_long, float* mel_short, void* stream, int64_t clip_len = 0, int64_t win_step = 0,
-               int64_t win0 = 0, int wins_per_clip = 1);
-int launch_mel_packed(Context* c, MelPlan* p, const float* audio, int64_t B, int64_t L, float* xp, int T, int KP, void* stream);
+// launch_mel_power + the log-mel image(s) / the packed log-mel image of the generic core; the window maxima are left at zero
+int launch_mel(Context* c, MelPlan* p, const MelSrc& src, int64_t out_frames, float* mel_long, float* mel_short, void* stream);
+int launch_mel_packed(Context* c, MelPlan* p, const MelSrc& src, float* xp, int T, int KP, void* stream);
 int upload_mel_plan(MelPlan* p);
 void free_mel_plan(MelPlan* p);
 

@@ -930,18 +930,11 @@ int launch_emotion(Context* c, const float* emo, int64_t B, float* zemo, void* s
 static int core_attrs(Context* c) {
     static PerDeviceOnce once;
     if (once.first(c->device)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core_fused_kernel<false, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, fused::LDS_BYTES));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core_fused_kernel<true, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, fused::LDS_BYTES));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core_fused_kernel<false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, fused::LDS_BYTES));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core_fused_kernel<false, true, 2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, fused::lds_bytes(2)));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core_fused_kernel<false, true, 3>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, fused::lds_bytes(3)));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core_fused_kernel<false, true, 0, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, fused::LDS_BYTES));
+        const struct { const void* fn; int lds; } kernels[] = {
+            {(const void*)&core_fused_kernel<false, false>, fused::LDS_BYTES}, {(const void*)&core_fused_kernel<true, false>, fused::LDS_BYTES},
+            {(const void*)&core_fused_kernel<false, true>, fused::LDS_BYTES}, {(const void*)&core_fused_kernel<false, true, 2>, fused::lds_bytes(2)},
+            {(const void*)&core_fused_kernel<false, true, 3>, fused::lds_bytes(3)}, {(const void*)&core_fused_kernel<false, true, 0, true>, fused::LDS_BYTES}};
+        for (const auto& k : kernels) HIP_TRY(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
     }
     return KM_OK;
 }
@@ -1039,19 +1032,21 @@ int launch_clip_window_max(Context* c, const float* span, const float* edge, con
     return KM_OK;
 }
 
-int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, const float* zemo, float* out,
-                         float* state, int first, void* stream, int64_t win0, int zemo_div, int64_t n_use,
-                         const unsigned char* ready, unsigned char* started, const SeqCore* seq) {
+int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, const float* zemo, float* out, void* stream,
+                         const CoreSrc& src) {
     if (int rc = core_attrs(c)) return rc;
     CoreArgs a{};
     core_weights(c, a);
     a.zemo = zemo; a.t_in = (int)n_frames;
-    a.out = out; a.state = state; a.first = first; a.win0 = win0; a.zemo_div = zemo_div > 0 ? zemo_div : 1;
+    a.out = out; a.state = src.state; a.first = src.first; a.win0 = src.win0; a.zemo_div = src.zemo_div > 0 ? src.zemo_div : 1;
     a.melpow = c->ws_melpow; a.melmax = c->ws_melmax; a.n_frames = (int)n_frames; a.lp = plan_log_params(p);
-    a.n_use = (int)(n_use > 0 ? n_use : n_frames); a.ready = ready; a.started = started;
-    if (seq) { a.seq_pow = seq->pow; a.seq_edge = seq->edge; a.seq_nfc = seq->nfc; a.seq_stride = seq->stride; a.seq_n = seq->n_per_clip; }
-    if (seq && seq->start) {     // km_forward_clip: rows by table (never with the experimental split core: km_forward_clip refuses it)
-        a.seq_start = seq->start; a.seq_min = seq->min_start;
+    a.n_use = (int)(src.n_use > 0 ? src.n_use : n_frames); a.ready = src.ready; a.started = src.started;
+    if (const SeqCore* s = src.seq) { a.seq_pow = s->pow; a.seq_edge = s->edge; a.seq_nfc = s->nfc; a.seq_stride = s->stride; a.seq_n = s->n_per_clip; }
+    if (const ClipTable* t = src.tab) {     // km_forward_clip: rows by table
+        if (src.seq || c->opt.core_split == 3 || c->opt.core_split == 6)
+            return fail(KM_ERR_UNSUPPORTED, "fused core: a start-frame table goes with neither strided images nor the split-bf16 variant");
+        a.seq_pow = t->span; a.seq_edge = t->edge; a.seq_nfc = t->n_span; a.seq_stride = 0; a.seq_n = 1;
+        a.seq_start = t->start; a.seq_min = t->min_start;
         hipLaunchKernelGGL((core_fused_kernel<false, true, 0, true>), dim3((unsigned)B), dim3(fused::NT), fused::LDS_BYTES, (hipStream_t)stream, a);
         HIP_TRY(hipGetLastError());
         return KM_OK;

@@ -1219,49 +1219,81 @@ static LogParams log_params(const km_mel_config& m) {
     return lp;
 }
 
-// One chunk-request counter per window of a launch (MelArgs::chunk_ctr).  The kernel leaves them at zero, so the buffer is
-// zeroed once, when it is (re)allocated; km_reserve sizes it, a larger launch grows it (not inside a stream capture).
-int ensure_chunk_counters(Context* c, int64_t windows, void* stream) {
-    if (windows <= c->ws_chunkctr_cap) return KM_OK;
-    hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-        return fail(KM_ERR_WORKSPACE, "front end: %lld windows exceed the reserved %lld during a stream capture: call km_reserve first",
-                    (long long)windows, (long long)c->ws_chunkctr_cap);
-    if (c->ws_chunkctr) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(c->ws_chunkctr)); c->ws_chunkctr = nullptr; c->ws_chunkctr_cap = 0; }
-    const int64_t cap_n = windows < 4096 ? 4096 : windows;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ws_chunkctr), (size_t)cap_n * sizeof(unsigned)));
-    HIP_TRY(hipMemsetAsync(c->ws_chunkctr, 0, (size_t)cap_n * sizeof(unsigned), st));
-    HIP_TRY(hipStreamSynchronize(st));            // the caller's later launches may be on another stream
-    c->ws_chunkctr_cap = cap_n;
+int growth_refused(void* stream, const char* what, int64_t need, int64_t cap) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(KM_ERR_WORKSPACE, "%s: %lld exceeds the %lld allocated during a stream capture: run one call with this span first",
+                    what, (long long)need, (long long)cap);
     return KM_OK;
 }
 
-// power-mel (B, n_frames, n_mels) + per-window max into the workspace
+int grow_buffer(void* ptr_addr, int64_t* cap, int64_t need, size_t unit_bytes, void* stream, const char* what) {
+    void** ptr = static_cast<void**>(ptr_addr);
+    if (need <= *cap) return KM_OK;
+    if (int rc = growth_refused(stream, what, need, *cap)) return rc;
+    if (*ptr) { HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); HIP_TRY(hipFree(*ptr)); *ptr = nullptr; *cap = 0; }
+    HIP_TRY(hipMalloc(ptr, (size_t)need * unit_bytes));
+    *cap = need;
+    return KM_OK;
+}
+
+// One chunk-request counter per window of a launch (MelArgs::chunk_ctr).  The kernel leaves them at zero, so the buffer is
+// zeroed once, when it is (re)allocated; km_finalize and km_reserve size it, a larger launch grows it (not inside a stream capture).
+int ensure_chunk_counters(Context* c, int64_t windows, void* stream) {
+    if (windows <= c->ws_chunkctr_cap) return KM_OK;
+    const int64_t cap_n = windows < 4096 ? 4096 : windows;
+    if (int rc = grow_buffer(&c->ws_chunkctr, &c->ws_chunkctr_cap, cap_n, sizeof(unsigned), stream, "front end: windows of one launch")) return rc;
+    HIP_TRY(hipMemsetAsync(c->ws_chunkctr, 0, (size_t)cap_n * sizeof(unsigned), (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));            // the caller's later launches may be on another stream
+    return KM_OK;
+}
+
+// mel_two_frame: A/B switch, the two-frames-per-wave kernel.  The grouped filter image: build_mel_plan makes one for every 1024-point
+// plan of up to 128 filters (its extent stays below kMelRpRow), and no entry point accepts more
+bool mel_rp_ok(Context* c, MelPlan* p) { return p->cfg.n_fft == 1024 && !c->opt.mel_two_frame && p->d_fbg_gid != nullptr; }
+
+// true when the windows of a batch that start at multiples of the hop inside one clip share the clip's STFT frames
+// (km_train_step_clip, km_forward_clip).  That needs (a) zero padding -- a reflected boundary frame is not a clip frame
+// either, but the span and edge images are built for zeros -- (b) hop >= n_fft / 2: frame f of a window spans its samples
+// [f hop - n_fft / 2, f hop + n_fft / 2), so only then are frames 1 .. T - 1 free of the window's padding and equal to the
+// clip's own frames (hop 533: frame 1 starts at sample 21; hop 266: frames 1 and T - 1 reach into the padding too), and (c) rows
+// of the model's NK channels, read four at a time.
+bool clip_frames_shared(Context* c, MelPlan* p) {
+    const km_mel_config& m = p->cfg;
+    return m.pad_mode == KM_PAD_CONSTANT && 2 * m.hop_length >= m.n_fft && m.n_mels == c->NK && c->NK % 4 == 0;
+}
+
 // true when launch_mel_power can compute the per-window emotion logits inside the front-end kernel
 bool mel_fuses_emotion(Context* c, MelPlan* p) {
-    const bool use_rp = !c->opt.mel_two_frame && !c->opt.emotion_separate;
     auto pow2 = [](int v) { return v >= 64 && v <= 1024 && (v & (v - 1)) == 0; };
     static const bool generic_ok = std::getenv("KM_EMOTION_GENERIC_SEPARATE") == nullptr;
     const bool d256 = c->d == 256 && c->DH == 128;
-    return use_rp && p->cfg.n_fft == 1024 && c->kind == 0 && c->ED <= 256 && (d256 || (generic_ok && pow2(c->d) && pow2(c->DH)));
+    return mel_rp_ok(c, p) && !c->opt.emotion_separate && c->kind == 0 && c->ED <= 256 && (d256 || (generic_ok && pow2(c->d) && pow2(c->DH)));
 }
 
-// true when launch_mel_power can write the training step's packed input itself (MelPack): the 1024-point kernel with a grouped
-// filter image, librosa's dB conversion with top_db == db_add and db_scale > 0 (the floor then maps to exactly 0 and the scale
+// true when launch_mel_power can write the training step's packed input itself (MelPack): the row-parallel kernel,
+// librosa's dB conversion with top_db == db_add and db_scale > 0 (the floor then maps to exactly 0 and the scale
 // commutes with the max: db_finish_fast; under a negative scale the floor becomes a ceiling, min(x scale, 0)), and at
 // least T frames (every slot of a row is then written by the launch: short clips take the conversion operation of phase 0)
 bool mel_packs(Context* c, MelPlan* p, int64_t n_frames, int64_t T) {
     const km_mel_config& m = p->cfg;
-    return m.n_fft == 1024 && !c->opt.mel_two_frame && p->d_fbg_gid != nullptr && m.log_mode == KM_LOG_DB_MAX && m.top_db == m.db_add &&
-           m.db_scale > 0.f &&
-           n_frames >= T && n_frames >= 3;
+    return mel_rp_ok(c, p) && m.log_mode == KM_LOG_DB_MAX && m.top_db == m.db_add && m.db_scale > 0.f && n_frames >= T && n_frames >= 3;
 }
 
-int launch_mel_power(Context* c, MelPlan* p, const float* audio, int64_t B, int64_t L, void* stream,
-                     int64_t clip_len, int64_t win_step, int64_t win0, int wins_per_clip, const int* ring_start,
-                     const unsigned char* ready, const float* emotion, float* zemo, const SeqFrames* seq, const MelPack* pack) {
+static void mel_plan_args(MelPlan* p, MelArgs& a) {
     const km_mel_config& m = p->cfg;
+    a.hop = m.hop_length; a.pad_mode = m.pad_mode;
+    a.n_mels = m.n_mels; a.window = p->d_window; a.twiddle = reinterpret_cast<const float2*>(p->d_twiddle);
+    a.fb_start = p->d_fb_start; a.fb_count = p->d_fb_count; a.fb_offset = p->d_fb_offset; a.fb_weight = p->d_fb_weight;
+    a.fb_nnz = (int)p->fb_weight.size();
+    a.fbg_gid = p->d_fbg_gid; a.fbg_desc = p->d_fbg_desc; a.fbg_weight = p->d_fbg_weight; a.fbg_nw = (int)p->fbg_weight.size();
+}
+
+// power-mel (B, n_frames, n_mels) + per-window max into the workspace (or what `carry` says)
+int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, const MelCarry& carry) {
+    const km_mel_config& m = p->cfg;
+    const SeqFrames* seq = carry.seq;
+    const int64_t B = src.B, L = src.L;
     const int64_t n_frames = seq ? seq->n_rows : 1 + L / m.hop_length;
     if (m.pad_mode == KM_PAD_REFLECT && L <= m.n_fft / 2)
         return fail(KM_ERR_INVALID_ARG, "reflect padding needs more than n_fft/2 = %d samples (got %lld)", m.n_fft / 2, (long long)L);
@@ -1270,25 +1302,21 @@ int launch_mel_power(Context* c, MelPlan* p, const float* audio, int64_t B, int6
                     (long long)c->ws_windows, (long long)c->ws_frames, (long long)B, (long long)n_frames);
     if (!seq && m.n_mels > c->ws_mels)
         return fail(KM_ERR_WORKSPACE, "workspace rows hold %d mel bins, this plan has %d: call km_reserve", c->ws_mels, m.n_mels);
-    if (seq && !(m.n_fft == 1024 && !c->opt.mel_two_frame))
-        return fail(KM_ERR_UNSUPPORTED, "shared-frame sequence mode needs the 1024-point front end");
+    // what the launch carries has to fit its source and its kernel (MelCarry in km_context.h): checked here and nowhere else
+    const bool ring = src.ring_start != nullptr, plain = !ring && src.wins_per_clip <= 1;
+    if ((carry.emotion != nullptr) + (seq != nullptr) + (carry.pack != nullptr) > 1 || (seq && !(mel_rp_ok(c, p) && !ring)) ||
+        (carry.pack && !(plain && mel_packs(c, p, n_frames, carry.pack->T) && carry.pack->KP >= carry.pack->T + 3)) ||
+        (carry.emotion && !(mel_fuses_emotion(c, p) && carry.zemo && src.wins_per_clip <= 1)))
+        return fail(KM_ERR_UNSUPPORTED, "launch_mel_power: emotion rider, frame image or packed output requested for an unsupported configuration");
     if (!p->uploaded) return fail(KM_ERR_NOT_FINALIZED, "mel plan not uploaded (km_finalize / km_reserve first)");
     static PerDeviceOnce once;
     if (once.first(c->device)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_power_kernel<1024, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)mel_lds_bytes(1024)));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_power_kernel<512, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)mel_lds_bytes(512)));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_power_kernel<1024, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)mel_lds_bytes(1024)));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_power_kernel<512, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)mel_lds_bytes(512)));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_power_rp_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_power_rp_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_power_rp_kernel<false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        const struct { const void* fn; int lds; } kernels[] = {
+            {(const void*)&mel_power_kernel<1024, false>, (int)mel_lds_bytes(1024)}, {(const void*)&mel_power_kernel<512, false>, (int)mel_lds_bytes(512)},
+            {(const void*)&mel_power_kernel<1024, true>, (int)mel_lds_bytes(1024)}, {(const void*)&mel_power_kernel<512, true>, (int)mel_lds_bytes(512)},
+            {(const void*)&mel_power_rp_kernel<false>, 160 * 1024}, {(const void*)&mel_power_rp_kernel<true>, 160 * 1024},
+            {(const void*)&mel_power_rp_kernel<false, true>, 160 * 1024}};
+        for (const auto& k : kernels) HIP_TRY(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
     }
     hipStream_t st = (hipStream_t)stream;
     if (int rc = ensure_chunk_counters(c, B, stream)) return rc;
@@ -1301,28 +1329,19 @@ int launch_mel_power(Context* c, MelPlan* p, const float* audio, int64_t B, int6
         c->melmax_dirty = false;
     }
     MelArgs a;
-    a.audio = audio; a.L = L; a.clip_len = clip_len > 0 ? clip_len : L; a.win_step = win_step; a.win0 = win0;
-    a.wins_per_clip = wins_per_clip > 0 ? wins_per_clip : 1; a.n_frames = (int)n_frames;
-    a.ring_start = ring_start; a.ready = ready; a.hop = m.hop_length; a.pad_mode = m.pad_mode;
-    a.n_mels = m.n_mels; a.window = p->d_window; a.twiddle = reinterpret_cast<const float2*>(p->d_twiddle);
-    a.fb_start = p->d_fb_start; a.fb_count = p->d_fb_count; a.fb_offset = p->d_fb_offset; a.fb_weight = p->d_fb_weight;
-    a.fb_nnz = (int)p->fb_weight.size();
-    a.fbg_gid = p->d_fbg_gid; a.fbg_desc = p->d_fbg_desc; a.fbg_weight = p->d_fbg_weight; a.fbg_nw = (int)p->fbg_weight.size();
+    mel_plan_args(p, a);
+    a.audio = src.audio; a.L = L; a.clip_len = src.clip_len; a.win_step = src.win_step; a.win0 = src.win0;
+    a.wins_per_clip = src.wins_per_clip > 0 ? src.wins_per_clip : 1; a.n_frames = (int)n_frames;
+    a.ring_start = src.ring_start; a.ready = src.ready;
     a.melpow = c->ws_melpow; a.melmax = c->ws_melmax;
     a.frame_mul = 1; a.frame_max = nullptr; a.chunk_ctr = c->ws_chunkctr;
     a.pack_xt = nullptr; a.pack_T = a.pack_KP = 0; a.pack_amin = m.amin;
     a.tab_start = nullptr; a.tab_edge = nullptr; a.tab_min = a.tab_T = a.tab_span_wgs = 0;
-    if (pack) {
-        if (!mel_packs(c, p, n_frames, pack->T) || seq || ring_start || wins_per_clip > 1 || pack->KP < pack->T + 3)
-            return fail(KM_ERR_UNSUPPORTED, "launch_mel_power: packed output requested for an unsupported configuration");
-        a.pack_xt = pack->xt; a.pack_T = pack->T; a.pack_KP = pack->KP;
-    }
+    if (carry.pack) { a.pack_xt = carry.pack->xt; a.pack_T = carry.pack->T; a.pack_KP = carry.pack->KP; }
     if (seq) { a.melpow = seq->pow; a.frame_max = seq->fmax; a.frame_mul = seq->frame_mul; a.melmax = nullptr; }
-    if (emotion) {
-        if (!mel_fuses_emotion(c, p) || !zemo || wins_per_clip > 1)
-            return fail(KM_ERR_UNSUPPORTED, "launch_mel_power: emotion fusion requested for an unsupported configuration");
+    if (carry.emotion) {
         auto dvp = [&](const char* name) { return (const float*)c->packed.at(name).dev; };
-        a.emo.emo = emotion; a.emo.ED = c->ED; a.emo.zemo = zemo;
+        a.emo.emo = carry.emotion; a.emo.ED = c->ED; a.emo.zemo = carry.zemo;
         a.emo.d = c->d; a.emo.DH = c->DH;
         a.emo.wee_t = (c->d == 256 && c->DH == 128) ? dvp("wee_t256") : dvp("wee_t"); a.emo.bee = dvp("bee"); a.emo.lg = dvp("eln_g"); a.emo.lb = dvp("eln_b");
         a.emo.we2 = dvp("we2"); a.emo.be2 = dvp("be2"); a.emo.w2 = dvp("w2"); a.emo.b2 = dvp("b2");
@@ -1334,19 +1353,18 @@ int launch_mel_power(Context* c, MelPlan* p, const float* audio, int64_t B, int6
     if (per_window > n_chunks) per_window = n_chunks;
     if (per_window < 1) per_window = 1;
     const dim3 grid((unsigned)per_window, (unsigned)B);
-    const bool use_rp = !c->opt.mel_two_frame;   // A/B switch: the two-frames-per-wave kernel
-    if (m.n_fft == 1024 && use_rp && p->d_fbg_gid) {     // (more than 128 filters have no grouped image: the kernel below)
+    if (mel_rp_ok(c, p)) {
         const size_t ldsrp = melrp_lds_bytes(a.fbg_nw);      // 74 KB: two workgroups per CU
-        if (pack) hipLaunchKernelGGL((mel_power_rp_kernel<false, true>), grid, dim3(melrp::NT), ldsrp, st, a);
-        else if (!ring_start) hipLaunchKernelGGL((mel_power_rp_kernel<false>), grid, dim3(melrp::NT), ldsrp, st, a);
+        if (carry.pack) hipLaunchKernelGGL((mel_power_rp_kernel<false, true>), grid, dim3(melrp::NT), ldsrp, st, a);
+        else if (!ring) hipLaunchKernelGGL((mel_power_rp_kernel<false>), grid, dim3(melrp::NT), ldsrp, st, a);
         else hipLaunchKernelGGL((mel_power_rp_kernel<true>), grid, dim3(melrp::NT), ldsrp, st, a);
         HIP_TRY(hipGetLastError());
         return KM_OK;
     }
     const size_t lds = mel_lds_bytes(m.n_fft, m.n_mels, a.fb_nnz);
-    if (m.n_fft == 1024 && !ring_start) hipLaunchKernelGGL((mel_power_kernel<1024, false>), grid, dim3(256), lds, st, a);
+    if (m.n_fft == 1024 && !ring) hipLaunchKernelGGL((mel_power_kernel<1024, false>), grid, dim3(256), lds, st, a);
     else if (m.n_fft == 1024) hipLaunchKernelGGL((mel_power_kernel<1024, true>), grid, dim3(256), lds, st, a);
-    else if (!ring_start) hipLaunchKernelGGL((mel_power_kernel<512, false>), grid, dim3(256), lds, st, a);
+    else if (!ring) hipLaunchKernelGGL((mel_power_kernel<512, false>), grid, dim3(256), lds, st, a);
     else hipLaunchKernelGGL((mel_power_kernel<512, true>), grid, dim3(256), lds, st, a);
     HIP_TRY(hipGetLastError());
     return KM_OK;
@@ -1452,19 +1470,10 @@ __global__ __launch_bounds__(clippack::NT) void train_clip_pack_kernel(ClipPackA
     }
 }
 
-static void mel_plan_args(MelPlan* p, MelArgs& a) {
-    const km_mel_config& m = p->cfg;
-    a.hop = m.hop_length; a.pad_mode = m.pad_mode;
-    a.n_mels = m.n_mels; a.window = p->d_window; a.twiddle = reinterpret_cast<const float2*>(p->d_twiddle);
-    a.fb_start = p->d_fb_start; a.fb_count = p->d_fb_count; a.fb_offset = p->d_fb_offset; a.fb_weight = p->d_fb_weight;
-    a.fb_nnz = (int)p->fb_weight.size();
-    a.fbg_gid = p->d_fbg_gid; a.fbg_desc = p->d_fbg_desc; a.fbg_weight = p->d_fbg_weight; a.fbg_nw = (int)p->fbg_weight.size();
-}
-
 int launch_mel_clip_span(Context* c, MelPlan* p, const float* clip, int64_t clip_len, const int* start_frames, int64_t B,
                          int min_start, int64_t n_span, int T, float* span, float* edge, void* stream) {
     const km_mel_config& m = p->cfg;
-    if (!(m.n_fft == 1024 && !c->opt.mel_two_frame && p->d_fbg_gid) || m.pad_mode != KM_PAD_CONSTANT || 2 * m.hop_length < m.n_fft)
+    if (!mel_rp_ok(c, p) || !clip_frames_shared(c, p))
         return fail(KM_ERR_UNSUPPORTED, "clip-span front end: needs the 1024-point kernel, constant padding and hop >= n_fft / 2");
     if (!p->uploaded) return fail(KM_ERR_NOT_FINALIZED, "mel plan not uploaded (km_finalize / km_reserve first)");
     if (!clip || !start_frames || !span || !edge || B <= 0 || n_span < T + 1 || min_start < 0)
@@ -1512,25 +1521,23 @@ int launch_train_clip_pack(Context* c, MelPlan* p, const float* span, const floa
 }
 
 // front end for the generic core: power-mel, then the packed log-mel image (B, KP, n_mels)
-int launch_mel_packed(Context* c, MelPlan* p, const float* audio, int64_t B, int64_t L, float* xp, int T, int KP, void* stream) {
-    if (int rc = launch_mel_power(c, p, audio, B, L, stream)) return rc;
+int launch_mel_packed(Context* c, MelPlan* p, const MelSrc& src, float* xp, int T, int KP, void* stream) {
+    if (int rc = launch_mel_power(c, p, src, stream)) return rc;
     const km_mel_config& m = p->cfg;
     LogArgs g;
-    g.melpow = c->ws_melpow; g.melmax = c->ws_melmax; g.n_frames = (int)(1 + L / m.hop_length);
+    g.melpow = c->ws_melpow; g.melmax = c->ws_melmax; g.n_frames = (int)(1 + src.L / m.hop_length);
     g.out_frames = g.n_frames; g.n_mels = m.n_mels; g.lp = log_params(m); g.mel_long = nullptr; g.mel_short = nullptr;
-    const dim3 grid((unsigned)((KP * m.n_mels + 255) / 256), (unsigned)B);
+    const dim3 grid((unsigned)((KP * m.n_mels + 255) / 256), (unsigned)src.B);
     hipLaunchKernelGGL(mel_log_packed_kernel, grid, dim3(256), 0, (hipStream_t)stream, g, xp, T, KP);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(c->ws_melmax, 0, (size_t)B * sizeof(unsigned), (hipStream_t)stream));   // leave the maxima as found
+    HIP_TRY(hipMemsetAsync(c->ws_melmax, 0, (size_t)src.B * sizeof(unsigned), (hipStream_t)stream));   // leave the maxima as found
     return KM_OK;
 }
 
-int launch_mel(Context* c, MelPlan* p, const float* audio, int64_t B, int64_t L, int64_t out_frames,
-               float* mel_long, float* mel_short, void* stream, int64_t clip_len, int64_t win_step, int64_t win0,
-               int wins_per_clip) {
-    if (int rc = launch_mel_power(c, p, audio, B, L, stream, clip_len, win_step, win0, wins_per_clip)) return rc;
+int launch_mel(Context* c, MelPlan* p, const MelSrc& src, int64_t out_frames, float* mel_long, float* mel_short, void* stream) {
+    if (int rc = launch_mel_power(c, p, src, stream)) return rc;
     const km_mel_config& m = p->cfg;
-    const int64_t n_frames = 1 + L / m.hop_length;
+    const int64_t B = src.B, n_frames = 1 + src.L / m.hop_length;
     LogArgs g;
     g.melpow = c->ws_melpow; g.melmax = c->ws_melmax; g.n_frames = (int)n_frames;
     g.out_frames = (int)(out_frames > 0 ? out_frames : n_frames); g.n_mels = m.n_mels; g.lp = log_params(m);

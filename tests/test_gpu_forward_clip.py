@@ -15,7 +15,7 @@ import torch
 from scipy.io import wavfile
 
 from koemorph_amd import synth
-from koemorph_amd._lib import KM_ERR_INVALID_ARG, KM_ERR_UNSUPPORTED, KoeMorphError, check, load
+from koemorph_amd._lib import KM_ERR_INVALID_ARG, KM_ERR_UNSUPPORTED, KM_PAD_REFLECT, KoeMorphError, check, load
 from koemorph_amd.data import SequentialKoeMorphDataset
 from koemorph_amd.engine import Engine, MelConfig
 
@@ -156,6 +156,67 @@ def test_argument_errors(eng, clip):
         eng.forward_clip(clip, starts, emo)
     with pytest.raises(ValueError):
         eng.forward_clip(clip, [0, 1, 2], emo)                                             # 3 windows, 4 emotion rows
+    torch.cuda.synchronize()
+
+
+# ---- which handles share frames: km_forward_clip_supported / km_train_clip_supported ---------------------------------------------
+# Expected (forward, train), written out from the derivations in the library, not from what it returns:
+#   both     the row-parallel 1024-point front end (n_fft 1024, not mel_two_frame), zero (constant) padding -- the span and
+#            edge images are built for zeros --, 2 hop >= n_fft (frame f of a window spans [f hop - n_fft / 2, f hop + n_fft / 2),
+#            so only then do frames 1 .. T - 1 stay clear of the window's padding: 2 * 533 >= 1024, 2 * 266 = 532 < 1024)
+#   forward  + the fused core without its split-bf16 variant (core_split 3 has no table variant); the training options and
+#            the dB constants do not matter to it
+#   train    + the packing front end: neither train_no_fe_pack nor train_no_dma, log mode dB with top_db == db_add and
+#            db_scale > 0 (under a negative scale the floor becomes a ceiling); core_split does not matter to it
+# Every row is the supported base (fused shape, n_fft 1024, hop 533, constant padding, (dB + 80) / 80) with the named change.
+SUPPORT_TABLE = [
+    # mel config changes                        options                            forward  train
+    ({},                                        {},                                1, 1),
+    (dict(db_scale=2.0),                        {},                                1, 1),     # positive scale, top_db == db_add
+    (dict(db_scale=-1.0 / 80.0),                {},                                1, 0),     # negative scale, top_db == db_add
+    (dict(top_db=60.0),                         {},                                1, 0),     # top_db != db_add
+    (dict(pad_mode=KM_PAD_REFLECT),             {},                                0, 0),
+    (dict(hop_length=266),                      {},                                0, 0),
+    (dict(n_fft=512),                           {},                                0, 0),     # 2 * 533 >= 512, but not the 1024-point kernel
+    (dict(n_fft=512, hop_length=266),           {},                                0, 0),     # 2 * 266 >= 512 as well
+    (dict(hop_length=266, pad_mode=KM_PAD_REFLECT), {},                            0, 0),
+    ({},                                        dict(mel_two_frame=1),             0, 0),
+    ({},                                        dict(core_split=3),                0, 1),
+    ({},                                        dict(train_no_fe_pack=1),          1, 0),
+    ({},                                        dict(train_no_dma=1),              1, 0),
+    ({},                                        dict(core_split=3, train_no_dma=1), 0, 0),
+    ({},                                        dict(train_no_fe_pack=1, train_no_dma=1), 1, 0),
+    (dict(db_scale=-1.0 / 80.0),                dict(core_split=3),                0, 0),
+    (dict(hop_length=266),                      dict(core_split=3, train_no_fe_pack=1), 0, 0),
+    (dict(n_fft=512),                           dict(mel_two_frame=1),             0, 0),
+]
+
+
+def test_clip_supported_predicates_over_front_end_configurations_and_options():
+    """km_forward_clip_supported and km_train_clip_supported on handles of the fused shape: one per mel configuration of
+    SUPPORT_TABLE, the options switched on the live handle and back.  No forward or training launch: km_finalize, and
+    km_train_init (one window) because km_train_clip_supported is 0 by contract before the training state exists."""
+    lib = load()
+    params = synth.make_core_params(795)
+    handles = {}
+    for mel_kw, opts, want_fwd, want_train in SUPPORT_TABLE:
+        key = tuple(sorted(mel_kw.items()))
+        if key not in handles:
+            e = Engine(mel=MelConfig(**mel_kw))
+            e.load_state_dict(params)
+            e.finalize()
+            assert lib.km_train_clip_supported(e._h) == 0                       # no training state yet
+            check(lib.km_train_init(e._h, 1, torch.cuda.current_stream().cuda_stream))
+            handles[key] = e
+        e = handles[key]
+        for k, v in opts.items():
+            e.set_option(k, v)
+        try:
+            got = (lib.km_forward_clip_supported(e._h), lib.km_train_clip_supported(e._h))
+        finally:
+            for k in opts:
+                e.set_option(k, 0)
+        assert got == (want_fwd, want_train), (mel_kw, opts, got)
     torch.cuda.synchronize()
 
 
