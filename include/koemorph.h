@@ -522,6 +522,34 @@ int km_stream_push(km_handle h, const float* samples_dev, int64_t n_per_stream, 
 int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* ready_dev, void* stream);
 int km_stream_reset(km_handle h, void* stream);
 
+/* ---- streaming the legacy SimplifiedKoeMorphModel: consuming FIFOs resident on the device ---------------------
+ * Legacy handles (km_legacy_create, after km_finalize) only; the km_stream_* family above keeps refusing them and this one
+ * refuses dual-stream and KoeMorphModel handles.  Replaces, for all streams at once, the real-time loop of
+ * scripts/rt_simplified.py: RingBuffer (:46-97) and SimplifiedRealTimeInference.process_audio_chunk / inference_step (:374-399).
+ *   km_legacy_stream_create  n_streams FIFOs of buffer_samples floats (int(buffer_duration * sr), :333) with their write_ptr,
+ *                            read_ptr and available (:49-54), plus everything a tick needs (pop staging, power-mel, window
+ *                            maxima, attention output; the workspace through km_reserve).  Allocates: call it once, outside
+ *                            any graph capture.  KM_ERR_INVALID_ARG for non-positive arguments or audio_length >
+ *                            buffer_samples; KM_ERR_UNSUPPORTED, naming the frame count, when 1 + audio_length / hop
+ *                            (simplified_model.py:40) exceeds 32 or the handle is not d_model 256 / 8 heads / decoder hidden
+ *                            128 behind the 1024-point front end.  Longer windows and other widths keep using
+ *                            km_legacy_forward on windows the caller pops.
+ *   km_legacy_stream_push    RingBuffer.write (:56-75) for every stream: samples_dev (n_streams, n_per_stream); counts_dev
+ *                            (n_streams) int32, each clamped to 0 .. n_per_stream, or NULL = n_per_stream for all.  Stream s
+ *                            appends min(count[s], buffer_samples - available[s]) samples and drops the rest (:59-62).
+ *   km_legacy_stream_tick    RingBuffer.read(audio_length) + model(audio) (:378-399) for every stream: ready_dev[s] (u8, may
+ *                            be NULL) = available[s] >= audio_length (:79-80); a ready stream consumes its window and gets
+ *                            out_dev[s, :52]; the row and the FIFO of a stream that is not ready are left untouched.  Three
+ *                            launches: pop, front end, model.
+ *   km_legacy_stream_reset   empties the FIFOs and zeroes the pointers; the model itself has no temporal state
+ *                            (simplified_model.py:155-157).
+ * push and tick never allocate, synchronise or read anything back: capture them in a hipGraph (one linear chain) and replay
+ * it per tick.  A later km_reserve that grows the workspace invalidates such a graph. */
+int km_legacy_stream_create(km_handle h, int64_t n_streams, int64_t buffer_samples, int64_t audio_length);
+int km_legacy_stream_push(km_handle h, const float* samples_dev, int64_t n_per_stream, const int32_t* counts_dev, void* stream);
+int km_legacy_stream_tick(km_handle h, float* out_dev, uint8_t* ready_dev, void* stream);
+int km_legacy_stream_reset(km_handle h, void* stream);
+
 /* ---- measurement aid used by bench.py ------------------------------------------------------------
  * With stage timing enabled, km_forward_audio / km_forward_audio_pipelined record HIP events on the stream each
  * kernel is launched on, right before and after it (emotion logits, power-mel front end, fused core);

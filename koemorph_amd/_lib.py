@@ -161,6 +161,10 @@ SIGNATURES = {
     "km_stream_push": (C.c_int, [_h, _p, _i64, _p]),
     "km_stream_tick": (C.c_int, [_h, _p, _p, _p, _p]),
     "km_stream_reset": (C.c_int, [_h, _p]),
+    "km_legacy_stream_create": (C.c_int, [_h, _i64, _i64, _i64]),
+    "km_legacy_stream_push": (C.c_int, [_h, _p, _i64, _p, _p]),
+    "km_legacy_stream_tick": (C.c_int, [_h, _p, _p, _p]),
+    "km_legacy_stream_reset": (C.c_int, [_h, _p]),
     "km_set_option": (C.c_int, [_h, C.c_char_p, _i64]),
     "km_egemaps_plan_create": (C.c_int, [C.POINTER(_p)]),
     "km_egemaps_plan_destroy": (C.c_int, [_p]),

@@ -24,6 +24,7 @@ using namespace km;
 static int free_streams(Context* c);
 static int free_train(Context* c);
 static int free_pipeline(Context* c);
+static int free_legacy_streams(Context* c);
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -133,6 +134,7 @@ int km_destroy(km_handle h) {
     (void)free_ws(c);
     if (c->ws_chunkctr) (void)hipFree(c->ws_chunkctr);
     (void)free_streams(c);
+    (void)free_legacy_streams(c);
     (void)free_train(c);
     (void)free_pipeline(c);
     for (void* q : {(void*)c->seq_pow, (void*)c->seq_fmax, (void*)c->seq_edge, (void*)c->seq_emax, (void*)c->fwd_span, (void*)c->fwd_edge})
@@ -980,6 +982,101 @@ int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_
     if (ready_dev)
         HIP_TRY(hipMemcpyAsync(ready_dev, c->ring_ready, (size_t)S, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return KM_OK;
+}
+
+// ---- streams of the legacy model: device-resident consuming FIFOs + the one-launch model (kernels: km_legacy_stream.hip,
+//      legacy_stream_kernel in km_kmmf.hip) ----
+static int free_legacy_streams(Context* c) {
+    void* ptrs[] = {c->lfifo, c->lfifo_state, c->lfifo_stage, c->lfifo_ready, c->lfifo_attn};
+    for (void* p : ptrs)
+        if (p) HIP_TRY(hipFree(p));
+    c->lfifo = nullptr; c->lfifo_state = nullptr; c->lfifo_stage = nullptr; c->lfifo_ready = nullptr; c->lfifo_attn = nullptr;
+    c->lfifo_cap = c->lfifo_state_cap = c->lfifo_stage_cap = c->lfifo_ready_cap = c->lfifo_attn_cap = 0;
+    c->lfifo_streams = c->lfifo_len = c->lfifo_window = 0;
+    return KM_OK;
+}
+
+// the shape legacy_stream_kernel is written for, behind the front end that leaves power-mel + window maxima
+static bool legacy_stream_ok(Context* c) {
+    return c->legacy_fused && c->legacy_tail_fused && c->d == 256 && c->H == 8 && c->legacy_hidden == 128 && c->NB == 52 && c->NK == 80 &&
+           !c->mel_plans.empty() && c->mel_plans[0]->cfg.n_fft == 1024 && legacy_pow_ok(c);
+}
+
+static int need_legacy_stream(Context* c, const char* who) {
+    if (int rc = need_ready(c)) return rc;
+    if (c->kind != 1) return fail(KM_ERR_INVALID_ARG, "%s needs a legacy handle (km_legacy_create)", who);
+    if (c->lfifo_streams <= 0) return fail(KM_ERR_INVALID_ARG, "%s: no streams (km_legacy_stream_create first)", who);
+    return KM_OK;
+}
+
+int km_legacy_stream_reset(km_handle h, void* stream) {
+    if (int rc = need_legacy_stream(h, "km_legacy_stream_reset")) return rc;
+    Context* c = h;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t S = (size_t)c->lfifo_streams;
+    HIP_TRY(hipMemsetAsync(c->lfifo, 0, S * c->lfifo_len * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(c->lfifo_stage, 0, S * c->lfifo_window * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(c->lfifo_state, 0, 3 * S * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(c->lfifo_ready, 0, S, st));
+    return KM_OK;
+}
+
+int km_legacy_stream_create(km_handle h, int64_t n_streams, int64_t buffer_samples, int64_t audio_length) {
+    if (int rc = need_ready(h)) return rc;
+    Context* c = h;
+    if (c->kind != 1) return fail(KM_ERR_INVALID_ARG, "km_legacy_stream_create needs a legacy handle (km_legacy_create)");
+    if (n_streams <= 0 || buffer_samples <= 0 || audio_length <= 0 || audio_length > buffer_samples || n_streams >= (1ll << 24) ||
+        buffer_samples >= (1ll << 30))
+        return fail(KM_ERR_INVALID_ARG, "km_legacy_stream_create: bad argument (%lld streams, buffer of %lld samples, windows of %lld)",
+                    (long long)n_streams, (long long)buffer_samples, (long long)audio_length);
+    const int64_t T = 1 + audio_length / c->cfg.mel.hop_length;                      // simplified_model.py:40
+    if (!legacy_stream_ok(c))
+        return fail(KM_ERR_UNSUPPORTED, "km_legacy_stream_create: windows of %lld frames are served for d_model 256, 8 heads, decoder hidden 128 "
+                    "behind the 1024-point front end only (got d_model %d, %d heads, hidden %d, n_fft %d)", (long long)T, c->d, c->H,
+                    c->legacy_hidden, c->mel_plans.empty() ? 0 : c->mel_plans[0]->cfg.n_fft);
+    if (T > 32)
+        return fail(KM_ERR_UNSUPPORTED, "km_legacy_stream_create: windows of %lld samples are %lld frames, the stream kernel holds at most 32 "
+                    "(use km_legacy_forward for longer windows)", (long long)audio_length, (long long)T);
+    c->lfifo_streams = 0;
+    const char* what = "km_legacy_stream_create";
+    if (int rc = grow_buffer(&c->lfifo, &c->lfifo_cap, n_streams * buffer_samples, sizeof(float), nullptr, what)) return rc;
+    if (int rc = grow_buffer(&c->lfifo_state, &c->lfifo_state_cap, 3 * n_streams, sizeof(int), nullptr, what)) return rc;
+    if (int rc = grow_buffer(&c->lfifo_stage, &c->lfifo_stage_cap, n_streams * audio_length, sizeof(float), nullptr, what)) return rc;
+    if (int rc = grow_buffer(&c->lfifo_ready, &c->lfifo_ready_cap, n_streams, 1, nullptr, what)) return rc;
+    if (int rc = grow_buffer(&c->lfifo_attn, &c->lfifo_attn_cap, n_streams * c->NB * c->d, sizeof(float), nullptr, what)) return rc;
+    if (int rc = km_reserve(h, n_streams, audio_length)) return rc;                  // power-mel, window maxima, chunk counters
+    if (!legacy_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "km_legacy_stream_create: the power-mel workspace is not 16-byte aligned");
+    c->lfifo_streams = n_streams; c->lfifo_len = buffer_samples; c->lfifo_window = audio_length;
+    HIP_TRY(hipMemset(c->ws_melmax, 0, (size_t)c->ws_windows * sizeof(unsigned)));
+    c->melmax_dirty = false;
+    if (int rc = km_legacy_stream_reset(h, nullptr)) return rc;
+    // one tick over the empty FIFOs: no stream is ready, so nothing is consumed or written (the result pointer is a dummy), but
+    // every kernel of a tick has had its attributes set before a capture can see its first launch
+    if (int rc = km_legacy_stream_tick(h, c->lfifo_attn, nullptr, nullptr)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return KM_OK;
+}
+
+int km_legacy_stream_push(km_handle h, const float* samples_dev, int64_t n_per_stream, const int32_t* counts_dev, void* stream) {
+    if (int rc = need_legacy_stream(h, "km_legacy_stream_push")) return rc;
+    if (!samples_dev || n_per_stream <= 0 || n_per_stream >= (1ll << 30))
+        return fail(KM_ERR_INVALID_ARG, "km_legacy_stream_push: bad argument");
+    return launch_lfifo_push(h, samples_dev, n_per_stream, counts_dev, stream);
+}
+
+int km_legacy_stream_tick(km_handle h, float* out_dev, uint8_t* ready_dev, void* stream) {
+    if (int rc = need_legacy_stream(h, "km_legacy_stream_tick")) return rc;
+    Context* c = h;
+    if (!out_dev) return fail(KM_ERR_INVALID_ARG, "km_legacy_stream_tick: NULL argument");
+    const int64_t S = c->lfifo_streams, W = c->lfifo_window, T = 1 + W / c->cfg.mel.hop_length;
+    if (S > c->ws_windows || T > c->ws_frames) return fail(KM_ERR_WORKSPACE, "stream workspace too small");
+    if (!legacy_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "km_legacy_stream_tick: the fused legacy kernels are switched off (km_set_option)");
+    // three launches: pop (ready flags + the claimed windows, chronological), the plain front end over the staging image,
+    // the model for every ready stream (which also puts every stream's window maximum back to zero)
+    if (int rc = launch_lfifo_pop(c, ready_dev, stream)) return rc;
+    if (int rc = launch_mel_power(c, c->mel_plans[0], mel_windows(c->lfifo_stage, S, W), stream)) return rc;
+    const LogParams lp = plan_log_params(c->mel_plans[0]);
+    return launch_legacy_stream_model(c, c->ws_melpow, c->ws_melmax, c->lfifo_ready, S, (int)T, lp, c->lfifo_attn, out_dev, stream);
 }
 
 int km_enable_stage_timing(km_handle h, int32_t enable) {

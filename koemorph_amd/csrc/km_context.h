@@ -151,6 +151,14 @@ struct Context {
     float* ring_state = nullptr;        // (n_streams, 52) EMA state
     MelPlan* stream_plan = nullptr;
     int64_t stream_out_frames = 0;
+    // streaming state of the legacy model (km_legacy_stream_*): device-resident consuming FIFOs (RingBuffer semantics,
+    // scripts/rt_simplified.py:46-97); grow-only buffers, n_streams == 0 until km_legacy_stream_create
+    int64_t lfifo_streams = 0, lfifo_len = 0, lfifo_window = 0;
+    float* lfifo = nullptr; int64_t lfifo_cap = 0;                  // (streams, lfifo_len) samples
+    int* lfifo_state = nullptr; int64_t lfifo_state_cap = 0;        // (3, streams): write_ptr | read_ptr | available
+    float* lfifo_stage = nullptr; int64_t lfifo_stage_cap = 0;      // (streams, lfifo_window) the popped windows, chronological
+    unsigned char* lfifo_ready = nullptr; int64_t lfifo_ready_cap = 0;   // (streams) this tick popped a window
+    float* lfifo_attn = nullptr; int64_t lfifo_attn_cap = 0;        // (streams, 52, 256) attention output of legacy_stream_kernel
     // training state (km_train_*): flat fp32 master parameters + AdamW moments on the device, in state-dict order
     int64_t tr_nparams = 0, tr_windows = 0;
     int64_t tr_early = 0;            // floats [0, tr_early) of the gradient bucket are final when tr_early_ev fires
@@ -360,6 +368,13 @@ int ensure_chunk_counters(Context* c, int64_t windows, void* stream);
 int growth_refused(void* stream, const char* what, int64_t need, int64_t cap);
 int grow_buffer(void* ptr_addr, int64_t* cap, int64_t need, size_t unit_bytes, void* stream, const char* what);
 int launch_ring_push(Context* c, const float* samples, int64_t n_per_stream, void* stream);
+
+// km_legacy_stream.hip: the FIFOs of km_legacy_stream_* (Context::lfifo_*)
+int launch_lfifo_push(Context* c, const float* samples, int64_t n_per_stream, const int* counts, void* stream);
+int launch_lfifo_pop(Context* c, unsigned char* ready_out, void* stream);
+// km_kmmf.hip: SimplifiedKoeMorphModel behind the front end for every stream with ready[s] != 0, windows of Tm <= 32 frames
+int launch_legacy_stream_model(Context* c, const float* melpow, unsigned* melmax, const unsigned char* ready, int64_t S, int Tm,
+                               const LogParams& lp, float* O, float* out, void* stream);
 // launch_mel_power + the log-mel image(s) / the packed log-mel image of the generic core; the window maxima are left at zero
 int launch_mel(Context* c, MelPlan* p, const MelSrc& src, int64_t out_frames, float* mel_long, float* mel_short, void* stream);
 int launch_mel_packed(Context* c, MelPlan* p, const MelSrc& src, float* xp, int T, int KP, void* stream);

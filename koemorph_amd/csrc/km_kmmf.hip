@@ -1018,6 +1018,173 @@ __global__ __launch_bounds__(512) void legacy_attn_tail_kernel(const float* __re
     legacy_tail_body(O, blob, out, b, smem);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// legacy_stream_kernel: SimplifiedKoeMorphModel behind the front end for ONE stream of km_legacy_stream_tick
+// (scripts/rt_simplified.py:378-399: model(audio[audio_length])), Tm <= 32 frames, one 512-thread workgroup, one launch.
+// A stream whose FIFO held no whole window (ready[s] == 0) leaves before the first barrier; the front end has still put the
+// maximum of whatever its staging row held into melmax[s], so that slot is put back to zero on both paths.
+//
+// LDS (128 rows of XS floats = 135 168 bytes), row ranges of the one image:
+//   [  0,  32)  E0: the window's dB mel rows (80 columns), later the encoder's second activation     |  tail: A  [0, 64)
+//   [ 32,  64)  E1: the encoder's first activation                                                    |
+//   [ 64,  96)  K rows of the window (all 8 heads)                                                    |  tail: Bi [64, 128)
+//   [ 96, 128)  V rows
+// The encoder runs as legacy_encoder_kernel does (same blob, same mm_cols), eight waves of 32 columns instead of four of 64;
+// K and V stay in LDS.  Attention: wave = head, the arithmetic of legacy_attention_body (base-2 online softmax over key tiles
+// of 16, keys >= Tm masked) with the K / V operands read from LDS.  Its output O (52 x 256) goes through memory, written and
+// read by this workgroup only (as legacy_attn_tail_kernel does), because legacy_tail_body stages its rows from there: the
+// tail's two 64-row images then take over the whole LDS image, K and V being dead.
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void legacy_stream_attention(const float* __restrict__ Qs, const float* Kl, const float* Vl,
+                                                        float* __restrict__ O, int head, int Tm) {
+    const int lane = threadIdx.x & 63, g = lane >> 4, j = lane & 15;
+    float qT[2][4][4];                          // [dim tile][query tile][reg]: Q^T[16 dt + 4 g + s][16 qt + j], base-2 domain
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int qt = 0; qt < 4; ++qt) {
+            const int q = 16 * qt + j;
+            const float4 v = q < NQ ? *reinterpret_cast<const float4*>(Qs + q * D + 32 * head + 16 * dt + 4 * g)
+                                    : make_float4(0.f, 0.f, 0.f, 0.f);
+            constexpr float kLog2e = 1.4426950408889634f;
+            qT[dt][qt][0] = v.x * kLog2e; qT[dt][qt][1] = v.y * kLog2e; qT[dt][qt][2] = v.z * kLog2e; qT[dt][qt][3] = v.w * kLog2e;
+        }
+    f32x4 oT[2][4];
+    float m[4], l[4];
+#pragma unroll
+    for (int qt = 0; qt < 4; ++qt) {
+        m[qt] = -INFINITY; l[qt] = 0.f;
+        oT[0][qt] = f32x4{0, 0, 0, 0}; oT[1][qt] = f32x4{0, 0, 0, 0};
+    }
+    const int nkt = (Tm + 15) / 16;             // 1 or 2: every row of a tile exists in the 32-row images (rows >= Tm are masked)
+    for (int kt = 0; kt < nkt; ++kt) {
+        f32x4 ka[2];
+        float va[2][4];
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) ka[dt] = *reinterpret_cast<const f32x4*>(Kl + (16 * kt + j) * XS + 32 * head + 16 * dt + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            va[0][r] = Vl[(16 * kt + 4 * g + r) * XS + 32 * head + j];
+            va[1][r] = Vl[(16 * kt + 4 * g + r) * XS + 32 * head + 16 + j];
+        }
+#pragma unroll
+        for (int qt = 0; qt < 4; ++qt) {
+            f32x4 S = f32x4{0, 0, 0, 0};
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                for (int s_ = 0; s_ < 4; ++s_) S = KM_MFMA(ka[dt][s_], qT[dt][qt][s_], S);          // S^T[key][query]
+            float tm = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (16 * kt + 4 * g + r >= Tm) S[r] = -INFINITY;
+                tm = fmaxf(tm, S[r]);
+            }
+            tm = fmaxf(tm, __shfl_xor(tm, 16));
+            tm = fmaxf(tm, __shfl_xor(tm, 32));
+            const float mn = fmaxf(m[qt], tm);
+            const float alpha = mn == -INFINITY ? 1.0f : __builtin_amdgcn_exp2f(m[qt] - mn);
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { S[r] = mn == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(S[r] - mn); ps += S[r]; }
+            l[qt] = l[qt] * alpha + ps;
+            m[qt] = mn;
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+                f32x4 o = oT[dt][qt];
+                o[0] *= alpha; o[1] *= alpha; o[2] *= alpha; o[3] *= alpha;
+#pragma unroll
+                for (int s_ = 0; s_ < 4; ++s_) o = KM_MFMA(va[dt][s_], S[s_], o);                   // O^T[dim][query]
+                oT[dt][qt] = o;
+            }
+        }
+    }
+#pragma unroll
+    for (int qt = 0; qt < 4; ++qt) {
+        float ls = l[qt];
+        ls += __shfl_xor(ls, 16);
+        ls += __shfl_xor(ls, 32);
+        const float inv = 1.0f / ls;
+        const int q = 16 * qt + j;
+        if (q < NQ) {
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt) {
+                const f32x4 o = oT[dt][qt];
+                *reinterpret_cast<float4*>(O + q * D + 32 * head + 16 * dt + 4 * g) = make_float4(o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv);
+            }
+        }
+    }
+}
+
+constexpr int LS_LDS_FLOATS = 4 * TMAX * XS;      // = the tail's 2 x 64 x XS
+__global__ __launch_bounds__(512) void legacy_stream_kernel(const float* __restrict__ melpow, unsigned* __restrict__ melmax,
+                                                           const unsigned char* __restrict__ ready, int Tm, LogParams lp,
+                                                           const float* __restrict__ enc, const float* __restrict__ Qs,
+                                                           float* __restrict__ O, const float* __restrict__ tail,
+                                                           float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int s = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (!ready[s]) {                    // nothing popped: the row of `out` and the FIFO stay as they are
+        if (tid == 0) melmax[s] = 0u;   // the front end ran over this stream's stale staging row
+        return;
+    }
+    float* E0 = smem;
+    float* E1 = smem + TMAX * XS;
+    float* Kl = smem + 2 * TMAX * XS;
+    float* Vl = smem + 3 * TMAX * XS;
+    const int g = lane >> 4, j = lane & 15;
+    const int col0 = 32 * wave;
+    {
+        float ref_db, floor_db;
+        log_window_consts(lp, __uint_as_float(melmax[s]), ref_db, floor_db);
+        const float* mp = melpow + (int64_t)s * Tm * LG_MEL;
+        for (int i = tid; i < TMAX * (LG_MEL / 4); i += NTH) {
+            const int r = i / (LG_MEL / 4), c4 = i - r * (LG_MEL / 4);
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < Tm) {
+                v = *reinterpret_cast<const float4*>(mp + r * LG_MEL + 4 * c4);
+                v = make_float4(log_one(lp, v.x, ref_db, floor_db), log_one(lp, v.y, ref_db, floor_db), log_one(lp, v.z, ref_db, floor_db),
+                                log_one(lp, v.w, ref_db, floor_db));
+            }
+            *reinterpret_cast<float4*>(E0 + r * XS + 4 * c4) = v;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) melmax[s] = 0u;       // consumed by every thread above: a clean slot for the next front-end launch
+    // dst rows = act(src W^T + b): wave = 32 columns of the 256
+    auto layer = [&](const float* src, float* dst, int64_t w_off, int64_t b_off, int kbs, bool relu) {
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = f32x4{0, 0, 0, 0};
+        mm_cols<2, 2, KM_KMMF_DEC_PIN>(acc, src, enc + w_off, 2 * wave, kbs, 0, kbs, lane);
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const float bb = enc[b_off + col0 + 16 * nt + j];
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = acc[mt][nt][r] + bb;
+                    dst[(16 * mt + 4 * g + r) * XS + col0 + 16 * nt + j] = relu && v < 0.f ? 0.f : v;
+                }
+        }
+    };
+    layer(E0, E1, LG_W0, LG_B0, LG_MEL / 16, true);
+    __syncthreads();
+    layer(E1, E0, LG_W3, LG_B3, KBD, true);
+    __syncthreads();
+    layer(E0, Kl, LG_WK, LG_BK, KBD, false);
+    layer(E0, Vl, LG_WV, LG_BV, KBD, false);
+    __syncthreads();
+    float* Os = O + (int64_t)s * NQ * D;
+    legacy_stream_attention(Qs, Kl, Vl, Os, wave, Tm);
+    __syncthreads();      // O is in memory for every wave of this workgroup, and nobody reads K or V any more
+    legacy_tail_body(O, tail, out, (int64_t)s, smem);
+}
+
 }  // namespace kf
 
 static const float* dvp(Context* c, const char* name) { return c->packed.at(name).dev; }
@@ -1109,6 +1276,20 @@ int launch_legacy_attn_tail_fused(Context* c, const float* Kp, const float* Vp, 
                                     2 * 64 * kf::XS * 4));
     hipLaunchKernelGGL(kf::legacy_attn_tail_kernel, dim3((unsigned)B), dim3(kf::NTH), 2 * 64 * kf::XS * 4, (hipStream_t)stream, dvp(c, "l_q"), Kp, Vp, O,
                        Tm, zero_max, dvp(c, "lgf_tail"), out);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+// km_legacy_stream_tick behind the front end: the whole model for every ready stream, one workgroup each, one launch
+int launch_legacy_stream_model(Context* c, const float* melpow, unsigned* melmax, const unsigned char* ready, int64_t S, int Tm,
+                               const LogParams& lp, float* O, float* out, void* stream) {
+    if (Tm < 1 || Tm > kmmf::TMAX) return fail(KM_ERR_UNSUPPORTED, "legacy stream kernel: %d frames per window, at most %d", Tm, kmmf::TMAX);
+    static PerDeviceOnce once;
+    if (once.first(c->device))
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&kf::legacy_stream_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    kf::LS_LDS_FLOATS * 4));
+    hipLaunchKernelGGL(kf::legacy_stream_kernel, dim3((unsigned)S), dim3(kf::NTH), kf::LS_LDS_FLOATS * 4, (hipStream_t)stream, melpow, melmax,
+                       ready, Tm, lp, dvp(c, "lgf_enc"), dvp(c, "l_q"), O, dvp(c, "lgf_tail"), out);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

@@ -10,6 +10,9 @@ move.  A tick is ``push`` (one ~hop-sized frame per stream, the only host->devic
 floats) followed by ``tick`` (emotion kernel, sliding-window front end over every full ring, fused core with
 per-stream EMA).  Neither allocates nor synchronises, so ``capture()`` records one tick into a hipGraph and
 ``replay()`` re-launches it with a single API call per 33 ms frame.
+
+``LegacyStreamEngine`` is the counterpart for ``SimplifiedKoeMorphModel``: the reference's consuming FIFO
+(scripts/rt_simplified.py:46-97) per stream instead of a sliding ring, no EMA, no emotion input (km_legacy_stream_*).
 """
 from __future__ import annotations
 
@@ -99,5 +102,95 @@ class StreamEngine:
             raise RuntimeError("capture() first")
         self._g_samples.copy_(samples, non_blocking=True)
         self._g_emotion.copy_(emotion, non_blocking=True)
+        self._graph.replay()
+        return self.out, self.ready
+
+
+def legacy_stream_shape(buffer_duration: float = 2.0, audio_length: int = 16000, hop: int = 533, sample_rate: int = 16000) -> dict:
+    """The arithmetic of the reference's simplified real-time loop, which km_legacy_stream_create follows: the FIFO's size in samples
+    (scripts/rt_simplified.py:333), the mel frames of one popped window (simplified_model.py:40: 1 + L // hop) and whether the
+    stream kernel holds them (at most 32).  A window longer than the FIFO can never be read: ValueError."""
+    buffer_samples = int(buffer_duration * sample_rate)
+    if audio_length <= 0 or buffer_samples <= 0 or hop <= 0:
+        raise ValueError("buffer_duration, audio_length and hop must be positive")
+    if audio_length > buffer_samples:
+        raise ValueError(f"audio_length {audio_length} exceeds the buffer of {buffer_samples} samples: no read could ever succeed")
+    n_frames = 1 + audio_length // hop
+    return dict(buffer_samples=buffer_samples, n_frames=n_frames, supported=n_frames <= 32)
+
+
+class LegacyStreamEngine:
+    """Streams of a ``SimplifiedKoeMorphModel`` with the reference's consuming FIFO (scripts/rt_simplified.py:46-97) resident on the
+    device: ``push`` is ``RingBuffer.write`` for every stream, ``tick`` is ``RingBuffer.read(audio_length)`` + ``model(audio)``
+    (:378-399) for every stream that holds a whole window.  No EMA and no emotion input: the model has neither.  The weights are
+    those the model held when the engine was created."""
+
+    def __init__(self, model, n_streams: int, buffer_duration: float = 2.0, audio_length: int = 16000):
+        lib, h, dev = model._handle()
+        self.model, self.n_streams, self.audio_length = model, n_streams, audio_length
+        self._lib, self._h, self.device = lib, h, dev
+        self.shape = legacy_stream_shape(buffer_duration, audio_length, model.hop_length, model.sample_rate)
+        self.buffer_samples = self.shape["buffer_samples"]
+        with torch.cuda.device(dev):
+            torch.cuda.synchronize(dev)
+            check(lib.km_legacy_stream_create(h, n_streams, self.buffer_samples, audio_length))
+        # km_legacy_stream_create reserved the workspace for (n_streams, audio_length): the model's own forward must not shrink it
+        model._reserved = (max(model._reserved[0], n_streams), max(model._reserved[1], audio_length))
+        self.out = torch.zeros(n_streams, model.num_blendshapes, device=dev)
+        self.ready = torch.zeros(n_streams, dtype=torch.uint8, device=dev)
+        self._graph = None
+        self._g_samples = self._g_counts = self._g_host_out = None
+
+    def push(self, samples: torch.Tensor, counts: Optional[torch.Tensor] = None) -> None:
+        """samples (n_streams, n) fp32 on the device; counts (n_streams) int32 on the device: how many of the n samples each
+        stream brings (default: all).  What does not fit a stream's FIFO is dropped."""
+        if samples.dim() != 2 or samples.shape[0] != self.n_streams or samples.dtype != torch.float32:
+            raise ValueError(f"expected ({self.n_streams}, n) float32 samples, got {tuple(samples.shape)} {samples.dtype}")
+        if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (self.n_streams,)):
+            raise ValueError(f"expected ({self.n_streams},) int32 counts")
+        samples = samples.contiguous()
+        check(self._lib.km_legacy_stream_push(self._h, _ptr(samples), samples.shape[1],
+                                              _ptr(counts.contiguous()) if counts is not None else None, _stream_ptr(samples.device)))
+
+    def tick(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (out (n_streams, 52), ready (n_streams) uint8); rows of streams that are not ready keep what they held."""
+        check(self._lib.km_legacy_stream_tick(self._h, _ptr(self.out), _ptr(self.ready), _stream_ptr(self.device)))
+        return self.out, self.ready
+
+    def reset(self) -> None:
+        check(self._lib.km_legacy_stream_reset(self._h, _stream_ptr(self.device)))
+        self.out.zero_()
+        self.ready.zero_()
+
+    # ---- hipGraph replay ------------------------------------------------------------------------
+    def capture(self, n_per_stream: int, host_out: Optional[torch.Tensor] = None) -> None:
+        """Record push (with per-stream counts) + tick on static input buffers into a hipGraph: a linear chain of four kernels.
+        ``host_out``: a pinned (n_streams, 52) host tensor -- the result readback becomes the graph's last node."""
+        dev = self.device
+        if host_out is not None and (not host_out.is_pinned() or tuple(host_out.shape) != tuple(self.out.shape)):
+            raise ValueError("host_out must be a pinned host tensor of the shape of the result")
+        self._g_samples = torch.zeros(self.n_streams, n_per_stream, device=dev)
+        self._g_counts = torch.full((self.n_streams,), n_per_stream, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.push(self._g_samples, self._g_counts)
+            self.tick()
+            if host_out is not None:
+                host_out.copy_(self.out, non_blocking=True)
+        self._graph = g
+        self._g_host_out = host_out
+        self._g_counts_full = True
+
+    def replay(self, samples: torch.Tensor, counts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self._graph is None:
+            raise RuntimeError("capture() first")
+        self._g_samples.copy_(samples, non_blocking=True)
+        if counts is not None:
+            self._g_counts.copy_(counts, non_blocking=True)
+            self._g_counts_full = False
+        elif not self._g_counts_full:
+            self._g_counts.fill_(self._g_samples.shape[1])
+            self._g_counts_full = True
         self._graph.replay()
         return self.out, self.ready
