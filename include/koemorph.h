@@ -572,7 +572,11 @@ int km_stage_times(km_handle h, float* ms3);
  *   km_egemaps_workspace_floats         floats of caller-owned scratch km_egemaps_functionals needs for (B, L)
  *   km_egemaps_functionals              audio_dev (B, L) -> out_dev (B, 88); launches on `stream`, no allocation, no sync
  *   km_egemaps_records                  per-frame low-level descriptors of the last call on that workspace, (B, frames, 36)
- *                                       floats to the host (tests) */
+ *                                       floats to the host (tests)
+ *   km_egemaps_track_from_records       the pitch-track kernel alone on caller-written records rec_dev (B, nf, 36), in place:
+ *                                       reads voicing, RMS, candidate frequencies / strengths, writes the F0 column (tests)
+ *   km_egemaps_functionals_from_records the functionals kernel alone on caller-written records -> out_dev (B, 88) (tests)
+ *                                       both: 1 <= nf <= 2048, 1 <= B <= 65535, the kernels km_egemaps_functionals launches */
 int km_egemaps_plan_create(void** plan_out);
 int km_egemaps_plan_destroy(void* plan);
 int64_t km_egemaps_num_frames(int64_t L);
@@ -580,6 +584,8 @@ int64_t km_egemaps_workspace_floats(int64_t B, int64_t L);
 int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
                            int64_t work_floats, float* out_dev, void* stream);
 int km_egemaps_records(const float* work_dev, int64_t B, int64_t L, float* rec_host, void* stream);
+int km_egemaps_track_from_records(float* rec_dev, int64_t B, int64_t nf, void* stream);
+int km_egemaps_functionals_from_records(const float* rec_dev, int64_t B, int64_t nf, float* out_dev, void* stream);
 /* out (B, N) = x (B, K) w^T + b with w stored (N, K) like nn.Linear: the 264 -> 256 compression of the three concatenated
  * eGeMAPS windows (OpenSMILEeGeMAPSExtractor.get_concatenated_features, opensmile_extractor.py:575-590).  b may be NULL. */
 int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev, void* stream);

@@ -172,6 +172,8 @@ SIGNATURES = {
     "km_egemaps_workspace_floats": (_i64, [_i64, _i64]),
     "km_egemaps_functionals": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p, _p]),
     "km_egemaps_records": (C.c_int, [_p, _i64, _i64, _p, _p]),
+    "km_egemaps_track_from_records": (C.c_int, [_p, _i64, _i64, _p]),
+    "km_egemaps_functionals_from_records": (C.c_int, [_p, _i64, _i64, _p, _p]),
     "km_metrics_create": (C.c_int, [C.POINTER(_p)]),
     "km_metrics_destroy": (C.c_int, [_p]),
     "km_metrics_reset": (C.c_int, [_p, _p]),

@@ -506,7 +506,7 @@ __global__ __launch_bounds__(256, 6) void egm_frame_kernel(EgmArgs a) {
 }
 
 // pitch track over the candidates: states 0..2 = candidate, 3 = unvoiced.  One thread per window walks the frames; the
-// back pointers live in the record's Famp slots until egm_voiced_kernel overwrites them.
+// back pointers live in the bp LDS array (two bits per state), which the backtrack then overwrites with the chosen state.
 __global__ __launch_bounds__(256) void egm_viterbi_kernel(float* __restrict__ recs, int nf) {
     using namespace egm;
     // The recursion itself is sequential (thread 0), but its inputs are not: all threads first gather the seven numbers a
@@ -785,8 +785,10 @@ __global__ __launch_bounds__(256) void egm_functional_kernel(const float* __rest
             int n = 0;
             for (int t = 0; t < nf; ++t) { const bool vo = f0s[t] > 0.f; if (sel == 0 || (sel == 1) == vo) s[n++] = v[t]; }
             cnt_s[0] = n;
-            // slopes of the rising / falling parts (cut at local extrema)
-            float rs = 0.f, rq = 0.f, fs = 0.f, fq = 0.f; int rn = 0, fn = 0;
+            // slopes of the rising / falling parts (cut at local extrema).  Their spread is accumulated as a running mean and
+            // a running sum of squared deviations (Welford): E[x^2] - E[x]^2 in float32 leaves the rounding of x^2 behind, and
+            // its square root is 2e-4 of the slope where the true deviation is zero (a single part, equal parts)
+            float rs = 0.f, rm = 0.f, rq = 0.f, fs = 0.f, fm = 0.f, fq = 0.f; int rn = 0, fn = 0;
             if (n >= 2) {
                 int start = 0;
                 for (int t = 1; t < n; ++t) {
@@ -795,13 +797,14 @@ __global__ __launch_bounds__(256) void egm_functional_kernel(const float* __rest
                     if (turn || last) {
                         const float dv = s[t] - s[start];
                         const float sl = dv / ((t - start) * (float)HOP / SR);
-                        if (dv > 0.f) { rs += sl; rq += sl * sl; ++rn; } else if (dv < 0.f) { fs += sl; fq += sl * sl; ++fn; }
+                        if (dv > 0.f) { rs += sl; ++rn; const float d = sl - rm; rm += d / rn; rq += d * (sl - rm); }
+                        else if (dv < 0.f) { fs += sl; ++fn; const float d = sl - fm; fm += d / fn; fq += d * (sl - fm); }
                         start = t;
                     }
                 }
             }
-            res[0] = rn ? rs / rn : 0.f; res[1] = rn ? sqrtf(fmaxf(rq / rn - (rs / rn) * (rs / rn), 0.f)) : 0.f;
-            res[2] = fn ? fs / fn : 0.f; res[3] = fn ? sqrtf(fmaxf(fq / fn - (fs / fn) * (fs / fn), 0.f)) : 0.f;
+            res[0] = rn ? rs / rn : 0.f; res[1] = rn ? sqrtf(fmaxf(rq / rn, 0.f)) : 0.f;
+            res[2] = fn ? fs / fn : 0.f; res[3] = fn ? sqrtf(fmaxf(fq / fn, 0.f)) : 0.f;
         }
         __syncthreads();
         const int n = cnt_s[0];
@@ -946,6 +949,31 @@ int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_
     hipLaunchKernelGGL(egm_viterbi_kernel, dim3((unsigned)B), dim3(256), 0, st, rec, (int)nf);
     hipLaunchKernelGGL(egm_voiced_kernel, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
     hipLaunchKernelGGL(egm_functional_kernel, dim3((unsigned)B), dim3(256), 0, st, rec, (int)nf, out_dev);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+// The two kernels that are pure functions of the record array, on records the caller wrote (tests): the same kernels, the
+// same launch shape as in km_egemaps_functionals, no copy.
+static int check_records(const char* who, const void* rec, const void* out, int64_t B, int64_t nf) {
+    using namespace egm;
+    if (!rec || !out || B <= 0) return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
+    if (nf < 1) return fail(KM_ERR_INVALID_ARG, "%s: %lld frames per window, at least 1", who, (long long)nf);
+    if (nf > MAXF) return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (20.5 s)", who, (long long)nf, MAXF);
+    if (B > 65535) return fail(KM_ERR_UNSUPPORTED, "%s: at most 65535 windows per call", who);
+    return KM_OK;
+}
+
+int km_egemaps_track_from_records(float* rec_dev, int64_t B, int64_t nf, void* stream) {
+    if (const int rc = check_records("km_egemaps_track_from_records", rec_dev, rec_dev, B, nf)) return rc;
+    hipLaunchKernelGGL(egm_viterbi_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, rec_dev, (int)nf);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+int km_egemaps_functionals_from_records(const float* rec_dev, int64_t B, int64_t nf, float* out_dev, void* stream) {
+    if (const int rc = check_records("km_egemaps_functionals_from_records", rec_dev, out_dev, B, nf)) return rc;
+    hipLaunchKernelGGL(egm_functional_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, rec_dev, (int)nf, out_dev);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

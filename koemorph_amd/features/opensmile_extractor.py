@@ -151,6 +151,35 @@ class EGeMAPSEngine:
                                                self._torch.cuda.current_stream(self.device).cuda_stream))
         return rec
 
+    def _records_on_device(self, rec):
+        torch = self._torch
+        if isinstance(rec, np.ndarray):
+            rec = torch.from_numpy(np.ascontiguousarray(rec, np.float32))
+        rec = rec.to(self.device, torch.float32).contiguous()
+        if rec.dim() != 3 or rec.shape[2] != 36:
+            raise ValueError(f"Expected records (B, frames, 36), got {tuple(rec.shape)}")
+        return rec
+
+    def track_from_records(self, rec):
+        """records (B, frames, 36) -> a copy on the device whose F0 column the pitch-track kernel has rewritten (tests)."""
+        torch = self._torch
+        rec = self._records_on_device(rec).clone()
+        B, nf, _ = rec.shape
+        with torch.cuda.device(self.device):
+            check(self._lib.km_egemaps_track_from_records(rec.data_ptr(), B, nf, torch.cuda.current_stream(self.device).cuda_stream))
+        return rec
+
+    def functionals_from_records(self, rec):
+        """records (B, frames, 36) -> (B, 88): the functionals kernel alone (tests)."""
+        torch = self._torch
+        rec = self._records_on_device(rec)
+        B, nf, _ = rec.shape
+        out = torch.empty(B, EGEMAPS_DIM, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self._lib.km_egemaps_functionals_from_records(rec.data_ptr(), B, nf, out.data_ptr(),
+                                                                torch.cuda.current_stream(self.device).cuda_stream))
+        return out
+
 
 class OpenSMILEeGeMAPSExtractor:
     """eGeMAPS extractor with a sliding window (reference :157-665); the features come from the GPU."""

@@ -16,7 +16,7 @@ signals (a harmonic complex of known F0, a two-resonance vowel of known formants
 """
 from __future__ import annotations
 
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -237,6 +237,79 @@ def viterbi_f0(cf: np.ndarray, cs: np.ndarray, vo: np.ndarray, rms: np.ndarray) 
     return f0
 
 
+def _viterbi_costs(cf: np.ndarray, cs: np.ndarray, vo: np.ndarray, rms: np.ndarray):
+    """Local costs (nf, 4) (inf where a state does not exist), log2 candidate frequencies and the transition cost of
+    viterbi_f0, written once for viterbi_tables and path_cost.  Same weights, same expressions."""
+    w_local, w_vv, w_vuv, w_thr = 2.0, 10.0, 10.0 / 8.0, 4.0
+    cf = np.asarray(cf, np.float64); cs = np.asarray(cs, np.float64); vo = np.asarray(vo, np.float64); rms = np.asarray(rms, np.float64)
+    nf, S = len(vo), N_CAND + 1
+    voiced_ok = (vo >= VOICING_CUTOFF) & (rms >= RMS_FLOOR)
+    loc = np.full((nf, S), np.inf)
+    for c in range(N_CAND):
+        good = cf[:, c] > 0
+        loc[good, c] = w_local * (1.0 - cs[good, c]) + np.where(voiced_ok[good], 0.0, w_thr)
+    loc[:, N_CAND] = np.where(voiced_ok, w_thr, 0.0)
+    lf = np.where(cf > 0, np.log2(np.maximum(cf, 1e-9)), 0.0)
+
+    def trans(t: int, p: int, s: int) -> float:                   # from state p at frame t - 1 to state s at frame t
+        if s < N_CAND and p < N_CAND:
+            return w_vv * abs(lf[t, s] - lf[t - 1, p])
+        return 0.0 if (s == N_CAND and p == N_CAND) else w_vuv
+    return loc, trans
+
+
+def _forward(loc: np.ndarray, trans) -> np.ndarray:
+    """alpha[t, s]: cheapest path from frame 0 that is in state s at frame t, local cost of t included; accumulated in the
+    order of viterbi_f0 ((previous + transition) + local), so that along its path the two agree to the bit."""
+    nf, S = loc.shape
+    alpha = np.full((nf, S), np.inf)
+    alpha[0] = loc[0]
+    for t in range(1, nf):
+        for s in range(S):
+            if not np.isfinite(loc[t, s]):
+                continue
+            best = np.inf
+            for p in range(S):
+                if np.isfinite(alpha[t - 1, p]):
+                    best = min(best, alpha[t - 1, p] + trans(t, p, s))
+            alpha[t, s] = best + loc[t, s]
+    return alpha
+
+
+def viterbi_tables(cf: np.ndarray, cs: np.ndarray, vo: np.ndarray, rms: np.ndarray) -> Tuple[float, np.ndarray]:
+    """The optimal total cost C* of viterbi_f0's dynamic programme and, per frame and state, the cost alpha + beta of the
+    cheapest track THROUGH that state (nf, 4; inf where the state does not exist): a forward and a backward pass of the same
+    recursion.  min over s of alpha + beta is C* at every frame (up to float64 rounding: the two passes add the same terms
+    in different order); the second smallest entry minus C* says how decidable the frame's state is."""
+    loc, trans = _viterbi_costs(cf, cs, vo, rms)
+    nf, S = loc.shape
+    alpha = _forward(loc, trans)
+    beta = np.full((nf, S), np.inf)                               # cheapest continuation after frame t from state s, loc[t, s] excluded
+    beta[nf - 1] = np.where(np.isfinite(loc[nf - 1]), 0.0, np.inf)
+    for t in range(nf - 2, -1, -1):
+        for s in range(S):
+            if not np.isfinite(loc[t, s]):
+                continue
+            best = np.inf
+            for n in range(S):
+                if np.isfinite(beta[t + 1, n]):
+                    best = min(best, trans(t + 1, s, n) + loc[t + 1, n] + beta[t + 1, n])
+            beta[t, s] = best
+    return float(alpha[-1].min()), alpha + beta
+
+
+def path_cost(cf: np.ndarray, cs: np.ndarray, vo: np.ndarray, rms: np.ndarray, f0_track: np.ndarray) -> float:
+    """float64 cost of a GIVEN track under viterbi_f0's weights.  A frame's state is the candidate whose frequency equals
+    the track value (0: unvoiced); where two candidates of a frame share that frequency the cheaper one is taken (the
+    recursion runs over the allowed states).  inf if a track value is none of its frame's candidates."""
+    loc, trans = _viterbi_costs(cf, cs, vo, rms)
+    cf = np.asarray(cf, np.float64); f0_track = np.asarray(f0_track, np.float64)
+    allowed = np.zeros(loc.shape, bool)
+    allowed[:, N_CAND] = f0_track == 0
+    allowed[:, :N_CAND] = (cf == f0_track[:, None]) & (cf > 0) & (f0_track != 0)[:, None]
+    return float(_forward(np.where(allowed, loc, np.inf), trans)[-1].min())
+
+
 def lpc_formants(M20: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """Formant frequencies and bandwidths (NF, 3) in Hz: order-11 LPC of the spectrum below 5.5 kHz (the spectrum is cut there
     and treated as that of a signal sampled at 11 kHz, which is what resampling in the spectral domain does), autocorrelation
@@ -370,9 +443,8 @@ def mean_std_norm(v: np.ndarray) -> Tuple[float, float]:
     return m, (0.0 if m == 0 else s / abs(m))
 
 
-def slopes(v: np.ndarray) -> Tuple[float, float, float, float]:
-    """Mean / standard deviation of the slopes (per second) of the rising and of the falling parts of a contour: the contour is
-    cut at its local extrema, a part's slope is its height over its duration."""
+def part_slopes(v: np.ndarray) -> Tuple[List[float], List[float]]:
+    """Slopes (per second) of the rising and of the falling parts of a contour cut at its local extrema."""
     n = len(v)
     rise, fall = [], []
     if n >= 2:
@@ -387,6 +459,13 @@ def slopes(v: np.ndarray) -> Tuple[float, float, float, float]:
                 elif dv < 0:
                     fall.append(dv / ((t - start) * HOP / SR))
                 start = t
+    return rise, fall
+
+
+def slopes(v: np.ndarray) -> Tuple[float, float, float, float]:
+    """Mean / standard deviation of the slopes (per second) of the rising and of the falling parts of a contour: the contour is
+    cut at its local extrema, a part's slope is its height over its duration."""
+    rise, fall = part_slopes(v)
     ms = lambda a: (0.0, 0.0) if len(a) == 0 else (float(np.mean(a)), float(np.std(a)))
     return (*ms(rise), *ms(fall))
 
@@ -429,32 +508,45 @@ def llds(x: np.ndarray) -> Dict[str, np.ndarray]:
 
 def functionals(x: np.ndarray) -> np.ndarray:
     """The 88 eGeMAPSv02 functionals of one audio window (FEATURE_NAMES order)."""
-    d = llds(x)
+    return functionals_from_llds(llds(x))
+
+
+def functionals_from_llds(d: Dict[str, np.ndarray], dtype=np.float32, contours: Optional[Dict[int, np.ndarray]] = None) -> np.ndarray:
+    """The 88 functionals from the per-frame descriptors of llds() (or of records written by hand): smoothing, frame
+    selection and statistics, nothing that looks at audio.  `dtype`: functionals() rounds to float32, the stage tests ask for
+    float64.  `contours`, if given, receives the smoothed contour over the selected frames behind every statistic, keyed by
+    the index of its first output (the ten functionals of a contour, or its mean / stddevNorm pair, or its mean) -- the
+    tests take their error scales from these; nothing is computed differently."""
     nf = len(d["f0"])
     out: List[float] = []
     if nf == 0:
-        return np.zeros(88, np.float32)
+        return np.zeros(88, dtype)
+
+    def keep(v):
+        if contours is not None:
+            contours[len(out)] = np.array(v, np.float64)
+        return v
     f0 = sma3(d["f0"], True)
     voiced = f0 > 0
     semitone = np.where(voiced, 12.0 * np.log2(np.maximum(f0, 1e-9) / 27.5), 0.0)
-    out += ten_functionals(semitone[voiced])
+    out += ten_functionals(keep(semitone[voiced]))
     loud = sma3(d["loudness"], False)
-    out += ten_functionals(loud)
+    out += ten_functionals(keep(loud))
     flux = sma3(d["spectralFlux"], False)
-    out += list(mean_std_norm(flux))
+    out += list(mean_std_norm(keep(flux)))
     mf = np.stack([sma3(d["mfcc"][:, i], False) for i in range(4)], axis=1)
     for i in range(4):
-        out += list(mean_std_norm(mf[:, i]))
+        out += list(mean_std_norm(keep(mf[:, i])))
     nzs = [d["jitterLocal"], d["shimmerLocaldB"], d["HNRdBACF"], d["H1-H2"], d["H1-A3"]]
     for i in range(3):
         nzs += [d["F"][:, i], d["BW"][:, i], d["Famp"][:, i]]
     for v in nzs:                                                   # voiced frames only
-        out += list(mean_std_norm(sma3(np.where(voiced, v, 0.0), True)[voiced]))
+        out += list(mean_std_norm(keep(sma3(np.where(voiced, v, 0.0), True)[voiced])))
     spec = [sma3(d[k], False) for k in ("alphaRatio", "hammarbergIndex", "slope0-500", "slope500-1500")] + [flux]
     for v in spec + [mf[:, i] for i in range(4)]:
-        out += list(mean_std_norm(v[voiced]))
+        out += list(mean_std_norm(keep(v[voiced])))
     for v in spec:
-        out.append(float(v[~voiced].mean()) if (~voiced).any() else 0.0)
+        out.append(float(keep(v[~voiced]).mean()) if (~voiced).any() else 0.0)
     dur = nf * HOP / SR
     peaks = int(((loud[1:-1] > loud[:-2]) & (loud[1:-1] >= loud[2:])).sum()) if nf > 2 else 0
     vs, us = segments(voiced), segments(~voiced)
@@ -466,7 +558,7 @@ def functionals(x: np.ndarray) -> np.ndarray:
     out.append(float(us.std() * HOP / SR) if len(us) else 0.0)
     out.append(float(10.0 * np.log10(max((d["rms"] ** 2).mean(), 1e-12))))
     assert len(out) == 88
-    return np.asarray(out, np.float32)
+    return np.asarray(out, dtype)
 
 
 def normalise(audio: np.ndarray) -> np.ndarray:
