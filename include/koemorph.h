@@ -522,6 +522,47 @@ int km_stream_push(km_handle h, const float* samples_dev, int64_t n_per_stream, 
 int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* ready_dev, void* stream);
 int km_stream_reset(km_handle h, void* stream);
 
+/* ---- streams out of phase: a chunk FIFO per stream in front of its ring ----------------------------------------
+ * Dual-stream handles with streams (km_stream_create) only; legacy and KoeMorphModel handles are refused as km_stream_* refuses
+ * them.  Replaces, for all streams at once, the production model's real-time loop of scripts/rt.py: chunks of any size are
+ * written into a consuming RingBuffer (:48-99) that drops what does not fit, one read(frame_samples) per inference step feeds
+ * process_audio_frame_realtime (:343-372, src/model/simplified_dual_stream_model.py:452-507), and reset_realtime_state() is per
+ * speaker.  km_stream_push / km_stream_tick keep serving streams that move in lockstep, unchanged.
+ *   km_stream_fifo_create    call after km_stream_create: one FIFO of fifo_samples floats per stream (RingBuffer(int(
+ *                            buffer_duration * sr)), 32000 by default) with its write_ptr, read_ptr and available (:51-56);
+ *                            frame_samples is int(sr / target_fps) (533 at 30 fps, 266 at 60 fps).  Allocates: call it once,
+ *                            outside any graph capture.  KM_ERR_INVALID_ARG without streams, for non-positive sizes, for
+ *                            frame_samples not within +/-1 of the ring hop ("Frame size mismatch", mel_sliding_window.py:80-82)
+ *                            and for fifo_samples < frame_samples (no read could ever succeed).  km_stream_create called again
+ *                            frees the FIFOs together with the rings.
+ *   km_stream_feed           RingBuffer.write (:58-79) for every stream: samples_dev (n_streams, n_per_stream); counts_dev
+ *                            (n_streams) int32 or NULL = n_per_stream for all.  Stream s appends min(clamp(counts[s], 0,
+ *                            n_per_stream), fifo_samples - available[s]) samples and drops the rest (:61-64).  May be called
+ *                            several times between steps.
+ *   km_stream_step           for every stream: read(frame_samples) (:81-99) -- a stream holding fewer samples does nothing on
+ *                            this step; a stream that popped runs MelAudioBuffer.add_audio_frame on the frame (padded /
+ *                            truncated to the ring hop, mel_sliding_window.py:84-91; is_full by :112); fired[s] = popped[s] &&
+ *                            is_full[s], and only fired streams go through the emotion stream, the front end and the core with
+ *                            the per-stream EMA.  A stream that did not fire -- a full ring that received no audio included --
+ *                            keeps its out_dev row, EMA state, ring and started flag exactly as they were.  fired_dev (u8, may be
+ *                            NULL); ready_dev (u8, may be NULL) mirrors is_full as km_stream_tick does; backlog_dev (int32, may
+ *                            be NULL) = available[s] / frame_samples after the pop: while it is positive another step without a
+ *                            feed drains the next whole frame.  The wall-clock gate of mel_sliding_window.py:267-269 is treated
+ *                            as km_stream_tick treats it: steps are one audio hop apart.  Shapes as km_stream_tick, same
+ *                            KM_ERR_UNSUPPORTED message.
+ *   km_stream_reset_streams  for the streams with mask_dev[s] != 0 (u8): FIFO pointers (if FIFOs exist), ring write pointer and
+ *                            frame count, is_full, started and the EMA state are cleared (MelSlidingWindowExtractor.reset
+ *                            :373-383 + reset_temporal_state, simplified_dual_stream_model.py:417-419): the stream then behaves
+ *                            as a freshly created one; every other stream is untouched.  Also works without FIFOs, with the
+ *                            lockstep push / tick.  km_stream_reset keeps its meaning and empties the FIFOs too.
+ * feed, step and reset_streams never allocate, synchronise or read anything back; feed + step capture into a hipGraph as one
+ * linear chain. */
+int km_stream_fifo_create(km_handle h, int64_t fifo_samples, int64_t frame_samples);
+int km_stream_feed(km_handle h, const float* samples_dev, int64_t n_per_stream, const int32_t* counts_dev, void* stream);
+int km_stream_step(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* fired_dev, uint8_t* ready_dev, int32_t* backlog_dev,
+                   void* stream);
+int km_stream_reset_streams(km_handle h, const uint8_t* mask_dev, void* stream);
+
 /* ---- streaming the legacy SimplifiedKoeMorphModel: consuming FIFOs resident on the device ---------------------
  * Legacy handles (km_legacy_create, after km_finalize) only; the km_stream_* family above keeps refusing them and this one
  * refuses dual-stream and KoeMorphModel handles.  Replaces, for all streams at once, the real-time loop of

@@ -161,6 +161,10 @@ SIGNATURES = {
     "km_stream_push": (C.c_int, [_h, _p, _i64, _p]),
     "km_stream_tick": (C.c_int, [_h, _p, _p, _p, _p]),
     "km_stream_reset": (C.c_int, [_h, _p]),
+    "km_stream_fifo_create": (C.c_int, [_h, _i64, _i64]),
+    "km_stream_feed": (C.c_int, [_h, _p, _i64, _p, _p]),
+    "km_stream_step": (C.c_int, [_h, _p, _p, _p, _p, _p, _p]),
+    "km_stream_reset_streams": (C.c_int, [_h, _p, _p]),
     "km_legacy_stream_create": (C.c_int, [_h, _i64, _i64, _i64]),
     "km_legacy_stream_push": (C.c_int, [_h, _p, _i64, _p, _p]),
     "km_legacy_stream_tick": (C.c_int, [_h, _p, _p, _p]),

@@ -896,11 +896,12 @@ int km_forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const 
 }
 
 static int free_streams(Context* c) {
-    void* ptrs[] = {c->ring, c->ring_wptr, c->ring_frames, c->ring_ready, c->ring_started, c->ring_state};
+    void* ptrs[] = {c->ring, c->ring_wptr, c->ring_frames, c->ring_ready, c->ring_started, c->ring_state, c->sfifo, c->sfifo_state, c->ring_fire};
     for (void* p : ptrs)
         if (p) HIP_TRY(hipFree(p));
     c->ring = nullptr; c->ring_wptr = nullptr; c->ring_frames = nullptr; c->ring_ready = nullptr;
     c->ring_started = nullptr; c->ring_state = nullptr; c->n_streams = 0;
+    c->sfifo = nullptr; c->sfifo_state = nullptr; c->ring_fire = nullptr; c->sfifo_len = 0; c->sfifo_frame = 0;
     return KM_OK;
 }
 
@@ -915,6 +916,10 @@ int km_stream_reset(km_handle h, void* stream) {
     HIP_TRY(hipMemsetAsync(c->ring_ready, 0, (size_t)c->n_streams, st));
     HIP_TRY(hipMemsetAsync(c->ring_started, 0, (size_t)c->n_streams, st));
     HIP_TRY(hipMemsetAsync(c->ring_state, 0, (size_t)c->n_streams * c->NB * sizeof(float), st));
+    if (c->sfifo_len > 0) {     // empty FIFOs: their samples are not read below `available` (stream_reset_masked_kernel)
+        HIP_TRY(hipMemsetAsync(c->sfifo_state, 0, 3 * (size_t)c->n_streams * sizeof(int), st));
+        HIP_TRY(hipMemsetAsync(c->ring_fire, 0, (size_t)c->n_streams, st));
+    }
     return KM_OK;
 }
 
@@ -982,6 +987,98 @@ int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_
     if (ready_dev)
         HIP_TRY(hipMemcpyAsync(ready_dev, c->ring_ready, (size_t)S, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return KM_OK;
+}
+
+// ---- streams out of phase: a chunk FIFO per stream in front of its ring (kernels: km_legacy_stream.hip) ----
+static int need_stream_fifos(Context* c, const char* who) {
+    if (int rc = need_dual(c)) return rc;
+    if (c->n_streams <= 0) return fail(KM_ERR_INVALID_ARG, "%s: no streams (km_stream_create first)", who);
+    if (c->sfifo_len <= 0) return fail(KM_ERR_INVALID_ARG, "%s: no FIFOs (km_stream_fifo_create first)", who);
+    return KM_OK;
+}
+
+// the launches of a step behind the pop: what km_stream_tick launches, gated on the step's fire flags instead of is_full
+static int stream_step_launches(Context* c, const float* emotion_dev, float* out_dev, void* stream) {
+    const int64_t S = c->n_streams, n_frames = 1 + c->ring_len / c->stream_plan->cfg.hop_length;
+    const bool fuse_emo = mel_fuses_emotion(c, c->stream_plan);
+    if (!fuse_emo)
+        if (int rc = launch_emotion(c, emotion_dev, S, c->ws_zemo, stream)) return rc;
+    if (int rc = launch_mel_power(c, c->stream_plan, mel_rings(c, c->ring_fire), stream,
+                                  fuse_emo ? mel_emotion(emotion_dev, c->ws_zemo) : MelCarry{})) return rc;
+    if (c->fused_ok) return launch_core_fused_db(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream, core_stream(c, c->ring_fire));
+    return launch_core512_stream(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream, c->ring_fire);
+}
+
+int km_stream_fifo_create(km_handle h, int64_t fifo_samples, int64_t frame_samples) {
+    if (int rc = need_dual(h)) return rc;
+    Context* c = h;
+    if (c->n_streams <= 0) return fail(KM_ERR_INVALID_ARG, "km_stream_fifo_create: no streams (km_stream_create first)");
+    if (fifo_samples <= 0 || frame_samples <= 0 || fifo_samples >= (1ll << 30))
+        return fail(KM_ERR_INVALID_ARG, "km_stream_fifo_create: bad argument (FIFOs of %lld samples, frames of %lld)", (long long)fifo_samples,
+                    (long long)frame_samples);
+    const int64_t diff = frame_samples - c->ring_hop;
+    if (diff > 1 || diff < -1)                                                      // mel_sliding_window.py:80-82
+        return fail(KM_ERR_INVALID_ARG, "Frame size mismatch: expected ~%d, got %lld", c->ring_hop, (long long)frame_samples);
+    if (fifo_samples < frame_samples)
+        return fail(KM_ERR_INVALID_ARG, "km_stream_fifo_create: frames of %lld samples exceed the FIFO of %lld: no read could ever succeed",
+                    (long long)frame_samples, (long long)fifo_samples);
+    if (c->ring_hop > c->ring_len) return fail(KM_ERR_INVALID_ARG, "km_stream_fifo_create: the ring hop exceeds the ring");
+    HIP_TRY(hipDeviceSynchronize());
+    void* old[] = {c->sfifo, c->sfifo_state, c->ring_fire};
+    for (void* p : old)
+        if (p) HIP_TRY(hipFree(p));
+    c->sfifo = nullptr; c->sfifo_state = nullptr; c->ring_fire = nullptr; c->sfifo_len = 0; c->sfifo_frame = 0;
+    const size_t S = (size_t)c->n_streams;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->sfifo), S * fifo_samples * sizeof(float)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->sfifo_state), 3 * S * sizeof(int)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ring_fire), S));
+    HIP_TRY(hipMemset(c->sfifo, 0, S * fifo_samples * sizeof(float)));
+    HIP_TRY(hipMemset(c->sfifo_state, 0, 3 * S * sizeof(int)));
+    HIP_TRY(hipMemset(c->ring_fire, 0, S));
+    c->sfifo_len = fifo_samples; c->sfifo_frame = (int)frame_samples;
+    // the launches of one step over a gate of zeros: no workgroup passes it, so nothing is read or written (the emotion rows and
+    // the result pointer are dummies), but every kernel of a step has had its attributes set before a capture sees its first launch
+    if (c->fused_ok || core512_stream_ok(c)) {
+        float* emo = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&emo), S * c->ED * sizeof(float)));
+        HIP_TRY(hipMemset(emo, 0, S * c->ED * sizeof(float)));
+        int rc = launch_sfifo_pop_ring(c, nullptr, nullptr, nullptr, nullptr);
+        if (!rc) rc = stream_step_launches(c, emo, c->ring_state, nullptr);
+        const hipError_t e = hipDeviceSynchronize();
+        (void)hipFree(emo);
+        if (rc) return rc;
+        HIP_TRY(e);
+    }
+    return KM_OK;
+}
+
+int km_stream_feed(km_handle h, const float* samples_dev, int64_t n_per_stream, const int32_t* counts_dev, void* stream) {
+    if (int rc = need_stream_fifos(h, "km_stream_feed")) return rc;
+    if (!samples_dev || n_per_stream <= 0 || n_per_stream >= (1ll << 30)) return fail(KM_ERR_INVALID_ARG, "km_stream_feed: bad argument");
+    return launch_sfifo_push(h, samples_dev, n_per_stream, counts_dev, stream);
+}
+
+int km_stream_step(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* fired_dev, uint8_t* ready_dev, int32_t* backlog_dev,
+                   void* stream) {
+    if (int rc = need_stream_fifos(h, "km_stream_step")) return rc;
+    Context* c = h;
+    if (!emotion_dev || !out_dev) return fail(KM_ERR_INVALID_ARG, "km_stream_step: NULL argument");
+    if (!c->fused_ok && !core512_stream_ok(c))                                      // as km_stream_tick, before anything is popped
+        return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
+    const int64_t S = c->n_streams;
+    if (S > c->ws_windows || 1 + c->ring_len / c->stream_plan->cfg.hop_length > c->ws_frames)
+        return fail(KM_ERR_WORKSPACE, "stream workspace too small");
+    // pop + ring advance (fire, ready, backlog), then the launches of a tick gated on fire: one linear chain
+    if (int rc = launch_sfifo_pop_ring(c, fired_dev, ready_dev, backlog_dev, stream)) return rc;
+    return stream_step_launches(c, emotion_dev, out_dev, stream);
+}
+
+int km_stream_reset_streams(km_handle h, const uint8_t* mask_dev, void* stream) {
+    if (int rc = need_dual(h)) return rc;
+    Context* c = h;
+    if (c->n_streams <= 0) return fail(KM_ERR_INVALID_ARG, "km_stream_reset_streams: no streams (km_stream_create first)");
+    if (!mask_dev) return fail(KM_ERR_INVALID_ARG, "km_stream_reset_streams: NULL mask");
+    return launch_stream_reset_masked(c, mask_dev, stream);
 }
 
 // ---- streams of the legacy model: device-resident consuming FIFOs + the one-launch model (kernels: km_legacy_stream.hip,

@@ -151,6 +151,12 @@ struct Context {
     float* ring_state = nullptr;        // (n_streams, 52) EMA state
     MelPlan* stream_plan = nullptr;
     int64_t stream_out_frames = 0;
+    // chunk FIFOs in front of the rings (km_stream_fifo_create / _feed / _step): one consuming FIFO per stream (RingBuffer
+    // semantics, scripts/rt.py:48-99), popped one frame per step straight into the stream's ring; sfifo_len == 0 until created
+    int64_t sfifo_len = 0; int sfifo_frame = 0;
+    float* sfifo = nullptr;             // (n_streams, sfifo_len) samples
+    int* sfifo_state = nullptr;         // (3, n_streams): write_ptr | read_ptr | available
+    unsigned char* ring_fire = nullptr; // (n_streams) this step popped a frame AND the ring is full: the gate of km_stream_step
     // streaming state of the legacy model (km_legacy_stream_*): device-resident consuming FIFOs (RingBuffer semantics,
     // scripts/rt_simplified.py:46-97); grow-only buffers, n_streams == 0 until km_legacy_stream_create
     int64_t lfifo_streams = 0, lfifo_len = 0, lfifo_window = 0;
@@ -250,7 +256,10 @@ inline CoreSrc core_workspace_seq(int64_t win0, int n_per_clip) { return {nullpt
 inline CoreSrc core_strided(const SeqCore* s, int64_t win0) { return {nullptr, 1, win0, s->n_per_clip, 0, nullptr, nullptr, s, nullptr}; }
 inline CoreSrc core_table(const ClipTable* t, float* state, int first) { return {state, first, 0, 1, 0, nullptr, nullptr, nullptr, t}; }
 // the handle's streams: rows of the workspace, EMA state and flags of the rings
-inline CoreSrc core_stream(Context* c) { return {c->ring_state, 0, 0, 1, c->stream_out_frames, c->ring_ready, c->ring_started, nullptr, nullptr}; }
+// (gate: the per-stream flags the kernel skips on -- is_full for km_stream_tick, this step's fire flags for km_stream_step)
+inline CoreSrc core_stream(Context* c, const unsigned char* gate = nullptr) {
+    return {c->ring_state, 0, 0, 1, c->stream_out_frames, gate ? gate : c->ring_ready, c->ring_started, nullptr, nullptr};
+}
 int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, const float* zemo, float* out, void* stream,
                          const CoreSrc& src);
 int launch_seq_window_max(Context* c, const unsigned* fmax, const unsigned* emax, int64_t nw, int64_t win0, int nfc, int stride,
@@ -315,7 +324,8 @@ int launch_core_generic(Context* c, const float* mel, int64_t B, int64_t T_in, c
                         float* out, float* raw, float* attn, void* stream);
 // km_stream_tick on the d_model 512 shapes (8 or 16 heads, window 512): core512's streaming kernel over the rings' power-mel
 bool core512_stream_ok(Context* c);
-int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream);
+int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
+                          const unsigned char* gate = nullptr);
 
 // km_mel.hip
 // Shared-frame sequence mode: the front end writes n_rows rows per window (row r = STFT frame r * frame_mul) into
@@ -339,7 +349,9 @@ inline MelSrc mel_windows(const float* audio, int64_t B, int64_t L) { return {au
 inline MelSrc mel_clip_windows(const float* clips, int64_t clip_len, int64_t B, int64_t L, int64_t win_step, int64_t win0, int wins_per_clip) {
     return {clips, B, L, clip_len, win_step, win0, wins_per_clip, nullptr, nullptr};
 }
-inline MelSrc mel_rings(Context* c) { return {c->ring, c->n_streams, c->ring_len, c->ring_len, 0, 0, 1, c->ring_wptr, c->ring_ready}; }
+inline MelSrc mel_rings(Context* c, const unsigned char* gate = nullptr) {
+    return {c->ring, c->n_streams, c->ring_len, c->ring_len, 0, 0, 1, c->ring_wptr, gate ? gate : c->ring_ready};
+}
 // What a launch may carry, at most one of: the emotion rider (the windows' logits from the same kernel: mel_fuses_emotion, one window
 // per clip), rows into a SeqFrames image instead of the workspace (mel_rp_ok, no rings), the packed training input (mel_packs, a plain batch)
 struct MelCarry { const float* emotion = nullptr; float* zemo = nullptr; const SeqFrames* seq = nullptr; const MelPack* pack = nullptr; };
@@ -372,6 +384,10 @@ int launch_ring_push(Context* c, const float* samples, int64_t n_per_stream, voi
 // km_legacy_stream.hip: the FIFOs of km_legacy_stream_* (Context::lfifo_*)
 int launch_lfifo_push(Context* c, const float* samples, int64_t n_per_stream, const int* counts, void* stream);
 int launch_lfifo_pop(Context* c, unsigned char* ready_out, void* stream);
+// ... and the chunk FIFOs of km_stream_* (Context::sfifo_*): write, pop one frame into the ring, reset the masked streams
+int launch_sfifo_push(Context* c, const float* samples, int64_t n_per_stream, const int* counts, void* stream);
+int launch_sfifo_pop_ring(Context* c, unsigned char* fire_out, unsigned char* ready_out, int* backlog_out, void* stream);
+int launch_stream_reset_masked(Context* c, const unsigned char* mask, void* stream);
 // km_kmmf.hip: SimplifiedKoeMorphModel behind the front end for every stream with ready[s] != 0, windows of Tm <= 32 frames
 int launch_legacy_stream_model(Context* c, const float* melpow, unsigned* melmax, const unsigned char* ready, int64_t S, int Tm,
                                const LogParams& lp, float* O, float* out, void* stream);

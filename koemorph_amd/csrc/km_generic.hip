@@ -682,7 +682,8 @@ int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_fr
 // km_stream_tick on the d_model 512 shapes: the front end has written the power-mel of every ready stream's ring
 bool core512_stream_ok(Context* c) { return core512_merge_ok(c, nullptr) && generic_core_takes_power(c); }
 
-int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream) {
+int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
+                          const unsigned char* gate) {
     if (!core512_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
     if (!c->ws_generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
     const int d = c->d, H = c->H, NKk = c->NK, KP = (c->KT + 15) / 16 * 16;
@@ -691,7 +692,7 @@ int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames
     const EncSrc src{c->ws_melpow, c->ws_melmax, (int)n_frames, c->T, plan_log_params(plan)};
     Core512StreamArgs sa{{nullptr, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), Sc, H * 28,
                           dv(c, "wv_bg"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, nullptr},
-                         {(int)(c->stream_out_frames > 0 ? c->stream_out_frames : n_frames), c->ring_ready, c->ring_started,
+                         {(int)(c->stream_out_frames > 0 ? c->stream_out_frames : n_frames), gate ? gate : c->ring_ready, c->ring_started,
                           c->ring_state, c->alpha}};
     static PerDeviceOnce once;
     if (once.first(c->device)) {

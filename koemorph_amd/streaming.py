@@ -11,6 +11,11 @@ floats) followed by ``tick`` (emotion kernel, sliding-window front end over ever
 per-stream EMA).  Neither allocates nor synchronises, so ``capture()`` records one tick into a hipGraph and
 ``replay()`` re-launches it with a single API call per 33 ms frame.
 
+``ChunkedStreamEngine`` serves streams that are out of phase: chunks of any size are fed into a consuming FIFO per stream
+(the reference's ``RingBuffer``, scripts/rt.py:48-99), a step pops one frame from every stream that holds one and computes only
+the streams that popped onto a full ring, and ``reset_streams`` hands one slot to the next speaker (km_stream_fifo_create / _feed /
+_step / _reset_streams).
+
 ``LegacyStreamEngine`` is the counterpart for ``SimplifiedKoeMorphModel``: the reference's consuming FIFO
 (scripts/rt_simplified.py:46-97) per stream instead of a sliding ring, no EMA, no emotion input (km_legacy_stream_*).
 """
@@ -104,6 +109,115 @@ class StreamEngine:
         self._g_emotion.copy_(emotion, non_blocking=True)
         self._graph.replay()
         return self.out, self.ready
+
+
+def chunked_stream_shape(context_window: float = 8.5, update_interval: float = 0.0333, buffer_duration: float = 2.0,
+                         frame_samples: Optional[int] = None, sample_rate: int = 16000) -> dict:
+    """The arithmetic of the reference's real-time loop around the production model, which km_stream_fifo_create follows: the FIFO's
+    size ``int(buffer_duration * sample_rate)`` (scripts/rt.py:259) and the frame one step reads, ``int(sample_rate / target_fps)``
+    (:255) with target_fps the stream's nominal rate round(1 / update_interval): 533 at 30 fps, 266 at 60 fps.  ValueError where
+    km_stream_fifo_create refuses: a non-positive size, a frame not within +/-1 of the ring hop (mel_sliding_window.py:80-82) or
+    longer than the FIFO."""
+    ring_hop = int(sample_rate / (1.0 / update_interval))
+    fifo_samples = int(buffer_duration * sample_rate)
+    if frame_samples is None:
+        frame_samples = int(sample_rate / round(1.0 / update_interval))
+    if fifo_samples <= 0 or frame_samples <= 0:
+        raise ValueError("buffer_duration and frame_samples must be positive")
+    if abs(frame_samples - ring_hop) > 1:
+        raise ValueError(f"Frame size mismatch: expected ~{ring_hop}, got {frame_samples}")
+    if fifo_samples < frame_samples:
+        raise ValueError(f"frames of {frame_samples} samples exceed the FIFO of {fifo_samples}: no read could ever succeed")
+    return dict(fifo_samples=fifo_samples, frame_samples=frame_samples, ring_hop=ring_hop)
+
+
+class ChunkedStreamEngine(StreamEngine):
+    """Streams that are out of phase.  ``feed`` is ``RingBuffer.write`` for every stream (what does not fit is dropped), ``step`` is
+    ``read(frame_samples)`` + ``process_audio_frame_realtime`` for every stream that holds a frame: the frame advances the stream's
+    ring, and a stream whose ring is full after it *fires* -- only fired streams are computed, every other stream keeps its row of
+    ``out``, its ring and its EMA state.  ``backlog`` says how many whole frames each FIFO still holds: step again without a feed
+    to drain them.  ``push`` / ``tick`` of the base class stay available and keep gating on a full ring alone."""
+
+    def __init__(self, engine: Engine, n_streams: int, context_window: float = 8.5, update_interval: float = 0.0333,
+                 mel: Optional[MelConfig] = None, buffer_duration: float = 2.0, frame_samples: Optional[int] = None):
+        sr = (mel or engine.mel).sample_rate
+        self.chunk = chunked_stream_shape(context_window, update_interval, buffer_duration, frame_samples, sr)
+        super().__init__(engine, n_streams, context_window, update_interval, mel)
+        self.fifo_samples, self.frame_samples = self.chunk["fifo_samples"], self.chunk["frame_samples"]
+        with torch.cuda.device(engine.device):
+            check(self._lib.km_stream_fifo_create(engine._h, self.fifo_samples, self.frame_samples))
+        self.fired = torch.zeros(n_streams, dtype=torch.uint8, device=engine.device)
+        self.backlog = torch.zeros(n_streams, dtype=torch.int32, device=engine.device)
+        self._g_counts = None
+
+    def feed(self, samples: torch.Tensor, counts: Optional[torch.Tensor] = None) -> None:
+        """samples (n_streams, n) fp32 on the device; counts (n_streams) int32 on the device: how many of the n samples each
+        stream brings (default: all)."""
+        if samples.dim() != 2 or samples.shape[0] != self.n_streams or samples.dtype != torch.float32:
+            raise ValueError(f"expected ({self.n_streams}, n) float32 samples, got {tuple(samples.shape)} {samples.dtype}")
+        if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (self.n_streams,)):
+            raise ValueError(f"expected ({self.n_streams},) int32 counts")
+        samples = samples.contiguous()
+        check(self._lib.km_stream_feed(self.engine._h, _ptr(samples), samples.shape[1],
+                                       _ptr(counts.contiguous()) if counts is not None else None, _stream_ptr(samples.device)))
+
+    def step(self, emotion: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """emotion (n_streams, emotion_dim) -> (out (n_streams, 52), fired (n_streams) uint8); ``ready`` and ``backlog`` are
+        updated as well.  Rows of streams that did not fire keep what they held."""
+        emotion = emotion.contiguous()
+        check(self._lib.km_stream_step(self.engine._h, _ptr(emotion), _ptr(self.out), _ptr(self.fired), _ptr(self.ready),
+                                       _ptr(self.backlog), _stream_ptr(emotion.device)))
+        return self.out, self.fired
+
+    def reset_streams(self, mask: torch.Tensor) -> None:
+        """mask (n_streams) bool or uint8 on the device: those streams become freshly created ones (empty FIFO, empty ring, no EMA
+        history, a zero row of ``out``); the others are untouched.  No synchronisation."""
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (self.n_streams,):
+            raise ValueError(f"expected a ({self.n_streams},) bool or uint8 mask")
+        m8 = mask.to(torch.uint8).contiguous()
+        check(self._lib.km_stream_reset_streams(self.engine._h, _ptr(m8), _stream_ptr(m8.device)))
+        gone = m8 != 0
+        self.out.masked_fill_(gone.unsqueeze(1), 0.0)
+        for flags in (self.ready, self.fired, self.backlog):
+            flags.masked_fill_(gone, 0)
+
+    def reset(self) -> None:
+        super().reset()
+        self.fired.zero_()
+        self.backlog.zero_()
+
+    # ---- hipGraph replay ------------------------------------------------------------------------
+    def capture(self, n_per_stream: int, host_out: Optional[torch.Tensor] = None) -> None:
+        """Record feed (with per-stream counts) + step on static input buffers into a hipGraph: one linear chain.  ``host_out``: a
+        pinned (n_streams, 52) host tensor -- the result readback becomes the graph's last node."""
+        dev = self.engine.device
+        if host_out is not None and (not host_out.is_pinned() or tuple(host_out.shape) != tuple(self.out.shape)):
+            raise ValueError("host_out must be a pinned host tensor of the shape of the result")
+        self._g_samples = torch.zeros(self.n_streams, n_per_stream, device=dev)
+        self._g_counts = torch.full((self.n_streams,), n_per_stream, dtype=torch.int32, device=dev)
+        self._g_emotion = torch.zeros(self.n_streams, self.engine.emotion_dim, device=dev)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.feed(self._g_samples, self._g_counts)
+            self.step(self._g_emotion)
+            if host_out is not None:
+                host_out.copy_(self.out, non_blocking=True)
+        self._graph = g
+        self._g_host_out = host_out
+
+    def replay(self, samples: torch.Tensor, counts: Optional[torch.Tensor], emotion: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One captured feed + step; counts None: every stream brings all ``n_per_stream`` samples."""
+        if self._graph is None:
+            raise RuntimeError("capture() first")
+        self._g_samples.copy_(samples, non_blocking=True)
+        if counts is not None:
+            self._g_counts.copy_(counts, non_blocking=True)
+        else:
+            self._g_counts.fill_(self._g_samples.shape[1])
+        self._g_emotion.copy_(emotion, non_blocking=True)
+        self._graph.replay()
+        return self.out, self.fired
 
 
 def legacy_stream_shape(buffer_duration: float = 2.0, audio_length: int = 16000, hop: int = 533, sample_rate: int = 16000) -> dict:

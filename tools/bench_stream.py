@@ -5,14 +5,20 @@ Prints ticks/s and p50/p99 tick latency (host wall clock around replay + the 26 
 Default: the 30 fps shape (d_model 256, 8 heads, window 256, 533-sample frames).  ``--d-model 512 --heads 8|16 --fps 60``: the 60 fps
 long-context shape (window 512, 8.5 s ring of hop 266, 267-sample frames).  ``--baseline`` adds what a caller had to do at that shape
 before the stream path covered it: rings kept outside the library, unrolled into 128 chronological windows per tick, km_forward_audio
-on them with the EMA state (km_smooth behind the generic core), and the same readback -- timed the same way."""
+on them with the EMA state (km_smooth behind the generic core), and the same readback -- timed the same way.
+
+``--chunked``: streams out of phase.  In ONE run, at d_model 256 / 30 fps and d_model 512 / 8 heads / 60 fps, interleaved in rounds:
+(a) a replayed km_stream_feed + km_stream_step with every stream firing, (b) the lockstep replayed km_stream_push + km_stream_tick,
+(c) a replayed feed + step on which one stream in four brings a frame; then the route there was before for streams that do not move
+together: one SimplifiedDualStreamModel(real_time_mode=True) per stream driven frame by frame (8 streams, the d_model 256 shape),
+reported per stream-frame.  Host wall clock around one synchronised tick, as above."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from koemorph_amd import synth
 from koemorph_amd.engine import Engine, MelConfig
-from koemorph_amd.streaming import StreamEngine
+from koemorph_amd.streaming import ChunkedStreamEngine, StreamEngine
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--streams", type=int, default=128)
@@ -21,8 +27,102 @@ ap.add_argument("--d-model", type=int, default=256, choices=(256, 512))
 ap.add_argument("--heads", type=int, default=8, choices=(8, 16))
 ap.add_argument("--fps", type=int, default=30, choices=(30, 60))
 ap.add_argument("--baseline", action="store_true", help="also time host-side rings + forward_audio + EMA per tick")
+ap.add_argument("--chunked", action="store_true", help="feed + step (all fire / one in four) against push + tick at both shapes, and one model per stream")
 args = ap.parse_args()
 S = args.streams
+
+
+def make_engine(d_model, heads, fps):
+    if d_model == 256:
+        e = Engine(); e.load_state_dict(synth.make_core_params(0)); e.finalize()
+    else:
+        e = Engine(d_model=512, num_heads=heads, mel_sequence_length=512, mel=MelConfig.model_batch(target_fps=fps))
+        e.load_state_dict(synth.make_core_params(0, 512, 512)); e.finalize()
+    return e
+
+
+def stats(lat):
+    lat = np.asarray(lat) * 1e3
+    return {"ms_mean": round(float(lat.mean()), 4), "ms_p10": round(float(np.percentile(lat, 10)), 4),
+            "ms_p50": round(float(np.percentile(lat, 50)), 4), "ms_p90": round(float(np.percentile(lat, 90)), 4)}
+
+
+def chunked_shape(d_model, heads, fps, rounds=8):
+    ui = 0.0333 if fps == 30 else 1.0 / fps
+    lock = StreamEngine(make_engine(d_model, heads, fps), S, update_interval=ui)
+    chk = ChunkedStreamEngine(make_engine(d_model, heads, fps), S, update_interval=ui)
+    n, frame = lock.ring_hop + 1, chk.frame_samples          # both routes upload n samples per stream and tick
+    frames = torch.from_numpy(synth.make_audio(1, S, n * 8, "uniform")).cuda()
+    emo = torch.from_numpy(synth.normal(2, (S, 256))).cuda()
+    every = torch.full((S,), frame, dtype=torch.int32, device="cuda")
+    quarter = [torch.where((torch.arange(S, device="cuda") + p) % 4 == 0, every, torch.zeros_like(every)) for p in range(4)]
+    chunk = lambda t: frames[:, (t % 8) * n:(t % 8 + 1) * n]
+    for t in range(lock.shape["ring_len"] // lock.ring_hop + 3):      # fill the rings (eager)
+        lock.push(chunk(t)); lock.tick(emo)
+        chk.feed(chunk(t), every); chk.step(emo)
+    h_lock, h_chk = torch.empty(S, 52, pin_memory=True), torch.empty(S, 52, pin_memory=True)
+    lock.capture(n, host_out=h_lock)
+    chk.capture(n, host_out=h_chk)
+    routes = {"a_feed_step_all_fire": lambda t: chk.replay(chunk(t), every, emo),
+              "b_push_tick": lambda t: lock.replay(chunk(t), emo),
+              "c_feed_step_one_in_four": lambda t: chk.replay(chunk(t), quarter[t % 4], emo)}
+    lat = {k: [] for k in routes}
+    fired = {}
+    per_round = max(1, args.ticks // rounds)
+    for r in range(rounds + 1):                               # round 0 warms up
+        for name, step in routes.items():
+            torch.cuda.synchronize()
+            for t in range(per_round):
+                t0 = time.perf_counter()
+                step(t)
+                torch.cuda.synchronize()
+                if r:
+                    lat[name].append(time.perf_counter() - t0)
+            fired[name] = int(chk.fired.sum()) if name != "b_push_tick" else int(lock.ready.sum())
+    res = {"workload": f"{S} streams/GPU (d_model {d_model}, {heads} heads, {fps} fps), replayed graph + D2H of {S}x52 floats, one "
+                       f"synchronisation per tick, {rounds} rounds x {per_round} ticks per route, interleaved",
+           "samples_uploaded_per_stream": n, "frame_samples": frame, "streams_computed_on_last_tick": fired}
+    for name in routes:
+        res[name] = stats(lat[name])
+    return res
+
+
+def per_model_route(n_models=8, ticks=60):
+    """One SimplifiedDualStreamModel(real_time_mode=True) per stream, each driven frame by frame (its ring on the host, the 8.5 s
+    window uploaded per frame, front end + core + EMA launches per stream).  Steps are one audio hop apart: a stepped clock."""
+    from koemorph_amd.model import SimplifiedDualStreamModel
+    sd = {"dual_stream_attention." + k: torch.from_numpy(v) for k, v in synth.make_core_params(0).items()}
+    sd["smoothing_alpha"] = torch.tensor(0.8)
+    models, clock = [], [0.0]
+    for _ in range(n_models):
+        m = SimplifiedDualStreamModel(real_time_mode=True).cuda().eval()
+        m.load_state_dict(sd)
+        m.mel_extractor._clock = lambda: clock[0]
+        models.append(m)
+    audio = synth.make_audio(1, n_models, 533 * 8, "uniform")
+    emo = torch.from_numpy(synth.normal(2, (n_models, 256))).cuda()
+    fill = 136000 // 532 + 3
+    lat = []
+    for t in range(fill + ticks):
+        clock[0] += 0.0333
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs = [m.process_audio_frame_realtime(audio[i, (t % 8) * 533:(t % 8 + 1) * 533], emotion_features=emo[i:i + 1])
+                for i, m in enumerate(models)]
+        torch.cuda.synchronize()
+        if t >= fill:
+            assert all(o is not None for o in outs)
+            lat.append((time.perf_counter() - t0) / n_models)
+    return {"workload": f"{n_models} x SimplifiedDualStreamModel(real_time_mode=True) (d_model 256, 30 fps), one 533-sample frame per model "
+                        f"per tick, one synchronisation per tick, {ticks} ticks; figures are per stream-frame",
+            "per_stream_frame": stats(lat)}
+
+
+if args.chunked:
+    for shape in ((256, 8, 30), (512, 8, 60)):
+        print(json.dumps(chunked_shape(*shape)), flush=True)
+    print(json.dumps(per_model_route()), flush=True)
+    sys.exit(0)
 if args.d_model == 256:
     eng = Engine(); eng.load_state_dict(synth.make_core_params(0)); eng.finalize()
 else:
