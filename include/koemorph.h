@@ -631,6 +631,49 @@ int km_egemaps_functionals_from_records(const float* rec_dev, int64_t B, int64_t
  * eGeMAPS windows (OpenSMILEeGeMAPSExtractor.get_concatenated_features, opensmile_extractor.py:575-590).  b may be NULL. */
 int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev, void* stream);
 
+/* ---- emotion vectors of many streams, from the pushed audio, resident on the device ------------------------------
+ * An object of its own (not tied to a km_handle), on the current device.  Replaces, for n_streams speakers at once, one
+ * OpenSMILEeGeMAPSExtractor(use_concatenation=True) per speaker (src/features/opensmile_extractor.py): its AudioBuffer (:29-154),
+ * process_audio_frame / _extract_features (:287-318, :380-425), the three window slots (_update_window_features :460-502), the
+ * Linear(264, 256) of get_concatenated_features (:559-608) and reset (:640-659).  With SR = 16000, per stream: a ring of
+ * R = int((context_window_s + 2.0) * SR) samples with write_pos, is_full and total (int64 samples since creation or reset); the
+ * window is [0, min(write_pos, C)) while the ring has not wrapped -- the OLDEST C samples once more than C have arrived, as
+ * get_window does (:128-130) -- and the newest C = min(int(context_window_s * SR), R) samples ending at write_pos once it has.
+ * Two deliberate deviations from the reference: time is audio time (a stream is due U = int(update_interval_s * SR) samples
+ * after its last update, not update_interval_s of time.time() after it, :308-312), and an empty buffer's window of zeros
+ * (:111-114) is never extracted -- a stream without audio has no features.
+ *   km_emotion_stream_create           validates like the constructor (:204-209): context >= 1.0 s, 0.1 s <= interval <= context
+ *                                      (KM_ERR_INVALID_ARG); 1 <= max_updates <= n_streams <= 4096 (KM_ERR_INVALID_ARG); the window
+ *                                      must fit km_egemaps_num_frames(C) <= 2048 (KM_ERR_UNSUPPORTED).  Allocates everything.
+ *   km_emotion_stream_set_compression  the Linear(264, 256) (:589-591): w_dev (256, 264) as nn.Linear stores it, b_dev (256); copied
+ *   km_emotion_stream_push             AudioBuffer.append (:63-96) for every stream: samples_dev (n_streams, n_per_stream);
+ *                                      counts_dev (n_streams) int32, each clamped to 0 .. n_per_stream, or NULL = n_per_stream for
+ *                                      all.  A stream with count 0 is untouched.  n_per_stream > R: KM_ERR_INVALID_ARG
+ *   km_emotion_stream_update           evaluates every stream once.  Eligible: total > 0, due (no features yet, or total -
+ *                                      last_update_total >= U) and a window of at least int(0.5 * SR) samples (:388-389).  Of the
+ *                                      eligible streams the max_updates that waited longest (total - last_update_total, never
+ *                                      updated = -1; ties to the lowest index) are selected; the others wait for the next call.
+ *                                      A selected stream: features = the 88 functionals of its window with peak normalisation
+ *                                      (km_egemaps_functionals' kernels, reading the ring in place), NaN / +-Inf -> 0 (:450-452);
+ *                                      empty 300 / 600 ms slots both take that vector and keep it until a reset (:478-490);
+ *                                      last_update_total = total; emotion row = W concat(features, slot_300, slot_600) + b.
+ *                                      Everything of a stream that was not selected is kept.  emotion_dev (n_streams, 256): every
+ *                                      row (zero until the first update); valid_dev (u8, may be NULL): has features; updated_dev
+ *                                      (u8, may be NULL): selected on this call.  KM_ERR_NOT_READY before set_compression
+ *   km_emotion_stream_reset_streams    mask_dev (n_streams) u8, NULL = all: those streams become freshly created ones (ring
+ *                                      zeroed, counters cleared, slots empty, zero emotion row); the others are untouched
+ *   km_emotion_stream_features         features_dev (n_streams, 88) <- current features; slots_dev (n_streams, 2, 88) or NULL <-
+ *                                      the 300 / 600 ms slots (device to device, on `stream`)
+ * push, update and reset_streams never allocate, synchronise or read anything back, and their launch shapes depend only on
+ * (n_streams, max_updates, n_per_stream): push + update capture into a hipGraph as one linear chain. */
+int km_emotion_stream_create(void** es, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates);
+int km_emotion_stream_destroy(void* es);
+int km_emotion_stream_set_compression(void* es, const float* w_dev, const float* b_dev, void* stream);
+int km_emotion_stream_push(void* es, const float* samples_dev, int64_t n_per_stream, const int32_t* counts_dev, void* stream);
+int km_emotion_stream_update(void* es, float* emotion_dev, uint8_t* valid_dev, uint8_t* updated_dev, void* stream);
+int km_emotion_stream_reset_streams(void* es, const uint8_t* mask_dev, void* stream);
+int km_emotion_stream_features(void* es, float* features_dev, float* slots_dev, void* stream);
+
 /* ---- evaluation metrics: a streaming accumulator in device memory ------------------------------------------------
  * Replaces BlendshapeMetrics (src/model/losses.py:421-521) and compute_lip_sync_metrics (:524-583).  The reference
  * copies every batch to the host, concatenates the epoch and reduces it there; here (N, 52) rows are folded into a

@@ -18,6 +18,8 @@
 //                          waveform), harmonic differences and formant amplitudes
 //   egm_functional_kernel  per window: 3-frame smoothing, means / normalised deviations / percentiles (bitonic sort in
 //                          LDS) / slopes of rising and falling parts over voiced, unvoiced or all frames
+// Each kernel has two instantiations: over a dense (B, L) array of windows (km_egemaps_*), and over ragged windows that are read
+// in place from stream rings through a slot table written on the device (egm_ragged_functionals, for km_emotion_stream.hip).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "km_context.h"
+#include "km_egemaps_ragged.h"
 
 namespace km {
 
@@ -161,17 +164,55 @@ struct EgmArgs {
     const float* audio; int64_t L; int nf;
     const float* scale;      // (B) peak normalisation factors, or null
     const float* tab;        // EgmPlan table blob
-    float* rec;              // (B, nf, REC)
+    float* rec;              // (B, rec_frames, REC)
+    int rec_frames;          // frames between two windows' records: nf, or the longest window's count when windows are ragged
+    const EgmSlot* slots;    // ragged windows only: per window {stream, ring start, length, frames} (km_egemaps_ragged.h)
+    int ring_len;            // ragged windows only: samples per stream ring; audio is then (n_streams, ring_len)
     int o_g60, o_ham, o_tw, o_fb_w, o_fb_start, o_fb_count, o_fb_off, o_eql, o_dct, o_logi, o_logf, o_hshift, o_hweight, o_pre, o_cos,
         o_sl0, o_sl1, o_gg;
     int n_log, j0, j1, nb_lpc, b_alpha[4], b_hamm[3], b_sl0[2], b_sl1[2];
 };
 
-__global__ __launch_bounds__(256) void egm_peak_kernel(const float* __restrict__ x, int64_t L, float* __restrict__ scale) {
+// Where a window's samples are.  The kernels below are written once against `xw[i]`, sample i of the window: LinearWin is
+// window b of a dense (B, L) array (km_egemaps_functionals, RAGGED = false), RingWin a window of its own length that starts
+// anywhere in a stream's ring and may wrap (the emotion streams, RAGGED = true: a device-written EgmSlot per window, a block
+// whose slot is empty or whose frame lies beyond the slot's frames leaves before it touches LDS or a barrier).  Only the
+// address differs; the arithmetic on the samples is the same code.
+struct LinearWin {
+    const float* p;
+    __device__ __forceinline__ float operator[](int64_t i) const { return p[i]; }
+};
+struct RingWin {
+    const float* p; int start, n;
+    __device__ __forceinline__ float operator[](int i) const { const int j = start + i; return p[j >= n ? j - n : j]; }   // start < n, i <= n
+};
+template <bool RAGGED> struct EgmWin;
+template <> struct EgmWin<false> {
+    using Src = LinearWin;
+    static __device__ __forceinline__ bool open(const float* audio, int64_t L, const EgmSlot*, int, int b, Src& x, int& len, int& nf) {
+        x.p = audio + (int64_t)b * L; len = (int)L;
+        return true;
+    }
+};
+template <> struct EgmWin<true> {
+    using Src = RingWin;
+    static __device__ __forceinline__ bool open(const float* audio, int64_t, const EgmSlot* slots, int ring_len, int b, Src& x, int& len, int& nf) {
+        const EgmSlot s = slots[b];
+        if (s.stream < 0) return false;
+        x.p = audio + (int64_t)s.stream * ring_len; x.start = s.start; x.n = ring_len; len = s.len; nf = s.nf;
+        return true;
+    }
+};
+
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void egm_peak_kernel(const float* __restrict__ x, int64_t L, const EgmSlot* __restrict__ slots, int ring_len,
+                                                       float* __restrict__ scale) {
     __shared__ float red[256];
-    const float* p = x + (int64_t)blockIdx.x * L;
+    typename EgmWin<RAGGED>::Src p; int len = 0, nf = 0;
+    if (!EgmWin<RAGGED>::open(x, L, slots, ring_len, blockIdx.x, p, len, nf)) return;
     float m = 0.f;
-    for (int64_t i = threadIdx.x; i < L; i += 256) m = fmaxf(m, fabsf(p[i]));
+    if constexpr (RAGGED) { for (int i = threadIdx.x; i < len; i += 256) m = fmaxf(m, fabsf(p[i])); }
+    else { for (int64_t i = threadIdx.x; i < L; i += 256) m = fmaxf(m, fabsf(p[i])); }
     red[threadIdx.x] = m;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -245,7 +286,8 @@ __device__ __forceinline__ void acf_lags(const float* sw, const float* gg, int l
 
 // 60 ms Gaussian frame (real part) and, optionally, a 20 ms Hamming frame (imaginary part) -> 1024-point spectra.
 // zb is loaded in bit-reversed order; after the FFT M60[k] = |(Z[k] + conj Z[N-k]) / 2|, M20[k] = |(Z[k] - conj Z[N-k]) / 2i|.
-__device__ __forceinline__ void frame_spectra(const EgmArgs& a, const float* xw, float sc, int start60, int start20, bool with20,
+template <class Src>
+__device__ __forceinline__ void frame_spectra(const EgmArgs& a, const Src& xw, float sc, int start60, int start20, bool with20,
                                               float2* zb, const float2* tw, float* M60, float* M20) {
     using namespace egm;
     const float* g60 = a.tab + a.o_g60; const float* ham = a.tab + a.o_ham;
@@ -267,15 +309,17 @@ __device__ __forceinline__ void frame_spectra(const EgmArgs& a, const float* xw,
     __syncthreads();
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256, 6) void egm_frame_kernel(EgmArgs a) {
     using namespace egm;
     __shared__ float2 zb[NFFT];
     __shared__ float2 tw[NFFT / 2];
     __shared__ float M60[NB + 3], M20[NB + 3], Mp[NB + 3], red[256], E[32], slog[512], shs[256], misc[64], sw[N60], rl[128];
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const float* xw = a.audio + (int64_t)b * a.L;
+    typename EgmWin<RAGGED>::Src xw; int len = 0, nf = a.nf;
+    if (!EgmWin<RAGGED>::open(a.audio, a.L, a.slots, a.ring_len, b, xw, len, nf) || t >= nf) return;
     const float sc = a.scale ? a.scale[b] : 1.0f;
-    float* rec = a.rec + ((int64_t)b * a.nf + t) * REC;
+    float* rec = a.rec + ((int64_t)b * a.rec_frames + t) * REC;
     for (int k = tid; k < NFFT / 2; k += 256) tw[k] = reinterpret_cast<const float2*>(a.tab + a.o_tw)[k];
     __syncthreads();
     // previous frame's 20 ms spectrum (for the spectral flux): the imaginary slot of a transform whose real slot is unused
@@ -507,7 +551,8 @@ __global__ __launch_bounds__(256, 6) void egm_frame_kernel(EgmArgs a) {
 
 // pitch track over the candidates: states 0..2 = candidate, 3 = unvoiced.  One thread per window walks the frames; the
 // back pointers live in the bp LDS array (two bits per state), which the backtrack then overwrites with the chosen state.
-__global__ __launch_bounds__(256) void egm_viterbi_kernel(float* __restrict__ recs, int nf) {
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void egm_viterbi_kernel(float* __restrict__ recs, int nf, int rec_frames, const EgmSlot* __restrict__ slots) {
     using namespace egm;
     // The recursion itself is sequential (thread 0), but its inputs are not: all threads first gather the seven numbers a
     // step needs -- voicing flag, log2 of the three candidate frequencies, their strengths -- into LDS, so that the walk
@@ -515,7 +560,12 @@ __global__ __launch_bounds__(256) void egm_viterbi_kernel(float* __restrict__ re
     // together at the end.  Same arithmetic in the same order as before.
     __shared__ float in[7 * MAXF];            // [0] voiced-ok, [1..3] log2 f (or -1: no candidate), [4..6] strength
     __shared__ unsigned char bp[MAXF];        // back pointers (two bits per state), then the chosen state
-    float* rec = recs + (int64_t)blockIdx.x * nf * REC;
+    if constexpr (RAGGED) {
+        const EgmSlot sl = slots[blockIdx.x];
+        if (sl.stream < 0) return;
+        nf = sl.nf;
+    }
+    float* rec = recs + (int64_t)blockIdx.x * rec_frames * REC;
     for (int t = threadIdx.x; t < nf; t += 256) {
         const float* r = rec + (int64_t)t * REC;
         in[t] = (r[R_VOI] >= VOICING_CUTOFF && r[R_RMS] >= RMS_FLOOR) ? 1.f : 0.f;
@@ -574,6 +624,7 @@ __global__ __launch_bounds__(256) void egm_viterbi_kernel(float* __restrict__ re
     }
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void egm_voiced_kernel(EgmArgs a) {
     using namespace egm;
     __shared__ float2 zb[NFFT];
@@ -581,9 +632,10 @@ __global__ __launch_bounds__(256) void egm_voiced_kernel(EgmArgs a) {
     __shared__ float M60[NB + 3], seg[N60], red[256], cc[128];
     __shared__ int redi[256], marks[64];
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const float* xw = a.audio + (int64_t)b * a.L;
+    typename EgmWin<RAGGED>::Src xw; int len = 0, nf = a.nf;
+    if (!EgmWin<RAGGED>::open(a.audio, a.L, a.slots, a.ring_len, b, xw, len, nf) || t >= nf) return;
     const float sc = a.scale ? a.scale[b] : 1.0f;
-    float* rec = a.rec + ((int64_t)b * a.nf + t) * REC;
+    float* rec = a.rec + ((int64_t)b * a.rec_frames + t) * REC;
     const float f0 = rec[R_F0];
     __syncthreads();                                     // everyone has read the record before thread 0 rewrites parts of it
     if (f0 <= 0.f) {
@@ -723,12 +775,19 @@ __device__ __forceinline__ void bitonic_sort(float* s, int n2) {      // ascendi
         }
 }
 
-__global__ __launch_bounds__(256) void egm_functional_kernel(const float* __restrict__ recs, int nf, float* __restrict__ out) {
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void egm_functional_kernel(const float* __restrict__ recs, int nf, int rec_frames, const EgmSlot* __restrict__ slots,
+                                                             float* __restrict__ out) {
     using namespace egm;
     __shared__ float v[MAXF], s[MAXF], f0s[MAXF], red[256], res[16];
     __shared__ int cnt_s[4];
     const int tid = threadIdx.x;
-    const float* rec = recs + (int64_t)blockIdx.x * nf * REC;
+    if constexpr (RAGGED) {
+        const EgmSlot sl = slots[blockIdx.x];
+        if (sl.stream < 0) return;
+        nf = sl.nf;
+    }
+    const float* rec = recs + (int64_t)blockIdx.x * rec_frames * REC;
     float* o = out + (int64_t)blockIdx.x * 88;
     auto raw = [&](int t, int field) { return rec[(int64_t)t * REC + field]; };
     // smoothed F0 (non-zero smoothing) defines the voiced frames
@@ -886,7 +945,7 @@ __global__ __launch_bounds__(256) void egm_functional_kernel(const float* __rest
 
 static EgmArgs egm_args(const EgmPlan* p, const float* audio, int64_t L, int nf, const float* scale, float* rec) {
     EgmArgs a{};
-    a.audio = audio; a.L = L; a.nf = nf; a.scale = scale; a.tab = p->d; a.rec = rec;
+    a.audio = audio; a.L = L; a.nf = nf; a.scale = scale; a.tab = p->d; a.rec = rec; a.rec_frames = nf; a.slots = nullptr; a.ring_len = 0;
     a.o_g60 = p->o_g60; a.o_ham = p->o_ham; a.o_tw = p->o_tw; a.o_fb_w = p->o_fb_w; a.o_fb_start = p->o_fb_start; a.o_fb_count = p->o_fb_count;
     a.o_fb_off = p->o_fb_off; a.o_eql = p->o_eql; a.o_dct = p->o_dct; a.o_logi = p->o_logi; a.o_logf = p->o_logf; a.o_hshift = p->o_hshift;
     a.o_hweight = p->o_hweight; a.o_pre = p->o_pre; a.o_cos = p->o_cos; a.o_sl0 = p->o_sl0; a.o_sl1 = p->o_sl1; a.o_gg = p->o_gg;
@@ -895,6 +954,25 @@ static EgmArgs egm_args(const EgmPlan* p, const float* audio, int64_t L, int nf,
     for (int i = 0; i < 3; ++i) a.b_hamm[i] = p->b_hamm[i];
     for (int i = 0; i < 2; ++i) { a.b_sl0[i] = p->b_sl0[i]; a.b_sl1[i] = p->b_sl1[i]; }
     return a;
+}
+
+// The five kernels over ragged windows that live in stream rings (km_emotion_stream.hip): fixed grids of max_nf frames x
+// n_slots windows, everything else from the slot table on the device.
+int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
+                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st) {
+    using namespace egm;
+    if (!plan || !rings_dev || !slots_dev || !scale_dev || !rec_dev || !out_dev || n_slots < 1 || n_slots > 65535 || max_nf < 1 || max_nf > MAXF ||
+        ring_len < 1 || ring_len > (1 << 30))
+        return fail(KM_ERR_INVALID_ARG, "egm_ragged_functionals: bad argument");
+    EgmArgs a = egm_args(static_cast<EgmPlan*>(plan), rings_dev, 0, 0, scale_dev, rec_dev);
+    a.rec_frames = max_nf; a.slots = slots_dev; a.ring_len = (int)ring_len;
+    hipLaunchKernelGGL(egm_peak_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, rings_dev, (int64_t)0, slots_dev, (int)ring_len, scale_dev);
+    hipLaunchKernelGGL(egm_frame_kernel<true>, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(egm_viterbi_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, rec_dev, 0, max_nf, slots_dev);
+    hipLaunchKernelGGL(egm_voiced_kernel<true>, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(egm_functional_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, (const float*)rec_dev, 0, max_nf, slots_dev, out_dev);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
 }
 
 }  // namespace km
@@ -941,14 +1019,14 @@ int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_
     float* scale = work_dev;                       // (B), padded to 4 B floats
     float* rec = work_dev + 4 * B;
     if (normalize) {
-        hipLaunchKernelGGL(egm_peak_kernel, dim3((unsigned)B), dim3(256), 0, st, audio_dev, L, scale);
+        hipLaunchKernelGGL(egm_peak_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, audio_dev, L, (const EgmSlot*)nullptr, 0, scale);
         HIP_TRY(hipGetLastError());
     }
     const EgmArgs a = egm_args(p, audio_dev, L, (int)nf, normalize ? scale : nullptr, rec);
-    hipLaunchKernelGGL(egm_frame_kernel, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(egm_viterbi_kernel, dim3((unsigned)B), dim3(256), 0, st, rec, (int)nf);
-    hipLaunchKernelGGL(egm_voiced_kernel, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(egm_functional_kernel, dim3((unsigned)B), dim3(256), 0, st, rec, (int)nf, out_dev);
+    hipLaunchKernelGGL(egm_frame_kernel<false>, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(egm_viterbi_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, rec, (int)nf, (int)nf, (const EgmSlot*)nullptr);
+    hipLaunchKernelGGL(egm_voiced_kernel<false>, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(egm_functional_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, (const float*)rec, (int)nf, (int)nf, (const EgmSlot*)nullptr, out_dev);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
@@ -966,14 +1044,14 @@ static int check_records(const char* who, const void* rec, const void* out, int6
 
 int km_egemaps_track_from_records(float* rec_dev, int64_t B, int64_t nf, void* stream) {
     if (const int rc = check_records("km_egemaps_track_from_records", rec_dev, rec_dev, B, nf)) return rc;
-    hipLaunchKernelGGL(egm_viterbi_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, rec_dev, (int)nf);
+    hipLaunchKernelGGL(egm_viterbi_kernel<false>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, rec_dev, (int)nf, (int)nf, (const EgmSlot*)nullptr);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
 
 int km_egemaps_functionals_from_records(const float* rec_dev, int64_t B, int64_t nf, float* out_dev, void* stream) {
     if (const int rc = check_records("km_egemaps_functionals_from_records", rec_dev, out_dev, B, nf)) return rc;
-    hipLaunchKernelGGL(egm_functional_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, rec_dev, (int)nf, out_dev);
+    hipLaunchKernelGGL(egm_functional_kernel<false>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, rec_dev, (int)nf, (int)nf, (const EgmSlot*)nullptr, out_dev);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

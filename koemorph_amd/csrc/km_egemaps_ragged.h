@@ -1,0 +1,25 @@
+// eGeMAPS functionals of ragged windows read in place from stream rings: the interface between km_emotion_stream.hip (which
+// writes the slot table on the device) and km_egemaps.hip (whose five kernels are instantiated for it).  Internal.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace km {
+
+// One window of an update.  stream < 0: the slot is empty and every block that belongs to it exits at once.
+struct EgmSlot {
+    int32_t stream;   // row of the ring array
+    int32_t start;    // ring index of the window's first sample, 0 <= start < ring_len
+    int32_t len;      // samples, <= ring_len; sample i is ring[(start + i) mod ring_len]
+    int32_t nf;       // 10 ms frames of a window of len samples (km_egemaps_num_frames), 1 <= nf <= max_nf
+};
+
+// peak, frame, pitch-track, voiced and functional kernels for n_slots slots: grids of max_nf x n_slots (per frame) and n_slots (per
+// window) whatever the table holds.  scale_dev (n_slots), rec_dev (n_slots, max_nf, 36), out_dev (n_slots, 88): rows of empty slots
+// are not written.  No allocation, no synchronisation.
+int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
+                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st);
+
+}  // namespace km

@@ -1,0 +1,319 @@
+// Emotion vectors of many speaker streams, resident on the device -- the real-time state machine of the reference's
+// OpenSMILEeGeMAPSExtractor (src/features/opensmile_extractor.py) for all streams at once:
+//   AudioBuffer.append / get_window          :29-154    es_append_kernel + es_advance_kernel, the window arithmetic of es_select_kernel
+//   process_audio_frame / _extract_features  :287-425   es_select_kernel (who is due, who holds half a second), the ragged eGeMAPS
+//                                                       kernels of km_egemaps.hip on the windows where they lie in the rings
+//   _extract_features_from_audio             :450-452   es_epilogue_kernel: NaN / Inf -> 0
+//   _update_window_features                  :460-502   es_epilogue_kernel: the 300 / 600 ms slots are filled once per life
+//   get_concatenated_features                :559-608   es_epilogue_kernel: Linear(264, 256) of current | slot 300 | slot 600
+//   reset                                    :640-659   es_reset_kernel, per stream
+//
+// Time is audio time: a stream is due when `update_samples` samples have arrived since its last update (the reference asks
+// time.time()), so every result is a function of the call sequence.  Nothing here allocates, synchronises or reads back after
+// creation and every grid is fixed by (n_streams, max_updates): push + update capture into a hipGraph as one linear chain.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <new>
+
+#include "km_context.h"
+#include "km_egemaps_ragged.h"
+
+namespace km {
+
+#define HIP_TRY(expr)                                                                         \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess) {                                                               \
+            (void)hipGetLastError();                                                          \
+            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                  \
+        }                                                                                     \
+    } while (0)
+
+namespace es {
+constexpr int SR = 16000, NFEAT = 88, NCAT = 3 * NFEAT, NEMO = 256, REC = 36, MAXF = 2048;
+constexpr int SEL_THREADS = 1024, MAX_STREAMS = 4096;   // the selection ranks all streams in one workgroup, waiting times in LDS
+}  // namespace es
+
+// per-stream counters (arrays of n_streams)
+struct EsState {
+    int32_t* write_pos;        // AudioBuffer.write_pos
+    int32_t* is_full;          // AudioBuffer.is_full
+    int64_t* total;            // samples since creation or reset
+    int64_t* last_total;       // `total` at the last update, -1 = never
+    int32_t* has_features;     // current_features is not None
+    int32_t* slots_filled;     // window_features[0.3] / [0.6] are not None
+};
+
+struct EmotionStream {
+    int64_t n = 0, max_updates = 0;
+    int ring_len = 0, window_len = 0, update_samples = 0, min_samples = 0, max_nf = 0;
+    void* plan = nullptr;
+    char* blob = nullptr;      // one allocation, carved below
+    float* ring = nullptr;     // (n, ring_len)
+    EsState st{};
+    float* features = nullptr; // (n, 88)
+    float* slots = nullptr;    // (n, 2, 88)
+    float* emotion = nullptr;  // (n, 256)
+    uint8_t* updated = nullptr;// (n)
+    EgmSlot* table = nullptr;  // (max_updates)
+    float* scale = nullptr;    // (max_updates)
+    float* rec = nullptr;      // (max_updates, max_nf, 36)
+    float* fout = nullptr;     // (max_updates, 88)
+    float* wt = nullptr;       // (264, 256): the compression weight transposed
+    float* bias = nullptr;     // (256)
+    bool has_compression = false;
+};
+
+// ---- AudioBuffer.append (:63-96) ----
+__global__ __launch_bounds__(256) void es_append_kernel(const float* __restrict__ samples, int m, const int32_t* __restrict__ counts,
+                                                        float* __restrict__ ring, int ring_len, const int32_t* __restrict__ write_pos) {
+    const int s = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    int c = counts ? counts[s] : m;
+    c = c < 0 ? 0 : (c > m ? m : c);
+    if (i >= c) return;
+    int j = write_pos[s] + i;                        // write_pos < ring_len, i < m <= ring_len
+    if (j >= ring_len) j -= ring_len;
+    ring[(int64_t)s * ring_len + j] = samples[(int64_t)s * m + i];
+}
+
+__global__ __launch_bounds__(256) void es_advance_kernel(int n, int m, const int32_t* __restrict__ counts, int ring_len, EsState st) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n) return;
+    int c = counts ? counts[s] : m;
+    c = c < 0 ? 0 : (c > m ? m : c);
+    if (c == 0) return;
+    int wp = st.write_pos[s], full = st.is_full[s];
+    const int room = ring_len - wp;
+    if (c <= room) wp += c;
+    else { wp = c - room; full = 1; }
+    if (wp >= ring_len) { wp = 0; full = 1; }
+    st.write_pos[s] = wp; st.is_full[s] = full; st.total[s] += c;
+}
+
+// ---- who updates on this call: eligibility, then the max_updates longest-waiting streams by counting ----
+__global__ __launch_bounds__(es::SEL_THREADS) void es_select_kernel(int n, int max_updates, int ring_len, int window_len, int update_samples,
+                                                                    int min_samples, EsState st, EgmSlot* __restrict__ table,
+                                                                    uint8_t* __restrict__ updated) {
+    __shared__ int64_t wait[es::MAX_STREAMS];
+    const int tid = threadIdx.x;
+    for (int k = tid; k < max_updates; k += es::SEL_THREADS) table[k] = EgmSlot{-1, 0, 0, 0};
+    for (int s = tid; s < n; s += es::SEL_THREADS) {
+        const int64_t total = st.total[s], last = st.last_total[s];
+        const int len = st.is_full[s] ? window_len : (st.write_pos[s] < window_len ? st.write_pos[s] : window_len);
+        const bool due = !st.has_features[s] || total - last >= update_samples;
+        wait[s] = (total > 0 && due && len >= min_samples) ? total - last : -1;    // never updated: last = -1, waits longest of its age
+        updated[s] = 0;
+    }
+    __syncthreads();
+    for (int s = tid; s < n; s += es::SEL_THREADS) {
+        const int64_t w = wait[s];
+        if (w < 0) continue;
+        int rank = 0;
+        for (int j = 0; j < n; ++j) { const int64_t wj = wait[j]; rank += (wj > w || (wj == w && j < s)) ? 1 : 0; }
+        if (rank >= max_updates) continue;
+        const int wp = st.write_pos[s];
+        EgmSlot sl;
+        sl.stream = s;
+        if (st.is_full[s]) { sl.len = window_len; sl.start = wp - window_len; if (sl.start < 0) sl.start += ring_len; }
+        else { sl.len = wp < window_len ? wp : window_len; sl.start = 0; }
+        sl.nf = (sl.len - 960) / 160 + 1;                                      // km_egemaps_num_frames; len >= min_samples = 8000
+        table[rank] = sl;
+        updated[s] = 1;
+    }
+}
+
+// ---- per selected stream: scrub, slots, bookkeeping, Linear(264, 256) ----
+__global__ __launch_bounds__(256) void es_epilogue_kernel(const EgmSlot* __restrict__ table, const float* __restrict__ fout, EsState st,
+                                                          float* __restrict__ features, float* __restrict__ slots,
+                                                          const float* __restrict__ wt, const float* __restrict__ bias, float* __restrict__ emotion) {
+    using namespace es;
+    __shared__ float x[NCAT];
+    const int tid = threadIdx.x;
+    const EgmSlot sl = table[blockIdx.x];
+    if (sl.stream < 0) return;
+    const int s = sl.stream;
+    const bool filled = st.slots_filled[s] != 0;
+    if (tid < NFEAT) {
+        float f = fout[(int64_t)blockIdx.x * NFEAT + tid];
+        if (!(fabsf(f) <= 3.4028234663852886e38f)) f = 0.f;                   // NaN, +Inf, -Inf -> 0 (np.nan_to_num, :450-452)
+        features[(int64_t)s * NFEAT + tid] = f;
+        float* sp = slots + (int64_t)s * 2 * NFEAT;
+        if (!filled) { sp[tid] = f; sp[NFEAT + tid] = f; }
+        x[tid] = f; x[NFEAT + tid] = filled ? sp[tid] : f; x[2 * NFEAT + tid] = filled ? sp[NFEAT + tid] : f;
+    }
+    __syncthreads();                                   // also: every thread has read slots_filled before thread 0 sets it
+    float acc = 0.f;
+    for (int k = 0; k < NCAT; ++k) acc = fmaf(wt[k * NEMO + tid], x[k], acc);
+    emotion[(int64_t)s * NEMO + tid] = acc + bias[tid];
+    if (tid == 0) { st.last_total[s] = st.total[s]; st.has_features[s] = 1; st.slots_filled[s] = 1; }
+}
+
+__global__ __launch_bounds__(256) void es_output_kernel(int n, const float* __restrict__ emotion, const int32_t* __restrict__ has_features,
+                                                        const uint8_t* __restrict__ updated, float* __restrict__ emotion_out,
+                                                        uint8_t* __restrict__ valid_out, uint8_t* __restrict__ updated_out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (int64_t)n * es::NEMO) emotion_out[i] = emotion[i];
+    if (i < n) {
+        if (valid_out) valid_out[i] = has_features[i] ? 1 : 0;
+        if (updated_out) updated_out[i] = updated[i];
+    }
+}
+
+// ---- OpenSMILEeGeMAPSExtractor.reset, per stream ----
+__global__ __launch_bounds__(256) void es_reset_kernel(const uint8_t* __restrict__ mask, float* __restrict__ ring, int ring_len, EsState st,
+                                                       float* __restrict__ features, float* __restrict__ slots, float* __restrict__ emotion,
+                                                       uint8_t* __restrict__ updated) {
+    using namespace es;
+    const int s = blockIdx.y;
+    if (mask && !mask[s]) return;
+    float* r = ring + (int64_t)s * ring_len;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < ring_len; i += gridDim.x * 256) r[i] = 0.f;
+    if (blockIdx.x != 0) return;
+    const int tid = threadIdx.x;
+    if (tid < NFEAT) { features[(int64_t)s * NFEAT + tid] = 0.f; slots[(int64_t)s * 2 * NFEAT + tid] = 0.f; slots[(int64_t)s * 2 * NFEAT + NFEAT + tid] = 0.f; }
+    emotion[(int64_t)s * NEMO + tid] = 0.f;
+    if (tid == 0) {
+        st.write_pos[s] = 0; st.is_full[s] = 0; st.total[s] = 0; st.last_total[s] = -1; st.has_features[s] = 0; st.slots_filled[s] = 0;
+        updated[s] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void es_transpose_kernel(const float* __restrict__ w, float* __restrict__ wt) {    // (256, 264) -> (264, 256)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < es::NEMO * es::NCAT) { const int o = i / es::NCAT, k = i % es::NCAT; wt[k * es::NEMO + o] = w[i]; }
+}
+
+static int64_t align16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
+
+}  // namespace km
+
+using namespace km;
+
+extern "C" {
+
+int km_emotion_stream_create(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates) {
+    using namespace es;
+    if (!es_out) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: NULL argument");
+    *es_out = nullptr;
+    if (n_streams < 1 || n_streams > MAX_STREAMS)
+        return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: n_streams %lld, 1 .. %d", (long long)n_streams, MAX_STREAMS);
+    if (!(context_window_s >= 1.0)) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: Context window must be at least 1.0 seconds");
+    if (!(update_interval_s >= 0.1)) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: Update interval must be at least 0.1 seconds");
+    if (update_interval_s > context_window_s) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: Update interval cannot be larger than context window");
+    if (max_updates < 1 || max_updates > n_streams)
+        return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: max_updates %lld, 1 .. n_streams (%lld)", (long long)max_updates, (long long)n_streams);
+    if (context_window_s > 3600.0) return fail(KM_ERR_UNSUPPORTED, "km_emotion_stream_create: context window of %g s", context_window_s);
+    const int64_t R = (int64_t)((context_window_s + 2.0) * SR), Cw = (int64_t)(context_window_s * SR);
+    const int64_t C = Cw < R ? Cw : R, U = (int64_t)(update_interval_s * SR), MIN = (int64_t)(0.5 * SR);
+    const int64_t nf = km_egemaps_num_frames(C);
+    if (nf > MAXF)
+        return fail(KM_ERR_UNSUPPORTED, "km_emotion_stream_create: %lld frames per window, at most %d (20.5 s)", (long long)nf, MAXF);
+    EmotionStream* e = new (std::nothrow) EmotionStream();
+    if (!e) return fail(KM_ERR_HIP, "km_emotion_stream_create: out of host memory");
+    e->n = n_streams; e->max_updates = max_updates;
+    e->ring_len = (int)R; e->window_len = (int)C; e->update_samples = (int)U; e->min_samples = (int)MIN; e->max_nf = (int)nf;
+    if (const int rc = km_egemaps_plan_create(&e->plan)) { delete e; return rc; }
+    const int64_t n = n_streams, mu = max_updates;
+    // one allocation; `carve` hands out 16-byte aligned pieces, first with a null base to learn the size, then for real
+    auto layout = [&](char* base) {
+        int64_t at = 0;
+        auto carve = [&](int64_t bytes) { char* p = base ? base + at : nullptr; at += align16(bytes); return p; };
+        e->ring = reinterpret_cast<float*>(carve(n * R * 4));
+        e->st.write_pos = reinterpret_cast<int32_t*>(carve(n * 4)); e->st.is_full = reinterpret_cast<int32_t*>(carve(n * 4));
+        e->st.total = reinterpret_cast<int64_t*>(carve(n * 8)); e->st.last_total = reinterpret_cast<int64_t*>(carve(n * 8));
+        e->st.has_features = reinterpret_cast<int32_t*>(carve(n * 4)); e->st.slots_filled = reinterpret_cast<int32_t*>(carve(n * 4));
+        e->features = reinterpret_cast<float*>(carve(n * NFEAT * 4)); e->slots = reinterpret_cast<float*>(carve(n * 2 * NFEAT * 4));
+        e->emotion = reinterpret_cast<float*>(carve(n * NEMO * 4)); e->updated = reinterpret_cast<uint8_t*>(carve(n));
+        e->table = reinterpret_cast<EgmSlot*>(carve(mu * (int64_t)sizeof(EgmSlot))); e->scale = reinterpret_cast<float*>(carve(mu * 4));
+        e->rec = reinterpret_cast<float*>(carve(mu * nf * REC * 4)); e->fout = reinterpret_cast<float*>(carve(mu * NFEAT * 4));
+        e->wt = reinterpret_cast<float*>(carve((int64_t)NCAT * NEMO * 4)); e->bias = reinterpret_cast<float*>(carve(NEMO * 4));
+        return at;
+    };
+    const int64_t bytes = layout(nullptr);
+    hipError_t err = hipMalloc(reinterpret_cast<void**>(&e->blob), (size_t)bytes);
+    if (err == hipSuccess) err = hipMemset(e->blob, 0, (size_t)bytes);
+    if (err == hipSuccess) { layout(e->blob); err = hipMemset(e->st.last_total, 0xff, (size_t)(n * 8)); }       // last_total = -1
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        if (e->blob) (void)hipFree(e->blob);
+        km_egemaps_plan_destroy(e->plan);
+        delete e;
+        return fail(KM_ERR_HIP, "km_emotion_stream_create: %lld bytes of device memory: %s", (long long)bytes, hipGetErrorString(err));
+    }
+    *es_out = e;
+    return KM_OK;
+}
+
+int km_emotion_stream_destroy(void* es) {
+    if (!es) return KM_OK;
+    EmotionStream* e = static_cast<EmotionStream*>(es);
+    if (e->blob) (void)hipFree(e->blob);
+    km_egemaps_plan_destroy(e->plan);
+    delete e;
+    return KM_OK;
+}
+
+int km_emotion_stream_set_compression(void* es, const float* w_dev, const float* b_dev, void* stream) {
+    if (!es || !w_dev || !b_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_set_compression: NULL argument");
+    EmotionStream* e = static_cast<EmotionStream*>(es);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(es_transpose_kernel, dim3((es::NEMO * es::NCAT + 255) / 256), dim3(256), 0, st, w_dev, e->wt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(e->bias, b_dev, es::NEMO * sizeof(float), hipMemcpyDeviceToDevice, st));
+    e->has_compression = true;
+    return KM_OK;
+}
+
+int km_emotion_stream_push(void* es, const float* samples_dev, int64_t n_per_stream, const int32_t* counts_dev, void* stream) {
+    if (!es || !samples_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_push: NULL argument");
+    EmotionStream* e = static_cast<EmotionStream*>(es);
+    if (n_per_stream < 1 || n_per_stream > e->ring_len)
+        return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_push: %lld samples per stream, 1 .. %d (the ring)", (long long)n_per_stream, e->ring_len);
+    hipStream_t st = (hipStream_t)stream;
+    const int m = (int)n_per_stream;
+    hipLaunchKernelGGL(es_append_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)e->n), dim3(256), 0, st, samples_dev, m, counts_dev, e->ring,
+                       e->ring_len, (const int32_t*)e->st.write_pos);
+    hipLaunchKernelGGL(es_advance_kernel, dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, st, (int)e->n, m, counts_dev, e->ring_len, e->st);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+int km_emotion_stream_update(void* es, float* emotion_dev, uint8_t* valid_dev, uint8_t* updated_dev, void* stream) {
+    if (!es || !emotion_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_update: NULL argument");
+    EmotionStream* e = static_cast<EmotionStream*>(es);
+    if (!e->has_compression) return fail(KM_ERR_NOT_READY, "km_emotion_stream_update: km_emotion_stream_set_compression first");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(es_select_kernel, dim3(1), dim3(es::SEL_THREADS), 0, st, (int)e->n, (int)e->max_updates, e->ring_len, e->window_len,
+                       e->update_samples, e->min_samples, e->st, e->table, e->updated);
+    HIP_TRY(hipGetLastError());
+    if (const int rc = egm_ragged_functionals(e->plan, e->ring, e->ring_len, e->table, (int)e->max_updates, e->max_nf, e->scale, e->rec, e->fout, st))
+        return rc;
+    hipLaunchKernelGGL(es_epilogue_kernel, dim3((unsigned)e->max_updates), dim3(256), 0, st, (const EgmSlot*)e->table, (const float*)e->fout, e->st,
+                       e->features, e->slots, (const float*)e->wt, (const float*)e->bias, e->emotion);
+    hipLaunchKernelGGL(es_output_kernel, dim3((unsigned)((e->n * es::NEMO + 255) / 256)), dim3(256), 0, st, (int)e->n, (const float*)e->emotion,
+                       (const int32_t*)e->st.has_features, (const uint8_t*)e->updated, emotion_dev, valid_dev, updated_dev);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+int km_emotion_stream_reset_streams(void* es, const uint8_t* mask_dev, void* stream) {
+    if (!es) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_reset_streams: NULL argument");
+    EmotionStream* e = static_cast<EmotionStream*>(es);
+    const int bx = (e->ring_len + 256 * 8 - 1) / (256 * 8);
+    hipLaunchKernelGGL(es_reset_kernel, dim3((unsigned)(bx < 256 ? bx : 256), (unsigned)e->n), dim3(256), 0, (hipStream_t)stream, mask_dev, e->ring,
+                       e->ring_len, e->st, e->features, e->slots, e->emotion, e->updated);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+int km_emotion_stream_features(void* es, float* features_dev, float* slots_dev, void* stream) {
+    if (!es || !features_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_features: NULL argument");
+    EmotionStream* e = static_cast<EmotionStream*>(es);
+    HIP_TRY(hipMemcpyAsync(features_dev, e->features, (size_t)e->n * es::NFEAT * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (slots_dev)
+        HIP_TRY(hipMemcpyAsync(slots_dev, e->slots, (size_t)e->n * 2 * es::NFEAT * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return KM_OK;
+}
+
+}  // extern "C"

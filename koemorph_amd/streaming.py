@@ -16,6 +16,10 @@ per-stream EMA).  Neither allocates nor synchronises, so ``capture()`` records o
 the streams that popped onto a full ring, and ``reset_streams`` hands one slot to the next speaker (km_stream_fifo_create / _feed /
 _step / _reset_streams).
 
+``StreamEmotion`` keeps the emotion half of the streams on the device as well: the audio pushed into it feeds one ring per stream,
+and ``update`` runs the reference's eGeMAPS extractor state machine (src/features/opensmile_extractor.py) for all streams at once;
+its ``emotion`` matrix is what ``tick`` / ``step`` read (km_emotion_stream_*).
+
 ``LegacyStreamEngine`` is the counterpart for ``SimplifiedKoeMorphModel``: the reference's consuming FIFO
 (scripts/rt_simplified.py:46-97) per stream instead of a sliding ring, no EMA, no emotion input (km_legacy_stream_*).
 """
@@ -308,3 +312,160 @@ class LegacyStreamEngine:
             self._g_counts_full = True
         self._graph.replay()
         return self.out, self.ready
+
+
+def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 0.3, sample_rate: int = 16000) -> dict:
+    """The arithmetic of the reference's OpenSMILEeGeMAPSExtractor in samples, which km_emotion_stream_create follows: the
+    AudioBuffer of ``context_window + 2`` seconds (opensmile_extractor.py:245-248), the window ``get_window(context_window)`` returns
+    once that much audio has arrived, the samples between two updates of a stream, the half second below which nothing is extracted
+    (:388-389) and the 10 ms frames of a full window.  ValueError where km_emotion_stream_create refuses: the constructor's own
+    checks (:204-209) and a window of more than 2048 frames (20.5 s), which the functionals kernel cannot hold."""
+    if sample_rate != 16000:
+        raise ValueError("the GPU eGeMAPS extractor is built for 16 kHz audio")
+    if not context_window >= 1.0:
+        raise ValueError("Context window must be at least 1.0 seconds")
+    if not update_interval >= 0.1:
+        raise ValueError("Update interval must be at least 0.1 seconds")
+    if update_interval > context_window:
+        raise ValueError("Update interval cannot be larger than context window")
+    ring_len = int((context_window + 2.0) * sample_rate)
+    window_len = min(int(context_window * sample_rate), ring_len)
+    max_frames = (window_len - 960) // 160 + 1
+    if max_frames > 2048:
+        raise ValueError(f"{max_frames} frames per window, at most 2048 (20.5 s)")
+    return dict(ring_len=ring_len, window_len=window_len, update_samples=int(update_interval * sample_rate),
+                min_samples=int(0.5 * sample_rate), max_frames=max_frames)
+
+
+class StreamEmotion:
+    """The emotion input of ``n_streams`` streams, computed on the device from the audio pushed into it: per stream the reference's
+    ``AudioBuffer``, the update rule of ``process_audio_frame``, the three window slots and ``Linear(264, 256)``
+    (OpenSMILEeGeMAPSExtractor with ``use_concatenation=True``).  ``push`` appends audio, ``update`` re-extracts the eGeMAPS
+    functionals of every stream that is due -- at most ``max_updates`` per call, longest waiting first -- and returns the
+    ``(n_streams, 256)`` matrix ``StreamEngine.tick`` / ``ChunkedStreamEngine.step`` take.  Time is audio time: a stream is due
+    ``update_interval`` seconds *of its own samples* after its last update (the reference reads the wall clock), and a stream without
+    audio has no features (the reference would extract the zeros of an empty buffer).  Neither call allocates or synchronises.
+
+    ``compression_layer``: a ``torch.nn.Linear(264, 256)``; created with torch's default initialisation when absent, as the
+    reference does on first use (:589-591).  Its weights are copied at construction."""
+
+    def __init__(self, n_streams: int, context_window: float = 20.0, update_interval: float = 0.3, max_updates: Optional[int] = None,
+                 compression_layer: Optional[torch.nn.Module] = None, device="cuda"):
+        self.shape = emotion_stream_shape(context_window, update_interval)
+        if max_updates is None:
+            max_updates = n_streams
+        if n_streams < 1 or not 1 <= max_updates <= n_streams:
+            raise ValueError(f"expected 1 <= max_updates <= n_streams, got max_updates {max_updates}, n_streams {n_streams}")
+        if not torch.cuda.is_available():
+            raise _lib.KoeMorphError(_lib.KM_ERR_HIP, "no GPU visible: the emotion streams have no CPU fallback")
+        self.n_streams, self.max_updates = n_streams, max_updates
+        self.context_window, self.update_interval = context_window, update_interval
+        self.ring_len = self.shape["ring_len"]
+        self.device = torch.device(device if device not in (None, "cpu", "auto") else "cuda")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._lib = _lib.load()
+        if compression_layer is None:
+            compression_layer = torch.nn.Linear(264, 256)
+        if tuple(compression_layer.weight.shape) != (256, 264):
+            raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
+        self.compression_layer = compression_layer
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self._lib.km_emotion_stream_create(C.byref(self._h), n_streams, context_window, update_interval, max_updates))
+            w = compression_layer.weight.detach().to(self.device, torch.float32).contiguous()
+            b = compression_layer.bias.detach().to(self.device, torch.float32).contiguous()
+            check(self._lib.km_emotion_stream_set_compression(self._h, _ptr(w), _ptr(b), _stream_ptr(self.device)))
+            torch.cuda.current_stream(self.device).synchronize()          # w and b may go once the copy is done
+        self.emotion = torch.zeros(n_streams, 256, device=self.device)
+        self.valid = torch.zeros(n_streams, dtype=torch.uint8, device=self.device)
+        self.updated = torch.zeros(n_streams, dtype=torch.uint8, device=self.device)
+        self._graph = None
+        self._g_samples = self._g_counts = None
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.km_emotion_stream_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, samples: torch.Tensor, counts: Optional[torch.Tensor] = None) -> None:
+        """samples (n_streams, n) fp32 on the device, n at most the ring; counts (n_streams) int32 on the device: how many of the
+        n samples each stream brings (default: all).  A stream that brings none is untouched."""
+        if samples.dim() != 2 or samples.shape[0] != self.n_streams or samples.dtype != torch.float32:
+            raise ValueError(f"expected ({self.n_streams}, n) float32 samples, got {tuple(samples.shape)} {samples.dtype}")
+        if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (self.n_streams,)):
+            raise ValueError(f"expected ({self.n_streams},) int32 counts")
+        samples = samples.contiguous()
+        check(self._lib.km_emotion_stream_push(self._h, _ptr(samples), samples.shape[1],
+                                               _ptr(counts.contiguous()) if counts is not None else None, _stream_ptr(samples.device)))
+
+    def update(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (emotion (n_streams, 256), updated (n_streams) uint8); ``valid`` says which streams have features at all.  Rows of
+        streams that were not selected keep what they held; a stream that never had features has a zero row."""
+        check(self._lib.km_emotion_stream_update(self._h, _ptr(self.emotion), _ptr(self.valid), _ptr(self.updated),
+                                                 _stream_ptr(self.device)))
+        return self.emotion, self.updated
+
+    @property
+    def features(self) -> torch.Tensor:
+        """(n_streams, 88): every stream's current eGeMAPS functionals (zero before its first update); a copy."""
+        out = torch.empty(self.n_streams, 88, device=self.device)
+        check(self._lib.km_emotion_stream_features(self._h, _ptr(out), None, _stream_ptr(self.device)))
+        return out
+
+    @property
+    def slots(self) -> torch.Tensor:
+        """(n_streams, 2, 88): the 300 ms and 600 ms window slots, i.e. the first features of each stream's current life; a copy."""
+        feats = torch.empty(self.n_streams, 88, device=self.device)
+        out = torch.empty(self.n_streams, 2, 88, device=self.device)
+        check(self._lib.km_emotion_stream_features(self._h, _ptr(feats), _ptr(out), _stream_ptr(self.device)))
+        return out
+
+    def reset_streams(self, mask: torch.Tensor) -> None:
+        """mask (n_streams) bool or uint8 on the device: those streams become freshly created ones (OpenSMILEeGeMAPSExtractor.reset
+        :640-659: empty ring, no features, empty slots, a zero row of ``emotion``); the others are untouched.  No synchronisation."""
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (self.n_streams,):
+            raise ValueError(f"expected a ({self.n_streams},) bool or uint8 mask")
+        m8 = mask.to(self.device, torch.uint8).contiguous()
+        check(self._lib.km_emotion_stream_reset_streams(self._h, _ptr(m8), _stream_ptr(self.device)))
+        gone = m8 != 0
+        self.emotion.masked_fill_(gone.unsqueeze(1), 0.0)
+        for flags in (self.valid, self.updated):
+            flags.masked_fill_(gone, 0)
+
+    def reset(self) -> None:
+        check(self._lib.km_emotion_stream_reset_streams(self._h, None, _stream_ptr(self.device)))
+        self.emotion.zero_()
+        self.valid.zero_()
+        self.updated.zero_()
+
+    # ---- hipGraph replay ------------------------------------------------------------------------
+    def capture(self, n_per_stream: int) -> None:
+        """Record push (with per-stream counts) + update on static input buffers into a hipGraph: one linear chain."""
+        dev = self.device
+        self._g_samples = torch.zeros(self.n_streams, n_per_stream, device=dev)
+        self._g_counts = torch.zeros(self.n_streams, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.push(self._g_samples, self._g_counts)
+            self.update()
+        self._graph = g
+
+    def replay(self, samples: torch.Tensor, counts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One captured push + update; counts None: every stream brings all ``n_per_stream`` samples."""
+        if self._graph is None:
+            raise RuntimeError("capture() first")
+        self._g_samples.copy_(samples, non_blocking=True)
+        if counts is not None:
+            self._g_counts.copy_(counts, non_blocking=True)
+        else:
+            self._g_counts.fill_(self._g_samples.shape[1])
+        self._graph.replay()
+        return self.emotion, self.updated
