@@ -674,6 +674,37 @@ int km_emotion_stream_update(void* es, float* emotion_dev, uint8_t* valid_dev, u
 int km_emotion_stream_reset_streams(void* es, const uint8_t* mask_dev, void* stream);
 int km_emotion_stream_features(void* es, float* features_dev, float* slots_dev, void* stream);
 
+/* ---- the emotion track of a resident clip: the offline producer of the model's emotion input ---------------------
+ * What ONE emotion stream (above) holds after t samples of a clip, for every update time at once.  With SR, R, C, U and MIN as
+ * km_emotion_stream_create computes them, a clip of n samples has K rows: K = 0 if n < MIN, else (n - MIN) / U + 1.  Row k
+ * belongs to audio time t_k = MIN + k U; its window is what the stream's AudioBuffer returns after t_k samples, the quirk
+ * included: [0, min(t_k, C)) while t_k < R, [t_k - C, t_k) from t_k >= R on -- the updates of a stream fed the clip in chunks of
+ * gcd(MIN, U) samples with an update after every push.  features[k] = the 88 functionals of that window, peak-normalised,
+ * NaN / +-Inf -> 0, by the kernels the streams run (the clip is read in place); emotion[k] = W concat(features[k], features[0],
+ * features[0]) + b: the 300 / 600 ms slots are filled once per life and a clip is one life.  A training window that starts at
+ * frame s, with T frames of hop h, ends at e = min(n, (s + T) h); its row is clamp((e - MIN) / U, 0, K - 1), the last update a
+ * live stream would have made by then (the first one for a window that ends before it).
+ *   km_emotion_clip_create           validates like km_emotion_stream_create; 1 <= max_slots <= 65535 windows are extracted per
+ *                                    pass.  Allocates everything (slot table, scales, max_slots x frames x 36 records,
+ *                                    max_slots x 88 functionals, the weights)
+ *   km_emotion_clip_set_compression  w_dev (256, 264) as nn.Linear stores it, b_dev (256); copied
+ *   km_emotion_clip_num_rows         K of a clip of clip_len samples (host arithmetic; 0 for a NULL object)
+ *   km_emotion_clip_build            clip_dev (clip_len) -> features_out (K, 88) or NULL, emotion_out (K, 256), in
+ *                                    ceil(K / max_slots) passes.  K = 0: nothing is launched, KM_OK.  clip_len > 2^30 (window
+ *                                    starts are 32-bit): KM_ERR_INVALID_ARG.  KM_ERR_NOT_READY before set_compression
+ *   km_emotion_clip_rows             emotion_track_dev (K, 256) of a clip of clip_len samples (K must be its num_rows),
+ *                                    start_frames_dev (B) int32 -> emotion_out (B, 256), valid_out (B) u8 or NULL.  K = 0:
+ *                                    zero rows, valid 0, as a stream without features
+ * build and rows never allocate, synchronise or read back; the launch shape of rows depends on B alone, so it can sit inside a
+ * captured training step. */
+int km_emotion_clip_create(void** ec, double context_window_s, double update_interval_s, int64_t max_slots);
+int km_emotion_clip_destroy(void* ec);
+int km_emotion_clip_set_compression(void* ec, const float* w_dev, const float* b_dev, void* stream);
+int64_t km_emotion_clip_num_rows(void* ec, int64_t clip_len);
+int km_emotion_clip_build(void* ec, const float* clip_dev, int64_t clip_len, float* features_out, float* emotion_out, void* stream);
+int km_emotion_clip_rows(void* ec, const float* emotion_track_dev, int64_t K, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
+                         int64_t hop, int64_t window_frames, float* emotion_out, uint8_t* valid_out, void* stream);
+
 /* ---- evaluation metrics: a streaming accumulator in device memory ------------------------------------------------
  * Replaces BlendshapeMetrics (src/model/losses.py:421-521) and compute_lip_sync_metrics (:524-583).  The reference
  * copies every batch to the host, concatenates the epoch and reduces it there; here (N, 52) rows are folded into a

@@ -196,6 +196,12 @@ SIGNATURES = {
     "km_emotion_stream_update": (C.c_int, [_p, _p, _p, _p, _p]),
     "km_emotion_stream_reset_streams": (C.c_int, [_p, _p, _p]),
     "km_emotion_stream_features": (C.c_int, [_p, _p, _p, _p]),
+    "km_emotion_clip_create": (C.c_int, [C.POINTER(_p), C.c_double, C.c_double, _i64]),
+    "km_emotion_clip_destroy": (C.c_int, [_p]),
+    "km_emotion_clip_set_compression": (C.c_int, [_p, _p, _p, _p]),
+    "km_emotion_clip_num_rows": (_i64, [_p, _i64]),
+    "km_emotion_clip_build": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
+    "km_emotion_clip_rows": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p]),
     "km_enable_stage_timing": (C.c_int, [_h, _i32]),
     "km_stage_times": (C.c_int, [_h, C.POINTER(C.c_float)]),
     "km_debug_buffer": (C.c_int, [_h, C.c_char_p, _p, C.POINTER(_i64)]),

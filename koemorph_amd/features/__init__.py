@@ -6,3 +6,6 @@ __all__ = ["MelSpectrogramExtractor", "MelAudioBuffer", "MelSlidingWindowExtract
 from .opensmile_extractor import AudioBuffer, OpenSMILEeGeMAPSExtractor, create_opensmile_extractor  # noqa: E402
 
 __all__ += ["AudioBuffer", "OpenSMILEeGeMAPSExtractor", "create_opensmile_extractor"]
+from .clip_emotion import ClipEmotion  # noqa: E402
+
+__all__ += ["ClipEmotion"]

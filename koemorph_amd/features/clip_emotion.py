@@ -1,0 +1,126 @@
+"""The emotion track of a resident clip (km_emotion_clip_*): the offline producer of the model's 256-D emotion input.
+
+A window's emotion vector is what a live ``StreamEmotion`` stream would hold at the moment the window ends -- a function of the
+clip and an audio time, not of the window.  Updates are ``update_interval`` apart (0.3 s) and windows 33 ms, so about nine
+windows share a row: ``build`` extracts the clip's track once, with the kernels the streams run, and a training step gathers
+rows from it by start frame (``rows``), which reads no audio and so keeps the step on the resident clip.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Hashable, Optional, Tuple
+
+import torch
+
+from .. import _lib
+from .._lib import check
+from ..engine import _ptr, _stream_ptr
+from ..streaming import emotion_stream_shape
+
+
+class ClipEmotion:
+    """``build(clip)`` -> the clip's emotion track ``(K, 256)`` and its eGeMAPS functionals ``(K, 88)``: row ``k`` is what one
+    ``StreamEmotion(1, context_window, update_interval)`` stream holds after ``min_samples + k * update_samples`` samples of the
+    clip (pushed in chunks of ``gcd(min_samples, update_samples)`` with an update after each).  ``rows`` maps windows to rows:
+    a window that starts at frame ``s`` with ``T`` frames of hop ``h`` ends at ``e = min(n, (s + T) h)`` and takes row
+    ``clamp((e - min_samples) // update_samples, 0, K - 1)``; a clip shorter than half a second has no rows and every window of it
+    a zero vector.  ``max_slots`` windows are extracted per pass (scratch: ``max_slots`` x frames x 36 floats of frame records).
+
+    ``compression_layer``: ``StreamEmotion``'s contract -- a ``torch.nn.Linear(264, 256)``, created with torch's default
+    initialisation when absent, copied at construction; hand the same layer to the server's ``StreamEmotion``.
+    ``track_for(key, clip)`` keeps built tracks on the device: the layer is fixed, so a clip is extracted once per run."""
+
+    def __init__(self, context_window: float = 20.0, update_interval: float = 0.3, max_slots: int = 64,
+                 compression_layer: Optional[torch.nn.Module] = None, device="cuda"):
+        self.shape = emotion_stream_shape(context_window, update_interval)
+        if not 1 <= max_slots <= 65535:
+            raise ValueError(f"expected 1 <= max_slots <= 65535, got {max_slots}")
+        if not torch.cuda.is_available():
+            raise _lib.KoeMorphError(_lib.KM_ERR_HIP, "no GPU visible: the clip emotion track has no CPU fallback")
+        self.context_window, self.update_interval, self.max_slots = context_window, update_interval, max_slots
+        self.device = torch.device(device if device not in (None, "cpu", "auto") else "cuda")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._lib = _lib.load()
+        if compression_layer is None:
+            compression_layer = torch.nn.Linear(264, 256)
+        if tuple(compression_layer.weight.shape) != (256, 264):
+            raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
+        self.compression_layer = compression_layer
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self._lib.km_emotion_clip_create(C.byref(self._h), context_window, update_interval, max_slots))
+            w = compression_layer.weight.detach().to(self.device, torch.float32).contiguous()
+            b = compression_layer.bias.detach().to(self.device, torch.float32).contiguous()
+            check(self._lib.km_emotion_clip_set_compression(self._h, _ptr(w), _ptr(b), _stream_ptr(self.device)))
+            torch.cuda.current_stream(self.device).synchronize()          # w and b may go once the copy is done
+        self._tracks: Dict[Hashable, Tuple[torch.Tensor, int]] = {}
+        self.builds = 0                                                   # calls of build(), track_for's misses included
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.km_emotion_clip_destroy(self._h)
+            self._h = C.c_void_p()
+        self._tracks = {}
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def num_rows(self, clip_len: int) -> int:
+        return int(self._lib.km_emotion_clip_num_rows(self._h, int(clip_len)))
+
+    def _check_clip(self, clip: torch.Tensor) -> torch.Tensor:
+        if clip.dim() != 1 or clip.dtype != torch.float32 or not clip.is_cuda:
+            raise ValueError(f"expected a 1-D float32 clip on the device, got {tuple(clip.shape)} {clip.dtype} on {clip.device}")
+        return clip.contiguous()
+
+    def build(self, clip: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """clip (n) fp32 on the device -> (emotion (K, 256), features (K, 88)).  No synchronisation."""
+        clip = self._check_clip(clip)
+        n = clip.shape[0]
+        K = self.num_rows(n)
+        emotion = torch.empty(K, 256, device=clip.device)
+        features = torch.empty(K, 88, device=clip.device)
+        with torch.cuda.device(clip.device):
+            check(self._lib.km_emotion_clip_build(self._h, _ptr(clip), n, _ptr(features), _ptr(emotion), _stream_ptr(clip.device)))
+        self.builds += 1
+        return emotion, features
+
+    def rows(self, track: torch.Tensor, clip_len: int, start_frames_dev: torch.Tensor, hop: int, window_frames: int,
+             out: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """track (K, 256) of a clip of ``clip_len`` samples, start_frames_dev (B) int32 on the device -> (B, 256): every window's
+        row.  ``out`` (B, 256) fp32 and ``valid`` (B) uint8 are written in place when given (static buffers of a captured step);
+        ``valid`` is 1 where the clip has a track at all.  One gather kernel, no synchronisation."""
+        if start_frames_dev.dim() != 1 or start_frames_dev.dtype != torch.int32 or not start_frames_dev.is_cuda:
+            raise ValueError("expected (B,) int32 start frames on the device")
+        if track.dim() != 2 or track.shape[1] != 256 or track.dtype != torch.float32:
+            raise ValueError(f"expected a (K, 256) float32 track, got {tuple(track.shape)} {track.dtype}")
+        B = start_frames_dev.shape[0]
+        dev = start_frames_dev.device
+        if out is None:
+            out = torch.empty(B, 256, device=dev)
+        elif tuple(out.shape) != (B, 256) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"expected a contiguous ({B}, 256) float32 out")
+        if valid is not None and (tuple(valid.shape) != (B,) or valid.dtype != torch.uint8):
+            raise ValueError(f"expected a ({B},) uint8 valid")
+        track, starts = track.contiguous(), start_frames_dev.contiguous()
+        with torch.cuda.device(dev):
+            check(self._lib.km_emotion_clip_rows(self._h, _ptr(track) if track.shape[0] else None, track.shape[0], int(clip_len), _ptr(starts),
+                                                 B, int(hop), int(window_frames), _ptr(out), _ptr(valid) if valid is not None else None,
+                                                 _stream_ptr(dev)))
+        return out
+
+    def track_for(self, key: Hashable, clip: torch.Tensor) -> torch.Tensor:
+        """The emotion track of ``clip``, built on first use and kept on the device under ``key`` (the data set's file index)."""
+        hit = self._tracks.get(key)
+        if hit is not None and hit[1] == clip.shape[0]:
+            return hit[0]
+        track, _ = self.build(clip)
+        self._tracks[key] = (track, clip.shape[0])
+        return track
+
+    def clear(self) -> None:
+        self._tracks = {}

@@ -10,7 +10,9 @@ the HIP training step behind the C-ABI (``koemorph_amd.training.Trainer``).  Dat
 
 The reference's ``MultiTaskLoss`` does not exist in its ``src/model/losses.py``; the loss here is ``KoeMorphLoss``
 (mse + optional terms, src/model/losses.py:29-178) against the label of each window's last frame.  The 256-D emotion
-vector is an input of the model: ``emotion_provider(audio) -> (B, 256)``; without one the reference's own failure
+vector is an input of the model: a ``ClipEmotion`` (``--emotion egemaps``) gives every window the row of its clip's eGeMAPS
+emotion track that a live stream would hold when the window ends, gathered by start frame, so the step stays on the resident
+clip; ``emotion_provider(audio) -> (B, 256)`` is handed window audio instead; without either the reference's own failure
 fallback is used (``randn * 0.1``, simplified_dual_stream_model.py:250-267), seeded per window for reproducibility.
 No hydra / TensorBoard dependency: plain argparse, metrics to the log.
 """
@@ -27,7 +29,9 @@ import torch
 
 from .. import parallel, synth
 from ..data import SequentialKoeMorphDataset
+from .._lib import KM_ERR_INVALID_ARG, KoeMorphError
 from ..engine import Engine
+from ..features.clip_emotion import ClipEmotion
 from ..metrics import BlendshapeMetrics, LossTerms
 from ..training import Trainer
 
@@ -39,17 +43,23 @@ class SequentialTrainer:
                  device: str = "cuda", learning_rate: float = 1e-4, weight_decay: float = 1e-5, gradient_clip: float = 1.0,
                  mse_weight: float = 1.0, l1_weight: float = 0.0, extra_loss_terms: Optional[Dict[str, float]] = None,
                  emotion_provider: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, dropout: float = 0.1, seed: int = 0,
-                 from_clip: bool = False):
+                 from_clip: bool = False, clip_emotion: Optional[ClipEmotion] = None):
         """``from_clip``: batches that name their windows inside the resident clip (``resident_windows=True`` data sets) go
         through ``Trainer.step_clip`` -- no window copy, shared STFT frames; same losses and weights, bit for bit.  An
         ``emotion_provider`` is handed window audio, so with one installed the trainer stays on the gathered path.
+        ``clip_emotion``: the emotion rows come from each clip's emotion track (built once per clip and kept on the device),
+        gathered by start frame; it reads no window audio, so ``step_clip`` / ``forward_clip`` stay in use.  It needs batches that
+        name their clip (``resident_windows=True``) and excludes an ``emotion_provider``.
         ``dropout``: the reference trains under ``model.train()`` (src/train_sequential.py:118) on a model built with
         dropout 0.1 (simplified_dual_stream_model.py:155): the attention weights of both streams and the decoder's hidden
         layer are dropped per step; ``validate()`` runs the eval-mode inference kernels.  Every rank draws its own masks
         (generator seed = ``seed`` + rank); the generator's step counter is part of the checkpoint."""
         self.engine, self.device = engine, torch.device(device)
         self.train_data, self.val_data = train_data, val_data
+        if clip_emotion is not None and emotion_provider is not None:
+            raise ValueError("clip_emotion and emotion_provider both produce the emotion input: pass one of them")
         self.emotion_provider = emotion_provider
+        self.clip_emotion = clip_emotion
         self.from_clip = from_clip
         self._from_clip_logged = False
         self.rank, self.world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) \
@@ -70,6 +80,13 @@ class SequentialTrainer:
 
     # ---- helpers ----------------------------------------------------------------------------------------
     def _emotion(self, batch) -> torch.Tensor:
+        if self.clip_emotion is not None:
+            if "clip_audio" not in batch or "start_frames_dev" not in batch:
+                raise KoeMorphError(KM_ERR_INVALID_ARG, "clip_emotion reads the resident clip: build the data set with resident_windows=True")
+            ce, ds, clip = self.clip_emotion, self.train_data, batch["clip_audio"]
+            # keyed by file index and by where the clip lies: the training and validation sets number their files alike
+            track = ce.track_for((int(batch["file_indices"][0]), clip.data_ptr()), clip)
+            return ce.rows(track, clip.shape[0], batch["start_frames_dev"], ds.hop_length, ds.window_frames)
         if self.emotion_provider is not None:
             return self.emotion_provider(batch["audio"]).to(self.device, torch.float32)
         rows = [0.1 * synth.normal(1000003 * int(f) + int(w), (256,)) for f, w in zip(batch["file_indices"], batch["window_indices"])]
@@ -323,6 +340,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loss-components", dest="loss_components", action="store_true",
                    help="validation reports the loss by component (LossTerms) and per-sequence loss / smoothness; with "
                         "--resident-clip the validation forward runs from the resident clip (Engine.forward_clip)")
+    p.add_argument("--emotion", choices=("noise", "egemaps"), default="noise",
+                   help="the model's emotion input: noise = the reference's extraction-failure fallback (randn * 0.1 per window); "
+                        "egemaps = each clip's eGeMAPS emotion track, computed once on the device and gathered by start frame "
+                        "(ClipEmotion; implies resident batches, what a StreamEmotion serves at inference)")
     p.add_argument("--metrics", action="store_true", help="log mae / rmse / mean_correlation / f1_score of every epoch (BlendshapeMetrics)")
     return p
 
@@ -338,11 +359,13 @@ def main(argv=None):
     eng.finalize(device)
     kw = dict(window_frames=args.window_frames, stride_frames=args.stride_frames, shuffle_files=False, loop_dataset=False,
               batch_size=args.batch_size, device=device, max_files=args.max_files)
-    train = SequentialKoeMorphDataset(args.data_dir, resident_windows=args.resident_clip, **kw)
-    val = SequentialKoeMorphDataset(args.val_dir, resident_windows=args.resident_clip and args.loss_components, **kw) if args.val_dir else None
+    egemaps = args.emotion == "egemaps"                  # the track is read from the resident clip: every batch must name it
+    train = SequentialKoeMorphDataset(args.data_dir, resident_windows=args.resident_clip or egemaps, **kw)
+    val = SequentialKoeMorphDataset(args.val_dir, resident_windows=(args.resident_clip and args.loss_components) or egemaps, **kw) \
+        if args.val_dir else None
     st = SequentialTrainer(eng, train, val, device=device, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
                            gradient_clip=args.gradient_clip, l1_weight=args.l1_weight, dropout=args.dropout, seed=args.seed,
-                           from_clip=args.resident_clip)
+                           from_clip=args.resident_clip, clip_emotion=ClipEmotion(device=device) if egemaps else None)
     if args.resume:
         st.load_checkpoint(args.resume)
     for _ in range(st.epoch, args.epochs):
