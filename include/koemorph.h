@@ -233,6 +233,24 @@ int km_ema_scan(km_handle h, float* x_dev, int64_t B, int64_t N, void* stream);
 int km_sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t L,
                         const float* emotion_dev, int32_t stride_frames, int32_t smooth,
                         float* out_dev, void* stream);
+/* km_sequence_forward with a per-window emotion input taken from a TRACK per clip: track_dev (B, K, emotion_dim), e.g. the
+ * emotion output of km_emotion_clip_build_batch.  It is km_sequence_forward in every respect (schedule, tiles, bit-identical
+ * shared-frame and per-window paths, smoothing, growth rules) except where a window's emotion logit comes from.  Output frame i of
+ * clip c ends, in clip coordinates, at e = min(clip_len, sample_offset + (i * stride_frames + T) * hop) and takes row
+ * k = e < first_samples ? 0 : min((e - first_samples) / interval_samples, K - 1) of the clip's track.  With sample_offset = 0,
+ * clip_len = L, first_samples = MIN and interval_samples = U of the emotion clip object this is km_emotion_clip_rows' mapping for
+ * start frame i * stride_frames; sample_offset / clip_len let a chunk audio[:, s0 : s0 + L] of a clip of clip_len samples map as
+ * the whole clip does (frames computed in chunks on several GPUs); first_samples = T * hop with interval_samples =
+ * stride_frames * hop is the identity map, one row per window, for callers who bring their own per-window emotion.
+ * The emotion branch runs ONCE per track row (B * K rows, not B * N windows: windows are 33 ms apart and rows 0.3 s), one small
+ * kernel writes a logit per window from the closed form (no audio is read and no table comes from the host) and the core
+ * launches read it.  KM_ERR_INVALID_ARG: K < 1, interval_samples < 1, negative first_samples or sample_offset,
+ * clip_len < sample_offset + L, B * K beyond 2^31 - 1.  Two more grow-only buffers (B * K and B * N floats), allocated before the
+ * first launch; the call neither synchronises nor reads back. */
+int km_sequence_forward_track(km_handle h, const float* audio_dev, int64_t B, int64_t L,
+                              const float* track_dev, int64_t K, int64_t first_samples, int64_t interval_samples,
+                              int64_t sample_offset, int64_t clip_len, int32_t stride_frames, int32_t smooth,
+                              float* out_dev, void* stream);
 
 /* ---- training step (data-parallel ready) -------------------------------------------------------------
  * Replaces the body of SequentialTrainer.train_epoch (src/train_sequential.py:158-181: forward, loss,
@@ -695,13 +713,22 @@ int km_emotion_stream_features(void* es, float* features_dev, float* slots_dev, 
  *   km_emotion_clip_rows             emotion_track_dev (K, 256) of a clip of clip_len samples (K must be its num_rows),
  *                                    start_frames_dev (B) int32 -> emotion_out (B, 256), valid_out (B) u8 or NULL.  K = 0:
  *                                    zero rows, valid 0, as a stream without features
- * build and rows never allocate, synchronise or read back; the launch shape of rows depends on B alone, so it can sit inside a
+ *   km_emotion_clip_build_batch      clips_dev (B, L), B clips of ONE length -> features_out (B, K, 88), emotion_out (B, K, 256),
+ *                                    each clip's slice bit-identical to km_emotion_clip_build of that clip.  Rows are numbered
+ *                                    g = c K + k and a pass takes max_slots consecutive g, so passes are filled across clip
+ *                                    boundaries: ceil(B K / max_slots) of them.  A row is compressed with features[0] of its OWN
+ *                                    clip: from the pass itself when row (c, 0) lies in it, else from features_out[c, 0] that
+ *                                    an earlier pass wrote -- which is why features_out is REQUIRED here.  K = 0 or B = 0:
+ *                                    nothing is launched.  L > 2^30 or B K > 2^31 - 1: KM_ERR_INVALID_ARG
+ * build, build_batch and rows never allocate, synchronise or read back; the launch shape of rows depends on B alone, so it can sit inside a
  * captured training step. */
 int km_emotion_clip_create(void** ec, double context_window_s, double update_interval_s, int64_t max_slots);
 int km_emotion_clip_destroy(void* ec);
 int km_emotion_clip_set_compression(void* ec, const float* w_dev, const float* b_dev, void* stream);
 int64_t km_emotion_clip_num_rows(void* ec, int64_t clip_len);
 int km_emotion_clip_build(void* ec, const float* clip_dev, int64_t clip_len, float* features_out, float* emotion_out, void* stream);
+int km_emotion_clip_build_batch(void* ec, const float* clips_dev, int64_t B, int64_t L, float* features_out, float* emotion_out,
+                                void* stream);
 int km_emotion_clip_rows(void* ec, const float* emotion_track_dev, int64_t K, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
                          int64_t hop, int64_t window_frames, float* emotion_out, uint8_t* valid_out, void* stream);
 

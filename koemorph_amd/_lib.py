@@ -107,6 +107,7 @@ SIGNATURES = {
     "km_pipeline_flush": (C.c_int, [_h, _p]),
     "km_sequence_num_outputs": (_i64, [_h, _i64, _i32]),
     "km_sequence_forward": (C.c_int, [_h, _p, _i64, _i64, _p, _i32, _i32, _p, _p]),
+    "km_sequence_forward_track": (C.c_int, [_h, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _p]),
     "km_ema_scan": (C.c_int, [_h, _p, _i64, _i64, _p]),
     "km_train_init": (C.c_int, [_h, _i64, _p]),
     "km_train_num_params": (_i64, [_h]),
@@ -201,6 +202,7 @@ SIGNATURES = {
     "km_emotion_clip_set_compression": (C.c_int, [_p, _p, _p, _p]),
     "km_emotion_clip_num_rows": (_i64, [_p, _i64]),
     "km_emotion_clip_build": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
+    "km_emotion_clip_build_batch": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p]),
     "km_emotion_clip_rows": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p]),
     "km_enable_stage_timing": (C.c_int, [_h, _i32]),
     "km_stage_times": (C.c_int, [_h, C.POINTER(C.c_float)]),

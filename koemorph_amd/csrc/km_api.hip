@@ -137,7 +137,7 @@ int km_destroy(km_handle h) {
     (void)free_legacy_streams(c);
     (void)free_train(c);
     (void)free_pipeline(c);
-    for (void* q : {(void*)c->seq_pow, (void*)c->seq_fmax, (void*)c->seq_edge, (void*)c->seq_emax, (void*)c->fwd_span, (void*)c->fwd_edge})
+    for (void* q : {(void*)c->seq_pow, (void*)c->seq_fmax, (void*)c->seq_edge, (void*)c->seq_emax, (void*)c->seq_ztrack, (void*)c->seq_zwin, (void*)c->fwd_span, (void*)c->fwd_edge})
         if (q) (void)hipFree(q);
     if (c->pipe_s1) {
         (void)hipStreamDestroy((hipStream_t)c->pipe_s1); (void)hipStreamDestroy((hipStream_t)c->pipe_s2);
@@ -1295,12 +1295,13 @@ int64_t km_sequence_num_outputs(km_handle h, int64_t L, int32_t stride_frames) {
     return nn > 1 ? nn : 1;
 }
 
-int km_sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
-                        int32_t stride_frames, int32_t smooth, float* out_dev, void* stream) {
-    if (int rc = need_dual(h)) return rc;
+// Where a window's emotion logit comes from in km_sequence_forward_track: the rows of every clip's track and the closed-form
+// window -> row map (SeqTrackMap).  Null: one vector per clip (km_sequence_forward).
+struct SeqTrack { const float* track; int64_t K, first, interval, sample_offset, clip_len; };
+
+static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev, const SeqTrack* trk,
+                            int32_t stride_frames, int32_t smooth, float* out_dev, void* stream) {
     Context* c = h;
-    if (!audio_dev || !emotion_dev || !out_dev || B <= 0 || L <= 0 || stride_frames <= 0)
-        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward: bad argument");
     if (!c->fused_ok && !c->ws_generic)
         return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
     const int hop = c->cfg.mel.hop_length;
@@ -1328,8 +1329,21 @@ int km_sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t 
         if (int rc = grow_buffer(&c->seq_edge, &c->seq_edge_cap, total, 2 * c->NK * sizeof(float), stream, what)) return rc;
         if (int rc = grow_buffer(&c->seq_emax, &c->seq_emax_cap, total, 2 * sizeof(unsigned), stream, what)) return rc;
     }
-    // emotion features ONCE for the entire audio (:88): one logit per clip
-    if (int rc = launch_emotion(c, emotion_dev, B, c->ws_zemo, stream)) return rc;
+    const float* zemo = c->ws_zemo;
+    if (trk) {
+        // a logit per track ROW (about nine windows share one), then one per window by the closed-form map: the core launches
+        // below read zwin[win0 + b]
+        const char* what = "km_sequence_forward_track: track rows / windows";
+        if (int rc = grow_buffer(&c->seq_ztrack, &c->seq_ztrack_cap, B * trk->K, sizeof(float), stream, what)) return rc;
+        if (int rc = grow_buffer(&c->seq_zwin, &c->seq_zwin_cap, total, sizeof(float), stream, what)) return rc;
+        if (int rc = launch_emotion(c, trk->track, B * trk->K, c->seq_ztrack, stream)) return rc;
+        const SeqTrackMap map{trk->K, trk->first, trk->interval, trk->sample_offset, trk->clip_len, step, W};
+        if (int rc = launch_seq_track_logits(c, c->seq_ztrack, c->seq_zwin, total, (int)N, map, stream)) return rc;
+        zemo = c->seq_zwin;
+    } else {
+        // emotion features ONCE for the entire audio (:88): one logit per clip
+        if (int rc = launch_emotion(c, emotion_dev, B, c->ws_zemo, stream)) return rc;
+    }
     if (shared) {
         hipStream_t st = (hipStream_t)stream;
         HIP_TRY(hipMemsetAsync(c->seq_fmax, 0, (size_t)B * nfc * sizeof(unsigned), st));
@@ -1346,7 +1360,8 @@ int km_sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t 
             const int64_t nw = (total - w0) < tile ? (total - w0) : tile;
             if (int rc = launch_seq_window_max(c, c->seq_fmax, c->seq_emax, nw, w0, (int)nfc, (int)stride_frames, (int)N,
                                                (int)n_frames, stream)) return rc;
-            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, c->ws_zemo, out_dev + w0 * c->NB, stream, core_strided(&sc, w0))) return rc;
+            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
+                                              trk ? core_strided_win(&sc, w0) : core_strided(&sc, w0))) return rc;
         }
         if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
         return KM_OK;
@@ -1356,17 +1371,45 @@ int km_sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t 
         const MelSrc src = mel_clip_windows(audio_dev, L, nw, W, step, w0, (int)N);
         if (c->fused_ok) {
             if (int rc = launch_mel_power(c, plan, src, stream)) return rc;
-            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, c->ws_zemo, out_dev + w0 * c->NB, stream, core_workspace_seq(w0, (int)N))) return rc;
+            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
+                                              trk ? core_workspace_seq_win(w0) : core_workspace_seq(w0, (int)N))) return rc;
         } else {
             // generic shapes: staged log-mel, per-window logits gathered from the per-clip ones, GEMM-chain core
             if (int rc = launch_mel(c, plan, src, 0, c->ws_mel, c->ws_short, stream)) return rc;
-            if (int rc = launch_gather_clip_logits(c, c->ws_zemo, c->ws_zemo_win, nw, w0, (int)N, stream)) return rc;
-            if (int rc = launch_core_generic(c, c->ws_mel, nw, n_frames, c->ws_short, c->ws_zemo_win, out_dev + w0 * c->NB,
+            if (!trk)
+                if (int rc = launch_gather_clip_logits(c, c->ws_zemo, c->ws_zemo_win, nw, w0, (int)N, stream)) return rc;
+            if (int rc = launch_core_generic(c, c->ws_mel, nw, n_frames, c->ws_short, trk ? zemo + w0 : c->ws_zemo_win, out_dev + w0 * c->NB,
                                              nullptr, nullptr, stream)) return rc;
         }
     }
     if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
     return KM_OK;
+}
+
+int km_sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
+                        int32_t stride_frames, int32_t smooth, float* out_dev, void* stream) {
+    if (int rc = need_dual(h)) return rc;
+    if (!audio_dev || !emotion_dev || !out_dev || B <= 0 || L <= 0 || stride_frames <= 0)
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward: bad argument");
+    return sequence_forward(h, audio_dev, B, L, emotion_dev, nullptr, stride_frames, smooth, out_dev, stream);
+}
+
+int km_sequence_forward_track(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* track_dev, int64_t K,
+                              int64_t first_samples, int64_t interval_samples, int64_t sample_offset, int64_t clip_len,
+                              int32_t stride_frames, int32_t smooth, float* out_dev, void* stream) {
+    // the argument checks need no handle state and come first: they hold on a handle that is not finalized yet
+    if (!h || !audio_dev || !track_dev || !out_dev || B <= 0 || L <= 0 || stride_frames <= 0)
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_track: bad argument");
+    const int64_t lim = (int64_t)1 << 62;                  // keeps sample_offset + (window index) * step + window inside int64
+    if (K < 1 || interval_samples < 1 || first_samples < 0 || sample_offset < 0 || clip_len > lim || clip_len < L ||
+        clip_len - L < sample_offset)
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_track: K %lld, first %lld, interval %lld, offset %lld, clip_len %lld for a chunk of %lld",
+                    (long long)K, (long long)first_samples, (long long)interval_samples, (long long)sample_offset, (long long)clip_len,
+                    (long long)L);
+    if (K > 0x7fffffff / B) return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_track: %lld x %lld track rows, at most 2^31 - 1", (long long)B, (long long)K);
+    if (int rc = need_dual(h)) return rc;
+    const SeqTrack trk{track_dev, K, first_samples, interval_samples, sample_offset, clip_len};
+    return sequence_forward(h, audio_dev, B, L, nullptr, &trk, stride_frames, smooth, out_dev, stream);
 }
 
 }  // extern "C"

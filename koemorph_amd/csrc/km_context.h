@@ -195,6 +195,9 @@ struct Context {
     // shared-frame sequence mode buffers (grow-only, allocated by km_sequence_forward)
     float* seq_pow = nullptr; unsigned* seq_fmax = nullptr; float* seq_edge = nullptr; unsigned* seq_emax = nullptr;
     int64_t seq_pow_cap = 0, seq_fmax_cap = 0, seq_edge_cap = 0, seq_emax_cap = 0;
+    // km_sequence_forward_track: the logits of the track's rows (clips * K) and of the sequence's windows (clips * N), grow-only
+    float* seq_ztrack = nullptr; float* seq_zwin = nullptr;
+    int64_t seq_ztrack_cap = 0, seq_zwin_cap = 0;
     // eval-mode forward from a resident clip (km_forward_clip): the span image (rows, NK) and the edge image (windows, 2, NK) of
     // launch_mel_clip_span, owned by the inference context (no km_train_init needed), grow-only
     float* fwd_span = nullptr; float* fwd_edge = nullptr;
@@ -254,6 +257,9 @@ inline CoreSrc core_workspace(float* state, int first) { return {state, first, 0
 // ... for windows win0 .. of a sequence, n_per_clip of them sharing a clip's logit; no EMA here (launch_ema_scan follows)
 inline CoreSrc core_workspace_seq(int64_t win0, int n_per_clip) { return {nullptr, 1, win0, n_per_clip, 0, nullptr, nullptr, nullptr, nullptr}; }
 inline CoreSrc core_strided(const SeqCore* s, int64_t win0) { return {nullptr, 1, win0, s->n_per_clip, 0, nullptr, nullptr, s, nullptr}; }
+// ... the same two sources with a logit per WINDOW of the sequence (km_sequence_forward_track: zemo is (clips * n_per_clip))
+inline CoreSrc core_workspace_seq_win(int64_t win0) { return {nullptr, 1, win0, 1, 0, nullptr, nullptr, nullptr, nullptr}; }
+inline CoreSrc core_strided_win(const SeqCore* s, int64_t win0) { return {nullptr, 1, win0, 1, 0, nullptr, nullptr, s, nullptr}; }
 inline CoreSrc core_table(const ClipTable* t, float* state, int first) { return {state, first, 0, 1, 0, nullptr, nullptr, nullptr, t}; }
 // the handle's streams: rows of the workspace, EMA state and flags of the rings
 // (gate: the per-stream flags the kernel skips on -- is_full for km_stream_tick, this step's fire flags for km_stream_step)
@@ -314,6 +320,10 @@ struct LegacyPowSrc { const float* melpow; unsigned* melmax; const LogParams* lp
 bool legacy_pow_ok(Context* c);
 int launch_legacy(Context* c, const float* mel, int64_t B, int64_t T_mel, float* out, void* stream, const LegacyPowSrc* pow_src = nullptr);
 int launch_gather_clip_logits(Context* c, const float* zclip, float* zwin, int64_t nw, int64_t w0, int wins_per_clip, void* stream);
+// km_sequence_forward_track: window j of clip c ends at e = min(clip_len, sample_offset + j step + window) and takes the logit of
+// track row k = e < first ? 0 : min((e - first) / interval, K - 1): zwin[c n_per_clip + j] = ztrack[c K + k]
+struct SeqTrackMap { int64_t K, first, interval, sample_offset, clip_len, step, window; };
+int launch_seq_track_logits(Context* c, const float* ztrack, float* zwin, int64_t total, int n_per_clip, const SeqTrackMap& m, void* stream);
 int launch_core_generic_packed(Context* c, const float* xp, int64_t B, const float* zemo, float* out, float* raw, float* attn,
                                void* stream);
 float* generic_packed_x(Context* c, int64_t B);

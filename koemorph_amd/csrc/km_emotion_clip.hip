@@ -7,6 +7,8 @@
 //   km_egemaps.hip       the five ragged eGeMAPS kernels, as the streams launch them (egm_ragged_functionals)
 //   ec_epilogue_kernel   NaN / Inf -> 0 (:450-452), features[k], and W concat(features[k], features[0], features[0]) + b for all rows
 //                        of the pass: the 300 / 600 ms slots are filled once per life (:478-490) and a clip is one life
+//   ecb_plan_kernel /    the same two for B clips of one length at once (km_emotion_clip_build_batch): rows numbered g = c K + k fill the
+//   ecb_epilogue_kernel  passes across clip boundaries, the clips are the B "rings", and a row takes its OWN clip's features[0]
 //   ec_rows_kernel       window -> row: e = min(n, (s + T) h), k = clamp((e - MIN) / U, 0, K - 1), a 256-float copy per window
 // build and rows neither allocate, synchronise nor read back; rows' grid depends on the batch alone, so it captures into a hipGraph.
 #include <hip/hip_runtime.h>
@@ -114,6 +116,68 @@ __global__ __launch_bounds__(256) void ec_epilogue_kernel(const float* __restric
             for (int k = 0; k < NFEAT; ++k) acc = fmaf(wr[NFEAT + k], f0l[k], acc);
             for (int k = 0; k < NFEAT; ++k) acc = fmaf(wr[2 * NFEAT + k], f0l[k], acc);
             emotion[(k0 + m) * NEMO + col0 + c] = acc + bc;
+        }
+    }
+}
+
+// ---- B clips of one length: rows g0 .. g0 + max_slots - 1 of the numbering g = c K + k, ec_plan_kernel's closed form with stream = c ----
+__global__ __launch_bounds__(256) void ecb_plan_kernel(int64_t g0, int64_t G, int64_t K, int max_slots, int ring_len, int window_len,
+                                                       int update_samples, int min_samples, EgmSlot* __restrict__ table) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= max_slots) return;
+    const int64_t g = g0 + i;
+    EgmSlot sl{-1, 0, 0, 0};
+    if (g < G) {
+        const int64_t c = g / K, k = g - c * K;
+        const int64_t t = min_samples + k * update_samples;                      // <= L <= 2^30
+        sl.stream = (int)c;
+        if (t < ring_len) { sl.start = 0; sl.len = t < window_len ? (int)t : window_len; }
+        else { sl.start = (int)(t - window_len); sl.len = window_len; }
+        sl.nf = (sl.len - 960) / 160 + 1;
+    }
+    table[i] = sl;
+}
+
+// ---- the pass's rows g0 + m, as ec_epilogue_kernel: scrub, features[g], emotion[g] = W (f_g | f_0 | f_0) + b with f_0 = features of
+// row 0 of the row's OWN clip c = g / K.  Row (c, 0) is slot c K - g0 of this pass when c K >= g0; otherwise an earlier pass wrote
+// features[c K] (every workgroup reads it, none of this launch writes it).  The sum keeps that kernel's order: one fmaf chain over
+// k = 0 .. 263 from zero, then + bias. ----
+__global__ __launch_bounds__(256) void ecb_epilogue_kernel(const float* __restrict__ fout, int rows, int64_t g0, int64_t K,
+                                                           const float* __restrict__ w, const float* __restrict__ bias,
+                                                           float* __restrict__ features, float* __restrict__ emotion) {
+    using namespace ec;
+    __shared__ float wl[TN * WS];
+    __shared__ float xl[TM * NFEAT];
+    __shared__ float f0l[TM * NFEAT];
+    const int tid = threadIdx.x, c = tid % TN, r = tid / TN, col0 = blockIdx.x * TN;
+    const float* wsrc = w + (int64_t)col0 * NCAT;
+    for (int i = tid; i < TN * NCAT; i += 256) wl[(i / NCAT) * WS + i % NCAT] = wsrc[i];
+    const float bc = bias[col0 + c];
+    for (int m0 = 0; m0 < rows; m0 += TM) {
+        __syncthreads();                                                         // the turn before is done with xl and f0l; wl is written
+        for (int i = tid; i < TM * NFEAT; i += 256) {
+            const int m = m0 + i / NFEAT, j = i % NFEAT;
+            float f = 0.f, f0 = 0.f;
+            if (m < rows) {
+                f = ec_scrub(fout[(int64_t)m * NFEAT + j]);
+                const int64_t r0 = (g0 + m) / K * K;                             // row 0 of this row's clip
+                f0 = r0 >= g0 ? ec_scrub(fout[(r0 - g0) * NFEAT + j]) : features[r0 * NFEAT + j];
+                if (blockIdx.x == 0) features[(g0 + m) * NFEAT + j] = f;
+            }
+            xl[i] = f;
+            f0l[i] = f0;
+        }
+        __syncthreads();
+        const int m = m0 + r;
+        if (m < rows) {
+            const float* wr = wl + c * WS;
+            const float* x = xl + r * NFEAT;
+            const float* x0 = f0l + r * NFEAT;
+            float acc = 0.f;
+            for (int k = 0; k < NFEAT; ++k) acc = fmaf(wr[k], x[k], acc);
+            for (int k = 0; k < NFEAT; ++k) acc = fmaf(wr[NFEAT + k], x0[k], acc);
+            for (int k = 0; k < NFEAT; ++k) acc = fmaf(wr[2 * NFEAT + k], x0[k], acc);
+            emotion[(g0 + m) * NEMO + col0 + c] = acc + bc;
         }
     }
 }
@@ -232,6 +296,35 @@ int km_emotion_clip_build(void* ec, const float* clip_dev, int64_t clip_len, flo
         HIP_TRY(hipGetLastError());
         if (const int rc = egm_ragged_functionals(e->plan, clip_dev, clip_len, e->table, ms, e->max_nf, e->scale, e->rec, e->fout, st)) return rc;
         hipLaunchKernelGGL(ec_epilogue_kernel, dim3(ec::NEMO / ec::TN), dim3(256), 0, st, (const float*)e->fout, rows, k0, e->f0,
+                           (const float*)e->w, (const float*)e->bias, features_out, emotion_out);
+        HIP_TRY(hipGetLastError());
+    }
+    return KM_OK;
+}
+
+int km_emotion_clip_build_batch(void* ec, const float* clips_dev, int64_t B, int64_t L, float* features_out, float* emotion_out, void* stream) {
+    if (!ec) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build_batch: NULL argument");
+    EmotionClip* e = static_cast<EmotionClip*>(ec);
+    if (B < 0 || L < 0 || L > ec::MAX_CLIP)
+        return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build_batch: %lld clips of %lld samples, 0 .. 2^30 (window starts are 32-bit)",
+                    (long long)B, (long long)L);
+    if (!e->has_compression) return fail(KM_ERR_NOT_READY, "km_emotion_clip_build_batch: km_emotion_clip_set_compression first");
+    const int64_t K = ec_num_rows(e, L);
+    if (K == 0 || B == 0) return KM_OK;
+    if (B > 0x7fffffff / K)
+        return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build_batch: %lld clips x %lld rows, at most 2^31 - 1 rows", (long long)B, (long long)K);
+    // features_out is read back by the passes that follow a clip's row 0, so it is not optional here
+    if (!clips_dev || !features_out || !emotion_out) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build_batch: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int ms = (int)e->max_slots;
+    const int64_t G = B * K;
+    for (int64_t g0 = 0; g0 < G; g0 += ms) {                                     // in order: a pass may read features[c, 0] of an earlier one
+        const int rows = (int)(G - g0 < ms ? G - g0 : ms);
+        hipLaunchKernelGGL(ecb_plan_kernel, dim3((unsigned)((ms + 255) / 256)), dim3(256), 0, st, g0, G, K, ms, e->ring_len, e->window_len,
+                           e->update_samples, e->min_samples, e->table);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = egm_ragged_functionals(e->plan, clips_dev, L, e->table, ms, e->max_nf, e->scale, e->rec, e->fout, st)) return rc;
+        hipLaunchKernelGGL(ecb_epilogue_kernel, dim3(ec::NEMO / ec::TN), dim3(256), 0, st, (const float*)e->fout, rows, g0, K,
                            (const float*)e->w, (const float*)e->bias, features_out, emotion_out);
         HIP_TRY(hipGetLastError());
     }

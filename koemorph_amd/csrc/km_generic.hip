@@ -437,6 +437,27 @@ int launch_gather_clip_logits(Context* c, const float* zclip, float* zwin, int64
     return KM_OK;
 }
 
+// one logit per window of a sequence from the logits of the clips' emotion tracks: the row a live stream would hold when the
+// window ends, in closed form (ec_rows_kernel's mapping when the chunk is the whole clip).  Reads no audio and no table.
+__global__ void seq_track_logits_kernel(const float* __restrict__ ztrack, float* __restrict__ zwin, int64_t total, int n_per_clip, SeqTrackMap m) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int64_t c = i / n_per_clip, j = i - c * n_per_clip;
+    int64_t e = m.sample_offset + j * m.step + m.window;
+    if (e > m.clip_len) e = m.clip_len;
+    int64_t k = e < m.first ? 0 : (e - m.first) / m.interval;
+    if (k > m.K - 1) k = m.K - 1;
+    zwin[i] = ztrack[c * m.K + k];
+}
+
+int launch_seq_track_logits(Context* c, const float* ztrack, float* zwin, int64_t total, int n_per_clip, const SeqTrackMap& m, void* stream) {
+    (void)c;
+    hipLaunchKernelGGL(seq_track_logits_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ztrack, zwin,
+                       total, n_per_clip, m);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
 static const float* dv(Context* c, const char* name) { return c->packed.at(name).dev; }
 
 // workspace floats per window for the generic forward

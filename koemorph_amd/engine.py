@@ -77,6 +77,15 @@ def _torch():
     return torch
 
 
+def sequence_track_row(i: int, K: int, first_samples: int, interval_samples: int, sample_offset: int, clip_len: int,
+                       stride_frames: int, window_frames: int, hop: int) -> int:
+    """The track row output frame ``i`` of a chunk takes in km_sequence_forward_track, restated on the host: the window ends, in
+    clip coordinates, at ``e = min(clip_len, sample_offset + (i * stride_frames + window_frames) * hop)`` and holds the last update
+    made by then, ``0 if e < first_samples else min((e - first_samples) // interval_samples, K - 1)``."""
+    e = min(clip_len, sample_offset + (i * stride_frames + window_frames) * hop)
+    return 0 if e < first_samples else min((e - first_samples) // interval_samples, K - 1)
+
+
 def _ptr(t) -> int:
     return t.data_ptr() if t is not None else 0
 
@@ -365,6 +374,30 @@ class Engine:
         with torch.cuda.device(audio.device):
             check(self._lib.km_sequence_forward(self._h, _ptr(audio), B, L, _ptr(emotion), stride_frames,
                                                 1 if smooth else 0, _ptr(out), _stream_ptr(audio.device)))
+        return out
+
+    def sequence_forward_track(self, audio, track, first_samples: int, interval_samples: int, stride_frames: int = 1,
+                               smooth: bool = True, sample_offset: int = 0, clip_len: Optional[int] = None, max_tile: int = 2048):
+        """audio (B, L), track (B, K, emotion_dim) -> (B, N, 52) as ``sequence_forward``, every window taking the track row
+        ``k = 0 if e < first_samples else min((e - first_samples) // interval_samples, K - 1)`` of its clip, ``e`` being the sample
+        at which the window ends in the clip (``sample_offset`` / ``clip_len`` place a chunk inside it; km_sequence_forward_track).
+        A track without rows (``K = 0``, a clip shorter than the first update) stands for one zero row per clip."""
+        torch = _torch()
+        audio = self._chk(audio, "audio", 2)
+        B, L = audio.shape
+        if track.dim() != 3 or track.shape[0] != B or track.shape[2] != self.emotion_dim:
+            raise ValueError(f"expected a ({B}, K, {self.emotion_dim}) track, got {tuple(track.shape)}")
+        if track.shape[1] == 0:
+            track = torch.zeros(B, 1, track.shape[2], device=audio.device, dtype=torch.float32)
+        track = self._chk(track, "emotion_track", 3)
+        N = self.sequence_num_outputs(L, stride_frames)
+        W = self.mel_sequence_length * self.mel.hop_length
+        self.reserve(max(B, min(B * N, max_tile)), W)
+        out = torch.empty(B, N, self.num_blendshapes, device=audio.device, dtype=torch.float32)
+        with torch.cuda.device(audio.device):
+            check(self._lib.km_sequence_forward_track(self._h, _ptr(audio), B, L, _ptr(track), track.shape[1], int(first_samples),
+                                                      int(interval_samples), int(sample_offset), int(L if clip_len is None else clip_len),
+                                                      stride_frames, 1 if smooth else 0, _ptr(out), _stream_ptr(audio.device)))
         return out
 
     def ema_scan(self, seq) -> None:

@@ -55,7 +55,7 @@ class ClipEmotion:
             check(self._lib.km_emotion_clip_set_compression(self._h, _ptr(w), _ptr(b), _stream_ptr(self.device)))
             torch.cuda.current_stream(self.device).synchronize()          # w and b may go once the copy is done
         self._tracks: Dict[Hashable, Tuple[torch.Tensor, int]] = {}
-        self.builds = 0                                                   # calls of build(), track_for's misses included
+        self.builds = 0                                                   # calls of build() / build_batch(), track_for's misses included
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -86,6 +86,22 @@ class ClipEmotion:
         features = torch.empty(K, 88, device=clip.device)
         with torch.cuda.device(clip.device):
             check(self._lib.km_emotion_clip_build(self._h, _ptr(clip), n, _ptr(features), _ptr(emotion), _stream_ptr(clip.device)))
+        self.builds += 1
+        return emotion, features
+
+    def build_batch(self, clips: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """clips (B, L) fp32 on the device, B clips of one length -> (emotion (B, K, 256), features (B, K, 88)); every clip's slice
+        is bit-identical to ``build`` of that clip.  The passes of ``max_slots`` windows are filled across clip boundaries
+        (km_emotion_clip_build_batch), so short clips do not leave them mostly empty.  One build in ``builds``; no synchronisation."""
+        if clips.dim() != 2 or clips.dtype != torch.float32 or not clips.is_cuda:
+            raise ValueError(f"expected (B, L) float32 clips on the device, got {tuple(clips.shape)} {clips.dtype} on {clips.device}")
+        clips = clips.contiguous()
+        B, L = clips.shape
+        K = self.num_rows(L)
+        emotion = torch.empty(B, K, 256, device=clips.device)
+        features = torch.empty(B, K, 88, device=clips.device)
+        with torch.cuda.device(clips.device):
+            check(self._lib.km_emotion_clip_build_batch(self._h, _ptr(clips), B, L, _ptr(features), _ptr(emotion), _stream_ptr(clips.device)))
         self.builds += 1
         return emotion, features
 

@@ -6,6 +6,10 @@ frame per window position (window = mel_sequence_length frames, stride = stride_
 walks the positions in a Python loop and recomputes the whole 257-frame mel on the CPU for each one
 (:101-145); here every window of every clip is one workgroup of the same HIP kernels, addressed in place
 inside the clip (km_sequence_forward), followed by an EMA scan along the frame axis.
+
+Not in the reference: ``clip_emotion`` (a ``koemorph_amd.features.ClipEmotion``) or ``forward(emotion_track=...)`` give every
+window the row of the clip's eGeMAPS emotion track that a live stream would hold when the window ends -- the input
+``train_sequential --emotion egemaps`` trains on -- instead of one vector per clip (km_sequence_forward_track).
 """
 from __future__ import annotations
 
@@ -34,7 +38,10 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
         stride_frames: int = 1,
         emotion_provider=None,
         shard_across_ranks: bool = False,
+        clip_emotion=None,
     ):
+        if clip_emotion is not None and emotion_provider is not None:
+            raise ValueError("clip_emotion and emotion_provider both produce the emotion input: pass one of them")
         super().__init__(d_model=d_model, num_heads=num_heads, num_blendshapes=num_blendshapes,
                          sample_rate=sample_rate, target_fps=target_fps, mel_sequence_length=mel_sequence_length,
                          emotion_config=emotion_config, device=device, real_time_mode=real_time_mode,
@@ -43,30 +50,58 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
         # not in the reference (single process): under torch.distributed the output frames of a clip are computed in contiguous
         # chunks, one per rank, and smoothed once over the gathered sequence (koemorph_amd.parallel.sequence_apply)
         self.shard_across_ranks = shard_across_ranks
+        # not in the reference either: the clips' emotion tracks, built per forward call (ClipEmotion.build_batch)
+        self.clip_emotion = clip_emotion
         self.window_frames = mel_sequence_length                      # reference :51
         self.window_samples = self.window_frames * self.hop_length    # :54
         self.stride_samples = self.stride_frames * self.hop_length    # :55
 
+    def _track_mapping(self):
+        if self.clip_emotion is None:
+            raise ValueError("emotion_track needs the model's clip_emotion: its shape maps windows to rows")
+        sh = self.clip_emotion.shape
+        return int(sh["min_samples"]), int(sh["update_samples"])
+
     def forward(self, audio: torch.Tensor, return_attention: bool = False,
-                emotion_features: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                emotion_features: Optional[torch.Tensor] = None,
+                emotion_track: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         if audio.dim() != 2:
             raise ValueError(f"Expected 2D input, got {audio.dim()}D")
+        if emotion_track is not None and emotion_features is not None:
+            raise ValueError("emotion_track and emotion_features both produce the emotion input: pass one of them")
         batch_size, audio_length = audio.shape
         emotion_metadata = {"backend_used": self.emotion_backend}
-        if emotion_features is None:                                   # emotion features ONCE per clip (:88)
+        mapping = None
+        if emotion_track is not None:
+            mapping = self._track_mapping()
+        elif emotion_features is None and self.clip_emotion is not None:
+            mapping = self._track_mapping()
+            emotion_track, _ = self.clip_emotion.build_batch(audio.to(torch.float32).contiguous())
+            emotion_metadata = {"backend_used": "egemaps_track"}
+        elif emotion_features is None:                                 # emotion features ONCE per clip (:88)
             emotion_features, emotion_metadata = self.extract_emotion_features(audio)
+        if mapping is not None:
+            if emotion_track.dim() != 3 or emotion_track.shape[0] != batch_size:
+                raise ValueError(f"expected a ({batch_size}, K, {self.emotion_dim}) emotion_track, got {tuple(emotion_track.shape)}")
+            if emotion_track.shape[1] == 0:                            # no update yet: the zero vector ClipEmotion.rows gives
+                emotion_track = torch.zeros(batch_size, 1, emotion_track.shape[2], device=audio.device)
         eng = self.dual_stream_attention.engine()
         self.reset_temporal_state()                                    # :99
         self.dual_stream_attention.require_eval_mode()
         results: Dict[str, object] = {}
         if not return_attention and self.shard_across_ranks:
             from .. import parallel
-            seq = parallel.sequence_apply(eng, audio, emotion_features, self.stride_frames, smooth=self.use_temporal_smoothing)
+            seq = parallel.sequence_apply(eng, audio, emotion_features, self.stride_frames, smooth=self.use_temporal_smoothing,
+                                          emotion_track=emotion_track, track_shape=mapping)
+        elif not return_attention and mapping is not None:
+            seq = eng.sequence_forward_track(audio, emotion_track, mapping[0], mapping[1], self.stride_frames,
+                                             smooth=self.use_temporal_smoothing)
         elif not return_attention:
             seq = eng.sequence_forward(audio, emotion_features, self.stride_frames,
                                        smooth=self.use_temporal_smoothing)
         else:
             # attention maps are a visualisation aid: walk the positions like the reference does
+            from ..engine import sequence_track_row
             num_frames = audio_length // self.hop_length
             n_out = max(1, (num_frames - self.window_frames) // self.stride_frames + 1)
             frames, mel_att, emo_att = [], [], []
@@ -76,6 +111,10 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
                 win = audio[:, s:e]
                 if e - s < self.window_samples:                        # zero-pad the last window (:111-115)
                     win = torch.nn.functional.pad(win, (0, self.window_samples - (e - s)))
+                if mapping is not None:                                # the row the fused call gives this window
+                    k = sequence_track_row(i, emotion_track.shape[1], mapping[0], mapping[1], 0, audio_length, self.stride_frames,
+                                           self.window_frames, self.hop_length)
+                    emotion_features = emotion_track[:, k].contiguous()
                 o = SimplifiedDualStreamModel.forward(self, win.contiguous(), True, emotion_features)
                 frames.append(o['blendshapes'])
                 mel_att.append(o['mel_attention_weights'])

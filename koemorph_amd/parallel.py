@@ -98,15 +98,28 @@ def sequence_chunk(L: int, hop: int, window_frames: int, stride_frames: int, n_o
     return lo, hi, s0, s1
 
 
-def sequence_apply(engine, audio: torch.Tensor, emotion: torch.Tensor, stride_frames: int = 1, smooth: bool = True) -> torch.Tensor:
+def sequence_apply(engine, audio: torch.Tensor, emotion: Optional[torch.Tensor], stride_frames: int = 1, smooth: bool = True,
+                   emotion_track: Optional[torch.Tensor] = None, track_shape: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """``SequentialDualStreamModel.forward`` of ONE batch of clips over all ranks (reference
     src/model/sequential_dual_stream_model.py:84-151): every rank holds the clips, computes a contiguous chunk of each clip's
     output frames WITHOUT smoothing (``engine.sequence_forward`` on the chunk's samples + one window of halo), the chunks are
     all-gathered in rank order (208 bytes per frame: the only exchange, and it is not on the kernels' path) and the EMA --
     a first-order recurrence along the frame axis -- runs once over the gathered (B, N, 52).  Every rank returns the full
     sequence; it is bit-identical to the single-rank result because every window is computed by the same kernels from the same
-    samples whichever sub-clip it is addressed in."""
+    samples whichever sub-clip it is addressed in.
+
+    ``emotion_track`` (B, K, emotion_dim) with ``track_shape = (first_samples, interval_samples)`` replaces the one vector per clip
+    by a row per window (``engine.sequence_forward_track``): every rank passes its chunk's ``sample_offset = s0`` and
+    ``clip_len = L``, so a window takes the row it takes in the whole clip."""
+    if emotion_track is not None:
+        if emotion is not None:
+            raise ValueError("emotion and emotion_track both produce the emotion input: pass one of them")
+        if track_shape is None:
+            raise ValueError("emotion_track needs track_shape = (first_samples, interval_samples)")
+        first, interval = int(track_shape[0]), int(track_shape[1])
     if not collectives_active():
+        if emotion_track is not None:
+            return engine.sequence_forward_track(audio, emotion_track, first, interval, stride_frames, smooth=smooth)
         return engine.sequence_forward(audio, emotion, stride_frames, smooth=smooth)
     rank, world = dist.get_rank(), dist.get_world_size()
     B, L = audio.shape
@@ -118,7 +131,11 @@ def sequence_apply(engine, audio: torch.Tensor, emotion: torch.Tensor, stride_fr
     maxn = max(h - l for l, h in sizes)
     pad = torch.zeros((B, maxn, nb), dtype=torch.float32, device=audio.device)
     if hi > lo:
-        part = engine.sequence_forward(audio[:, s0:s1].contiguous(), emotion, stride_frames, smooth=False)
+        if emotion_track is not None:
+            part = engine.sequence_forward_track(audio[:, s0:s1].contiguous(), emotion_track, first, interval, stride_frames,
+                                                 smooth=False, sample_offset=s0, clip_len=L)
+        else:
+            part = engine.sequence_forward(audio[:, s0:s1].contiguous(), emotion, stride_frames, smooth=False)
         if part.shape[1] != hi - lo:
             raise RuntimeError(f"sequence chunk [{lo}, {hi}) of {N} frames came back with {part.shape[1]} frames")
         pad[:, : hi - lo] = part

@@ -1,0 +1,106 @@
+"""Offline rendering of one audio file with a ``train_sequential`` checkpoint:
+
+    python -m koemorph_amd.scripts.render_sequential --model_path ckpt.pth --input_audio a.wav --output_json out.jsonl
+                                                     [--stride 1] [--emotion egemaps|noise]
+
+The clip goes through ``SequentialDualStreamModel.forward`` (one output frame per window position, EMA along the clip) and every
+frame is written as one ``{"timestamp", "blendshapes"}`` line, encoded by ``koemorph_amd.wire`` as the streaming scripts encode
+theirs.  A frame's timestamp is the time at which its window ends.  ``--emotion egemaps`` gives every window the row of the
+clip's eGeMAPS emotion track a live stream would hold at that time (``ClipEmotion``), the input ``train_sequential --emotion
+egemaps`` trains on; ``noise`` is the reference's extraction-failure fallback, one ``0.1 * randn`` vector per clip.
+"""
+from __future__ import annotations
+
+import argparse
+import logging
+from pathlib import Path
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import wire
+from ..data.sequential_dataset import _load_wav
+from ..features.clip_emotion import ClipEmotion
+from ..model import SequentialDualStreamModel
+
+logger = logging.getLogger(__name__)
+
+COMPRESSION_SEED = 0          # the Linear(264, 256) of a checkpoint that carries none: torch's default initialisation under this seed
+
+
+def compression_layer(ckpt: dict) -> "tuple[torch.nn.Linear, str]":
+    """The 264 -> 256 layer behind the emotion track and where it came from: ``ckpt["emotion_compression"]`` (``weight`` (256, 264),
+    ``bias`` (256)) when the checkpoint carries one, else a seeded default initialisation."""
+    saved = ckpt.get("emotion_compression")
+    if saved is not None:
+        layer = torch.nn.Linear(264, 256)
+        layer.load_state_dict({"weight": torch.as_tensor(saved["weight"], dtype=torch.float32),
+                               "bias": torch.as_tensor(saved["bias"], dtype=torch.float32)})
+        return layer, "checkpoint"
+    with torch.random.fork_rng(devices=[]):                # the caller's generator is left as it was
+        torch.manual_seed(COMPRESSION_SEED)
+        layer = torch.nn.Linear(264, 256)
+    return layer, f"default initialisation, seed {COMPRESSION_SEED}"
+
+
+def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: str = "cuda") -> SequentialDualStreamModel:
+    ckpt = torch.load(model_path, map_location="cpu", weights_only=True)
+    cfg = dict(ckpt.get("model_config") or {})
+    clip_emotion: Optional[ClipEmotion] = None
+    if emotion == "egemaps":
+        layer, source = compression_layer(ckpt)
+        logger.info("emotion track: eGeMAPS, compression layer from the %s", source)
+        clip_emotion = ClipEmotion(compression_layer=layer, device=device)
+    model = SequentialDualStreamModel(d_model=int(cfg.get("d_model", 256)), num_heads=int(cfg.get("num_heads", 8)),
+                                      mel_sequence_length=int(cfg.get("mel_sequence_length", 256)), stride_frames=stride,
+                                      device=device, clip_emotion=clip_emotion)
+    model.load_state_dict(ckpt["model_state_dict"])
+    return model.to(device).eval()
+
+
+def frame_timestamps(n_frames: int, audio_length: int, model: SequentialDualStreamModel) -> np.ndarray:
+    """Seconds at which each output frame's window ends (the last, zero-padded window ends with the clip)."""
+    ends = (np.arange(n_frames, dtype=np.int64) * model.stride_frames + model.window_frames) * model.hop_length
+    return np.minimum(ends, audio_length) / float(model.sample_rate)
+
+
+def render(model: SequentialDualStreamModel, audio: np.ndarray, output_json) -> int:
+    """audio (L) -> one JSONL line per output frame; returns the number of frames written."""
+    dev = next(model.parameters()).device
+    with torch.no_grad():
+        out = model(torch.from_numpy(np.ascontiguousarray(audio, np.float32))[None].to(dev))
+    frames = out["blendshapes"][0].cpu().numpy()
+    lines = wire.format_frames(frames, frame_timestamps(frames.shape[0], audio.shape[0], model))
+    output_json = Path(output_json)
+    output_json.parent.mkdir(parents=True, exist_ok=True)
+    with open(output_json, "wb") as f:
+        for line in lines:
+            f.write(line + b"\n")
+    return len(lines)
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("--model_path", required=True)
+    p.add_argument("--input_audio", required=True)
+    p.add_argument("--output_json", required=True)
+    p.add_argument("--stride", type=int, default=1, help="frames between two window positions")
+    p.add_argument("--emotion", choices=("egemaps", "noise"), default="egemaps")
+    p.add_argument("--device", default="cuda")
+    return p
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    model = load_model(args.model_path, args.stride, args.emotion, args.device)
+    audio = _load_wav(Path(args.input_audio), model.sample_rate)
+    n = render(model, audio, args.output_json)
+    logger.info("%d frames (%.2f s of audio, stride %d, emotion %s) -> %s", n, audio.shape[0] / model.sample_rate, args.stride,
+                args.emotion, args.output_json)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
