@@ -252,6 +252,35 @@ int km_sequence_forward_track(km_handle h, const float* audio_dev, int64_t B, in
                               int64_t sample_offset, int64_t clip_len, int32_t stride_frames, int32_t smooth,
                               float* out_dev, void* stream);
 
+/* ---- attention maps and pre-weight outputs from the audio paths ------------------------------------------------------------
+ * The reference treats the mel stream's attention map as an output of the model (DualStreamTrainer.train_step calls
+ * model(audio, return_attention=True); SequentialTrainer logs outputs['mel_attention_weights'][0]).  These are km_forward_audio,
+ * km_forward_clip and km_sequence_forward / km_sequence_forward_track with two more outputs, indexed like out_dev:
+ *   raw_dev   (..., 52) or NULL        the sigmoid outputs before the stream weights and before any smoothing (km_core_forward)
+ *   attn_dev  (..., 28, 80) or NULL    'mel_attention_weights', head-averaged as km_core_forward defines it
+ * On handles of the fused shape out_dev and state_dev are bit-identical to the entry point without _attn (the ATTN instantiation
+ * of the same fused core writes the map from the LDS image behind its O tile), and raw_dev / attn_dev are bit-identical across
+ * the shared-frame and per-window schedules, any tile size, km_forward_audio_attn on the gathered windows and
+ * km_forward_clip_attn on their start frames.  With the experimental split-bf16 core (core_split 3 / 6) a call that asks for
+ * maps returns KM_ERR_UNSUPPORTED before it launches anything.  On generic shapes the GEMM-chain core writes both (the merged
+ * d_model 512 launch is declined when a map is asked for, so bit equality with the plain call is not promised there).
+ * km_sequence_forward_attn: exactly one of emotion_dev (B, emotion_dim) and track_dev (B, K, emotion_dim) is non-NULL; K ..
+ * clip_len are km_sequence_forward_track's and are ignored with emotion_dev; the argument checks are that entry point's.
+ * stats is NULL or an accumulator of km_attn_stats_create(28, 80): every tile's maps are added to it with one
+ * km_attn_stats_update, in tile order.  With stats and attn_dev == NULL the maps never exist as a whole: they go to a grow-only
+ * buffer of one tile (reserved windows x 28 x 80 floats) on the handle, allocated before the first launch and refused inside a
+ * capture when it would have to grow, like the other sequence buffers. */
+int km_forward_audio_attn(km_handle h, const float* audio_dev, int64_t B, int64_t L,
+                          const float* emotion_dev, float* out_dev, float* state_dev, int32_t first,
+                          float* raw_dev, float* attn_dev, void* stream);
+int km_forward_clip_attn(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
+                         int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev,
+                         float* out_dev, float* state_dev, int32_t first, float* raw_dev, float* attn_dev, void* stream);
+int km_sequence_forward_attn(km_handle h, const float* audio_dev, int64_t B, int64_t L,
+                             const float* emotion_dev, const float* track_dev, int64_t K, int64_t first_samples,
+                             int64_t interval_samples, int64_t sample_offset, int64_t clip_len, int32_t stride_frames,
+                             int32_t smooth, float* out_dev, float* raw_dev, float* attn_dev, void* stats, void* stream);
+
 /* ---- training step (data-parallel ready) -------------------------------------------------------------
  * Replaces the body of SequentialTrainer.train_epoch (src/train_sequential.py:158-181: forward, loss,
  * backward, clip_grad_norm_(1.0), AdamW.step) for the 28 tensors of DualStreamCrossAttention + smoothing_alpha.
@@ -764,6 +793,30 @@ int km_metrics_destroy(void* acc);
 int km_metrics_reset(void* acc, void* stream);
 int km_metrics_update(void* acc, const float* pred_dev, const float* target_dev, const float* audio_energy_dev, int64_t N, void* stream);
 int km_metrics_compute(void* acc, float* out_dev, void* stream);
+
+/* ---- attention-map statistics: a streaming accumulator in device memory ---------------------------------------------------
+ * Replaces the reductions AttentionVisualizer is built on (src/visualization/attention_viz.py: the mean map, :96-98, and the
+ * mass per frequency band, :329-331) for maps that stay on the device: (rows, Q, K) float32 maps are folded into a float64 /
+ * integer state, per query q over every map since the last reset
+ *   sum[q][k]   the float64 sum of A                                   (compute: / rows, the mean map)
+ *   ent[q]      the sum over maps of -sum_k A ln A, every term in float64 from the float32 entry, 0 for an entry of 0
+ *                                                                      (compute: / rows, the mean entropy)
+ *   peak[q][k]  the number of maps whose largest entry of query q is key k, ties to the lowest k (np.argmax); exact
+ * Fixed-order reductions, no atomics: the same rows in the same calls with the same max_rows_per_launch give the same bits.
+ *   km_attn_stats_create    Q = n_queries >= 1, K = n_keys a multiple of 4 up to 256 (28 x 80 for this model);
+ *                           max_rows_per_launch = 0 is a default (4096), larger updates are cut into pieces inside
+ *   km_attn_stats_shape     the Q and K of an accumulator
+ *   km_attn_stats_update    attn_dev (rows, Q, K), 16-byte aligned; rows = 0 does nothing
+ *   km_attn_stats_compute   out_dev[KM_ATTN_STATS_COUNT(Q, K)] float64: rows, the mean map (Q K), the mean entropy (Q), the peak
+ *                           counts (Q K); all 0 before any row.  The state is left as it is (compute, update, compute works)
+ * reset / update / compute launch on `stream`, neither allocate nor synchronise nor read back, and can be captured. */
+#define KM_ATTN_STATS_COUNT(Q, K) (1 + (Q) * (K) + (Q) + (Q) * (K))
+int km_attn_stats_create(void** acc_out, int32_t n_queries, int32_t n_keys, int64_t max_rows_per_launch);
+int km_attn_stats_destroy(void* acc);
+int km_attn_stats_shape(void* acc, int32_t* n_queries, int32_t* n_keys);
+int km_attn_stats_reset(void* acc, void* stream);
+int km_attn_stats_update(void* acc, const float* attn_dev, int64_t rows, void* stream);
+int km_attn_stats_compute(void* acc, double* out_dev, void* stream);
 
 /* ---- the loss by component: a streaming accumulator in device memory ------------------------------------------------
  * Replaces the `metrics` dict of KoeMorphLoss.forward (src/model/losses.py:111-183: one .item() per term and batch), the

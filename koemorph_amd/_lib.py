@@ -70,6 +70,13 @@ KM_METRICS_NAMES = ("mae", "mse", "rmse", "max_bs_mae", "min_bs_mae", "std_bs_ma
                     "precision", "recall", "f1_score", "mouth_mae", "mouth_correlation", "audiovisual_sync", "rows",
                     "valid_correlations", "has_energy")
 
+
+
+def km_attn_stats_count(n_queries: int, n_keys: int) -> int:
+    """KM_ATTN_STATS_COUNT(Q, K) of include/koemorph.h: rows, the mean map, the mean entropy per query, the peak counts."""
+    return 1 + n_queries * n_keys + n_queries + n_queries * n_keys
+
+
 # km_loss_terms_update's terms_dev / the first KM_LOSS_TERMS entries of km_loss_terms_compute (include/koemorph.h: KM_LOSS_TERM_*)
 KM_LOSS_TERMS = 11
 KM_LOSS_TERM_NAMES = ("mse", "l1", "perceptual", "temporal", "velocity", "sparsity", "smoothness", "landmark", "ds_velocity",
@@ -108,6 +115,9 @@ SIGNATURES = {
     "km_sequence_num_outputs": (_i64, [_h, _i64, _i32]),
     "km_sequence_forward": (C.c_int, [_h, _p, _i64, _i64, _p, _i32, _i32, _p, _p]),
     "km_sequence_forward_track": (C.c_int, [_h, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _p]),
+    "km_forward_audio_attn": (C.c_int, [_h, _p, _i64, _i64, _p, _p, _p, _i32, _p, _p, _p]),
+    "km_forward_clip_attn": (C.c_int, [_h, _p, _i64, _p, _i64, _i32, _i32, _p, _p, _p, _i32, _p, _p, _p]),
+    "km_sequence_forward_attn": (C.c_int, [_h, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _p, _p, _p, _p]),
     "km_ema_scan": (C.c_int, [_h, _p, _i64, _i64, _p]),
     "km_train_init": (C.c_int, [_h, _i64, _p]),
     "km_train_num_params": (_i64, [_h]),
@@ -184,6 +194,12 @@ SIGNATURES = {
     "km_metrics_reset": (C.c_int, [_p, _p]),
     "km_metrics_update": (C.c_int, [_p, _p, _p, _p, _i64, _p]),
     "km_metrics_compute": (C.c_int, [_p, _p, _p]),
+    "km_attn_stats_create": (C.c_int, [C.POINTER(_p), _i32, _i32, _i64]),
+    "km_attn_stats_destroy": (C.c_int, [_p]),
+    "km_attn_stats_shape": (C.c_int, [_p, C.POINTER(_i32), C.POINTER(_i32)]),
+    "km_attn_stats_reset": (C.c_int, [_p, _p]),
+    "km_attn_stats_update": (C.c_int, [_p, _p, _i64, _p]),
+    "km_attn_stats_compute": (C.c_int, [_p, _p, _p]),
     "km_loss_terms_create": (C.c_int, [C.POINTER(_p)]),
     "km_loss_terms_destroy": (C.c_int, [_p]),
     "km_loss_terms_reset": (C.c_int, [_p, _p]),

@@ -137,7 +137,7 @@ int km_destroy(km_handle h) {
     (void)free_legacy_streams(c);
     (void)free_train(c);
     (void)free_pipeline(c);
-    for (void* q : {(void*)c->seq_pow, (void*)c->seq_fmax, (void*)c->seq_edge, (void*)c->seq_emax, (void*)c->seq_ztrack, (void*)c->seq_zwin, (void*)c->fwd_span, (void*)c->fwd_edge})
+    for (void* q : {(void*)c->seq_pow, (void*)c->seq_fmax, (void*)c->seq_edge, (void*)c->seq_emax, (void*)c->seq_ztrack, (void*)c->seq_zwin, (void*)c->seq_attn, (void*)c->fwd_span, (void*)c->fwd_edge})
         if (q) (void)hipFree(q);
     if (c->pipe_s1) {
         (void)hipStreamDestroy((hipStream_t)c->pipe_s1); (void)hipStreamDestroy((hipStream_t)c->pipe_s2);
@@ -800,12 +800,22 @@ int km_smooth(km_handle h, float* x_dev, float* state_dev, int64_t B, int32_t fi
     return launch_smooth(h, x_dev, state_dev, B, first, stream);
 }
 
-int km_forward_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
-                     float* out_dev, float* state_dev, int32_t first, void* stream) {
+// The fused core's attention-map output exists for the plain fp32 instantiations only: refused before anything is launched
+static int attn_refused(Context* c, const char* who) {
+    if (c->fused_ok && (c->opt.core_split == 3 || c->opt.core_split == 6))
+        return fail(KM_ERR_UNSUPPORTED, "%s: the split-bf16 core (core_split %d) has no attention-map output", who, c->opt.core_split);
+    return KM_OK;
+}
+
+// km_forward_audio and km_forward_audio_attn (raw_dev / attn_dev: null in the former, which makes the launches it always made)
+static int forward_audio(km_handle h, const char* who, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
+                         float* out_dev, float* state_dev, int32_t first, float* raw_dev, float* attn_dev, void* stream) {
     if (int rc = need_dual(h)) return rc;
     Context* c = h;
     if (!audio_dev || !emotion_dev || !out_dev || B <= 0 || L <= 0)
-        return fail(KM_ERR_INVALID_ARG, "km_forward_audio: bad argument");
+        return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
+    if (attn_dev)
+        if (int rc = attn_refused(c, who)) return rc;
     const int64_t n_frames = 1 + L / c->cfg.mel.hop_length;
     if (B > c->ws_windows || n_frames > c->ws_frames)
         return fail(KM_ERR_WORKSPACE, "workspace too small for %lld windows x %lld samples: call km_reserve",
@@ -821,15 +831,15 @@ int km_forward_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, 
         if (power_path) {
             // power-mel -> dB conversion inside the encoder's tile staging: no log-mel image at all
             if (int rc = launch_mel_power(c, plan, src, stream, fuse_emo ? mel_emotion(emotion_dev, c->ws_zemo) : MelCarry{})) return rc;
-            if (int rc = launch_core_generic_power(c, plan, B, n_frames, c->ws_zemo, out_dev, nullptr, nullptr, stream)) return rc;
+            if (int rc = launch_core_generic_power(c, plan, B, n_frames, c->ws_zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
         } else if (c->NK == 80 && !c->opt.generic_staged) {
             // log-mel written straight into the packed encoder input; long + short-term rows in one contraction
             float* xp = generic_packed_x(c, B);
             if (int rc = launch_mel_packed(c, plan, src, xp, c->T, (c->KT + 15) / 16 * 16, stream)) return rc;
-            if (int rc = launch_core_generic_packed(c, xp, B, c->ws_zemo, out_dev, nullptr, nullptr, stream)) return rc;
+            if (int rc = launch_core_generic_packed(c, xp, B, c->ws_zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
         } else {
             if (int rc = launch_mel(c, plan, src, 0, c->ws_mel, c->ws_short, stream)) return rc;
-            if (int rc = launch_core_generic(c, c->ws_mel, B, n_frames, c->ws_short, c->ws_zemo, out_dev, nullptr, nullptr, stream)) return rc;
+            if (int rc = launch_core_generic(c, c->ws_mel, B, n_frames, c->ws_short, c->ws_zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
         }
         if (state_dev) return launch_smooth(c, out_dev, state_dev, B, first, stream);
         return KM_OK;
@@ -844,9 +854,20 @@ int km_forward_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, 
     if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[1], st));
     if (int rc = launch_mel_power(c, plan, src, stream, fuse_emo ? mel_emotion(emotion_dev, c->ws_zemo) : MelCarry{})) return rc;
     if (tm) { HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[2], st)); HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[3], st)); }
-    if (int rc = launch_core_fused_db(c, plan, B, n_frames, c->ws_zemo, out_dev, stream, core_workspace(state_dev, first))) return rc;
+    if (int rc = launch_core_fused_db(c, plan, B, n_frames, c->ws_zemo, out_dev, stream,
+                                      with_outputs(core_workspace(state_dev, first), raw_dev, attn_dev))) return rc;
     if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[4], st));
     return KM_OK;
+}
+
+int km_forward_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
+                     float* out_dev, float* state_dev, int32_t first, void* stream) {
+    return forward_audio(h, "km_forward_audio", audio_dev, B, L, emotion_dev, out_dev, state_dev, first, nullptr, nullptr, stream);
+}
+
+int km_forward_audio_attn(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
+                          float* out_dev, float* state_dev, int32_t first, float* raw_dev, float* attn_dev, void* stream) {
+    return forward_audio(h, "km_forward_audio_attn", audio_dev, B, L, emotion_dev, out_dev, state_dev, first, raw_dev, attn_dev, stream);
 }
 
 // km_forward_clip shares STFT frames between the windows of a batch exactly as km_train_step_clip does; behind the span
@@ -862,9 +883,9 @@ int km_forward_clip_supported(km_handle h) {
     return forward_clip_ok(h) ? 1 : 0;
 }
 
-int km_forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
-                    int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev, float* out_dev,
-                    float* state_dev, int32_t first, void* stream) {
+static int forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
+                        int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev, float* out_dev,
+                        float* state_dev, int32_t first, float* raw_dev, float* attn_dev, void* stream) {
     if (int rc = need_dual(h)) return rc;
     Context* c = h;
     if (!clip_dev || !start_frames_dev || !emotion_dev || !out_dev || B <= 0 || clip_len <= 0 || min_start_frame < 0 ||
@@ -892,7 +913,22 @@ int km_forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const 
     if (int rc = launch_clip_window_max(c, c->fwd_span, c->fwd_edge, start_frames_dev, B, min_start_frame, n_span, (int)(T + 1),
                                         stream)) return rc;
     const ClipTable tab{c->fwd_span, c->fwd_edge, (int)n_span, start_frames_dev, min_start_frame};
-    return launch_core_fused_db(c, c->mel_plans[0], B, T + 1, c->ws_zemo, out_dev, stream, core_table(&tab, state_dev, first));
+    return launch_core_fused_db(c, c->mel_plans[0], B, T + 1, c->ws_zemo, out_dev, stream,
+                                with_outputs(core_table(&tab, state_dev, first), raw_dev, attn_dev));
+}
+
+int km_forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
+                    int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev, float* out_dev,
+                    float* state_dev, int32_t first, void* stream) {
+    return forward_clip(h, clip_dev, clip_len, start_frames_dev, B, min_start_frame, max_start_frame, emotion_dev, out_dev, state_dev, first,
+                        nullptr, nullptr, stream);
+}
+
+int km_forward_clip_attn(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
+                         int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev, float* out_dev,
+                         float* state_dev, int32_t first, float* raw_dev, float* attn_dev, void* stream) {
+    return forward_clip(h, clip_dev, clip_len, start_frames_dev, B, min_start_frame, max_start_frame, emotion_dev, out_dev, state_dev, first,
+                        raw_dev, attn_dev, stream);
 }
 
 static int free_streams(Context* c) {
@@ -1299,8 +1335,13 @@ int64_t km_sequence_num_outputs(km_handle h, int64_t L, int32_t stride_frames) {
 // window -> row map (SeqTrackMap).  Null: one vector per clip (km_sequence_forward).
 struct SeqTrack { const float* track; int64_t K, first, interval, sample_offset, clip_len; };
 
+// What km_sequence_forward_attn adds to a sequence call: the pre-weight sigmoid values (B, N, 52) and the head-averaged maps
+// (B, N, 28, NK) of every window, indexed like out_dev, and / or an accumulator (km_attn_stats_*) that takes every tile's maps.
+// With an accumulator and no caller's map the maps of a tile live in seq_attn and are overwritten by the next tile.
+struct SeqOutputs { float* raw; float* attn; void* stats; };
+
 static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev, const SeqTrack* trk,
-                            int32_t stride_frames, int32_t smooth, float* out_dev, void* stream) {
+                            int32_t stride_frames, int32_t smooth, float* out_dev, void* stream, const SeqOutputs& xo = SeqOutputs{nullptr, nullptr, nullptr}) {
     Context* c = h;
     if (!c->fused_ok && !c->ws_generic)
         return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
@@ -1329,6 +1370,14 @@ static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int6
         if (int rc = grow_buffer(&c->seq_edge, &c->seq_edge_cap, total, 2 * c->NK * sizeof(float), stream, what)) return rc;
         if (int rc = grow_buffer(&c->seq_emax, &c->seq_emax_cap, total, 2 * sizeof(unsigned), stream, what)) return rc;
     }
+    const int64_t map_floats = (int64_t)28 * c->NK;
+    const bool tile_maps = xo.stats && !xo.attn;     // the maps of one tile at a time, for the accumulator alone
+    if (tile_maps)
+        if (int rc = grow_buffer(&c->seq_attn, &c->seq_attn_cap, tile, map_floats * sizeof(float), stream, "km_sequence_forward_attn: maps of one tile")) return rc;
+    // rows of tile w0: the caller's arrays at w0, or the tile buffer
+    auto raw_at = [&](int64_t w0) { return xo.raw ? xo.raw + w0 * c->NB : nullptr; };
+    auto attn_at = [&](int64_t w0) { return xo.attn ? xo.attn + w0 * map_floats : (tile_maps ? c->seq_attn : nullptr); };
+    auto stats_take = [&](int64_t w0, int64_t nw) { return xo.stats ? km_attn_stats_update(xo.stats, attn_at(w0), nw, stream) : KM_OK; };
     const float* zemo = c->ws_zemo;
     if (trk) {
         // a logit per track ROW (about nine windows share one), then one per window by the closed-form map: the core launches
@@ -1361,7 +1410,8 @@ static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int6
             if (int rc = launch_seq_window_max(c, c->seq_fmax, c->seq_emax, nw, w0, (int)nfc, (int)stride_frames, (int)N,
                                                (int)n_frames, stream)) return rc;
             if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
-                                              trk ? core_strided_win(&sc, w0) : core_strided(&sc, w0))) return rc;
+                                              with_outputs(trk ? core_strided_win(&sc, w0) : core_strided(&sc, w0), raw_at(w0), attn_at(w0)))) return rc;
+            if (int rc = stats_take(w0, nw)) return rc;
         }
         if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
         return KM_OK;
@@ -1372,15 +1422,16 @@ static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int6
         if (c->fused_ok) {
             if (int rc = launch_mel_power(c, plan, src, stream)) return rc;
             if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
-                                              trk ? core_workspace_seq_win(w0) : core_workspace_seq(w0, (int)N))) return rc;
+                                              with_outputs(trk ? core_workspace_seq_win(w0) : core_workspace_seq(w0, (int)N), raw_at(w0), attn_at(w0)))) return rc;
         } else {
             // generic shapes: staged log-mel, per-window logits gathered from the per-clip ones, GEMM-chain core
             if (int rc = launch_mel(c, plan, src, 0, c->ws_mel, c->ws_short, stream)) return rc;
             if (!trk)
                 if (int rc = launch_gather_clip_logits(c, c->ws_zemo, c->ws_zemo_win, nw, w0, (int)N, stream)) return rc;
             if (int rc = launch_core_generic(c, c->ws_mel, nw, n_frames, c->ws_short, trk ? zemo + w0 : c->ws_zemo_win, out_dev + w0 * c->NB,
-                                             nullptr, nullptr, stream)) return rc;
+                                             raw_at(w0), attn_at(w0), stream)) return rc;
         }
+        if (int rc = stats_take(w0, nw)) return rc;
     }
     if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
     return KM_OK;
@@ -1410,6 +1461,41 @@ int km_sequence_forward_track(km_handle h, const float* audio_dev, int64_t B, in
     if (int rc = need_dual(h)) return rc;
     const SeqTrack trk{track_dev, K, first_samples, interval_samples, sample_offset, clip_len};
     return sequence_forward(h, audio_dev, B, L, nullptr, &trk, stride_frames, smooth, out_dev, stream);
+}
+
+int km_sequence_forward_attn(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
+                             const float* track_dev, int64_t K, int64_t first_samples, int64_t interval_samples,
+                             int64_t sample_offset, int64_t clip_len, int32_t stride_frames, int32_t smooth,
+                             float* out_dev, float* raw_dev, float* attn_dev, void* stats, void* stream) {
+    // as in km_sequence_forward_track, the argument checks need no handle state and come first
+    if (!h || !audio_dev || !out_dev || B <= 0 || L <= 0 || stride_frames <= 0 || (emotion_dev != nullptr) == (track_dev != nullptr))
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: bad argument (exactly one of emotion_dev and track_dev)");
+    if (track_dev) {
+        const int64_t lim = (int64_t)1 << 62;
+        if (K < 1 || interval_samples < 1 || first_samples < 0 || sample_offset < 0 || clip_len > lim || clip_len < L ||
+            clip_len - L < sample_offset)
+            return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: K %lld, first %lld, interval %lld, offset %lld, clip_len %lld for a chunk of %lld",
+                        (long long)K, (long long)first_samples, (long long)interval_samples, (long long)sample_offset, (long long)clip_len,
+                        (long long)L);
+        if (K > 0x7fffffff / B) return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: %lld x %lld track rows, at most 2^31 - 1", (long long)B, (long long)K);
+    }
+    if (stats && attn_dev && !aligned16(attn_dev))
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: with an accumulator attn_dev must be 16-byte aligned");
+    if (int rc = need_dual(h)) return rc;
+    if (stats) {
+        int32_t q = 0, k = 0;
+        if (int rc = km_attn_stats_shape(stats, &q, &k)) return rc;
+        if (q != 28 || k != h->NK)
+            return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: the accumulator holds %d x %d maps, the model's are 28 x %d", q, k, h->NK);
+    }
+    if (attn_dev || stats)
+        if (int rc = attn_refused(h, "km_sequence_forward_attn")) return rc;
+    const SeqOutputs xo{raw_dev, attn_dev, stats};
+    if (track_dev) {
+        const SeqTrack trk{track_dev, K, first_samples, interval_samples, sample_offset, clip_len};
+        return sequence_forward(h, audio_dev, B, L, nullptr, &trk, stride_frames, smooth, out_dev, stream, xo);
+    }
+    return sequence_forward(h, audio_dev, B, L, emotion_dev, nullptr, stride_frames, smooth, out_dev, stream, xo);
 }
 
 }  // extern "C"

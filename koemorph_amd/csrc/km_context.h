@@ -198,6 +198,8 @@ struct Context {
     // km_sequence_forward_track: the logits of the track's rows (clips * K) and of the sequence's windows (clips * N), grow-only
     float* seq_ztrack = nullptr; float* seq_zwin = nullptr;
     int64_t seq_ztrack_cap = 0, seq_zwin_cap = 0;
+    // km_sequence_forward_attn with an accumulator and no caller's map: the maps of ONE tile (ws_windows, 28, NK), grow-only
+    float* seq_attn = nullptr; int64_t seq_attn_cap = 0;
     // eval-mode forward from a resident clip (km_forward_clip): the span image (rows, NK) and the edge image (windows, 2, NK) of
     // launch_mel_clip_span, owned by the inference context (no km_train_init needed), grow-only
     float* fwd_span = nullptr; float* fwd_edge = nullptr;
@@ -251,6 +253,7 @@ struct CoreSrc {
     const unsigned char* ready; unsigned char* started;   // streams: windows with ready[b] == 0 are skipped, first = !started[b]
     const SeqCore* seq;                      // rows of the strided images instead of the workspace, or null
     const ClipTable* tab;                    // ... of the span image through the table, or null
+    float* raw; float* attn;                 // (B, 52) / (B, 28, 80) rows of window 0 of the launch, or null (with_outputs)
 };
 // rows of the workspace (launch_mel_power wrote them), the caller's EMA state
 inline CoreSrc core_workspace(float* state, int first) { return {state, first, 0, 1, 0, nullptr, nullptr, nullptr, nullptr}; }
@@ -266,6 +269,9 @@ inline CoreSrc core_table(const ClipTable* t, float* state, int first) { return 
 inline CoreSrc core_stream(Context* c, const unsigned char* gate = nullptr) {
     return {c->ring_state, 0, 0, 1, c->stream_out_frames, gate ? gate : c->ring_ready, c->ring_started, nullptr, nullptr};
 }
+// any of the sources above with the pre-weight sigmoid values and / or the head-averaged attention map written as well (attn set:
+// the ATTN instantiation of the same source; the split-bf16 variants have none and refuse)
+inline CoreSrc with_outputs(CoreSrc s, float* raw, float* attn) { s.raw = raw; s.attn = attn; return s; }
 int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, const float* zemo, float* out, void* stream,
                          const CoreSrc& src);
 int launch_seq_window_max(Context* c, const unsigned* fmax, const unsigned* emax, int64_t nw, int64_t win0, int nfc, int stride,

@@ -933,7 +933,8 @@ static int core_attrs(Context* c) {
         const struct { const void* fn; int lds; } kernels[] = {
             {(const void*)&core_fused_kernel<false, false>, fused::LDS_BYTES}, {(const void*)&core_fused_kernel<true, false>, fused::LDS_BYTES},
             {(const void*)&core_fused_kernel<false, true>, fused::LDS_BYTES}, {(const void*)&core_fused_kernel<false, true, 2>, fused::lds_bytes(2)},
-            {(const void*)&core_fused_kernel<false, true, 3>, fused::lds_bytes(3)}, {(const void*)&core_fused_kernel<false, true, 0, true>, fused::LDS_BYTES}};
+            {(const void*)&core_fused_kernel<false, true, 3>, fused::lds_bytes(3)}, {(const void*)&core_fused_kernel<false, true, 0, true>, fused::LDS_BYTES},
+            {(const void*)&core_fused_kernel<true, true>, fused::LDS_BYTES}, {(const void*)&core_fused_kernel<true, true, 0, true>, fused::LDS_BYTES}};
         for (const auto& k : kernels) HIP_TRY(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
     }
     return KM_OK;
@@ -1041,13 +1042,19 @@ int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, co
     a.out = out; a.state = src.state; a.first = src.first; a.win0 = src.win0; a.zemo_div = src.zemo_div > 0 ? src.zemo_div : 1;
     a.melpow = c->ws_melpow; a.melmax = c->ws_melmax; a.n_frames = (int)n_frames; a.lp = plan_log_params(p);
     a.n_use = (int)(src.n_use > 0 ? src.n_use : n_frames); a.ready = src.ready; a.started = src.started;
+    a.raw = src.raw; a.attn = src.attn;
+    if (src.attn && (c->opt.core_split == 3 || c->opt.core_split == 6))
+        return fail(KM_ERR_UNSUPPORTED, "fused core: the split-bf16 variant (core_split %d) has no attention-map output", c->opt.core_split);
     if (const SeqCore* s = src.seq) { a.seq_pow = s->pow; a.seq_edge = s->edge; a.seq_nfc = s->nfc; a.seq_stride = s->stride; a.seq_n = s->n_per_clip; }
     if (const ClipTable* t = src.tab) {     // km_forward_clip: rows by table
         if (src.seq || c->opt.core_split == 3 || c->opt.core_split == 6)
             return fail(KM_ERR_UNSUPPORTED, "fused core: a start-frame table goes with neither strided images nor the split-bf16 variant");
         a.seq_pow = t->span; a.seq_edge = t->edge; a.seq_nfc = t->n_span; a.seq_stride = 0; a.seq_n = 1;
         a.seq_start = t->start; a.seq_min = t->min_start;
-        hipLaunchKernelGGL((core_fused_kernel<false, true, 0, true>), dim3((unsigned)B), dim3(fused::NT), fused::LDS_BYTES, (hipStream_t)stream, a);
+        if (src.attn)
+            hipLaunchKernelGGL((core_fused_kernel<true, true, 0, true>), dim3((unsigned)B), dim3(fused::NT), fused::LDS_BYTES, (hipStream_t)stream, a);
+        else
+            hipLaunchKernelGGL((core_fused_kernel<false, true, 0, true>), dim3((unsigned)B), dim3(fused::NT), fused::LDS_BYTES, (hipStream_t)stream, a);
         HIP_TRY(hipGetLastError());
         return KM_OK;
     }
@@ -1059,6 +1066,8 @@ int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, co
     } else if (terms == 6) {
         a.qkv_s = dv(c, "qkv_s3"); a.wce_s = dv(c, "wce_s3");
         hipLaunchKernelGGL((core_fused_kernel<false, true, 3>), dim3((unsigned)B), dim3(fused::NT), fused::lds_bytes(3), (hipStream_t)stream, a);
+    } else if (src.attn) {
+        hipLaunchKernelGGL((core_fused_kernel<true, true>), dim3((unsigned)B), dim3(fused::NT), fused::LDS_BYTES, (hipStream_t)stream, a);
     } else {
         hipLaunchKernelGGL((core_fused_kernel<false, true>), dim3((unsigned)B), dim3(fused::NT), fused::LDS_BYTES, (hipStream_t)stream, a);
     }

@@ -281,7 +281,16 @@ class Engine:
             check(self._lib.km_smooth(self._h, _ptr(x), _ptr(state), x.shape[0], 1 if first else 0,
                                       _stream_ptr(x.device)))
 
-    def forward_audio(self, audio, emotion, state=None, first: bool = True, out=None):
+    def _attention_outputs(self, lead, device):
+        """``raw`` (*lead, 52) and the head-averaged map (*lead, 28, n_mels) a ``return_attention=True`` call fills."""
+        torch = _torch()
+        raw = torch.empty(*lead, self.num_blendshapes, device=device, dtype=torch.float32)
+        attn = torch.empty(*lead, 28, self.n_mels, device=device, dtype=torch.float32)
+        return raw, attn
+
+    def forward_audio(self, audio, emotion, state=None, first: bool = True, out=None, return_attention: bool = False):
+        """audio (B, L) -> (B, 52) (km_forward_audio).  ``return_attention=True`` returns the dict of ``core_forward``:
+        'blendshapes' (the same bits), 'raw' (B, 52) and 'mel_attention_weights' (B, 28, 80) (km_forward_audio_attn)."""
         torch = _torch()
         audio = self._chk(audio, "audio", 2)
         emotion = self._chk(emotion, "emotion_features", 2)
@@ -289,6 +298,12 @@ class Engine:
         self.reserve(B, L)
         if out is None:
             out = torch.empty(B, self.num_blendshapes, device=audio.device, dtype=torch.float32)
+        if return_attention:
+            raw, attn = self._attention_outputs((B,), audio.device)
+            with torch.cuda.device(audio.device):
+                check(self._lib.km_forward_audio_attn(self._h, _ptr(audio), B, L, _ptr(emotion), _ptr(out), _ptr(state),
+                                                      1 if first else 0, _ptr(raw), _ptr(attn), _stream_ptr(audio.device)))
+            return {"blendshapes": out, "raw": raw, "mel_attention_weights": attn}
         with torch.cuda.device(audio.device):
             check(self._lib.km_forward_audio(self._h, _ptr(audio), B, L, _ptr(emotion), _ptr(out), _ptr(state),
                                              1 if first else 0, _stream_ptr(audio.device)))
@@ -298,12 +313,15 @@ class Engine:
         """km_forward_clip_supported: ``forward_clip`` runs on this engine (fused core, windows share the clip's STFT frames)."""
         return bool(self._lib.km_forward_clip_supported(self._h))
 
-    def forward_clip(self, clip, start_frames, emotion, state=None, first: bool = True, extremes=None, out=None):
+    def forward_clip(self, clip, start_frames, emotion, state=None, first: bool = True, extremes=None, out=None,
+                     return_attention: bool = False):
         """``forward_audio`` on the windows of ONE clip (a 1-D device tensor) that start at ``start_frames`` (in frames of hop
         samples; any order, repeats allowed), without the (B, window) copy and with the STFT frames the windows share computed
         once (km_forward_clip): same ``out`` and ``state`` bits as gathering the windows first.  ``emotion`` is (B, emotion_dim).
         A host sequence / CPU tensor of start frames is uploaded and its extremes taken here; a device int32 tensor comes with
-        ``extremes`` = (min, max) from the host copy its producer has, so nothing is read back on the way to the launch."""
+        ``extremes`` = (min, max) from the host copy its producer has, so nothing is read back on the way to the launch.
+        ``return_attention=True`` returns the dict of ``core_forward`` instead (km_forward_clip_attn): the same 'blendshapes' and
+        ``state`` bits, 'raw' and 'mel_attention_weights' as ``forward_audio`` gives them on the gathered windows."""
         torch = _torch()
         clip = self._chk(clip, "clip", 1)
         emotion = self._chk(emotion, "emotion_features", 2)
@@ -325,6 +343,12 @@ class Engine:
         self.reserve(B, 0)
         if out is None:
             out = torch.empty(B, self.num_blendshapes, device=clip.device, dtype=torch.float32)
+        if return_attention:
+            raw, attn = self._attention_outputs((B,), clip.device)
+            with torch.cuda.device(clip.device):
+                check(self._lib.km_forward_clip_attn(self._h, _ptr(clip), clip.shape[0], _ptr(starts), B, lo, hi, _ptr(emotion), _ptr(out),
+                                                     _ptr(state), 1 if first else 0, _ptr(raw), _ptr(attn), _stream_ptr(clip.device)))
+            return {"blendshapes": out, "raw": raw, "mel_attention_weights": attn}
         with torch.cuda.device(clip.device):
             check(self._lib.km_forward_clip(self._h, _ptr(clip), clip.shape[0], _ptr(starts), B, lo, hi, _ptr(emotion), _ptr(out),
                                             _ptr(state), 1 if first else 0, _stream_ptr(clip.device)))
@@ -361,8 +385,33 @@ class Engine:
     def pipeline_flush(self) -> None:
         check(self._lib.km_pipeline_flush(self._h, _stream_ptr(self.device)))
 
-    def sequence_forward(self, audio, emotion, stride_frames: int = 1, smooth: bool = True, max_tile: int = 2048):
-        """audio (B, L) -> (B, N, 52): one frame per window position (km_sequence_forward)."""
+    def _sequence_attn(self, audio, emotion, track, K, first, interval, offset, clip_len, stride_frames, smooth, out,
+                       return_attention, stats):
+        """km_sequence_forward_attn: the sequence call with the maps returned and / or folded into ``stats``."""
+        torch = _torch()
+        B, N = out.shape[0], out.shape[1]
+        raw = attn = None
+        if return_attention:
+            raw, attn = self._attention_outputs((B, N), audio.device)
+        acc = None
+        if stats is not None:
+            acc = stats._handle(audio.device, 28, self.n_mels)
+        with torch.cuda.device(audio.device):
+            check(self._lib.km_sequence_forward_attn(self._h, _ptr(audio), B, audio.shape[1], _ptr(emotion), _ptr(track), K, first, interval,
+                                                     offset, clip_len, stride_frames, 1 if smooth else 0, _ptr(out), _ptr(raw), _ptr(attn),
+                                                     acc, _stream_ptr(audio.device)))
+        if stats is not None:
+            stats.rows += B * N
+        if return_attention:
+            return {"blendshapes": out, "raw": raw, "mel_attention_weights": attn}
+        return out
+
+    def sequence_forward(self, audio, emotion, stride_frames: int = 1, smooth: bool = True, max_tile: int = 2048,
+                         return_attention: bool = False, stats=None):
+        """audio (B, L) -> (B, N, 52): one frame per window position (km_sequence_forward).  ``return_attention=True`` returns the
+        dict of ``core_forward`` with 'blendshapes' (B, N, 52) -- the same bits -- 'raw' (B, N, 52) and 'mel_attention_weights'
+        (B, N, 28, 80); ``stats`` (a ``koemorph_amd.metrics.AttentionStats``) takes every tile's maps on the device, and with
+        ``return_attention=False`` the tensor is returned and the maps are never materialised (km_sequence_forward_attn)."""
         torch = _torch()
         audio = self._chk(audio, "audio", 2)
         emotion = self._chk(emotion, "emotion_features", 2)
@@ -371,17 +420,21 @@ class Engine:
         W = self.mel_sequence_length * self.mel.hop_length
         self.reserve(max(B, min(B * N, max_tile)), W)
         out = torch.empty(B, N, self.num_blendshapes, device=audio.device, dtype=torch.float32)
+        if return_attention or stats is not None:
+            return self._sequence_attn(audio, emotion, None, 0, 0, 0, 0, 0, stride_frames, smooth, out, return_attention, stats)
         with torch.cuda.device(audio.device):
             check(self._lib.km_sequence_forward(self._h, _ptr(audio), B, L, _ptr(emotion), stride_frames,
                                                 1 if smooth else 0, _ptr(out), _stream_ptr(audio.device)))
         return out
 
     def sequence_forward_track(self, audio, track, first_samples: int, interval_samples: int, stride_frames: int = 1,
-                               smooth: bool = True, sample_offset: int = 0, clip_len: Optional[int] = None, max_tile: int = 2048):
+                               smooth: bool = True, sample_offset: int = 0, clip_len: Optional[int] = None, max_tile: int = 2048,
+                               return_attention: bool = False, stats=None):
         """audio (B, L), track (B, K, emotion_dim) -> (B, N, 52) as ``sequence_forward``, every window taking the track row
         ``k = 0 if e < first_samples else min((e - first_samples) // interval_samples, K - 1)`` of its clip, ``e`` being the sample
         at which the window ends in the clip (``sample_offset`` / ``clip_len`` place a chunk inside it; km_sequence_forward_track).
-        A track without rows (``K = 0``, a clip shorter than the first update) stands for one zero row per clip."""
+        A track without rows (``K = 0``, a clip shorter than the first update) stands for one zero row per clip.
+        ``return_attention`` / ``stats`` as in ``sequence_forward``."""
         torch = _torch()
         audio = self._chk(audio, "audio", 2)
         B, L = audio.shape
@@ -394,6 +447,9 @@ class Engine:
         W = self.mel_sequence_length * self.mel.hop_length
         self.reserve(max(B, min(B * N, max_tile)), W)
         out = torch.empty(B, N, self.num_blendshapes, device=audio.device, dtype=torch.float32)
+        if return_attention or stats is not None:
+            return self._sequence_attn(audio, None, track, track.shape[1], int(first_samples), int(interval_samples), int(sample_offset),
+                                       int(L if clip_len is None else clip_len), stride_frames, smooth, out, return_attention, stats)
         with torch.cuda.device(audio.device):
             check(self._lib.km_sequence_forward_track(self._h, _ptr(audio), B, L, _ptr(track), track.shape[1], int(first_samples),
                                                       int(interval_samples), int(sample_offset), int(L if clip_len is None else clip_len),

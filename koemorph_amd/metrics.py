@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from ._lib import KM_LOSS_TERM_NAMES, KM_LOSS_TERMS, KM_METRICS_COUNT, KM_METRICS_NAMES, check, load
+from ._lib import KM_LOSS_TERM_NAMES, KM_LOSS_TERMS, KM_METRICS_COUNT, KM_METRICS_NAMES, check, km_attn_stats_count, load
 
 REFERENCE_KEYS = KM_METRICS_NAMES[:16]           # BlendshapeMetrics.compute(), in the reference's order
 TEMPORAL_KEYS = ("temporal_consistency", "pred_smoothness", "target_smoothness")   # absent when one row was seen (:492)
@@ -371,6 +371,124 @@ class LossTerms:
         m["updates"] = float(v[KM_LOSS_TERMS])
         m["row_smoothness"] = float(v[KM_LOSS_TERMS + 1])
         return m
+
+
+def frequency_bands() -> Dict[str, List[int]]:
+    """``DualStreamCrossAttention.get_frequency_bands()``: the mel channels of each band."""
+    from .model.dual_stream_attention import FREQUENCY_BANDS
+    return {band: list(idx) for band, idx in FREQUENCY_BANDS.items()}
+
+
+def band_reductions(mean_map: np.ndarray, bands: Optional[Dict[str, List[int]]] = None):
+    """The two reductions the reference's AttentionVisualizer draws from a (queries, keys) map
+    (src/visualization/attention_viz.py): ``band_mean[band]`` = ``map[:, idx].mean(axis=1)`` per query (:96-98) and
+    ``band_share[band]`` = ``map[:, idx].mean()`` (:329-331)."""
+    bands = frequency_bands() if bands is None else bands
+    band_mean = {band: mean_map[:, idx].mean(axis=1) for band, idx in bands.items()}
+    band_share = {band: float(mean_map[:, idx].mean()) for band, idx in bands.items()}
+    return band_mean, band_share
+
+
+def unpack_attention_stats(vec: np.ndarray, n_queries: int, n_keys: int) -> Dict[str, object]:
+    """km_attn_stats_compute's float64 vector (KM_ATTN_STATS_COUNT(Q, K): rows, mean map, mean entropy, peak counts) as the
+    dict ``AttentionStats.compute()`` returns, band reductions included when the maps have the model's 80 keys."""
+    q, k = n_queries, n_keys
+    vec = np.asarray(vec, np.float64)
+    if vec.shape != (km_attn_stats_count(q, k),):
+        raise ValueError(f"expected {km_attn_stats_count(q, k)} values for {q} x {k} maps, got {vec.shape}")
+    mean_map = vec[1:1 + q * k].reshape(q, k).copy()
+    res: Dict[str, object] = {"rows": int(vec[0]), "mean_map": mean_map, "entropy": vec[1 + q * k:1 + q * k + q].copy(),
+                              "peak_hist": np.rint(vec[1 + q * k + q:]).astype(np.int64).reshape(q, k)}
+    bands = frequency_bands()
+    if k > max(max(idx) for idx in bands.values()):
+        res["band_mean"], res["band_share"] = band_reductions(mean_map, bands)
+    return res
+
+
+class AttentionStats:
+    """What the reference's AttentionVisualizer reduces the mel stream's attention maps to, accumulated on the device
+    (``km_attn_stats_*``, koemorph_amd/csrc/km_attn_stats.hip): the mean map, the mean entropy per query, a histogram of each
+    query's peak key, and the band reductions of the mean map.  ``update`` takes (..., n_queries, n_keys) device maps;
+    ``Engine.sequence_forward(..., stats=acc)`` feeds it tile by tile without the maps ever existing as a whole.  ``update``
+    enqueues on the current stream and returns; ``compute`` enqueues the finalisation and does the only readback.
+    ``max_rows_per_launch`` = 0 is the library's default; larger updates are cut into pieces inside."""
+
+    def __init__(self, n_queries: int = 28, n_keys: int = 80, max_rows_per_launch: int = 0):
+        self.n_queries, self.n_keys, self.max_rows_per_launch = int(n_queries), int(n_keys), int(max_rows_per_launch)
+        self._acc = C.c_void_p()
+        self._device = None
+        self._lib = None
+        self.rows = 0
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self._device).cuda_stream
+
+    def _handle(self, device, n_queries: Optional[int] = None, n_keys: Optional[int] = None):
+        """The accumulator on ``device`` (created on first use), after checking that it holds maps of the caller's shape."""
+        import torch
+        if n_queries is not None and (n_queries, n_keys) != (self.n_queries, self.n_keys):
+            raise ValueError(f"AttentionStats holds {self.n_queries} x {self.n_keys} maps, got {n_queries} x {n_keys}")
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._acc and self._device != device:
+            if self.rows:
+                raise ValueError("one accumulation mixes devices; reset() first")
+            self.close()
+        if not self._acc:
+            self._lib = load()
+            self._device = device
+            with torch.cuda.device(device):
+                check(self._lib.km_attn_stats_create(C.byref(self._acc), self.n_queries, self.n_keys, self.max_rows_per_launch))
+        return self._acc
+
+    def close(self):
+        if self._acc:
+            import torch
+            torch.cuda.synchronize(self._device)
+            self._lib.km_attn_stats_destroy(self._acc)
+            self._acc = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self.rows = 0
+        if self._acc:
+            import torch
+            with torch.cuda.device(self._device):
+                check(self._lib.km_attn_stats_reset(self._acc, self._stream()))
+
+    def update(self, maps):
+        """Fold (..., n_queries, n_keys) float32 device maps in; any leading shape, also empty."""
+        import torch
+        if not isinstance(maps, torch.Tensor) or not maps.is_cuda:
+            raise ValueError("AttentionStats takes device tensors (the float64 restatement for host data is tests/attn_stats_cases.py)")
+        if maps.dim() < 2 or tuple(maps.shape[-2:]) != (self.n_queries, self.n_keys):
+            raise ValueError(f"expected (..., {self.n_queries}, {self.n_keys}) maps, got {tuple(maps.shape)}")
+        maps = maps.detach().to(torch.float32).contiguous()
+        n = int(maps.numel() // (self.n_queries * self.n_keys))
+        acc = self._handle(maps.device)
+        with torch.cuda.device(self._device):
+            check(self._lib.km_attn_stats_update(acc, maps.data_ptr() if n else None, n, self._stream()))
+        self.rows += n
+
+    def compute(self) -> Dict[str, object]:
+        """'rows', 'mean_map' (Q, K) float64, 'entropy' (Q,), 'peak_hist' (Q, K) int64, 'band_mean' {band: (Q,)} and 'band_share'
+        {band: float} over every map since the last reset; all zero before any.  One readback."""
+        import torch
+        n = km_attn_stats_count(self.n_queries, self.n_keys)
+        if not self._acc:
+            return unpack_attention_stats(np.zeros(n), self.n_queries, self.n_keys)
+        with torch.cuda.device(self._device):
+            out = torch.empty(n, device=self._device, dtype=torch.float64)
+            check(self._lib.km_attn_stats_compute(self._acc, out.data_ptr(), self._stream()))
+            vec = out.cpu().numpy()
+        return unpack_attention_stats(vec, self.n_queries, self.n_keys)
 
 
 def compute_lip_sync_metrics(pred_blendshapes, target_blendshapes, audio_features=None) -> Dict[str, float]:

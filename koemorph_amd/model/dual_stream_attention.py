@@ -43,6 +43,8 @@ ARKIT_BLENDSHAPES = [
 ]
 MOUTH_INDICES = [i for i, name in enumerate(ARKIT_BLENDSHAPES) if name in MOUTH_BLENDSHAPES]
 EXPRESSION_INDICES = [i for i in range(52) if i not in MOUTH_INDICES]
+# mel channels per frequency band (dual_stream_attention.py:282-290, get_frequency_bands)
+FREQUENCY_BANDS = {'low': range(0, 20), 'mid_low': range(20, 40), 'mid_high': range(40, 60), 'high': range(60, 80)}
 
 
 class DualStreamCrossAttention(nn.Module):
@@ -186,5 +188,4 @@ class DualStreamCrossAttention(nn.Module):
         return result
 
     def get_frequency_bands(self) -> Dict[str, List[int]]:
-        return {'low': list(range(0, 20)), 'mid_low': list(range(20, 40)),
-                'mid_high': list(range(40, 60)), 'high': list(range(60, 80))}
+        return {band: list(idx) for band, idx in FREQUENCY_BANDS.items()}

@@ -5,7 +5,9 @@
 frame per window position (window = mel_sequence_length frames, stride = stride_frames).  The reference
 walks the positions in a Python loop and recomputes the whole 257-frame mel on the CPU for each one
 (:101-145); here every window of every clip is one workgroup of the same HIP kernels, addressed in place
-inside the clip (km_sequence_forward), followed by an EMA scan along the frame axis.
+inside the clip (km_sequence_forward), followed by an EMA scan along the frame axis.  ``return_attention=True`` is the same
+call with the head-averaged attention map of every window written as well (km_sequence_forward_attn): 'mel_attention_weights'
+(B, T_out, 28, 80), 'emotion_attention_weights' all ones, and the same 'blendshapes' bits.
 
 Not in the reference: ``clip_emotion`` (a ``koemorph_amd.features.ClipEmotion``) or ``forward(emotion_track=...)`` give every
 window the row of the clip's eGeMAPS emotion track that a live stream would hold when the window ends -- the input
@@ -64,7 +66,9 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
 
     def forward(self, audio: torch.Tensor, return_attention: bool = False,
                 emotion_features: Optional[torch.Tensor] = None,
-                emotion_track: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                emotion_track: Optional[torch.Tensor] = None, attention_stats=None) -> Dict[str, torch.Tensor]:
+        """``attention_stats`` (not in the reference): a ``koemorph_amd.metrics.AttentionStats`` that takes the attention map of
+        every window on the device, tile by tile, whether or not the maps are returned."""
         if audio.dim() != 2:
             raise ValueError(f"Expected 2D input, got {audio.dim()}D")
         if emotion_track is not None and emotion_features is not None:
@@ -89,39 +93,26 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
         self.reset_temporal_state()                                    # :99
         self.dual_stream_attention.require_eval_mode()
         results: Dict[str, object] = {}
-        if not return_attention and self.shard_across_ranks:
+        if self.shard_across_ranks:
+            # with return_attention every rank computes the whole sequence: the maps are not gathered
             from .. import parallel
             seq = parallel.sequence_apply(eng, audio, emotion_features, self.stride_frames, smooth=self.use_temporal_smoothing,
-                                          emotion_track=emotion_track, track_shape=mapping)
-        elif not return_attention and mapping is not None:
+                                          emotion_track=emotion_track, track_shape=mapping, return_attention=return_attention,
+                                          stats=attention_stats)
+        elif mapping is not None:
             seq = eng.sequence_forward_track(audio, emotion_track, mapping[0], mapping[1], self.stride_frames,
-                                             smooth=self.use_temporal_smoothing)
-        elif not return_attention:
-            seq = eng.sequence_forward(audio, emotion_features, self.stride_frames,
-                                       smooth=self.use_temporal_smoothing)
+                                             smooth=self.use_temporal_smoothing, return_attention=return_attention,
+                                             stats=attention_stats)
         else:
-            # attention maps are a visualisation aid: walk the positions like the reference does
-            from ..engine import sequence_track_row
-            num_frames = audio_length // self.hop_length
-            n_out = max(1, (num_frames - self.window_frames) // self.stride_frames + 1)
-            frames, mel_att, emo_att = [], [], []
-            for i in range(n_out):
-                s = i * self.stride_samples
-                e = min(s + self.window_samples, audio_length)
-                win = audio[:, s:e]
-                if e - s < self.window_samples:                        # zero-pad the last window (:111-115)
-                    win = torch.nn.functional.pad(win, (0, self.window_samples - (e - s)))
-                if mapping is not None:                                # the row the fused call gives this window
-                    k = sequence_track_row(i, emotion_track.shape[1], mapping[0], mapping[1], 0, audio_length, self.stride_frames,
-                                           self.window_frames, self.hop_length)
-                    emotion_features = emotion_track[:, k].contiguous()
-                o = SimplifiedDualStreamModel.forward(self, win.contiguous(), True, emotion_features)
-                frames.append(o['blendshapes'])
-                mel_att.append(o['mel_attention_weights'])
-                emo_att.append(o['emotion_attention_weights'])
-            seq = torch.stack(frames, dim=1)
-            results['mel_attention_weights'] = torch.stack(mel_att, dim=1)
-            results['emotion_attention_weights'] = torch.stack(emo_att, dim=1)
+            seq = eng.sequence_forward(audio, emotion_features, self.stride_frames,
+                                       smooth=self.use_temporal_smoothing, return_attention=return_attention,
+                                       stats=attention_stats)
+        if return_attention:
+            # one call for every window (km_sequence_forward_attn): the blendshapes are the bits of the plain call
+            results['mel_attention_weights'] = seq['mel_attention_weights']
+            # softmax over a single key (reference dual_stream_attention.py:234-239)
+            results['emotion_attention_weights'] = torch.ones(seq['raw'].shape[0], seq['raw'].shape[1], 24, 1, device=audio.device)
+            seq = seq['blendshapes']
         if self.use_temporal_smoothing and seq.shape[1] > 0:
             self.prev_blendshapes = seq[:, -1].clone()                 # the state the reference is left with
         results['blendshapes'] = seq

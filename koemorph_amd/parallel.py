@@ -99,7 +99,8 @@ def sequence_chunk(L: int, hop: int, window_frames: int, stride_frames: int, n_o
 
 
 def sequence_apply(engine, audio: torch.Tensor, emotion: Optional[torch.Tensor], stride_frames: int = 1, smooth: bool = True,
-                   emotion_track: Optional[torch.Tensor] = None, track_shape: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+                   emotion_track: Optional[torch.Tensor] = None, track_shape: Optional[Tuple[int, int]] = None,
+                   return_attention: bool = False, stats=None):
     """``SequentialDualStreamModel.forward`` of ONE batch of clips over all ranks (reference
     src/model/sequential_dual_stream_model.py:84-151): every rank holds the clips, computes a contiguous chunk of each clip's
     output frames WITHOUT smoothing (``engine.sequence_forward`` on the chunk's samples + one window of halo), the chunks are
@@ -110,13 +111,22 @@ def sequence_apply(engine, audio: torch.Tensor, emotion: Optional[torch.Tensor],
 
     ``emotion_track`` (B, K, emotion_dim) with ``track_shape = (first_samples, interval_samples)`` replaces the one vector per clip
     by a row per window (``engine.sequence_forward_track``): every rank passes its chunk's ``sample_offset = s0`` and
-    ``clip_len = L``, so a window takes the row it takes in the whole clip."""
+    ``clip_len = L``, so a window takes the row it takes in the whole clip.
+
+    ``return_attention=True`` (the engine's dict: 'blendshapes', 'raw', 'mel_attention_weights') and ``stats`` (an
+    ``AttentionStats`` fed on the device) are NOT sharded: every rank computes the whole sequence and its maps (208 bytes per
+    frame are worth gathering, 9 KB per frame of maps are not yet)."""
     if emotion_track is not None:
         if emotion is not None:
             raise ValueError("emotion and emotion_track both produce the emotion input: pass one of them")
         if track_shape is None:
             raise ValueError("emotion_track needs track_shape = (first_samples, interval_samples)")
         first, interval = int(track_shape[0]), int(track_shape[1])
+    if return_attention or stats is not None:
+        if emotion_track is not None:
+            return engine.sequence_forward_track(audio, emotion_track, first, interval, stride_frames, smooth=smooth,
+                                                 return_attention=return_attention, stats=stats)
+        return engine.sequence_forward(audio, emotion, stride_frames, smooth=smooth, return_attention=return_attention, stats=stats)
     if not collectives_active():
         if emotion_track is not None:
             return engine.sequence_forward_track(audio, emotion_track, first, interval, stride_frames, smooth=smooth)

@@ -1,17 +1,21 @@
 """Offline rendering of one audio file with a ``train_sequential`` checkpoint:
 
     python -m koemorph_amd.scripts.render_sequential --model_path ckpt.pth --input_audio a.wav --output_json out.jsonl
-                                                     [--stride 1] [--emotion egemaps|noise]
+                                                     [--stride 1] [--emotion egemaps|noise] [--attention-summary summary.json]
 
 The clip goes through ``SequentialDualStreamModel.forward`` (one output frame per window position, EMA along the clip) and every
 frame is written as one ``{"timestamp", "blendshapes"}`` line, encoded by ``koemorph_amd.wire`` as the streaming scripts encode
 theirs.  A frame's timestamp is the time at which its window ends.  ``--emotion egemaps`` gives every window the row of the
 clip's eGeMAPS emotion track a live stream would hold at that time (``ClipEmotion``), the input ``train_sequential --emotion
 egemaps`` trains on; ``noise`` is the reference's extraction-failure fallback, one ``0.1 * randn`` vector per clip.
+``--attention-summary`` writes what the reference's AttentionVisualizer reduces the clip's attention maps to (``AttentionStats``:
+mean map, mean entropy and peak histogram per mouth query, mean and share per frequency band) as one JSON object; the maps are
+reduced on the device tile by tile, no (frames, 28, 80) array is made.
 """
 from __future__ import annotations
 
 import argparse
+import json
 import logging
 from pathlib import Path
 from typing import Optional
@@ -22,6 +26,7 @@ import torch
 from .. import wire
 from ..data.sequential_dataset import _load_wav
 from ..features.clip_emotion import ClipEmotion
+from ..metrics import AttentionStats
 from ..model import SequentialDualStreamModel
 
 logger = logging.getLogger(__name__)
@@ -65,11 +70,24 @@ def frame_timestamps(n_frames: int, audio_length: int, model: SequentialDualStre
     return np.minimum(ends, audio_length) / float(model.sample_rate)
 
 
-def render(model: SequentialDualStreamModel, audio: np.ndarray, output_json) -> int:
-    """audio (L) -> one JSONL line per output frame; returns the number of frames written."""
+def attention_summary(stats: AttentionStats) -> dict:
+    """``AttentionStats.compute()`` with lists for arrays."""
+    plain = lambda v: v.tolist() if isinstance(v, np.ndarray) else v
+    return {k: ({b: plain(x) for b, x in v.items()} if isinstance(v, dict) else plain(v)) for k, v in stats.compute().items()}
+
+
+def render(model: SequentialDualStreamModel, audio: np.ndarray, output_json, attention_summary_json=None) -> int:
+    """audio (L) -> one JSONL line per output frame; returns the number of frames written.  ``attention_summary_json``: where
+    the attention statistics of the rendered windows go."""
     dev = next(model.parameters()).device
+    stats = AttentionStats() if attention_summary_json is not None else None
     with torch.no_grad():
-        out = model(torch.from_numpy(np.ascontiguousarray(audio, np.float32))[None].to(dev))
+        out = model(torch.from_numpy(np.ascontiguousarray(audio, np.float32))[None].to(dev), attention_stats=stats)
+    if stats is not None:
+        path = Path(attention_summary_json)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(json.dumps(attention_summary(stats)))
+        stats.close()
     frames = out["blendshapes"][0].cpu().numpy()
     lines = wire.format_frames(frames, frame_timestamps(frames.shape[0], audio.shape[0], model))
     output_json = Path(output_json)
@@ -87,6 +105,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--output_json", required=True)
     p.add_argument("--stride", type=int, default=1, help="frames between two window positions")
     p.add_argument("--emotion", choices=("egemaps", "noise"), default="egemaps")
+    p.add_argument("--attention-summary", default=None, metavar="PATH",
+                   help="write the clip's attention statistics (AttentionStats.compute()) as JSON")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -96,7 +116,7 @@ def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     model = load_model(args.model_path, args.stride, args.emotion, args.device)
     audio = _load_wav(Path(args.input_audio), model.sample_rate)
-    n = render(model, audio, args.output_json)
+    n = render(model, audio, args.output_json, args.attention_summary)
     logger.info("%d frames (%.2f s of audio, stride %d, emotion %s) -> %s", n, audio.shape[0] / model.sample_rate, args.stride,
                 args.emotion, args.output_json)
     return 0
