@@ -849,6 +849,39 @@ int km_loss_terms_update(void* acc, const km_loss_config* cfg, float mse_weight,
                          const float* pred_dev, const float* target_dev, int64_t N, float* terms_dev, void* stream);
 int km_loss_terms_compute(void* acc, float* out_dev, void* stream);
 
+/* ---- sample-rate conversion: whole clips and stateful streams, on the device -------------------------------------------
+ * Replaces the host-side conversion in front of every 16 kHz entry point (the reference's librosa.resample in
+ * src/data/sequential_dataset.py:100-101; here scipy.signal.resample_poly) for audio that arrives at its capture rate.
+ * up / down is the reduced ratio rate_out / rate_in.  The taps are the caller's: for resample_poly's filter,
+ *     half_len = 10 max(up, down),   h[k] = up * fc sinc(fc (k - half_len)) kaiser_5.0[k] / (sum of those),   fc = 1 / max(up, down),
+ * k = 0 .. 2 half_len (koemorph_amd.features.resample.resample_filter); half_len is taken as (n_taps - 1) / 2.  The library rounds
+ * them to float32 once.  Output m of an input x[0..N) is
+ *     y[m] = sum_j x[j] h[m down - j up + half_len]      (tap index within [0, 2 half_len], x zero outside [0, N)),
+ * one float32 fmaf chain over ascending j; n_out(N) = ceil(N up / down).  A stream that has consumed N samples has emitted the
+ * max(0, ceil((N up - half_len) / down)) outputs whose samples have all arrived; its state is the last ceil(2 half_len / up)
+ * samples and one bounded integer, so nothing wraps however long it runs.  The same output index has the same bits from
+ * km_resample_clip, from km_resampler_push under any chunking and from km_resampler_flush.
+ *   km_resampler_create         n_streams 1 .. 65535; n_taps odd; up != down; KM_ERR_UNSUPPORTED when the polyphase table and one
+ *                               tile's input span do not fit the kernels' 64 KiB of LDS (8000, 11025, 22050, 24000, 32000,
+ *                               44100, 48000 and 96000 -> 16000 do)
+ *   km_resampler_out_max        ceil(n_in_max up / down) + 1: a row length that holds whatever a push of n_in_max samples emits
+ *   km_resampler_push           samples_dev (n_streams, n_per_stream), counts_dev (n_streams) or NULL (all) as in km_stream_feed;
+ *                               stream s's new outputs go to out_dev + s out_stride, their number to out_counts_dev[s]; a stream
+ *                               that brings nothing is untouched and reports 0.  out_stride >= ceil(n_per_stream up / down)
+ *   km_resampler_flush          the streams of mask_dev (NULL: all) emit what they still owe up to n_out(N), as though zeros
+ *                               followed, and are left reset; the others report 0.  out_stride >= ceil(half_len / down)
+ *   km_resampler_reset_streams  those streams become freshly created ones (NULL: all)
+ *   km_resample_clip            clip_dev (n_in) -> out_dev (n_out), n_out == ceil(n_in up / down); uses no stream state
+ * push / flush / reset_streams / clip launch on `stream`, neither allocate nor synchronise nor read back, and can be captured. */
+int km_resampler_create(void** rs, int64_t n_streams, int32_t up, int32_t down, const double* taps_host, int64_t n_taps);
+int km_resampler_destroy(void* rs);
+int km_resampler_out_max(void* rs, int64_t n_in_max, int64_t* n_out_max);
+int km_resampler_push(void* rs, const float* samples_dev, int64_t n_per_stream, const int32_t* counts_dev,
+                      float* out_dev, int64_t out_stride, int32_t* out_counts_dev, void* stream);
+int km_resampler_flush(void* rs, const uint8_t* mask_dev, float* out_dev, int64_t out_stride, int32_t* out_counts_dev, void* stream);
+int km_resampler_reset_streams(void* rs, const uint8_t* mask_dev, void* stream);
+int km_resample_clip(void* rs, const float* clip_dev, int64_t n_in, float* out_dev, int64_t n_out, void* stream);
+
 /* ---- run-time switches ---------------------------------------------------------------------------
  * Replaces what would be module attributes / environment switches on the reference side (the reference has none on
  * this path: every switch selects between two implementations of the SAME arithmetic, for A/B timing and for the

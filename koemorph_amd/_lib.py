@@ -220,7 +220,14 @@ SIGNATURES = {
     "km_emotion_clip_build": (C.c_int, [_p, _p, _i64, _p, _p, _p]),
     "km_emotion_clip_build_batch": (C.c_int, [_p, _p, _i64, _i64, _p, _p, _p]),
     "km_emotion_clip_rows": (C.c_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p]),
-    "km_enable_stage_timing": (C.c_int, [_h, _i32]),
+    "km_resampler_create": (C.c_int, [C.POINTER(_p), _i64, _i32, _i32, C.POINTER(C.c_double), _i64]),
+    "km_resampler_destroy": (C.c_int, [_p]),
+    "km_resampler_out_max": (C.c_int, [_p, _i64, C.POINTER(_i64)]),
+    "km_resampler_push": (C.c_int, [_p, _p, _i64, _p, _p, _i64, _p, _p]),
+    "km_resampler_flush": (C.c_int, [_p, _p, _p, _i64, _p, _p]),
+    "km_resampler_reset_streams": (C.c_int, [_p, _p, _p]),
+    "km_resample_clip": (C.c_int, [_p, _p, _i64, _p, _i64, _p]),
+    "km_enable_stage_timing":(C.c_int, [_h, _i32]),
     "km_stage_times": (C.c_int, [_h, C.POINTER(C.c_float)]),
     "km_debug_buffer": (C.c_int, [_h, C.c_char_p, _p, C.POINTER(_i64)]),
 }

@@ -50,14 +50,19 @@ def detect_source_fps(timestamps) -> float:
     return float(source_fps)
 
 
-def _load_wav(path: Path, sample_rate: int) -> np.ndarray:
+def _read_wav(path: Path) -> Tuple[int, np.ndarray]:
+    """(the file's own rate, mono float32 samples): the mono mix and integer -> float, no rate conversion."""
     from scipy.io import wavfile
     sr, data = wavfile.read(str(path))
     if data.ndim > 1:
         data = data.mean(axis=1)
     if np.issubdtype(data.dtype, np.integer):
         data = data.astype(np.float32) / float(np.iinfo(data.dtype).max + 1)
-    data = data.astype(np.float32)
+    return int(sr), data.astype(np.float32)
+
+
+def _load_wav(path: Path, sample_rate: int) -> np.ndarray:
+    sr, data = _read_wav(path)
     if sr != sample_rate:          # the reference calls librosa.resample here (:100-101); polyphase is the stand-in
         from math import gcd
         from scipy.signal import resample_poly
@@ -77,10 +82,14 @@ class SequentialKoeMorphDataset:
     def __init__(self, data_dir: Union[str, Path], window_frames: int = 256, stride_frames: int = 1,
                  sample_rate: int = 16000, target_fps: int = 30, shuffle_files: bool = True, loop_dataset: bool = True,
                  max_files: Optional[int] = None, batch_size: int = 8, device: Union[str, torch.device] = "cuda",
-                 resident_windows: bool = False):
+                 resident_windows: bool = False, device_resample: bool = False):
         """``resident_windows``: iterate ``index_batch`` instead of ``gather`` -- batches name their windows inside the resident
-        clip (for ``Trainer.step_clip``) instead of carrying a copy of their audio."""
+        clip (for ``Trainer.step_clip``) instead of carrying a copy of their audio.  ``device_resample``: a WAV file at another
+        rate is uploaded as it is and converted on the device (``koemorph_amd.features.Resampler``, the filter of
+        ``resample_poly`` in float32) instead of on the host before the upload."""
         self.resident_windows = resident_windows
+        self.device_resample = device_resample
+        self._resamplers: Dict[int, object] = {}
         self.data_dir = Path(data_dir)
         self.window_frames, self.stride_frames = window_frames, stride_frames
         self.sample_rate, self.target_fps = sample_rate, target_fps
@@ -125,10 +134,22 @@ class SequentialKoeMorphDataset:
                                                self._stream()))
         return out
 
+    def _load_audio(self, audio_path: Path) -> torch.Tensor:
+        if not self.device_resample:
+            return torch.from_numpy(_load_wav(audio_path, self.sample_rate)).to(self.device)
+        sr, data = _read_wav(audio_path)
+        audio = torch.from_numpy(data).to(self.device)
+        if sr == self.sample_rate or audio.shape[0] == 0:
+            return audio
+        if sr not in self._resamplers:
+            from ..features.resample import Resampler
+            self._resamplers[sr] = Resampler(sr, self.sample_rate, self.device)
+        return self._resamplers[sr].clip(audio)
+
     def clip(self, file_idx: int) -> _Clip:
         if file_idx not in self._clips:
             audio_path, jsonl_path = self.file_pairs[file_idx]
-            audio = torch.from_numpy(_load_wav(audio_path, self.sample_rate)).to(self.device)
+            audio = self._load_audio(audio_path)
             rows, ts = load_jsonl_labels(jsonl_path)
             source_fps = detect_source_fps(ts)
             labels = torch.from_numpy(rows).to(self.device)

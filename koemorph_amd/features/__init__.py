@@ -9,3 +9,6 @@ __all__ += ["AudioBuffer", "OpenSMILEeGeMAPSExtractor", "create_opensmile_extrac
 from .clip_emotion import ClipEmotion  # noqa: E402
 
 __all__ += ["ClipEmotion"]
+from .resample import Resampler, StreamPlan, resample_filter, resample_ratio  # noqa: E402
+
+__all__ += ["Resampler", "StreamPlan", "resample_filter", "resample_ratio"]

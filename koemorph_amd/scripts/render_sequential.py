@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from .. import wire
-from ..data.sequential_dataset import _load_wav
+from ..data.sequential_dataset import _load_wav, _read_wav
 from ..features.clip_emotion import ClipEmotion
 from ..metrics import AttentionStats
 from ..model import SequentialDualStreamModel
@@ -76,13 +76,24 @@ def attention_summary(stats: AttentionStats) -> dict:
     return {k: ({b: plain(x) for b, x in v.items()} if isinstance(v, dict) else plain(v)) for k, v in stats.compute().items()}
 
 
-def render(model: SequentialDualStreamModel, audio: np.ndarray, output_json, attention_summary_json=None) -> int:
-    """audio (L) -> one JSONL line per output frame; returns the number of frames written.  ``attention_summary_json``: where
-    the attention statistics of the rendered windows go."""
+def load_audio_device_resample(path, sample_rate: int, device) -> torch.Tensor:
+    """The file at its own rate, uploaded and converted to ``sample_rate`` on the device (``koemorph_amd.features.Resampler``)."""
+    from ..features.resample import Resampler
+    sr, data = _read_wav(Path(path))
+    audio = torch.from_numpy(data).to(device)
+    if sr == sample_rate or audio.shape[0] == 0:
+        return audio
+    return Resampler(sr, sample_rate, audio.device).clip(audio)
+
+
+def render(model: SequentialDualStreamModel, audio, output_json, attention_summary_json=None) -> int:
+    """audio (L), a NumPy array or a tensor already on the device -> one JSONL line per output frame; returns the number of frames
+    written.  ``attention_summary_json``: where the attention statistics of the rendered windows go."""
     dev = next(model.parameters()).device
     stats = AttentionStats() if attention_summary_json is not None else None
     with torch.no_grad():
-        out = model(torch.from_numpy(np.ascontiguousarray(audio, np.float32))[None].to(dev), attention_stats=stats)
+        x = audio.to(dev, torch.float32) if isinstance(audio, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(audio, np.float32)).to(dev)
+        out = model(x[None], attention_stats=stats)
     if stats is not None:
         path = Path(attention_summary_json)
         path.parent.mkdir(parents=True, exist_ok=True)
@@ -107,6 +118,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--emotion", choices=("egemaps", "noise"), default="egemaps")
     p.add_argument("--attention-summary", default=None, metavar="PATH",
                    help="write the clip's attention statistics (AttentionStats.compute()) as JSON")
+    p.add_argument("--device-resample", dest="device_resample", action="store_true",
+                   help="upload the file at its own rate and convert it to the model's rate on the device")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -115,7 +128,10 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     model = load_model(args.model_path, args.stride, args.emotion, args.device)
-    audio = _load_wav(Path(args.input_audio), model.sample_rate)
+    if args.device_resample:
+        audio = load_audio_device_resample(args.input_audio, model.sample_rate, next(model.parameters()).device)
+    else:
+        audio = _load_wav(Path(args.input_audio), model.sample_rate)
     n = render(model, audio, args.output_json, args.attention_summary)
     logger.info("%d frames (%.2f s of audio, stride %d, emotion %s) -> %s", n, audio.shape[0] / model.sample_rate, args.stride,
                 args.emotion, args.output_json)

@@ -337,6 +337,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resident-clip", dest="resident_clip", action="store_true",
                    help="train from the clips resident in GPU memory (Trainer.step_clip): no window copies, the STFT frames the "
                         "windows of a batch share are computed once; same losses and weights")
+    p.add_argument("--device-resample", dest="device_resample", action="store_true",
+                   help="WAV files at another rate are uploaded as they are and converted to 16 kHz on the device")
     p.add_argument("--loss-components", dest="loss_components", action="store_true",
                    help="validation reports the loss by component (LossTerms) and per-sequence loss / smoothness; with "
                         "--resident-clip the validation forward runs from the resident clip (Engine.forward_clip)")
@@ -358,7 +360,7 @@ def main(argv=None):
     eng.load_state_dict(synth.make_core_params(0, T=args.window_frames, style="init"))
     eng.finalize(device)
     kw = dict(window_frames=args.window_frames, stride_frames=args.stride_frames, shuffle_files=False, loop_dataset=False,
-              batch_size=args.batch_size, device=device, max_files=args.max_files)
+              batch_size=args.batch_size, device=device, max_files=args.max_files, device_resample=args.device_resample)
     egemaps = args.emotion == "egemaps"                  # the track is read from the resident clip: every batch must name it
     train = SequentialKoeMorphDataset(args.data_dir, resident_windows=args.resident_clip or egemaps, **kw)
     val = SequentialKoeMorphDataset(args.val_dir, resident_windows=(args.resident_clip and args.loss_components) or egemaps, **kw) \

@@ -469,3 +469,93 @@ class StreamEmotion:
             self._g_counts.fill_(self._g_samples.shape[1])
         self._graph.replay()
         return self.emotion, self.updated
+
+
+class StreamResampler:
+    """Audio of ``n_streams`` streams at its capture rate -> the 16 kHz every other entry point takes, with the per-stream filter
+    state on the device (km_resampler_*; the filter and the laws: ``koemorph_amd.features.resample``).  ``push`` takes chunks of
+    any size -- ``(n_streams, n)`` samples plus per-stream counts, the convention of ``ChunkedStreamEngine.feed`` and
+    ``StreamEmotion.push`` -- and returns each stream's newly determined outputs and their number, which go unchanged into those
+    two.  The outputs are those of ``Resampler.clip`` on the concatenated input, bit for bit and whatever the chunking: a stream lags
+    its input by ``half_len / up`` samples (30 at 48 kHz) and ``flush`` emits that remainder.  No call allocates or synchronises, so
+    ``push`` -> ``feed`` -> ``step`` captures into one ``torch.cuda.graph``."""
+
+    def __init__(self, n_streams: int, rate_in: int, rate_out: int = 16000, device="cuda"):
+        from .features import resample as _rs
+        self.n_streams, self.rate_in, self.rate_out = n_streams, int(rate_in), int(rate_out)
+        self.up, self.down = _rs._check_rate_pair(rate_in, rate_out)
+        if n_streams < 1:
+            raise ValueError(f"expected n_streams >= 1, got {n_streams}")
+        if not torch.cuda.is_available():
+            raise _lib.KoeMorphError(_lib.KM_ERR_HIP, "no GPU visible: the resampler has no CPU fallback")
+        self.device = torch.device(device if device not in (None, "cpu", "auto") else "cuda")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._lib = _lib.load()
+        with torch.cuda.device(self.device):
+            self._h, self.half_len = _rs.create_handle(self._lib, n_streams, self.up, self.down)
+        self._flush_max = -(-self.half_len // self.down)
+        self._bufs = {}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.km_resampler_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def out_max(self, n: int) -> int:
+        """The row length that holds whatever a push of ``n`` samples per stream emits: ceil(n up / down) + 1."""
+        v = C.c_int64()
+        check(self._lib.km_resampler_out_max(self._h, n, C.byref(v)))
+        return v.value
+
+    def _out(self, width: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One (out, out_counts) pair per row length, created on first use and kept: what a captured graph wrote into stays valid."""
+        if width not in self._bufs:
+            self._bufs[width] = (torch.zeros(self.n_streams, width, device=self.device),
+                                 torch.zeros(self.n_streams, dtype=torch.int32, device=self.device))
+        return self._bufs[width]
+
+    def push(self, samples: torch.Tensor, counts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """samples (n_streams, n) fp32 on the device; counts (n_streams) int32 on the device: how many of the n samples each stream
+        brings (default: all) -> (out (n_streams, out_max(n)), out_counts (n_streams) int32), owned by this object and overwritten by
+        the next push of the same n.  A stream that brings nothing is untouched and reports 0."""
+        if samples.dim() != 2 or samples.shape[0] != self.n_streams or samples.dtype != torch.float32 or samples.shape[1] < 1:
+            raise ValueError(f"expected ({self.n_streams}, n) float32 samples, got {tuple(samples.shape)} {samples.dtype}")
+        if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (self.n_streams,)):
+            raise ValueError(f"expected ({self.n_streams},) int32 counts")
+        samples = samples.contiguous()
+        out, out_counts = self._out(self.out_max(samples.shape[1]))
+        check(self._lib.km_resampler_push(self._h, _ptr(samples), samples.shape[1], _ptr(counts.contiguous()) if counts is not None else None,
+                                          _ptr(out), out.shape[1], _ptr(out_counts), _stream_ptr(samples.device)))
+        return out, out_counts
+
+    def flush(self, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The streams of ``mask`` (None: all) emit the outputs they still owe up to ``ceil(N up / down)``, as though zeros followed,
+        and are left reset; the others report 0 -> (out (n_streams, ceil(half_len / down)), out_counts)."""
+        m8 = self._mask(mask)
+        out, out_counts = self._out(max(1, self._flush_max))
+        check(self._lib.km_resampler_flush(self._h, _ptr(m8), _ptr(out), out.shape[1], _ptr(out_counts), _stream_ptr(self.device)))
+        return out, out_counts
+
+    def _mask(self, mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        if mask is None:
+            return None
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (self.n_streams,):
+            raise ValueError(f"expected a ({self.n_streams},) bool or uint8 mask")
+        return mask.to(self.device, torch.uint8).contiguous()
+
+    def reset_streams(self, mask: torch.Tensor) -> None:
+        """mask (n_streams) bool or uint8 on the device: those streams become freshly created ones; the others are untouched."""
+        m8 = self._mask(mask)
+        if m8 is None:
+            raise ValueError("reset_streams needs a mask; reset() resets every stream")
+        check(self._lib.km_resampler_reset_streams(self._h, _ptr(m8), _stream_ptr(self.device)))
+
+    def reset(self) -> None:
+        check(self._lib.km_resampler_reset_streams(self._h, None, _stream_ptr(self.device)))
