@@ -610,6 +610,24 @@ int km_stream_step(km_handle h, const float* emotion_dev, float* out_dev, uint8_
                    void* stream);
 int km_stream_reset_streams(km_handle h, const uint8_t* mask_dev, void* stream);
 
+/* ---- the model's other outputs from the live ticks ---------------------------------------------------------------
+ * km_stream_tick / km_stream_step with two more outputs, indexed by stream (either may be NULL; with both NULL the calls ARE the
+ * plain ones):
+ *   raw_dev  (n_streams, 52)      the sigmoid values before the stream weights, the clamp and the EMA (km_core_forward's raw_dev)
+ *   attn_dev (n_streams, 28, 80)  the mel stream's attention map, averaged over the heads as km_core_forward defines it; 16-byte
+ *                                 aligned
+ * A stream that is not computed -- not ready on a tick, not fired on a step -- keeps its rows of both exactly as it keeps its row
+ * of out_dev.  out_dev, ready_dev, fired_dev, backlog_dev, the rings and the EMA state are bit-identical to the plain call's.  At
+ * d_model 256 the map comes from the fused core's own attention-map instantiation; at d_model 512 from a dependent launch that
+ * averages the heads' softmaxed scores of the computed streams (float32, heads added in the order 0 .. H - 1, then one multiply by
+ * 1 / H).  The handle checks and refusals are those of km_stream_tick / km_stream_step, with their messages; a map asked for under
+ * option core_split 3 / 6 is KM_ERR_UNSUPPORTED before anything is launched or popped.  No allocation, synchronisation or
+ * readback: both capture, alone or in front of km_attn_stats_update_masked(acc, attn_dev, ready_dev / fired_dev, n_streams). */
+int km_stream_tick_attn(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* ready_dev, float* raw_dev, float* attn_dev,
+                        void* stream);
+int km_stream_step_attn(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* fired_dev, uint8_t* ready_dev, int32_t* backlog_dev,
+                        float* raw_dev, float* attn_dev, void* stream);
+
 /* ---- streaming the legacy SimplifiedKoeMorphModel: consuming FIFOs resident on the device ---------------------
  * Legacy handles (km_legacy_create, after km_finalize) only; the km_stream_* family above keeps refusing them and this one
  * refuses dual-stream and KoeMorphModel handles.  Replaces, for all streams at once, the real-time loop of
@@ -809,14 +827,35 @@ int km_metrics_compute(void* acc, float* out_dev, void* stream);
  *   km_attn_stats_update    attn_dev (rows, Q, K), 16-byte aligned; rows = 0 does nothing
  *   km_attn_stats_compute   out_dev[KM_ATTN_STATS_COUNT(Q, K)] float64: rows, the mean map (Q K), the mean entropy (Q), the peak
  *                           counts (Q K); all 0 before any row.  The state is left as it is (compute, update, compute works)
- * reset / update / compute launch on `stream`, neither allocate nor synchronise nor read back, and can be captured. */
+ *   km_attn_stats_update_masked  folds the rows of attn_dev (rows, Q, K) whose byte of mask_dev (rows) u8 is non-zero, in index
+ *                           order: the state afterwards is bit-identical to km_attn_stats_update on those rows compacted into a
+ *                           dense array, for any mask (all zero: nothing changes).  How many rows are selected stays on the device:
+ *                           an ordered compaction writes an index table (allocated by create, max_rows_per_launch entries) and the
+ *                           count, piece by piece as the dense update cuts them.  rows below 2^31.
+ * reset / update / update_masked / compute launch on `stream`, neither allocate nor synchronise nor read back, and can be captured.
+ *
+ * One independent state per stream, for the maps of km_stream_tick_attn / km_stream_step_attn:
+ *   km_attn_stats_streams_create   n_streams states (1 .. 65535) for Q x K maps
+ *   km_attn_stats_streams_update   attn_dev (n_streams, Q, K), 16-byte aligned, and mask_dev (n_streams) u8: stream s takes its map
+ *                                  when mask_dev[s] != 0.  No reduction across streams or rows: stream s's state is bit-identical
+ *                                  to an accumulator of km_attn_stats_create that received the stream's selected maps one
+ *                                  km_attn_stats_update(rows = 1) at a time, in order
+ *   km_attn_stats_streams_reset    the streams with mask_dev[s] != 0 become fresh, the others are untouched; NULL: all
+ *   km_attn_stats_streams_compute  out_dev (n_streams, KM_ATTN_STATS_COUNT(Q, K)) float64, one km_attn_stats_compute vector per stream
+ * update / reset / compute neither allocate nor synchronise nor read back, and can be captured. */
 #define KM_ATTN_STATS_COUNT(Q, K) (1 + (Q) * (K) + (Q) + (Q) * (K))
 int km_attn_stats_create(void** acc_out, int32_t n_queries, int32_t n_keys, int64_t max_rows_per_launch);
 int km_attn_stats_destroy(void* acc);
 int km_attn_stats_shape(void* acc, int32_t* n_queries, int32_t* n_keys);
 int km_attn_stats_reset(void* acc, void* stream);
 int km_attn_stats_update(void* acc, const float* attn_dev, int64_t rows, void* stream);
+int km_attn_stats_update_masked(void* acc, const float* attn_dev, const uint8_t* mask_dev, int64_t rows, void* stream);
 int km_attn_stats_compute(void* acc, double* out_dev, void* stream);
+int km_attn_stats_streams_create(void** acc_out, int64_t n_streams, int32_t n_queries, int32_t n_keys);
+int km_attn_stats_streams_destroy(void* acc);
+int km_attn_stats_streams_update(void* acc, const float* attn_dev, const uint8_t* mask_dev, void* stream);
+int km_attn_stats_streams_reset(void* acc, const uint8_t* mask_dev, void* stream);
+int km_attn_stats_streams_compute(void* acc, double* out_dev, void* stream);
 
 /* ---- the loss by component: a streaming accumulator in device memory ------------------------------------------------
  * Replaces the `metrics` dict of KoeMorphLoss.forward (src/model/losses.py:111-183: one .item() per term and batch), the

@@ -176,6 +176,8 @@ SIGNATURES = {
     "km_stream_feed": (C.c_int, [_h, _p, _i64, _p, _p]),
     "km_stream_step": (C.c_int, [_h, _p, _p, _p, _p, _p, _p]),
     "km_stream_reset_streams": (C.c_int, [_h, _p, _p]),
+    "km_stream_tick_attn": (C.c_int, [_h, _p, _p, _p, _p, _p, _p]),
+    "km_stream_step_attn": (C.c_int, [_h, _p, _p, _p, _p, _p, _p, _p, _p]),
     "km_legacy_stream_create": (C.c_int, [_h, _i64, _i64, _i64]),
     "km_legacy_stream_push": (C.c_int, [_h, _p, _i64, _p, _p]),
     "km_legacy_stream_tick": (C.c_int, [_h, _p, _p, _p]),
@@ -199,7 +201,13 @@ SIGNATURES = {
     "km_attn_stats_shape": (C.c_int, [_p, C.POINTER(_i32), C.POINTER(_i32)]),
     "km_attn_stats_reset": (C.c_int, [_p, _p]),
     "km_attn_stats_update": (C.c_int, [_p, _p, _i64, _p]),
+    "km_attn_stats_update_masked": (C.c_int, [_p, _p, _p, _i64, _p]),
     "km_attn_stats_compute": (C.c_int, [_p, _p, _p]),
+    "km_attn_stats_streams_create": (C.c_int, [C.POINTER(_p), _i64, _i32, _i32]),
+    "km_attn_stats_streams_destroy": (C.c_int, [_p]),
+    "km_attn_stats_streams_update": (C.c_int, [_p, _p, _p, _p]),
+    "km_attn_stats_streams_reset": (C.c_int, [_p, _p, _p]),
+    "km_attn_stats_streams_compute": (C.c_int, [_p, _p, _p]),
     "km_loss_terms_create": (C.c_int, [C.POINTER(_p)]),
     "km_loss_terms_destroy": (C.c_int, [_p]),
     "km_loss_terms_reset": (C.c_int, [_p, _p]),

@@ -1000,7 +1000,15 @@ int km_stream_push(km_handle h, const float* samples_dev, int64_t n_per_stream, 
     return launch_ring_push(c, samples_dev, n_per_stream, stream);
 }
 
-int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* ready_dev, void* stream) {
+// what asking for raw / the map adds to the refusals of tick and step, before anything is launched or popped
+static int stream_outputs_ok(Context* c, const float* attn_dev) {
+    if (attn_dev && (c->opt.core_split == 3 || c->opt.core_split == 6))
+        return fail(KM_ERR_UNSUPPORTED, "streams: the split-bf16 variant (core_split %d) has no attention-map output", c->opt.core_split);
+    if ((uintptr_t)attn_dev & 15) return fail(KM_ERR_INVALID_ARG, "streams: the attention maps must be 16-byte aligned");
+    return KM_OK;
+}
+
+static int stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* ready_dev, float* raw_dev, float* attn_dev, void* stream) {
     if (int rc = need_dual(h)) return rc;
     Context* c = h;
     if (c->n_streams <= 0) return fail(KM_ERR_INVALID_ARG, "km_stream_tick: no streams (km_stream_create first)");
@@ -1011,18 +1019,29 @@ int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_
     const int64_t S = c->n_streams, L = c->ring_len;
     const int64_t n_frames = 1 + L / c->stream_plan->cfg.hop_length;
     if (S > c->ws_windows || n_frames > c->ws_frames) return fail(KM_ERR_WORKSPACE, "stream workspace too small");
+    if (int rc = stream_outputs_ok(c, attn_dev)) return rc;
     const bool fuse_emo = mel_fuses_emotion(c, c->stream_plan);
     if (!fuse_emo)
         if (int rc = launch_emotion(c, emotion_dev, S, c->ws_zemo, stream)) return rc;
     if (int rc = launch_mel_power(c, c->stream_plan, mel_rings(c), stream, fuse_emo ? mel_emotion(emotion_dev, c->ws_zemo) : MelCarry{})) return rc;
     if (c->fused_ok) {
-        if (int rc = launch_core_fused_db(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream, core_stream(c))) return rc;
+        if (int rc = launch_core_fused_db(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream,
+                                          with_outputs(core_stream(c), raw_dev, attn_dev))) return rc;
     } else {
-        if (int rc = launch_core512_stream(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream)) return rc;
+        if (int rc = launch_core512_stream(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream, nullptr, raw_dev, attn_dev)) return rc;
     }
     if (ready_dev)
         HIP_TRY(hipMemcpyAsync(ready_dev, c->ring_ready, (size_t)S, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return KM_OK;
+}
+
+int km_stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* ready_dev, void* stream) {
+    return stream_tick(h, emotion_dev, out_dev, ready_dev, nullptr, nullptr, stream);
+}
+
+int km_stream_tick_attn(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* ready_dev, float* raw_dev, float* attn_dev,
+                        void* stream) {
+    return stream_tick(h, emotion_dev, out_dev, ready_dev, raw_dev, attn_dev, stream);
 }
 
 // ---- streams out of phase: a chunk FIFO per stream in front of its ring (kernels: km_legacy_stream.hip) ----
@@ -1034,15 +1053,18 @@ static int need_stream_fifos(Context* c, const char* who) {
 }
 
 // the launches of a step behind the pop: what km_stream_tick launches, gated on the step's fire flags instead of is_full
-static int stream_step_launches(Context* c, const float* emotion_dev, float* out_dev, void* stream) {
+static int stream_step_launches(Context* c, const float* emotion_dev, float* out_dev, void* stream, float* raw_dev = nullptr,
+                                float* attn_dev = nullptr) {
     const int64_t S = c->n_streams, n_frames = 1 + c->ring_len / c->stream_plan->cfg.hop_length;
     const bool fuse_emo = mel_fuses_emotion(c, c->stream_plan);
     if (!fuse_emo)
         if (int rc = launch_emotion(c, emotion_dev, S, c->ws_zemo, stream)) return rc;
     if (int rc = launch_mel_power(c, c->stream_plan, mel_rings(c, c->ring_fire), stream,
                                   fuse_emo ? mel_emotion(emotion_dev, c->ws_zemo) : MelCarry{})) return rc;
-    if (c->fused_ok) return launch_core_fused_db(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream, core_stream(c, c->ring_fire));
-    return launch_core512_stream(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream, c->ring_fire);
+    if (c->fused_ok)
+        return launch_core_fused_db(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream,
+                                    with_outputs(core_stream(c, c->ring_fire), raw_dev, attn_dev));
+    return launch_core512_stream(c, c->stream_plan, S, n_frames, c->ws_zemo, out_dev, stream, c->ring_fire, raw_dev, attn_dev);
 }
 
 int km_stream_fifo_create(km_handle h, int64_t fifo_samples, int64_t frame_samples) {
@@ -1094,8 +1116,8 @@ int km_stream_feed(km_handle h, const float* samples_dev, int64_t n_per_stream, 
     return launch_sfifo_push(h, samples_dev, n_per_stream, counts_dev, stream);
 }
 
-int km_stream_step(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* fired_dev, uint8_t* ready_dev, int32_t* backlog_dev,
-                   void* stream) {
+static int stream_step(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* fired_dev, uint8_t* ready_dev, int32_t* backlog_dev,
+                       float* raw_dev, float* attn_dev, void* stream) {
     if (int rc = need_stream_fifos(h, "km_stream_step")) return rc;
     Context* c = h;
     if (!emotion_dev || !out_dev) return fail(KM_ERR_INVALID_ARG, "km_stream_step: NULL argument");
@@ -1104,9 +1126,20 @@ int km_stream_step(km_handle h, const float* emotion_dev, float* out_dev, uint8_
     const int64_t S = c->n_streams;
     if (S > c->ws_windows || 1 + c->ring_len / c->stream_plan->cfg.hop_length > c->ws_frames)
         return fail(KM_ERR_WORKSPACE, "stream workspace too small");
+    if (int rc = stream_outputs_ok(c, attn_dev)) return rc;
     // pop + ring advance (fire, ready, backlog), then the launches of a tick gated on fire: one linear chain
     if (int rc = launch_sfifo_pop_ring(c, fired_dev, ready_dev, backlog_dev, stream)) return rc;
-    return stream_step_launches(c, emotion_dev, out_dev, stream);
+    return stream_step_launches(c, emotion_dev, out_dev, stream, raw_dev, attn_dev);
+}
+
+int km_stream_step(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* fired_dev, uint8_t* ready_dev, int32_t* backlog_dev,
+                   void* stream) {
+    return stream_step(h, emotion_dev, out_dev, fired_dev, ready_dev, backlog_dev, nullptr, nullptr, stream);
+}
+
+int km_stream_step_attn(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* fired_dev, uint8_t* ready_dev, int32_t* backlog_dev,
+                        float* raw_dev, float* attn_dev, void* stream) {
+    return stream_step(h, emotion_dev, out_dev, fired_dev, ready_dev, backlog_dev, raw_dev, attn_dev, stream);
 }
 
 int km_stream_reset_streams(km_handle h, const uint8_t* mask_dev, void* stream) {

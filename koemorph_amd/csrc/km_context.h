@@ -340,8 +340,9 @@ int launch_core_generic(Context* c, const float* mel, int64_t B, int64_t T_in, c
                         float* out, float* raw, float* attn, void* stream);
 // km_stream_tick on the d_model 512 shapes (8 or 16 heads, window 512): core512's streaming kernel over the rings' power-mel
 bool core512_stream_ok(Context* c);
+// raw (S, 52) / attn (S, 28, 80, 16-byte aligned) or null: the pre-weight sigmoid values and the head-averaged map of the computed streams
 int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
-                          const unsigned char* gate = nullptr);
+                          const unsigned char* gate = nullptr, float* raw = nullptr, float* attn = nullptr);
 
 // km_mel.hip
 // Shared-frame sequence mode: the front end writes n_rows rows per window (row r = STFT frame r * frame_mul) into

@@ -703,8 +703,30 @@ int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_fr
 // km_stream_tick on the d_model 512 shapes: the front end has written the power-mel of every ready stream's ring
 bool core512_stream_ok(Context* c) { return core512_merge_ok(c, nullptr) && generic_core_takes_power(c); }
 
+// The head-averaged map of every stream that core512_stream_kernel just computed (km_stream_tick_attn / _step_attn): the kernel
+// leaves the softmaxed scores of all heads in the workspace, H blocks of 28 x 80 per stream.  A dependent launch gated on the flags
+// the core was gated on, so a stream that was skipped keeps its rows.  A thread owns one float4 of the map: 16-byte loads and one
+// 16-byte store, the heads added in the order h = 0 .. H - 1 in float32 and one multiply by 1 / H (head_mean_kernel's order and,
+// H being a power of two, its bits).  blockIdx.x is the stream, blockIdx.y * 128 + threadIdx.x the float4.
+constexpr int kStreamMapThreads = 128;
+__global__ __launch_bounds__(kStreamMapThreads) void stream_head_mean_kernel(const float* __restrict__ p, const unsigned char* __restrict__ gate,
+                                                                             float* __restrict__ attn, int H, int per4) {
+    const int b = (int)blockIdx.x;
+    if (!gate[b]) return;                                                     // workgroup-uniform
+    const int i = (int)blockIdx.y * kStreamMapThreads + (int)threadIdx.x;
+    if (i >= per4) return;
+    const float4* src = reinterpret_cast<const float4*>(p) + (int64_t)b * H * per4 + i;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int h = 0; h < H; ++h) {
+        const float4 v = src[(int64_t)h * per4];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    const float inv = 1.0f / (float)H;
+    reinterpret_cast<float4*>(attn)[(int64_t)b * per4 + i] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
+}
+
 int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
-                          const unsigned char* gate) {
+                          const unsigned char* gate, float* raw, float* attn) {
     if (!core512_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
     if (!c->ws_generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
     const int d = c->d, H = c->H, NKk = c->NK, KP = (c->KT + 15) / 16 * 16;
@@ -712,7 +734,7 @@ int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames
     float* Sc = Y + 2 * S * NKk * d;
     const EncSrc src{c->ws_melpow, c->ws_melmax, (int)n_frames, c->T, plan_log_params(plan)};
     Core512StreamArgs sa{{nullptr, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), Sc, H * 28,
-                          dv(c, "wv_bg"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, nullptr},
+                          dv(c, "wv_bg"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw},
                          {(int)(c->stream_out_frames > 0 ? c->stream_out_frames : n_frames), gate ? gate : c->ring_ready, c->ring_started,
                           c->ring_state, c->alpha}};
     static PerDeviceOnce once;
@@ -724,6 +746,12 @@ int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames
     else hipLaunchKernelGGL((core512_stream_kernel<4, 2>), dim3((unsigned)S), dim3(512), kCore512Lds, (hipStream_t)stream, sa);
     HIP_TRY(hipGetLastError());
     c->melmax_dirty = false;     // as in launch_core_generic_power: the slots the front end wrote are re-zeroed by the encoder stage
+    if (attn) {
+        const int per4 = 28 * NKk / 4;
+        hipLaunchKernelGGL(stream_head_mean_kernel, dim3((unsigned)S, (unsigned)((per4 + kStreamMapThreads - 1) / kStreamMapThreads)),
+                           dim3(kStreamMapThreads), 0, (hipStream_t)stream, Sc, sa.st.ready, attn, H, per4);
+        HIP_TRY(hipGetLastError());
+    }
     return KM_OK;
 }
 

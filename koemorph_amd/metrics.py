@@ -419,6 +419,7 @@ class AttentionStats:
         self._device = None
         self._lib = None
         self.rows = 0
+        self._masked = False                                            # a masked update may have folded rows `rows` does not count
 
     def _stream(self):
         import torch
@@ -433,7 +434,7 @@ class AttentionStats:
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         if self._acc and self._device != device:
-            if self.rows:
+            if self.rows or self._masked:
                 raise ValueError("one accumulation mixes devices; reset() first")
             self.close()
         if not self._acc:
@@ -458,13 +459,17 @@ class AttentionStats:
 
     def reset(self):
         self.rows = 0
+        self._masked = False
         if self._acc:
             import torch
             with torch.cuda.device(self._device):
                 check(self._lib.km_attn_stats_reset(self._acc, self._stream()))
 
-    def update(self, maps):
-        """Fold (..., n_queries, n_keys) float32 device maps in; any leading shape, also empty."""
+    def update(self, maps, mask=None):
+        """Fold (..., n_queries, n_keys) float32 device maps in; any leading shape, also empty.  ``mask``: a bool or uint8 device
+        tensor with one entry per map -- only the maps whose entry is non-zero are folded, in index order, with the bits a plain
+        update of those maps alone would leave (km_attn_stats_update_masked).  How many were selected stays on the device, so
+        ``rows`` counts the maps of the unmasked updates only; ``compute()['rows']`` is the number folded."""
         import torch
         if not isinstance(maps, torch.Tensor) or not maps.is_cuda:
             raise ValueError("AttentionStats takes device tensors (the float64 restatement for host data is tests/attn_stats_cases.py)")
@@ -472,9 +477,19 @@ class AttentionStats:
             raise ValueError(f"expected (..., {self.n_queries}, {self.n_keys}) maps, got {tuple(maps.shape)}")
         maps = maps.detach().to(torch.float32).contiguous()
         n = int(maps.numel() // (self.n_queries * self.n_keys))
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.device != maps.device or mask.dtype not in (torch.bool, torch.uint8) or mask.numel() != n:
+                raise ValueError(f"expected a bool or uint8 mask of {n} entries on the maps' device")
+            mask = mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else mask.contiguous()
         acc = self._handle(maps.device)
         with torch.cuda.device(self._device):
-            check(self._lib.km_attn_stats_update(acc, maps.data_ptr() if n else None, n, self._stream()))
+            if mask is None:
+                check(self._lib.km_attn_stats_update(acc, maps.data_ptr() if n else None, n, self._stream()))
+            else:
+                check(self._lib.km_attn_stats_update_masked(acc, maps.data_ptr() if n else None, mask.data_ptr() if n else None, n,
+                                                            self._stream()))
+                self._masked = True
+                return
         self.rows += n
 
     def compute(self) -> Dict[str, object]:
@@ -489,6 +504,91 @@ class AttentionStats:
             check(self._lib.km_attn_stats_compute(self._acc, out.data_ptr(), self._stream()))
             vec = out.cpu().numpy()
         return unpack_attention_stats(vec, self.n_queries, self.n_keys)
+
+
+class StreamAttentionStats:
+    """One ``AttentionStats`` state per stream, on the device (``km_attn_stats_streams_*``): ``update(maps, mask)`` takes the
+    (n_streams, n_queries, n_keys) maps of ``StreamEngine.tick`` / ``ChunkedStreamEngine.step`` and the ``ready`` / ``fired`` flags of the
+    same call -- stream ``s`` folds its map when ``mask[s]`` is non-zero, with the bits an ``AttentionStats`` of its own fed one map
+    at a time would hold.  ``reset(mask)`` makes the masked streams fresh (None: all); ``compute()`` returns one dict per stream."""
+
+    def __init__(self, n_streams: int, n_queries: int = 28, n_keys: int = 80):
+        self.n_streams, self.n_queries, self.n_keys = int(n_streams), int(n_queries), int(n_keys)
+        self._acc = C.c_void_p()
+        self._device = None
+        self._lib = None
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self._device).cuda_stream
+
+    def _handle(self, device):
+        import torch
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._acc and self._device != device:
+            raise ValueError("the per-stream states live on another device")
+        if not self._acc:
+            self._lib = load()
+            self._device = device
+            with torch.cuda.device(device):
+                check(self._lib.km_attn_stats_streams_create(C.byref(self._acc), self.n_streams, self.n_queries, self.n_keys))
+        return self._acc
+
+    def close(self):
+        if self._acc:
+            import torch
+            torch.cuda.synchronize(self._device)
+            self._lib.km_attn_stats_streams_destroy(self._acc)
+            self._acc = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _mask(self, mask, device):
+        import torch
+        if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype not in (torch.bool, torch.uint8) or \
+                tuple(mask.shape) != (self.n_streams,):
+            raise ValueError(f"expected a ({self.n_streams},) bool or uint8 device mask")
+        if device is not None and mask.device != device:
+            raise ValueError("the mask lives on another device than the maps")
+        return mask.contiguous().view(torch.uint8) if mask.dtype == torch.bool else mask.contiguous()
+
+    def update(self, maps, mask):
+        import torch
+        if not isinstance(maps, torch.Tensor) or not maps.is_cuda:
+            raise ValueError("StreamAttentionStats takes device tensors")
+        if tuple(maps.shape) != (self.n_streams, self.n_queries, self.n_keys):
+            raise ValueError(f"expected ({self.n_streams}, {self.n_queries}, {self.n_keys}) maps, got {tuple(maps.shape)}")
+        maps = maps.detach().to(torch.float32).contiguous()
+        m8 = self._mask(mask, maps.device)
+        acc = self._handle(maps.device)
+        with torch.cuda.device(self._device):
+            check(self._lib.km_attn_stats_streams_update(acc, maps.data_ptr(), m8.data_ptr(), self._stream()))
+
+    def reset(self, mask=None):
+        if not self._acc:
+            return
+        import torch
+        m8 = self._mask(mask, self._device) if mask is not None else None
+        with torch.cuda.device(self._device):
+            check(self._lib.km_attn_stats_streams_reset(self._acc, m8.data_ptr() if m8 is not None else None, self._stream()))
+
+    def compute(self) -> List[Dict[str, object]]:
+        """One ``AttentionStats.compute()`` dict per stream (band reductions included); all zero before any update.  One readback."""
+        import torch
+        n = km_attn_stats_count(self.n_queries, self.n_keys)
+        if not self._acc:
+            return [unpack_attention_stats(np.zeros(n), self.n_queries, self.n_keys) for _ in range(self.n_streams)]
+        with torch.cuda.device(self._device):
+            out = torch.empty(self.n_streams, n, device=self._device, dtype=torch.float64)
+            check(self._lib.km_attn_stats_streams_compute(self._acc, out.data_ptr(), self._stream()))
+            vec = out.cpu().numpy()
+        return [unpack_attention_stats(vec[s], self.n_queries, self.n_keys) for s in range(self.n_streams)]
 
 
 def compute_lip_sync_metrics(pred_blendshapes, target_blendshapes, audio_features=None) -> Dict[str, float]:

@@ -11,6 +11,11 @@ floats) followed by ``tick`` (emotion kernel, sliding-window front end over ever
 per-stream EMA).  Neither allocates nor synchronises, so ``capture()`` records one tick into a hipGraph and
 ``replay()`` re-launches it with a single API call per 33 ms frame.
 
+``tick`` / ``step`` with ``return_attention=True`` also return the model's other two outputs for the streams they computed (km_stream_tick_attn
+/ km_stream_step_attn): ``raw``, the sigmoid values before the stream weights and the EMA, and ``mel_attention_weights``, the head-averaged
+attention map of the mel stream.  ``capture(..., return_attention=True, stats=acc)`` records them and, gated on ``ready`` / ``fired``, the
+masked update of an ``AttentionStats`` / ``StreamAttentionStats`` accumulator into the same graph.
+
 ``ChunkedStreamEngine`` serves streams that are out of phase: chunks of any size are fed into a consuming FIFO per stream
 (the reference's ``RingBuffer``, scripts/rt.py:48-99), a step pops one frame from every stream that holds one and computes only
 the streams that popped onto a full ring, and ``reset_streams`` hands one slot to the next speaker (km_stream_fifo_create / _feed /
@@ -62,6 +67,31 @@ class StreamEngine:
         self.ready = torch.zeros(n_streams, dtype=torch.uint8, device=dev)
         self._graph = None
         self._g_samples = self._g_emotion = None
+        self._g_attention = False
+        self.raw = self.attention = None
+
+    def attention_outputs(self) -> dict:
+        """{"raw": (n_streams, 52), "mel_attention_weights": (n_streams, 28, 80)}: persistent device tensors owned by the engine,
+        allocated (zero) on first use; a row is rewritten whenever its stream is computed with ``return_attention=True``."""
+        if self.raw is None:
+            dev = self.engine.device
+            self.raw = torch.zeros(self.n_streams, self.engine.num_blendshapes, device=dev)
+            self.attention = torch.zeros(self.n_streams, 28, self.engine.n_mels, device=dev)
+        return {"raw": self.raw, "mel_attention_weights": self.attention}
+
+    def _zero_attention(self, gone: Optional[torch.Tensor] = None) -> None:
+        if self.raw is None:
+            return
+        if gone is None:
+            self.raw.zero_()
+            self.attention.zero_()
+        else:
+            self.raw.masked_fill_(gone.view(-1, 1), 0.0)
+            self.attention.masked_fill_(gone.view(-1, 1, 1), 0.0)
+
+    def _record_stats(self, stats, gate: torch.Tensor) -> None:
+        if stats is not None:
+            stats.update(self.attention, mask=gate)
 
     def push(self, samples: torch.Tensor) -> None:
         """samples (n_streams, n) fp32 on the device, n within +/-1 of the ring hop (532)."""
@@ -70,9 +100,15 @@ class StreamEngine:
         samples = samples.contiguous()
         check(self._lib.km_stream_push(self.engine._h, _ptr(samples), samples.shape[1], _stream_ptr(samples.device)))
 
-    def tick(self, emotion: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """emotion (n_streams, emotion_dim) -> (out (n_streams, 52), ready (n_streams) uint8)."""
+    def tick(self, emotion: torch.Tensor, return_attention: bool = False):
+        """emotion (n_streams, emotion_dim) -> (out (n_streams, 52), ready (n_streams) uint8); with ``return_attention`` also the
+        dict of ``attention_outputs()``, whose rows of the ready streams this tick has rewritten."""
         emotion = emotion.contiguous()
+        if return_attention:
+            extra = self.attention_outputs()
+            check(self._lib.km_stream_tick_attn(self.engine._h, _ptr(emotion), _ptr(self.out), _ptr(self.ready), _ptr(self.raw),
+                                                _ptr(self.attention), _stream_ptr(emotion.device)))
+            return self.out, self.ready, extra
         check(self._lib.km_stream_tick(self.engine._h, _ptr(emotion), _ptr(self.out), _ptr(self.ready),
                                        _stream_ptr(emotion.device)))
         return self.out, self.ready
@@ -81,15 +117,31 @@ class StreamEngine:
         check(self._lib.km_stream_reset(self.engine._h, _stream_ptr(self.engine.device)))
         self.out.zero_()
         self.ready.zero_()
+        self._zero_attention()
 
     # ---- hipGraph replay ------------------------------------------------------------------------
-    def capture(self, n_per_stream: Optional[int] = None, host_out: Optional[torch.Tensor] = None) -> None:
+    def _prepare_attention_capture(self, return_attention: bool, stats) -> bool:
+        """What must exist before a capture that records the attention outputs: the output tensors, the accumulator, and one
+        launch of the masked update's kernels outside the capture (over a mask of zeros, which changes nothing)."""
+        if stats is not None and not return_attention:
+            raise ValueError("stats needs return_attention=True: the accumulator is fed from the captured maps")
+        if return_attention:
+            self.attention_outputs()
+        if stats is not None:
+            stats.update(self.attention, mask=torch.zeros(self.n_streams, dtype=torch.uint8, device=self.engine.device))
+        return bool(return_attention)
+
+    def capture(self, n_per_stream: Optional[int] = None, host_out: Optional[torch.Tensor] = None, return_attention: bool = False,
+                stats=None) -> None:
         """Record push + tick on static input buffers into a hipGraph (torch.cuda.CUDAGraph drives
         hipStreamBeginCapture on the current stream; the kernels are launched by libkoemorph_hip).  ``n_per_stream``: the
         frame size every replay() will bring, within +/-1 of ``ring_hop``; default 533 wherever push accepts it (ring hop 532
         or 533: every 30 fps engine, as before), otherwise ``ring_hop + 1`` (267 at 60 fps).  ``host_out``: a pinned
-        (n_streams, 52) host tensor -- the tick's result readback becomes the graph's last node instead of a call per tick."""
+        (n_streams, 52) host tensor -- the tick's result readback becomes the graph's last node instead of a call per tick.
+        ``return_attention``: record the tick that also writes ``attention_outputs()``; replay() then returns them as tick does.
+        ``stats``: an ``AttentionStats`` or ``StreamAttentionStats`` whose masked update, gated on ``ready``, is recorded behind it."""
         dev = self.engine.device
+        self._g_attention = self._prepare_attention_capture(return_attention, stats)
         if n_per_stream is None:
             n_per_stream = 533 if abs(533 - self.ring_hop) <= 1 else self.ring_hop + 1
         if host_out is not None and (not host_out.is_pinned() or tuple(host_out.shape) != tuple(self.out.shape)):
@@ -100,18 +152,21 @@ class StreamEngine:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self.push(self._g_samples)
-            self.tick(self._g_emotion)
+            self.tick(self._g_emotion, return_attention=self._g_attention)
+            self._record_stats(stats, self.ready)
             if host_out is not None:
                 host_out.copy_(self.out, non_blocking=True)
         self._graph = g
         self._g_host_out = host_out
 
-    def replay(self, samples: torch.Tensor, emotion: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def replay(self, samples: torch.Tensor, emotion: torch.Tensor):
         if self._graph is None:
             raise RuntimeError("capture() first")
         self._g_samples.copy_(samples, non_blocking=True)
         self._g_emotion.copy_(emotion, non_blocking=True)
         self._graph.replay()
+        if self._g_attention:
+            return self.out, self.ready, self.attention_outputs()
         return self.out, self.ready
 
 
@@ -165,10 +220,16 @@ class ChunkedStreamEngine(StreamEngine):
         check(self._lib.km_stream_feed(self.engine._h, _ptr(samples), samples.shape[1],
                                        _ptr(counts.contiguous()) if counts is not None else None, _stream_ptr(samples.device)))
 
-    def step(self, emotion: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def step(self, emotion: torch.Tensor, return_attention: bool = False):
         """emotion (n_streams, emotion_dim) -> (out (n_streams, 52), fired (n_streams) uint8); ``ready`` and ``backlog`` are
-        updated as well.  Rows of streams that did not fire keep what they held."""
+        updated as well.  Rows of streams that did not fire keep what they held.  With ``return_attention`` also the dict of
+        ``attention_outputs()``, whose rows of the fired streams this step has rewritten."""
         emotion = emotion.contiguous()
+        if return_attention:
+            extra = self.attention_outputs()
+            check(self._lib.km_stream_step_attn(self.engine._h, _ptr(emotion), _ptr(self.out), _ptr(self.fired), _ptr(self.ready),
+                                                _ptr(self.backlog), _ptr(self.raw), _ptr(self.attention), _stream_ptr(emotion.device)))
+            return self.out, self.fired, extra
         check(self._lib.km_stream_step(self.engine._h, _ptr(emotion), _ptr(self.out), _ptr(self.fired), _ptr(self.ready),
                                        _ptr(self.backlog), _stream_ptr(emotion.device)))
         return self.out, self.fired
@@ -182,6 +243,7 @@ class ChunkedStreamEngine(StreamEngine):
         check(self._lib.km_stream_reset_streams(self.engine._h, _ptr(m8), _stream_ptr(m8.device)))
         gone = m8 != 0
         self.out.masked_fill_(gone.unsqueeze(1), 0.0)
+        self._zero_attention(gone)
         for flags in (self.ready, self.fired, self.backlog):
             flags.masked_fill_(gone, 0)
 
@@ -191,12 +253,14 @@ class ChunkedStreamEngine(StreamEngine):
         self.backlog.zero_()
 
     # ---- hipGraph replay ------------------------------------------------------------------------
-    def capture(self, n_per_stream: int, host_out: Optional[torch.Tensor] = None) -> None:
+    def capture(self, n_per_stream: int, host_out: Optional[torch.Tensor] = None, return_attention: bool = False, stats=None) -> None:
         """Record feed (with per-stream counts) + step on static input buffers into a hipGraph: one linear chain.  ``host_out``: a
-        pinned (n_streams, 52) host tensor -- the result readback becomes the graph's last node."""
+        pinned (n_streams, 52) host tensor -- the result readback becomes the graph's last node.  ``return_attention`` / ``stats``:
+        as ``StreamEngine.capture``, the masked update gated on ``fired``."""
         dev = self.engine.device
         if host_out is not None and (not host_out.is_pinned() or tuple(host_out.shape) != tuple(self.out.shape)):
             raise ValueError("host_out must be a pinned host tensor of the shape of the result")
+        self._g_attention = self._prepare_attention_capture(return_attention, stats)
         self._g_samples = torch.zeros(self.n_streams, n_per_stream, device=dev)
         self._g_counts = torch.full((self.n_streams,), n_per_stream, dtype=torch.int32, device=dev)
         self._g_emotion = torch.zeros(self.n_streams, self.engine.emotion_dim, device=dev)
@@ -204,13 +268,14 @@ class ChunkedStreamEngine(StreamEngine):
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self.feed(self._g_samples, self._g_counts)
-            self.step(self._g_emotion)
+            self.step(self._g_emotion, return_attention=self._g_attention)
+            self._record_stats(stats, self.fired)
             if host_out is not None:
                 host_out.copy_(self.out, non_blocking=True)
         self._graph = g
         self._g_host_out = host_out
 
-    def replay(self, samples: torch.Tensor, counts: Optional[torch.Tensor], emotion: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    def replay(self, samples: torch.Tensor, counts: Optional[torch.Tensor], emotion: torch.Tensor):
         """One captured feed + step; counts None: every stream brings all ``n_per_stream`` samples."""
         if self._graph is None:
             raise RuntimeError("capture() first")
@@ -221,6 +286,8 @@ class ChunkedStreamEngine(StreamEngine):
             self._g_counts.fill_(self._g_samples.shape[1])
         self._g_emotion.copy_(emotion, non_blocking=True)
         self._graph.replay()
+        if self._g_attention:
+            return self.out, self.fired, self.attention_outputs()
         return self.out, self.fired
 
 

@@ -11,7 +11,12 @@ on them with the EMA state (km_smooth behind the generic core), and the same rea
 (a) a replayed km_stream_feed + km_stream_step with every stream firing, (b) the lockstep replayed km_stream_push + km_stream_tick,
 (c) a replayed feed + step on which one stream in four brings a frame; then the route there was before for streams that do not move
 together: one SimplifiedDualStreamModel(real_time_mode=True) per stream driven frame by frame (8 streams, the d_model 256 shape),
-reported per stream-frame.  Host wall clock around one synchronised tick, as above."""
+reported per stream-frame.  Host wall clock around one synchronised tick, as above.
+
+``--attention``: what the attention outputs cost.  In ONE run, at both shapes, a replayed chunked tick (feed + step, every stream
+firing) on three engines, interleaved in rounds: (plain) km_stream_step, (maps) km_stream_step_attn writing `raw` and the
+head-averaged maps, (maps_stats) the same with km_attn_stats_update_masked gated on `fired` in the graph.  The figure of a round is
+the host clock around its synchronised ticks divided by their number; reported: the median of 15 rounds, and the spread."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -27,6 +32,7 @@ ap.add_argument("--d-model", type=int, default=256, choices=(256, 512))
 ap.add_argument("--heads", type=int, default=8, choices=(8, 16))
 ap.add_argument("--fps", type=int, default=30, choices=(30, 60))
 ap.add_argument("--baseline", action="store_true", help="also time host-side rings + forward_audio + EMA per tick")
+ap.add_argument("--attention", action="store_true", help="a replayed chunked tick without maps, with maps, with maps + the masked statistics update")
 ap.add_argument("--chunked", action="store_true", help="feed + step (all fire / one in four) against push + tick at both shapes, and one model per stream")
 args = ap.parse_args()
 S = args.streams
@@ -87,6 +93,48 @@ def chunked_shape(d_model, heads, fps, rounds=8):
     return res
 
 
+def attention_shape(d_model, heads, fps, rounds=15):
+    from koemorph_amd.metrics import AttentionStats
+    ui = 0.0333 if fps == 30 else 1.0 / fps
+    eng = {k: ChunkedStreamEngine(make_engine(d_model, heads, fps), S, update_interval=ui) for k in ("plain", "maps", "maps_stats")}
+    n, frame = eng["plain"].ring_hop + 1, eng["plain"].frame_samples
+    frames = torch.from_numpy(synth.make_audio(1, S, n * 8, "uniform")).cuda()
+    emo = torch.from_numpy(synth.normal(2, (S, 256))).cuda()
+    every = torch.full((S,), frame, dtype=torch.int32, device="cuda")
+    chunk = lambda t: frames[:, (t % 8) * n:(t % 8 + 1) * n]
+    for t in range(eng["plain"].shape["ring_len"] // eng["plain"].ring_hop + 3):      # fill the rings (eager)
+        for k, se in eng.items():
+            se.feed(chunk(t), every); se.step(emo, return_attention=(k != "plain"))
+    acc = AttentionStats()
+    host = {k: torch.empty(S, 52, pin_memory=True) for k in eng}
+    eng["plain"].capture(n, host_out=host["plain"])
+    eng["maps"].capture(n, host_out=host["maps"], return_attention=True)
+    eng["maps_stats"].capture(n, host_out=host["maps_stats"], return_attention=True, stats=acc)
+    per_round = max(1, args.ticks // rounds)
+    ms = {k: [] for k in eng}
+    for r in range(rounds + 1):                               # round 0 warms up
+        for k, se in eng.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for t in range(per_round):
+                se.replay(chunk(t), every, emo)
+                torch.cuda.synchronize()
+            if r:
+                ms[k].append((time.perf_counter() - t0) / per_round * 1e3)
+    same = all(torch.equal(eng["plain"].out, eng[k].out) for k in ("maps", "maps_stats"))
+    res = {"workload": f"{S} streams/GPU (d_model {d_model}, {heads} heads, {fps} fps), replayed feed + step with every stream firing + D2H of "
+                       f"{S}x52 floats, one synchronisation per tick, {rounds} rounds x {per_round} ticks per route, interleaved",
+           "out_identical_across_routes": bool(same), "stats_rows": int(acc.compute()["rows"]),
+           "all_fired": bool(all(int(se.fired.sum()) == S for se in eng.values()))}
+    for k in eng:
+        v = np.asarray(ms[k])
+        res[k] = {"tick_ms_median_of_rounds": round(float(np.median(v)), 4), "tick_ms_min": round(float(v.min()), 4),
+                  "tick_ms_max": round(float(v.max()), 4)}
+    for k in ("maps", "maps_stats"):
+        res[k]["over_plain_ms"] = round(res[k]["tick_ms_median_of_rounds"] - res["plain"]["tick_ms_median_of_rounds"], 4)
+    return res
+
+
 def per_model_route(n_models=8, ticks=60):
     """One SimplifiedDualStreamModel(real_time_mode=True) per stream, each driven frame by frame (its ring on the host, the 8.5 s
     window uploaded per frame, front end + core + EMA launches per stream).  Steps are one audio hop apart: a stepped clock."""
@@ -118,6 +166,10 @@ def per_model_route(n_models=8, ticks=60):
             "per_stream_frame": stats(lat)}
 
 
+if args.attention:
+    for shape in ((256, 8, 30), (512, 8, 60)):
+        print(json.dumps(attention_shape(*shape)), flush=True)
+    sys.exit(0)
 if args.chunked:
     for shape in ((256, 8, 30), (512, 8, 60)):
         print(json.dumps(chunked_shape(*shape)), flush=True)
