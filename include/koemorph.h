@@ -99,6 +99,10 @@ const char* km_last_error(void);
  * parameter folding can be exercised on the CPU; device memory is touched from km_finalize on. */
 int km_create(const km_config* cfg, km_handle* out);
 int km_destroy(km_handle h);
+/* Bytes of device memory this library holds in the whole process: every allocation of every handle (km_create, the accumulators,
+ * the emotion / resampler / eGeMAPS handles) counts from the moment it exists until it is freed.  0 after load; back at its earlier
+ * value once everything created since has been destroyed.  A leak check that does not depend on what else uses the device. */
+int64_t km_live_device_bytes(void);
 
 /* Replaces nn.Module.load_state_dict for one tensor.  `key` is the reference state-dict key
  * relative to DualStreamCrossAttention (e.g. "mel_attention.in_proj_weight"; the full-model

@@ -94,6 +94,7 @@ SIGNATURES = {
     "km_last_error": (C.c_char_p, []),
     "km_create": (C.c_int, [C.POINTER(KMConfig), C.POINTER(_h)]),
     "km_destroy": (C.c_int, [_h]),
+    "km_live_device_bytes": (_i64, []),
     "km_load_param": (C.c_int, [_h, C.c_char_p, _p, C.POINTER(_i64), _i32]),
     "km_get_param": (C.c_int, [_h, C.c_char_p, _p, _i64]),
     "km_param_count": (C.c_int, [_h, C.POINTER(_i32), C.POINTER(_i32)]),

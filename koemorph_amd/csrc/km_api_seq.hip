@@ -1,0 +1,193 @@
+// C-ABI entry points of sequence mode: km_sequence_* (declared in include/koemorph.h).
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "km_api_internal.h"
+#include "km_context.h"
+#include "km_device.h"
+#include "km_gemm.h"
+
+using namespace km;
+
+extern "C" {
+
+int64_t km_sequence_num_outputs(km_handle h, int64_t L, int32_t stride_frames) {
+    if (!h || L < 0 || stride_frames <= 0) return -1;
+    const int64_t num_frames = L / h->cfg.mel.hop_length;                       // sequential_dual_stream_model.py:84
+    const int64_t n = (num_frames - h->T) / stride_frames + 1;                   // :96 (floor division)
+    const int64_t nn = (num_frames - h->T) >= 0 ? n : ((num_frames - h->T - (stride_frames - 1)) / stride_frames + 1);
+    return nn > 1 ? nn : 1;
+}
+
+// Where a window's emotion logit comes from in km_sequence_forward_track: the rows of every clip's track and the closed-form
+// window -> row map (SeqTrackMap).  Null: one vector per clip (km_sequence_forward).
+struct SeqTrack { const float* track; int64_t K, first, interval, sample_offset, clip_len; };
+
+// What km_sequence_forward_attn adds to a sequence call: the pre-weight sigmoid values (B, N, 52) and the head-averaged maps
+// (B, N, 28, NK) of every window, indexed like out_dev, and / or an accumulator (km_attn_stats_*) that takes every tile's maps.
+// With an accumulator and no caller's map the maps of a tile live in seq.attn and are overwritten by the next tile.
+struct SeqOutputs { float* raw; float* attn; void* stats; };
+
+static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev, const SeqTrack* trk,
+                            int32_t stride_frames, int32_t smooth, float* out_dev, void* stream, const SeqOutputs& xo = SeqOutputs{nullptr, nullptr, nullptr}) {
+    Context* c = h;
+    if (!c->fused_ok && !c->ws.generic)
+        return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
+    const int hop = c->cfg.mel.hop_length;
+    const int64_t N = km_sequence_num_outputs(h, L, stride_frames);
+    const int64_t W = (int64_t)c->T * hop;                 // window_samples (sequential_dual_stream_model.py:54)
+    const int64_t step = (int64_t)stride_frames * hop;     // stride_samples (:55)
+    const int64_t n_frames = 1 + W / hop;
+    if (c->ws.windows < B || c->ws.windows < 1 || n_frames > c->ws.frames)
+        return fail(KM_ERR_WORKSPACE, "workspace too small for %lld clips / %lld-frame windows: call km_reserve",
+                    (long long)B, (long long)n_frames);
+    if (N > 0x7fffffff) return fail(KM_ERR_INVALID_ARG, "too many output frames");
+    const int64_t total = B * N, tile = c->ws.windows;
+    // Shared-frame path.  Windows start at multiples of the hop (:101-117), so frame f of window i IS clip frame
+    // i*stride + f for f = 1 .. T-1; only frame 0 and frame T see the zero padding at the window boundary.  The STFT
+    // of the clip is computed once (N-1)*stride + T + 1 frames instead of N * (T+1)), the two edge frames per window
+    // separately, and the core reads its rows from both images.  Results are bit-identical to the per-window path.
+    const bool dedup = !c->opt.seq_per_window;       // km_set_option: tests compare both paths
+    MelPlan* plan = c->mel_plans[0];
+    const bool shared = c->fused_ok && dedup && mel_rp_ok(c, plan) && N < (1 << 24);
+    const int64_t nfc = (N - 1) * stride_frames + n_frames;                     // clip frames any window touches
+    if (shared) {     // grow-only images and their per-row maxima; allocates, so refused inside a stream capture, before any launch
+        const char* what = "km_sequence_forward: elements of the clip / window images";
+        if (int rc = c->seq.pow.grow(B * nfc * c->NK, stream, what)) return rc;
+        if (int rc = c->seq.fmax.grow(B * nfc, stream, what)) return rc;
+        if (int rc = c->seq.edge.grow(total * 2 * c->NK, stream, what)) return rc;
+        if (int rc = c->seq.emax.grow(total * 2, stream, what)) return rc;
+    }
+    const int64_t map_floats = (int64_t)28 * c->NK;
+    const bool tile_maps = xo.stats && !xo.attn;     // the maps of one tile at a time, for the accumulator alone
+    if (tile_maps)
+        if (int rc = c->seq.attn.grow(tile * map_floats, stream, "km_sequence_forward_attn: floats of the maps of one tile")) return rc;
+    // rows of tile w0: the caller's arrays at w0, or the tile buffer
+    auto raw_at = [&](int64_t w0) { return xo.raw ? xo.raw + w0 * c->NB : nullptr; };
+    auto attn_at = [&](int64_t w0) { return xo.attn ? xo.attn + w0 * map_floats : (tile_maps ? c->seq.attn : nullptr); };
+    auto stats_take = [&](int64_t w0, int64_t nw) { return xo.stats ? km_attn_stats_update(xo.stats, attn_at(w0), nw, stream) : KM_OK; };
+    const float* zemo = c->ws.zemo;
+    if (trk) {
+        // a logit per track ROW (about nine windows share one), then one per window by the closed-form map: the core launches
+        // below read zwin[win0 + b]
+        const char* what = "km_sequence_forward_track: track rows / windows";
+        if (int rc = c->seq.ztrack.grow(B * trk->K, stream, what)) return rc;
+        if (int rc = c->seq.zwin.grow(total, stream, what)) return rc;
+        if (int rc = launch_emotion(c, trk->track, B * trk->K, c->seq.ztrack, stream)) return rc;
+        const SeqTrackMap map{trk->K, trk->first, trk->interval, trk->sample_offset, trk->clip_len, step, W};
+        if (int rc = launch_seq_track_logits(c, c->seq.ztrack, c->seq.zwin, total, (int)N, map, stream)) return rc;
+        zemo = c->seq.zwin;
+    } else {
+        // emotion features ONCE for the entire audio (:88): one logit per clip
+        if (int rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, stream)) return rc;
+    }
+    if (shared) {
+        hipStream_t st = (hipStream_t)stream;
+        HIP_TRY(hipMemsetAsync(c->seq.fmax, 0, (size_t)B * nfc * sizeof(unsigned), st));
+        HIP_TRY(hipMemsetAsync(c->seq.emax, 0, (size_t)total * 2 * sizeof(unsigned), st));
+        // (1) every clip as one long "window" of nfc frames, zero beyond the clip end
+        const SeqFrames clip_img{c->seq.pow, c->seq.fmax, nfc, 1};
+        if (int rc = launch_mel_power(c, plan, mel_clip_windows(audio_dev, L, B, (nfc - 1) * hop, 0, 0, 1), stream, mel_to_frames(&clip_img))) return rc;
+        // (2) the first and last frame of every window (rows 0 and 1 = frames 0 and T of the window)
+        const SeqFrames edge_img{c->seq.edge, c->seq.emax, 2, (int)(n_frames - 1)};
+        if (int rc = launch_mel_power(c, plan, mel_clip_windows(audio_dev, L, total, W, step, 0, (int)N), stream, mel_to_frames(&edge_img))) return rc;
+        // (3) per tile: window maxima, then the fused core reading rows from both images
+        const SeqCore sc{c->seq.pow, c->seq.edge, (int)nfc, (int)stride_frames, (int)N};
+        for (int64_t w0 = 0; w0 < total; w0 += tile) {
+            const int64_t nw = (total - w0) < tile ? (total - w0) : tile;
+            if (int rc = launch_seq_window_max(c, c->seq.fmax, c->seq.emax, nw, w0, (int)nfc, (int)stride_frames, (int)N,
+                                               (int)n_frames, stream)) return rc;
+            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
+                                              with_outputs(trk ? core_strided_win(&sc, w0) : core_strided(&sc, w0), raw_at(w0), attn_at(w0)))) return rc;
+            if (int rc = stats_take(w0, nw)) return rc;
+        }
+        if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
+        return KM_OK;
+    }
+    for (int64_t w0 = 0; w0 < total; w0 += tile) {
+        const int64_t nw = (total - w0) < tile ? (total - w0) : tile;
+        const MelSrc src = mel_clip_windows(audio_dev, L, nw, W, step, w0, (int)N);
+        if (c->fused_ok) {
+            if (int rc = launch_mel_power(c, plan, src, stream)) return rc;
+            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
+                                              with_outputs(trk ? core_workspace_seq_win(w0) : core_workspace_seq(w0, (int)N), raw_at(w0), attn_at(w0)))) return rc;
+        } else {
+            // generic shapes: staged log-mel, per-window logits gathered from the per-clip ones, GEMM-chain core
+            if (int rc = launch_mel(c, plan, src, 0, c->ws.mel, c->ws.mel_short, stream)) return rc;
+            if (!trk)
+                if (int rc = launch_gather_clip_logits(c, c->ws.zemo, c->ws.zemo_win, nw, w0, (int)N, stream)) return rc;
+            if (int rc = launch_core_generic(c, c->ws.mel, nw, n_frames, c->ws.mel_short, trk ? zemo + w0 : c->ws.zemo_win, out_dev + w0 * c->NB,
+                                             raw_at(w0), attn_at(w0), stream)) return rc;
+        }
+        if (int rc = stats_take(w0, nw)) return rc;
+    }
+    if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
+    return KM_OK;
+}
+
+int km_sequence_forward(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
+                        int32_t stride_frames, int32_t smooth, float* out_dev, void* stream) {
+    if (int rc = need_dual(h)) return rc;
+    if (!audio_dev || !emotion_dev || !out_dev || B <= 0 || L <= 0 || stride_frames <= 0)
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward: bad argument");
+    return sequence_forward(h, audio_dev, B, L, emotion_dev, nullptr, stride_frames, smooth, out_dev, stream);
+}
+
+int km_sequence_forward_track(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* track_dev, int64_t K,
+                              int64_t first_samples, int64_t interval_samples, int64_t sample_offset, int64_t clip_len,
+                              int32_t stride_frames, int32_t smooth, float* out_dev, void* stream) {
+    // the argument checks need no handle state and come first: they hold on a handle that is not finalized yet
+    if (!h || !audio_dev || !track_dev || !out_dev || B <= 0 || L <= 0 || stride_frames <= 0)
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_track: bad argument");
+    const int64_t lim = (int64_t)1 << 62;                  // keeps sample_offset + (window index) * step + window inside int64
+    if (K < 1 || interval_samples < 1 || first_samples < 0 || sample_offset < 0 || clip_len > lim || clip_len < L ||
+        clip_len - L < sample_offset)
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_track: K %lld, first %lld, interval %lld, offset %lld, clip_len %lld for a chunk of %lld",
+                    (long long)K, (long long)first_samples, (long long)interval_samples, (long long)sample_offset, (long long)clip_len,
+                    (long long)L);
+    if (K > 0x7fffffff / B) return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_track: %lld x %lld track rows, at most 2^31 - 1", (long long)B, (long long)K);
+    if (int rc = need_dual(h)) return rc;
+    const SeqTrack trk{track_dev, K, first_samples, interval_samples, sample_offset, clip_len};
+    return sequence_forward(h, audio_dev, B, L, nullptr, &trk, stride_frames, smooth, out_dev, stream);
+}
+
+int km_sequence_forward_attn(km_handle h, const float* audio_dev, int64_t B, int64_t L, const float* emotion_dev,
+                             const float* track_dev, int64_t K, int64_t first_samples, int64_t interval_samples,
+                             int64_t sample_offset, int64_t clip_len, int32_t stride_frames, int32_t smooth,
+                             float* out_dev, float* raw_dev, float* attn_dev, void* stats, void* stream) {
+    // as in km_sequence_forward_track, the argument checks need no handle state and come first
+    if (!h || !audio_dev || !out_dev || B <= 0 || L <= 0 || stride_frames <= 0 || (emotion_dev != nullptr) == (track_dev != nullptr))
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: bad argument (exactly one of emotion_dev and track_dev)");
+    if (track_dev) {
+        const int64_t lim = (int64_t)1 << 62;
+        if (K < 1 || interval_samples < 1 || first_samples < 0 || sample_offset < 0 || clip_len > lim || clip_len < L ||
+            clip_len - L < sample_offset)
+            return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: K %lld, first %lld, interval %lld, offset %lld, clip_len %lld for a chunk of %lld",
+                        (long long)K, (long long)first_samples, (long long)interval_samples, (long long)sample_offset, (long long)clip_len,
+                        (long long)L);
+        if (K > 0x7fffffff / B) return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: %lld x %lld track rows, at most 2^31 - 1", (long long)B, (long long)K);
+    }
+    if (stats && attn_dev && !aligned16(attn_dev))
+        return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: with an accumulator attn_dev must be 16-byte aligned");
+    if (int rc = need_dual(h)) return rc;
+    if (stats) {
+        int32_t q = 0, k = 0;
+        if (int rc = km_attn_stats_shape(stats, &q, &k)) return rc;
+        if (q != 28 || k != h->NK)
+            return fail(KM_ERR_INVALID_ARG, "km_sequence_forward_attn: the accumulator holds %d x %d maps, the model's are 28 x %d", q, k, h->NK);
+    }
+    if (attn_dev || stats)
+        if (int rc = attn_refused(h, "km_sequence_forward_attn")) return rc;
+    const SeqOutputs xo{raw_dev, attn_dev, stats};
+    if (track_dev) {
+        const SeqTrack trk{track_dev, K, first_samples, interval_samples, sample_offset, clip_len};
+        return sequence_forward(h, audio_dev, B, L, nullptr, &trk, stride_frames, smooth, out_dev, stream, xo);
+    }
+    return sequence_forward(h, audio_dev, B, L, emotion_dev, nullptr, stride_frames, smooth, out_dev, stream, xo);
+}
+
+}  // extern "C"

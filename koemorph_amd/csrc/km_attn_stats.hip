@@ -44,18 +44,12 @@
 
 #include <cstdint>
 
+#include <memory>
+
 #include "km_context.h"
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 namespace ast {
 constexpr int CHUNK_ROWS = 16;                     // maps per workgroup: 1 380 windows (4 clips of 20 s) are 87 workgroups
@@ -70,17 +64,17 @@ constexpr int FOLD_THREADS = 256, FOLD_BATCH = 8;
 union AstSlot { double d; long long i; };
 
 struct AttnStatsAcc {
-    AstSlot* state = nullptr;      // device: 1 + rec slots
-    AstSlot* work = nullptr;       // device: max_records partial records
+    DevBuf<AstSlot> state;         // 1 + rec slots
+    DevBuf<AstSlot> work;          // max_records partial records
     int Q = 0, K = 0;
     int lanes_per_q = 0, q_per_wave = 0, q_groups = 0, waves = 0;
     int rec = 0;                   // slots per record: Q K + Q + Q K
     int64_t rows_per_launch = 0;
-    int* table = nullptr;          // device: 4 ints holding the piece's row count (a long long) + rows_per_launch row indices
+    DevBuf<int> table;             // 4 ints holding the piece's row count (a long long) + rows_per_launch row indices
 };
 
 struct AttnStatsStreams {          // km_attn_stats_streams_*: n_streams states of 1 + rec slots, nothing else
-    AstSlot* state = nullptr;
+    DevBuf<AstSlot> state;
     int S = 0, Q = 0, K = 0;
     int lanes_per_q = 0, q_per_wave = 0, q_groups = 0, waves = 0, rec = 0;
 };
@@ -313,7 +307,7 @@ int km_attn_stats_create(void** acc_out, int32_t n_queries, int32_t n_keys, int6
     if (max_rows_per_launch < 0 || max_rows_per_launch > MAX_ROWS_PER_LAUNCH)
         return fail(KM_ERR_INVALID_ARG, "km_attn_stats_create: max_rows_per_launch %lld (0 .. %lld)", (long long)max_rows_per_launch,
                     (long long)MAX_ROWS_PER_LAUNCH);
-    AttnStatsAcc* a = new AttnStatsAcc();
+    auto a = std::make_unique<AttnStatsAcc>();
     a->Q = n_queries; a->K = n_keys;
     a->lanes_per_q = n_keys / 4;
     a->q_per_wave = 64 / a->lanes_per_q;
@@ -322,32 +316,19 @@ int km_attn_stats_create(void** acc_out, int32_t n_queries, int32_t n_keys, int6
     a->rec = 2 * n_queries * n_keys + n_queries;
     a->rows_per_launch = max_rows_per_launch > 0 ? max_rows_per_launch : DEFAULT_ROWS_PER_LAUNCH;
     const int64_t max_rec = (a->rows_per_launch + CHUNK_ROWS - 1) / CHUNK_ROWS;
-    const size_t state_bytes = (size_t)(1 + a->rec) * sizeof(AstSlot);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&a->state), state_bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->work), (size_t)max_rec * a->rec * sizeof(AstSlot));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->table), (size_t)(4 + a->rows_per_launch) * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(a->state, 0, state_bytes);
-    if (e == hipSuccess) e = hipMemset(a->table, 0, (size_t)(4 + a->rows_per_launch) * sizeof(int));
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the cleared state is visible to whichever stream updates first
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (a->state) (void)hipFree(a->state);
-        if (a->work) (void)hipFree(a->work);
-        if (a->table) (void)hipFree(a->table);
-        delete a;
-        return fail(KM_ERR_HIP, "km_attn_stats_create: %s", hipGetErrorString(e));
-    }
-    *acc_out = a;
+    if (int rc = a->state.alloc(1 + a->rec, "km_attn_stats_create")) return rc;
+    if (int rc = a->work.alloc(max_rec * a->rec, "km_attn_stats_create")) return rc;
+    if (int rc = a->table.alloc(4 + a->rows_per_launch, "km_attn_stats_create")) return rc;
+    HIP_TRY(hipMemset(a->state, 0, (size_t)a->state.bytes()));
+    HIP_TRY(hipMemset(a->table, 0, (size_t)a->table.bytes()));
+    HIP_TRY(hipStreamSynchronize(nullptr));   // the cleared state is visible to whichever stream updates first
+    *acc_out = a.release();
     return KM_OK;
 }
 
 int km_attn_stats_destroy(void* acc) {
     if (!acc) return KM_OK;
-    AttnStatsAcc* a = static_cast<AttnStatsAcc*>(acc);
-    if (a->state) (void)hipFree(a->state);
-    if (a->work) (void)hipFree(a->work);
-    if (a->table) (void)hipFree(a->table);
-    delete a;
+    delete static_cast<AttnStatsAcc*>(acc);
     return KM_OK;
 }
 
@@ -401,7 +382,7 @@ int km_attn_stats_update_masked(void* acc, const float* attn_dev, const uint8_t*
     const AstShape s{a->Q, a->K, a->lanes_per_q, a->q_per_wave, a->q_groups, a->rec};
     const int first_int = a->Q * a->K + a->Q;
     hipStream_t st = (hipStream_t)stream;
-    const long long* count = reinterpret_cast<const long long*>(a->table);
+    const long long* count = reinterpret_cast<const long long*>(a->table.p);
     int* table = a->table + 4;
     // piece p holds the selected rows of rank [lo, hi): at most `rows` rows are selected, so these are all the pieces the dense
     // update could cut, and a piece whose ranks do not exist adds records of zeros and a count of 0
@@ -409,7 +390,7 @@ int km_attn_stats_update_masked(void* acc, const float* attn_dev, const uint8_t*
         const int64_t hi = lo + a->rows_per_launch < rows ? lo + a->rows_per_launch : rows;
         const int n_rec = (int)((hi - lo + CHUNK_ROWS - 1) / CHUNK_ROWS);
         hipLaunchKernelGGL(attn_stats_compact_kernel, dim3(1), dim3(AST_COMPACT_THREADS), 0, st, mask_dev, rows, lo, hi, table,
-                           reinterpret_cast<long long*>(a->table));
+                           reinterpret_cast<long long*>(a->table.p));
         hipLaunchKernelGGL(attn_stats_partial_kernel<true>, dim3((unsigned)n_rec), dim3((unsigned)(64 * a->waves)), 0, st, attn_dev, (int64_t)0,
                            (int64_t)0, s, a->work, (const int*)table, count);
         hipLaunchKernelGGL(attn_stats_fold_kernel<true>, dim3((unsigned)((a->rec + FOLD_THREADS - 1) / FOLD_THREADS)), dim3(FOLD_THREADS), 0, st,
@@ -437,32 +418,23 @@ int km_attn_stats_streams_create(void** acc_out, int64_t n_streams, int32_t n_qu
     if (n_queries < 1 || n_queries > 4096 || n_keys < 4 || n_keys % 4 != 0 || n_keys > MAX_KEYS)
         return fail(KM_ERR_INVALID_ARG, "km_attn_stats_streams_create: %d queries x %d keys (keys: a multiple of 4 up to %d)", n_queries, n_keys,
                     MAX_KEYS);
-    AttnStatsStreams* a = new AttnStatsStreams();
+    auto a = std::make_unique<AttnStatsStreams>();
     a->S = (int)n_streams; a->Q = n_queries; a->K = n_keys;
     a->lanes_per_q = n_keys / 4;
     a->q_per_wave = 64 / a->lanes_per_q;
     a->q_groups = (n_queries + a->q_per_wave - 1) / a->q_per_wave;
     a->waves = a->q_groups < MAX_WAVES ? a->q_groups : MAX_WAVES;
     a->rec = 2 * n_queries * n_keys + n_queries;
-    const size_t state_bytes = (size_t)n_streams * (1 + a->rec) * sizeof(AstSlot);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&a->state), state_bytes);
-    if (e == hipSuccess) e = hipMemset(a->state, 0, state_bytes);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (a->state) (void)hipFree(a->state);
-        delete a;
-        return fail(KM_ERR_HIP, "km_attn_stats_streams_create: %s", hipGetErrorString(e));
-    }
-    *acc_out = a;
+    if (int rc = a->state.alloc(n_streams * (1 + a->rec), "km_attn_stats_streams_create")) return rc;
+    HIP_TRY(hipMemset(a->state, 0, (size_t)a->state.bytes()));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    *acc_out = a.release();
     return KM_OK;
 }
 
 int km_attn_stats_streams_destroy(void* acc) {
     if (!acc) return KM_OK;
-    AttnStatsStreams* a = static_cast<AttnStatsStreams*>(acc);
-    if (a->state) (void)hipFree(a->state);
-    delete a;
+    delete static_cast<AttnStatsStreams*>(acc);
     return KM_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "koemorph.h"
+#include "km_devbuf.h"
 
 namespace km {
 
@@ -25,7 +26,7 @@ struct HostParam {
 // A named host buffer produced by folding/packing, mirrored 1:1 on the device.
 struct Packed {
     std::vector<float> host;
-    float* dev = nullptr;
+    DevBuf<float> dev;
 };
 
 constexpr int kMelRpWaves = 8;      // waves per workgroup of mel_power_rp_kernel
@@ -49,16 +50,12 @@ struct MelPlan {
     std::vector<float> fbg_weight;  // four taps x 1/4 per (filter, step), zero padded to the group's step count
     int fbg_extent = 0;             // 1 + the highest bin a step reads (the power rows are padded with zeros up to it)
     // device mirrors
-    float* d_window = nullptr;
-    float* d_twiddle = nullptr;
-    int32_t* d_fb_start = nullptr;
-    int32_t* d_fb_count = nullptr;
-    int32_t* d_fb_offset = nullptr;
-    float* d_fb_weight = nullptr;
-    int32_t* d_fbg_gid = nullptr;
-    int32_t* d_fbg_desc = nullptr;
-    float* d_fbg_weight = nullptr;
-    bool uploaded = false;
+    DevBuf<float> d_window, d_twiddle;
+    DevBuf<int32_t> d_fb_start, d_fb_count, d_fb_offset;
+    DevBuf<float> d_fb_weight;
+    DevBuf<int32_t> d_fbg_gid, d_fbg_desc;
+    DevBuf<float> d_fbg_weight;
+    bool uploaded = false;          // set by upload_mel_plan once every mirror exists
 };
 
 // Run-time switches (km_set_option).  Seeded ONCE per handle, at creation, from the KM_* environment variables of
@@ -105,13 +102,119 @@ struct PerDeviceOnce {
     }
 };
 
+// ---- the device memory of a handle, grouped by what is torn down and rebuilt as a unit: the reset of a group is the assignment of
+// a fresh value (c->st = Streams{}), teardown is the destructor (km_devbuf.h) ----
+
+// km_reserve
+struct Workspace {
+    int64_t windows = 0, samples = 0, frames = 0;
+    int mels = 0;                  // mel bins per frame the power-mel / log-mel / short-term workspaces were sized for
+    DevBuf<float> zemo;            // (windows)             emotion-stream logit
+    DevBuf<float> zemo_win;        // (windows)             per-window copy of per-clip logits (generic sequence mode)
+    DevBuf<float> melpow;          // (windows, frames, 80) power-mel
+    DevBuf<unsigned> melmax;       // (windows)             max power (float bits)
+    DevBuf<float> mel;             // (windows, frames, 80) log-mel
+    DevBuf<float> mel_short;       // (windows, 3, 80)
+    DevBuf<float> generic;         // generic (non-fused) core intermediates, generic_ws_floats() per window; KoeMorphModel: km_koemorph_reserve
+};
+
+// chunk FIFOs in front of the rings (km_stream_fifo_create / _feed / _step): one consuming FIFO per stream (RingBuffer
+// semantics, scripts/rt.py:48-99), popped one frame per step straight into the stream's ring; len == 0 until created
+struct ChunkFifos {
+    int64_t len = 0; int frame = 0;
+    DevBuf<float> samples;               // (n_streams, len)
+    DevBuf<int> state;                   // (3, n_streams): write_ptr | read_ptr | available
+    DevBuf<unsigned char> fire;          // (n_streams) this step popped a frame AND the ring is full: the gate of km_stream_step
+};
+
+// streaming state (km_stream_*): device-resident per-stream audio rings (MelAudioBuffer semantics); n_streams == 0 until created
+struct Streams {
+    int64_t n_streams = 0, ring_len = 0;
+    int ring_hop = 0;
+    DevBuf<float> ring;                  // (n_streams, ring_len)
+    DevBuf<int> ring_wptr;               // (n_streams) write pointer == chronological start once full
+    DevBuf<int> ring_frames;             // (n_streams) frames added
+    DevBuf<unsigned char> ring_ready;    // (n_streams) is_full
+    DevBuf<unsigned char> ring_started;  // (n_streams) EMA state valid
+    DevBuf<float> ring_state;            // (n_streams, 52) EMA state
+    MelPlan* plan = nullptr;
+    int64_t out_frames = 0;
+    ChunkFifos fifo;
+};
+
+// streaming state of the legacy model (km_legacy_stream_*): device-resident consuming FIFOs (RingBuffer semantics,
+// scripts/rt_simplified.py:46-97); grow-only buffers, streams == 0 until km_legacy_stream_create
+struct LegacyFifos {
+    int64_t streams = 0, len = 0, window = 0;
+    DevBuf<float> fifo;                  // (streams, len) samples
+    DevBuf<int> state;                   // (3, streams): write_ptr | read_ptr | available
+    DevBuf<float> stage;                 // (streams, window) the popped windows, chronological
+    DevBuf<unsigned char> ready;         // (streams) this tick popped a window
+    DevBuf<float> attn;                  // (streams, 52, 256) attention output of legacy_stream_kernel
+};
+
+// training state (km_train_* / km_legacy_train_*): flat fp32 master parameters + AdamW moments on the device, in state-dict order
+struct TrainState {
+    int64_t nparams = 0, windows = 0;
+    int64_t early = 0;               // floats [0, early) of the gradient bucket are final when early_ev fires
+    DevEvent early_ev;               // recorded by the step after the last phase that writes an early gradient
+    bool early_recorded = false;
+    std::map<std::string, int64_t> offset;
+    DevBuf<float> params, m, v;
+    DevBuf<float> wcep;              // (d, KP) the channel encoder weight with rows padded to KP floats (zeros): written with params (upload, AdamW)
+    DevBuf<float> part, gnorm, loss;
+    DevBuf<int> steps;               // device-side AdamW step counters (graph replay safe)
+    // training step (km_trainp.hip): activation workspace, dropout masks and per-step mask counter
+    DevBuf<float> act;
+    DevBuf<float> split;             // partial outputs of the split-K gradient products of one step
+    DevBuf<float> tail_part; DevBuf<unsigned> tail_ctr;   // per-workgroup sums of the loss tail + its arrival counter
+    DevBuf<unsigned char> masks;     // mel (W,H,28,NK) | emo (W,H,24) | dec (W,52,DH), W = windows
+    DevBuf<int> drop_ctr;            // device-side step counter of the mask generator (graph-replay safe)
+    // training step of the legacy model (km_legacy_train.hip); parameters, moments and counters are the ones above
+    DevBuf<float> l_ws;              // activations and their gradients, carved for (windows, l_frames)
+    int64_t l_frames = 0;
+    DevBuf<float> l_part;            // split-K partials of one weight gradient, then of its bias gradient
+    DevBuf<unsigned char> l_masks;   // keep flags: enc1 | enc2 | attn | dec1 | dec2, packed for the step's (B, T)
+    int64_t l_mask_B = 0, l_mask_T = 0;   // the (B, T) the masks on the device belong to
+    // training from a resident clip (km_train_step_clip): power-mel of the clip span the batch touches (clip_span_rows, NK), then
+    // (clip_edge, a view into the same allocation) every window's two zero-padded boundary frames (windows, 2, NK); sized by
+    // km_train_init, the span grow-only afterwards
+    DevBuf<float> clip_span; float* clip_edge = nullptr;
+    int64_t clip_span_rows = 0;
+};
+
+// grow-only images of sequence mode and of the eval-mode forward from a resident clip
+struct SeqBufs {
+    // shared-frame sequence mode (km_sequence_forward)
+    DevBuf<float> pow; DevBuf<unsigned> fmax; DevBuf<float> edge; DevBuf<unsigned> emax;
+    // km_sequence_forward_track: the logits of the track's rows (clips * K) and of the sequence's windows (clips * N)
+    DevBuf<float> ztrack, zwin;
+    // km_sequence_forward_attn with an accumulator and no caller's map: the maps of ONE tile (ws.windows, 28, NK)
+    DevBuf<float> attn;
+    // km_forward_clip: the span image (rows, NK) and the edge image (windows, 2, NK) of launch_mel_clip_span, owned by the
+    // inference context (no km_train_init needed)
+    DevBuf<float> fwd_span, fwd_edge;
+};
+
+// two-deep pipeline across calls (km_forward_audio_pipelined)
+struct PipeSlot {
+    DevBuf<float> melpow; DevBuf<unsigned> melmax; DevBuf<float> zemo;
+    bool dirty = true;
+};
+struct Pipeline {
+    DevStream s1, s2;              // front end / core
+    DevEvent ev_in[2], ev_mel[2], ev_core[2];
+    PipeSlot slot[2];
+    int64_t seq = 0, windows = 0, frames = 0;
+};
+
 struct Context {
     km_config cfg{};
     Options opt{};
     int kind = 0;                                // 0 dual-stream production model, 1 legacy SimplifiedKoeMorphModel, 2 legacy KoeMorphModel
     int legacy_hidden = 128;
     km_koemorph_config kmm{};                    // kind 2
-    int64_t kmm_batch = 0, kmm_frames = 0;       // kind 2: reserved workspace (ws_generic)
+    int64_t kmm_batch = 0, kmm_frames = 0;       // kind 2: reserved workspace (ws.generic)
     bool legacy_tail_fused = false;              // kind 1: the blob of legacy_tail_kernel exists as well (decoder 128 wide, 52 queries)
     bool legacy_fused = false;                   // kind 1: the blob of legacy_encoder_kernel exists (d_model 256, 80 mel bins, 8 heads)
     bool kmm_fused = false;                      // kind 2: the model has the width of the fused kernels (km_kmmf.hip) and their blobs exist
@@ -127,101 +230,31 @@ struct Context {
 
     std::vector<MelPlan*> mel_plans;             // [0] = cfg.mel
 
-    // workspace (device)
-    int64_t ws_windows = 0, ws_samples = 0;
-    float* ws_zemo = nullptr;      // (windows)             emotion-stream logit
-    float* ws_zemo_win = nullptr;  // (windows)             per-window copy of per-clip logits (generic sequence mode)
-    float* ws_melpow = nullptr;    // (windows, frames, 80) power-mel
-    unsigned* ws_melmax = nullptr; // (windows)             max power (float bits)
-    unsigned* ws_chunkctr = nullptr;   // (ws_chunkctr_cap) chunk requests per window of mel_power_rp_kernel: zero between launches
-    int64_t ws_chunkctr_cap = 0;
-    float* ws_mel = nullptr;       // (windows, frames, 80) log-mel
-    float* ws_short = nullptr;     // (windows, 3, 80)
-    float* ws_generic = nullptr;   // generic (non-fused) core intermediates, generic_ws_floats() per window
-    int64_t ws_frames = 0;
-    int ws_mels = 0;               // mel bins per frame the power-mel / log-mel / short-term workspaces were sized for
-    // streaming state (km_stream_*): device-resident per-stream audio rings (MelAudioBuffer semantics)
-    int64_t n_streams = 0, ring_len = 0;
-    int ring_hop = 0;
-    float* ring = nullptr;              // (n_streams, ring_len)
-    int* ring_wptr = nullptr;           // (n_streams) write pointer == chronological start once full
-    int* ring_frames = nullptr;         // (n_streams) frames added
-    unsigned char* ring_ready = nullptr;    // (n_streams) is_full
-    unsigned char* ring_started = nullptr;  // (n_streams) EMA state valid
-    float* ring_state = nullptr;        // (n_streams, 52) EMA state
-    MelPlan* stream_plan = nullptr;
-    int64_t stream_out_frames = 0;
-    // chunk FIFOs in front of the rings (km_stream_fifo_create / _feed / _step): one consuming FIFO per stream (RingBuffer
-    // semantics, scripts/rt.py:48-99), popped one frame per step straight into the stream's ring; sfifo_len == 0 until created
-    int64_t sfifo_len = 0; int sfifo_frame = 0;
-    float* sfifo = nullptr;             // (n_streams, sfifo_len) samples
-    int* sfifo_state = nullptr;         // (3, n_streams): write_ptr | read_ptr | available
-    unsigned char* ring_fire = nullptr; // (n_streams) this step popped a frame AND the ring is full: the gate of km_stream_step
-    // streaming state of the legacy model (km_legacy_stream_*): device-resident consuming FIFOs (RingBuffer semantics,
-    // scripts/rt_simplified.py:46-97); grow-only buffers, n_streams == 0 until km_legacy_stream_create
-    int64_t lfifo_streams = 0, lfifo_len = 0, lfifo_window = 0;
-    float* lfifo = nullptr; int64_t lfifo_cap = 0;                  // (streams, lfifo_len) samples
-    int* lfifo_state = nullptr; int64_t lfifo_state_cap = 0;        // (3, streams): write_ptr | read_ptr | available
-    float* lfifo_stage = nullptr; int64_t lfifo_stage_cap = 0;      // (streams, lfifo_window) the popped windows, chronological
-    unsigned char* lfifo_ready = nullptr; int64_t lfifo_ready_cap = 0;   // (streams) this tick popped a window
-    float* lfifo_attn = nullptr; int64_t lfifo_attn_cap = 0;        // (streams, 52, 256) attention output of legacy_stream_kernel
-    // training state (km_train_*): flat fp32 master parameters + AdamW moments on the device, in state-dict order
-    int64_t tr_nparams = 0, tr_windows = 0;
-    int64_t tr_early = 0;            // floats [0, tr_early) of the gradient bucket are final when tr_early_ev fires
-    void* tr_early_ev = nullptr;     // hipEvent_t, recorded by the step after the last phase that writes an early gradient
-    bool tr_early_recorded = false;
-    std::map<std::string, int64_t> tr_offset;
-    float* tr_params = nullptr; float* tr_m = nullptr; float* tr_v = nullptr;
-    float* trp_wcep = nullptr;     // (d, KP) the channel encoder weight with rows padded to KP floats (zeros): written with tr_params (upload, AdamW)
-    float* tr_part = nullptr; float* tr_gnorm = nullptr; float* tr_loss = nullptr;
-    int* tr_steps = nullptr;         // device-side AdamW step counters (graph replay safe)
+    DevBuf<unsigned> ws_chunkctr;                // chunk requests per window of mel_power_rp_kernel: zero between launches; outlives km_reserve
+    Workspace ws;                                // km_reserve
+    Streams st;                                  // km_stream_*
+    LegacyFifos lf;                              // km_legacy_stream_*
+    TrainState tr;                               // km_train_init / km_legacy_train_init
     bool tr_alpha_live = false;      // smoothing_alpha was in the last step's graph (see adamw_kernel)
+    // settings of the training step: they outlive a second km_train_init / km_legacy_train_init
     km_loss_config tr_loss_cfg{};    // extra KoeMorphLoss terms (all weights 0 = off)
-    // training step (km_trainp.hip): activation workspace, dropout masks and per-step mask counter
-    float* trp_act = nullptr; int64_t trp_act_floats = 0;
-    float* trp_split = nullptr; int64_t trp_split_floats = 0;   // partial outputs of the split-K gradient products of one step
-    float* trp_tail_part = nullptr; unsigned* trp_tail_ctr = nullptr;   // per-workgroup sums of the loss tail + its arrival counter
-    void* trp_masks = nullptr;       // bytes: mel (W,H,28,NK) | emo (W,H,24) | dec (W,52,DH), W = tr_windows
-    int* trp_drop_ctr = nullptr;     // device-side step counter of the mask generator (graph-replay safe)
     float tr_dropout_p = 0.f;        // training-mode dropout probability (0 = eval-mode arithmetic)
     int tr_dropout_mode = 0;         // 0: masks drawn per step (Philox), 1: masks supplied by the caller (km_train_set_dropout_masks)
     unsigned long long tr_dropout_seed = 0;
-    // training step of the legacy model (km_legacy_train.hip); parameters, moments, counters and dropout settings are the tr_* above
-    float* ltr_ws = nullptr; int64_t ltr_ws_floats = 0;   // activations and their gradients, carved for (tr_windows, ltr_frames)
-    int64_t ltr_frames = 0;
-    float* ltr_part = nullptr;       // split-K partials of one weight gradient, then of its bias gradient
-    unsigned char* ltr_masks = nullptr; int64_t ltr_mask_bytes = 0;   // keep flags: enc1 | enc2 | attn | dec1 | dec2, packed for the step's (B, T)
-    int64_t ltr_mask_B = 0, ltr_mask_T = 0;               // the (B, T) the masks on the device belong to
-    // shared-frame sequence mode buffers (grow-only, allocated by km_sequence_forward)
-    float* seq_pow = nullptr; unsigned* seq_fmax = nullptr; float* seq_edge = nullptr; unsigned* seq_emax = nullptr;
-    int64_t seq_pow_cap = 0, seq_fmax_cap = 0, seq_edge_cap = 0, seq_emax_cap = 0;
-    // km_sequence_forward_track: the logits of the track's rows (clips * K) and of the sequence's windows (clips * N), grow-only
-    float* seq_ztrack = nullptr; float* seq_zwin = nullptr;
-    int64_t seq_ztrack_cap = 0, seq_zwin_cap = 0;
-    // km_sequence_forward_attn with an accumulator and no caller's map: the maps of ONE tile (ws_windows, 28, NK), grow-only
-    float* seq_attn = nullptr; int64_t seq_attn_cap = 0;
-    // eval-mode forward from a resident clip (km_forward_clip): the span image (rows, NK) and the edge image (windows, 2, NK) of
-    // launch_mel_clip_span, owned by the inference context (no km_train_init needed), grow-only
-    float* fwd_span = nullptr; float* fwd_edge = nullptr;
-    int64_t fwd_span_cap = 0, fwd_edge_cap = 0;
-    // training from a resident clip (km_train_step_clip): power-mel of the clip span the batch touches (rows, NK) and of every
-    // window's two zero-padded boundary frames (windows, 2, NK); sized by km_train_init, the span image grow-only afterwards
-    float* clip_span = nullptr; float* clip_edge = nullptr;
-    int64_t clip_span_cap = 0, clip_edge_cap = 0;
-    int64_t tr_alpha_steps = 0;
+    SeqBufs seq;                                 // km_sequence_forward*, km_forward_clip
+    Pipeline pipe;                               // km_forward_audio_pipelined
     bool stage_timing = false;
-    void* stage_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // hipEvent_t: emo b/e, mel e, core b/e
-    // two-deep pipeline across calls (km_forward_audio_pipelined)
-    void* pipe_s1 = nullptr; void* pipe_s2 = nullptr;      // hipStream_t: front end / core
-    void* pipe_ev_in[2] = {nullptr, nullptr}; void* pipe_ev_mel[2] = {nullptr, nullptr}; void* pipe_ev_core[2] = {nullptr, nullptr};
-    float* pipe_melpow[2] = {nullptr, nullptr}; unsigned* pipe_melmax[2] = {nullptr, nullptr}; float* pipe_zemo[2] = {nullptr, nullptr};
-    bool pipe_dirty[2] = {true, true};
-    int64_t pipe_seq = 0, pipe_windows = 0, pipe_frames = 0;
-    bool melmax_dirty = true;      // ws_melmax may hold stale maxima (see launch_mel_power)
+    DevEvent stage_ev[6];                        // emo b/e, mel e, core b/e
+    bool melmax_dirty = true;      // ws.melmax may hold stale maxima (see launch_mel_power)
+
+    Context() = default;
+    Context(const Context&) = delete;
+    Context& operator=(const Context&) = delete;
+    ~Context() { for (MelPlan* p : mel_plans) delete p; }   // everything else frees itself (km_devbuf.h)
 };
 
 void set_error(const char* fmt, ...);
-int fail(int code, const char* fmt, ...);
+int fail(int code, const char* fmt, ...);   // (also declared by km_devbuf.h)
 
 // km_host.cpp
 int finalize_host(Context* c);
@@ -267,7 +300,7 @@ inline CoreSrc core_table(const ClipTable* t, float* state, int first) { return 
 // the handle's streams: rows of the workspace, EMA state and flags of the rings
 // (gate: the per-stream flags the kernel skips on -- is_full for km_stream_tick, this step's fire flags for km_stream_step)
 inline CoreSrc core_stream(Context* c, const unsigned char* gate = nullptr) {
-    return {c->ring_state, 0, 0, 1, c->stream_out_frames, gate ? gate : c->ring_ready, c->ring_started, nullptr, nullptr};
+    return {c->st.ring_state, 0, 0, 1, c->st.out_frames, gate ? gate : c->st.ring_ready, c->st.ring_started, nullptr, nullptr};
 }
 // any of the sources above with the pre-weight sigmoid values and / or the head-averaged attention map written as well (attn set:
 // the ATTN instantiation of the same source; the split-bf16 variants have none and refuse)
@@ -276,7 +309,7 @@ int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, co
                          const CoreSrc& src);
 int launch_seq_window_max(Context* c, const unsigned* fmax, const unsigned* emax, int64_t nw, int64_t win0, int nfc, int stride,
                           int n_per_clip, int n_frames, void* stream);
-// km_forward_clip: the maximum over each window's OWN n_frames rows of the span / edge images (found through the table) -> ws_melmax
+// km_forward_clip: the maximum over each window's OWN n_frames rows of the span / edge images (found through the table) -> ws.melmax
 int launch_clip_window_max(Context* c, const float* span, const float* edge, const int* start, int64_t B, int min_start,
                            int64_t n_span, int n_frames, void* stream);
 int launch_ema_scan(Context* c, float* x, int64_t B, int64_t N, void* stream);
@@ -290,7 +323,7 @@ int train_adamw(Context* c, const float* flat_grad, float lr, float b1, float b2
 // km_trainp.hip
 int64_t trainp_act_floats(Context* c, int64_t* fixed);
 int64_t trainp_kp(Context* c);
-int64_t trainp_mask_alloc_bytes(Context* c);
+int64_t trainp_mask_alloc_bytes(Context* c, int64_t windows);
 int trainp_mask_sizes(Context* c, int64_t B, int64_t* mel, int64_t* emo, int64_t* dec);
 int trainp_copy_masks(Context* c, int64_t B, unsigned char* mel, unsigned char* emo, unsigned char* dec, int to_device, void* stream);
 // from-audio training step: the front end's power-mel + window maxima, converted and packed by phase 0 of the program
@@ -367,7 +400,7 @@ inline MelSrc mel_clip_windows(const float* clips, int64_t clip_len, int64_t B, 
     return {clips, B, L, clip_len, win_step, win0, wins_per_clip, nullptr, nullptr};
 }
 inline MelSrc mel_rings(Context* c, const unsigned char* gate = nullptr) {
-    return {c->ring, c->n_streams, c->ring_len, c->ring_len, 0, 0, 1, c->ring_wptr, gate ? gate : c->ring_ready};
+    return {c->st.ring, c->st.n_streams, c->st.ring_len, c->st.ring_len, 0, 0, 1, c->st.ring_wptr, gate ? gate : c->st.ring_ready};
 }
 // What a launch may carry, at most one of: the emotion rider (the windows' logits from the same kernel: mel_fuses_emotion, one window
 // per clip), rows into a SeqFrames image instead of the workspace (mel_rp_ok, no rings), the packed training input (mel_packs, a plain batch)
@@ -384,24 +417,19 @@ bool mel_packs(Context* c, MelPlan* p, int64_t n_frames, int64_t T);
 // launch_mel_clip_span: ONE front-end launch writes `span` (n_span, n_mels) = the power-mel of clip frames min_start ..
 // min_start + n_span - 1 (frame f of window b is row start[b] - min_start + f for f = 1 .. T - 1) and `edge` (B, 2, n_mels) =
 // frames 0 and T of every window, the two that see its zero padding.  launch_train_clip_pack: from both images the packed
-// encoder input xt (B, n_mels, KP) as MelPack leaves it and the window maxima into ws_melmax.
+// encoder input xt (B, n_mels, KP) as MelPack leaves it and the window maxima into ws.melmax.
 int launch_mel_clip_span(Context* c, MelPlan* p, const float* clip, int64_t clip_len, const int* start_frames, int64_t B,
                          int min_start, int64_t n_span, int T, float* span, float* edge, void* stream);
 int launch_train_clip_pack(Context* c, MelPlan* p, const float* span, const float* edge, const int* start_frames, int64_t B,
                            int min_start, int64_t n_span, int T, int KP, float* xt, void* stream);
 bool mel_fuses_emotion(Context* c, MelPlan* p);
 int ensure_chunk_counters(Context* c, int64_t windows, void* stream);
-// Grow-only device buffers.  grow_buffer(&ptr, &cap, ...): ptr holds cap units of unit_bytes; when `need` exceeds that it is replaced,
-// once the stream has drained, by one of `need` units (contents undefined).  An allocation cannot be captured: inside a stream
-// capture growth_refused fails with KM_ERR_WORKSPACE, before any HIP call of the entry point.
-int growth_refused(void* stream, const char* what, int64_t need, int64_t cap);
-int grow_buffer(void* ptr_addr, int64_t* cap, int64_t need, size_t unit_bytes, void* stream, const char* what);
 int launch_ring_push(Context* c, const float* samples, int64_t n_per_stream, void* stream);
 
-// km_legacy_stream.hip: the FIFOs of km_legacy_stream_* (Context::lfifo_*)
+// km_legacy_stream.hip: the FIFOs of km_legacy_stream_* (Context::lf)
 int launch_lfifo_push(Context* c, const float* samples, int64_t n_per_stream, const int* counts, void* stream);
 int launch_lfifo_pop(Context* c, unsigned char* ready_out, void* stream);
-// ... and the chunk FIFOs of km_stream_* (Context::sfifo_*): write, pop one frame into the ring, reset the masked streams
+// ... and the chunk FIFOs of km_stream_* (Context::st.fifo): write, pop one frame into the ring, reset the masked streams
 int launch_sfifo_push(Context* c, const float* samples, int64_t n_per_stream, const int* counts, void* stream);
 int launch_sfifo_pop_ring(Context* c, unsigned char* fire_out, unsigned char* ready_out, int* backlog_out, void* stream);
 int launch_stream_reset_masked(Context* c, const unsigned char* mask, void* stream);
@@ -412,7 +440,6 @@ int launch_legacy_stream_model(Context* c, const float* melpow, unsigned* melmax
 int launch_mel(Context* c, MelPlan* p, const MelSrc& src, int64_t out_frames, float* mel_long, float* mel_short, void* stream);
 int launch_mel_packed(Context* c, MelPlan* p, const MelSrc& src, float* xp, int T, int KP, void* stream);
 int upload_mel_plan(MelPlan* p);
-void free_mel_plan(MelPlan* p);
 
 }  // namespace km
 

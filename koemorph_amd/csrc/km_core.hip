@@ -38,14 +38,6 @@ namespace km {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define KM_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 namespace fused {
 constexpr int D = 256, T = 256, NK = 80, NQ = 28, DH = 128;
@@ -982,7 +974,7 @@ __global__ __launch_bounds__(64) void seq_window_max_kernel(const unsigned* __re
 
 int launch_seq_window_max(Context* c, const unsigned* fmax, const unsigned* emax, int64_t nw, int64_t win0, int nfc, int stride,
                           int n_per_clip, int n_frames, void* stream) {
-    hipLaunchKernelGGL(seq_window_max_kernel, dim3((unsigned)nw), dim3(64), 0, (hipStream_t)stream, fmax, emax, c->ws_melmax,
+    hipLaunchKernelGGL(seq_window_max_kernel, dim3((unsigned)nw), dim3(64), 0, (hipStream_t)stream, fmax, emax, c->ws.melmax,
                        win0, nfc, stride, n_per_clip, n_frames);
     HIP_TRY(hipGetLastError());
     c->melmax_dirty = false;     // every slot the following core launch reads was just written (and is re-zeroed by it)
@@ -1025,7 +1017,7 @@ int launch_clip_window_max(Context* c, const float* span, const float* edge, con
                            int64_t n_span, int n_frames, void* stream) {
     if (!span || !edge || !start || B <= 0 || n_frames < 3 || n_span < n_frames || c->NK % 4 != 0)
         return fail(KM_ERR_INVALID_ARG, "clip window maximum: bad argument");
-    hipLaunchKernelGGL(clip_window_max_kernel, dim3((unsigned)B), dim3(CWM_NT), 0, (hipStream_t)stream, span, edge, start, c->ws_melmax,
+    hipLaunchKernelGGL(clip_window_max_kernel, dim3((unsigned)B), dim3(CWM_NT), 0, (hipStream_t)stream, span, edge, start, c->ws.melmax,
                        min_start, (int)n_span, n_frames, c->NK / 4);
     HIP_TRY(hipGetLastError());
     // melmax_dirty stays as it is: slots 0 .. B - 1 were just stored and are re-zeroed by the core launch that follows, the
@@ -1040,7 +1032,7 @@ int launch_core_fused_db(Context* c, MelPlan* p, int64_t B, int64_t n_frames, co
     core_weights(c, a);
     a.zemo = zemo; a.t_in = (int)n_frames;
     a.out = out; a.state = src.state; a.first = src.first; a.win0 = src.win0; a.zemo_div = src.zemo_div > 0 ? src.zemo_div : 1;
-    a.melpow = c->ws_melpow; a.melmax = c->ws_melmax; a.n_frames = (int)n_frames; a.lp = plan_log_params(p);
+    a.melpow = c->ws.melpow; a.melmax = c->ws.melmax; a.n_frames = (int)n_frames; a.lp = plan_log_params(p);
     a.n_use = (int)(src.n_use > 0 ? src.n_use : n_frames); a.ready = src.ready; a.started = src.started;
     a.raw = src.raw; a.attn = src.attn;
     if (src.attn && (c->opt.core_split == 3 || c->opt.core_split == 6))

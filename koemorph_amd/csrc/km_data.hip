@@ -11,14 +11,6 @@
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 // dst[t, k] = float32(np.interp(np.linspace(0, n_src - 1, n_dst)[t], np.arange(n_src), src[:, k]))
 //   np.linspace: step = (n_src - 1) / (n_dst - 1) in float64, x_t = t * step, last point = n_src - 1 exactly

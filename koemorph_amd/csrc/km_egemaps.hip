@@ -26,19 +26,13 @@
 #include <cstring>
 #include <vector>
 
+#include <memory>
+
 #include "km_context.h"
 #include "km_egemaps_ragged.h"
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 namespace egm {
 constexpr int SR = 16000, HOP = 160, N60 = 960, N20 = 320, NFFT = 1024, NB = NFFT / 2 + 1, OFF20 = (N60 - N20) / 2;
@@ -53,7 +47,7 @@ constexpr float VOICING_CUTOFF = 0.55f, RMS_FLOOR = 0.001f;   // on the autocorr
 struct EgmPlan {
     // host tables (double precision arithmetic, stored as float), mirrored on the device
     std::vector<float> h;
-    float* d = nullptr;
+    DevBuf<float> d;
     // offsets into the table blob
     int o_g60, o_ham, o_tw, o_fb_w, o_fb_start, o_fb_count, o_fb_off, o_eql, o_dct, o_logi, o_logf, o_hshift, o_hweight, o_pre, o_cos,
         o_sl0, o_sl1, o_gg;
@@ -983,18 +977,16 @@ extern "C" {
 
 int km_egemaps_plan_create(void** plan_out) {
     if (!plan_out) return fail(KM_ERR_INVALID_ARG, "km_egemaps_plan_create: NULL argument");
-    EgmPlan* p = build_egm_plan();
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p->d), p->h.size() * sizeof(float)));
+    std::unique_ptr<EgmPlan> p(build_egm_plan());
+    if (int rc = p->d.alloc((int64_t)p->h.size(), "km_egemaps_plan_create")) return rc;
     HIP_TRY(hipMemcpy(p->d, p->h.data(), p->h.size() * sizeof(float), hipMemcpyHostToDevice));
-    *plan_out = p;
+    *plan_out = p.release();
     return KM_OK;
 }
 
 int km_egemaps_plan_destroy(void* plan) {
     if (!plan) return KM_OK;
-    EgmPlan* p = static_cast<EgmPlan*>(plan);
-    if (p->d) (void)hipFree(p->d);
-    delete p;
+    delete static_cast<EgmPlan*>(plan);
     return KM_OK;
 }
 

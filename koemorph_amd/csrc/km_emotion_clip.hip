@@ -15,19 +15,13 @@
 
 #include <new>
 
+#include <memory>
+
 #include "km_context.h"
 #include "km_egemaps_ragged.h"
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            (void)hipGetLastError();                                                          \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                  \
-        }                                                                                     \
-    } while (0)
 
 namespace ec {
 constexpr int SR = 16000, NFEAT = 88, NCAT = 3 * NFEAT, NEMO = 256, REC = 36, MAXF = 2048;
@@ -40,7 +34,7 @@ struct EmotionClip {
     int64_t max_slots = 0;
     int ring_len = 0, window_len = 0, update_samples = 0, min_samples = 0, max_nf = 0;
     void* plan = nullptr;
-    char* blob = nullptr;      // one allocation, carved below
+    DevBuf<char> blob;         // one allocation, carved below
     EgmSlot* table = nullptr;  // (max_slots)
     float* scale = nullptr;    // (max_slots)
     float* rec = nullptr;      // (max_slots, max_nf, 36)
@@ -49,6 +43,7 @@ struct EmotionClip {
     float* w = nullptr;        // (256, 264) as nn.Linear stores it
     float* bias = nullptr;     // (256)
     bool has_compression = false;
+    ~EmotionClip() { (void)km_egemaps_plan_destroy(plan); }
 };
 
 static int64_t ec_num_rows(const EmotionClip* e, int64_t clip_len) {
@@ -223,11 +218,11 @@ int km_emotion_clip_create(void** ec_out, double context_window_s, double update
     const int64_t nf = km_egemaps_num_frames(C);
     if (nf > MAXF)
         return fail(KM_ERR_UNSUPPORTED, "km_emotion_clip_create: %lld frames per window, at most %d (20.5 s)", (long long)nf, MAXF);
-    EmotionClip* e = new (std::nothrow) EmotionClip();
+    std::unique_ptr<EmotionClip> e(new (std::nothrow) EmotionClip());
     if (!e) return fail(KM_ERR_HIP, "km_emotion_clip_create: out of host memory");
     e->max_slots = max_slots;
     e->ring_len = (int)R; e->window_len = (int)C; e->update_samples = (int)U; e->min_samples = (int)MIN; e->max_nf = (int)nf;
-    if (const int rc = km_egemaps_plan_create(&e->plan)) { delete e; return rc; }
+    if (const int rc = km_egemaps_plan_create(&e->plan)) return rc;
     const int64_t ms = max_slots;
     // one allocation; `carve` hands out 16-byte aligned pieces, first with a null base to learn the size, then for real
     auto layout = [&](char* base) {
@@ -240,26 +235,16 @@ int km_emotion_clip_create(void** ec_out, double context_window_s, double update
         return at;
     };
     const int64_t bytes = layout(nullptr);
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&e->blob), (size_t)bytes);
-    if (err == hipSuccess) err = hipMemset(e->blob, 0, (size_t)bytes);
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        if (e->blob) (void)hipFree(e->blob);
-        km_egemaps_plan_destroy(e->plan);
-        delete e;
-        return fail(KM_ERR_HIP, "km_emotion_clip_create: %lld bytes of device memory: %s", (long long)bytes, hipGetErrorString(err));
-    }
+    if (int rc = e->blob.alloc(bytes, "km_emotion_clip_create")) return rc;
+    HIP_TRY(hipMemset(e->blob, 0, (size_t)bytes));
     layout(e->blob);
-    *ec_out = e;
+    *ec_out = e.release();
     return KM_OK;
 }
 
 int km_emotion_clip_destroy(void* ec) {
     if (!ec) return KM_OK;
-    EmotionClip* e = static_cast<EmotionClip*>(ec);
-    if (e->blob) (void)hipFree(e->blob);
-    km_egemaps_plan_destroy(e->plan);
-    delete e;
+    delete static_cast<EmotionClip*>(ec);
     return KM_OK;
 }
 

@@ -16,19 +16,13 @@
 #include <cmath>
 #include <new>
 
+#include <memory>
+
 #include "km_context.h"
 #include "km_egemaps_ragged.h"
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            (void)hipGetLastError();                                                          \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                  \
-        }                                                                                     \
-    } while (0)
 
 namespace es {
 constexpr int SR = 16000, NFEAT = 88, NCAT = 3 * NFEAT, NEMO = 256, REC = 36, MAXF = 2048;
@@ -49,7 +43,7 @@ struct EmotionStream {
     int64_t n = 0, max_updates = 0;
     int ring_len = 0, window_len = 0, update_samples = 0, min_samples = 0, max_nf = 0;
     void* plan = nullptr;
-    char* blob = nullptr;      // one allocation, carved below
+    DevBuf<char> blob;         // one allocation, carved below
     float* ring = nullptr;     // (n, ring_len)
     EsState st{};
     float* features = nullptr; // (n, 88)
@@ -63,6 +57,7 @@ struct EmotionStream {
     float* wt = nullptr;       // (264, 256): the compression weight transposed
     float* bias = nullptr;     // (256)
     bool has_compression = false;
+    ~EmotionStream() { (void)km_egemaps_plan_destroy(plan); }
 };
 
 // ---- AudioBuffer.append (:63-96) ----
@@ -209,11 +204,11 @@ int km_emotion_stream_create(void** es_out, int64_t n_streams, double context_wi
     const int64_t nf = km_egemaps_num_frames(C);
     if (nf > MAXF)
         return fail(KM_ERR_UNSUPPORTED, "km_emotion_stream_create: %lld frames per window, at most %d (20.5 s)", (long long)nf, MAXF);
-    EmotionStream* e = new (std::nothrow) EmotionStream();
+    std::unique_ptr<EmotionStream> e(new (std::nothrow) EmotionStream());
     if (!e) return fail(KM_ERR_HIP, "km_emotion_stream_create: out of host memory");
     e->n = n_streams; e->max_updates = max_updates;
     e->ring_len = (int)R; e->window_len = (int)C; e->update_samples = (int)U; e->min_samples = (int)MIN; e->max_nf = (int)nf;
-    if (const int rc = km_egemaps_plan_create(&e->plan)) { delete e; return rc; }
+    if (const int rc = km_egemaps_plan_create(&e->plan)) return rc;
     const int64_t n = n_streams, mu = max_updates;
     // one allocation; `carve` hands out 16-byte aligned pieces, first with a null base to learn the size, then for real
     auto layout = [&](char* base) {
@@ -231,26 +226,17 @@ int km_emotion_stream_create(void** es_out, int64_t n_streams, double context_wi
         return at;
     };
     const int64_t bytes = layout(nullptr);
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&e->blob), (size_t)bytes);
-    if (err == hipSuccess) err = hipMemset(e->blob, 0, (size_t)bytes);
-    if (err == hipSuccess) { layout(e->blob); err = hipMemset(e->st.last_total, 0xff, (size_t)(n * 8)); }       // last_total = -1
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        if (e->blob) (void)hipFree(e->blob);
-        km_egemaps_plan_destroy(e->plan);
-        delete e;
-        return fail(KM_ERR_HIP, "km_emotion_stream_create: %lld bytes of device memory: %s", (long long)bytes, hipGetErrorString(err));
-    }
-    *es_out = e;
+    if (int rc = e->blob.alloc(bytes, "km_emotion_stream_create")) return rc;
+    HIP_TRY(hipMemset(e->blob, 0, (size_t)bytes));
+    layout(e->blob);
+    HIP_TRY(hipMemset(e->st.last_total, 0xff, (size_t)(n * 8)));       // last_total = -1
+    *es_out = e.release();
     return KM_OK;
 }
 
 int km_emotion_stream_destroy(void* es) {
     if (!es) return KM_OK;
-    EmotionStream* e = static_cast<EmotionStream*>(es);
-    if (e->blob) (void)hipFree(e->blob);
-    km_egemaps_plan_destroy(e->plan);
-    delete e;
+    delete static_cast<EmotionStream*>(es);
     return KM_OK;
 }
 

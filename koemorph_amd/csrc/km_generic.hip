@@ -34,14 +34,6 @@
 namespace km {
 
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 namespace gg {
 constexpr int BM = 64, BN = 64, BK = 32, LDT = 80;   // LDS tile row stride (floats)
@@ -562,7 +554,7 @@ __global__ __launch_bounds__(256) void encoder_tn_kernel(const float* __restrict
 template <int NW, int CT, bool FUSE_DB>
 static int launch_encoder_ln(Context* c, int64_t B, hipStream_t st, const float* xp, int KP, const EncSrc& src) {
     hipLaunchKernelGGL((encoder_ln_kernel<NW, CT, FUSE_DB>), dim3((unsigned)B), dim3(64 * NW), 0, st, xp, dv(c, "wce_pg"), dv(c, "bce"),
-                       dv(c, "ln_g"), dv(c, "ln_b"), c->ws_generic, KP, src);
+                       dv(c, "ln_g"), dv(c, "ln_b"), c->ws.generic, KP, src);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
@@ -625,7 +617,7 @@ template <bool FUSE_DB>
 static int launch_core512(Context* c, int64_t B, const float* xp, int KP, const EncSrc& src, const float* zemo, float* out, float* raw,
                           hipStream_t st) {
     const int d = c->d, H = c->H, NKk = c->NK;
-    float* Y = c->ws_generic;
+    float* Y = c->ws.generic;
     float* S = Y + 2 * B * NKk * d;
     Core512Args a{xp, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), S, H * 28,
                   dv(c, "wv_bg"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw};
@@ -660,7 +652,7 @@ int launch_core_generic_packed(Context* c, const float* xp, int64_t B, const flo
                                void* stream) {
     const int d = c->d, NKk = c->NK, KP = (c->KT + 15) / 16 * 16;
     if (NKk != 80) return fail(KM_ERR_UNSUPPORTED, "packed encoder path needs 80 mel channels");
-    float* Y = c->ws_generic;
+    float* Y = c->ws.generic;
     const bool fuse_ln = !c->opt.no_ln_fusion;
     hipStream_t st = (hipStream_t)stream;
     bool ln_done = fuse_ln;
@@ -689,7 +681,7 @@ int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_fr
     if (!generic_core_takes_power(c)) return fail(KM_ERR_UNSUPPORTED, "no fused encoder for d_model=%d", c->d);
     const int KP = (c->KT + 15) / 16 * 16;
     hipStream_t st = (hipStream_t)stream;
-    EncSrc src{c->ws_melpow, c->ws_melmax, (int)n_frames, c->T, plan_log_params(plan)};
+    EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
     if (core512_merge_ok(c, attn)) {
         if (int rc = launch_core512<true>(c, B, nullptr, KP, src, zemo, out, raw, st)) return rc;
         c->melmax_dirty = false;
@@ -728,15 +720,15 @@ __global__ __launch_bounds__(kStreamMapThreads) void stream_head_mean_kernel(con
 int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
                           const unsigned char* gate, float* raw, float* attn) {
     if (!core512_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
-    if (!c->ws_generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
+    if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
     const int d = c->d, H = c->H, NKk = c->NK, KP = (c->KT + 15) / 16 * 16;
-    float* Y = c->ws_generic;
+    float* Y = c->ws.generic;
     float* Sc = Y + 2 * S * NKk * d;
-    const EncSrc src{c->ws_melpow, c->ws_melmax, (int)n_frames, c->T, plan_log_params(plan)};
+    const EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
     Core512StreamArgs sa{{nullptr, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), Sc, H * 28,
                           dv(c, "wv_bg"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw},
-                         {(int)(c->stream_out_frames > 0 ? c->stream_out_frames : n_frames), gate ? gate : c->ring_ready, c->ring_started,
-                          c->ring_state, c->alpha}};
+                         {(int)(c->st.out_frames > 0 ? c->st.out_frames : n_frames), gate ? gate : c->st.ring_ready, c->st.ring_started,
+                          c->st.ring_state, c->alpha}};
     static PerDeviceOnce once;
     if (once.first(c->device)) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_stream_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
@@ -757,7 +749,7 @@ int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames
 
 float* generic_packed_x(Context* c, int64_t B) {     // the packed-X slot behind the other intermediates of B windows
     const int64_t d = c->d, H = c->H, NKk = c->NK;
-    return c->ws_generic + B * (2 * NKk * d + H * 28 * NKk + 28 * d + 28 * (d / 2));
+    return c->ws.generic + B * (2 * NKk * d + H * 28 * NKk + 28 * d + 28 * (d / 2));
 }
 
 // caller-provided log-mel (B, T_in, 80) + short-term rows (B, 3, 80) -> packed encoder input (B, KP, 80):
@@ -787,7 +779,7 @@ int launch_core_generic(Context* c, const float* mel, int64_t B, int64_t T_in, c
         HIP_TRY(hipGetLastError());
         return launch_core_generic_packed(c, xp, B, zemo, out, raw, attn, stream);
     }
-    float* Y = c->ws_generic;
+    float* Y = c->ws.generic;
     const float* Wce = dv(c, "wce_raw");
     GemmArgs g{};
     g.alpha = 1.f; g.batch2 = 1;
@@ -807,7 +799,7 @@ int launch_core_generic(Context* c, const float* mel, int64_t B, int64_t T_in, c
 static int core_generic_after_encoder(Context* c, int64_t B, const float* zemo, float* out, float* raw, float* attn, void* stream,
                                       bool ln_done) {
     const int d = c->d, H = c->H, hd = c->hd, DH = c->DH, NKk = c->NK;
-    float* Y = c->ws_generic;
+    float* Y = c->ws.generic;
     float* V = Y + B * NKk * d;
     float* S = V + B * NKk * d;
     float* O = S + B * H * 28 * NKk;
@@ -932,11 +924,11 @@ int launch_legacy_attn_tail_fused(Context* c, const float* Kp, const float* Vp, 
 // (the caller has checked legacy_pow_ok); the attention kernel then puts the maxima back to zero
 bool legacy_pow_ok(Context* c) {
     return c->legacy_fused && !c->opt.legacy_no_enc_fusion && !c->opt.legacy_no_attn_fusion && c->hd == 32 && c->NB <= 64 &&
-           (reinterpret_cast<uintptr_t>(c->ws_melpow) & 15) == 0;
+           (reinterpret_cast<uintptr_t>(c->ws.melpow.p) & 15) == 0;
 }
 int launch_legacy(Context* c, const float* mel, int64_t B, int64_t Tm, float* out, void* stream, const LegacyPowSrc* pow_src) {
     const int d = c->d, H = c->H, hd = c->hd, NQ = c->NB, hid = c->legacy_hidden, NKk = c->NK;
-    float* E1 = c->ws_generic;
+    float* E1 = c->ws.generic;
     float* E = E1 + B * Tm * d;
     float* Kp = E + B * Tm * d;
     float* Vp = Kp + B * Tm * d;

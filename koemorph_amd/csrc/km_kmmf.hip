@@ -29,14 +29,6 @@
 #include "km_gemm.h"
 #include "km_kmmf.h"
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return km::fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                       \
-        }                                                                                                                              \
-    } while (0)
 
 namespace km {
 

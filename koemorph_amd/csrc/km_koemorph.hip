@@ -11,14 +11,6 @@
 #include "km_context.h"
 #include "km_gemm.h"
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return km::fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                       \
-        }                                                                                                                              \
-    } while (0)
 
 namespace km {
 
@@ -218,7 +210,7 @@ int launch_koemorph(Context* c, const float* mel, const float* emo, int64_t B, i
     const int d = c->d, H = c->H, hd = c->hd, NB = c->NB, hid = k.decoder_hidden_dim, L = k.num_attention_layers;
     const int64_t R = B * T, RQ = B * NB;
     const int64_t s_enc = 8 * T * T, s_x = (int64_t)H * NB * T;
-    float* xm = c->ws_generic;
+    float* xm = c->ws.generic;
     float* xe = xm + R * d;
     float* qkv = xe + R * d;
     float* S = qkv + R * 3 * d;

@@ -1,7 +1,7 @@
 // Device-resident FIFOs of km_legacy_stream_* -- the reference's RingBuffer (scripts/rt_simplified.py:46-97) for every stream at
-// once.  A stream owns lfifo_len samples and three integers (write_ptr, read_ptr, available) in Context::lfifo_state.
+// once.  A stream owns lf.len samples and three integers (write_ptr, read_ptr, available) in Context::lf.state.
 //
-//   fifo_push_kernel   RingBuffer.write (:56-77): stream s appends min(count[s], lfifo_len - available[s]) samples at its write
+//   fifo_push_kernel   RingBuffer.write (:56-77): stream s appends min(count[s], lf.len - available[s]) samples at its write
 //                      pointer, with wrap-around, and drops the rest.
 //   fifo_pop_kernel    RingBuffer.read(audio_length) (:79-97): ready[s] = available[s] >= audio_length; a ready stream's window
 //                      is copied in chronological order into the dense staging image (streams, audio_length) that the plain
@@ -11,7 +11,7 @@
 // barrier -- plain stores, no atomics, nothing read back by the host.
 //
 // The chunk FIFOs of km_stream_feed / _step (the production model's loop, scripts/rt.py:48-99, 343-372) have the same layout in
-// Context::sfifo_* and share fifo_push_kernel.  Their pop has no staging image, because the destination is the stream's ring:
+// Context::st.fifo and share fifo_push_kernel.  Their pop has no staging image, because the destination is the stream's ring:
 //
 //   fifo_pop_ring_kernel         RingBuffer.read(frame) + MelAudioBuffer.add_audio_frame (mel_sliding_window.py:70-116) for every
 //                                stream that holds a frame; fire[s] = popped && is_full is the gate of the step's other kernels.
@@ -22,14 +22,6 @@
 
 #include "km_context.h"
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            (void)hipGetLastError();                                                          \
-            return km::fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));              \
-        }                                                                                     \
-    } while (0)
 
 namespace km {
 
@@ -174,39 +166,39 @@ __global__ __launch_bounds__(64) void stream_reset_masked_kernel(const unsigned 
 }
 
 int launch_lfifo_push(Context* c, const float* samples, int64_t n_per_stream, const int* counts, void* stream) {
-    hipLaunchKernelGGL(fifo_push_kernel, dim3((unsigned)c->lfifo_streams), dim3(kFifoPushThreads), 0, (hipStream_t)stream, c->lfifo,
-                       c->lfifo_state, (int)c->lfifo_streams, (int)c->lfifo_len, samples, (int)n_per_stream, counts);
+    hipLaunchKernelGGL(fifo_push_kernel, dim3((unsigned)c->lf.streams), dim3(kFifoPushThreads), 0, (hipStream_t)stream, c->lf.fifo,
+                       c->lf.state, (int)c->lf.streams, (int)c->lf.len, samples, (int)n_per_stream, counts);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
 
 int launch_lfifo_pop(Context* c, unsigned char* ready_out, void* stream) {
-    hipLaunchKernelGGL(fifo_pop_kernel, dim3((unsigned)c->lfifo_streams), dim3(kFifoPopThreads), 0, (hipStream_t)stream, c->lfifo,
-                       c->lfifo_state, (int)c->lfifo_streams, (int)c->lfifo_len, (int)c->lfifo_window, c->lfifo_stage, c->lfifo_ready,
+    hipLaunchKernelGGL(fifo_pop_kernel, dim3((unsigned)c->lf.streams), dim3(kFifoPopThreads), 0, (hipStream_t)stream, c->lf.fifo,
+                       c->lf.state, (int)c->lf.streams, (int)c->lf.len, (int)c->lf.window, c->lf.stage, c->lf.ready,
                        ready_out);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
 
 int launch_sfifo_push(Context* c, const float* samples, int64_t n_per_stream, const int* counts, void* stream) {
-    hipLaunchKernelGGL(fifo_push_kernel, dim3((unsigned)c->n_streams), dim3(kFifoPushThreads), 0, (hipStream_t)stream, c->sfifo,
-                       c->sfifo_state, (int)c->n_streams, (int)c->sfifo_len, samples, (int)n_per_stream, counts);
+    hipLaunchKernelGGL(fifo_push_kernel, dim3((unsigned)c->st.n_streams), dim3(kFifoPushThreads), 0, (hipStream_t)stream, c->st.fifo.samples,
+                       c->st.fifo.state, (int)c->st.n_streams, (int)c->st.fifo.len, samples, (int)n_per_stream, counts);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
 
 int launch_sfifo_pop_ring(Context* c, unsigned char* fire_out, unsigned char* ready_out, int* backlog_out, void* stream) {
-    hipLaunchKernelGGL(fifo_pop_ring_kernel, dim3((unsigned)c->n_streams), dim3(kFifoPushThreads), 0, (hipStream_t)stream, c->sfifo,
-                       c->sfifo_state, (int)c->n_streams, (int)c->sfifo_len, c->sfifo_frame, c->ring, c->ring_wptr, c->ring_frames,
-                       c->ring_ready, c->ring_hop, (int)c->ring_len, c->ring_fire, fire_out, ready_out, backlog_out);
+    hipLaunchKernelGGL(fifo_pop_ring_kernel, dim3((unsigned)c->st.n_streams), dim3(kFifoPushThreads), 0, (hipStream_t)stream, c->st.fifo.samples,
+                       c->st.fifo.state, (int)c->st.n_streams, (int)c->st.fifo.len, c->st.fifo.frame, c->st.ring, c->st.ring_wptr, c->st.ring_frames,
+                       c->st.ring_ready, c->st.ring_hop, (int)c->st.ring_len, c->st.fifo.fire, fire_out, ready_out, backlog_out);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
 
 int launch_stream_reset_masked(Context* c, const unsigned char* mask, void* stream) {
-    hipLaunchKernelGGL(stream_reset_masked_kernel, dim3((unsigned)c->n_streams), dim3(64), 0, (hipStream_t)stream, mask, (int)c->n_streams,
-                       c->sfifo_len > 0 ? c->sfifo_state : nullptr, c->ring_wptr, c->ring_frames, c->ring_ready, c->ring_started,
-                       c->ring_fire, c->ring_state, c->NB);
+    hipLaunchKernelGGL(stream_reset_masked_kernel, dim3((unsigned)c->st.n_streams), dim3(64), 0, (hipStream_t)stream, mask, (int)c->st.n_streams,
+                       c->st.fifo.len > 0 ? c->st.fifo.state : nullptr, c->st.ring_wptr, c->st.ring_frames, c->st.ring_ready, c->st.ring_started,
+                       c->st.fifo.fire, c->st.ring_state, c->NB);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

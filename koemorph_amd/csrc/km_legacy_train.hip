@@ -30,14 +30,6 @@
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 #include "km_philox.h"
 #include "km_train_tail.h"
@@ -494,7 +486,7 @@ static int wgrad(Context* c, const float* dY, int64_t ldy, int N, const float* X
     split_rows(rows, &chunk, &whole, &rem);
     const int parts = whole + (rem > 0 ? 1 : 0);
     const int64_t mn = (int64_t)N * K;
-    float* part = parts > 1 ? c->ltr_part : dW;
+    float* part = parts > 1 ? c->tr.l_part : dW;
     GemmArgs g{};
     g.alpha = 1.f; g.batch2 = 1;
     g.a_rs = 1; g.a_cs = ldy; g.b_rs = ldx; g.b_cs = 1; g.c_rs = K; g.M = N; g.N = K;
@@ -510,7 +502,7 @@ static int wgrad(Context* c, const float* dY, int64_t ldy, int N, const float* X
     }
     if (parts > 1) hipLaunchKernelGGL(ltr_sum_parts_kernel, dim3((unsigned)((mn + 255) / 256)), dim3(256), 0, st, part, mn, parts, dW);
     if (db) {
-        float* bpart = parts > 1 ? c->ltr_part + (int64_t)ltr::MAX_PARTS * 512 * 256 : db;
+        float* bpart = parts > 1 ? c->tr.l_part + (int64_t)ltr::MAX_PARTS * 512 * 256 : db;
         hipLaunchKernelGGL(ltr_colsum_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)parts), dim3(256), 0, st, dY, rows, N, ldy, chunk, bpart);
         if (parts > 1) hipLaunchKernelGGL(ltr_sum_parts_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, bpart, (int64_t)N, parts, db);
     }
@@ -535,62 +527,61 @@ struct LtrWs {
 };
 
 // the workspace is carved for (max_windows, max_frames): the offsets do not depend on the step's (B, T)
-static int64_t carve(Context* c, LtrWs* q) {
+static int64_t carve(float* base, int64_t windows, int64_t frames, LtrWs* q) {
     using namespace ltr;
-    const int64_t Rm = c->tr_windows * c->ltr_frames, R2 = c->tr_windows * NQ;
+    const int64_t Rm = windows * frames, R2 = windows * NQ;
     int64_t off = 0;
-    auto take = [&](float** p, int64_t n) { *p = c->ltr_ws ? c->ltr_ws + off : nullptr; off += (n + 3) / 4 * 4; };
+    auto take = [&](float** p, int64_t n) { *p = base ? base + off : nullptr; off += (n + 3) / 4 * 4; };
     take(&q->mel, Rm * NK); take(&q->E1, Rm * D); take(&q->E2, Rm * D); take(&q->KV, Rm * 2 * D); take(&q->dKV, Rm * 2 * D);
     take(&q->dE2, Rm * D); take(&q->dE1, Rm * D); take(&q->Q, NQ * D); take(&q->dQ, NQ * D);
     take(&q->O, R2 * D); take(&q->A1, R2 * D); take(&q->dA1, R2 * D); take(&q->dO, R2 * D);
     take(&q->D1, R2 * HID); take(&q->D2, R2 * HID); take(&q->dD1, R2 * HID); take(&q->dD2, R2 * HID);
-    take(&q->Z3, R2 * NQ); take(&q->dZ3, R2 * NQ); take(&q->dQpart, R2 * D); take(&q->out, c->tr_windows * NQ);
-    take(&q->stat_m, c->tr_windows * H * NQ); take(&q->stat_il, c->tr_windows * H * NQ);
+    take(&q->Z3, R2 * NQ); take(&q->dZ3, R2 * NQ); take(&q->dQpart, R2 * D); take(&q->out, windows * NQ);
+    take(&q->stat_m, windows * H * NQ); take(&q->stat_il, windows * H * NQ);
     return off;
 }
 
 int legacy_train_init(Context* c, int64_t max_windows, int64_t max_frames, void* stream) {
     using namespace ltr;
     hipStream_t st = (hipStream_t)stream;
-    c->tr_offset.clear();
+    c->tr.offset.clear();
     int64_t off = 0;
     for (const auto& k : c->param_order) {      // state-dict order, every offset a multiple of 4 floats (16 B)
-        c->tr_offset[k] = off;
+        c->tr.offset[k] = off;
         off += ((int64_t)c->params.at(k).data.size() + 3) / 4 * 4;
     }
-    c->tr_nparams = off; c->tr_early = off;
+    c->tr.nparams = off; c->tr.early = off;
     const size_t nb = (size_t)off * sizeof(float);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_params), nb));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_m), nb));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_v), nb));
-    HIP_TRY(hipMemsetAsync(c->tr_m, 0, nb, st));
-    HIP_TRY(hipMemsetAsync(c->tr_v, 0, nb, st));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_part), 256 * sizeof(float)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_gnorm), sizeof(float)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_loss), sizeof(float)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->tr_steps), 2 * sizeof(int)));
-    HIP_TRY(hipMemsetAsync(c->tr_steps, 0, 2 * sizeof(int), st));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->trp_drop_ctr), sizeof(int)));
-    HIP_TRY(hipMemsetAsync(c->trp_drop_ctr, 0, sizeof(int), st));
-    c->tr_windows = max_windows; c->ltr_frames = max_frames;
+    const char* what = "km_legacy_train_init";
+    if (int rc = c->tr.params.alloc(off, what)) return rc;
+    if (int rc = c->tr.m.alloc(off, what)) return rc;
+    if (int rc = c->tr.v.alloc(off, what)) return rc;
+    HIP_TRY(hipMemsetAsync(c->tr.m, 0, nb, st));
+    HIP_TRY(hipMemsetAsync(c->tr.v, 0, nb, st));
+    if (int rc = c->tr.part.alloc(256, what)) return rc;
+    if (int rc = c->tr.gnorm.alloc(1, what)) return rc;
+    if (int rc = c->tr.loss.alloc(1, what)) return rc;
+    if (int rc = c->tr.steps.alloc(2, what)) return rc;
+    HIP_TRY(hipMemsetAsync(c->tr.steps, 0, 2 * sizeof(int), st));
+    if (int rc = c->tr.drop_ctr.alloc(1, what)) return rc;
+    HIP_TRY(hipMemsetAsync(c->tr.drop_ctr, 0, sizeof(int), st));
     c->tr_dropout_p = 0.f; c->tr_dropout_mode = 0; c->tr_dropout_seed = 0; c->tr_loss_cfg = km_loss_config{};
-    c->ltr_mask_B = c->ltr_mask_T = 0;
-    { LtrWs tmp{}; c->ltr_ws_floats = carve(c, &tmp); }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ltr_ws), (size_t)c->ltr_ws_floats * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(c->ltr_ws, 0, (size_t)c->ltr_ws_floats * sizeof(float), st));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ltr_part), (size_t)MAX_PARTS * (512 * 256 + 512) * sizeof(float)));
+    LtrWs tmp{};
+    if (int rc = c->tr.l_ws.alloc(carve(nullptr, max_windows, max_frames, &tmp), what)) return rc;
+    HIP_TRY(hipMemsetAsync(c->tr.l_ws, 0, (size_t)c->tr.l_ws.bytes(), st));
+    if (int rc = c->tr.l_part.alloc((int64_t)MAX_PARTS * (512 * 256 + 512), what)) return rc;
     int64_t mo[6];
     legacy_train_mask_layout(max_windows, max_frames, mo);
-    c->ltr_mask_bytes = mo[5];
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->ltr_masks), (size_t)c->ltr_mask_bytes));
-    HIP_TRY(hipMemsetAsync(c->ltr_masks, 1, (size_t)c->ltr_mask_bytes, st));
+    if (int rc = c->tr.l_masks.alloc(mo[5], what)) return rc;
+    HIP_TRY(hipMemsetAsync(c->tr.l_masks, 1, (size_t)c->tr.l_masks.n, st));
     std::vector<float> flat((size_t)off, 0.f);
     for (const auto& k : c->param_order) {
         const HostParam& hp = c->params.at(k);
-        std::memcpy(flat.data() + c->tr_offset.at(k), hp.data.data(), hp.data.size() * sizeof(float));
+        std::memcpy(flat.data() + c->tr.offset.at(k), hp.data.data(), hp.data.size() * sizeof(float));
     }
-    HIP_TRY(hipMemcpyAsync(c->tr_params, flat.data(), nb, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->tr.params, flat.data(), nb, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
+    c->tr.windows = max_windows; c->tr.l_frames = max_frames;     // the step's guards: written when everything above exists
     return KM_OK;
 }
 
@@ -598,21 +589,21 @@ int legacy_train_copy_masks(Context* c, int64_t B, int64_t T, unsigned char* con
     hipStream_t st = (hipStream_t)stream;
     int64_t mo[6];
     legacy_train_mask_layout(B, T, mo);
-    if (!to_device && (B != c->ltr_mask_B || T != c->ltr_mask_T))
-        return fail(KM_ERR_INVALID_ARG, "the masks on the device are those of a (%lld, %lld) step, not (%lld, %lld)", (long long)c->ltr_mask_B,
-                    (long long)c->ltr_mask_T, (long long)B, (long long)T);
+    if (!to_device && (B != c->tr.l_mask_B || T != c->tr.l_mask_T))
+        return fail(KM_ERR_INVALID_ARG, "the masks on the device are those of a (%lld, %lld) step, not (%lld, %lld)", (long long)c->tr.l_mask_B,
+                    (long long)c->tr.l_mask_T, (long long)B, (long long)T);
     HIP_TRY(hipStreamSynchronize(st));
     for (int s = 0; s < 5; ++s) {
-        if (to_device) HIP_TRY(hipMemcpy(c->ltr_masks + mo[s], host[s], (size_t)(mo[s + 1] - mo[s]), hipMemcpyHostToDevice));
-        else HIP_TRY(hipMemcpy(host[s], c->ltr_masks + mo[s], (size_t)(mo[s + 1] - mo[s]), hipMemcpyDeviceToHost));
+        if (to_device) HIP_TRY(hipMemcpy(c->tr.l_masks + mo[s], host[s], (size_t)(mo[s + 1] - mo[s]), hipMemcpyHostToDevice));
+        else HIP_TRY(hipMemcpy(host[s], c->tr.l_masks + mo[s], (size_t)(mo[s + 1] - mo[s]), hipMemcpyDeviceToHost));
     }
-    if (to_device) { c->ltr_mask_B = B; c->ltr_mask_T = T; }
+    if (to_device) { c->tr.l_mask_B = B; c->tr.l_mask_T = T; }
     return KM_OK;
 }
 
 float* legacy_train_mel_buffer(Context* c) {
     LtrWs w{};
-    carve(c, &w);
+    carve(c->tr.l_ws, c->tr.windows, c->tr.l_frames, &w);
     return w.mel;
 }
 
@@ -621,11 +612,11 @@ int legacy_train_step(Context* c, const float* mel, int64_t B, int64_t T, const 
     using namespace ltr;
     hipStream_t st = (hipStream_t)stream;
     LtrWs w{};
-    carve(c, &w);
+    carve(c->tr.l_ws, c->tr.windows, c->tr.l_frames, &w);
     const int64_t R = B * T, R2 = B * NQ;
-    const float* P = c->tr_params;
-    auto par = [&](const char* k) { return P + c->tr_offset.at(k); };
-    auto gr = [&](const char* k) { return grad + c->tr_offset.at(k); };
+    const float* P = c->tr.params;
+    auto par = [&](const char* k) { return P + c->tr.offset.at(k); };
+    auto gr = [&](const char* k) { return grad + c->tr.offset.at(k); };
     const float *W0 = par("audio_encoder.0.weight"), *b0 = par("audio_encoder.0.bias"), *W3 = par("audio_encoder.3.weight"),
                 *b3 = par("audio_encoder.3.bias"), *Win = par("attention.in_proj_weight"), *bin = par("attention.in_proj_bias"),
                 *Wo = par("attention.out_proj.weight"), *bo = par("attention.out_proj.bias"), *Wd0 = par("decoder.0.weight"),
@@ -636,16 +627,16 @@ int legacy_train_step(Context* c, const float* mel, int64_t B, int64_t T, const 
     const float sc = drop ? 1.0f / (1.0f - p) : 1.0f;
     int64_t mo[6];
     legacy_train_mask_layout(B, T, mo);
-    unsigned char* M = c->ltr_masks;
-    if (drop && c->tr_dropout_mode == 1 && (c->ltr_mask_B != B || c->ltr_mask_T != T))
+    unsigned char* M = c->tr.l_masks;
+    if (drop && c->tr_dropout_mode == 1 && (c->tr.l_mask_B != B || c->tr.l_mask_T != T))
         return fail(KM_ERR_INVALID_ARG, "external dropout masks were set for a (%lld, %lld) step, this one is (%lld, %lld)",
-                    (long long)c->ltr_mask_B, (long long)c->ltr_mask_T, (long long)B, (long long)T);
+                    (long long)c->tr.l_mask_B, (long long)c->tr.l_mask_T, (long long)B, (long long)T);
     if (drop && c->tr_dropout_mode == 0) {
         double t = (double)p * 4294967296.0;
         const unsigned thr = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
-        hipLaunchKernelGGL(ltr_mask_gen_kernel, dim3((unsigned)((mo[5] / 4 + 255) / 256)), dim3(256), 0, st, M, mo[5], c->trp_drop_ctr,
+        hipLaunchKernelGGL(ltr_mask_gen_kernel, dim3((unsigned)((mo[5] / 4 + 255) / 256)), dim3(256), 0, st, M, mo[5], c->tr.drop_ctr,
                            (unsigned)c->tr_dropout_seed, (unsigned)(c->tr_dropout_seed >> 32), thr);
-        c->ltr_mask_B = B; c->ltr_mask_T = T;
+        c->tr.l_mask_B = B; c->tr.l_mask_T = T;
     }
     auto drop_rows = [&](float* x, int site, int64_t n) {
         if (drop) hipLaunchKernelGGL(ltr_drop_rows_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, x, M + mo[site], n, sc);
@@ -669,7 +660,7 @@ int legacy_train_step(Context* c, const float* mel, int64_t B, int64_t T, const 
     drop_rows(w.D2, 4, R2 * HID);
     if (int rc = launch_gemm(lin(w.D2, HID, Wd6, HID, w.Z3, R2, NQ, bd6, 0), 1, stream)) return rc;
     hipLaunchKernelGGL(ltr_loss_kernel, dim3(1), dim3(256), 0, st, w.Z3, target, (int)B, mse_w, l1_w, c->tr_loss_cfg, w.out, out_dev, w.dZ3,
-                       loss_dev, c->trp_drop_ctr);
+                       loss_dev, c->tr.drop_ctr);
     HIP_TRY(hipGetLastError());
     // ---- backward: decoder and out_proj on the B 52 rows ----
     if (int rc = wgrad(c, w.dZ3, NQ, NQ, w.D2, HID, HID, R2, gr("decoder.6.weight"), gr("decoder.6.bias"), stream)) return rc;

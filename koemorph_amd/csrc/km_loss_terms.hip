@@ -36,18 +36,12 @@
 //   loss_terms_compute_kernel   one thread per output: sum / count, rounded once.
 #include <hip/hip_runtime.h>
 
+#include <memory>
+
 #include "km_context.h"
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 namespace lt {
 constexpr int NC = 52, NL = 136;
@@ -63,8 +57,8 @@ struct LossTermsState {
 };
 
 struct LossTermsAcc {
-    LossTermsState* state = nullptr;    // device
-    double* work = nullptr;             // device, MAX_WGS partial records
+    DevBuf<LossTermsState> state;
+    DevBuf<double> work;                // MAX_WGS partial records
 };
 
 struct LossTermsArgs {
@@ -225,28 +219,18 @@ extern "C" {
 
 int km_loss_terms_create(void** acc_out) {
     if (!acc_out) return fail(KM_ERR_INVALID_ARG, "km_loss_terms_create: NULL argument");
-    LossTermsAcc* a = new LossTermsAcc();
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&a->state), sizeof(LossTermsState));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->work), (size_t)lt::MAX_WGS * lt::NQ * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(a->state, 0, sizeof(LossTermsState));
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the cleared state is visible to whichever stream updates first
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (a->state) (void)hipFree(a->state);
-        if (a->work) (void)hipFree(a->work);
-        delete a;
-        return fail(KM_ERR_HIP, "km_loss_terms_create: %s", hipGetErrorString(e));
-    }
-    *acc_out = a;
+    auto a = std::make_unique<LossTermsAcc>();
+    if (int rc = a->state.alloc(1, "km_loss_terms_create")) return rc;
+    if (int rc = a->work.alloc((int64_t)lt::MAX_WGS * lt::NQ, "km_loss_terms_create")) return rc;
+    HIP_TRY(hipMemset(a->state, 0, sizeof(LossTermsState)));
+    HIP_TRY(hipStreamSynchronize(nullptr));   // the cleared state is visible to whichever stream updates first
+    *acc_out = a.release();
     return KM_OK;
 }
 
 int km_loss_terms_destroy(void* acc) {
     if (!acc) return KM_OK;
-    LossTermsAcc* a = static_cast<LossTermsAcc*>(acc);
-    if (a->state) (void)hipFree(a->state);
-    if (a->work) (void)hipFree(a->work);
-    delete a;
+    delete static_cast<LossTermsAcc*>(acc);
     return KM_OK;
 }
 

@@ -31,14 +31,6 @@
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 namespace mel {
 constexpr int FPB = 16;          // frames per workgroup
@@ -1170,36 +1162,27 @@ __global__ __launch_bounds__(256) void mel_log_packed_kernel(LogArgs a, float* _
 
 // ---------------------------------------------------------------------------------------------
 template <typename Tv>
-static int upload(Tv** dst, const std::vector<Tv>& src) {
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(dst), src.size() * sizeof(Tv)));
-    HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(Tv), hipMemcpyHostToDevice));
+static int upload(DevBuf<Tv>& dst, const std::vector<Tv>& src) {
+    if (int rc = dst.alloc((int64_t)src.size(), "front-end plan")) return rc;
+    HIP_TRY(hipMemcpy(dst, src.data(), src.size() * sizeof(Tv), hipMemcpyHostToDevice));
     return KM_OK;
 }
 
 int upload_mel_plan(MelPlan* p) {
     if (p->uploaded) return KM_OK;
-    if (int rc = upload(&p->d_window, p->window)) return rc;
-    if (int rc = upload(&p->d_twiddle, p->twiddle)) return rc;
-    if (int rc = upload(&p->d_fb_start, p->fb_start)) return rc;
-    if (int rc = upload(&p->d_fb_count, p->fb_count)) return rc;
-    if (int rc = upload(&p->d_fb_offset, p->fb_offset)) return rc;
-    if (int rc = upload(&p->d_fb_weight, p->fb_weight)) return rc;
+    if (int rc = upload(p->d_window, p->window)) return rc;
+    if (int rc = upload(p->d_twiddle, p->twiddle)) return rc;
+    if (int rc = upload(p->d_fb_start, p->fb_start)) return rc;
+    if (int rc = upload(p->d_fb_count, p->fb_count)) return rc;
+    if (int rc = upload(p->d_fb_offset, p->fb_offset)) return rc;
+    if (int rc = upload(p->d_fb_weight, p->fb_weight)) return rc;
     if (!p->fbg_gid.empty()) {
-        if (int rc = upload(&p->d_fbg_gid, p->fbg_gid)) return rc;
-        if (int rc = upload(&p->d_fbg_desc, p->fbg_desc)) return rc;
-        if (int rc = upload(&p->d_fbg_weight, p->fbg_weight)) return rc;
+        if (int rc = upload(p->d_fbg_gid, p->fbg_gid)) return rc;
+        if (int rc = upload(p->d_fbg_desc, p->fbg_desc)) return rc;
+        if (int rc = upload(p->d_fbg_weight, p->fbg_weight)) return rc;
     }
     p->uploaded = true;
     return KM_OK;
-}
-
-void free_mel_plan(MelPlan* p) {
-    if (p->uploaded) {
-        (void)hipFree(p->d_window); (void)hipFree(p->d_twiddle); (void)hipFree(p->d_fb_start);
-        (void)hipFree(p->d_fb_count); (void)hipFree(p->d_fb_offset); (void)hipFree(p->d_fb_weight);
-        (void)hipFree(p->d_fbg_gid); (void)hipFree(p->d_fbg_desc); (void)hipFree(p->d_fbg_weight);
-    }
-    delete p;
 }
 
 static size_t melrp_lds_bytes(int nnz4) {
@@ -1227,22 +1210,12 @@ int growth_refused(void* stream, const char* what, int64_t need, int64_t cap) {
     return KM_OK;
 }
 
-int grow_buffer(void* ptr_addr, int64_t* cap, int64_t need, size_t unit_bytes, void* stream, const char* what) {
-    void** ptr = static_cast<void**>(ptr_addr);
-    if (need <= *cap) return KM_OK;
-    if (int rc = growth_refused(stream, what, need, *cap)) return rc;
-    if (*ptr) { HIP_TRY(hipStreamSynchronize((hipStream_t)stream)); HIP_TRY(hipFree(*ptr)); *ptr = nullptr; *cap = 0; }
-    HIP_TRY(hipMalloc(ptr, (size_t)need * unit_bytes));
-    *cap = need;
-    return KM_OK;
-}
-
 // One chunk-request counter per window of a launch (MelArgs::chunk_ctr).  The kernel leaves them at zero, so the buffer is
 // zeroed once, when it is (re)allocated; km_finalize and km_reserve size it, a larger launch grows it (not inside a stream capture).
 int ensure_chunk_counters(Context* c, int64_t windows, void* stream) {
-    if (windows <= c->ws_chunkctr_cap) return KM_OK;
+    if (windows <= c->ws_chunkctr.n) return KM_OK;
     const int64_t cap_n = windows < 4096 ? 4096 : windows;
-    if (int rc = grow_buffer(&c->ws_chunkctr, &c->ws_chunkctr_cap, cap_n, sizeof(unsigned), stream, "front end: windows of one launch")) return rc;
+    if (int rc = c->ws_chunkctr.grow(cap_n, stream, "front end: windows of one launch")) return rc;
     HIP_TRY(hipMemsetAsync(c->ws_chunkctr, 0, (size_t)cap_n * sizeof(unsigned), (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));            // the caller's later launches may be on another stream
     return KM_OK;
@@ -1283,7 +1256,7 @@ bool mel_packs(Context* c, MelPlan* p, int64_t n_frames, int64_t T) {
 static void mel_plan_args(MelPlan* p, MelArgs& a) {
     const km_mel_config& m = p->cfg;
     a.hop = m.hop_length; a.pad_mode = m.pad_mode;
-    a.n_mels = m.n_mels; a.window = p->d_window; a.twiddle = reinterpret_cast<const float2*>(p->d_twiddle);
+    a.n_mels = m.n_mels; a.window = p->d_window; a.twiddle = reinterpret_cast<const float2*>(p->d_twiddle.p);
     a.fb_start = p->d_fb_start; a.fb_count = p->d_fb_count; a.fb_offset = p->d_fb_offset; a.fb_weight = p->d_fb_weight;
     a.fb_nnz = (int)p->fb_weight.size();
     a.fbg_gid = p->d_fbg_gid; a.fbg_desc = p->d_fbg_desc; a.fbg_weight = p->d_fbg_weight; a.fbg_nw = (int)p->fbg_weight.size();
@@ -1297,11 +1270,11 @@ int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, co
     const int64_t n_frames = seq ? seq->n_rows : 1 + L / m.hop_length;
     if (m.pad_mode == KM_PAD_REFLECT && L <= m.n_fft / 2)
         return fail(KM_ERR_INVALID_ARG, "reflect padding needs more than n_fft/2 = %d samples (got %lld)", m.n_fft / 2, (long long)L);
-    if (!seq && (B > c->ws_windows || n_frames > c->ws_frames))
+    if (!seq && (B > c->ws.windows || n_frames > c->ws.frames))
         return fail(KM_ERR_WORKSPACE, "workspace holds %lld windows x %lld frames, need %lld x %lld: call km_reserve",
-                    (long long)c->ws_windows, (long long)c->ws_frames, (long long)B, (long long)n_frames);
-    if (!seq && m.n_mels > c->ws_mels)
-        return fail(KM_ERR_WORKSPACE, "workspace rows hold %d mel bins, this plan has %d: call km_reserve", c->ws_mels, m.n_mels);
+                    (long long)c->ws.windows, (long long)c->ws.frames, (long long)B, (long long)n_frames);
+    if (!seq && m.n_mels > c->ws.mels)
+        return fail(KM_ERR_WORKSPACE, "workspace rows hold %d mel bins, this plan has %d: call km_reserve", c->ws.mels, m.n_mels);
     // what the launch carries has to fit its source and its kernel (MelCarry in km_context.h): checked here and nowhere else
     const bool ring = src.ring_start != nullptr, plain = !ring && src.wins_per_clip <= 1;
     if ((carry.emotion != nullptr) + (seq != nullptr) + (carry.pack != nullptr) > 1 || (seq && !(mel_rp_ok(c, p) && !ring)) ||
@@ -1320,12 +1293,12 @@ int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, co
     }
     hipStream_t st = (hipStream_t)stream;
     if (int rc = ensure_chunk_counters(c, B, stream)) return rc;
-    // ws_melmax is all-zero on entry: the fused core, the generic encoder and phase 1 of the training program re-zero the
+    // ws.melmax is all-zero on entry: the fused core, the generic encoder and phase 1 of the training program re-zero the
     // entries they consume, and the stand-alone log kernels below are followed by a memset of theirs -- so a step recorded
     // into a hipGraph needs no memset node and stays correct whatever ran between two replays.  The flag only covers a
     // freshly (re)allocated workspace.
     if (!seq && c->melmax_dirty) {
-        HIP_TRY(hipMemsetAsync(c->ws_melmax, 0, (size_t)c->ws_windows * sizeof(unsigned), st));
+        HIP_TRY(hipMemsetAsync(c->ws.melmax, 0, (size_t)c->ws.windows * sizeof(unsigned), st));
         c->melmax_dirty = false;
     }
     MelArgs a;
@@ -1333,7 +1306,7 @@ int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, co
     a.audio = src.audio; a.L = L; a.clip_len = src.clip_len; a.win_step = src.win_step; a.win0 = src.win0;
     a.wins_per_clip = src.wins_per_clip > 0 ? src.wins_per_clip : 1; a.n_frames = (int)n_frames;
     a.ring_start = src.ring_start; a.ready = src.ready;
-    a.melpow = c->ws_melpow; a.melmax = c->ws_melmax;
+    a.melpow = c->ws.melpow; a.melmax = c->ws.melmax;
     a.frame_mul = 1; a.frame_max = nullptr; a.chunk_ctr = c->ws_chunkctr;
     a.pack_xt = nullptr; a.pack_T = a.pack_KP = 0; a.pack_amin = m.amin;
     a.tab_start = nullptr; a.tab_edge = nullptr; a.tab_min = a.tab_T = a.tab_span_wgs = 0;
@@ -1509,7 +1482,7 @@ int launch_train_clip_pack(Context* c, MelPlan* p, const float* span, const floa
         return fail(KM_ERR_INVALID_ARG, "clip pack: the edge image has to follow the span image in one allocation");
     a.span = span; a.edge_off = (int)(edge - span); a.start = start_frames; a.min_start = min_start; a.n_span = (int)n_span; a.T = T; a.KP = KP;
     a.n_mels = m.n_mels; a.row_stride = clippack::row_stride(m.n_mels); a.tile_cols = clippack::tile_cols(m.n_mels, KP);
-    a.amin = m.amin; a.xt = xt; a.melmax = c->ws_melmax;
+    a.amin = m.amin; a.xt = xt; a.melmax = c->ws.melmax;
     const size_t lds = (size_t)a.tile_cols * a.row_stride * sizeof(float);
     static PerDeviceOnce once;
     if (once.first(c->device))
@@ -1525,12 +1498,12 @@ int launch_mel_packed(Context* c, MelPlan* p, const MelSrc& src, float* xp, int 
     if (int rc = launch_mel_power(c, p, src, stream)) return rc;
     const km_mel_config& m = p->cfg;
     LogArgs g;
-    g.melpow = c->ws_melpow; g.melmax = c->ws_melmax; g.n_frames = (int)(1 + src.L / m.hop_length);
+    g.melpow = c->ws.melpow; g.melmax = c->ws.melmax; g.n_frames = (int)(1 + src.L / m.hop_length);
     g.out_frames = g.n_frames; g.n_mels = m.n_mels; g.lp = log_params(m); g.mel_long = nullptr; g.mel_short = nullptr;
     const dim3 grid((unsigned)((KP * m.n_mels + 255) / 256), (unsigned)src.B);
     hipLaunchKernelGGL(mel_log_packed_kernel, grid, dim3(256), 0, (hipStream_t)stream, g, xp, T, KP);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(c->ws_melmax, 0, (size_t)src.B * sizeof(unsigned), (hipStream_t)stream));   // leave the maxima as found
+    HIP_TRY(hipMemsetAsync(c->ws.melmax, 0, (size_t)src.B * sizeof(unsigned), (hipStream_t)stream));   // leave the maxima as found
     return KM_OK;
 }
 
@@ -1539,7 +1512,7 @@ int launch_mel(Context* c, MelPlan* p, const MelSrc& src, int64_t out_frames, fl
     const km_mel_config& m = p->cfg;
     const int64_t B = src.B, n_frames = 1 + src.L / m.hop_length;
     LogArgs g;
-    g.melpow = c->ws_melpow; g.melmax = c->ws_melmax; g.n_frames = (int)n_frames;
+    g.melpow = c->ws.melpow; g.melmax = c->ws.melmax; g.n_frames = (int)n_frames;
     g.out_frames = (int)(out_frames > 0 ? out_frames : n_frames); g.n_mels = m.n_mels; g.lp = log_params(m);
     g.mel_long = mel_long; g.mel_short = mel_short;
     const dim3 grid2((unsigned)((g.out_frames * m.n_mels + 255) / 256), (unsigned)B);
@@ -1547,7 +1520,7 @@ int launch_mel(Context* c, MelPlan* p, const MelSrc& src, int64_t out_frames, fl
         hipLaunchKernelGGL(mel_log_kernel, grid2, dim3(256), 0, (hipStream_t)stream, g);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipMemsetAsync(c->ws_melmax, 0, (size_t)B * sizeof(unsigned), (hipStream_t)stream));       // leave the maxima as found
+    HIP_TRY(hipMemsetAsync(c->ws.melmax, 0, (size_t)B * sizeof(unsigned), (hipStream_t)stream));       // leave the maxima as found
     return KM_OK;
 }
 
@@ -1579,9 +1552,9 @@ __global__ void ring_push_kernel(float* __restrict__ ring, int* __restrict__ wpt
 }
 
 int launch_ring_push(Context* c, const float* samples, int64_t n_per_stream, void* stream) {
-    hipLaunchKernelGGL(ring_push_kernel, dim3((unsigned)c->n_streams), dim3(256), 0, (hipStream_t)stream, c->ring,
-                       c->ring_wptr, c->ring_frames, c->ring_ready, samples, (int)n_per_stream, c->ring_hop,
-                       (int)c->ring_len);
+    hipLaunchKernelGGL(ring_push_kernel, dim3((unsigned)c->st.n_streams), dim3(256), 0, (hipStream_t)stream, c->st.ring,
+                       c->st.ring_wptr, c->st.ring_frames, c->st.ring_ready, samples, (int)n_per_stream, c->st.ring_hop,
+                       (int)c->st.ring_len);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

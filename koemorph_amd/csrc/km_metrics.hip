@@ -39,18 +39,12 @@
 
 #include <cstdlib>
 
+#include <memory>
+
 #include "km_context.h"
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 namespace met {
 constexpr int NC = 52, NQ = 13;                       // columns; float4 slots per row
@@ -80,8 +74,8 @@ struct MetricsState {
 };
 
 struct MetricsAcc {
-    MetricsState* state = nullptr;     // device
-    Slot* work = nullptr;              // device, wgs partial records
+    DevBuf<MetricsState> state;
+    DevBuf<Slot> work;                 // wgs partial records
     int wgs = met::DEFAULT_WGS;
 };
 
@@ -407,32 +401,22 @@ extern "C" {
 
 int km_metrics_create(void** acc_out) {
     if (!acc_out) return fail(KM_ERR_INVALID_ARG, "km_metrics_create: NULL argument");
-    MetricsAcc* a = new MetricsAcc();
+    auto a = std::make_unique<MetricsAcc>();
     if (const char* env = std::getenv("KM_METRICS_WGS")) {     // read once, here; no launch path reads the environment
         const long v = std::strtol(env, nullptr, 10);
         if (v >= 1 && v <= met::MAX_WGS) a->wgs = (int)v;
     }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&a->state), sizeof(MetricsState));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&a->work), (size_t)a->wgs * met::REC * sizeof(Slot));
-    if (e == hipSuccess) e = hipMemset(a->state, 0, sizeof(MetricsState));
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // the cleared state is visible to whichever stream updates first
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (a->state) (void)hipFree(a->state);
-        if (a->work) (void)hipFree(a->work);
-        delete a;
-        return fail(KM_ERR_HIP, "km_metrics_create: %s", hipGetErrorString(e));
-    }
-    *acc_out = a;
+    if (int rc = a->state.alloc(1, "km_metrics_create")) return rc;
+    if (int rc = a->work.alloc((int64_t)a->wgs * met::REC, "km_metrics_create")) return rc;
+    HIP_TRY(hipMemset(a->state, 0, sizeof(MetricsState)));
+    HIP_TRY(hipStreamSynchronize(nullptr));   // the cleared state is visible to whichever stream updates first
+    *acc_out = a.release();
     return KM_OK;
 }
 
 int km_metrics_destroy(void* acc) {
     if (!acc) return KM_OK;
-    MetricsAcc* a = static_cast<MetricsAcc*>(acc);
-    if (a->state) (void)hipFree(a->state);
-    if (a->work) (void)hipFree(a->work);
-    delete a;
+    delete static_cast<MetricsAcc*>(acc);
     return KM_OK;
 }
 

@@ -29,18 +29,12 @@
 #include <new>
 #include <vector>
 
+#include <memory>
+
 #include "km_context.h"
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            (void)hipGetLastError();                                                          \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                  \
-        }                                                                                     \
-    } while (0)
 
 namespace rs {
 constexpr int THREADS = 256, TILE = 1024;
@@ -57,7 +51,7 @@ struct Resampler {
     int64_t n = 0;
     RsGeom g{};
     size_t lds_bytes = 0;
-    char* blob = nullptr;
+    DevBuf<char> blob;          // one allocation: the three views below
     float* table = nullptr;     // (up, stride), padded to tab_floats
     float* tail = nullptr;      // (n, T)
     int32_t* d = nullptr;       // (n)
@@ -224,7 +218,7 @@ int km_resampler_create(void** rs_out, int64_t n_streams, int32_t up, int32_t do
     if (lds_bytes > rs::LDS_BUDGET || n_taps > (1 << 24))
         return fail(KM_ERR_UNSUPPORTED, "km_resampler_create: %d/%d with %lld taps needs %lld bytes of LDS (table %lld, input span %lld), at most %lld",
                     up, down, (long long)n_taps, (long long)lds_bytes, (long long)(tab_floats * 4), (long long)(span_cap * 4), (long long)rs::LDS_BUDGET);
-    Resampler* r = new (std::nothrow) Resampler();
+    std::unique_ptr<Resampler> r(new (std::nothrow) Resampler());
     if (!r) return fail(KM_ERR_HIP, "km_resampler_create: out of host memory");
     r->n = n_streams;
     r->g = RsGeom{up, down, (int)half, (int)K, (int)stride, (int)T, (int)tab_floats, (int)span_cap};
@@ -234,33 +228,21 @@ int km_resampler_create(void** rs_out, int64_t n_streams, int32_t up, int32_t do
         for (int64_t k = 0; k < K && p + k * up <= 2 * half; ++k) tab[(size_t)(p * stride + k)] = (float)taps_host[p + k * up];
     const int64_t tab_bytes = rs_align16(tab_floats * 4), tail_bytes = rs_align16(n_streams * T * 4 + 16), d_bytes = rs_align16(n_streams * 4);
     const int64_t bytes = tab_bytes + tail_bytes + d_bytes;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&r->blob), (size_t)bytes);
-    if (err == hipSuccess) err = hipMemset(r->blob, 0, (size_t)bytes);
-    if (err == hipSuccess) {
-        r->table = reinterpret_cast<float*>(r->blob);
-        r->tail = reinterpret_cast<float*>(r->blob + tab_bytes);
-        r->d = reinterpret_cast<int32_t*>(r->blob + tab_bytes + tail_bytes);
-        err = hipMemcpy(r->table, tab.data(), (size_t)tab_floats * 4, hipMemcpyHostToDevice);
-    }
-    if (err == hipSuccess) {
-        std::vector<int32_t> d0((size_t)n_streams, (int32_t)half);
-        err = hipMemcpy(r->d, d0.data(), (size_t)n_streams * 4, hipMemcpyHostToDevice);
-    }
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        if (r->blob) (void)hipFree(r->blob);
-        delete r;
-        return fail(KM_ERR_HIP, "km_resampler_create: %lld bytes of device memory: %s", (long long)bytes, hipGetErrorString(err));
-    }
-    *rs_out = r;
+    if (int rc = r->blob.alloc(bytes, "km_resampler_create")) return rc;
+    HIP_TRY(hipMemset(r->blob, 0, (size_t)bytes));
+    r->table = reinterpret_cast<float*>(r->blob.p);
+    r->tail = reinterpret_cast<float*>(r->blob + tab_bytes);
+    r->d = reinterpret_cast<int32_t*>(r->blob + tab_bytes + tail_bytes);
+    HIP_TRY(hipMemcpy(r->table, tab.data(), (size_t)tab_floats * 4, hipMemcpyHostToDevice));
+    const std::vector<int32_t> d0((size_t)n_streams, (int32_t)half);
+    HIP_TRY(hipMemcpy(r->d, d0.data(), (size_t)n_streams * 4, hipMemcpyHostToDevice));
+    *rs_out = r.release();
     return KM_OK;
 }
 
 int km_resampler_destroy(void* rs) {
     if (!rs) return KM_OK;
-    Resampler* r = static_cast<Resampler*>(rs);
-    if (r->blob) (void)hipFree(r->blob);
-    delete r;
+    delete static_cast<Resampler*>(rs);
     return KM_OK;
 }
 

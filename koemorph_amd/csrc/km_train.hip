@@ -13,14 +13,6 @@
 
 namespace km {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 // sum of squares of the flat gradient, deterministic two-stage reduction
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part,
@@ -157,28 +149,28 @@ __global__ __launch_bounds__(256) void pad_rows_kernel(const float* __restrict__
 int train_adamw(Context* c, const float* flat_grad, float lr, float b1, float b2, float eps, float wd, float max_norm,
                 int64_t step, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    const int64_t n = c->tr_nparams;
+    const int64_t n = c->tr.nparams;
     const int nb = 256;
     // two launches: partial sums of squares (+ the step counters), then norm + clip + AdamW in one kernel
-    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, st, flat_grad, n, c->tr_part, c->tr_steps, c->tr_alpha_live ? 1 : 0);
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, st, flat_grad, n, c->tr.part, c->tr.steps, c->tr_alpha_live ? 1 : 0);
     (void)step;
     // the legacy model (km_legacy_train_*) has neither a smoothing_alpha nor a padded channel-encoder copy
-    const auto alpha_it = c->tr_offset.find("smoothing_alpha");
-    const int64_t alpha_idx = alpha_it == c->tr_offset.end() ? -1 : alpha_it->second;
-    const PaddedCopy pc = c->trp_wcep ? PaddedCopy{c->trp_wcep, c->tr_offset.at("mel_channel_encoder.weight"), (int64_t)c->d * c->KT, (int)c->KT, (int)trainp_kp(c)}
+    const auto alpha_it = c->tr.offset.find("smoothing_alpha");
+    const int64_t alpha_idx = alpha_it == c->tr.offset.end() ? -1 : alpha_it->second;
+    const PaddedCopy pc = c->tr.wcep ? PaddedCopy{c->tr.wcep, c->tr.offset.at("mel_channel_encoder.weight"), (int64_t)c->d * c->KT, (int)c->KT, (int)trainp_kp(c)}
                                       : PaddedCopy{nullptr, 0, 0, 1, 1};
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, st, c->tr_params, c->tr_m, c->tr_v, flat_grad, n,
-                       c->tr_part, c->tr_gnorm, max_norm, lr, b1, b2, eps, wd, c->tr_steps, alpha_idx, c->tr_alpha_live ? 1 : 0, pc);
+    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, st, c->tr.params, c->tr.m, c->tr.v, flat_grad, n,
+                       c->tr.part, c->tr.gnorm, max_norm, lr, b1, b2, eps, wd, c->tr.steps, alpha_idx, c->tr_alpha_live ? 1 : 0, pc);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
 
 // after the master parameters were written from outside (km_train_init, km_train_set_params): the padded copy from scratch
 int train_refresh_padded_weights(Context* c, void* stream) {
-    if (!c->trp_wcep) return KM_OK;
+    if (!c->tr.wcep) return KM_OK;
     const int64_t KP = trainp_kp(c);
     hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((c->d * KP + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       c->tr_params + c->tr_offset.at("mel_channel_encoder.weight"), c->trp_wcep, (int64_t)c->d, (int)c->KT, (int)KP);
+                       c->tr.params + c->tr.offset.at("mel_channel_encoder.weight"), c->tr.wcep, (int64_t)c->d, (int)c->KT, (int)KP);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

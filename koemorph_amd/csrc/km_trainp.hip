@@ -38,14 +38,6 @@ namespace km {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define KM_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                                                                        \
-            (void)hipGetLastError(); /* the runtime keeps a failed call as its last error: do not leave it to the next launch check */ \
-            return fail(KM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));                                                           \
-        }                                                                                                                              \
-    } while (0)
 
 #include "km_gemm_dev.h"
 #include "km_gemm_dma_dev.h"
@@ -545,7 +537,7 @@ __global__ __launch_bounds__(256) void trainp_tail_window_kernel(TailArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     train_tail_window_dev(a, smem);
 }
-constexpr int kTailMaxGroups = 1024;      // rows of Context::trp_tail_part
+constexpr int kTailMaxGroups = 1024;      // rows of Context::tr.tail_part
 
 // ---- host: building and launching the program ----------------------------------------------------------------
 // Split-K: a gradient product over all rows of the batch (K = 80 B, 28 B or 24 B) with an output of a few tiles is a few
@@ -812,11 +804,11 @@ int64_t trainp_act_floats(Context* c, int64_t* fixed) {
 
 struct MaskSet { unsigned char *mel, *emo, *dec; };
 static MaskSet mask_ptrs(Context* c, int64_t B) {
-    unsigned char* base = reinterpret_cast<unsigned char*>(c->trp_masks);
+    unsigned char* base = c->tr.masks;
     MaskSet m;
     m.mel = base;
-    m.emo = m.mel + (size_t)c->tr_windows * c->H * 28 * c->NK;
-    m.dec = m.emo + (((size_t)c->tr_windows * c->H * 24 + 15) / 16) * 16;
+    m.emo = m.mel + (size_t)c->tr.windows * c->H * 28 * c->NK;
+    m.dec = m.emo + (((size_t)c->tr.windows * c->H * 24 + 15) / 16) * 16;
     (void)B;
     return m;
 }
@@ -844,8 +836,8 @@ int trainp_copy_masks(Context* c, int64_t B, unsigned char* mel, unsigned char* 
     return KM_OK;
 }
 
-int64_t trainp_mask_alloc_bytes(Context* c) {
-    return (int64_t)c->tr_windows * (c->H * 28 * c->NK + c->H * 24 + 52 * c->DH) + 64;
+int64_t trainp_mask_alloc_bytes(Context* c, int64_t windows) {
+    return windows * (c->H * 28 * c->NK + c->H * 24 + 52 * c->DH) + 64;
 }
 
 #define RUN(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
@@ -861,18 +853,18 @@ int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in
     if (NKk % 4 != 0 || NKk > 16 * kAttnMaxKT)
         return fail(KM_ERR_UNSUPPORTED, "phased training step needs num_mel_channels <= %d, a multiple of 4 (got %lld)", 16 * kAttnMaxKT, (long long)NKk);
     c->tr_alpha_live = sa.ema_state != nullptr && !sa.ema_first;
-    auto P = [&](const char* k) -> const float* { return c->tr_params + c->tr_offset.at(k); };
-    auto Gd = [&](const char* k) -> float* { return sa.flat_grad + c->tr_offset.at(k); };
-    float* w = c->trp_act;
+    auto P = [&](const char* k) -> const float* { return c->tr.params + c->tr.offset.at(k); };
+    auto Gd = [&](const char* k) -> float* { return sa.flat_grad + c->tr.offset.at(k); };
+    float* w = c->tr.act;
     auto take = [&](int64_t n) { float* p = w; w += (n + 3) / 4 * 4; return p; };
-    float* xp = take(c->tr_windows * KP * NKk);            // first: km_train_step_audio writes the packed input here
-    float* x2 = take(c->tr_windows * KP * NKk);            // ... as 10 log10(power) when the front end packs (asrc->packed): the finished features
+    float* xp = take(c->tr.windows * KP * NKk);            // first: km_train_step_audio writes the packed input here
+    float* x2 = take(c->tr.windows * KP * NKk);            // ... as 10 log10(power) when the front end packs (asrc->packed): the finished features
     // fixed part
     float* Qb = take(28 * d); float* dQb = take(28 * d);
     float* T1m = take(d * d); float* T1e = take(d * d); float* Wfm = take(DH * d); float* Wfe = take(DH * d);
     float* t1m = take(d); float* t1e = take(d); float* bfm = take(DH); float* bfe = take(DH);
-    float* ones = take(c->tr_windows * NKk);
-    float* WceP = c->trp_wcep;                             // channel encoder weight with rows padded to KP (zeros), kept beside the parameters (PaddedCopy, km_train.hip)
+    float* ones = take(c->tr.windows * NKk);
+    float* WceP = c->tr.wcep;                             // channel encoder weight with rows padded to KP (zeros), kept beside the parameters (PaddedCopy, km_train.hip)
     // per-window part
     float* Y0 = take(R * d); float* Y = take(R * d); float* mu = take(R); float* rs = take(R);
     float* KV = take(R * 2 * d);
@@ -889,7 +881,7 @@ int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in
     float* bs = take(B * 52); float* outb = take(B * 52); float* dz = take(B * 52); float* tfac = take(B * 52); float* txp = take(B * 52);
     float* dQ_part = take(B * 28 * d);
     float* statsY = take(2 * R * (d / 32 + 1)); float* statsE = take(2 * B * (d / 32 + 1));      // LayerNorm parts of Y0 / E0 rows (float2 [row][d / 32])
-    if ((w - c->trp_act) > c->trp_act_floats) return fail(KM_ERR_WORKSPACE, "phased training workspace too small (internal)");
+    if ((w - c->tr.act) > c->tr.act.n) return fail(KM_ERR_WORKSPACE, "phased training workspace too small (internal)");
 
     const float p_drop = c->tr_dropout_p;
     const bool drop = p_drop > 0.f;
@@ -922,9 +914,9 @@ int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in
         return fail(KM_ERR_UNSUPPORTED, "the fused training attention blocks are built for heads of 16, 32 or 64 columns (got %lld)", (long long)hd);
 
     Program pg;
-    pg.scratch = c->trp_split; pg.scratch_left = c->trp_split_floats;
+    pg.scratch = c->tr.split; pg.scratch_left = c->tr.split.n;
     pg.allow_split = !c->opt.train_no_split;
-    pg.leaf_lo = sa.flat_grad; pg.leaf_hi = sa.flat_grad + c->tr_nparams;
+    pg.leaf_lo = sa.flat_grad; pg.leaf_hi = sa.flat_grad + c->tr.nparams;
     if (c->opt.train_bm32_below > 0) pg.bm32_below = c->opt.train_bm32_below;
     pg.op_per_launch = c->opt.train_op_per_launch != 0; pg.dbg_stream = st;
     pg.use_dma = !c->opt.train_no_dma;
@@ -999,8 +991,8 @@ int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in
     // channel encoder waits for; the emotion chain and the folds run one phase later than before, still ahead of their readers)
     if (asrc && !asrc->packed) {       // the window maxima were read in P0: clean slots for the next front-end launch (no memset)
         ElemArgs z{};
-        z.q0 = reinterpret_cast<float*>(c->ws_melmax); z.n0 = c->ws_windows;
-        pg.elem(OP_ZERO, z, (c->ws_windows + 4095) / 4096);
+        z.q0 = reinterpret_cast<float*>(c->ws.melmax.p); z.n0 = c->ws.windows;
+        pg.elem(OP_ZERO, z, (c->ws.windows + 4095) / 4096);
         c->melmax_dirty = false;
     }
     {   // Y0[b] (NK x d) = XT_b (NK x KP) WceP^T + b: both operands k-contiguous with K = KP a multiple of 32 (zeros beyond KT on
@@ -1054,8 +1046,8 @@ int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in
     auto zero_maxima = [&]() {          // the window maxima were read by DbXform and OP_DBCONV: clean slots for the next front-end launch
         if (!xf) return;
         ElemArgs z{};
-        z.q0 = reinterpret_cast<float*>(c->ws_melmax); z.n0 = c->ws_windows;
-        pg.elem(OP_ZERO, z, (c->ws_windows + 4095) / 4096);
+        z.q0 = reinterpret_cast<float*>(c->ws.melmax.p); z.n0 = c->ws.windows;
+        pg.elem(OP_ZERO, z, (c->ws.windows + 4095) / 4096);
         c->melmax_dirty = false;
     };
     if (!fuse_ln) zero_maxima();          // (with fuse_ln OP_DBCONV reads them in THIS phase: they are cleaned in P4)
@@ -1087,7 +1079,7 @@ int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in
         for (int r = 0; r < 3; ++r) {
             ElemArgs e{};
             e.mask_out = regions[r]; e.n0 = sizes[r]; e.i0 = r; e.i1 = (int)thr; e.u0 = (unsigned)c->tr_dropout_seed;
-            e.u1 = (unsigned)(c->tr_dropout_seed >> 32); e.p0 = reinterpret_cast<const float*>(c->trp_drop_ctr);
+            e.u1 = (unsigned)(c->tr_dropout_seed >> 32); e.p0 = reinterpret_cast<const float*>(c->tr.drop_ctr.p);
             pg.elem(OP_MASKGEN, e, (sizes[r] + 1023) / 1024);
         }
     }
@@ -1113,8 +1105,8 @@ int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in
     // clean gradient bucket and the ones vector (first touched in P8): they ride under the attention blocks
     {
         ElemArgs e{};
-        e.q0 = sa.flat_grad; e.n0 = c->tr_nparams;
-        pg.elem(OP_ZERO, e, (c->tr_nparams + 4095) / 4096);
+        e.q0 = sa.flat_grad; e.n0 = c->tr.nparams;
+        pg.elem(OP_ZERO, e, (c->tr.nparams + 4095) / 4096);
         ElemArgs f{};
         f.q0 = ones; f.n0 = R; f.f0 = 1.0f;
         pg.elem(OP_FILL, f, blocks256(R));
@@ -1135,8 +1127,8 @@ int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in
         t.mse_w = sa.mse_w; t.l1_w = sa.l1_w; t.lc = c->tr_loss_cfg; t.fac = tfac; t.xp = txp; t.loss = sa.loss_dev;
         t.d_melw = Gd("mel_weights"); t.d_emow = Gd("emotion_weights"); t.d_alpha = Gd("smoothing_alpha");
         t.B = (int)B; t.DH = (int)DH; t.expr_rows = 24; t.audio_energy = c->tr_loss_cfg.audio_energy_dev; t.out2 = sa.out_dev;
-        t.d_b2 = Gd("blendshape_decoder.3.bias"); t.drop_ctr = (drop && c->tr_dropout_mode == 0) ? c->trp_drop_ctr : nullptr;
-        t.part = c->trp_tail_part; t.ctr = c->trp_tail_ctr;
+        t.d_b2 = Gd("blendshape_decoder.3.bias"); t.drop_ctr = (drop && c->tr_dropout_mode == 0) ? c->tr.drop_ctr : nullptr;
+        t.part = c->tr.tail_part; t.ctr = c->tr.tail_ctr;
         t.dh1 = dH1; t.dhe = dHe; t.keep_scale = keep_scale;
         // one workgroup per window, at most 32 (round 4, with the hidden layer's gradient in the tail: 8 workgroups 0.1628 ms per
         // 8-window step, 4: 0.1653, 2: 0.1717); the audio-visual term couples the whole batch: one
@@ -1245,8 +1237,8 @@ int train_forward_backward(Context* c, const float* mel, int64_t B, int64_t T_in
     RUN(pg.end_phase(st));
     if (!pg.pend_prev.empty()) return fail(KM_ERR_UNSUPPORTED, "training program: a reduction is still pending behind phase 11 (internal)");
     // everything but the "late" group of the bucket (km_train_init) is final: a side stream may start its all-reduce
-    HIP_TRY(hipEventRecord((hipEvent_t)c->tr_early_ev, st));
-    c->tr_early_recorded = true;
+    HIP_TRY(hipEventRecord((hipEvent_t)c->tr.early_ev, st));
+    c->tr.early_recorded = true;
     // ================= P12: channel encoder gradients; LayerNorm parameters; emotion encoder =================
     // dWce (d x KT) = dY0^T XT over ALL rows (window, channel) of the batch: with the transposed input it is ONE product with a
     // uniform k stride (round 3: a contraction batch over the windows on the register tile, 19 us at 8 windows); split along K
