@@ -699,6 +699,11 @@ int km_egemaps_functionals_from_records(const float* rec_dev, int64_t B, int64_t
 /* out (B, N) = x (B, K) w^T + b with w stored (N, K) like nn.Linear: the 264 -> 256 compression of the three concatenated
  * eGeMAPS windows (OpenSMILEeGeMAPSExtractor.get_concatenated_features, opensmile_extractor.py:575-590).  b may be NULL. */
 int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev, void* stream);
+/* The GEMM kernel km_linear(B = M, K, N) runs on, for 16-byte aligned x and w (`batch` such products in one launch, as the
+ * model's batched products are): 0 gemm_kernel (64 x 64 tile, any strides), gemm_nt_kernel 1 <2,2,true> (64 x 64),
+ * 2 <4,2,true> (128 x 64), 3 <4,4,true> (128 x 128, K <= 256), 4 <4,4,false> (128 x 128, K > 256).  -1 for a bad argument.
+ * Host only, no device needed: the tests name the kernel a product ran on with it. */
+int km_gemm_kernel_choice(int64_t M, int64_t N, int64_t K, int64_t batch);
 
 /* ---- emotion vectors of many streams, from the pushed audio, resident on the device ------------------------------
  * An object of its own (not tied to a km_handle), on the current device.  Replaces, for n_streams speakers at once, one

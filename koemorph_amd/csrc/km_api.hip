@@ -160,13 +160,22 @@ int km_core_forward_z(km_handle h, const float* mel_dev, int64_t B, int64_t T_in
     return launch_core_fused(c, mel_dev, B, T_in, mel_short_dev, z_dev, out_dev, raw_dev, attn_mel_dev, nullptr, 1, stream);
 }
 
-int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev, void* stream) {
-    if (!x_dev || !w_dev || !out_dev || B <= 0 || K <= 0 || N <= 0) return fail(KM_ERR_INVALID_ARG, "km_linear: bad argument");
+static GemmArgs linear_args(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev) {
     GemmArgs g{};
     g.alpha = 1.f; g.batch2 = 1; g.kb_count = 1;
     g.A = x_dev; g.a_rs = K; g.a_cs = 1; g.B = w_dev; g.b_rs = 1; g.b_cs = K; g.C = out_dev; g.c_rs = N;
     g.M = (int)B; g.N = (int)N; g.K = (int)K; g.bias = b_dev; g.bias_mode = b_dev ? 1 : 0;
-    return launch_gemm(g, 1, stream);
+    return g;
+}
+
+int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev, void* stream) {
+    if (!x_dev || !w_dev || !out_dev || B <= 0 || K <= 0 || N <= 0) return fail(KM_ERR_INVALID_ARG, "km_linear: bad argument");
+    return launch_gemm(linear_args(x_dev, w_dev, b_dev, B, K, N, out_dev), 1, stream);
+}
+
+int km_gemm_kernel_choice(int64_t M, int64_t N, int64_t K, int64_t batch) {
+    if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || batch > INT32_MAX) return -1;
+    return gemm_kernel_choice(linear_args(nullptr, nullptr, nullptr, M, K, N, nullptr), (int)batch);
 }
 
 int km_audio_energy(const float* features_dev, int64_t B, int64_t T, int64_t D, float* energy_dev, void* stream) {

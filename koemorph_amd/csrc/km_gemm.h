@@ -75,6 +75,7 @@ inline int64_t gemm_drop_row(int map, int64_t m) {
 }
 
 int launch_gemm(const GemmArgs& g, int batch, void* stream);
+int gemm_kernel_choice(const GemmArgs& g, int batch);   // the kernel launch_gemm picks, 0 .. 4 (km_generic.hip)
 int launch_softmax_rows(float* x, int64_t rows, int w, void* stream);
 
 }  // namespace km

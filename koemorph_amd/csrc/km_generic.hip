@@ -267,7 +267,9 @@ static bool gemm_nt_ok(const GemmArgs& g) {
            g.a_rs % 4 == 0 && g.b_cs % 4 == 0 && g.a_bs1 % 4 == 0 && g.a_bs2 % 4 == 0 && g.b_bs1 % 4 == 0 && g.b_bs2 % 4 == 0;
 }
 
-int launch_gemm(const GemmArgs& g, int batch, void* stream) {
+// Which kernel launch_gemm runs a product on: 0 gemm_kernel, 1 gemm_nt_kernel<2,2,true>, 2 <4,2,true>, 3 <4,4,true>, 4 <4,4,false>
+// (exported for km_linear's operands as km_gemm_kernel_choice, so that a test can name the kernel it ran).
+int gemm_kernel_choice(const GemmArgs& g, int batch) {
     static const bool fast = std::getenv("KM_GEMM_GENERIC_ONLY") == nullptr;
 #ifndef KM_NT_MIN_WGS
 #define KM_NT_MIN_WGS 192
@@ -282,16 +284,23 @@ int launch_gemm(const GemmArgs& g, int batch, void* stream) {
     const bool use4 = g.N > 64 && wgs4 >= KM_NT_MIN_WGS;
     const bool use2 = !use4 && wgs2 >= KM_NT_MIN_WGS && (mid || g.N <= 64);
     const bool use22 = small && gemm_nt_ok(g) && ((!use4 && !use2 && wgs22 >= KM_NT_MIN_WGS) || ((use4 ? wgs4 : wgs2) < small_below && (use4 || use2)));
-    if (fast && use22) {
+    if (fast && use22) return 1;
+    if (fast && gemm_nt_ok(g) && (use4 || use2)) return !use4 ? 2 : g.K <= 256 ? 3 : 4;
+    return 0;
+}
+
+int launch_gemm(const GemmArgs& g, int batch, void* stream) {
+    const int choice = gemm_kernel_choice(g, batch);
+    if (choice == 1) {
         const dim3 grid((unsigned)((g.N + 63) / 64), (unsigned)((g.M + 63) / 64), (unsigned)batch);
         hipLaunchKernelGGL((gemm_nt_kernel<2, 2, true>), grid, dim3(256), 0, (hipStream_t)stream, g);
         HIP_TRY(hipGetLastError());
         return KM_OK;
     }
-    if (fast && gemm_nt_ok(g) && (use4 || use2)) {
-        if (use4) {
+    if (choice >= 2) {
+        if (choice >= 3) {
             const dim3 grid((unsigned)((g.N + 127) / 128), (unsigned)((g.M + 127) / 128), (unsigned)batch);
-            if (g.K <= 256) hipLaunchKernelGGL((gemm_nt_kernel<4, 4, true>), grid, dim3(256), 0, (hipStream_t)stream, g);
+            if (choice == 3) hipLaunchKernelGGL((gemm_nt_kernel<4, 4, true>), grid, dim3(256), 0, (hipStream_t)stream, g);
             else hipLaunchKernelGGL((gemm_nt_kernel<4, 4, false>), grid, dim3(256), 0, (hipStream_t)stream, g);
         } else {
             const dim3 grid((unsigned)((g.N + 63) / 64), (unsigned)((g.M + 127) / 128), (unsigned)batch);

@@ -1,8 +1,10 @@
-"""Parameter sets, inputs and planted faults shared by tests/test_gpu_core_logit.py (the kernels against the float64 oracle in
-logit space) and tests/test_oracle_core.py (the same measure on a stand-in kernel, without a GPU).  Not a test module."""
+"""Parameter sets, inputs, planted faults and the judging harness shared by tests/test_gpu_core_logit.py and
+tests/test_gpu_generic_shapes.py (the kernels against the float64 oracle in logit space) and tests/test_oracle_core.py (the same
+measure on a stand-in kernel, without a GPU).  Not a test module."""
 import numpy as np
 
 from koemorph_amd import synth
+from oracle import core
 
 K = 4.0          # the factor of the bound; how it was chosen: the docstring of tests/test_gpu_core_logit.py
 
@@ -38,27 +40,29 @@ PARAM_KINDS = ("init", "trained", "sharp", "bias0", "offset")
 
 
 # ---- inputs --------------------------------------------------------------------------------------------------------------------
-def make_inputs(kind, seed, B, t_in, T=256):
-    """(mel (B, t_in, 80), short (B, 3, 80), emotion (B, 256)).  Rows of `mel` from T on are NaN: the core truncates to T rows,
-    and a kernel that multiplied the surplus rows by zero instead of skipping them would turn NaN.
+def make_inputs(kind, seed, B, t_in, T=256, n_mels=80, emotion_dim=256):
+    """(mel (B, t_in, n_mels), short (B, 3, n_mels), emotion (B, emotion_dim)).  Rows of `mel` from T on are NaN: the core truncates
+    to T rows, and a kernel that multiplied the surplus rows by zero instead of skipping them would turn NaN.
     mel01 / randn  synth's styles
     const          every frame of a window is the same row (and the three short frames another one)
-    zeroch         mel01 with channels 0, 37 and 79 zero in every frame, short ones included (with `bias0`: zero variance)
+    zeroch         mel01 with channels 0, 37 n_mels / 80 and n_mels - 1 zero in every frame, short ones included (with `bias0`: zero
+                   variance); 0, 37 and 79 of 80 channels
     huge           mel01 with one entry of 1e4 in one frame of every window, and one in a short frame of window 0
     denorm         mel01 x 1e-39: float32 subnormals"""
     style = "randn" if kind == "randn" else "mel01"
-    mel, short, emo = synth.make_core_inputs(seed, B, t_in, style=style)
+    mel, short, emo = synth.make_core_inputs(seed, B, t_in, n_mels=n_mels, emotion_dim=emotion_dim, style=style)
     mel, short = mel.copy(), short.copy()
+    zero = sorted({0, 37 * n_mels // 80, n_mels - 1})
     if kind == "const":
         mel[:] = mel[:, :1]
         short[:] = short[:, :1]
     elif kind == "zeroch":
-        mel[:, :, [0, 37, 79]] = 0.0
-        short[:, :, [0, 37, 79]] = 0.0
+        mel[:, :, zero] = 0.0
+        short[:, :, zero] = 0.0
     elif kind == "huge":
         for b in range(B):
-            mel[b, (17 * b + min(t_in, T) - 1) % min(t_in, T), (29 * b + 5) % 80] = 1e4
-        short[0, 1, 63] = 1e4
+            mel[b, (17 * b + min(t_in, T) - 1) % min(t_in, T), (29 * b + 5) % n_mels] = 1e4
+        short[0, 1, 63 % n_mels] = 1e4
     elif kind == "denorm":
         mel = (mel.astype(np.float64) * 1e-39).astype(np.float32)
         short = (short.astype(np.float64) * 1e-39).astype(np.float32)
@@ -118,14 +122,72 @@ FAULTS = ("short_reversed", "last_long_row", "ln_eps", "softmax_scale", "value_c
 
 
 # ---- guarded device views ------------------------------------------------------------------------------------------------------
-def guarded(x, guard=1280):
+def guarded(x, guard=1280, n_mels=None):
     """x on the device as a view into a larger NaN-filled allocation: `guard` floats of NaN (16 rows of 80) before the first
     element and after the last, so a read outside the tensor meets NaN.  The default keeps the 16-byte alignment of the rows
-    (the kernels read them as float4); guard = 1281 puts the view 4 bytes off it (the emotion vectors are read word by word)."""
+    (the kernels read them as float4); guard = 1281 puts the view 4 bytes off it (the emotion vectors are read word by word).
+    With n_mels the guard is 16 rows of n_mels channels: 16 n_mels floats, a multiple of 4 floats for any channel count."""
     import torch
+    if n_mels is not None:
+        guard = 16 * n_mels
     x = np.ascontiguousarray(x, dtype=np.float32)
     buf = torch.full((x.size + 2 * guard,), float("nan"), dtype=torch.float32, device="cuda")
     view = buf[guard:guard + x.size].view(*x.shape)
     view.copy_(torch.from_numpy(x))
     assert view.is_contiguous() and view.data_ptr() == buf.data_ptr() + 4 * guard
     return view
+
+
+# ---- engines and the judge (the bound: the docstring of tests/test_gpu_core_logit.py) --------------------------------------------------
+EMA_ROUNDINGS = 5.0
+
+
+def engine_for(params, **kw):
+    from koemorph_amd.engine import Engine
+    e = Engine(**kw)
+    e.load_state_dict(params)
+    e.finalize()
+    e.set_option("core_split", 0)          # the split-bf16 images are opt-in and no case here opts in
+    return e
+
+
+def judge(group, label, ref, s=None, a=None, extra=None, out_over_c=False):
+    """Assert the bound on the sigmoid values `s` (B, 52) and / or the attention map `a` (B, 28, 80).  out_over_c: `s` was recovered
+    as out / c_i and the bound holds three storage terms instead of one (core.logit_bound); `extra` is a derived per-entry term
+    added to the bound (the EMA recovery)."""
+    zmax = float(np.abs(ref["z64"]).max())
+    assert zmax <= core.LOGIT_Z_MAX, f"{group} {label}: |z64| reaches {zmax}, choose other parameters"
+    e_max = e_ratio = a_max = a_ratio = float("nan")
+    if s is not None:
+        e_max, e_ratio = core.logit_verdict(s, ref, K, core.OUT_OVER_C_ROUNDINGS if out_over_c else 1, extra)
+    if a is not None:
+        a_max, a_ratio = core.attention_verdict(a, ref, K)
+    print(f"CORELOGIT|{group}|{label}|{e_max:.3e}|{ref['yard_e']:.3e}|{e_ratio:.3f}|{a_max:.3e}|{ref['yard_a']:.3e}|{a_ratio:.3f}")
+    if s is not None:
+        assert e_ratio <= 1.0, f"{group} {label}: logit error {e_max:.3e} is {e_ratio:.2f} x its bound (float32 yardstick {ref['yard_e']:.3e})"
+    if a is not None:
+        assert a_ratio <= 1.0, f"{group} {label}: attention error {a_max:.3e} is {a_ratio:.2f} x its bound (yardstick {ref['yard_a']:.3e})"
+
+
+def ema_term(x64, prev, params):
+    """The rounding of the float32 EMA as seen through undo_ema, in the units of logit_error (see the module docstring)."""
+    alpha = 1.0 / (1.0 + np.exp(-0.8))
+    c = core.stream_coefficients(params)
+    s64 = x64 / c
+    return EMA_ROUNDINGS * core.LOGIT_U * np.maximum(x64, prev) / (alpha * c * s64 * (1.0 - s64))
+
+
+def run_core(e, group, label, params, inputs, H=8, T=256):
+    """core_forward with and without the attention outputs on guarded views; `raw`, out / c_i of both calls and the map judged."""
+    mel, short, emo = inputs
+    ref = core.logit_reference(params, mel, short, emo, num_heads=H, mel_sequence_length=T)
+    gm, gs, ge = guarded(mel), guarded(short), guarded(emo)
+    o = e.core_forward(gm, gs, ge, return_attention=True)
+    o2 = e.core_forward(gm, gs, ge)
+    judge(group, label + " raw", ref, s=o["raw"].cpu().numpy(), a=o["mel_attention_weights"].cpu().numpy())
+    judge(group, label + " out/c", ref, s=core.recover_sigmoid(o["blendshapes"].cpu().numpy(), params), out_over_c=True)
+    judge(group, label + " out/c noattn", ref, s=core.recover_sigmoid(o2["blendshapes"].cpu().numpy(), params), out_over_c=True)
+    # raw and the recovery agree to the storage of both (c_i s is one more float32 product)
+    d = np.abs(core.recover_sigmoid(o["blendshapes"].cpu().numpy(), params) - o["raw"].cpu().numpy().astype(np.float64))
+    assert (d <= 3 * core.LOGIT_U * ref["s64"] + 1e-45).all(), (group, label, float(d.max()))
+    return ref, o

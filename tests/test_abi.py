@@ -44,3 +44,11 @@ def test_create_validates_like_the_reference_constructors():
     assert e.sequence_num_outputs(136448 + 533 * 9, 1) == 10
     assert e.sequence_num_outputs(1000, 1) == 1
     e.close()
+
+
+def test_gemm_kernel_choice_is_a_host_function():
+    """km_gemm_kernel_choice names the kernel launch_gemm would run without touching a device (tests/test_gemm_choice.py holds the
+    table): a code of 0 .. 4, -1 for a bad argument."""
+    lib = _lib.load()
+    assert lib.km_gemm_kernel_choice(1, 256, 264, 1) == 0 and lib.km_gemm_kernel_choice(1000, 800, 48, 1) == 1
+    assert lib.km_gemm_kernel_choice(0, 1, 1, 1) == -1

@@ -70,64 +70,13 @@ import pytest
 import torch
 
 import core_logit_cases as cc
-from core_logit_cases import K, guarded, make_inputs, make_params
+from core_logit_cases import EMA_ROUNDINGS, K, ema_term, engine_for, guarded, judge, make_inputs, make_params, run_core  # noqa: F401
 from koemorph_amd import synth
 from koemorph_amd.engine import Engine, MelConfig
 from oracle import core
 
 pytestmark = pytest.mark.gpu
-EMA_ROUNDINGS = 5.0
 EXPR0 = core.EXPRESSION_INDICES[0]
-
-
-def engine_for(params, **kw):
-    e = Engine(**kw)
-    e.load_state_dict(params)
-    e.finalize()
-    e.set_option("core_split", 0)          # the split-bf16 images are opt-in and no case here opts in
-    return e
-
-
-def judge(group, label, ref, s=None, a=None, extra=None, out_over_c=False):
-    """Assert the bound on the sigmoid values `s` (B, 52) and / or the attention map `a` (B, 28, 80).  out_over_c: `s` was recovered
-    as out / c_i and the bound holds three storage terms instead of one (core.logit_bound); `extra` is a derived per-entry term
-    added to the bound (the EMA recovery)."""
-    zmax = float(np.abs(ref["z64"]).max())
-    assert zmax <= core.LOGIT_Z_MAX, f"{group} {label}: |z64| reaches {zmax}, choose other parameters"
-    e_max = e_ratio = a_max = a_ratio = float("nan")
-    if s is not None:
-        e_max, e_ratio = core.logit_verdict(s, ref, K, core.OUT_OVER_C_ROUNDINGS if out_over_c else 1, extra)
-    if a is not None:
-        a_max, a_ratio = core.attention_verdict(a, ref, K)
-    print(f"CORELOGIT|{group}|{label}|{e_max:.3e}|{ref['yard_e']:.3e}|{e_ratio:.3f}|{a_max:.3e}|{ref['yard_a']:.3e}|{a_ratio:.3f}")
-    if s is not None:
-        assert e_ratio <= 1.0, f"{group} {label}: logit error {e_max:.3e} is {e_ratio:.2f} x its bound (float32 yardstick {ref['yard_e']:.3e})"
-    if a is not None:
-        assert a_ratio <= 1.0, f"{group} {label}: attention error {a_max:.3e} is {a_ratio:.2f} x its bound (yardstick {ref['yard_a']:.3e})"
-
-
-def ema_term(x64, prev, params):
-    """The rounding of the float32 EMA as seen through undo_ema, in the units of logit_error (see the module docstring)."""
-    alpha = 1.0 / (1.0 + np.exp(-0.8))
-    c = core.stream_coefficients(params)
-    s64 = x64 / c
-    return EMA_ROUNDINGS * core.LOGIT_U * np.maximum(x64, prev) / (alpha * c * s64 * (1.0 - s64))
-
-
-def run_core(e, group, label, params, inputs, H=8, T=256):
-    """core_forward with and without the attention outputs on guarded views; `raw`, out / c_i of both calls and the map judged."""
-    mel, short, emo = inputs
-    ref = core.logit_reference(params, mel, short, emo, num_heads=H, mel_sequence_length=T)
-    gm, gs, ge = guarded(mel), guarded(short), guarded(emo)
-    o = e.core_forward(gm, gs, ge, return_attention=True)
-    o2 = e.core_forward(gm, gs, ge)
-    judge(group, label + " raw", ref, s=o["raw"].cpu().numpy(), a=o["mel_attention_weights"].cpu().numpy())
-    judge(group, label + " out/c", ref, s=core.recover_sigmoid(o["blendshapes"].cpu().numpy(), params), out_over_c=True)
-    judge(group, label + " out/c noattn", ref, s=core.recover_sigmoid(o2["blendshapes"].cpu().numpy(), params), out_over_c=True)
-    # raw and the recovery agree to the storage of both (c_i s is one more float32 product)
-    d = np.abs(core.recover_sigmoid(o["blendshapes"].cpu().numpy(), params) - o["raw"].cpu().numpy().astype(np.float64))
-    assert (d <= 3 * core.LOGIT_U * ref["s64"] + 1e-45).all(), (group, label, float(d.max()))
-    return ref, o
 
 
 # ---- fused d256 kernel: parameter sets x inputs, and every t_in ------------------------------------------------------------------

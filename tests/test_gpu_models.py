@@ -236,9 +236,12 @@ def test_60fps_long_context_configuration_end_to_end():
 @pytest.mark.parametrize("d,T,H,fps,L", [(512, 512, 16, 60, 512 * 266), (512, 512, 8, 60, 300 * 266 + 5), (64, 32, 4, 30, 33 * 533),
                                          (64, 32, 4, 30, 2 * 533 + 1)])
 def test_generic_packed_encoder_path_matches_staged_path(d, T, H, fps, L):
-    """km_forward_audio on generic shapes: log-mel written straight into the packed encoder input + encoder_tn_kernel,
-    against the staged path (mel_log_kernel + strided GEMM + K=3 accumulate), incl. windows shorter than T (zero rows)
-    and shorter than 3 frames' worth of context."""
+    """km_forward_audio on generic shapes against the staged path (option generic_staged: mel_log_kernel + strided gemm_kernel + K=3
+    accumulate + ln_rows_kernel), incl. windows shorter than T (zero rows) and shorter than 3 frames' worth of context.  At d_model
+    512 and 64 the default from-audio route is the power path (generic_core_takes_power): the power-mel handed to
+    encoder_ln_kernel<FUSE_DB = true>, inside core512_kernel at d 512.  Neither side reaches the packed image (launch_mel_packed) or
+    encoder_tn_kernel any more: tests/test_gpu_generic_shapes.py holds those (d_model 128 from audio, the no_db_fusion and
+    no_ln_fusion switches) against the float64 oracle."""
     import os
     from koemorph_amd.engine import Engine, MelConfig
     eng = Engine(d_model=d, num_heads=H, mel_sequence_length=T, mel=MelConfig.model_batch(target_fps=fps))

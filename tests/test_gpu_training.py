@@ -243,6 +243,41 @@ def test_training_step_is_reproducible_and_agrees_with_the_float64_oracle():
         np.testing.assert_allclose(g_ph[k], g_64[k], atol=1e-8 + 2e-5 * np.abs(g_64[k]).max(), rtol=2e-4, err_msg=k)
 
 
+@pytest.mark.parametrize("variant,T,ED,seed", [("fast", 128, 256, 91), ("basic", 256, 9, 93)])
+def test_training_step_at_the_d128_variants_agrees_with_the_float64_oracle(variant, T, ED, seed):
+    """The reference's d_model 128 / 4-head variants (configs/model/dual_stream.yaml: `fast`, window 128; `basic`, window 256 and
+    emotion_dim 9) in training: forward_backward_mel with B = 3 and mse + 0.1 l1 against torch.autograd in FLOAT64 on the oracle
+    (core_full_loss_and_grads, the other KoeMorphLoss terms weighted zero), under the bounds of
+    test_training_step_is_reproducible_and_agrees_with_the_float64_oracle, unchanged: loss 1e-6 max(1, |loss|), output 1e-6,
+    gradients atol 1e-8 + 2e-5 max|ref| with rtol 2e-4.  Run twice: the same bits.  Prints what it observes (pytest -s); on the
+    MI355X: `fast` loss 9.5e-9, output 9.7e-8, gradients 3.1e-6 of a tensor's largest entry; `basic` 1.0e-9, 2.8e-8, 1.2e-6."""
+    d, H, B = 128, 4, 3
+    params = synth.make_core_params(seed, d, T, ED, "trained")
+    mel, short, emo = synth.make_core_inputs(seed + 1, B, T + 1, emotion_dim=ED)
+    target, prev_pred, prev_target, lw = full_loss_inputs(seed, B)                 # all but the target: placeholders, weighted zero
+    shapes = {k: v.shape for k, v in params.items()}
+    e = Engine(d_model=d, num_heads=H, mel_sequence_length=T, emotion_dim=ED)
+    e.load_state_dict(params)
+    e.finalize()
+    tr = Trainer(e, max_windows=B, use_smoothing=False, l1_weight=0.1)
+    l_ph = float(tr.forward_backward_mel(dev(mel), dev(short), dev(emo), dev(target)).item())
+    g_ph, out_ph = tr.grads(shapes), tr.out[:B].cpu().numpy()
+    again = float(tr.forward_backward_mel(dev(mel), dev(short), dev(emo), dev(target)).item())
+    assert again == l_ph and all(np.array_equal(v, tr.grads(shapes)[k]) for k, v in g_ph.items())     # no atomics: bit-reproducible
+    only_mse_l1 = dict(mse_weight=1.0, l1_weight=0.1, perceptual_weight=0.0, temporal_weight=0.0, sparsity_weight=0.0,
+                       smoothness_weight=0.0, landmark_weight=0.0, velocity_weight=0.0)
+    l_64, g_64, out_64 = core.core_full_loss_and_grads(params, mel, short, emo, target, prev_pred, prev_target, lw, weights=only_mse_l1,
+                                                       num_heads=H, mel_sequence_length=T, dtype=torch.float64)
+    assert sorted(g_ph) == sorted(g_64)
+    worst = max(float(np.abs(g_ph[k] - g_64[k]).max()) / max(float(np.abs(g_64[k]).max()), 1e-300) for k in g_ph)
+    print(f"{variant}: loss {l_ph!r} vs float64 {l_64!r} (|diff| {abs(l_ph - l_64):.3e}); output max |diff| {np.abs(out_ph - out_64).max():.3e}; "
+          f"gradients: worst max |diff| / max |ref| over the tensors {worst:.3e}")
+    assert abs(l_ph - l_64) < 1e-6 * max(1.0, abs(l_64)) and float(np.abs(out_ph - out_64).max()) < 1e-6
+    for k in g_ph:
+        np.testing.assert_allclose(g_ph[k], g_64[k], atol=1e-8 + 2e-5 * np.abs(g_64[k]).max(), rtol=2e-4, err_msg=k)
+    e.close()
+
+
 @pytest.mark.parametrize("name", ["core_d64_T32_H4_train", "core_d256_T256_H8_train", "core_d512_T512_H8_train"])
 def test_training_mode_dropout_gradients_match_reference(name):
     """model.train() with dropout 0.1: the step replays the three dropout masks of the fixture (drawn by torch in the
