@@ -240,6 +240,7 @@ SIGNATURES = {
     "km_enable_stage_timing":(C.c_int, [_h, _i32]),
     "km_stage_times": (C.c_int, [_h, C.POINTER(C.c_float)]),
     "km_debug_buffer": (C.c_int, [_h, C.c_char_p, _p, C.POINTER(_i64)]),
+    "km_core_route": (C.c_int, [_h, _i32]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -101,6 +101,8 @@ static int stream_launches(Context* c, const unsigned char* gate, const float* e
     if (int rc = launch_mel_power(c, c->st.plan, mel_rings(c, gate), stream, fuse_emo ? mel_emotion(emotion_dev, c->ws.zemo) : MelCarry{})) return rc;
     if (c->fused_ok)
         return launch_core_fused_db(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, with_outputs(core_stream(c, gate), raw_dev, attn_dev));
+    if (core256w_stream_ok(c))
+        return launch_core256w_stream(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, gate, raw_dev, attn_dev);
     return launch_core512_stream(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, gate, raw_dev, attn_dev);
 }
 
@@ -109,8 +111,9 @@ static int stream_tick(km_handle h, const float* emotion_dev, float* out_dev, ui
     Context* c = h;
     if (c->st.n_streams <= 0) return fail(KM_ERR_INVALID_ARG, "km_stream_tick: no streams (km_stream_create first)");
     if (!emotion_dev || !out_dev) return fail(KM_ERR_INVALID_ARG, "km_stream_tick: NULL argument");
-    // two shapes have a streaming core: the fused one (d_model 256, 8 heads, window 256) and core512's (512, 8 or 16 heads, window 512)
-    if (!c->fused_ok && !core512_stream_ok(c))
+    // three shapes have a streaming core: the fused one (d_model 256, 8 heads, window 256), core512's (512, 8 or 16 heads, window 512)
+    // and core256w's (256, 8 heads, window 512)
+    if (!stream_core_ok(c))
         return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
     const int64_t S = c->st.n_streams, L = c->st.ring_len;
     const int64_t n_frames = 1 + L / c->st.plan->cfg.hop_length;
@@ -165,7 +168,7 @@ int km_stream_fifo_create(km_handle h, int64_t fifo_samples, int64_t frame_sampl
     HIP_TRY(hipMemset(f.state, 0, 3 * S * sizeof(int)));
     HIP_TRY(hipMemset(f.fire, 0, S));
     f.len = fifo_samples; f.frame = (int)frame_samples;
-    if (!c->fused_ok && !core512_stream_ok(c)) { c->st.fifo = std::move(f); return KM_OK; }
+    if (!stream_core_ok(c)) { c->st.fifo = std::move(f); return KM_OK; }
     // the launches of one step over a gate of zeros: no workgroup passes it, so nothing is read or written (the emotion rows and
     // the result pointer are dummies), but every kernel of a step has had its attributes set before a capture sees its first launch
     DevBuf<float> emo;
@@ -191,7 +194,7 @@ static int stream_step(km_handle h, const float* emotion_dev, float* out_dev, ui
     if (int rc = need_stream_fifos(h, "km_stream_step")) return rc;
     Context* c = h;
     if (!emotion_dev || !out_dev) return fail(KM_ERR_INVALID_ARG, "km_stream_step: NULL argument");
-    if (!c->fused_ok && !core512_stream_ok(c))                                      // as km_stream_tick, before anything is popped
+    if (!stream_core_ok(c))                                                         // as km_stream_tick, before anything is popped
         return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
     const int64_t S = c->st.n_streams;
     if (S > c->ws.windows || 1 + c->st.ring_len / c->st.plan->cfg.hop_length > c->ws.frames)

@@ -68,7 +68,7 @@ struct Options {
     int emotion_separate = 0;      // 1: emotion logits in their own kernel
     int no_ln_fusion = 0, no_db_fusion = 0, no_score_fusion = 0, no_out_fusion = 0, no_v_fusion = 0;   // generic chain A/B
     int legacy_no_merge = 0;       // 1: the legacy model's attention and tail as two launches instead of one (legacy_attn_tail_kernel)
-    int no_core_merge = 0;         // 1: the d_model 512 core as its three launches (encoder + LayerNorm, scores, output) instead of one workgroup per window walking the three stages (core512_kernel)
+    int no_core_merge = 0;         // 1: the d_model 512 core as its three launches (encoder + LayerNorm, scores, output) instead of one workgroup per window walking the three stages (core512_kernel); d_model 256 / window 512: the launch-per-product chain instead of core256w_kernel
     int legacy_no_tail_fusion = 0; // 1: SimplifiedKoeMorphModel out_proj + decoder as four GEMM launches + a row kernel (A/B, tests)
     int legacy_no_enc_fusion = 0;  // 1: SimplifiedKoeMorphModel audio encoder + key / value projections as four GEMM launches (A/B, tests)
     int legacy_no_attn_fusion = 0; // 1: SimplifiedKoeMorphModel attention as two batched strided products + a row softmax (A/B, tests)
@@ -376,6 +376,14 @@ bool core512_stream_ok(Context* c);
 // raw (S, 52) / attn (S, 28, 80, 16-byte aligned) or null: the pre-weight sigmoid values and the head-averaged map of the computed streams
 int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
                           const unsigned char* gate = nullptr, float* raw = nullptr, float* attn = nullptr);
+// ... and on d_model 256 / 8 heads / window 512 (the shape of the 60 fps recipe): core256w's streaming kernel, same contract
+bool core256w_stream_ok(Context* c);
+int launch_core256w_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
+                           const unsigned char* gate = nullptr, float* raw = nullptr, float* attn = nullptr);
+// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or one of the two above
+bool stream_core_ok(Context* c);
+// km_core_route: 0 fused d_model 256 core, 1 core512_kernel, 2 core256w_kernel, 3 the launch-per-product chain
+int core_route(Context* c, bool with_attention);
 
 // km_mel.hip
 // Shared-frame sequence mode: the front end writes n_rows rows per window (row r = STFT frame r * frame_mul) into

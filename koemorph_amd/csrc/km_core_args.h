@@ -1,0 +1,26 @@
+// Kernel arguments of the one-launch generic cores (core512_kernel in km_generic.hip, core256w_kernel in km_core256w.hip) and the
+// launchers of the latter.  Internal: not part of the public ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "km_encoder_dev.h"
+
+namespace km {
+
+struct Core512Args {
+    const float* xp; const float* wce_pg; const float* bce; const float* ln_g; const float* ln_b; float* Y; int KP; EncSrc src;
+    const float* qk_pg; float* S; int rows;
+    const float* wv_bg; const float* wf_pg; const float* bf; const float* w2; const float* b2; const float* zemo; const float* wsum;
+    float* out; float* raw;
+};
+struct Core512StreamArgs { Core512Args c; StreamSrc st; };
+
+// km_core256w.hip: one 512-thread workgroup per window / stream; a.wv_bg holds the wv_bg32 image.  The launch only: what follows
+// a streaming launch (window maxima, maps) is the caller's
+int launch_core256w_kernel(const Core512Args& a, bool fuse_db, int64_t B, int device, hipStream_t st);
+int launch_core256w_stream_kernel(const Core512StreamArgs& sa, int64_t S, int device, hipStream_t st);
+
+}  // namespace km

@@ -27,6 +27,7 @@
 #include "km_context.h"
 #include "km_device.h"
 #include "km_attn_dev.h"
+#include "km_core_args.h"
 #include "km_legacy_attn_dev.h"
 #include "km_encoder_dev.h"
 #include "km_gemm.h"
@@ -577,12 +578,7 @@ static int launch_encoder_ln(Context* c, int64_t B, hipStream_t st, const float*
 // __syncthreads() orders the stages.  LDS: the encoder's 26 KB static + the 109 KB dynamic image of the last stage, whose head doubles
 // as the scores stage's Y buffers.
 // ---------------------------------------------------------------------------------------------------------
-struct Core512Args {
-    const float* xp; const float* wce_pg; const float* bce; const float* ln_g; const float* ln_b; float* Y; int KP; EncSrc src;
-    const float* qk_pg; float* S; int rows;
-    const float* wv_bg; const float* wf_pg; const float* bf; const float* w2; const float* b2; const float* zemo; const float* wsum;
-    float* out; float* raw;
-};
+// (Core512Args, Core512StreamArgs: km_core_args.h)
 template <int TPW, int HPW, bool FUSE_DB>
 __global__ __launch_bounds__(512) void core512_kernel(Core512Args a) {
     __shared__ EncLds<8> el;
@@ -599,7 +595,6 @@ __global__ __launch_bounds__(512) void core512_kernel(Core512Args a) {
 // first barrier and leaves its out row, EMA state and window maximum as they were; the encoder reads its rows under the streaming
 // row policy and the tail applies the per-stream EMA (StreamSrc, km_encoder_dev.h).  A kernel of its own around the same three
 // bodies, so that core512_kernel's instantiations and their arguments are what they were.  No LDS beyond theirs.
-struct Core512StreamArgs { Core512Args c; StreamSrc st; };
 template <int TPW, int HPW>
 __global__ __launch_bounds__(512) void core512_stream_kernel(Core512StreamArgs sa) {
     __shared__ EncLds<8> el;
@@ -614,8 +609,8 @@ __global__ __launch_bounds__(512) void core512_stream_kernel(Core512StreamArgs s
     attn_out_vr_body<512, HPW, true>(a.S, a.Y, a.wv_bg, a.wf_pg, a.bf, a.w2, a.b2, a.zemo, a.wsum, a.out, a.raw, b, gsm, sa.st);
 }
 
-static bool core512_merge_ok(Context* c, const float* attn) {
-    return c->d == 512 && c->NK == 80 && c->DH == 256 && (c->H == 8 || c->H == 16) && !attn && !c->opt.no_ln_fusion &&
+static bool core512_merge_ok(Context* c, bool with_attn) {
+    return c->d == 512 && c->NK == 80 && c->DH == 256 && (c->H == 8 || c->H == 16) && !with_attn && !c->opt.no_ln_fusion &&
            !c->opt.no_score_fusion && !c->opt.no_out_fusion && !c->opt.no_v_fusion && !c->opt.no_core_merge && c->packed.count("qk_pg") &&
            c->packed.count("wf_pg") && c->packed.count("wv_bg");
 }
@@ -642,6 +637,25 @@ static int launch_core512(Context* c, int64_t B, const float* xp, int KP, const 
     return KM_OK;
 }
 
+// core256w_kernel (km_core256w.hip), the one-launch core of d_model 256 / 8 heads / decoder hidden 128 at window 512 -- the shape the
+// reference's frame_rate=60 recipe trains.  T is restricted on purpose: every other d_model 256 window keeps the launches it has
+// (encoder_ln_kernel<8, 2> + the chain)
+static bool core256w_ok(Context* c, bool with_attn) {
+    return c->d == 256 && c->H == 8 && c->NK == 80 && c->DH == 128 && c->T == 512 && !with_attn && !c->opt.no_ln_fusion &&
+           !c->opt.no_score_fusion && !c->opt.no_out_fusion && !c->opt.no_v_fusion && !c->opt.no_core_merge && c->packed.count("qk_pg") &&
+           c->packed.count("wf_pg") && c->packed.count("wv_bg32") && c->packed.count("wce_pg");
+}
+
+// ... and its launch (the kernels: km_core256w.hip); fuse_db: rows from the power-mel of `src` instead of the packed image xp
+static int launch_core256w(Context* c, bool fuse_db, int64_t B, const float* xp, int KP, const EncSrc& src, const float* zemo, float* out,
+                           float* raw, hipStream_t st) {
+    float* Y = c->ws.generic;
+    float* S = Y + 2 * B * c->NK * c->d;      // where the chain keeps its scores
+    Core512Args a{xp, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), S, c->H * 28,
+                  dv(c, "wv_bg32"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw};
+    return launch_core256w_kernel(a, fuse_db, B, c->device, st);
+}
+
 // d_model -> (waves, column tiles per wave) of the fused encoder + LayerNorm kernel
 template <bool FUSE_DB>
 static int launch_encoder_ln_for(Context* c, int64_t B, hipStream_t st, const float* xp, int KP, const EncSrc& src) {
@@ -665,7 +679,8 @@ int launch_core_generic_packed(Context* c, const float* xp, int64_t B, const flo
     const bool fuse_ln = !c->opt.no_ln_fusion;
     hipStream_t st = (hipStream_t)stream;
     bool ln_done = fuse_ln;
-    if (core512_merge_ok(c, attn)) return launch_core512<false>(c, B, xp, KP, EncSrc{}, zemo, out, raw, st);
+    if (core512_merge_ok(c, attn != nullptr)) return launch_core512<false>(c, B, xp, KP, EncSrc{}, zemo, out, raw, st);
+    if (core256w_ok(c, attn != nullptr)) return launch_core256w(c, false, B, xp, KP, EncSrc{}, zemo, out, raw, st);
     if (fuse_ln && (d == 512 || d == 256 || d == 64)) {
         if (int rc = launch_encoder_ln_for<false>(c, B, st, xp, KP, EncSrc{})) return rc;
     } else {
@@ -691,8 +706,13 @@ int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_fr
     const int KP = (c->KT + 15) / 16 * 16;
     hipStream_t st = (hipStream_t)stream;
     EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
-    if (core512_merge_ok(c, attn)) {
+    if (core512_merge_ok(c, attn != nullptr)) {
         if (int rc = launch_core512<true>(c, B, nullptr, KP, src, zemo, out, raw, st)) return rc;
+        c->melmax_dirty = false;
+        return KM_OK;
+    }
+    if (core256w_ok(c, attn != nullptr)) {
+        if (int rc = launch_core256w(c, true, B, nullptr, KP, src, zemo, out, raw, st)) return rc;
         c->melmax_dirty = false;
         return KM_OK;
     }
@@ -702,7 +722,21 @@ int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_fr
 }
 
 // km_stream_tick on the d_model 512 shapes: the front end has written the power-mel of every ready stream's ring
-bool core512_stream_ok(Context* c) { return core512_merge_ok(c, nullptr) && generic_core_takes_power(c); }
+bool core512_stream_ok(Context* c) { return core512_merge_ok(c, false) && generic_core_takes_power(c); }
+// ... and on d_model 256 / 8 heads / window 512 (core256w_stream_kernel)
+bool core256w_stream_ok(Context* c) { return core256w_ok(c, false) && generic_core_takes_power(c); }
+// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or one of the two above
+bool stream_core_ok(Context* c) { return c->fused_ok || core512_stream_ok(c) || core256w_stream_ok(c); }
+
+// km_core_route: the kernel the forward calls take behind the packed image or the power-mel (km_core_forward, km_forward_audio,
+// the generic branch of km_sequence_forward*); host only
+int core_route(Context* c, bool with_attention) {
+    if (c->fused_ok) return 0;
+    if (c->opt.generic_staged) return 3;
+    if (core512_merge_ok(c, with_attention)) return 1;
+    if (core256w_ok(c, with_attention)) return 2;
+    return 3;
+}
 
 // The head-averaged map of every stream that core512_stream_kernel just computed (km_stream_tick_attn / _step_attn): the kernel
 // leaves the softmaxed scores of all heads in the workspace, H blocks of 28 x 80 per stream.  A dependent launch gated on the flags
@@ -726,34 +760,54 @@ __global__ __launch_bounds__(kStreamMapThreads) void stream_head_mean_kernel(con
     reinterpret_cast<float4*>(attn)[(int64_t)b * per4 + i] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
 }
 
+// the arguments of a streaming core launch over the rings' power-mel (wv: the value image of the shape's last stage)
+static Core512StreamArgs stream_core_args(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out,
+                                          const unsigned char* gate, float* raw, const char* wv) {
+    const int KP = (c->KT + 15) / 16 * 16;
+    float* Y = c->ws.generic;
+    float* Sc = Y + 2 * S * c->NK * c->d;
+    const EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
+    return {{nullptr, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), Sc, c->H * 28,
+             dv(c, wv), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw},
+            {(int)(c->st.out_frames > 0 ? c->st.out_frames : n_frames), gate ? gate : c->st.ring_ready, c->st.ring_started,
+             c->st.ring_state, c->alpha}};
+}
+
+// what follows a streaming core launch: the window maxima are clean again; the maps, where asked for
+static int stream_core_done(Context* c, const Core512StreamArgs& sa, int64_t S, float* attn, void* stream) {
+    HIP_TRY(hipGetLastError());
+    c->melmax_dirty = false;     // as in launch_core_generic_power: the slots the front end wrote are re-zeroed by the encoder stage
+    if (attn) {
+        const int per4 = 28 * c->NK / 4;
+        hipLaunchKernelGGL(stream_head_mean_kernel, dim3((unsigned)S, (unsigned)((per4 + kStreamMapThreads - 1) / kStreamMapThreads)),
+                           dim3(kStreamMapThreads), 0, (hipStream_t)stream, sa.c.S, sa.st.ready, attn, c->H, per4);
+        HIP_TRY(hipGetLastError());
+    }
+    return KM_OK;
+}
+
 int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
                           const unsigned char* gate, float* raw, float* attn) {
     if (!core512_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
     if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
-    const int d = c->d, H = c->H, NKk = c->NK, KP = (c->KT + 15) / 16 * 16;
-    float* Y = c->ws.generic;
-    float* Sc = Y + 2 * S * NKk * d;
-    const EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
-    Core512StreamArgs sa{{nullptr, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), Sc, H * 28,
-                          dv(c, "wv_bg"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw},
-                         {(int)(c->st.out_frames > 0 ? c->st.out_frames : n_frames), gate ? gate : c->st.ring_ready, c->st.ring_started,
-                          c->st.ring_state, c->alpha}};
+    const Core512StreamArgs sa = stream_core_args(c, plan, S, n_frames, zemo, out, gate, raw, "wv_bg");
     static PerDeviceOnce once;
     if (once.first(c->device)) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_stream_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_stream_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
     }
-    if (H == 8) hipLaunchKernelGGL((core512_stream_kernel<2, 1>), dim3((unsigned)S), dim3(512), kCore512Lds, (hipStream_t)stream, sa);
+    if (c->H == 8) hipLaunchKernelGGL((core512_stream_kernel<2, 1>), dim3((unsigned)S), dim3(512), kCore512Lds, (hipStream_t)stream, sa);
     else hipLaunchKernelGGL((core512_stream_kernel<4, 2>), dim3((unsigned)S), dim3(512), kCore512Lds, (hipStream_t)stream, sa);
-    HIP_TRY(hipGetLastError());
-    c->melmax_dirty = false;     // as in launch_core_generic_power: the slots the front end wrote are re-zeroed by the encoder stage
-    if (attn) {
-        const int per4 = 28 * NKk / 4;
-        hipLaunchKernelGGL(stream_head_mean_kernel, dim3((unsigned)S, (unsigned)((per4 + kStreamMapThreads - 1) / kStreamMapThreads)),
-                           dim3(kStreamMapThreads), 0, (hipStream_t)stream, Sc, sa.st.ready, attn, H, per4);
-        HIP_TRY(hipGetLastError());
-    }
-    return KM_OK;
+    return stream_core_done(c, sa, S, attn, stream);
+}
+
+int launch_core256w_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
+                           const unsigned char* gate, float* raw, float* attn) {
+    if (!core256w_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
+    if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
+    const Core512StreamArgs sa = stream_core_args(c, plan, S, n_frames, zemo, out, gate, raw, "wv_bg32");
+    if (int rc = launch_core256w_stream_kernel(sa, S, c->device, (hipStream_t)stream)) return rc;
+    return stream_core_done(c, sa, S, attn, stream);
 }
 
 float* generic_packed_x(Context* c, int64_t B) {     // the packed-X slot behind the other intermediates of B windows

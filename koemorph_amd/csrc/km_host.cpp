@@ -384,6 +384,22 @@ int finalize_host(Context* c) {
                         }
         put(c, "wv_bg", std::move(wv_bg));
     }
+    if (d == 256) {
+        // the same operand for attn_out_vr32_body (km_attn256_dev.h): wave w owns the 32 columns of head w, two column tiles;
+        // [kb][w][ct][lane][s] = Wv[32 w + 16 ct + j][16 kb + 4 g + s]
+        const int NWv = d / 32, KBv = d / 16;
+        std::vector<float> wv_bg32((size_t)d * d);
+        for (int kb = 0; kb < KBv; ++kb)
+            for (int w2 = 0; w2 < NWv; ++w2)
+                for (int ct = 0; ct < 2; ++ct)
+                    for (int l = 0; l < 64; ++l)
+                        for (int e = 0; e < 4; ++e) {
+                            const int g = l >> 4, j = l & 15;
+                            wv_bg32[((((size_t)kb * NWv + w2) * 2 + ct) * 64 + l) * 4 + e] =
+                                (float)Wv[(size_t)(32 * w2 + 16 * ct + j) * d + 16 * kb + 4 * g + e];
+                        }
+        put(c, "wv_bg32", std::move(wv_bg32));
+    }
     {   // channel encoder weight with K padded to a multiple of 16 (zeros): rows stay 16-byte aligned and the long
         // and short-term columns form ONE contraction for encoder_tn_kernel (km_generic.hip)
         const int KT = c->KT, KP = (KT + 15) / 16 * 16;
@@ -712,6 +728,13 @@ static int check_mel_cfg(const km_mel_config& m) {
 int km_set_option(km_handle h, const char* name, int64_t value) {
     if (!h || !name) return km::fail(KM_ERR_INVALID_ARG, "km_set_option: NULL argument");
     return km::set_option(h, name, (long long)value);
+}
+
+int km_core_route(km_handle h, int32_t with_attention) {
+    if (!h) return km::fail(KM_ERR_INVALID_ARG, "km_core_route: NULL handle");
+    if (h->kind != 0) return km::fail(KM_ERR_INVALID_ARG, "km_core_route needs a dual-stream handle (km_create)");
+    if (!h->host_finalized) return km::fail(KM_ERR_NOT_FINALIZED, "km_core_route: call km_finalize_host or km_finalize first");
+    return km::core_route(h, with_attention != 0);
 }
 
 int km_create(const km_config* cfg, km_handle* out) {

@@ -354,6 +354,15 @@ class Engine:
                                             _ptr(state), 1 if first else 0, _stream_ptr(clip.device)))
         return out
 
+    def core_route(self, with_attention: bool = False) -> int:
+        """km_core_route: the core the forward calls run for this shape and its switches, after ``finalize_host`` (host only).
+        0 the fused d_model 256 / window 256 core, 1 core512_kernel, 2 core256w_kernel (d_model 256, 8 heads, window 512),
+        3 the launch-per-product chain."""
+        rc = self._lib.km_core_route(self._h, int(bool(with_attention)))
+        if rc < 0:
+            check(rc)
+        return rc
+
     def set_option(self, name: str, value: int) -> None:
         """Run-time switch of this handle (km_set_option): e.g. ("seq_per_window", 1), ("core_split", 3)."""
         check(self._lib.km_set_option(self._h, name.encode(), int(value)))

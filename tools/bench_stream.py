@@ -3,7 +3,8 @@
 Prints ticks/s and p50/p99 tick latency (host wall clock around replay + the 26 KB result readback).
 
 Default: the 30 fps shape (d_model 256, 8 heads, window 256, 533-sample frames).  ``--d-model 512 --heads 8|16 --fps 60``: the 60 fps
-long-context shape (window 512, 8.5 s ring of hop 266, 267-sample frames).  ``--baseline`` adds what a caller had to do at that shape
+long-context shape (window 512, 8.5 s ring of hop 266, 267-sample frames); ``--d-model 256 --heads 8 --fps 60``: the shape of the
+reference's frame_rate=60 recipe (window 512, same ring), with ``--chunked`` / ``--attention`` that shape alone.  ``--baseline`` adds what a caller had to do at that shape
 before the stream path covered it: rings kept outside the library, unrolled into 128 chronological windows per tick, km_forward_audio
 on them with the EMA state (km_smooth behind the generic core), and the same readback -- timed the same way.
 
@@ -39,11 +40,11 @@ S = args.streams
 
 
 def make_engine(d_model, heads, fps):
-    if d_model == 256:
+    if d_model == 256 and fps == 30:
         e = Engine(); e.load_state_dict(synth.make_core_params(0)); e.finalize()
-    else:
-        e = Engine(d_model=512, num_heads=heads, mel_sequence_length=512, mel=MelConfig.model_batch(target_fps=fps))
-        e.load_state_dict(synth.make_core_params(0, 512, 512)); e.finalize()
+    else:      # window 512 at hop 266: d_model 512 (long context) or d_model 256 / 8 heads (the frame_rate=60 recipe)
+        e = Engine(d_model=d_model, num_heads=heads, mel_sequence_length=512, mel=MelConfig.model_batch(target_fps=fps))
+        e.load_state_dict(synth.make_core_params(0, d_model, 512)); e.finalize()
     return e
 
 
@@ -166,20 +167,20 @@ def per_model_route(n_models=8, ticks=60):
             "per_stream_frame": stats(lat)}
 
 
+if args.d_model == 256 and args.fps == 60 and args.heads != 8:
+    ap.error("d_model 256 at 60 fps streams with 8 heads only")
+recipe60 = args.d_model == 256 and args.fps == 60         # the shape of the frame_rate=60 recipe: that shape alone
 if args.attention:
-    for shape in ((256, 8, 30), (512, 8, 60)):
+    for shape in (((256, 8, 60),) if recipe60 else ((256, 8, 30), (512, 8, 60))):
         print(json.dumps(attention_shape(*shape)), flush=True)
     sys.exit(0)
 if args.chunked:
-    for shape in ((256, 8, 30), (512, 8, 60)):
+    for shape in (((256, 8, 60),) if recipe60 else ((256, 8, 30), (512, 8, 60))):
         print(json.dumps(chunked_shape(*shape)), flush=True)
-    print(json.dumps(per_model_route()), flush=True)
+    if not recipe60:
+        print(json.dumps(per_model_route()), flush=True)
     sys.exit(0)
-if args.d_model == 256:
-    eng = Engine(); eng.load_state_dict(synth.make_core_params(0)); eng.finalize()
-else:
-    eng = Engine(d_model=512, num_heads=args.heads, mel_sequence_length=512, mel=MelConfig.model_batch(target_fps=args.fps))
-    eng.load_state_dict(synth.make_core_params(0, 512, 512)); eng.finalize()
+eng = make_engine(args.d_model, args.heads, args.fps)
 se = StreamEngine(eng, S) if args.fps == 30 else StreamEngine(eng, S, update_interval=1.0 / args.fps)
 n = se.ring_hop + 1                                    # 533 / 267 samples per stream and tick
 fill = se.shape["ring_len"] // se.ring_hop + 3
