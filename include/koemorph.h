@@ -561,11 +561,13 @@ int km_koemorph_forward(km_handle h, const float* mel_dev, const float* emotion_
  *                     is full; ready_dev (n_streams) u8 mirrors MelAudioBuffer.is_full (rows of not-ready streams
  *                     are left untouched).  Per-stream EMA state lives in the handle.  The short-term rows are
  *                     the last three kept frames.  push + tick never allocate or synchronise: capture them in a
- *                     hipGraph and replay it per tick.  Three model shapes have a streaming core: d_model 256 /
+ *                     hipGraph and replay it per tick.  Five model shapes have a streaming core: d_model 256 /
  *                     8 heads / mel_sequence_length 256 (30 fps: update_interval 0.0333 s, front end hop 533),
  *                     d_model 512 / 8 or 16 heads / mel_sequence_length 512 (60 fps long context: update_interval
- *                     1/60 s, ring hop 266, front end hop 266, 512 frames per 8.5 s ring of which 510 are kept) and
- *                     d_model 256 / 8 heads / mel_sequence_length 512 (the 60 fps recipe itself, same ring and front end);
+ *                     1/60 s, ring hop 266, front end hop 266, 512 frames per 8.5 s ring of which 510 are kept),
+ *                     d_model 256 / 8 heads / mel_sequence_length 512 (the 60 fps recipe itself, same ring and front end) and
+ *                     d_model 128 / 4 heads / mel_sequence_length 128 or 256 with 80 mel channels (the `fast` and `basic`
+ *                     variants, 30 fps as the first shape; 255 kept rows of an 8.5 s ring, truncated to 128 at `fast`);
  *                     any other shape returns KM_ERR_UNSUPPORTED ("no kernel for d_model=...").
  *   km_stream_reset   clear rings, readiness and EMA state (MelSlidingWindowExtractor.reset :373-383). */
 int km_stream_create(km_handle h, int64_t n_streams, double context_window_s, double update_interval_s,
@@ -938,6 +940,8 @@ int km_resample_clip(void* rs, const float* clip_dev, int64_t n_in, float* out_d
  * "seq_per_window", "generic_staged", "mel_two_frame", "emotion_separate", "no_ln_fusion", "no_db_fusion",
  * "no_score_fusion", "no_out_fusion", "no_v_fusion",
  * "no_core_merge" (the one-launch cores of d_model 512 and of d_model 256 / window 512 as the launches they replaced: km_core_route),
+ * "core128" (default 0; 1: the forward calls at d_model 128 / 4 heads / window 128 or 256 run core128_kernel, route 4, instead of the
+ * launch-per-product chain; the streams at those shapes run its streaming form either way),
  * "kmm_no_fuse" (km_koemorph_forward as the launch-per-step GEMM chain even at the width of the two fused kernels),
  * "legacy_no_enc_fusion" / "legacy_no_attn_fusion" / "legacy_no_tail_fusion" (km_legacy_forward's three fused kernels back to GEMM-chain launches), "train_op_per_launch" (timing aid:
  * every operation of the training program as its own launch), "train_bm32_below", "train_tail_groups", "train_split_min_k",
@@ -957,7 +961,9 @@ int km_debug_buffer(km_handle h, const char* name, float* out, int64_t* n);
  * branch of km_sequence_forward*), for the handle's shape and its switches as they stand; with_attention != 0: when the caller
  * asks for the attention map.  Host only, valid after km_finalize_host.  0: the fused d_model 256 / window 256 core; 1:
  * core512_kernel (d_model 512, 8 or 16 heads); 2: core256w_kernel (d_model 256, 8 heads, window 512, 80 channels -- the shape
- * of the reference's frame_rate=60 recipe); 3: the launch-per-product chain.  Negative: an error code. */
+ * of the reference's frame_rate=60 recipe); 3: the launch-per-product chain; 4: core128_kernel (d_model 128, 4 heads, window 128 or
+ * 256, 80 channels -- the `fast` and `basic` variants -- with option core128 set; the default there is 3).  A call that asks for the
+ * map takes 3 at every generic shape.  Negative: an error code. */
 int km_core_route(km_handle h, int32_t with_attention);
 
 /* ---- window producer for sequence training -------------------------------------------------------------

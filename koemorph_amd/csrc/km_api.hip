@@ -272,7 +272,7 @@ static int forward_audio(km_handle h, const char* who, const float* audio_dev, i
     const MelSrc src = mel_windows(audio_dev, B, L);
     if (!c->fused_ok) {     // generic shapes: staged front end, GEMM-chain core, stand-alone EMA
         if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
-        const bool power_path = generic_core_takes_power(c) && !c->opt.generic_staged;
+        const bool power_path = (generic_core_takes_power(c) || core128_forward_ok(c, attn_dev != nullptr)) && !c->opt.generic_staged;
         const bool fuse_emo = power_path && mel_fuses_emotion(c, plan);   // emotion logits inside the front-end kernel
         if (!fuse_emo)
             if (int rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, stream)) return rc;

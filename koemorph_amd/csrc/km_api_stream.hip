@@ -103,6 +103,8 @@ static int stream_launches(Context* c, const unsigned char* gate, const float* e
         return launch_core_fused_db(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, with_outputs(core_stream(c, gate), raw_dev, attn_dev));
     if (core256w_stream_ok(c))
         return launch_core256w_stream(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, gate, raw_dev, attn_dev);
+    if (core128_stream_ok(c))
+        return launch_core128_stream(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, gate, raw_dev, attn_dev);
     return launch_core512_stream(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, gate, raw_dev, attn_dev);
 }
 
@@ -111,8 +113,8 @@ static int stream_tick(km_handle h, const float* emotion_dev, float* out_dev, ui
     Context* c = h;
     if (c->st.n_streams <= 0) return fail(KM_ERR_INVALID_ARG, "km_stream_tick: no streams (km_stream_create first)");
     if (!emotion_dev || !out_dev) return fail(KM_ERR_INVALID_ARG, "km_stream_tick: NULL argument");
-    // three shapes have a streaming core: the fused one (d_model 256, 8 heads, window 256), core512's (512, 8 or 16 heads, window 512)
-    // and core256w's (256, 8 heads, window 512)
+    // the shapes with a streaming core: the fused one (d_model 256, 8 heads, window 256), core512's (512, 8 or 16 heads, window 512),
+    // core256w's (256, 8 heads, window 512) and core128's (128, 4 heads, window 128 or 256)
     if (!stream_core_ok(c))
         return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
     const int64_t S = c->st.n_streams, L = c->st.ring_len;

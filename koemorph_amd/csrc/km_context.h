@@ -69,6 +69,7 @@ struct Options {
     int no_ln_fusion = 0, no_db_fusion = 0, no_score_fusion = 0, no_out_fusion = 0, no_v_fusion = 0;   // generic chain A/B
     int legacy_no_merge = 0;       // 1: the legacy model's attention and tail as two launches instead of one (legacy_attn_tail_kernel)
     int no_core_merge = 0;         // 1: the d_model 512 core as its three launches (encoder + LayerNorm, scores, output) instead of one workgroup per window walking the three stages (core512_kernel); d_model 256 / window 512: the launch-per-product chain instead of core256w_kernel
+    int core128 = 0;               // 1: the forward calls at d_model 128 / 4 heads / window 128 or 256 run core128_kernel (route 4) instead of the launch-per-product chain; the streams at those shapes run core128_stream_kernel either way
     int legacy_no_tail_fusion = 0; // 1: SimplifiedKoeMorphModel out_proj + decoder as four GEMM launches + a row kernel (A/B, tests)
     int legacy_no_enc_fusion = 0;  // 1: SimplifiedKoeMorphModel audio encoder + key / value projections as four GEMM launches (A/B, tests)
     int legacy_no_attn_fusion = 0; // 1: SimplifiedKoeMorphModel attention as two batched strided products + a row softmax (A/B, tests)
@@ -380,9 +381,15 @@ int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames
 bool core256w_stream_ok(Context* c);
 int launch_core256w_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
                            const unsigned char* gate = nullptr, float* raw = nullptr, float* attn = nullptr);
-// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or one of the two above
+// ... and on d_model 128 / 4 heads / window 128 or 256 (the reference's `fast` and `basic` variants): core128's streaming kernel
+bool core128_stream_ok(Context* c);
+int launch_core128_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
+                          const unsigned char* gate = nullptr, float* raw = nullptr, float* attn = nullptr);
+// the forward calls take core128_kernel at those shapes: option core128 is set and no map is asked for
+bool core128_forward_ok(Context* c, bool with_attention);
+// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or one of the three above
 bool stream_core_ok(Context* c);
-// km_core_route: 0 fused d_model 256 core, 1 core512_kernel, 2 core256w_kernel, 3 the launch-per-product chain
+// km_core_route: 0 fused d_model 256 core, 1 core512_kernel, 2 core256w_kernel, 3 the launch-per-product chain, 4 core128_kernel
 int core_route(Context* c, bool with_attention);
 
 // km_mel.hip

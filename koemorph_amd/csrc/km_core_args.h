@@ -1,5 +1,5 @@
-// Kernel arguments of the one-launch generic cores (core512_kernel in km_generic.hip, core256w_kernel in km_core256w.hip) and the
-// launchers of the latter.  Internal: not part of the public ABI.
+// Kernel arguments of the one-launch generic cores (core512_kernel in km_generic.hip, core256w_kernel in km_core256w.hip, core128_kernel
+// in km_core128.hip) and the launchers of the latter two.  Internal: not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,5 +22,10 @@ struct Core512StreamArgs { Core512Args c; StreamSrc st; };
 // a streaming launch (window maxima, maps) is the caller's
 int launch_core256w_kernel(const Core512Args& a, bool fuse_db, int64_t B, int device, hipStream_t st);
 int launch_core256w_stream_kernel(const Core512StreamArgs& sa, int64_t S, int device, hipStream_t st);
+
+// km_core128.hip: one 256-thread workgroup per window / stream at d_model 128 / 4 heads; a.wce_pg, a.wv_bg and a.wf_pg hold the
+// wce_pg128, wv_bg128 and wf_pg128 images.  The launch only, as above
+int launch_core128_kernel(const Core512Args& a, bool fuse_db, int64_t B, int device, hipStream_t st);
+int launch_core128_stream_kernel(const Core512StreamArgs& sa, int64_t S, int device, hipStream_t st);
 
 }  // namespace km

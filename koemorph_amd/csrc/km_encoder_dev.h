@@ -216,6 +216,15 @@ __device__ __forceinline__ void encoder_ln_body(const float* __restrict__ xp, co
                 for (int r = 0; r < 4; ++r) acc[i][ct][r] += bb[ct];
     }
     float mean[5][4] = {}, rstd[5][4] = {};
+    // REFINE (the four-wave instantiation, core128_kernel): the mean takes one step of refinement.  The residuals about the first
+    // mean are exact or nearly so, and their sum, which pass 1 adds up next to the squares, is what the first mean is off by -- one
+    // ulp of the mean where |mean| >> standard deviation (a bias of 40 over a spread of 0.04: 1e-4 of the normalised row).  It is
+    // taken off the residuals, not added to the mean, so it is not rounded to the mean's grid.  Partial sums and totals of the
+    // residuals sit in As, which the MFMA loop is done with two barriers before.  No other instantiation compiles any of it.
+    constexpr bool REFINE = NW == 4;
+    float corr[REFINE ? 5 : 1][4] = {};
+    float* Cp = As;                   // [row][wave]
+    float* Ct = As + NKc * NW;        // [row]
 #pragma unroll
     for (int pass = 0; pass < ((KM_ENC_SKIP & 4) ? 0 : 2); ++pass) {
         float* P = Ps[pass];
@@ -236,6 +245,15 @@ __device__ __forceinline__ void encoder_ln_body(const float* __restrict__ xp, co
                 }
                 v = row16_sum(v);
                 if (lj == 0) P[(16 * i + 4 * lg + r) * NW + wave] = v;
+                if constexpr (REFINE) {
+                    if (pass == 1) {
+                        float c = 0.f;
+#pragma unroll
+                        for (int ct = 0; ct < CT; ++ct) c += acc[i][ct][r] - mean[i][r];
+                        c = row16_sum(c);
+                        if (lj == 0) Cp[(16 * i + 4 * lg + r) * NW + wave] = c;
+                    }
+                }
             }
         __syncthreads();
         // row totals: wave w adds up the NW partials (in wave order) of rows w * RPW .. + RPW - 1, one row per lane
@@ -245,6 +263,13 @@ __device__ __forceinline__ void encoder_ln_body(const float* __restrict__ xp, co
             float s = 0.f;
             for (int w = 0; w < NW; ++w) s += P[row * NW + w];
             Ts[pass][row] = s;
+            if constexpr (REFINE) {
+                if (pass == 1) {
+                    float c = 0.f;
+                    for (int w = 0; w < NW; ++w) c += Cp[row * NW + w];
+                    Ct[row] = c;
+                }
+            }
         }
         __syncthreads();
 #pragma unroll
@@ -253,7 +278,10 @@ __device__ __forceinline__ void encoder_ln_body(const float* __restrict__ xp, co
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (pass == 0) mean[i][r] = t[r] * (1.0f / D);
-                else rstd[i][r] = 1.0f / sqrtf(t[r] * (1.0f / D) + 1e-5f);
+                else if constexpr (REFINE) {
+                    corr[i][r] = Ct[16 * i + 4 * lg + r] * (1.0f / D);
+                    rstd[i][r] = 1.0f / sqrtf(t[r] * (1.0f / D) - corr[i][r] * corr[i][r] + 1e-5f);
+                } else rstd[i][r] = 1.0f / sqrtf(t[r] * (1.0f / D) + 1e-5f);
             }
         }
     }
@@ -268,7 +296,10 @@ __device__ __forceinline__ void encoder_ln_body(const float* __restrict__ xp, co
         for (int r = 0; r < 4; ++r) {
             float o[CT];
 #pragma unroll
-            for (int ct = 0; ct < CT; ++ct) o[ct] = (acc[i][ct][r] - mean[i][r]) * rstd[i][r] * g[ct] + be[ct];
+            for (int ct = 0; ct < CT; ++ct) {
+                if constexpr (REFINE) o[ct] = ((acc[i][ct][r] - mean[i][r]) - corr[i][r]) * rstd[i][r] * g[ct] + be[ct];
+                else o[ct] = (acc[i][ct][r] - mean[i][r]) * rstd[i][r] * g[ct] + be[ct];
+            }
             float* dst = Yb + (int64_t)(16 * i + 4 * lg + r) * D + n0;
             if constexpr (CT == 4) *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
             else *reinterpret_cast<float2*>(dst) = make_float2(o[0], o[1]);

@@ -656,6 +656,25 @@ static int launch_core256w(Context* c, bool fuse_db, int64_t B, const float* xp,
     return launch_core256w_kernel(a, fuse_db, B, c->device, st);
 }
 
+// core128_kernel (km_core128.hip), the one-launch core of d_model 128 / 4 heads / decoder hidden 64 at windows 128 and 256 -- the
+// reference's `fast` and `basic` variants.  The streams at these shapes take it; the forward calls take it under option core128
+// (core128_forward_ok) and keep the launch-per-product chain otherwise
+static bool core128_ok(Context* c, bool with_attn) {
+    return c->d == 128 && c->H == 4 && c->NK == 80 && c->DH == 64 && (c->T == 128 || c->T == 256) && !with_attn && !c->opt.no_ln_fusion &&
+           !c->opt.no_score_fusion && !c->opt.no_out_fusion && !c->opt.no_v_fusion && !c->opt.no_core_merge && !c->opt.no_db_fusion &&
+           c->packed.count("qk_pg") && c->packed.count("wce_pg128") && c->packed.count("wv_bg128") && c->packed.count("wf_pg128");
+}
+bool core128_forward_ok(Context* c, bool with_attention) { return c->opt.core128 && !c->opt.generic_staged && core128_ok(c, with_attention); }
+
+static int launch_core128(Context* c, bool fuse_db, int64_t B, const float* xp, int KP, const EncSrc& src, const float* zemo, float* out,
+                          float* raw, hipStream_t st) {
+    float* Y = c->ws.generic;
+    float* S = Y + 2 * B * c->NK * c->d;      // where the chain keeps its scores
+    Core512Args a{xp, dv(c, "wce_pg128"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), S, c->H * 28,
+                  dv(c, "wv_bg128"), dv(c, "wf_pg128"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw};
+    return launch_core128_kernel(a, fuse_db, B, c->device, st);
+}
+
 // d_model -> (waves, column tiles per wave) of the fused encoder + LayerNorm kernel
 template <bool FUSE_DB>
 static int launch_encoder_ln_for(Context* c, int64_t B, hipStream_t st, const float* xp, int KP, const EncSrc& src) {
@@ -681,6 +700,7 @@ int launch_core_generic_packed(Context* c, const float* xp, int64_t B, const flo
     bool ln_done = fuse_ln;
     if (core512_merge_ok(c, attn != nullptr)) return launch_core512<false>(c, B, xp, KP, EncSrc{}, zemo, out, raw, st);
     if (core256w_ok(c, attn != nullptr)) return launch_core256w(c, false, B, xp, KP, EncSrc{}, zemo, out, raw, st);
+    if (core128_forward_ok(c, attn != nullptr)) return launch_core128(c, false, B, xp, KP, EncSrc{}, zemo, out, raw, st);
     if (fuse_ln && (d == 512 || d == 256 || d == 64)) {
         if (int rc = launch_encoder_ln_for<false>(c, B, st, xp, KP, EncSrc{})) return rc;
     } else {
@@ -702,10 +722,16 @@ LogParams plan_log_params(MelPlan* p);
 
 int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_frames, const float* zemo, float* out,
                               float* raw, float* attn, void* stream) {
-    if (!generic_core_takes_power(c)) return fail(KM_ERR_UNSUPPORTED, "no fused encoder for d_model=%d", c->d);
+    const bool core128 = core128_forward_ok(c, attn != nullptr);      // d_model 128 has no encoder_ln_kernel: the power-mel feeds this route alone
+    if (!core128 && !generic_core_takes_power(c)) return fail(KM_ERR_UNSUPPORTED, "no fused encoder for d_model=%d", c->d);
     const int KP = (c->KT + 15) / 16 * 16;
     hipStream_t st = (hipStream_t)stream;
     EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
+    if (core128) {
+        if (int rc = launch_core128(c, true, B, nullptr, KP, src, zemo, out, raw, st)) return rc;
+        c->melmax_dirty = false;
+        return KM_OK;
+    }
     if (core512_merge_ok(c, attn != nullptr)) {
         if (int rc = launch_core512<true>(c, B, nullptr, KP, src, zemo, out, raw, st)) return rc;
         c->melmax_dirty = false;
@@ -725,8 +751,10 @@ int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_fr
 bool core512_stream_ok(Context* c) { return core512_merge_ok(c, false) && generic_core_takes_power(c); }
 // ... and on d_model 256 / 8 heads / window 512 (core256w_stream_kernel)
 bool core256w_stream_ok(Context* c) { return core256w_ok(c, false) && generic_core_takes_power(c); }
-// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or one of the two above
-bool stream_core_ok(Context* c) { return c->fused_ok || core512_stream_ok(c) || core256w_stream_ok(c); }
+// ... and on d_model 128 / 4 heads / window 128 or 256 (core128_stream_kernel; the predicate holds no_db_fusion already)
+bool core128_stream_ok(Context* c) { return core128_ok(c, false); }
+// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or one of the three above
+bool stream_core_ok(Context* c) { return c->fused_ok || core512_stream_ok(c) || core256w_stream_ok(c) || core128_stream_ok(c); }
 
 // km_core_route: the kernel the forward calls take behind the packed image or the power-mel (km_core_forward, km_forward_audio,
 // the generic branch of km_sequence_forward*); host only
@@ -735,6 +763,7 @@ int core_route(Context* c, bool with_attention) {
     if (c->opt.generic_staged) return 3;
     if (core512_merge_ok(c, with_attention)) return 1;
     if (core256w_ok(c, with_attention)) return 2;
+    if (core128_forward_ok(c, with_attention)) return 4;
     return 3;
 }
 
@@ -760,15 +789,17 @@ __global__ __launch_bounds__(kStreamMapThreads) void stream_head_mean_kernel(con
     reinterpret_cast<float4*>(attn)[(int64_t)b * per4 + i] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
 }
 
-// the arguments of a streaming core launch over the rings' power-mel (wv: the value image of the shape's last stage)
+// the arguments of a streaming core launch over the rings' power-mel (wv: the value image of the shape's last stage; wce, wf: the
+// encoder and fold images, under names of their own at d_model 128)
 static Core512StreamArgs stream_core_args(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out,
-                                          const unsigned char* gate, float* raw, const char* wv) {
+                                          const unsigned char* gate, float* raw, const char* wv, const char* wce = "wce_pg",
+                                          const char* wf = "wf_pg") {
     const int KP = (c->KT + 15) / 16 * 16;
     float* Y = c->ws.generic;
     float* Sc = Y + 2 * S * c->NK * c->d;
     const EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
-    return {{nullptr, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), Sc, c->H * 28,
-             dv(c, wv), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw},
+    return {{nullptr, dv(c, wce), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), Sc, c->H * 28,
+             dv(c, wv), dv(c, wf), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw},
             {(int)(c->st.out_frames > 0 ? c->st.out_frames : n_frames), gate ? gate : c->st.ring_ready, c->st.ring_started,
              c->st.ring_state, c->alpha}};
 }
@@ -807,6 +838,15 @@ int launch_core256w_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frame
     if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
     const Core512StreamArgs sa = stream_core_args(c, plan, S, n_frames, zemo, out, gate, raw, "wv_bg32");
     if (int rc = launch_core256w_stream_kernel(sa, S, c->device, (hipStream_t)stream)) return rc;
+    return stream_core_done(c, sa, S, attn, stream);
+}
+
+int launch_core128_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
+                          const unsigned char* gate, float* raw, float* attn) {
+    if (!core128_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
+    if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
+    const Core512StreamArgs sa = stream_core_args(c, plan, S, n_frames, zemo, out, gate, raw, "wv_bg128", "wce_pg128", "wf_pg128");
+    if (int rc = launch_core128_stream_kernel(sa, S, c->device, (hipStream_t)stream)) return rc;
     return stream_core_done(c, sa, S, attn, stream);
 }
 

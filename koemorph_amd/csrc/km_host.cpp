@@ -400,16 +400,45 @@ int finalize_host(Context* c) {
                         }
         put(c, "wv_bg32", std::move(wv_bg32));
     }
+    const bool core128_shape = d == 128 && H == 4 && DH == 64 && c->NK == 80;
+    if (core128_shape) {
+        // the operands of core128_kernel (km_core128_dev.h), four waves, under names of their own: the presence of wce_pg / wv_bg32
+        // keeps meaning what it meant.  Value projection, wave w = head w, two column tiles:
+        // [kb][w][ct][lane][s] = Wv[32 w + 16 ct + j][16 kb + 4 g + s]
+        const int NWv = 4, KBv = d / 16;
+        std::vector<float> wv_bg128((size_t)d * d);
+        for (int kb = 0; kb < KBv; ++kb)
+            for (int w2 = 0; w2 < NWv; ++w2)
+                for (int ct = 0; ct < 2; ++ct)
+                    for (int l = 0; l < 64; ++l)
+                        for (int e = 0; e < 4; ++e) {
+                            const int g = l >> 4, j = l & 15;
+                            wv_bg128[((((size_t)kb * NWv + w2) * 2 + ct) * 64 + l) * 4 + e] =
+                                (float)Wv[(size_t)(32 * w2 + 16 * ct + j) * d + 16 * kb + 4 * g + e];
+                        }
+        put(c, "wv_bg128", std::move(wv_bg128));
+        // decoder[0] fold as A operand, one row tile of 16 hidden units per wave: [w][kb][lane][s] = Wf[16 kb + 4 g + s][16 w + j]
+        // (at DH = 64 wf_pg's two row tiles per group of 32 come to the same bytes; the law is stated for the 16 units a wave folds)
+        std::vector<float> wf_pg128((size_t)d * DH);
+        for (int w = 0; w < NWv; ++w)
+            for (int kb = 0; kb < KBv; ++kb)
+                for (int l = 0; l < 64; ++l)
+                    for (int e = 0; e < 4; ++e) {
+                        const int g = l >> 4, j = l & 15;
+                        wf_pg128[(((size_t)w * KBv + kb) * 64 + l) * 4 + e] = (float)Wf[(size_t)(16 * kb + 4 * g + e) * DH + 16 * w + j];
+                    }
+        put(c, "wf_pg128", std::move(wf_pg128));
+    }
     {   // channel encoder weight with K padded to a multiple of 16 (zeros): rows stay 16-byte aligned and the long
         // and short-term columns form ONE contraction for encoder_tn_kernel (km_generic.hip)
         const int KT = c->KT, KP = (KT + 15) / 16 * 16;
         const std::vector<float>& w = P(c, "mel_channel_encoder.weight");          // (d, KT)
         std::vector<float> wp((size_t)d * KP, 0.0f);
         for (int n = 0; n < d; ++n) std::copy(w.begin() + (size_t)n * KT, w.begin() + (size_t)(n + 1) * KT, wp.begin() + (size_t)n * KP);
-        if (d == 512 || d == 256 || d == 64) {
-            // the same weight as MFMA B-operand image for encoder_ln_kernel<NW, CT> (km_encoder_dev.h): wave w, column tile
-            // ct, lane (g, j) holds column n = 16 CT w + CT j + ct; [k block][w][ct][lane][s] = W[n][16 kb + 4 g + s]
-            const int NWv = d == 64 ? 2 : 8, CT = d / (16 * NWv), KBv = KP / 16;
+        // the same weight as MFMA B-operand image for encoder_ln_body<NW, CT> (km_encoder_dev.h): wave w, column tile
+        // ct, lane (g, j) holds column n = 16 CT w + CT j + ct; [k block][w][ct][lane][s] = W[n][16 kb + 4 g + s]
+        auto operand_image = [&](int NWv) {
+            const int CT = d / (16 * NWv), KBv = KP / 16;
             std::vector<float> pg((size_t)d * KP);
             for (int kb = 0; kb < KBv; ++kb)
                 for (int w2 = 0; w2 < NWv; ++w2)
@@ -419,8 +448,10 @@ int finalize_host(Context* c) {
                                 const int g = l >> 4, j = l & 15, n = 16 * CT * w2 + CT * j + ct;
                                 pg[((((size_t)kb * NWv + w2) * CT + ct) * 64 + l) * 4 + e] = wp[(size_t)n * KP + 16 * kb + 4 * g + e];
                             }
-            put(c, "wce_pg", std::move(pg));
-        }
+            return pg;
+        };
+        if (d == 512 || d == 256 || d == 64) put(c, "wce_pg", operand_image(d == 64 ? 2 : 8));      // encoder_ln_kernel
+        if (core128_shape) put(c, "wce_pg128", operand_image(4));      // <4, 2>: the first stage of core128_kernel
         put(c, "wce_pad", std::move(wp));
     }
     put(c, "bf", to_f(bf));                                        // (DH)
@@ -671,7 +702,7 @@ const OptName kOptNames[] = {
     {"generic_staged", &Options::generic_staged}, {"mel_two_frame", &Options::mel_two_frame},
     {"emotion_separate", &Options::emotion_separate}, {"no_ln_fusion", &Options::no_ln_fusion},
     {"no_db_fusion", &Options::no_db_fusion}, {"no_score_fusion", &Options::no_score_fusion},
-    {"no_out_fusion", &Options::no_out_fusion}, {"no_v_fusion", &Options::no_v_fusion}, {"no_core_merge", &Options::no_core_merge}, {"legacy_no_merge", &Options::legacy_no_merge}, {"kmm_no_fuse", &Options::kmm_no_fuse}, {"legacy_no_attn_fusion", &Options::legacy_no_attn_fusion}, {"legacy_no_enc_fusion", &Options::legacy_no_enc_fusion}, {"legacy_no_tail_fusion", &Options::legacy_no_tail_fusion},
+    {"no_out_fusion", &Options::no_out_fusion}, {"no_v_fusion", &Options::no_v_fusion}, {"no_core_merge", &Options::no_core_merge}, {"core128", &Options::core128}, {"legacy_no_merge", &Options::legacy_no_merge}, {"kmm_no_fuse", &Options::kmm_no_fuse}, {"legacy_no_attn_fusion", &Options::legacy_no_attn_fusion}, {"legacy_no_enc_fusion", &Options::legacy_no_enc_fusion}, {"legacy_no_tail_fusion", &Options::legacy_no_tail_fusion},
     {"train_no_split", &Options::train_no_split}, {"train_tail_groups", &Options::train_tail_groups}, {"train_bm32_below", &Options::train_bm32_below}, {"train_op_per_launch", &Options::train_op_per_launch}, {"train_split_min_k", &Options::train_split_min_k}, {"train_no_dma", &Options::train_no_dma}, {"train_attn_regs", &Options::train_attn_regs}, {"train_no_fe_pack", &Options::train_no_fe_pack}, {"train_colsum_gemm", &Options::train_colsum_gemm}, {"train_no_ln_fuse", &Options::train_no_ln_fuse}, {"train_ln_fuse_rows", &Options::train_ln_fuse_rows}, {"train_no_dy_split", &Options::train_no_dy_split}, {"train_alone_max", &Options::train_alone_max},
 };
 }  // namespace

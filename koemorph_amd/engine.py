@@ -357,7 +357,8 @@ class Engine:
     def core_route(self, with_attention: bool = False) -> int:
         """km_core_route: the core the forward calls run for this shape and its switches, after ``finalize_host`` (host only).
         0 the fused d_model 256 / window 256 core, 1 core512_kernel, 2 core256w_kernel (d_model 256, 8 heads, window 512),
-        3 the launch-per-product chain."""
+        3 the launch-per-product chain, 4 core128_kernel (d_model 128, 4 heads, window 128 or 256, after
+        ``set_option("core128", 1)``; these shapes take 3 by default)."""
         rc = self._lib.km_core_route(self._h, int(bool(with_attention)))
         if rc < 0:
             check(rc)

@@ -1,8 +1,9 @@
 """Many concurrent speaker streams with device-resident state (BASELINE config 5: 1024 streams, 128 per GPU).
 
-Three model shapes have a streaming core: d_model 256 / 8 heads / window 256 (the 30 fps configuration: 8.5 s ring, hop 532),
-d_model 256 / 8 heads / window 512 (what the reference's ``frame_rate=60`` recipe trains) and d_model 512 / 8 or 16 heads / window
-512 (its ``long_context`` variant); the two 60 fps shapes with ``update_interval=1/60``, ring hop 266 and the front end at hop 266.
+Five model shapes have a streaming core -- every variant of the reference's model config: d_model 256 / 8 heads / window 256 (the
+30 fps configuration: 8.5 s ring, hop 532), d_model 128 / 4 heads / window 128 (``fast``) and window 256 (``basic``) on the same ring
+and front end, d_model 256 / 8 heads / window 512 (what the ``frame_rate=60`` recipe trains) and d_model 512 / 8 or 16 heads / window
+512 (``long_context``); the two 60 fps shapes with ``update_interval=1/60``, ring hop 266 and the front end at hop 266.
 Any other shape raises ``KoeMorphError`` from ``tick``.
 
 Each stream owns an 8.5 s audio ring (``MelAudioBuffer`` semantics, reference

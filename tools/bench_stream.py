@@ -4,7 +4,10 @@ Prints ticks/s and p50/p99 tick latency (host wall clock around replay + the 26 
 
 Default: the 30 fps shape (d_model 256, 8 heads, window 256, 533-sample frames).  ``--d-model 512 --heads 8|16 --fps 60``: the 60 fps
 long-context shape (window 512, 8.5 s ring of hop 266, 267-sample frames); ``--d-model 256 --heads 8 --fps 60``: the shape of the
-reference's frame_rate=60 recipe (window 512, same ring), with ``--chunked`` / ``--attention`` that shape alone.  ``--baseline`` adds what a caller had to do at that shape
+reference's frame_rate=60 recipe (window 512, same ring), with ``--chunked`` / ``--attention`` that shape alone;
+``--d-model 128 --heads 4 --window 128|256``: the reference's `fast` / `basic` variants at 30 fps (core128_stream_kernel), again with
+``--chunked`` / ``--attention`` that shape alone, and with ``--baseline`` the two routes interleaved in 15 rounds of one run (medians
+of the rounds, minimum and maximum).  ``--baseline`` adds what a caller had to do at that shape
 before the stream path covered it: rings kept outside the library, unrolled into 128 chronological windows per tick, km_forward_audio
 on them with the EMA state (km_smooth behind the generic core), and the same readback -- timed the same way.
 
@@ -29,8 +32,9 @@ from koemorph_amd.streaming import ChunkedStreamEngine, StreamEngine
 ap = argparse.ArgumentParser()
 ap.add_argument("--streams", type=int, default=128)
 ap.add_argument("--ticks", type=int, default=1000)
-ap.add_argument("--d-model", type=int, default=256, choices=(256, 512))
-ap.add_argument("--heads", type=int, default=8, choices=(8, 16))
+ap.add_argument("--d-model", type=int, default=256, choices=(128, 256, 512))
+ap.add_argument("--heads", type=int, default=8, choices=(4, 8, 16))
+ap.add_argument("--window", type=int, default=None, choices=(128, 256), help="mel_sequence_length at d_model 128 (default 128)")
 ap.add_argument("--fps", type=int, default=30, choices=(30, 60))
 ap.add_argument("--baseline", action="store_true", help="also time host-side rings + forward_audio + EMA per tick")
 ap.add_argument("--attention", action="store_true", help="a replayed chunked tick without maps, with maps, with maps + the masked statistics update")
@@ -40,7 +44,10 @@ S = args.streams
 
 
 def make_engine(d_model, heads, fps):
-    if d_model == 256 and fps == 30:
+    if d_model == 128:         # `fast` (window 128) / `basic` (window 256); emotion_dim 256 at both, as every shape here
+        e = Engine(d_model=128, num_heads=4, mel_sequence_length=args.window)
+        e.load_state_dict(synth.make_core_params(0, 128, args.window)); e.finalize()
+    elif d_model == 256 and fps == 30:
         e = Engine(); e.load_state_dict(synth.make_core_params(0)); e.finalize()
     else:      # window 512 at hop 266: d_model 512 (long context) or d_model 256 / 8 heads (the frame_rate=60 recipe)
         e = Engine(d_model=d_model, num_heads=heads, mel_sequence_length=512, mel=MelConfig.model_batch(target_fps=fps))
@@ -169,15 +176,23 @@ def per_model_route(n_models=8, ticks=60):
 
 if args.d_model == 256 and args.fps == 60 and args.heads != 8:
     ap.error("d_model 256 at 60 fps streams with 8 heads only")
+d128 = args.d_model == 128
+if d128:
+    args.window = args.window or 128
+    if args.heads != 4 or args.fps != 30:
+        ap.error("d_model 128 streams with --heads 4 at 30 fps")
+elif args.window is not None or args.heads == 4:
+    ap.error("--window and --heads 4 go with --d-model 128")
 recipe60 = args.d_model == 256 and args.fps == 60         # the shape of the frame_rate=60 recipe: that shape alone
+one_shape = ((128, 4, 30),) if d128 else ((256, 8, 60),) if recipe60 else None
 if args.attention:
-    for shape in (((256, 8, 60),) if recipe60 else ((256, 8, 30), (512, 8, 60))):
+    for shape in (one_shape or ((256, 8, 30), (512, 8, 60))):
         print(json.dumps(attention_shape(*shape)), flush=True)
     sys.exit(0)
 if args.chunked:
-    for shape in (((256, 8, 60),) if recipe60 else ((256, 8, 30), (512, 8, 60))):
+    for shape in (one_shape or ((256, 8, 30), (512, 8, 60))):
         print(json.dumps(chunked_shape(*shape)), flush=True)
-    if not recipe60:
+    if not one_shape:
         print(json.dumps(per_model_route()), flush=True)
     sys.exit(0)
 eng = make_engine(args.d_model, args.heads, args.fps)
@@ -205,7 +220,7 @@ def timed(step):
 
 
 t_all, lat = timed(lambda t: se.replay(frames[:, (t % 8) * n:(t % 8 + 1) * n], emo))
-shape = f"d_model {args.d_model}, {args.heads} heads, {args.fps} fps"
+shape = f"d_model {args.d_model}, {args.heads} heads, {args.fps} fps" + (f", window {args.window}" if d128 else "")
 res = {"workload": f"C5: {S} streams/GPU ({shape}), one {n}-sample frame per stream per tick, hipGraph replay + D2H of {S}x52 floats",
        "ticks_per_s": round(args.ticks / t_all, 1), "frames_per_s": round(args.ticks * S / t_all, 1),
        "tick_ms_mean": round(t_all / args.ticks * 1e3, 4),
@@ -237,6 +252,25 @@ if args.baseline:
 
     for t in range(20):
         host_rings(t)
+    if d128:       # the two routes interleaved in rounds of one run: the figure of a round is its mean synchronised tick
+        rounds, per_round = 15, max(1, args.ticks // 15)
+        routes = {"stream_replay": lambda t: se.replay(frames[:, (t % 8) * n:(t % 8 + 1) * n], emo), "baseline_forward_audio": host_rings}
+        ms = {k: [] for k in routes}
+        for r in range(rounds + 1):                           # round 0 warms up
+            for k, step in routes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for t in range(per_round):
+                    step(t)
+                    torch.cuda.synchronize()
+                if r:
+                    ms[k].append((time.perf_counter() - t0) / per_round * 1e3)
+        for k, v in ms.items():
+            v = np.asarray(v)
+            res[k + "_interleaved"] = {"tick_ms_median_of_rounds": round(float(np.median(v)), 4), "tick_ms_min": round(float(v.min()), 4),
+                                       "tick_ms_max": round(float(v.max()), 4), "rounds": rounds, "ticks_per_round": per_round}
+        res["stream_not_above_baseline"] = bool(res["stream_replay_interleaved"]["tick_ms_median_of_rounds"] <=
+                                                res["baseline_forward_audio_interleaved"]["tick_ms_median_of_rounds"])
     b_all, b_lat = timed(host_rings)
     res["baseline_forward_audio_tick_ms_mean"] = round(b_all / args.ticks * 1e3, 4)
     res["baseline_forward_audio_tick_ms_p50"] = round(float(np.percentile(b_lat, 50)), 4)
