@@ -751,6 +751,47 @@ int km_emotion_stream_update(void* es, float* emotion_dev, uint8_t* valid_dev, u
 int km_emotion_stream_reset_streams(void* es, const uint8_t* mask_dev, void* stream);
 int km_emotion_stream_features(void* es, float* features_dev, float* slots_dev, void* stream);
 
+/* ---- the `basic` prosodic emotion features: EmotionExtractor._extract_basic on the device ------------------------------
+ * Replaces the librosa calls of EmotionExtractor._extract_basic (src/features/emotion_extractor.py:503-545), which forward runs
+ * once per batch row on the whole audio it was handed (:280-300): for a window y of L >= 1 samples at 16 kHz the nine values
+ * [energy, zcr, spectral_centroid, f0_mean, f0_std, mean, std, max, min], raw, with no normalisation -- np.mean(y ** 2), the means
+ * over frames of librosa.feature.zero_crossing_rate and librosa.feature.spectral_centroid, nanmean / nanstd of
+ * librosa.yin(fmin=50, fmax=400), np.mean / std / max / min.  librosa is a third-party package the reference pins only as
+ * >=0.10.0: the arithmetic is the restatement of its 0.10 defaults (frames of 2048 samples, hop 512, centred: F = 1 + L / 512)
+ * in tests/prosody_cases.py and in the header of km_prosody.hip, and has not been checked against the package (PARITY UNPINNED).
+ * One deliberate deviation: yin's difference function is the direct sum of squared differences, not librosa's FFT
+ * autocorrelation with terms below 1e-6 zeroed; digital silence gives f0 = 400 either way.  Inputs are assumed finite.
+ *   km_prosody_plan_create / _destroy   Hann window and twiddle tables on the device
+ *   km_prosody_num_frames               frames of a window of L samples: 1 + L / 512 (0 for L < 1)
+ *   km_prosody_workspace_floats         floats of caller-owned scratch for B windows of L samples (4 per frame); -1 for B or L < 1
+ *   km_prosody_features                 audio_dev: B rows of L samples, row b at audio_dev + b * row_stride (row_stride >= L) ->
+ *                                       out_dev (B, 9).  frames_dev (B, F, 4) or NULL: the per-frame records (Z_f, C_f, f0_f, i*),
+ *                                       i* the chosen index into yin's 281 candidate periods (period 40 + i*); when given, the
+ *                                       records are written there and work_dev may be NULL.  1 <= L <= 2^20 and 1 <= B <= 65535:
+ *                                       below 1 KM_ERR_INVALID_ARG, above KM_ERR_UNSUPPORTED; a short workspace KM_ERR_WORKSPACE
+ *   km_prosody_windows                  W windows of a resident clip: window w covers clip_dev[s, s + L) with s =
+ *                                       start_samples_dev[w] (int32, on the device), shortened ON THE DEVICE to what the clip
+ *                                       holds -> out_dev (W, 9), each row what km_prosody_features gives on the shortened window,
+ *                                       bit for bit.  A window that holds nothing (s < 0 or s >= clip_len) writes a zero row.
+ *                                       Limits of W and L as for B and L above; 1 <= clip_len < 2^31
+ * Neither call allocates, synchronises or reads anything back; every sum has a fixed order that depends on L only, so a window
+ * gives the same bits wherever it lies (dense row, clip, stream ring). */
+int km_prosody_plan_create(void** plan_out);
+int km_prosody_plan_destroy(void* plan);
+int64_t km_prosody_num_frames(int64_t L);
+int64_t km_prosody_workspace_floats(int64_t B, int64_t L);
+int km_prosody_features(void* plan, const float* audio_dev, int64_t B, int64_t L, int64_t row_stride, float* work_dev, int64_t work_floats,
+                        float* out_dev, float* frames_dev, void* stream);
+int km_prosody_windows(void* plan, const float* clip_dev, int64_t clip_len, const int32_t* start_samples_dev, int64_t W, int64_t L,
+                       float* work_dev, int64_t work_floats, float* out_dev, void* stream);
+/* The emotion-stream object above in a second back end: the same rings, push, eligibility and selection rule, reset and capture
+ * contract, but a selected stream's features are the nine values above of its window (km_prosody_features' kernels, reading the
+ * ring in place), raw: no peak normalisation, no window slots, no compression layer.  The window may hold up to 2^20 samples
+ * (KM_ERR_UNSUPPORTED beyond).  On such an object km_emotion_stream_update writes emotion_dev (n_streams, 9),
+ * km_emotion_stream_features writes features_dev (n_streams, 9) and refuses a non-NULL slots_dev (KM_ERR_INVALID_ARG), and
+ * km_emotion_stream_set_compression returns KM_ERR_INVALID_ARG; no call is needed before the first update. */
+int km_emotion_stream_create_basic(void** es, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates);
+
 /* ---- the emotion track of a resident clip: the offline producer of the model's emotion input ---------------------
  * What ONE emotion stream (above) holds after t samples of a clip, for every update time at once.  With SR, R, C, U and MIN as
  * km_emotion_stream_create computes them, a clip of n samples has K rows: K = 0 if n < MIN, else (n - MIN) / U + 1.  Row k

@@ -223,6 +223,13 @@ SIGNATURES = {
     "km_emotion_stream_update": (C.c_int, [_p, _p, _p, _p, _p]),
     "km_emotion_stream_reset_streams": (C.c_int, [_p, _p, _p]),
     "km_emotion_stream_features": (C.c_int, [_p, _p, _p, _p]),
+    "km_emotion_stream_create_basic": (C.c_int, [C.POINTER(_p), _i64, C.c_double, C.c_double, _i64]),
+    "km_prosody_plan_create": (C.c_int, [C.POINTER(_p)]),
+    "km_prosody_plan_destroy": (C.c_int, [_p]),
+    "km_prosody_num_frames": (_i64, [_i64]),
+    "km_prosody_workspace_floats": (_i64, [_i64, _i64]),
+    "km_prosody_features": (C.c_int, [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p]),
+    "km_prosody_windows": (C.c_int, [_p, _p, _i64, _p, _i64, _i64, _p, _i64, _p, _p]),
     "km_emotion_clip_create": (C.c_int, [C.POINTER(_p), C.c_double, C.c_double, _i64]),
     "km_emotion_clip_destroy": (C.c_int, [_p]),
     "km_emotion_clip_set_compression": (C.c_int, [_p, _p, _p, _p]),

@@ -8,6 +8,10 @@
 //   get_concatenated_features                :559-608   es_epilogue_kernel: Linear(264, 256) of current | slot 300 | slot 600
 //   reset                                    :640-659   es_reset_kernel, per stream
 //
+// A second back end on the same rings, push, selection, reset and capture contract (km_emotion_stream_create_basic): a selected
+// stream's features are the nine raw values of EmotionExtractor._extract_basic on its window (km_prosody.hip over the same slot
+// table), kept in the first 9 of the stream's 88 feature floats; no peak normalisation, no slots, no Linear(264, 256).
+//
 // Time is audio time: a stream is due when `update_samples` samples have arrived since its last update (the reference asks
 // time.time()), so every result is a function of the call sequence.  Nothing here allocates, synchronises or reads back after
 // creation and every grid is fixed by (n_streams, max_updates): push + update capture into a hipGraph as one linear chain.
@@ -20,6 +24,7 @@
 
 #include "km_context.h"
 #include "km_egemaps_ragged.h"
+#include "km_prosody_ragged.h"
 
 namespace km {
 
@@ -27,6 +32,7 @@ namespace km {
 namespace es {
 constexpr int SR = 16000, NFEAT = 88, NCAT = 3 * NFEAT, NEMO = 256, REC = 36, MAXF = 2048;
 constexpr int SEL_THREADS = 1024, MAX_STREAMS = 4096;   // the selection ranks all streams in one workgroup, waiting times in LDS
+constexpr int NBASIC = 9, BASIC_REC = 4, BASIC_HOP = 512, BASIC_MAX_WINDOW = 1 << 20;   // the `basic` back end (km_prosody.hip)
 }  // namespace es
 
 // per-stream counters (arrays of n_streams)
@@ -57,7 +63,9 @@ struct EmotionStream {
     float* wt = nullptr;       // (264, 256): the compression weight transposed
     float* bias = nullptr;     // (256)
     bool has_compression = false;
-    ~EmotionStream() { (void)km_egemaps_plan_destroy(plan); }
+    bool basic = false;        // the `basic` back end: features holds 9 values per stream (row stride 88), no slots, no emotion layer
+    void* prosody = nullptr;
+    ~EmotionStream() { (void)km_egemaps_plan_destroy(plan); (void)km_prosody_plan_destroy(prosody); }
 };
 
 // ---- AudioBuffer.append (:63-96) ----
@@ -155,6 +163,29 @@ __global__ __launch_bounds__(256) void es_output_kernel(int n, const float* __re
     }
 }
 
+// ---- the `basic` back end: the nine values of a selected stream's window are its features as they are ----
+__global__ __launch_bounds__(64) void es_basic_epilogue_kernel(const EgmSlot* __restrict__ table, const float* __restrict__ fout, EsState st,
+                                                               float* __restrict__ features) {
+    using namespace es;
+    const EgmSlot sl = table[blockIdx.x];
+    if (sl.stream < 0) return;
+    const int s = sl.stream, tid = threadIdx.x;
+    if (tid < NBASIC) features[(int64_t)s * NFEAT + tid] = fout[(int64_t)blockIdx.x * NBASIC + tid];
+    if (tid == 0) { st.last_total[s] = st.total[s]; st.has_features[s] = 1; }
+}
+
+__global__ __launch_bounds__(256) void es_basic_output_kernel(int n, const float* __restrict__ features, const int32_t* __restrict__ has_features,
+                                                              const uint8_t* __restrict__ updated, float* __restrict__ emotion_out,
+                                                              uint8_t* __restrict__ valid_out, uint8_t* __restrict__ updated_out) {
+    using namespace es;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (int64_t)n * NBASIC) emotion_out[i] = features[(i / NBASIC) * NFEAT + i % NBASIC];
+    if (i < n) {
+        if (valid_out) valid_out[i] = has_features[i] ? 1 : 0;
+        if (updated_out) updated_out[i] = updated[i];
+    }
+}
+
 // ---- OpenSMILEeGeMAPSExtractor.reset, per stream ----
 __global__ __launch_bounds__(256) void es_reset_kernel(const uint8_t* __restrict__ mask, float* __restrict__ ring, int ring_len, EsState st,
                                                        float* __restrict__ features, float* __restrict__ slots, float* __restrict__ emotion,
@@ -181,13 +212,7 @@ __global__ __launch_bounds__(256) void es_transpose_kernel(const float* __restri
 
 static int64_t align16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
 
-}  // namespace km
-
-using namespace km;
-
-extern "C" {
-
-int km_emotion_stream_create(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates) {
+static int es_create(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates, bool basic) {
     using namespace es;
     if (!es_out) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: NULL argument");
     *es_out = nullptr;
@@ -201,14 +226,18 @@ int km_emotion_stream_create(void** es_out, int64_t n_streams, double context_wi
     if (context_window_s > 3600.0) return fail(KM_ERR_UNSUPPORTED, "km_emotion_stream_create: context window of %g s", context_window_s);
     const int64_t R = (int64_t)((context_window_s + 2.0) * SR), Cw = (int64_t)(context_window_s * SR);
     const int64_t C = Cw < R ? Cw : R, U = (int64_t)(update_interval_s * SR), MIN = (int64_t)(0.5 * SR);
-    const int64_t nf = km_egemaps_num_frames(C);
-    if (nf > MAXF)
+    const int64_t nf = basic ? 1 + C / BASIC_HOP : km_egemaps_num_frames(C);          // frame records per window
+    const int64_t rec = basic ? BASIC_REC : REC, nout = basic ? NBASIC : NFEAT;
+    if (basic && C > BASIC_MAX_WINDOW)
+        return fail(KM_ERR_UNSUPPORTED, "km_emotion_stream_create: a window of %lld samples, at most %d (65.5 s)", (long long)C, BASIC_MAX_WINDOW);
+    if (!basic && nf > MAXF)
         return fail(KM_ERR_UNSUPPORTED, "km_emotion_stream_create: %lld frames per window, at most %d (20.5 s)", (long long)nf, MAXF);
     std::unique_ptr<EmotionStream> e(new (std::nothrow) EmotionStream());
     if (!e) return fail(KM_ERR_HIP, "km_emotion_stream_create: out of host memory");
     e->n = n_streams; e->max_updates = max_updates;
     e->ring_len = (int)R; e->window_len = (int)C; e->update_samples = (int)U; e->min_samples = (int)MIN; e->max_nf = (int)nf;
-    if (const int rc = km_egemaps_plan_create(&e->plan)) return rc;
+    e->basic = basic;
+    if (const int rc = basic ? km_prosody_plan_create(&e->prosody) : km_egemaps_plan_create(&e->plan)) return rc;
     const int64_t n = n_streams, mu = max_updates;
     // one allocation; `carve` hands out 16-byte aligned pieces, first with a null base to learn the size, then for real
     auto layout = [&](char* base) {
@@ -221,7 +250,7 @@ int km_emotion_stream_create(void** es_out, int64_t n_streams, double context_wi
         e->features = reinterpret_cast<float*>(carve(n * NFEAT * 4)); e->slots = reinterpret_cast<float*>(carve(n * 2 * NFEAT * 4));
         e->emotion = reinterpret_cast<float*>(carve(n * NEMO * 4)); e->updated = reinterpret_cast<uint8_t*>(carve(n));
         e->table = reinterpret_cast<EgmSlot*>(carve(mu * (int64_t)sizeof(EgmSlot))); e->scale = reinterpret_cast<float*>(carve(mu * 4));
-        e->rec = reinterpret_cast<float*>(carve(mu * nf * REC * 4)); e->fout = reinterpret_cast<float*>(carve(mu * NFEAT * 4));
+        e->rec = reinterpret_cast<float*>(carve(mu * nf * rec * 4)); e->fout = reinterpret_cast<float*>(carve(mu * nout * 4));
         e->wt = reinterpret_cast<float*>(carve((int64_t)NCAT * NEMO * 4)); e->bias = reinterpret_cast<float*>(carve(NEMO * 4));
         return at;
     };
@@ -234,6 +263,20 @@ int km_emotion_stream_create(void** es_out, int64_t n_streams, double context_wi
     return KM_OK;
 }
 
+}  // namespace km
+
+using namespace km;
+
+extern "C" {
+
+int km_emotion_stream_create(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates) {
+    return es_create(es_out, n_streams, context_window_s, update_interval_s, max_updates, false);
+}
+
+int km_emotion_stream_create_basic(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates) {
+    return es_create(es_out, n_streams, context_window_s, update_interval_s, max_updates, true);
+}
+
 int km_emotion_stream_destroy(void* es) {
     if (!es) return KM_OK;
     delete static_cast<EmotionStream*>(es);
@@ -243,6 +286,7 @@ int km_emotion_stream_destroy(void* es) {
 int km_emotion_stream_set_compression(void* es, const float* w_dev, const float* b_dev, void* stream) {
     if (!es || !w_dev || !b_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_set_compression: NULL argument");
     EmotionStream* e = static_cast<EmotionStream*>(es);
+    if (e->basic) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_set_compression: the basic back end has no compression layer");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(es_transpose_kernel, dim3((es::NEMO * es::NCAT + 255) / 256), dim3(256), 0, st, w_dev, e->wt);
     HIP_TRY(hipGetLastError());
@@ -268,11 +312,20 @@ int km_emotion_stream_push(void* es, const float* samples_dev, int64_t n_per_str
 int km_emotion_stream_update(void* es, float* emotion_dev, uint8_t* valid_dev, uint8_t* updated_dev, void* stream) {
     if (!es || !emotion_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_update: NULL argument");
     EmotionStream* e = static_cast<EmotionStream*>(es);
-    if (!e->has_compression) return fail(KM_ERR_NOT_READY, "km_emotion_stream_update: km_emotion_stream_set_compression first");
+    if (!e->basic && !e->has_compression) return fail(KM_ERR_NOT_READY, "km_emotion_stream_update: km_emotion_stream_set_compression first");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(es_select_kernel, dim3(1), dim3(es::SEL_THREADS), 0, st, (int)e->n, (int)e->max_updates, e->ring_len, e->window_len,
                        e->update_samples, e->min_samples, e->st, e->table, e->updated);
     HIP_TRY(hipGetLastError());
+    if (e->basic) {
+        if (const int rc = prosody_ragged(e->prosody, e->ring, e->ring_len, e->table, (int)e->max_updates, e->max_nf, e->rec, e->fout, st)) return rc;
+        hipLaunchKernelGGL(es_basic_epilogue_kernel, dim3((unsigned)e->max_updates), dim3(64), 0, st, (const EgmSlot*)e->table, (const float*)e->fout,
+                           e->st, e->features);
+        hipLaunchKernelGGL(es_basic_output_kernel, dim3((unsigned)((e->n * es::NBASIC + 255) / 256)), dim3(256), 0, st, (int)e->n,
+                           (const float*)e->features, (const int32_t*)e->st.has_features, (const uint8_t*)e->updated, emotion_dev, valid_dev, updated_dev);
+        HIP_TRY(hipGetLastError());
+        return KM_OK;
+    }
     if (const int rc = egm_ragged_functionals(e->plan, e->ring, e->ring_len, e->table, (int)e->max_updates, e->max_nf, e->scale, e->rec, e->fout, st))
         return rc;
     hipLaunchKernelGGL(es_epilogue_kernel, dim3((unsigned)e->max_updates), dim3(256), 0, st, (const EgmSlot*)e->table, (const float*)e->fout, e->st,
@@ -296,6 +349,14 @@ int km_emotion_stream_reset_streams(void* es, const uint8_t* mask_dev, void* str
 int km_emotion_stream_features(void* es, float* features_dev, float* slots_dev, void* stream) {
     if (!es || !features_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_features: NULL argument");
     EmotionStream* e = static_cast<EmotionStream*>(es);
+    if (e->basic) {
+        if (slots_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_features: the basic back end has no window slots");
+        hipLaunchKernelGGL(es_basic_output_kernel, dim3((unsigned)((e->n * es::NBASIC + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)e->n,
+                           (const float*)e->features, (const int32_t*)e->st.has_features, (const uint8_t*)e->updated, features_dev,
+                           (uint8_t*)nullptr, (uint8_t*)nullptr);
+        HIP_TRY(hipGetLastError());
+        return KM_OK;
+    }
     HIP_TRY(hipMemcpyAsync(features_dev, e->features, (size_t)e->n * es::NFEAT * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (slots_dev)
         HIP_TRY(hipMemcpyAsync(slots_dev, e->slots, (size_t)e->n * 2 * es::NFEAT * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));

@@ -9,6 +9,9 @@ __all__ += ["AudioBuffer", "OpenSMILEeGeMAPSExtractor", "create_opensmile_extrac
 from .clip_emotion import ClipEmotion  # noqa: E402
 
 __all__ += ["ClipEmotion"]
+from .basic_emotion import BasicEmotion  # noqa: E402
+
+__all__ += ["BasicEmotion"]
 from .resample import Resampler, StreamPlan, resample_filter, resample_ratio  # noqa: E402
 
 __all__ += ["Resampler", "StreamPlan", "resample_filter", "resample_ratio"]

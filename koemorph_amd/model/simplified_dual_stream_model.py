@@ -12,14 +12,17 @@ through the C-ABI; there is no CPU path.
 Emotion features.  In the reference the 256-D vector comes from openSMILE eGeMAPS / emotion2vec
 (third-party CPU libraries that also fetch models; SURVEY.md section 2 marks them out of scope).
 Here it is an INPUT: pass ``emotion_features=`` to ``forward`` or install an ``emotion_provider``
-callable ``(audio (B, L) tensor) -> (B, emotion_dim) tensor``.  Without either, the model does
+callable ``(audio (B, L) tensor) -> (B, emotion_dim) tensor``.  ``emotion_provider="basic"`` (with
+``emotion_config={"backend": "basic"}``, emotion_dim 9) is the one producer that needs nothing from
+outside: the reference's ``EmotionExtractor._extract_basic`` on the device
+(``koemorph_amd.features.BasicEmotion``, built on first use).  Without either, the model does
 what the reference does when extraction fails (simplified_dual_stream_model.py:250-267): it logs
 a warning and uses ``randn * 0.1`` dummy features.
 """
 from __future__ import annotations
 
 import logging
-from typing import Any, Callable, Dict, Optional, Tuple
+from typing import Any, Callable, Dict, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -46,7 +49,7 @@ class SimplifiedDualStreamModel(nn.Module):
         mel_config: Optional[Dict] = None,
         device: str = "cuda",
         real_time_mode: bool = False,
-        emotion_provider: Optional[EmotionProvider] = None,
+        emotion_provider: Optional[Union[EmotionProvider, str]] = None,
     ):
         super().__init__()
         self.d_model = d_model
@@ -73,7 +76,13 @@ class SimplifiedDualStreamModel(nn.Module):
             self.emotion_dim = 9
         else:                                                # opensmile, concatenated 3x88 -> 256 (production)
             self.emotion_dim = 256
+        if isinstance(emotion_provider, str):
+            if emotion_provider != "basic":
+                raise ValueError(f"emotion_provider: a callable or 'basic', got {emotion_provider!r}")
+            if self.emotion_dim != 9:
+                raise ValueError(f"emotion_provider='basic' produces 9 features, the model's emotion_dim is {self.emotion_dim}")
         self.emotion_provider = emotion_provider
+        self._basic_provider = None
 
         mel_config = dict(mel_config or {})
         self.mel_context_window = mel_config.get("context_window", 8.5)
@@ -115,7 +124,16 @@ class SimplifiedDualStreamModel(nn.Module):
         """audio (B, T) -> (long (B, T_mel, 80), short (B, 3, 80))   (reference :166-229)."""
         return self.dual_stream_attention.engine().mel_batch(audio)
 
+    def _basic_emotion(self, device: torch.device):
+        """The ``BasicEmotion`` behind ``emotion_provider="basic"``, built on first use on the audio's device."""
+        if self._basic_provider is None or self._basic_provider.device != device:
+            from ..features.basic_emotion import BasicEmotion
+            self._basic_provider = BasicEmotion(device)
+        return self._basic_provider
+
     def extract_emotion_features(self, audio: torch.Tensor) -> Tuple[torch.Tensor, Dict]:
+        if isinstance(self.emotion_provider, str):                             # "basic", checked by the constructor
+            return self._basic_emotion(audio.device)(audio), {"backend_used": "basic"}
         if self.emotion_provider is not None:
             feats = self.emotion_provider(audio)
             feats = torch.as_tensor(feats, dtype=torch.float32, device=audio.device)

@@ -383,12 +383,17 @@ class LegacyStreamEngine:
         return self.out, self.ready
 
 
-def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 0.3, sample_rate: int = 16000) -> dict:
+def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 0.3, sample_rate: int = 16000,
+                         backend: str = "egemaps") -> dict:
     """The arithmetic of the reference's OpenSMILEeGeMAPSExtractor in samples, which km_emotion_stream_create follows: the
     AudioBuffer of ``context_window + 2`` seconds (opensmile_extractor.py:245-248), the window ``get_window(context_window)`` returns
     once that much audio has arrived, the samples between two updates of a stream, the half second below which nothing is extracted
     (:388-389) and the 10 ms frames of a full window.  ValueError where km_emotion_stream_create refuses: the constructor's own
-    checks (:204-209) and a window of more than 2048 frames (20.5 s), which the functionals kernel cannot hold."""
+    checks (:204-209) and a window of more than 2048 frames (20.5 s), which the functionals kernel cannot hold.
+    ``backend="basic"`` (km_emotion_stream_create_basic): the same rings and rule; ``max_frames`` counts the 32 ms frames of the
+    prosodic features, ``1 + window_len // 512``, and the window may hold up to 2**20 samples (65.5 s)."""
+    if backend not in ("egemaps", "basic"):
+        raise ValueError(f"backend must be 'egemaps' or 'basic', got {backend!r}")
     if sample_rate != 16000:
         raise ValueError("the GPU eGeMAPS extractor is built for 16 kHz audio")
     if not context_window >= 1.0:
@@ -399,9 +404,14 @@ def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 
         raise ValueError("Update interval cannot be larger than context window")
     ring_len = int((context_window + 2.0) * sample_rate)
     window_len = min(int(context_window * sample_rate), ring_len)
-    max_frames = (window_len - 960) // 160 + 1
-    if max_frames > 2048:
-        raise ValueError(f"{max_frames} frames per window, at most 2048 (20.5 s)")
+    if backend == "basic":
+        max_frames = 1 + window_len // 512
+        if window_len > 1 << 20:
+            raise ValueError(f"a window of {window_len} samples, at most {1 << 20} (65.5 s)")
+    else:
+        max_frames = (window_len - 960) // 160 + 1
+        if max_frames > 2048:
+            raise ValueError(f"{max_frames} frames per window, at most 2048 (20.5 s)")
     return dict(ring_len=ring_len, window_len=window_len, update_samples=int(update_interval * sample_rate),
                 min_samples=int(0.5 * sample_rate), max_frames=max_frames)
 
@@ -416,11 +426,20 @@ class StreamEmotion:
     audio has no features (the reference would extract the zeros of an empty buffer).  Neither call allocates or synchronises.
 
     ``compression_layer``: a ``torch.nn.Linear(264, 256)``; created with torch's default initialisation when absent, as the
-    reference does on first use (:589-591).  Its weights are copied at construction."""
+    reference does on first use (:589-591).  Its weights are copied at construction.
+
+    ``backend="basic"`` (km_emotion_stream_create_basic): the same rings, update rule, reset and capture contract, but a selected
+    stream's row is the nine raw prosodic values of its window -- bit for bit ``BasicEmotion()(window[None])[0]``
+    (koemorph_amd.features.basic_emotion: EmotionExtractor._extract_basic).  ``emotion`` and ``features`` are ``(n_streams, 9)``,
+    the input of a model with ``emotion_dim`` 9; there is no peak normalisation, no slots (``slots`` raises) and no compression
+    layer (passing one raises ``ValueError``)."""
 
     def __init__(self, n_streams: int, context_window: float = 20.0, update_interval: float = 0.3, max_updates: Optional[int] = None,
-                 compression_layer: Optional[torch.nn.Module] = None, device="cuda"):
-        self.shape = emotion_stream_shape(context_window, update_interval)
+                 compression_layer: Optional[torch.nn.Module] = None, device="cuda", backend: str = "egemaps"):
+        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend)
+        self.backend = backend
+        if backend == "basic" and compression_layer is not None:
+            raise ValueError("the basic back end has no compression layer: its nine features are the emotion input as they are")
         if max_updates is None:
             max_updates = n_streams
         if n_streams < 1 or not 1 <= max_updates <= n_streams:
@@ -434,19 +453,26 @@ class StreamEmotion:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._lib = _lib.load()
-        if compression_layer is None:
-            compression_layer = torch.nn.Linear(264, 256)
-        if tuple(compression_layer.weight.shape) != (256, 264):
-            raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
-        self.compression_layer = compression_layer
         self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            check(self._lib.km_emotion_stream_create(C.byref(self._h), n_streams, context_window, update_interval, max_updates))
-            w = compression_layer.weight.detach().to(self.device, torch.float32).contiguous()
-            b = compression_layer.bias.detach().to(self.device, torch.float32).contiguous()
-            check(self._lib.km_emotion_stream_set_compression(self._h, _ptr(w), _ptr(b), _stream_ptr(self.device)))
-            torch.cuda.current_stream(self.device).synchronize()          # w and b may go once the copy is done
-        self.emotion = torch.zeros(n_streams, 256, device=self.device)
+        if backend == "basic":
+            self.compression_layer = None
+            self.emotion_dim = self.feature_dim = 9
+            with torch.cuda.device(self.device):
+                check(self._lib.km_emotion_stream_create_basic(C.byref(self._h), n_streams, context_window, update_interval, max_updates))
+        else:
+            if compression_layer is None:
+                compression_layer = torch.nn.Linear(264, 256)
+            if tuple(compression_layer.weight.shape) != (256, 264):
+                raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
+            self.compression_layer = compression_layer
+            self.emotion_dim, self.feature_dim = 256, 88
+            with torch.cuda.device(self.device):
+                check(self._lib.km_emotion_stream_create(C.byref(self._h), n_streams, context_window, update_interval, max_updates))
+                w = compression_layer.weight.detach().to(self.device, torch.float32).contiguous()
+                b = compression_layer.bias.detach().to(self.device, torch.float32).contiguous()
+                check(self._lib.km_emotion_stream_set_compression(self._h, _ptr(w), _ptr(b), _stream_ptr(self.device)))
+                torch.cuda.current_stream(self.device).synchronize()          # w and b may go once the copy is done
+        self.emotion = torch.zeros(n_streams, self.emotion_dim, device=self.device)
         self.valid = torch.zeros(n_streams, dtype=torch.uint8, device=self.device)
         self.updated = torch.zeros(n_streams, dtype=torch.uint8, device=self.device)
         self._graph = None
@@ -475,7 +501,7 @@ class StreamEmotion:
                                                _ptr(counts.contiguous()) if counts is not None else None, _stream_ptr(samples.device)))
 
     def update(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """-> (emotion (n_streams, 256), updated (n_streams) uint8); ``valid`` says which streams have features at all.  Rows of
+        """-> (emotion (n_streams, 256) -- (n_streams, 9) on the basic back end --, updated (n_streams) uint8); ``valid`` says which streams have features at all.  Rows of
         streams that were not selected keep what they held; a stream that never had features has a zero row."""
         check(self._lib.km_emotion_stream_update(self._h, _ptr(self.emotion), _ptr(self.valid), _ptr(self.updated),
                                                  _stream_ptr(self.device)))
@@ -483,14 +509,17 @@ class StreamEmotion:
 
     @property
     def features(self) -> torch.Tensor:
-        """(n_streams, 88): every stream's current eGeMAPS functionals (zero before its first update); a copy."""
-        out = torch.empty(self.n_streams, 88, device=self.device)
+        """(n_streams, 88): every stream's current eGeMAPS functionals (zero before its first update); a copy.  (n_streams, 9) on
+        the basic back end."""
+        out = torch.empty(self.n_streams, self.feature_dim, device=self.device)
         check(self._lib.km_emotion_stream_features(self._h, _ptr(out), None, _stream_ptr(self.device)))
         return out
 
     @property
     def slots(self) -> torch.Tensor:
         """(n_streams, 2, 88): the 300 ms and 600 ms window slots, i.e. the first features of each stream's current life; a copy."""
+        if self.backend == "basic":
+            raise AttributeError("the basic back end has no window slots")
         feats = torch.empty(self.n_streams, 88, device=self.device)
         out = torch.empty(self.n_streams, 2, 88, device=self.device)
         check(self._lib.km_emotion_stream_features(self._h, _ptr(feats), _ptr(out), _stream_ptr(self.device)))
