@@ -978,7 +978,8 @@ int km_resample_clip(void* rs, const float* clip_dev, int64_t n_in, float* out_d
  * Replaces what would be module attributes / environment switches on the reference side (the reference has none on
  * this path: every switch selects between two implementations of the SAME arithmetic, for A/B timing and for the
  * tests that pin one path against the other).  Names: "core_split" (0 | 3 | 6, experimental split-bf16 core),
- * "seq_per_window", "generic_staged", "mel_two_frame", "emotion_separate", "no_ln_fusion", "no_db_fusion",
+ * "seq_per_window", "seq_assemble" (default 0; 1: sequence mode shares each clip's STFT frames at every shape and hop whose forward
+ * call has a power path, assembling the windows into the workspace: km_sequence_plan route 2), "generic_staged", "mel_two_frame", "emotion_separate", "no_ln_fusion", "no_db_fusion",
  * "no_score_fusion", "no_out_fusion", "no_v_fusion",
  * "no_core_merge" (the one-launch cores of d_model 512 and of d_model 256 / window 512 as the launches they replaced: km_core_route),
  * "core128" (default 0; 1: the forward calls at d_model 128 / 4 heads / window 128 or 256 run core128_kernel, route 4, instead of the
@@ -1006,6 +1007,17 @@ int km_debug_buffer(km_handle h, const char* name, float* out, int64_t* n);
  * 256, 80 channels -- the `fast` and `basic` variants -- with option core128 set; the default there is 3).  A call that asks for the
  * map takes 3 at every generic shape.  Negative: an error code. */
 int km_core_route(km_handle h, int32_t with_attention);
+/* The schedule km_sequence_forward / _track / _attn run for B clips of L samples at stride_frames, for the handle's shape, front end
+ * and switches as they stand (with_attention != 0: the call asks for maps or brings an accumulator).  Host only, valid after
+ * km_finalize_host; nothing is launched or allocated.  out[0] route: 0 per window (every window's T + 1 STFT frames); 1 the clip's
+ * STFT once + two boundary frames per window, both images read by the fused core (the fused shape with hop >= n_fft / 2, zero
+ * padding); 2 the clip's STFT once + the edge frames of every window, assembled per tile into the front end's workspace for the
+ * core behind km_forward_audio's power path (option "seq_assemble", any hop, the fused shape and every generic shape whose forward
+ * call has a power path; zero padding, clips of at least one window).  out[1] N = km_sequence_num_outputs.  out[2] the STFT frames
+ * the call's front-end launches compute in total, discarded rows included: B N (T + 1) on route 0, B (nfc + 2 N) on route 1 and
+ * B (nfc + 3 E N) on route 2, nfc = (N - 1) stride_frames + T + 1.  out[3] E = ceil((n_fft / 2) / hop): the frames at either end of
+ * a window that see its zero padding.  KM_ERR_INVALID_ARG: NULL argument, B, L or stride_frames <= 0. */
+int km_sequence_plan(km_handle h, int64_t B, int64_t L, int32_t stride_frames, int32_t with_attention, int64_t out[4]);
 
 /* ---- window producer for sequence training -------------------------------------------------------------
  * Replaces the per-window host slicing + H2D copies of KoeMorphSequentialDataset (src/data/sequential_dataset.py:

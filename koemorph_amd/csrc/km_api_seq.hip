@@ -23,6 +23,61 @@ int64_t km_sequence_num_outputs(km_handle h, int64_t L, int32_t stride_frames) {
     return nn > 1 ? nn : 1;
 }
 
+}  // extern "C"
+
+// The schedule of a sequence call (km_sequence_plan names it; sequence_forward runs it).  Host arithmetic on the handle's shape,
+// its front-end plan and its switches alone, so the query and the call cannot disagree.
+//   route 0  per window: every window's T + 1 STFT frames
+//   route 1  the clip's STFT once + frames 0 and T of every window, both images read by the fused core (which takes frames 0 and
+//            T alone from the edge image: right only where no other frame sees the window's padding, clip_frames_shared)
+//   route 2  option seq_assemble: the clip's STFT once + the E frames at either end of every window that see its padding
+//            (E = ceil((n_fft / 2) / hop), koemorph_amd/clip_span.py::edge_frames), assembled per tile into the workspace the core
+//            behind km_forward_audio's power path reads (km_seq_assemble.hip)
+struct SeqPlan { int route, E; int64_t N, nfc, stft_frames; };
+
+// mel_rp_ok as the host knows it before the plan is uploaded (upload_mel_plan mirrors the grouped filter image whenever it exists)
+static bool mel_rp_planned(Context* c, MelPlan* p) { return p->cfg.n_fft == 1024 && !c->opt.mel_two_frame && !p->fbg_gid.empty(); }
+
+static SeqPlan seq_plan(km_handle h, int64_t B, int64_t L, int32_t stride_frames, bool with_attention) {
+    Context* c = h;
+    MelPlan* plan = c->mel_plans[0];
+    const km_mel_config& m = plan->cfg;
+    const int64_t hop = m.hop_length, n_frames = (int64_t)c->T + 1, lim = (int64_t)1 << 31;
+    SeqPlan p{};
+    p.N = km_sequence_num_outputs(h, L, stride_frames);
+    p.E = (int)((m.n_fft / 2 + hop - 1) / hop);
+    p.nfc = (p.N - 1) * stride_frames + n_frames;                                // clip frames any window touches
+    const bool rp = mel_rp_planned(c, plan), dedup = !c->opt.seq_per_window;     // seq_per_window: tests compare the schedules
+    const bool sizes_ok = B < lim && p.N < lim && p.nfc < lim;                   // (the products below then fit 64 bits)
+    const int64_t total = sizes_ok ? B * p.N : 0;
+    // the power path of km_forward_audio (forward_audio in km_api.hip): the fused core, or a generic core that converts to dB itself
+    const bool power = c->fused_ok || ((generic_core_takes_power(c) || core128_forward_ok(c, with_attention)) && !c->opt.generic_staged);
+    if (c->opt.seq_assemble && dedup && power && rp && m.pad_mode == KM_PAD_CONSTANT && c->NK % 4 == 0 && n_frames >= 2 * p.E &&
+        L >= (int64_t)c->T * hop && sizes_ok && B * p.nfc < lim / c->NK && total * 3 * p.E < lim / c->NK) {
+        p.route = 2;
+        p.stft_frames = B * p.nfc + total * 3 * p.E;         // per window E left-edge rows and E launches of 2 rows (row 0 discarded)
+    } else if (c->fused_ok && dedup && rp && clip_frames_shared(c, plan) && p.N < (1 << 24)) {
+        p.route = 1;
+        p.stft_frames = B * (p.nfc + 2 * p.N);
+    } else {
+        p.route = 0;
+        p.stft_frames = B * p.N * n_frames;
+    }
+    return p;
+}
+
+extern "C" {
+
+int km_sequence_plan(km_handle h, int64_t B, int64_t L, int32_t stride_frames, int32_t with_attention, int64_t out[4]) {
+    if (!h || !out || B <= 0 || L <= 0 || stride_frames <= 0) return fail(KM_ERR_INVALID_ARG, "km_sequence_plan: bad argument");
+    if (h->kind != 0) return fail(KM_ERR_INVALID_ARG, "km_sequence_plan needs a dual-stream handle (km_create)");
+    if (!h->host_finalized) return fail(KM_ERR_NOT_FINALIZED, "km_sequence_plan: call km_finalize_host or km_finalize first");
+    const SeqPlan p = seq_plan(h, B, L, stride_frames, with_attention != 0);
+    if (p.N > 0x7fffffff) return fail(KM_ERR_INVALID_ARG, "too many output frames");
+    out[0] = p.route; out[1] = p.N; out[2] = p.stft_frames; out[3] = p.E;
+    return KM_OK;
+}
+
 // Where a window's emotion logit comes from in km_sequence_forward_track: the rows of every clip's track and the closed-form
 // window -> row map (SeqTrackMap).  Null: one vector per clip (km_sequence_forward).
 struct SeqTrack { const float* track; int64_t K, first, interval, sample_offset, clip_len; };
@@ -51,16 +106,21 @@ static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int6
     // i*stride + f for f = 1 .. T-1; only frame 0 and frame T see the zero padding at the window boundary.  The STFT
     // of the clip is computed once (N-1)*stride + T + 1 frames instead of N * (T+1)), the two edge frames per window
     // separately, and the core reads its rows from both images.  Results are bit-identical to the per-window path.
-    const bool dedup = !c->opt.seq_per_window;       // km_set_option: tests compare both paths
+    // That holds for hop >= n_fft / 2 (clip_frames_shared); below it frames 1 and T - 1 reach into the padding too, and the
+    // schedule is the per-window one unless option seq_assemble asks for the assembled route, which knows every edge frame.
     MelPlan* plan = c->mel_plans[0];
-    const bool shared = c->fused_ok && dedup && mel_rp_ok(c, plan) && N < (1 << 24);
-    const int64_t nfc = (N - 1) * stride_frames + n_frames;                     // clip frames any window touches
-    if (shared) {     // grow-only images and their per-row maxima; allocates, so refused inside a stream capture, before any launch
+    const SeqPlan sp = seq_plan(h, B, L, stride_frames, xo.attn != nullptr || xo.stats != nullptr);
+    const bool shared = sp.route == 1, assembled = sp.route == 2;
+    const int64_t nfc = sp.nfc;                                                 // clip frames any window touches
+    const int64_t edge_rows = assembled ? 3 * sp.E : 2;                         // rows per window of the edge image(s)
+    if (shared || assembled) {     // grow-only images and their per-row maxima; allocates, so refused inside a stream capture, before any launch
         const char* what = "km_sequence_forward: elements of the clip / window images";
         if (int rc = c->seq.pow.grow(B * nfc * c->NK, stream, what)) return rc;
         if (int rc = c->seq.fmax.grow(B * nfc, stream, what)) return rc;
-        if (int rc = c->seq.edge.grow(total * 2 * c->NK, stream, what)) return rc;
-        if (int rc = c->seq.emax.grow(total * 2, stream, what)) return rc;
+        if (int rc = c->seq.edge.grow(total * edge_rows * c->NK, stream, what)) return rc;
+        if (int rc = c->seq.emax.grow(total * edge_rows, stream, what)) return rc;
+        if (assembled)
+            if (int rc = ensure_chunk_counters(c, total, stream)) return rc;    // the edge launches run over all windows at once
     }
     const int64_t map_floats = (int64_t)28 * c->NK;
     const bool tile_maps = xo.stats && !xo.attn;     // the maps of one tile at a time, for the accumulator alone
@@ -84,6 +144,49 @@ static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int6
     } else {
         // emotion features ONCE for the entire audio (:88): one logit per clip
         if (int rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, stream)) return rc;
+    }
+    if (assembled) {
+        hipStream_t st = (hipStream_t)stream;
+        const int E = sp.E, T = c->T;
+        if (int rc = launch_seq_zero_maxima(c->seq.fmax, B * nfc, c->seq.emax, total * edge_rows, stream)) return rc;
+        // (1) every clip as one long "window" of nfc frames
+        const SeqFrames clip_img{c->seq.pow, c->seq.fmax, nfc, 1};
+        if (int rc = launch_mel_power(c, plan, mel_clip_windows(audio_dev, L, B, (nfc - 1) * hop, 0, 0, 1), stream, mel_to_frames(&clip_img))) return rc;
+        // (2) the edge frames of every window with the front end as it is: frames 0 .. E - 1 in one launch, then frame T - j as row
+        // 1 of a two-row launch with frame_mul = T - j (its row 0, frame 0 again, is not read), j = 0 .. E - 1
+        const MelSrc wins = mel_clip_windows(audio_dev, L, total, W, step, 0, (int)N);
+        const SeqFrames left_img{c->seq.edge, c->seq.emax, E, 1};
+        if (int rc = launch_mel_power(c, plan, wins, stream, mel_to_frames(&left_img))) return rc;
+        float* right = c->seq.edge + total * E * c->NK;
+        unsigned* rmax = c->seq.emax + total * E;
+        for (int j = 0; j < E; ++j) {
+            const SeqFrames right_img{right + (int64_t)j * total * 2 * c->NK, rmax + (int64_t)j * total * 2, 2, T - j};
+            if (int rc = launch_mel_power(c, plan, wins, stream, mel_to_frames(&right_img))) return rc;
+        }
+        // (3) per tile: the windows' rows and maxima into the workspace, then the core km_forward_audio runs on its power path
+        // (the assemble kernel stores the maxima it needs; the slots of a fresh workspace beyond a short tile are cleared as
+        // launch_mel_power clears them, because the core launches below declare the maxima clean)
+        if (c->melmax_dirty) {
+            HIP_TRY(hipMemsetAsync(c->ws.melmax, 0, (size_t)c->ws.windows * sizeof(unsigned), st));
+            c->melmax_dirty = false;
+        }
+        const SeqAssemble sa{c->seq.pow, c->seq.fmax, c->seq.edge, c->seq.emax, right, rmax, total, (int)nfc, (int)stride_frames, (int)N, E, T};
+        for (int64_t w0 = 0; w0 < total; w0 += tile) {
+            const int64_t nw = (total - w0) < tile ? (total - w0) : tile;
+            if (int rc = launch_seq_assemble(c, sa, nw, w0, stream)) return rc;
+            if (c->fused_ok) {
+                if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
+                                                  with_outputs(trk ? core_workspace_seq_win(w0) : core_workspace_seq(w0, (int)N), raw_at(w0), attn_at(w0)))) return rc;
+            } else {
+                if (!trk)
+                    if (int rc = launch_gather_clip_logits(c, c->ws.zemo, c->ws.zemo_win, nw, w0, (int)N, stream)) return rc;
+                if (int rc = launch_core_generic_power(c, plan, nw, n_frames, trk ? zemo + w0 : c->ws.zemo_win, out_dev + w0 * c->NB,
+                                                       raw_at(w0), attn_at(w0), stream)) return rc;
+            }
+            if (int rc = stats_take(w0, nw)) return rc;
+        }
+        if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
+        return KM_OK;
     }
     if (shared) {
         hipStream_t st = (hipStream_t)stream;

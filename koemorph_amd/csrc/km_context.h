@@ -63,6 +63,7 @@ struct MelPlan {
 struct Options {
     int core_split = 0;            // 3 / 6: split-bf16 variant of the fused core (experimental, never the default)
     int seq_per_window = 0;        // 1: sequence mode recomputes every window's STFT (the reference's schedule)
+    int seq_assemble = 0;          // 1: sequence mode computes each clip's STFT once at every shape and hop whose forward call has a power path, and assembles the windows into the workspace (km_seq_assemble.hip; km_sequence_plan route 2)
     int generic_staged = 0;        // 1: generic core from a staged log-mel image instead of the power-mel workspace
     int mel_two_frame = 0;         // 1: two-frames-per-wave front end (A/B baseline)
     int emotion_separate = 0;      // 1: emotion logits in their own kernel
@@ -186,7 +187,9 @@ struct TrainState {
 
 // grow-only images of sequence mode and of the eval-mode forward from a resident clip
 struct SeqBufs {
-    // shared-frame sequence mode (km_sequence_forward)
+    // shared-frame sequence mode (km_sequence_forward): the clip image and its per-row maxima; the edge image and its maxima --
+    // (windows, 2, NK) read by the fused core, or on the assembled route (windows, E, NK) left edges followed by E images of
+    // (windows, 2, NK) right edges
     DevBuf<float> pow; DevBuf<unsigned> fmax; DevBuf<float> edge; DevBuf<unsigned> emax;
     // km_sequence_forward_track: the logits of the track's rows (clips * K) and of the sequence's windows (clips * N)
     DevBuf<float> ztrack, zwin;
@@ -438,6 +441,19 @@ int launch_mel_clip_span(Context* c, MelPlan* p, const float* clip, int64_t clip
 int launch_train_clip_pack(Context* c, MelPlan* p, const float* span, const float* edge, const int* start_frames, int64_t B,
                            int min_start, int64_t n_span, int T, int KP, float* xt, void* stream);
 bool mel_fuses_emotion(Context* c, MelPlan* p);
+
+// km_seq_assemble.hip
+// Sequence mode, assembled route: windows win0 .. win0 + nw - 1 of `total` (n_per_clip per clip, `stride` frames apart) written into
+// ws.melpow (nw, T + 1, NK) and their maxima stored into ws.melmax, from the clip image pow (clips, nfc, NK), the left-edge image
+// left (total, E, NK: frames 0 .. E - 1 of every window) and the right-edge images right (E, total, 2, NK: row 1 of image j is
+// frame T - j), with the per-row maxima the front end left beside each (float bits).  NK % 4 == 0, images 16-byte aligned.
+struct SeqAssemble {
+    const float* pow; const unsigned* fmax; const float* left; const unsigned* lmax; const float* right; const unsigned* rmax;
+    int64_t total; int nfc, stride, n_per_clip, E, T;
+};
+int launch_seq_assemble(Context* c, const SeqAssemble& s, int64_t nw, int64_t win0, void* stream);
+// ... and the two arrays of per-row maxima zeroed by one kernel launch ahead of the front-end launches that raise them
+int launch_seq_zero_maxima(unsigned* fmax, int64_t n_fmax, unsigned* emax, int64_t n_emax, void* stream);
 int ensure_chunk_counters(Context* c, int64_t windows, void* stream);
 int launch_ring_push(Context* c, const float* samples, int64_t n_per_stream, void* stream);
 

@@ -364,6 +364,16 @@ class Engine:
             check(rc)
         return rc
 
+    def sequence_plan(self, L: int, stride_frames: int = 1, B: int = 1, with_attention: bool = False) -> Dict[str, int]:
+        """km_sequence_plan: the schedule ``sequence_forward`` runs for ``B`` clips of ``L`` samples, after ``finalize_host`` (host
+        only).  ``route``: 0 per window, 1 the clip's STFT once with both images read by the fused core, 2 the clip's STFT once
+        with the windows assembled into the workspace (``set_option("seq_assemble", 1)``); ``N`` outputs per clip; ``stft_frames``
+        the frames the front-end launches compute in total; ``edge_frames_per_side`` the frames at either end of a window that
+        see its zero padding (``clip_span.edge_frames``)."""
+        out = (C.c_int64 * 4)()
+        check(self._lib.km_sequence_plan(self._h, int(B), int(L), int(stride_frames), int(bool(with_attention)), out))
+        return {"route": int(out[0]), "N": int(out[1]), "stft_frames": int(out[2]), "edge_frames_per_side": int(out[3])}
+
     def set_option(self, name: str, value: int) -> None:
         """Run-time switch of this handle (km_set_option): e.g. ("seq_per_window", 1), ("core_split", 3)."""
         check(self._lib.km_set_option(self._h, name.encode(), int(value)))

@@ -12,6 +12,8 @@ call with the head-averaged attention map of every window written as well (km_se
 Not in the reference: ``clip_emotion`` (a ``koemorph_amd.features.ClipEmotion``) or ``forward(emotion_track=...)`` give every
 window the row of the clip's eGeMAPS emotion track that a live stream would hold when the window ends -- the input
 ``train_sequential --emotion egemaps`` trains on -- instead of one vector per clip (km_sequence_forward_track).
+``share_frames=True`` computes each clip's STFT once at every model shape and hop and assembles the windows on the device (engine
+option "seq_assemble"); the default leaves the engine's schedule as it is.
 """
 from __future__ import annotations
 
@@ -41,6 +43,7 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
         emotion_provider=None,
         shard_across_ranks: bool = False,
         clip_emotion=None,
+        share_frames: bool = False,
     ):
         if clip_emotion is not None and emotion_provider is not None:
             raise ValueError("clip_emotion and emotion_provider both produce the emotion input: pass one of them")
@@ -54,6 +57,10 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
         self.shard_across_ranks = shard_across_ranks
         # not in the reference either: the clips' emotion tracks, built per forward call (ClipEmotion.build_batch)
         self.clip_emotion = clip_emotion
+        # not in the reference: each clip's STFT once at every shape and hop, the windows assembled on the device (engine option
+        # "seq_assemble", Engine.sequence_plan route 2); off, the engine keeps its default schedule for the shape
+        self.share_frames = bool(share_frames)
+        self._share_frames_applied = False
         self.window_frames = mel_sequence_length                      # reference :51
         self.window_samples = self.window_frames * self.hop_length    # :54
         self.stride_samples = self.stride_frames * self.hop_length    # :55
@@ -90,6 +97,9 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
             if emotion_track.shape[1] == 0:                            # no update yet: the zero vector ClipEmotion.rows gives
                 emotion_track = torch.zeros(batch_size, 1, emotion_track.shape[2], device=audio.device)
         eng = self.dual_stream_attention.engine()
+        if self.share_frames or self._share_frames_applied:            # (a model that never asked leaves the engine's switch alone)
+            eng.set_option("seq_assemble", int(self.share_frames))
+            self._share_frames_applied = self.share_frames
         self.reset_temporal_state()                                    # :99
         self.dual_stream_attention.require_eval_mode()
         results: Dict[str, object] = {}

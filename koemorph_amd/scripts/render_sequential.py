@@ -2,6 +2,7 @@
 
     python -m koemorph_amd.scripts.render_sequential --model_path ckpt.pth --input_audio a.wav --output_json out.jsonl
                                                      [--stride 1] [--emotion egemaps|noise] [--attention-summary summary.json]
+                                                     [--share-frames]
 
 The clip goes through ``SequentialDualStreamModel.forward`` (one output frame per window position, EMA along the clip) and every
 frame is written as one ``{"timestamp", "blendshapes"}`` line, encoded by ``koemorph_amd.wire`` as the streaming scripts encode
@@ -10,7 +11,8 @@ clip's eGeMAPS emotion track a live stream would hold at that time (``ClipEmotio
 egemaps`` trains on; ``noise`` is the reference's extraction-failure fallback, one ``0.1 * randn`` vector per clip.
 ``--attention-summary`` writes what the reference's AttentionVisualizer reduces the clip's attention maps to (``AttentionStats``:
 mean map, mean entropy and peak histogram per mouth query, mean and share per frequency band) as one JSON object; the maps are
-reduced on the device tile by tile, no (frames, 28, 80) array is made.
+reduced on the device tile by tile, no (frames, 28, 80) array is made.  ``--share-frames`` computes the clip's STFT once at every
+model shape and hop (``SequentialDualStreamModel(share_frames=True)``).
 """
 from __future__ import annotations
 
@@ -49,7 +51,8 @@ def compression_layer(ckpt: dict) -> "tuple[torch.nn.Linear, str]":
     return layer, f"default initialisation, seed {COMPRESSION_SEED}"
 
 
-def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: str = "cuda") -> SequentialDualStreamModel:
+def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: str = "cuda",
+               share_frames: bool = False) -> SequentialDualStreamModel:
     ckpt = torch.load(model_path, map_location="cpu", weights_only=True)
     cfg = dict(ckpt.get("model_config") or {})
     clip_emotion: Optional[ClipEmotion] = None
@@ -59,7 +62,7 @@ def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: st
         clip_emotion = ClipEmotion(compression_layer=layer, device=device)
     model = SequentialDualStreamModel(d_model=int(cfg.get("d_model", 256)), num_heads=int(cfg.get("num_heads", 8)),
                                       mel_sequence_length=int(cfg.get("mel_sequence_length", 256)), stride_frames=stride,
-                                      device=device, clip_emotion=clip_emotion)
+                                      device=device, clip_emotion=clip_emotion, share_frames=share_frames)
     model.load_state_dict(ckpt["model_state_dict"])
     return model.to(device).eval()
 
@@ -120,6 +123,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="write the clip's attention statistics (AttentionStats.compute()) as JSON")
     p.add_argument("--device-resample", dest="device_resample", action="store_true",
                    help="upload the file at its own rate and convert it to the model's rate on the device")
+    p.add_argument("--share-frames", dest="share_frames", action="store_true",
+                   help="compute the clip's STFT once and assemble the windows on the device (engine option seq_assemble)")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -127,7 +132,7 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
-    model = load_model(args.model_path, args.stride, args.emotion, args.device)
+    model = load_model(args.model_path, args.stride, args.emotion, args.device, args.share_frames)
     if args.device_resample:
         audio = load_audio_device_resample(args.input_audio, model.sample_rate, next(model.parameters()).device)
     else:

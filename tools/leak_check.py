@@ -26,6 +26,9 @@ def cycle(i):
     tr.step(audio[:8], emo[:8], torch.rand(8, 52, device="cuda"))
     g = Engine(d_model=64, num_heads=4, mel_sequence_length=32); g.load_state_dict(synth.make_core_params(i, 64, 32, 256, "init")); g.finalize()
     g.reserve(4, 32 * 533); g.forward_audio(audio[:4, :32 * 533].contiguous(), emo[:4])
+    g.set_option("seq_assemble", 1)                      # one assembled sequence call: the clip and edge images grow
+    assert g.sequence_plan(40 * 533, B=2)["route"] == 2
+    g.sequence_forward(audio[:2, :40 * 533].contiguous(), emo[:2])
     m = KoeMorphModel(d_model=64, d_query=64, num_heads=4, num_encoder_layers=1, num_attention_layers=1, decoder_hidden_dim=32, emotion_dim=8).cuda().eval()
     with torch.no_grad():
         m(torch.randn(2, 12, 80, device="cuda"), torch.randn(2, 12, 8, device="cuda"))
