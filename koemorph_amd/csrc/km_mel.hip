@@ -386,6 +386,8 @@ __global__ __launch_bounds__(256) void mel_power_kernel(MelArgs a) {
 // KM_MEL_STAMP (timing builds only, tools/micro/mel_stamp.py): every wave sums the shader-clock cycles it spends in each part
 // of the frame loop (s_memtime at the part boundaries; the stamps drain the wave's LDS queue, so the parts are measured with
 // less overlap than they run with) into km_mel_stamps[(workgroup, wave)][part], read back through km_debug_mel_stamps.
+// Slots 19-22 of a wave: the cycles of part 0 (the wait at the loop top) spent on frames that touch the padding and the number of
+// such frames; the cycles of its partial turns (fewer than 16 frames: the lone last frame) and of its full turns, hand-out to last barrier.
 #ifdef KM_MEL_STAMP
 #define KM_ASM asm volatile      /* keeps the arithmetic blocks between their stamps */
 __device__ unsigned long long km_mel_stamps[1024 * 8 * 24];
@@ -696,24 +698,61 @@ __device__ __forceinline__ bool load_frame_rp_fast(const float* __restrict__ x, 
     return true;
 }
 
-// Edge frames (2 of 257 in the batch shape): zero / reflect padding and ring wrap-around per sample.  Deliberately
-// NOT inlined and staged through the wave's LDS buffer: inlined, the compiler if-converts this path into the hot
-// block (predicated integer arithmetic executed for every frame: ~500 extra VALU instructions per frame).
-__device__ __noinline__ void load_frame_rp_slow(const float* __restrict__ x, int Li, int rs, int ring, int hop, int refl, int f,
-                                                int lane, float2* __restrict__ buf) {
-    const int p0 = f * hop - 512 + 2 * lane;
-    for (int i = 0; i < 8; ++i) {
-        float v[2];
-        for (int e = 0; e < 2; ++e) {
-            int q = p0 + 128 * i + e;
-            bool ok = true;
-            if (refl) q = q < 0 ? -q : (q >= Li ? 2 * (Li - 1) - q : q);      // np.pad(mode='reflect')
-            else ok = q >= 0 && q < Li;                                       // zero padding
-            if (ring) { q += rs; q -= q >= Li ? Li : 0; }                     // logical sample q lives at (rs + q) mod L
-            v[e] = ok ? x[ok ? q : 0] : 0.f;
-        }
-        buf[lane + 64 * i] = make_float2(v[0], v[1]);
+// Edge frames (2 of 257 in the batch shape; a ring's wrap frames): zero / reflect padding and ring wrap-around per sample.
+// Deliberately NOT inlined: inlined, the compiler if-converts this path into the hot block (predicated integer arithmetic
+// executed for every frame: ~500 extra VALU instructions per frame).  The 16 sample indices of a lane are computed first
+// (reflect, then the ring offset) and clamped into the clip, so that the 16 loads are unconditional and all in flight before
+// the first wait: one memory round trip, not eight dependent ones behind divergent branches.  Zero padding is a select on
+// the loaded values.  The frame comes back in registers (16 floats: returned directly), not through the wave's LDS buffer.
+struct EdgeFrame { melrp::v2f z[8]; };
+template <bool REFL>
+__device__ __forceinline__ void edge_request(const __attribute__((address_space(1))) float* xg, int p0, int Li, int rs0, float (&v)[16]) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        int q = p0 + 128 * (i >> 1) + (i & 1);
+        if (REFL) q = q < 0 ? -q : (q >= Li ? 2 * (Li - 1) - q : q);                            // np.pad(mode='reflect')
+        q += rs0; q -= q >= Li ? Li : 0;                                                        // logical sample q lives at (rs + q) mod L
+        q = q < Li - 1 ? q : Li - 1;
+        q = q > 0 ? q : 0;
+        asm volatile("global_load_dword %0, %1, off" : "=v"(v[i]) : "v"(xg + q));
     }
+}
+__device__ __noinline__ EdgeFrame load_frame_rp_edge(const float* __restrict__ x, int Li, int rs, int ring, int hop, int refl, int f, int lane) {
+    EdgeFrame r;
+    // every argument but the lane is wave-uniform: as scalars they cost no vector registers and the mode tests are scalar branches
+    Li = __builtin_amdgcn_readfirstlane(Li);
+    const int rs0 = __builtin_amdgcn_readfirstlane(ring) ? __builtin_amdgcn_readfirstlane(rs) : 0;            // ring arithmetic with offset 0 is the identity on [0, Li)
+    const int p0 = __builtin_amdgcn_readfirstlane(f * hop) - 512 + 2 * lane;
+    const uint64_t xb = (uint64_t)x;
+    const __attribute__((address_space(1))) float* xg = (const __attribute__((address_space(1))) float*)(
+        (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)xb) | (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(xb >> 32)) << 32);
+    // The loads are assembly so that they keep this order, each index computed just ahead of its load, under ONE wait:
+    // scheduled freely the function holds all 16 addresses at once (53 registers against 23), and whatever it takes beyond
+    // the 16 registers it returns in, its caller -- at its 128 -- has to spill around the call.  Nothing may touch v[] between
+    // a load and the wait (the compiler does not count assembly loads): the loads write straight into the wait's operands.
+    float v[16];
+    const bool refl_s = __builtin_amdgcn_readfirstlane(refl) != 0;
+    if (Li <= 0) {                                                    // an empty window (clip-span launch): zeros, nothing is read
+#pragma unroll
+        for (int i = 0; i < 8; ++i) r.z[i] = melrp::v2f{0.f, 0.f};
+        return r;
+    }
+    if (refl_s) edge_request<true>(xg, p0, Li, rs0, v);
+    else edge_request<false>(xg, p0, Li, rs0, v);
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]),
+                   "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
+    // zero padding: sample q counts when 0 <= q < Li (tested again here rather than carried as 16 flags across the loads);
+    // a reflected sample always does
+    int p0s = p0;
+    asm volatile("" : "+v"(p0s));                                     // (not the 16 positions of the request kept alive across the loads)
+    if (!refl_s) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = (unsigned)(p0s + 128 * (i >> 1) + (i & 1)) < (unsigned)Li ? v[i] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.z[i] = melrp::v2f{v[2 * i], v[2 * i + 1]};
+    return r;
 }
 
 // Mel stage lane map: the four 16-lane groups in which the LDS serves a ds_read_b128 ({0-3, 12-15, 20-27}, {4-11, 16-19,
@@ -799,8 +838,9 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
     };
     // The emotion stream of this window (0.2 MFLOP, latency bound, independent of the audio) rides in the last workgroup of
     // the window: no separate launch, and the chunk hand-out below lets that workgroup take correspondingly fewer chunks.
-    // (It requests its first frame after the rider: the rider's weight loads need the registers.)
-    if (!(KM_MEL_SKIP & 16) && a.emo.emo && bx == (int)gx - 1) {
+    // (It requests its first frame after the rider: the rider's weight loads need the registers.)  The packing and the
+    // clip-span launches never carry one (launch_mel_power refuses the combination, launch_mel_clip_span sets none).
+    if (!PACK && !TAB && !(KM_MEL_SKIP & 16) && a.emo.emo && bx == (int)gx - 1) {
         if (a.emo.d == 256 && a.emo.DH == 128) emotion_window_d256(a.emo, gw, pw);
         else emotion_window_generic(a.emo, EmoShape{a.emo.d, a.emo.DH}, gw, pw);
         first_frame();
@@ -858,6 +898,9 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
     const unsigned long long st_first = st_last;
 #endif
     while (chunk < n_chunks) {
+#ifdef KM_MEL_STAMP
+        const unsigned long long st_turn = __builtin_readcyclecounter();
+#endif
         unsigned req = 0;                                                // the chunk after next: requested here, looked at before the barrier
         if (tid == 0) req = atomicAdd(a.chunk_ctr + b, 1u);
         const int f0 = chunk * FPB;
@@ -867,14 +910,17 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
             const int f = f0 + fl;
             if (f < n_frames) {   // wave-uniform
                 if (!zn_ok) {       // edge frame (padding / ring wrap): 2 of 257 in the batch shape
-                    load_frame_rp_slow(x, Lv, rs, RING ? 1 : 0, a.hop, a.pad_mode == KM_PAD_REFLECT ? 1 : 0, f * fmul, lane,
-                                       reinterpret_cast<float2*>(buf));
-                    __builtin_amdgcn_wave_barrier();
+                    const EdgeFrame e = load_frame_rp_edge(x, Lv, rs, RING ? 1 : 0, a.hop, a.pad_mode == KM_PAD_REFLECT ? 1 : 0, f * fmul, lane);
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) zn[i] = buf[lane + 64 * i];
-                    __builtin_amdgcn_wave_barrier();
+                    for (int i = 0; i < 8; ++i) zn[i] = e.z[i];
                 }
+#ifdef KM_MEL_STAMP
+                const unsigned st_before = st_acc[0];
+#endif
                 KM_STAMP(0);                                              // loop overhead, edge frames, waiting for the samples
+#ifdef KM_MEL_STAMP
+                if (f * fmul * a.hop < 512 || f * fmul * a.hop + 512 > Lv) { st_acc[12] += st_acc[0] - st_before; st_acc[13] += 1; }   // edge frames
+#endif
                 v2f z[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) z[i] = zn[i] * win2[i];
@@ -1081,6 +1127,10 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
         chunk_next = __builtin_amdgcn_readfirstlane(sched[0]);           // written ahead of the barrier that opened the mel stage
         __syncthreads();                                                 // the power rows are free again
         KM_STAMP(11);
+#ifdef KM_MEL_STAMP
+        if (f0 + FPB > n_frames) st_acc[14] += (unsigned)(st_last - st_turn);                        // a partial turn, hand-out to last barrier
+        else { st_acc[15] += (unsigned)(st_last - st_turn); }
+#endif
     }
 #ifdef KM_MEL_STAMP
     if (lane == 0) {
@@ -1090,6 +1140,7 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
             o[12] = st_last - st_first;
             o[13] = st_entry; o[14] = st_first; o[15] = st_last; o[16] = st_entry_rt; o[17] = __builtin_amdgcn_s_memrealtime();
             o[18] = __builtin_readcyclecounter();
+            o[19] = st_acc[12]; o[20] = st_acc[13]; o[21] = st_acc[14]; o[22] = st_acc[15];   // part 0 of edge frames, their number, partial turns, full turns
         }
     }
 #endif

@@ -1,4 +1,6 @@
-"""Where a wave of mel_power_rp_kernel spends its cycles at the C2 shape.  Needs a library built with -DKM_MEL_STAMP
+"""Where a wave of mel_power_rp_kernel spends its cycles at the C2 shape: by part of the frame loop, by workgroup role, and
+for the frames off the fast path -- the wait at the loop top for an edge frame against an ordinary one, the lone 17th turn
+against a full one, and when the two workgroups of a window end.  Needs a library built with -DKM_MEL_STAMP
 (tools/micro/mel_xchg.sh with EXTRA=-DKM_MEL_STAMP):  KM_LIBRARY=tools/micro/bin/libkm_xchg0.so python tools/micro/mel_stamp.py"""
 import ctypes as C
 import os
@@ -58,6 +60,21 @@ def main():
         print(f"   role {role}: starts {np.mean(rt0[sel] - rt0.min()) / 100:6.2f} us after the first wave (max {np.max(rt0[sel] - rt0.min()) / 100:.2f}); "
               f"prologue {np.mean(first[sel] - ent[sel]) / ghz / 1e3:6.2f} us; loop {np.mean(last[sel] - first[sel]) / ghz / 1e3:6.2f} us; "
               f"ends {np.mean(rt1[sel] - rt0.min()) / 100:6.2f} us (max {np.max(rt1[sel] - rt0.min()) / 100:.2f}, min {np.min(rt1[sel] - rt0.min()) / 100:.2f})")
+    # edge frames (padding / ring wrap) and the partial last turn: slots 19-22 of a wave
+    edge_cyc, edge_n, part_cyc, full_cyc = (st[:, :, i] for i in (19, 20, 21, 22))
+    n_edge = edge_n.sum()
+    ord_cyc = (st[:, :, 0].sum() - edge_cyc.sum()) / max(257 * 256 - n_edge, 1)
+    print(f"part 0 (loop top / sample wait): {ord_cyc / ghz / 1e3:6.3f} us per ordinary frame; {edge_cyc.sum() / max(n_edge, 1) / ghz / 1e3:6.3f} us per edge "
+          f"frame ({int(n_edge)} edge frames)")
+    fr0 = st[0::2, 0, :]
+    print(f"   wave 0 of a window's first workgroup (frame 0 at kernel start, and frame 256 where that workgroup takes the last chunk): {np.mean(fr0[:, 19] / np.maximum(fr0[:, 20], 1)) / ghz / 1e3:6.3f} us "
+          f"(the other waves' first frames: {np.mean(st[0::2, 1:, 0]) / 16.1 / ghz / 1e3:6.3f} us per frame over the whole loop)")
+    had = part_cyc[:, 0] > 0
+    print(f"partial last turn (hand-out to last barrier): {int(had.sum())} workgroups, mean {part_cyc[had, 0].mean() / ghz / 1e3 if had.any() else 0:6.3f} us "
+          f"(max {part_cyc[had, 0].max() / ghz / 1e3 if had.any() else 0:6.3f}); full turn: mean {full_cyc[:, 0].sum() / (256 * (257 // 16)) / ghz / 1e3:6.3f} us")
+    wg_end = rt1.max(axis=1) - rt0.min()
+    print(f"the two workgroups of a window end {np.mean(np.abs(wg_end[0::2] - wg_end[1::2])) / 100:5.2f} us apart (mean; max "
+          f"{np.max(np.abs(wg_end[0::2] - wg_end[1::2])) / 100:5.2f}); the later one at {np.mean(np.maximum(wg_end[0::2], wg_end[1::2])) / 100:6.2f} us")
     frames = 257 * 256 / (512 * 8)
     print(f"frames per wave: {frames:.2f}")
 
