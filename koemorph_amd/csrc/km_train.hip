@@ -45,6 +45,10 @@ struct PaddedCopy {
     }
 };
 
+// 1 - beta^t of step t without the cancellation of 1.0f - powf(beta, t): while beta^t is close to 1 (beta2 = 0.999 up to
+// t ~ 100) rounding it to float32 costs 2^-24 / (1 - beta^t) of the correction, 500 ulp at t = 2
+__device__ __forceinline__ float bias_correction(float beta, int t) { return -expm1f((float)t * logf(beta)); }
+
 // torch.nn.utils.clip_grad_norm_(max_norm) + torch.optim.AdamW (decoupled weight decay, bias correction).
 // smoothing_alpha is outside the autograd graph whenever the EMA passes its input through (first call / batch-size
 // change / smoothing off): torch leaves its .grad as None and AdamW then skips it entirely (no decay, no moment
@@ -85,25 +89,30 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     // corrections are the same for every element but smoothing_alpha: one thread computes them for the block.
     if (tid == 0) {
         const int t = steps[0];
-        sh[4] = 1.0f - powf(b1, (float)t);
-        sh[5] = 1.0f - powf(b2, (float)t);
+        sh[4] = bias_correction(b1, t);
+        sh[5] = bias_correction(b2, t);
     }
     __syncthreads();
     const float gnorm = sqrtf((sh[0] + sh[1]) + (sh[2] + sh[3]));
     if (blockIdx.x == 0 && tid == 0) gnorm_out[0] = gnorm;
     float scale = 1.f;
     if (max_norm > 0.f) {
-        const float c = max_norm / (gnorm + 1e-6f);          // clip_coef, clamped to 1
-        scale = c < 1.f ? c : 1.f;
+        // clip_coef, clamped to 1 the way torch.clamp(max=1) does it: a NaN norm (one NaN gradient, error_if_nonfinite=False)
+        // stays a NaN scale and reaches every parameter
+        const float c = max_norm / (gnorm + 1e-6f);
+        scale = !(c >= 1.f) ? c : 1.f;
     }
     const float bc1_all = sh[4], bc2_all = sh[5];
+    // The fused multiply-adds are spelled out: left to the compiler's contraction, the float4 path and the element path below
+    // were fused differently (fma(1 - b1, g, b1 m) against fma(b1, m, (1 - b1) g), likewise v), so smoothing_alpha's neighbours,
+    // and every element of a bucket that is not 16-byte aligned, were rounded unlike the rest.  These are the float4 path's forms.
+    const float decay = fmaf(-lr, wd, 1.0f);
     auto update = [&](float& pi, float& mi, float& vi, float gi, float bc1, float bc2) {
         gi *= scale;
-        pi *= (1.0f - lr * wd);
-        mi = b1 * mi + (1.0f - b1) * gi;
-        vi = b2 * vi + (1.0f - b2) * gi * gi;
+        mi = fmaf(1.0f - b1, gi, b1 * mi);
+        vi = fmaf(gi, (1.0f - b2) * gi, b2 * vi);
         const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-        pi -= (lr / bc1) * mi / denom;
+        pi = fmaf(pi, decay, -((lr / bc1) * mi / denom));
     };
 #pragma unroll
     for (int u = 0; u < GR; ++u) {
@@ -126,7 +135,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
                 // update, its own step counter
                 if (!alpha_live) continue;
                 const int t = steps[1];
-                bc1 = 1.0f - powf(b1, (float)t); bc2 = 1.0f - powf(b2, (float)t);
+                bc1 = bias_correction(b1, t); bc2 = bias_correction(b2, t);
             }
             float pi = p[i], mi = m[i], vi = v[i];
             update(pi, mi, vi, g[i], bc1, bc2);
