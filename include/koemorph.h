@@ -195,7 +195,9 @@ int km_forward_audio(km_handle h, const float* audio_dev, int64_t B, int64_t L,
  *   km_forward_clip_supported   1 when km_forward_clip runs on this handle (after km_finalize), else 0: the fused core
  *                        (d_model 256, window 256, 8 heads) behind the 1024-point front end (not mel_two_frame), pad_mode
  *                        constant and hop_length >= n_fft / 2 (see km_train_clip_supported).  On any other handle
- *                        km_forward_clip returns KM_ERR_UNSUPPORTED, never another result. */
+ *                        km_forward_clip returns KM_ERR_UNSUPPORTED, never another result -- unless option "clip_assemble"
+ *                        is set, which adds the handles of km_clip_plan route 2 (they need km_reserve(B, T * hop): the windows
+ *                        are assembled into the front end's workspace). */
 int km_forward_clip_supported(km_handle h);
 int km_forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
                     int32_t min_start_frame, int32_t max_start_frame, const float* emotion_dev,
@@ -319,6 +321,7 @@ int km_sequence_forward_attn(km_handle h, const float* audio_dev, int64_t B, int
  *                        frames 0 and T the only frames of a window that see its zero padding (hop 533: frame 1 spans
  *                        samples 21 .. 1044; at the 60 fps shape, hop 266, frames 1 and T - 1 reach into it too).
  *                        km_train_step_clip on an unsupported handle returns KM_ERR_UNSUPPORTED, never another result.
+ *                        Option "clip_assemble" adds the handles of km_clip_plan route 2 (any hop with T + 1 >= 2 E).
  *   km_train_adamw       grad-norm clipping (max_grad_norm <= 0 disables) + AdamW on the flat vectors; `step`
  *                        is the 1-based optimizer step for the bias correction
  *   km_train_get_params / km_train_set_params   flat master copy <-> host
@@ -979,7 +982,9 @@ int km_resample_clip(void* rs, const float* clip_dev, int64_t n_in, float* out_d
  * this path: every switch selects between two implementations of the SAME arithmetic, for A/B timing and for the
  * tests that pin one path against the other).  Names: "core_split" (0 | 3 | 6, experimental split-bf16 core),
  * "seq_per_window", "seq_assemble" (default 0; 1: sequence mode shares each clip's STFT frames at every shape and hop whose forward
- * call has a power path, assembling the windows into the workspace: km_sequence_plan route 2), "generic_staged", "mel_two_frame", "emotion_separate", "no_ln_fusion", "no_db_fusion",
+ * call has a power path, assembling the windows into the workspace: km_sequence_plan route 2), "clip_assemble" (default 0; 1:
+ * km_train_step_clip / km_forward_clip / km_forward_clip_attn also run on the handles they refuse by default, from a span image and
+ * E edge rows a side per window: km_clip_plan route 2; a handle they accept keeps its launches and bits), "generic_staged", "mel_two_frame", "emotion_separate", "no_ln_fusion", "no_db_fusion",
  * "no_score_fusion", "no_out_fusion", "no_v_fusion",
  * "no_core_merge" (the one-launch cores of d_model 512 and of d_model 256 / window 512 as the launches they replaced: km_core_route),
  * "core128" (default 0; 1: the forward calls at d_model 128 / 4 heads / window 128 or 256 run core128_kernel, route 4, instead of the
@@ -1018,6 +1023,19 @@ int km_core_route(km_handle h, int32_t with_attention);
  * B (nfc + 3 E N) on route 2, nfc = (N - 1) stride_frames + T + 1.  out[3] E = ceil((n_fft / 2) / hop): the frames at either end of
  * a window that see its zero padding.  KM_ERR_INVALID_ARG: NULL argument, B, L or stride_frames <= 0. */
 int km_sequence_plan(km_handle h, int64_t B, int64_t L, int32_t stride_frames, int32_t with_attention, int64_t out[4]);
+/* The schedule km_train_step_clip (training = 1), km_forward_clip (0) or km_forward_clip_attn (2) runs for B windows whose start
+ * frames lie in [min_start_frame, max_start_frame], for the handle's shape, front end and switches as they stand.  Host only, valid
+ * after km_finalize_host; nothing is launched or allocated.  out[0] route: 0 the call is refused (the Python wrappers gather the
+ * windows: km_gather_windows + the from-audio call); 1 the default shared route (the span once + frames 0 and T of every window:
+ * hop >= n_fft / 2, the packing front end for training, the fused core for the forward calls), whatever option "clip_assemble"
+ * says; 2 option "clip_assemble" on a handle route 1 does not cover: the span once + two snippets of 2 E frames per window, then
+ * the packed training input (the packing 1024-point front end, zero padding, T + 1 >= 2 E) or the windows assembled into the front
+ * end's workspace for the core behind km_forward_audio's power path (the fused shape below hop n_fft / 2, core512, core256w, core128
+ * under option "core128", the chain where maps are asked for; zero padding, T + 1 >= 2 E).  out[1] the span rows max - min + T + 1.
+ * out[2] the STFT frames the call's front-end launches compute: B (T + 1) gathered, span + 2 B on route 1, span + 4 E B on route 2.
+ * out[3] E = ceil((n_fft / 2) / hop).  km_train_clip_supported / km_forward_clip_supported answer 1 on routes 1 and 2.
+ * KM_ERR_INVALID_ARG: NULL argument, B <= 0, min_start_frame < 0, max_start_frame < min_start_frame, training outside 0 .. 2. */
+int km_clip_plan(km_handle h, int64_t B, int32_t min_start_frame, int32_t max_start_frame, int32_t training, int64_t out[4]);
 
 /* ---- window producer for sequence training -------------------------------------------------------------
  * Replaces the per-window host slicing + H2D copies of KoeMorphSequentialDataset (src/data/sequential_dataset.py:

@@ -249,6 +249,7 @@ SIGNATURES = {
     "km_debug_buffer": (C.c_int, [_h, C.c_char_p, _p, C.POINTER(_i64)]),
     "km_core_route": (C.c_int, [_h, _i32]),
     "km_sequence_plan": (C.c_int, [_h, _i64, _i64, _i32, _i32, C.POINTER(_i64)]),
+    "km_clip_plan": (C.c_int, [_h, _i64, _i32, _i32, _i32, C.POINTER(_i64)]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -5,7 +5,14 @@ The windows of a dense batch start at multiples of the hop inside one clip: wind
 samples ``[f * hop - n_fft / 2, f * hop + n_fft / 2)``.  A frame that stays inside the window reads clip samples only: it IS clip
 frame ``start[b] + f`` and can be shared by every window that contains it.  A frame that leaves the window sees its zero
 padding and belongs to that window alone (an "edge" frame).  With ``hop >= n_fft / 2`` the edge frames are exactly 0 and T;
-below that frames 1 and T - 1 leave the window too, which is why the step supports only the former.
+below that frames 1 and T - 1 leave the window too, which is why the step supports only the former by default.
+
+With option ``clip_assemble`` (km_clip_plan route 2) the step and the eval-mode forward run at every hop: E = ceil((n_fft / 2) / hop)
+frames at either end of a window are edge frames (``edge_frames``), and they are computed from two snippets of the window, its
+first and its last ``Ls = (2 E - 1) * hop`` samples, each a dense row of 2 E frames for the unchanged front end (``edge_source``):
+window frame f < E is row f of the left snippet, window frame T - j (j < E) row 2 E - 1 - j of the right one.  Row k >= E of the
+right snippet is centred at k * hop >= n_fft / 2 and sees no left padding; row k < E of the left one reaches sample
+(E - 1) * hop + n_fft / 2 <= Ls and sees no right padding.  Frames E .. T - E come from the span image as before.
 """
 from __future__ import annotations
 
@@ -52,3 +59,29 @@ def frames_computed(starts, T: int, shared: bool) -> int:
     if not shared:
         return len(starts) * (T + 1)
     return n_span(min(starts), max(starts), T) + 2 * len(starts)
+
+
+def edges_per_side(hop: int, n_fft: int = 1024) -> int:
+    """E: the frames at either end of a window that see its zero padding."""
+    return -(-(n_fft // 2) // hop)
+
+
+def snippet_samples(hop: int, E: int) -> int:
+    """Ls: samples of the left / right snippet of a window, 2 E frames each."""
+    return (2 * E - 1) * hop
+
+
+def edge_source(f: int, T: int, E: int) -> Tuple[str, int]:
+    """Where frame f of a window comes from on the assembled route: ("left", row) / ("right", row) of the window's 2 E-row
+    snippet images, or ("span", f): row start - min_start + f of the span image.  Needs T + 1 >= 2 E."""
+    if f < E:
+        return "left", f
+    if f > T - E:
+        return "right", 2 * E - 1 - (T - f)
+    return "span", f
+
+
+def frames_computed_edges(starts, T: int, E: int) -> int:
+    """STFT frames the front end computes for one batch on the assembled route: the span + two snippets of 2 E frames a window."""
+    starts = [int(s) for s in starts]
+    return n_span(min(starts), max(starts), T) + 4 * E * len(starts)

@@ -64,6 +64,10 @@ int km_reserve(km_handle h, int64_t max_windows, int64_t max_samples) {
     if (int rc = ws.zemo.alloc(W, what)) return rc;
     if (int rc = ws.zemo_win.alloc(W, what)) return rc;
     if (int rc = ws.melmax.alloc(W, what)) return rc;
+    // zero from the start, not only through the memset the first front-end launch issues (melmax_dirty): where that launch is
+    // recorded into a stream capture the memset is a node of the graph and does not run, and the eager launches that follow
+    // raised their maxima over whatever the allocation held (km_stream_tick captured before its first eager tick)
+    HIP_TRY(hipMemset(ws.melmax, 0, (size_t)W * sizeof(unsigned)));
     if (int rc = ws.mel_short.alloc(W * 3 * max_mels, what)) return rc;
     if (F > 0) {
         if (int rc = ws.melpow.alloc(W * F * max_mels, what)) return rc;
@@ -328,7 +332,7 @@ static bool forward_clip_ok(Context* c) {
 
 int km_forward_clip_supported(km_handle h) {
     if (!h || !h->dev_finalized || h->kind != 0) return 0;
-    return forward_clip_ok(h) ? 1 : 0;
+    return forward_clip_ok(h) || clip_plan(h, 1, 0, 0, 0).route == 2 ? 1 : 0;      // (the route does not depend on the batch)
 }
 
 static int forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
@@ -340,7 +344,10 @@ static int forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, co
         max_start_frame < min_start_frame)
         return fail(KM_ERR_INVALID_ARG, "km_forward_clip: bad argument");
     const km_mel_config& m = c->mel_plans[0]->cfg;
-    if (!forward_clip_ok(c))
+    // option clip_assemble: a handle refused here by default takes the assembled route (km_clip_plan route 2); one accepted keeps its route
+    const ClipPlan cp = clip_plan(c, B, min_start_frame, max_start_frame, attn_dev ? 2 : 0);
+    const bool assembled = !forward_clip_ok(c) && cp.route == 2;
+    if (!forward_clip_ok(c) && !assembled)
         return fail(KM_ERR_UNSUPPORTED, "km_forward_clip: needs the fused core (d_model 256, window 256, 8 heads) behind the 1024-point "
                     "front end with constant padding and hop >= n_fft / 2 (hop %d, n_fft %d): gather the windows (km_gather_windows) "
                     "and call km_forward_audio", m.hop_length, m.n_fft);
@@ -350,6 +357,38 @@ static int forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, co
         return fail(KM_ERR_INVALID_ARG, "km_forward_clip: clip or start frame beyond 2^31 samples");
     if (B > c->ws.windows)
         return fail(KM_ERR_WORKSPACE, "workspace holds %lld windows, need %lld: call km_reserve", (long long)c->ws.windows, (long long)B);
+    if (assembled) {
+        if (attn_dev)
+            if (int rc = attn_refused(c, "km_forward_clip_attn")) return rc;
+        if (!c->fused_ok && !c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
+        if (T + 1 > c->ws.frames)
+            return fail(KM_ERR_WORKSPACE, "workspace holds %lld frames a window, need %lld: call km_reserve", (long long)c->ws.frames, (long long)(T + 1));
+        // emotion logits, the span and edge images, the windows' rows and maxima into the workspace, then the core km_forward_audio
+        // runs on its power path (the assemble kernel stores the maxima it needs; the slots of a fresh workspace beyond the batch
+        // are cleared as launch_mel_power clears them, because the core launches below declare the maxima clean)
+        MelPlan* plan = c->mel_plans[0];
+        // The logits have to be the ones km_forward_audio computes.  At d_model 256 its rider and emotion_kernel_d256 are
+        // bit-identical; at the other shapes the rider sums in another order than emotion_kernel, so the rider itself runs: an
+        // ordinary front-end launch over B windows of one zero sample (one frame each, rows and maxima the assemble kernel
+        // overwrites; the pointer stays inside the clip).
+        if (mel_fuses_emotion(c, plan) && !(c->d == 256 && c->DH == 128)) {
+            if (int rc = launch_mel_power(c, plan, mel_clip_windows(clip_dev, 0, B, 1, 0, 0, 1), stream, mel_emotion(emotion_dev, c->ws.zemo))) return rc;
+        } else {
+            if (int rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, stream)) return rc;
+        }
+        if (int rc = launch_clip_images(c, plan, clip_dev, clip_len, start_frames_dev, B, min_start_frame, n_span, cp.E, stream)) return rc;
+        if (c->melmax_dirty) {
+            HIP_TRY(hipMemsetAsync(c->ws.melmax, 0, (size_t)c->ws.windows * sizeof(unsigned), (hipStream_t)stream));
+            c->melmax_dirty = false;
+        }
+        if (int rc = launch_clip_assemble(c, start_frames_dev, B, min_start_frame, n_span, cp.E, stream)) return rc;
+        if (c->fused_ok)
+            return launch_core_fused_db(c, plan, B, T + 1, c->ws.zemo, out_dev, stream,
+                                        with_outputs(core_workspace(state_dev, first), raw_dev, attn_dev));
+        if (int rc = launch_core_generic_power(c, plan, B, T + 1, c->ws.zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
+        if (state_dev) return launch_smooth(c, out_dev, state_dev, B, first, stream);
+        return KM_OK;
+    }
     // grow-only; allocates, so not inside a stream capture
     if (int rc = c->seq.fwd_span.grow(n_span * c->NK, stream, "km_forward_clip: floats of the span image")) return rc;
     if (int rc = c->seq.fwd_edge.grow(B * 2 * c->NK, stream, "km_forward_clip: floats of the edge image")) return rc;

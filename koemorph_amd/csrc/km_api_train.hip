@@ -185,7 +185,7 @@ int km_train_step_audio(km_handle h, const float* audio_dev, int64_t B, int64_t 
 
 int km_train_clip_supported(km_handle h) {
     if (!h || !h->dev_finalized || h->kind != 0 || !h->tr.params) return 0;
-    return train_clip_ok(h) ? 1 : 0;
+    return train_clip_ok(h) || clip_plan(h, 1, 0, 0, 1).route == 2 ? 1 : 0;      // (the route does not depend on the batch)
 }
 
 int km_train_step_clip(km_handle h, const float* clip_dev, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
@@ -198,7 +198,10 @@ int km_train_step_clip(km_handle h, const float* clip_dev, int64_t clip_len, con
         min_start_frame < 0 || max_start_frame < min_start_frame)
         return fail(KM_ERR_INVALID_ARG, "km_train_step_clip: bad argument");
     const km_mel_config& m = c->mel_plans[0]->cfg;
-    if (!train_clip_ok(c))
+    // option clip_assemble: a handle refused here by default takes the assembled route (km_clip_plan route 2); one accepted keeps its route
+    const ClipPlan cp = clip_plan(c, B, min_start_frame, max_start_frame, 1);
+    const bool assembled = !train_clip_ok(c) && cp.route == 2;
+    if (!train_clip_ok(c) && !assembled)
         return fail(KM_ERR_UNSUPPORTED, "km_train_step_clip: windows share STFT frames only with the packing 1024-point front end, constant "
                     "padding and hop >= n_fft / 2 (hop %d, n_fft %d): gather the windows (km_gather_windows) and call km_train_step_audio",
                     m.hop_length, m.n_fft);
@@ -208,6 +211,18 @@ int km_train_step_clip(km_handle h, const float* clip_dev, int64_t clip_len, con
         return fail(KM_ERR_INVALID_ARG, "km_train_step_clip: clip or start frame beyond 2^31 samples");
     if (B > c->ws.windows)
         return fail(KM_ERR_WORKSPACE, "workspace holds %lld windows, need %lld: call km_reserve", (long long)c->ws.windows, (long long)B);
+    if (assembled) {
+        // the span and the 2 B snippets through the front end as it is, then the packed input and the window maxima (stored: no
+        // zeroed slots needed); behind them the step of km_train_step_audio's packing branch
+        if (int rc = launch_clip_images(c, c->mel_plans[0], clip_dev, clip_len, start_frames_dev, B, min_start_frame, n_span, cp.E, stream)) return rc;
+        if (int rc = launch_clip_pack_edges(c, c->mel_plans[0], start_frames_dev, B, min_start_frame, n_span, cp.E, (int)trainp_kp(c), c->tr.act,
+                                            stream)) return rc;
+        c->melmax_dirty = true;      // until phase 3 / 4 has re-zeroed the maxima
+        const LogParams lp = plan_log_params(c->mel_plans[0]);
+        const TrainAudioSrc asrc{c->ws.melpow, c->ws.melmax, (int)(T + 1), &lp, true};
+        const TrainStepArgs sa{emotion_dev, target_dev, mse_weight, l1_weight, flat_grad_dev, loss_dev, out_dev, ema_state_dev, ema_first, stream};
+        return train_forward_backward(c, nullptr, B, T + 1, nullptr, c->tr.act, &asrc, sa);
+    }
     if (n_span > c->tr.clip_span_rows) {     // grow-only, both images in one allocation (the edge image holds tr.windows >= B windows)
         if (int rc = growth_refused(stream, "km_train_step_clip: span frames", n_span, c->tr.clip_span_rows)) return rc;
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));

@@ -64,6 +64,7 @@ struct Options {
     int core_split = 0;            // 3 / 6: split-bf16 variant of the fused core (experimental, never the default)
     int seq_per_window = 0;        // 1: sequence mode recomputes every window's STFT (the reference's schedule)
     int seq_assemble = 0;          // 1: sequence mode computes each clip's STFT once at every shape and hop whose forward call has a power path, and assembles the windows into the workspace (km_seq_assemble.hip; km_sequence_plan route 2)
+    int clip_assemble = 0;         // 1: km_train_step_clip / km_forward_clip / km_forward_clip_attn also run on the handles they refuse by default (hop below n_fft / 2, no fused core): span image + E edge rows a side per window, packed or assembled into the workspace (km_clip_assemble.hip; km_clip_plan route 2)
     int generic_staged = 0;        // 1: generic core from a staged log-mel image instead of the power-mel workspace
     int mel_two_frame = 0;         // 1: two-frames-per-wave front end (A/B baseline)
     int emotion_separate = 0;      // 1: emotion logits in their own kernel
@@ -200,6 +201,13 @@ struct SeqBufs {
     DevBuf<float> fwd_span, fwd_edge;
 };
 
+// grow-only images of the resident-clip calls on their assembled route (option clip_assemble, km_clip_assemble.hip)
+struct ClipAsmBufs {
+    DevBuf<float> span; DevBuf<unsigned> smax;   // (n_span, NK) clip frames min_start .. max_start + T and their per-row maxima
+    DevBuf<float> snip;                          // (2 windows, Ls rounded up to 4) the first / last Ls = (2 E - 1) hop samples of every window
+    DevBuf<float> edge; DevBuf<unsigned> emax;   // (2 windows, 2 E, NK) the snippets' frames and their per-row maxima
+};
+
 // two-deep pipeline across calls (km_forward_audio_pipelined)
 struct PipeSlot {
     DevBuf<float> melpow; DevBuf<unsigned> melmax; DevBuf<float> zemo;
@@ -246,6 +254,7 @@ struct Context {
     int tr_dropout_mode = 0;         // 0: masks drawn per step (Philox), 1: masks supplied by the caller (km_train_set_dropout_masks)
     unsigned long long tr_dropout_seed = 0;
     SeqBufs seq;                                 // km_sequence_forward*, km_forward_clip
+    ClipAsmBufs clipasm;                         // km_train_step_clip / km_forward_clip with option clip_assemble
     Pipeline pipe;                               // km_forward_audio_pipelined
     bool stage_timing = false;
     DevEvent stage_ev[6];                        // emo b/e, mel e, core b/e
@@ -455,6 +464,21 @@ int launch_seq_assemble(Context* c, const SeqAssemble& s, int64_t nw, int64_t wi
 // ... and the two arrays of per-row maxima zeroed by one kernel launch ahead of the front-end launches that raise them
 int launch_seq_zero_maxima(unsigned* fmax, int64_t n_fmax, unsigned* emax, int64_t n_emax, void* stream);
 int ensure_chunk_counters(Context* c, int64_t windows, void* stream);
+
+// km_clip_assemble.hip
+// The schedule of a resident-clip call on B windows whose start frames lie in [min_start, max_start]; mode 0 km_forward_clip,
+// 1 km_train_step_clip, 2 km_forward_clip_attn.  route 0: refused (the caller gathers the windows); 1: the default shared route
+// (launch_mel_clip_span: n_span + 2 B frames); 2: option clip_assemble (n_span + 4 E B frames).
+struct ClipPlan { int route, E; int64_t n_span, stft_frames; };
+ClipPlan clip_plan(Context* c, int64_t B, int64_t min_start, int64_t max_start, int mode);
+// the span and edge images of route 2 into c->clipasm (grow-only: refused inside a stream capture, before any launch)
+int launch_clip_images(Context* c, MelPlan* plan, const float* clip, int64_t clip_len, const int* start_frames, int64_t B, int min_start,
+                       int64_t n_span, int E, void* stream);
+// ... from them ws.melpow (B, T + 1, NK) and ws.melmax (B), as launch_mel_power leaves them for the windows
+int launch_clip_assemble(Context* c, const int* start_frames, int64_t B, int min_start, int64_t n_span, int E, void* stream);
+// ... or the packed encoder input xt (B, n_mels, KP) as MelPack leaves it, and ws.melmax
+int launch_clip_pack_edges(Context* c, MelPlan* p, const int* start_frames, int64_t B, int min_start, int64_t n_span, int E, int KP, float* xt,
+                           void* stream);
 int launch_ring_push(Context* c, const float* samples, int64_t n_per_stream, void* stream);
 
 // km_legacy_stream.hip: the FIFOs of km_legacy_stream_* (Context::lf)

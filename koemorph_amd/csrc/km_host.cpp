@@ -698,7 +698,7 @@ namespace km {
 namespace {
 struct OptName { const char* name; int Options::*field; };
 const OptName kOptNames[] = {
-    {"core_split", &Options::core_split}, {"seq_per_window", &Options::seq_per_window}, {"seq_assemble", &Options::seq_assemble},
+    {"core_split", &Options::core_split}, {"seq_per_window", &Options::seq_per_window}, {"seq_assemble", &Options::seq_assemble}, {"clip_assemble", &Options::clip_assemble},
     {"generic_staged", &Options::generic_staged}, {"mel_two_frame", &Options::mel_two_frame},
     {"emotion_separate", &Options::emotion_separate}, {"no_ln_fusion", &Options::no_ln_fusion},
     {"no_db_fusion", &Options::no_db_fusion}, {"no_score_fusion", &Options::no_score_fusion},

@@ -310,7 +310,8 @@ class Engine:
         return out
 
     def forward_clip_supported(self) -> bool:
-        """km_forward_clip_supported: ``forward_clip`` runs on this engine (fused core, windows share the clip's STFT frames)."""
+        """km_forward_clip_supported: ``forward_clip`` runs on this engine (fused core, windows share the clip's STFT frames; with
+        option clip_assemble also every shape ``clip_plan`` gives route 2)."""
         return bool(self._lib.km_forward_clip_supported(self._h))
 
     def forward_clip(self, clip, start_frames, emotion, state=None, first: bool = True, extremes=None, out=None,
@@ -340,7 +341,9 @@ class Engine:
         B = int(starts.numel())
         if tuple(emotion.shape) != (B, self.emotion_dim):
             raise ValueError(f"shape mismatch: {B} start frames, emotion {tuple(emotion.shape)}")
-        self.reserve(B, 0)
+        # the assembled route (option clip_assemble) writes the windows' rows into the front end's workspace
+        assembled = self.clip_plan(B, lo, hi, forward_attention=return_attention)["route"] == 2
+        self.reserve(B, self.mel_sequence_length * self.mel.hop_length if assembled else 0)
         if out is None:
             out = torch.empty(B, self.num_blendshapes, device=clip.device, dtype=torch.float32)
         if return_attention:
@@ -373,6 +376,16 @@ class Engine:
         out = (C.c_int64 * 4)()
         check(self._lib.km_sequence_plan(self._h, int(B), int(L), int(stride_frames), int(bool(with_attention)), out))
         return {"route": int(out[0]), "N": int(out[1]), "stft_frames": int(out[2]), "edge_frames_per_side": int(out[3])}
+
+    def clip_plan(self, B: int, min_start: int, max_start: int, training: bool = False, forward_attention: bool = False) -> Dict[str, int]:
+        """km_clip_plan: the schedule ``Trainer.forward_backward_clip`` (``training``) or ``forward_clip`` (``forward_attention``:
+        with ``return_attention``) runs for ``B`` windows whose start frames lie in ``[min_start, max_start]``, after
+        ``finalize_host`` (host only).  ``route``: 0 refused (the wrappers gather the windows), 1 the default shared route, 2 the
+        assembled one (``set_option("clip_assemble", 1)``); ``span_rows``; ``stft_frames`` the frames the front-end launches
+        compute (``clip_span.frames_computed`` / ``frames_computed_edges``); ``edge_frames_per_side``."""
+        out = (C.c_int64 * 4)()
+        check(self._lib.km_clip_plan(self._h, int(B), int(min_start), int(max_start), 1 if training else (2 if forward_attention else 0), out))
+        return {"route": int(out[0]), "span_rows": int(out[1]), "stft_frames": int(out[2]), "edge_frames_per_side": int(out[3])}
 
     def set_option(self, name: str, value: int) -> None:
         """Run-time switch of this handle (km_set_option): e.g. ("seq_per_window", 1), ("core_split", 3)."""

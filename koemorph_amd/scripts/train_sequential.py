@@ -43,10 +43,13 @@ class SequentialTrainer:
                  device: str = "cuda", learning_rate: float = 1e-4, weight_decay: float = 1e-5, gradient_clip: float = 1.0,
                  mse_weight: float = 1.0, l1_weight: float = 0.0, extra_loss_terms: Optional[Dict[str, float]] = None,
                  emotion_provider: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, dropout: float = 0.1, seed: int = 0,
-                 from_clip: bool = False, clip_emotion: Optional[ClipEmotion] = None):
+                 from_clip: bool = False, clip_emotion: Optional[ClipEmotion] = None, clip_assemble: bool = False):
         """``from_clip``: batches that name their windows inside the resident clip (``resident_windows=True`` data sets) go
         through ``Trainer.step_clip`` -- no window copy, shared STFT frames; same losses and weights, bit for bit.  An
         ``emotion_provider`` is handed window audio, so with one installed the trainer stays on the gathered path.
+        ``clip_assemble``: sets the engine's option of that name, with which ``step_clip`` / ``forward_clip`` also run at the
+        shapes and hops they refuse by default (hop below n_fft / 2, no fused core: ``Engine.clip_plan`` route 2) instead of
+        gathering; same bits again.  Off, the engine's option is left as it is.
         ``clip_emotion``: the emotion rows come from each clip's emotion track (built once per clip and kept on the device),
         gathered by start frame; it reads no window audio, so ``step_clip`` / ``forward_clip`` stay in use.  It needs batches that
         name their clip (``resident_windows=True``) and excludes an ``emotion_provider``.
@@ -61,6 +64,8 @@ class SequentialTrainer:
         self.emotion_provider = emotion_provider
         self.clip_emotion = clip_emotion
         self.from_clip = from_clip
+        if clip_assemble:
+            engine.set_option("clip_assemble", 1)
         self._from_clip_logged = False
         self.rank, self.world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) \
             if torch.distributed.is_initialized() else (0, 1)
@@ -337,6 +342,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--resident-clip", dest="resident_clip", action="store_true",
                    help="train from the clips resident in GPU memory (Trainer.step_clip): no window copies, the STFT frames the "
                         "windows of a batch share are computed once; same losses and weights")
+    p.add_argument("--clip-assemble", dest="clip_assemble", action="store_true",
+                   help="with --resident-clip: train and validate from the resident clip at every shape and hop (engine option "
+                        "clip_assemble: span image + edge rows per window) instead of gathering where the default refuses")
     p.add_argument("--device-resample", dest="device_resample", action="store_true",
                    help="WAV files at another rate are uploaded as they are and converted to 16 kHz on the device")
     p.add_argument("--loss-components", dest="loss_components", action="store_true",
@@ -367,7 +375,8 @@ def main(argv=None):
         if args.val_dir else None
     st = SequentialTrainer(eng, train, val, device=device, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
                            gradient_clip=args.gradient_clip, l1_weight=args.l1_weight, dropout=args.dropout, seed=args.seed,
-                           from_clip=args.resident_clip, clip_emotion=ClipEmotion(device=device) if egemaps else None)
+                           from_clip=args.resident_clip, clip_emotion=ClipEmotion(device=device) if egemaps else None,
+                           clip_assemble=args.clip_assemble)
     if args.resume:
         st.load_checkpoint(args.resume)
     for _ in range(st.epoch, args.epochs):

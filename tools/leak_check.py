@@ -29,6 +29,16 @@ def cycle(i):
     g.set_option("seq_assemble", 1)                      # one assembled sequence call: the clip and edge images grow
     assert g.sequence_plan(40 * 533, B=2)["route"] == 2
     g.sequence_forward(audio[:2, :40 * 533].contiguous(), emo[:2])
+    # one training step and one forward from a resident clip on the assembled route (option clip_assemble): the span, snippet and edge images grow
+    from koemorph_amd.engine import MelConfig
+    c = Engine(d_model=64, num_heads=4, mel_sequence_length=32, mel=MelConfig.model_batch(target_fps=60))
+    c.load_state_dict(synth.make_core_params(i, 64, 32, 256, "init")); c.finalize(); c.set_option("clip_assemble", 1)
+    assert c.clip_plan(4, 0, 9, training=True)["route"] == 2 and c.clip_plan(4, 0, 9)["route"] == 2
+    ctr = Trainer(c, max_windows=4, use_smoothing=False)
+    clip = audio[0, :60 * 266].contiguous()
+    ctr.step_clip(clip, [0, 1, 2, 9], emo[:4], torch.rand(4, 52, device="cuda"))
+    c.forward_clip(clip, [0, 1, 2, 9], emo[:4])
+    del ctr, c, clip
     m = KoeMorphModel(d_model=64, d_query=64, num_heads=4, num_encoder_layers=1, num_attention_layers=1, decoder_hidden_dim=32, emotion_dim=8).cuda().eval()
     with torch.no_grad():
         m(torch.randn(2, 12, 80, device="cuda"), torch.randn(2, 12, 8, device="cuda"))
