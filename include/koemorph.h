@@ -834,6 +834,25 @@ int km_emotion_clip_build_batch(void* ec, const float* clips_dev, int64_t B, int
                                 void* stream);
 int km_emotion_clip_rows(void* ec, const float* emotion_track_dev, int64_t K, int64_t clip_len, const int32_t* start_frames_dev, int64_t B,
                          int64_t hop, int64_t window_frames, float* emotion_out, uint8_t* valid_out, void* stream);
+/* The `basic` back end of the track: row k is the nine raw prosodic values [energy, zcr, centroid, f0_mean, f0_std, mean, std, max,
+ * min] of the SAME window, i.e. what one km_emotion_stream_create_basic stream holds after t_k samples of the clip, bit for bit, and
+ * bit for bit km_prosody_features on that window: no peak normalisation, no 300 / 600 ms slots, no compression layer, no NaN scrub.
+ * K, the windows and the window -> row mapping are the ones above.
+ *   km_emotion_clip_create_basic     validates like km_emotion_clip_create, except that the window limit is the stream back end's:
+ *                                    C <= 2^20 samples (65.5 s), else KM_ERR_UNSUPPORTED.  Holds a prosody plan; scratch is the
+ *                                    slot table and max_slots x (1 + C / 512) x 4 floats of frame records
+ *   km_emotion_clip_width            256 or 9: the row width of the object's tracks (host only; 0 for a NULL object)
+ * On such an object
+ *   km_emotion_clip_set_compression  KM_ERR_INVALID_ARG; no call is needed before the first build
+ *   km_emotion_clip_build            emotion_out (K, 9); features_out must be NULL (KM_ERR_INVALID_ARG otherwise: there are no
+ *                                    functionals).  The windows are read in place and every pass writes its rows straight into
+ *                                    emotion_out (empty slots write nothing), so rows beyond K are never touched
+ *   km_emotion_clip_build_batch      emotion_out (B, K, 9), features_out NULL; each clip's slice bit-identical to build of that clip
+ *   km_emotion_clip_rows             emotion_track_dev (K, 9) -> emotion_out (B, 9); one launch of ceil(B / 16) workgroups
+ *   km_emotion_clip_num_rows         unchanged
+ * and, as above, none of them allocates, synchronises or reads back. */
+int km_emotion_clip_create_basic(void** ec, double context_window_s, double update_interval_s, int64_t max_slots);
+int km_emotion_clip_width(void* ec);
 
 /* ---- evaluation metrics: a streaming accumulator in device memory ------------------------------------------------
  * Replaces BlendshapeMetrics (src/model/losses.py:421-521) and compute_lip_sync_metrics (:524-583).  The reference

@@ -231,6 +231,8 @@ SIGNATURES = {
     "km_prosody_features": (C.c_int, [_p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p]),
     "km_prosody_windows": (C.c_int, [_p, _p, _i64, _p, _i64, _i64, _p, _i64, _p, _p]),
     "km_emotion_clip_create": (C.c_int, [C.POINTER(_p), C.c_double, C.c_double, _i64]),
+    "km_emotion_clip_create_basic": (C.c_int, [C.POINTER(_p), C.c_double, C.c_double, _i64]),
+    "km_emotion_clip_width": (C.c_int, [_p]),
     "km_emotion_clip_destroy": (C.c_int, [_p]),
     "km_emotion_clip_set_compression": (C.c_int, [_p, _p, _p, _p]),
     "km_emotion_clip_num_rows": (_i64, [_p, _i64]),

@@ -11,6 +11,12 @@
 //   ecb_epilogue_kernel  passes across clip boundaries, the clips are the B "rings", and a row takes its OWN clip's features[0]
 //   ec_rows_kernel       window -> row: e = min(n, (s + T) h), k = clamp((e - MIN) / U, 0, K - 1), a 256-float copy per window
 // build and rows neither allocate, synchronise nor read back; rows' grid depends on the batch alone, so it captures into a hipGraph.
+//
+// The `basic` back end (km_emotion_clip_create_basic): the same slot law and the same row mapping, but a row is the nine raw prosodic
+// values of its window as km_emotion_stream_create_basic's streams hold them.  ec_plan_kernel / ecb_plan_kernel write the table,
+// prosody_ragged (km_prosody.hip) reads the windows in place from the clip and writes slot i to row i of the pointer it is handed --
+// which is track row k0 (or g0) of the caller's output, since it skips empty slots: no staging copy, no epilogue.
+//   ec_rows9_kernel      ec_rows_kernel's mapping at width 9: sixteen windows per workgroup, sixteen lanes a window (nine of them copy)
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -19,6 +25,7 @@
 
 #include "km_context.h"
 #include "km_egemaps_ragged.h"
+#include "km_prosody_ragged.h"
 
 namespace km {
 
@@ -28,6 +35,8 @@ constexpr int SR = 16000, NFEAT = 88, NCAT = 3 * NFEAT, NEMO = 256, REC = 36, MA
 constexpr int TN = 16, TM = 16;          // the epilogue's tile: output columns per workgroup, rows per turn (TN * TM = 256 threads)
 constexpr int WS = NCAT + 1;             // LDS stride of a weight row: 265 is odd, so the 16 columns of a half wave hit 16 banks
 constexpr int64_t MAX_CLIP = (int64_t)1 << 30;     // egm_ragged_functionals' ring limit; EgmSlot.start is an int32
+constexpr int NBASIC = 9, BASIC_REC = 4, BASIC_HOP = 512, BASIC_MAX_WINDOW = 1 << 20;   // the `basic` back end (km_prosody.hip)
+constexpr int RW = 16;                   // ec_rows9_kernel: windows per workgroup, and the lanes a window takes
 }  // namespace ec
 
 struct EmotionClip {
@@ -43,7 +52,9 @@ struct EmotionClip {
     float* w = nullptr;        // (256, 264) as nn.Linear stores it
     float* bias = nullptr;     // (256)
     bool has_compression = false;
-    ~EmotionClip() { (void)km_egemaps_plan_destroy(plan); }
+    bool basic = false;        // the `basic` back end: rows of 9, rec is (max_slots, max_nf, 4), no scale / fout / f0 / w / bias
+    void* prosody = nullptr;
+    ~EmotionClip() { (void)km_egemaps_plan_destroy(plan); (void)km_prosody_plan_destroy(prosody); }
 };
 
 static int64_t ec_num_rows(const EmotionClip* e, int64_t clip_len) {
@@ -195,6 +206,26 @@ __global__ __launch_bounds__(256) void ec_rows_kernel(const float* __restrict__ 
     if (valid && tid == 0) valid[b] = K > 0 ? 1 : 0;
 }
 
+// ---- the same mapping at width 9: window b = 16 blockIdx.x + tid / 16, column tid % 16 (columns 9 .. 15 idle); the row law is the
+// only division ----
+__global__ __launch_bounds__(256) void ec_rows9_kernel(const float* __restrict__ track, int64_t K, int64_t clip_len, const int32_t* __restrict__ starts,
+                                                       int64_t B, int64_t hop, int64_t window_frames, int update_samples, int min_samples,
+                                                       float* __restrict__ out, uint8_t* __restrict__ valid) {
+    const int tid = threadIdx.x, c = tid % ec::RW;                               // RW is a power of two: a mask and a shift
+    const int64_t b = (int64_t)blockIdx.x * ec::RW + tid / ec::RW;
+    if (b >= B || c >= ec::NBASIC) return;
+    float v = 0.f;
+    if (K > 0) {
+        int64_t e = ((int64_t)starts[b] + window_frames) * hop;
+        if (e > clip_len) e = clip_len;
+        int64_t k = e < min_samples ? 0 : (e - min_samples) / update_samples;
+        if (k > K - 1) k = K - 1;
+        v = track[k * ec::NBASIC + c];
+    }
+    out[b * ec::NBASIC + c] = v;
+    if (valid && c == 0) valid[b] = K > 0 ? 1 : 0;
+}
+
 static int64_t ec_align16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
 
 }  // namespace km
@@ -242,6 +273,42 @@ int km_emotion_clip_create(void** ec_out, double context_window_s, double update
     return KM_OK;
 }
 
+int km_emotion_clip_create_basic(void** ec_out, double context_window_s, double update_interval_s, int64_t max_slots) {
+    using namespace ec;
+    if (!ec_out) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_create_basic: NULL argument");
+    *ec_out = nullptr;
+    if (!(context_window_s >= 1.0)) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_create_basic: Context window must be at least 1.0 seconds");
+    if (!(update_interval_s >= 0.1)) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_create_basic: Update interval must be at least 0.1 seconds");
+    if (update_interval_s > context_window_s)
+        return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_create_basic: Update interval cannot be larger than context window");
+    if (max_slots < 1 || max_slots > 65535)
+        return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_create_basic: max_slots %lld, 1 .. 65535", (long long)max_slots);
+    if (context_window_s > 3600.0) return fail(KM_ERR_UNSUPPORTED, "km_emotion_clip_create_basic: context window of %g s", context_window_s);
+    const int64_t R = (int64_t)((context_window_s + 2.0) * SR), Cw = (int64_t)(context_window_s * SR);
+    const int64_t C = Cw < R ? Cw : R, U = (int64_t)(update_interval_s * SR), MIN = (int64_t)(0.5 * SR);
+    if (C > BASIC_MAX_WINDOW)
+        return fail(KM_ERR_UNSUPPORTED, "km_emotion_clip_create_basic: a window of %lld samples, at most %d (65.5 s)", (long long)C, BASIC_MAX_WINDOW);
+    const int64_t nf = 1 + C / BASIC_HOP;                                        // 32 ms frame records per window
+    std::unique_ptr<EmotionClip> e(new (std::nothrow) EmotionClip());
+    if (!e) return fail(KM_ERR_HIP, "km_emotion_clip_create_basic: out of host memory");
+    e->max_slots = max_slots; e->basic = true;
+    e->ring_len = (int)R; e->window_len = (int)C; e->update_samples = (int)U; e->min_samples = (int)MIN; e->max_nf = (int)nf;
+    if (const int rc = km_prosody_plan_create(&e->prosody)) return rc;
+    const int64_t table_bytes = ec_align16(max_slots * (int64_t)sizeof(EgmSlot));
+    const int64_t bytes = table_bytes + ec_align16(max_slots * nf * BASIC_REC * 4);
+    if (int rc = e->blob.alloc(bytes, "km_emotion_clip_create_basic")) return rc;
+    HIP_TRY(hipMemset(e->blob, 0, (size_t)bytes));
+    e->table = reinterpret_cast<EgmSlot*>((char*)e->blob);
+    e->rec = reinterpret_cast<float*>((char*)e->blob + table_bytes);
+    *ec_out = e.release();
+    return KM_OK;
+}
+
+int km_emotion_clip_width(void* ec) {
+    if (!ec) return 0;
+    return static_cast<EmotionClip*>(ec)->basic ? ec::NBASIC : ec::NEMO;
+}
+
 int km_emotion_clip_destroy(void* ec) {
     if (!ec) return KM_OK;
     delete static_cast<EmotionClip*>(ec);
@@ -251,6 +318,7 @@ int km_emotion_clip_destroy(void* ec) {
 int km_emotion_clip_set_compression(void* ec, const float* w_dev, const float* b_dev, void* stream) {
     if (!ec || !w_dev || !b_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_set_compression: NULL argument");
     EmotionClip* e = static_cast<EmotionClip*>(ec);
+    if (e->basic) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_set_compression: the basic back end has no compression layer");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(e->w, w_dev, (size_t)ec::NEMO * ec::NCAT * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(e->bias, b_dev, ec::NEMO * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -268,12 +336,23 @@ int km_emotion_clip_build(void* ec, const float* clip_dev, int64_t clip_len, flo
     EmotionClip* e = static_cast<EmotionClip*>(ec);
     if (clip_len < 0 || clip_len > ec::MAX_CLIP)
         return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build: clip of %lld samples, 0 .. 2^30 (window starts are 32-bit)", (long long)clip_len);
-    if (!e->has_compression) return fail(KM_ERR_NOT_READY, "km_emotion_clip_build: km_emotion_clip_set_compression first");
+    if (e->basic && features_out) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build: the basic back end has no functionals (features_out)");
+    if (!e->basic && !e->has_compression) return fail(KM_ERR_NOT_READY, "km_emotion_clip_build: km_emotion_clip_set_compression first");
     const int64_t K = ec_num_rows(e, clip_len);
     if (K == 0) return KM_OK;                                                    // shorter than half a second: a track without rows
     if (!clip_dev || !emotion_out) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build: NULL argument");
     hipStream_t st = (hipStream_t)stream;
     const int ms = (int)e->max_slots;
+    if (e->basic) {
+        for (int64_t k0 = 0; k0 < K; k0 += ms) {                                 // slot i of the pass is row k0 + i; slots past K are empty
+            hipLaunchKernelGGL(ec_plan_kernel, dim3((unsigned)((ms + 255) / 256)), dim3(256), 0, st, k0, K, ms, e->ring_len, e->window_len,
+                               e->update_samples, e->min_samples, e->table);
+            HIP_TRY(hipGetLastError());
+            if (const int rc = prosody_ragged(e->prosody, clip_dev, clip_len, e->table, ms, e->max_nf, e->rec, emotion_out + k0 * ec::NBASIC, st))
+                return rc;
+        }
+        return KM_OK;
+    }
     for (int64_t k0 = 0; k0 < K; k0 += ms) {                                     // pass 0 first: it leaves features[0] in f0
         const int rows = (int)(K - k0 < ms ? K - k0 : ms);
         hipLaunchKernelGGL(ec_plan_kernel, dim3((unsigned)((ms + 255) / 256)), dim3(256), 0, st, k0, K, ms, e->ring_len, e->window_len,
@@ -293,11 +372,27 @@ int km_emotion_clip_build_batch(void* ec, const float* clips_dev, int64_t B, int
     if (B < 0 || L < 0 || L > ec::MAX_CLIP)
         return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build_batch: %lld clips of %lld samples, 0 .. 2^30 (window starts are 32-bit)",
                     (long long)B, (long long)L);
-    if (!e->has_compression) return fail(KM_ERR_NOT_READY, "km_emotion_clip_build_batch: km_emotion_clip_set_compression first");
+    if (e->basic && features_out)
+        return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build_batch: the basic back end has no functionals (features_out)");
+    if (!e->basic && !e->has_compression) return fail(KM_ERR_NOT_READY, "km_emotion_clip_build_batch: km_emotion_clip_set_compression first");
     const int64_t K = ec_num_rows(e, L);
     if (K == 0 || B == 0) return KM_OK;
     if (B > 0x7fffffff / K)
         return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build_batch: %lld clips x %lld rows, at most 2^31 - 1 rows", (long long)B, (long long)K);
+    if (e->basic) {
+        if (!clips_dev || !emotion_out) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build_batch: NULL argument");
+        hipStream_t st = (hipStream_t)stream;
+        const int ms = (int)e->max_slots;
+        const int64_t G = B * K;
+        for (int64_t g0 = 0; g0 < G; g0 += ms) {                                 // slot i of the pass is row g0 + i of (B, K, 9)
+            hipLaunchKernelGGL(ecb_plan_kernel, dim3((unsigned)((ms + 255) / 256)), dim3(256), 0, st, g0, G, K, ms, e->ring_len, e->window_len,
+                               e->update_samples, e->min_samples, e->table);
+            HIP_TRY(hipGetLastError());
+            if (const int rc = prosody_ragged(e->prosody, clips_dev, L, e->table, ms, e->max_nf, e->rec, emotion_out + g0 * ec::NBASIC, st))
+                return rc;
+        }
+        return KM_OK;
+    }
     // features_out is read back by the passes that follow a clip's row 0, so it is not optional here
     if (!clips_dev || !features_out || !emotion_out) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_build_batch: NULL argument");
     hipStream_t st = (hipStream_t)stream;
@@ -330,8 +425,14 @@ int km_emotion_clip_rows(void* ec, const float* emotion_track_dev, int64_t K, in
                     (long long)window_frames);
     if (B == 0) return KM_OK;
     if (!start_frames_dev || !emotion_out || (K > 0 && !emotion_track_dev)) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_rows: NULL argument");
-    hipLaunchKernelGGL(ec_rows_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, emotion_track_dev, K, clip_len, start_frames_dev, hop,
-                       window_frames, e->update_samples, e->min_samples, emotion_out, valid_out);
+    if (e->basic) {
+        hipLaunchKernelGGL(ec_rows9_kernel, dim3((unsigned)((B + ec::RW - 1) / ec::RW)), dim3(ec::RW * ec::RW), 0, (hipStream_t)stream,
+                           emotion_track_dev, K, clip_len, start_frames_dev, B, hop, window_frames, e->update_samples, e->min_samples, emotion_out,
+                           valid_out);
+    } else {
+        hipLaunchKernelGGL(ec_rows_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, emotion_track_dev, K, clip_len, start_frames_dev, hop,
+                           window_frames, e->update_samples, e->min_samples, emotion_out, valid_out);
+    }
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

@@ -28,11 +28,21 @@ class ClipEmotion:
 
     ``compression_layer``: ``StreamEmotion``'s contract -- a ``torch.nn.Linear(264, 256)``, created with torch's default
     initialisation when absent, copied at construction; hand the same layer to the server's ``StreamEmotion``.
-    ``track_for(key, clip)`` keeps built tracks on the device: the layer is fixed, so a clip is extracted once per run."""
+    ``track_for(key, clip)`` keeps built tracks on the device: the layer is fixed, so a clip is extracted once per run.
+
+    ``backend="basic"`` (km_emotion_clip_create_basic): the same windows and the same window -> row mapping, but a row is the nine
+    raw prosodic values of its window -- bit for bit what a ``StreamEmotion(1, context_window, update_interval, backend="basic")``
+    stream holds after that many samples, and bit for bit ``BasicEmotion()(window[None])[0]``.  ``emotion_dim`` is 9, the input of a
+    model with ``emotion_dim`` 9; ``build`` -> ``(emotion (K, 9), None)``, ``build_batch`` -> ``((B, K, 9), None)``, ``rows`` takes and
+    returns width 9.  There is no compression layer (passing one raises ``ValueError``); the window may hold up to 2**20 samples and
+    the scratch is ``max_slots`` x ``(1 + window_len // 512)`` x 4 floats."""
 
     def __init__(self, context_window: float = 20.0, update_interval: float = 0.3, max_slots: int = 64,
-                 compression_layer: Optional[torch.nn.Module] = None, device="cuda"):
-        self.shape = emotion_stream_shape(context_window, update_interval)
+                 compression_layer: Optional[torch.nn.Module] = None, device="cuda", backend: str = "egemaps"):
+        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend)
+        self.backend = backend
+        if backend == "basic" and compression_layer is not None:
+            raise ValueError("the basic back end has no compression layer: its nine features are the emotion input as they are")
         if not 1 <= max_slots <= 65535:
             raise ValueError(f"expected 1 <= max_slots <= 65535, got {max_slots}")
         if not torch.cuda.is_available():
@@ -42,18 +52,25 @@ class ClipEmotion:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._lib = _lib.load()
-        if compression_layer is None:
-            compression_layer = torch.nn.Linear(264, 256)
-        if tuple(compression_layer.weight.shape) != (256, 264):
-            raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
-        self.compression_layer = compression_layer
         self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            check(self._lib.km_emotion_clip_create(C.byref(self._h), context_window, update_interval, max_slots))
-            w = compression_layer.weight.detach().to(self.device, torch.float32).contiguous()
-            b = compression_layer.bias.detach().to(self.device, torch.float32).contiguous()
-            check(self._lib.km_emotion_clip_set_compression(self._h, _ptr(w), _ptr(b), _stream_ptr(self.device)))
-            torch.cuda.current_stream(self.device).synchronize()          # w and b may go once the copy is done
+        if backend == "basic":
+            self.compression_layer = None
+            self.emotion_dim = 9
+            with torch.cuda.device(self.device):
+                check(self._lib.km_emotion_clip_create_basic(C.byref(self._h), context_window, update_interval, max_slots))
+        else:
+            if compression_layer is None:
+                compression_layer = torch.nn.Linear(264, 256)
+            if tuple(compression_layer.weight.shape) != (256, 264):
+                raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
+            self.compression_layer = compression_layer
+            self.emotion_dim = 256
+            with torch.cuda.device(self.device):
+                check(self._lib.km_emotion_clip_create(C.byref(self._h), context_window, update_interval, max_slots))
+                w = compression_layer.weight.detach().to(self.device, torch.float32).contiguous()
+                b = compression_layer.bias.detach().to(self.device, torch.float32).contiguous()
+                check(self._lib.km_emotion_clip_set_compression(self._h, _ptr(w), _ptr(b), _stream_ptr(self.device)))
+                torch.cuda.current_stream(self.device).synchronize()      # w and b may go once the copy is done
         self._tracks: Dict[Hashable, Tuple[torch.Tensor, int]] = {}
         self.builds = 0                                                   # calls of build() / build_batch(), track_for's misses included
 
@@ -77,31 +94,34 @@ class ClipEmotion:
             raise ValueError(f"expected a 1-D float32 clip on the device, got {tuple(clip.shape)} {clip.dtype} on {clip.device}")
         return clip.contiguous()
 
-    def build(self, clip: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """clip (n) fp32 on the device -> (emotion (K, 256), features (K, 88)).  No synchronisation."""
+    def build(self, clip: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """clip (n) fp32 on the device -> (emotion (K, 256), features (K, 88)); (emotion (K, 9), None) on the basic back end.
+        No synchronisation."""
         clip = self._check_clip(clip)
         n = clip.shape[0]
         K = self.num_rows(n)
-        emotion = torch.empty(K, 256, device=clip.device)
-        features = torch.empty(K, 88, device=clip.device)
+        emotion = torch.empty(K, self.emotion_dim, device=clip.device)
+        features = torch.empty(K, 88, device=clip.device) if self.backend != "basic" else None
         with torch.cuda.device(clip.device):
-            check(self._lib.km_emotion_clip_build(self._h, _ptr(clip), n, _ptr(features), _ptr(emotion), _stream_ptr(clip.device)))
+            check(self._lib.km_emotion_clip_build(self._h, _ptr(clip), n, _ptr(features) if features is not None else None, _ptr(emotion),
+                                                  _stream_ptr(clip.device)))
         self.builds += 1
         return emotion, features
 
-    def build_batch(self, clips: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """clips (B, L) fp32 on the device, B clips of one length -> (emotion (B, K, 256), features (B, K, 88)); every clip's slice
-        is bit-identical to ``build`` of that clip.  The passes of ``max_slots`` windows are filled across clip boundaries
+    def build_batch(self, clips: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """clips (B, L) fp32 on the device, B clips of one length -> (emotion (B, K, 256), features (B, K, 88)) -- ((B, K, 9), None) on
+        the basic back end --; every clip's slice is bit-identical to ``build`` of that clip.  The passes of ``max_slots`` windows are filled across clip boundaries
         (km_emotion_clip_build_batch), so short clips do not leave them mostly empty.  One build in ``builds``; no synchronisation."""
         if clips.dim() != 2 or clips.dtype != torch.float32 or not clips.is_cuda:
             raise ValueError(f"expected (B, L) float32 clips on the device, got {tuple(clips.shape)} {clips.dtype} on {clips.device}")
         clips = clips.contiguous()
         B, L = clips.shape
         K = self.num_rows(L)
-        emotion = torch.empty(B, K, 256, device=clips.device)
-        features = torch.empty(B, K, 88, device=clips.device)
+        emotion = torch.empty(B, K, self.emotion_dim, device=clips.device)
+        features = torch.empty(B, K, 88, device=clips.device) if self.backend != "basic" else None
         with torch.cuda.device(clips.device):
-            check(self._lib.km_emotion_clip_build_batch(self._h, _ptr(clips), B, L, _ptr(features), _ptr(emotion), _stream_ptr(clips.device)))
+            check(self._lib.km_emotion_clip_build_batch(self._h, _ptr(clips), B, L, _ptr(features) if features is not None else None,
+                                                        _ptr(emotion), _stream_ptr(clips.device)))
         self.builds += 1
         return emotion, features
 
@@ -109,17 +129,19 @@ class ClipEmotion:
              out: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
         """track (K, 256) of a clip of ``clip_len`` samples, start_frames_dev (B) int32 on the device -> (B, 256): every window's
         row.  ``out`` (B, 256) fp32 and ``valid`` (B) uint8 are written in place when given (static buffers of a captured step);
-        ``valid`` is 1 where the clip has a track at all.  One gather kernel, no synchronisation."""
+        ``valid`` is 1 where the clip has a track at all.  One gather kernel, no synchronisation.  On the basic back end the
+        width is 9 throughout."""
+        D = self.emotion_dim
         if start_frames_dev.dim() != 1 or start_frames_dev.dtype != torch.int32 or not start_frames_dev.is_cuda:
             raise ValueError("expected (B,) int32 start frames on the device")
-        if track.dim() != 2 or track.shape[1] != 256 or track.dtype != torch.float32:
-            raise ValueError(f"expected a (K, 256) float32 track, got {tuple(track.shape)} {track.dtype}")
+        if track.dim() != 2 or track.shape[1] != D or track.dtype != torch.float32:
+            raise ValueError(f"expected a (K, {D}) float32 track, got {tuple(track.shape)} {track.dtype}")
         B = start_frames_dev.shape[0]
         dev = start_frames_dev.device
         if out is None:
-            out = torch.empty(B, 256, device=dev)
-        elif tuple(out.shape) != (B, 256) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError(f"expected a contiguous ({B}, 256) float32 out")
+            out = torch.empty(B, D, device=dev)
+        elif tuple(out.shape) != (B, D) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"expected a contiguous ({B}, {D}) float32 out")
         if valid is not None and (tuple(valid.shape) != (B,) or valid.dtype != torch.uint8):
             raise ValueError(f"expected a ({B},) uint8 valid")
         track, starts = track.contiguous(), start_frames_dev.contiguous()

@@ -11,7 +11,9 @@ call with the head-averaged attention map of every window written as well (km_se
 
 Not in the reference: ``clip_emotion`` (a ``koemorph_amd.features.ClipEmotion``) or ``forward(emotion_track=...)`` give every
 window the row of the clip's eGeMAPS emotion track that a live stream would hold when the window ends -- the input
-``train_sequential --emotion egemaps`` trains on -- instead of one vector per clip (km_sequence_forward_track).
+``train_sequential --emotion egemaps`` trains on -- instead of one vector per clip (km_sequence_forward_track).  With a
+``ClipEmotion(backend="basic")`` and ``emotion_config={"backend": "basic"}`` (emotion_dim 9) the track holds the nine prosodic values
+per row (``--emotion basic``) and 'emotion_backend' reports ``basic_track``.
 ``share_frames=True`` computes each clip's STFT once at every model shape and hop and assembles the windows on the device (engine
 option "seq_assemble"); the default leaves the engine's schedule as it is.
 """
@@ -56,6 +58,9 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
         # chunks, one per rank, and smoothed once over the gathered sequence (koemorph_amd.parallel.sequence_apply)
         self.shard_across_ranks = shard_across_ranks
         # not in the reference either: the clips' emotion tracks, built per forward call (ClipEmotion.build_batch)
+        width = getattr(clip_emotion, "emotion_dim", self.emotion_dim)       # an object that only maps windows to rows names none
+        if width != self.emotion_dim:
+            raise ValueError(f"clip_emotion produces rows of {width} values, the model's emotion_dim is {self.emotion_dim}")
         self.clip_emotion = clip_emotion
         # not in the reference: each clip's STFT once at every shape and hop, the windows assembled on the device (engine option
         # "seq_assemble", Engine.sequence_plan route 2); off, the engine keeps its default schedule for the shape
@@ -88,11 +93,11 @@ class SequentialDualStreamModel(SimplifiedDualStreamModel):
         elif emotion_features is None and self.clip_emotion is not None:
             mapping = self._track_mapping()
             emotion_track, _ = self.clip_emotion.build_batch(audio.to(torch.float32).contiguous())
-            emotion_metadata = {"backend_used": "egemaps_track"}
+            emotion_metadata = {"backend_used": getattr(self.clip_emotion, "backend", "egemaps") + "_track"}     # or 'basic_track'
         elif emotion_features is None:                                 # emotion features ONCE per clip (:88)
             emotion_features, emotion_metadata = self.extract_emotion_features(audio)
         if mapping is not None:
-            if emotion_track.dim() != 3 or emotion_track.shape[0] != batch_size:
+            if emotion_track.dim() != 3 or emotion_track.shape[0] != batch_size or emotion_track.shape[2] != self.emotion_dim:
                 raise ValueError(f"expected a ({batch_size}, K, {self.emotion_dim}) emotion_track, got {tuple(emotion_track.shape)}")
             if emotion_track.shape[1] == 0:                            # no update yet: the zero vector ClipEmotion.rows gives
                 emotion_track = torch.zeros(batch_size, 1, emotion_track.shape[2], device=audio.device)

@@ -22,6 +22,7 @@ a warning and uses ``randn * 0.1`` dummy features.
 from __future__ import annotations
 
 import logging
+import weakref
 from typing import Any, Callable, Dict, Optional, Tuple, Union
 
 import numpy as np
@@ -102,12 +103,15 @@ class SimplifiedDualStreamModel(nn.Module):
 
         if self.real_time_mode:
             from ..features.mel_sliding_window import MelSlidingWindowExtractor
+            # the extractor reaches the engine through a weak reference: a strong one would close a cycle model -> extractor ->
+            # getter -> model, and the engine's device memory would then wait for a cyclic collection instead of going with the model
+            me = weakref.ref(self)
             self.mel_extractor = MelSlidingWindowExtractor(
                 context_window=self.mel_context_window, update_interval=self.mel_update_interval,
                 sample_rate=sample_rate, n_mels=self.n_mels, n_fft=mel_config.get("n_fft", 1024),
                 hop_length=self.hop_length, f_min=mel_config.get("f_min", 80.0),
                 f_max=mel_config.get("f_max", sample_rate // 2), device=device,
-                engine_getter=lambda: self.dual_stream_attention.engine())
+                engine_getter=lambda: me().dual_stream_attention.engine())
         else:
             self.mel_extractor = None
 

@@ -1,14 +1,16 @@
 """Offline rendering of one audio file with a ``train_sequential`` checkpoint:
 
     python -m koemorph_amd.scripts.render_sequential --model_path ckpt.pth --input_audio a.wav --output_json out.jsonl
-                                                     [--stride 1] [--emotion egemaps|noise] [--attention-summary summary.json]
+                                                     [--stride 1] [--emotion egemaps|basic|noise] [--attention-summary summary.json]
                                                      [--share-frames]
 
 The clip goes through ``SequentialDualStreamModel.forward`` (one output frame per window position, EMA along the clip) and every
 frame is written as one ``{"timestamp", "blendshapes"}`` line, encoded by ``koemorph_amd.wire`` as the streaming scripts encode
 theirs.  A frame's timestamp is the time at which its window ends.  ``--emotion egemaps`` gives every window the row of the
 clip's eGeMAPS emotion track a live stream would hold at that time (``ClipEmotion``), the input ``train_sequential --emotion
-egemaps`` trains on; ``noise`` is the reference's extraction-failure fallback, one ``0.1 * randn`` vector per clip.
+egemaps`` trains on; ``basic`` is the same with the nine prosodic values per row (``ClipEmotion(backend="basic")``), for
+checkpoints trained with ``--variant basic --emotion basic``; ``noise`` is the reference's extraction-failure fallback, one
+``0.1 * randn`` vector per clip.  The checkpoint's ``model_config["emotion_dim"]`` (256 when absent) sizes the model.
 ``--attention-summary`` writes what the reference's AttentionVisualizer reduces the clip's attention maps to (``AttentionStats``:
 mean map, mean entropy and peak histogram per mouth query, mean and share per frequency band) as one JSON object; the maps are
 reduced on the device tile by tile, no (frames, 28, 80) array is made.  ``--share-frames`` computes the clip's STFT once at every
@@ -55,13 +57,21 @@ def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: st
                share_frames: bool = False) -> SequentialDualStreamModel:
     ckpt = torch.load(model_path, map_location="cpu", weights_only=True)
     cfg = dict(ckpt.get("model_config") or {})
+    emotion_dim = int(cfg.get("emotion_dim", 256))
+    width = {"egemaps": 256, "basic": 9}.get(emotion)
+    if width is not None and width != emotion_dim:
+        raise ValueError(f"--emotion {emotion} produces {width} values per window, the checkpoint's emotion_dim is {emotion_dim}")
     clip_emotion: Optional[ClipEmotion] = None
     if emotion == "egemaps":
         layer, source = compression_layer(ckpt)
         logger.info("emotion track: eGeMAPS, compression layer from the %s", source)
         clip_emotion = ClipEmotion(compression_layer=layer, device=device)
+    elif emotion == "basic":
+        logger.info("emotion track: the nine basic prosodic values per row")
+        clip_emotion = ClipEmotion(device=device, backend="basic")
     model = SequentialDualStreamModel(d_model=int(cfg.get("d_model", 256)), num_heads=int(cfg.get("num_heads", 8)),
                                       mel_sequence_length=int(cfg.get("mel_sequence_length", 256)), stride_frames=stride,
+                                      emotion_config={"emotion_dim": emotion_dim, "backend": "basic" if emotion_dim == 9 else "opensmile"},
                                       device=device, clip_emotion=clip_emotion, share_frames=share_frames)
     model.load_state_dict(ckpt["model_state_dict"])
     return model.to(device).eval()
@@ -118,7 +128,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--input_audio", required=True)
     p.add_argument("--output_json", required=True)
     p.add_argument("--stride", type=int, default=1, help="frames between two window positions")
-    p.add_argument("--emotion", choices=("egemaps", "noise"), default="egemaps")
+    p.add_argument("--emotion", choices=("egemaps", "noise", "basic"), default="egemaps",
+                   help="basic: the clip's track of nine prosodic values per row, for checkpoints of train_sequential --variant basic "
+                        "--emotion basic (emotion_dim 9); a back end whose width is not the checkpoint's emotion_dim is refused")
     p.add_argument("--attention-summary", default=None, metavar="PATH",
                    help="write the clip's attention statistics (AttentionStats.compute()) as JSON")
     p.add_argument("--device-resample", dest="device_resample", action="store_true",

@@ -12,8 +12,10 @@ The reference's ``MultiTaskLoss`` does not exist in its ``src/model/losses.py``;
 (mse + optional terms, src/model/losses.py:29-178) against the label of each window's last frame.  The 256-D emotion
 vector is an input of the model: a ``ClipEmotion`` (``--emotion egemaps``) gives every window the row of its clip's eGeMAPS
 emotion track that a live stream would hold when the window ends, gathered by start frame, so the step stays on the resident
-clip; ``emotion_provider(audio) -> (B, 256)`` is handed window audio instead; without either the reference's own failure
-fallback is used (``randn * 0.1``, simplified_dual_stream_model.py:250-267), seeded per window for reproducibility.
+clip; ``--variant basic --emotion basic`` is the same at the ``basic`` shape (d_model 128, 4 heads, emotion_dim 9) with the track of
+nine prosodic values per row (``ClipEmotion(backend="basic")``); ``emotion_provider(audio) -> (B, emotion_dim)`` is handed window
+audio instead; without either the reference's own failure fallback is used (``randn * 0.1`` of the engine's emotion width,
+simplified_dual_stream_model.py:250-267), seeded per window for reproducibility.
 No hydra / TensorBoard dependency: plain argparse, metrics to the log.
 """
 from __future__ import annotations
@@ -61,6 +63,9 @@ class SequentialTrainer:
         self.train_data, self.val_data = train_data, val_data
         if clip_emotion is not None and emotion_provider is not None:
             raise ValueError("clip_emotion and emotion_provider both produce the emotion input: pass one of them")
+        if clip_emotion is not None and clip_emotion.emotion_dim != engine.emotion_dim:
+            raise ValueError(f"clip_emotion produces rows of {clip_emotion.emotion_dim} values ({clip_emotion.backend} back end), "
+                             f"the engine's emotion_dim is {engine.emotion_dim}")
         self.emotion_provider = emotion_provider
         self.clip_emotion = clip_emotion
         self.from_clip = from_clip
@@ -94,7 +99,8 @@ class SequentialTrainer:
             return ce.rows(track, clip.shape[0], batch["start_frames_dev"], ds.hop_length, ds.window_frames)
         if self.emotion_provider is not None:
             return self.emotion_provider(batch["audio"]).to(self.device, torch.float32)
-        rows = [0.1 * synth.normal(1000003 * int(f) + int(w), (256,)) for f, w in zip(batch["file_indices"], batch["window_indices"])]
+        D = self.engine.emotion_dim
+        rows = [0.1 * synth.normal(1000003 * int(f) + int(w), (D,)) for f, w in zip(batch["file_indices"], batch["window_indices"])]
         return torch.from_numpy(np.stack(rows)).to(self.device)
 
     def _my_share(self, batch):
@@ -296,7 +302,9 @@ class SequentialTrainer:
                 "best_val_loss": self.best_val_loss, "optimizer_state_dict": self.trainer.optimizer_state(),
                 "current_file_idx": -1 if self.current_file_idx is None else int(self.current_file_idx),
                 "model_config": {"d_model": self.engine.d_model, "num_heads": self.engine.num_heads,
-                                 "mel_sequence_length": self.engine.mel_sequence_length}}
+                                 "mel_sequence_length": self.engine.mel_sequence_length, "emotion_dim": self.engine.emotion_dim,
+                                 "emotion_backend": self.clip_emotion.backend if self.clip_emotion is not None else
+                                 ("provider" if self.emotion_provider is not None else "noise")}}
         if self.rank == 0:
             torch.save(ckpt, path)
             if is_best:
@@ -328,7 +336,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--val_dir", help="validation directory (optional)")
     p.add_argument("--epochs", type=int, default=10)
     p.add_argument("--batch_size", type=int, default=8, help="windows per step over ALL ranks")
-    p.add_argument("--window_frames", type=int, default=256)
+    p.add_argument("--window_frames", type=int, default=256, help="frames per window (with --variant: the variant's unless given)")
     p.add_argument("--stride_frames", type=int, default=1)
     p.add_argument("--learning_rate", type=float, default=1e-4)
     p.add_argument("--weight_decay", type=float, default=1e-5)
@@ -350,32 +358,64 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loss-components", dest="loss_components", action="store_true",
                    help="validation reports the loss by component (LossTerms) and per-sequence loss / smoothness; with "
                         "--resident-clip the validation forward runs from the resident clip (Engine.forward_clip)")
-    p.add_argument("--emotion", choices=("noise", "egemaps"), default="noise",
+    p.add_argument("--emotion", choices=("noise", "egemaps", "basic"), default="noise",
                    help="the model's emotion input: noise = the reference's extraction-failure fallback (randn * 0.1 per window); "
                         "egemaps = each clip's eGeMAPS emotion track, computed once on the device and gathered by start frame "
-                        "(ClipEmotion; implies resident batches, what a StreamEmotion serves at inference)")
+                        "(ClipEmotion; implies resident batches, what a StreamEmotion serves at inference); basic = the same track "
+                        "of nine prosodic values per row (ClipEmotion(backend='basic'), what StreamEmotion(backend='basic') serves; "
+                        "needs an emotion_dim of 9: --variant basic)")
+    p.add_argument("--variant", choices=tuple(VARIANTS), default="default",
+                   help="the model shape, as configs/model/dual_stream.yaml names its variants: d_model, heads, emotion_dim and the "
+                        "default of --window_frames")
     p.add_argument("--metrics", action="store_true", help="log mae / rmse / mean_correlation / f1_score of every epoch (BlendshapeMetrics)")
     return p
 
 
+# d_model, num_heads, mel_sequence_length, emotion_dim of configs/model/dual_stream.yaml and its `variants`
+VARIANTS = {"default": dict(d_model=256, num_heads=8, window_frames=256, emotion_dim=256),
+            "fast": dict(d_model=128, num_heads=4, window_frames=128, emotion_dim=256),
+            "basic": dict(d_model=128, num_heads=4, window_frames=256, emotion_dim=9),
+            "long_context": dict(d_model=512, num_heads=16, window_frames=512, emotion_dim=256)}
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    """The command line with the variant resolved: ``d_model``, ``num_heads`` and ``emotion_dim`` are the variant's, ``window_frames``
+    is the variant's unless --window_frames is given.  ``--emotion basic`` with an emotion_dim other than 9 is a usage error."""
+    p = build_parser()
+    p.set_defaults(window_frames=None)                   # None: not given on the command line
+    args = p.parse_args(argv)
+    v = VARIANTS[args.variant]
+    args.d_model, args.num_heads, args.emotion_dim = v["d_model"], v["num_heads"], v["emotion_dim"]
+    if args.window_frames is None:
+        args.window_frames = v["window_frames"]
+    if args.emotion == "basic" and args.emotion_dim != 9:
+        p.error(f"--emotion basic produces 9 values per window, the emotion_dim of --variant {args.variant} is {args.emotion_dim}: "
+                "use --variant basic")
+    if args.emotion == "egemaps" and args.emotion_dim != 256:
+        p.error(f"--emotion egemaps produces 256 values per window, the emotion_dim of --variant {args.variant} is {args.emotion_dim}")
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     rank, world, local = parallel.init_from_env()
     device = f"cuda:{local}"
     torch.cuda.set_device(local)
-    eng = Engine(mel_sequence_length=args.window_frames)
-    eng.load_state_dict(synth.make_core_params(0, T=args.window_frames, style="init"))
+    eng = Engine(d_model=args.d_model, num_heads=args.num_heads, mel_sequence_length=args.window_frames, emotion_dim=args.emotion_dim)
+    eng.load_state_dict(synth.make_core_params(0, d_model=args.d_model, mel_sequence_length=args.window_frames,
+                                               emotion_dim=args.emotion_dim, style="init"))
     eng.finalize(device)
     kw = dict(window_frames=args.window_frames, stride_frames=args.stride_frames, shuffle_files=False, loop_dataset=False,
               batch_size=args.batch_size, device=device, max_files=args.max_files, device_resample=args.device_resample)
-    egemaps = args.emotion == "egemaps"                  # the track is read from the resident clip: every batch must name it
-    train = SequentialKoeMorphDataset(args.data_dir, resident_windows=args.resident_clip or egemaps, **kw)
-    val = SequentialKoeMorphDataset(args.val_dir, resident_windows=(args.resident_clip and args.loss_components) or egemaps, **kw) \
+    track = args.emotion in ("egemaps", "basic")         # the track is read from the resident clip: every batch must name it
+    train = SequentialKoeMorphDataset(args.data_dir, resident_windows=args.resident_clip or track, **kw)
+    val = SequentialKoeMorphDataset(args.val_dir, resident_windows=(args.resident_clip and args.loss_components) or track, **kw) \
         if args.val_dir else None
     st = SequentialTrainer(eng, train, val, device=device, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
                            gradient_clip=args.gradient_clip, l1_weight=args.l1_weight, dropout=args.dropout, seed=args.seed,
-                           from_clip=args.resident_clip, clip_emotion=ClipEmotion(device=device) if egemaps else None,
+                           from_clip=args.resident_clip,
+                           clip_emotion=ClipEmotion(device=device, backend=args.emotion) if track else None,
                            clip_assemble=args.clip_assemble)
     if args.resume:
         st.load_checkpoint(args.resume)

@@ -11,6 +11,13 @@ Then ``rows`` for 64 windows (eager, synchronised), and a ``SequentialTrainer.tr
 ``clip_emotion`` (track cached: built in the warm-up epoch) against the seeded-noise rows, epochs interleaved.
 
     python tools/bench_clip_emotion.py --seconds 60 --out profiles/clip_emotion_bench.txt
+
+``--backend basic``: the same three measurements for the track of nine prosodic values (``ClipEmotion(backend="basic")``) at the
+`basic` model shape (d_model 128, 4 heads, window 256, emotion_dim 9): ``build``, ``rows`` for 64 windows, and ``train_epoch`` three
+ways, interleaved round by round -- the track, the seeded noise, and the route that existed before the track, an
+``emotion_provider`` that runs ``BasicEmotion.windows`` on every gathered batch.  Medians of ``--rounds`` rounds with best and worst.
+
+    python tools/bench_clip_emotion.py --backend basic --seconds 60 --out profiles/clip_emotion_basic_bench.txt
 """
 import argparse
 import json
@@ -79,8 +86,77 @@ def write_pair(d, audio):
             f.write(json.dumps({"timestamp": i / 30.0, "blendshapes": labels[i].tolist()}) + "\n")
 
 
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def main_basic(a):
+    from koemorph_amd.features.basic_emotion import BasicEmotion
+    audio = speech(a.seconds)
+    clip = torch.from_numpy(audio).cuda()
+    ce = ClipEmotion(backend="basic")
+    K = ce.num_rows(len(audio))
+    built = {}
+    ts = [timed(lambda: built.__setitem__("t", ce.build(clip)[0])) for _ in range(a.rounds + 1)][1:]
+    track = built["t"]
+    lines = [f"basic back end: clip of {a.seconds:g} s ({len(audio)} samples), context 20 s, interval 0.3 s: K = {K} rows of 9, max_slots "
+             f"{ce.max_slots} ({-(-K // ce.max_slots)} passes); medians of {a.rounds} rounds after one warm-up round",
+             f"  ClipEmotion.build, ms per whole track  {stats(ts)}   ({np.median(ts) / max(K, 1):.3f} ms per row)"]
+    starts = torch.arange(64, dtype=torch.int32, device="cuda") * 20
+    out = torch.empty(64, 9, device="cuda")
+    ts = [timed(lambda: ce.rows(track, len(audio), starts, 533, 256, out=out)) for _ in range(a.rounds + 5)][5:]
+    lines.append(f"  rows for 64 windows (eager, synchronised), ms  {stats(ts)}")
+    if not a.no_train:
+        be = BasicEmotion()
+
+        def provider(windows):                               # what existed: the windows' own prosody, once per gathered batch
+            B, L = windows.shape
+            at = torch.arange(B, dtype=torch.int32, device=windows.device) * L
+            return be.windows(windows.reshape(-1), at, L)
+
+        with tempfile.TemporaryDirectory() as d:
+            write_pair(d, audio)
+            trainers = {}
+            for name in ("basic", "noise", "provider"):
+                eng = Engine(d_model=128, num_heads=4, mel_sequence_length=256, emotion_dim=9)
+                eng.load_state_dict(synth.make_core_params(0, 128, 256, 9, "init"))
+                eng.finalize()
+                ds = SequentialKoeMorphDataset(d, shuffle_files=False, loop_dataset=False, batch_size=a.batch_size, resident_windows=True)
+                trainers[name] = SequentialTrainer(eng, ds, from_clip=True, clip_emotion=ce if name == "basic" else None,
+                                                   emotion_provider=provider if name == "provider" else None)
+            ep = {k: [] for k in trainers}
+            steps = 0
+            for e in range(a.rounds + 1):                    # the warm-up round builds and caches the track
+                for name, st in trainers.items():
+                    res = {}
+                    t = timed(lambda: res.update(st.train_epoch()))
+                    steps = res["batches"]
+                    if e:
+                        ep[name].append(t)
+            lines.append(f"train_epoch over the clip at d_model 128 / 4 heads / window 256 / emotion_dim 9, batch {a.batch_size}, {steps} steps, "
+                         f"ms per epoch, sources interleaved round by round (track cached; {ce.builds} builds in all):")
+            label = {"basic": "--emotion basic (track, resident clip)", "noise": "--emotion noise (resident clip)",
+                     "provider": "emotion_provider: BasicEmotion.windows per batch (gathered)"}
+            for name, ts in ep.items():
+                lines.append(f"  {label[name]:62s} {stats(ts)}   ({np.median(ts) / max(steps, 1):.3f} ms per step)")
+        be.close()
+    ce.close()
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--backend", choices=("egemaps", "basic"), default="egemaps")
+    ap.add_argument("--rounds", type=int, default=15, help="--backend basic: timed rounds of every measurement")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--epochs", type=int, default=3, help="timed epochs per emotion source")
@@ -90,6 +166,8 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark needs a GPU"
+    if a.backend == "basic":
+        return main_basic(a)
     audio = speech(a.seconds)
     clip = torch.from_numpy(audio).cuda()
     lin = layer()

@@ -38,7 +38,13 @@ def cycle(i):
     clip = audio[0, :60 * 266].contiguous()
     ctr.step_clip(clip, [0, 1, 2, 9], emo[:4], torch.rand(4, 52, device="cuda"))
     c.forward_clip(clip, [0, 1, 2, 9], emo[:4])
-    del ctr, c, clip
+    # one basic emotion track of that clip and one rows call on it: the prosody plan, the slot table and the frame records
+    from koemorph_amd.features import ClipEmotion
+    ce = ClipEmotion(1.0, 0.1, max_slots=4, backend="basic")
+    track, _ = ce.build(clip)
+    ce.rows(track, clip.shape[0], torch.tensor([0, 1, 2, 9], dtype=torch.int32, device="cuda"), 266, 32)
+    ce.close()
+    del ctr, c, clip, ce, track
     m = KoeMorphModel(d_model=64, d_query=64, num_heads=4, num_encoder_layers=1, num_attention_layers=1, decoder_hidden_dim=32, emotion_dim=8).cuda().eval()
     with torch.no_grad():
         m(torch.randn(2, 12, 80, device="cuda"), torch.randn(2, 12, 8, device="cuda"))
