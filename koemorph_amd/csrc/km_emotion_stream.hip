@@ -24,15 +24,15 @@
 
 #include "km_context.h"
 #include "km_egemaps_ragged.h"
+#include "km_emotion_common.h"
 #include "km_prosody_ragged.h"
 
 namespace km {
 
 
 namespace es {
-constexpr int SR = 16000, NFEAT = 88, NCAT = 3 * NFEAT, NEMO = 256, REC = 36, MAXF = 2048;
+using namespace emo;
 constexpr int SEL_THREADS = 1024, MAX_STREAMS = 4096;   // the selection ranks all streams in one workgroup, waiting times in LDS
-constexpr int NBASIC = 9, BASIC_REC = 4, BASIC_HOP = 512, BASIC_MAX_WINDOW = 1 << 20;   // the `basic` back end (km_prosody.hip)
 }  // namespace es
 
 // per-stream counters (arrays of n_streams)
@@ -45,9 +45,8 @@ struct EsState {
     int32_t* slots_filled;     // window_features[0.3] / [0.6] are not None
 };
 
-struct EmotionStream {
+struct EmotionStream : EmoTiming {
     int64_t n = 0, max_updates = 0;
-    int ring_len = 0, window_len = 0, update_samples = 0, min_samples = 0, max_nf = 0;
     void* plan = nullptr;
     DevBuf<char> blob;         // one allocation, carved below
     float* ring = nullptr;     // (n, ring_len)
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(es::SEL_THREADS) void es_select_kernel(int n, int m
         sl.stream = s;
         if (st.is_full[s]) { sl.len = window_len; sl.start = wp - window_len; if (sl.start < 0) sl.start += ring_len; }
         else { sl.len = wp < window_len ? wp : window_len; sl.start = 0; }
-        sl.nf = (sl.len - 960) / 160 + 1;                                      // km_egemaps_num_frames; len >= min_samples = 8000
+        sl.nf = emo_slot_frames(sl.len);
         table[rank] = sl;
         updated[s] = 1;
     }
@@ -138,8 +137,7 @@ __global__ __launch_bounds__(256) void es_epilogue_kernel(const EgmSlot* __restr
     const int s = sl.stream;
     const bool filled = st.slots_filled[s] != 0;
     if (tid < NFEAT) {
-        float f = fout[(int64_t)blockIdx.x * NFEAT + tid];
-        if (!(fabsf(f) <= 3.4028234663852886e38f)) f = 0.f;                   // NaN, +Inf, -Inf -> 0 (np.nan_to_num, :450-452)
+        const float f = emo_scrub(fout[(int64_t)blockIdx.x * NFEAT + tid]);
         features[(int64_t)s * NFEAT + tid] = f;
         float* sp = slots + (int64_t)s * 2 * NFEAT;
         if (!filled) { sp[tid] = f; sp[NFEAT + tid] = f; }
@@ -152,11 +150,14 @@ __global__ __launch_bounds__(256) void es_epilogue_kernel(const EgmSlot* __restr
     if (tid == 0) { st.last_total[s] = st.total[s]; st.has_features[s] = 1; st.slots_filled[s] = 1; }
 }
 
-__global__ __launch_bounds__(256) void es_output_kernel(int n, const float* __restrict__ emotion, const int32_t* __restrict__ has_features,
+// ---- rows of W floats, STRIDE apart in the object, to the caller's dense (n, W): <256, 256> the emotion rows, <9, 88> the nine
+// values of the `basic` back end where they lie in `features` ----
+template <int W, int STRIDE>
+__global__ __launch_bounds__(256) void es_output_kernel(int n, const float* __restrict__ src, const int32_t* __restrict__ has_features,
                                                         const uint8_t* __restrict__ updated, float* __restrict__ emotion_out,
                                                         uint8_t* __restrict__ valid_out, uint8_t* __restrict__ updated_out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < (int64_t)n * es::NEMO) emotion_out[i] = emotion[i];
+    if (i < (int64_t)n * W) emotion_out[i] = src[W == STRIDE ? i : (i / W) * STRIDE + i % W];
     if (i < n) {
         if (valid_out) valid_out[i] = has_features[i] ? 1 : 0;
         if (updated_out) updated_out[i] = updated[i];
@@ -172,18 +173,6 @@ __global__ __launch_bounds__(64) void es_basic_epilogue_kernel(const EgmSlot* __
     const int s = sl.stream, tid = threadIdx.x;
     if (tid < NBASIC) features[(int64_t)s * NFEAT + tid] = fout[(int64_t)blockIdx.x * NBASIC + tid];
     if (tid == 0) { st.last_total[s] = st.total[s]; st.has_features[s] = 1; }
-}
-
-__global__ __launch_bounds__(256) void es_basic_output_kernel(int n, const float* __restrict__ features, const int32_t* __restrict__ has_features,
-                                                              const uint8_t* __restrict__ updated, float* __restrict__ emotion_out,
-                                                              uint8_t* __restrict__ valid_out, uint8_t* __restrict__ updated_out) {
-    using namespace es;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < (int64_t)n * NBASIC) emotion_out[i] = features[(i / NBASIC) * NFEAT + i % NBASIC];
-    if (i < n) {
-        if (valid_out) valid_out[i] = has_features[i] ? 1 : 0;
-        if (updated_out) updated_out[i] = updated[i];
-    }
 }
 
 // ---- OpenSMILEeGeMAPSExtractor.reset, per stream ----
@@ -210,52 +199,36 @@ __global__ __launch_bounds__(256) void es_transpose_kernel(const float* __restri
     if (i < es::NEMO * es::NCAT) { const int o = i / es::NCAT, k = i % es::NCAT; wt[k * es::NEMO + o] = w[i]; }
 }
 
-static int64_t align16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
-
 static int es_create(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates, bool basic) {
     using namespace es;
-    if (!es_out) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: NULL argument");
+    const char* fn = "km_emotion_stream_create";                                // the name both entry points say
+    if (!es_out) return fail(KM_ERR_INVALID_ARG, "%s: NULL argument", fn);
     *es_out = nullptr;
-    if (n_streams < 1 || n_streams > MAX_STREAMS)
-        return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: n_streams %lld, 1 .. %d", (long long)n_streams, MAX_STREAMS);
-    if (!(context_window_s >= 1.0)) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: Context window must be at least 1.0 seconds");
-    if (!(update_interval_s >= 0.1)) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: Update interval must be at least 0.1 seconds");
-    if (update_interval_s > context_window_s) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: Update interval cannot be larger than context window");
+    if (n_streams < 1 || n_streams > MAX_STREAMS) return fail(KM_ERR_INVALID_ARG, "%s: n_streams %lld, 1 .. %d", fn, (long long)n_streams, MAX_STREAMS);
+    if (const int rc = emo_check_seconds(fn, context_window_s, update_interval_s)) return rc;
     if (max_updates < 1 || max_updates > n_streams)
-        return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_create: max_updates %lld, 1 .. n_streams (%lld)", (long long)max_updates, (long long)n_streams);
-    if (context_window_s > 3600.0) return fail(KM_ERR_UNSUPPORTED, "km_emotion_stream_create: context window of %g s", context_window_s);
-    const int64_t R = (int64_t)((context_window_s + 2.0) * SR), Cw = (int64_t)(context_window_s * SR);
-    const int64_t C = Cw < R ? Cw : R, U = (int64_t)(update_interval_s * SR), MIN = (int64_t)(0.5 * SR);
-    const int64_t nf = basic ? 1 + C / BASIC_HOP : km_egemaps_num_frames(C);          // frame records per window
-    const int64_t rec = basic ? BASIC_REC : REC, nout = basic ? NBASIC : NFEAT;
-    if (basic && C > BASIC_MAX_WINDOW)
-        return fail(KM_ERR_UNSUPPORTED, "km_emotion_stream_create: a window of %lld samples, at most %d (65.5 s)", (long long)C, BASIC_MAX_WINDOW);
-    if (!basic && nf > MAXF)
-        return fail(KM_ERR_UNSUPPORTED, "km_emotion_stream_create: %lld frames per window, at most %d (20.5 s)", (long long)nf, MAXF);
+        return fail(KM_ERR_INVALID_ARG, "%s: max_updates %lld, 1 .. n_streams (%lld)", fn, (long long)max_updates, (long long)n_streams);
     std::unique_ptr<EmotionStream> e(new (std::nothrow) EmotionStream());
-    if (!e) return fail(KM_ERR_HIP, "km_emotion_stream_create: out of host memory");
-    e->n = n_streams; e->max_updates = max_updates;
-    e->ring_len = (int)R; e->window_len = (int)C; e->update_samples = (int)U; e->min_samples = (int)MIN; e->max_nf = (int)nf;
-    e->basic = basic;
+    if (!e) return fail(KM_ERR_HIP, "%s: out of host memory", fn);
+    if (const int rc = emo_timing(fn, context_window_s, update_interval_s, basic, e.get())) return rc;
+    e->n = n_streams; e->max_updates = max_updates; e->basic = basic;
     if (const int rc = basic ? km_prosody_plan_create(&e->prosody) : km_egemaps_plan_create(&e->plan)) return rc;
-    const int64_t n = n_streams, mu = max_updates;
-    // one allocation; `carve` hands out 16-byte aligned pieces, first with a null base to learn the size, then for real
+    const int64_t n = n_streams, mu = max_updates, R = e->ring_len, nf = e->max_nf;
     auto layout = [&](char* base) {
-        int64_t at = 0;
-        auto carve = [&](int64_t bytes) { char* p = base ? base + at : nullptr; at += align16(bytes); return p; };
-        e->ring = reinterpret_cast<float*>(carve(n * R * 4));
-        e->st.write_pos = reinterpret_cast<int32_t*>(carve(n * 4)); e->st.is_full = reinterpret_cast<int32_t*>(carve(n * 4));
-        e->st.total = reinterpret_cast<int64_t*>(carve(n * 8)); e->st.last_total = reinterpret_cast<int64_t*>(carve(n * 8));
-        e->st.has_features = reinterpret_cast<int32_t*>(carve(n * 4)); e->st.slots_filled = reinterpret_cast<int32_t*>(carve(n * 4));
-        e->features = reinterpret_cast<float*>(carve(n * NFEAT * 4)); e->slots = reinterpret_cast<float*>(carve(n * 2 * NFEAT * 4));
-        e->emotion = reinterpret_cast<float*>(carve(n * NEMO * 4)); e->updated = reinterpret_cast<uint8_t*>(carve(n));
-        e->table = reinterpret_cast<EgmSlot*>(carve(mu * (int64_t)sizeof(EgmSlot))); e->scale = reinterpret_cast<float*>(carve(mu * 4));
-        e->rec = reinterpret_cast<float*>(carve(mu * nf * rec * 4)); e->fout = reinterpret_cast<float*>(carve(mu * nout * 4));
-        e->wt = reinterpret_cast<float*>(carve((int64_t)NCAT * NEMO * 4)); e->bias = reinterpret_cast<float*>(carve(NEMO * 4));
-        return at;
+        EmoCarver c{base};
+        e->ring = c.take<float>(n * R);
+        e->st.write_pos = c.take<int32_t>(n); e->st.is_full = c.take<int32_t>(n);
+        e->st.total = c.take<int64_t>(n); e->st.last_total = c.take<int64_t>(n);
+        e->st.has_features = c.take<int32_t>(n); e->st.slots_filled = c.take<int32_t>(n);
+        e->features = c.take<float>(n * NFEAT); e->slots = c.take<float>(n * 2 * NFEAT);
+        e->emotion = c.take<float>(n * NEMO); e->updated = c.take<uint8_t>(n);
+        e->table = c.take<EgmSlot>(mu); e->scale = c.take<float>(mu);
+        e->rec = c.take<float>(mu * nf * (basic ? BASIC_REC : REC)); e->fout = c.take<float>(mu * (basic ? NBASIC : NFEAT));
+        e->wt = c.take<float>((int64_t)NCAT * NEMO); e->bias = c.take<float>(NEMO);
+        return c.at;
     };
     const int64_t bytes = layout(nullptr);
-    if (int rc = e->blob.alloc(bytes, "km_emotion_stream_create")) return rc;
+    if (int rc = e->blob.alloc(bytes, fn)) return rc;
     HIP_TRY(hipMemset(e->blob, 0, (size_t)bytes));
     layout(e->blob);
     HIP_TRY(hipMemset(e->st.last_total, 0xff, (size_t)(n * 8)));       // last_total = -1
@@ -321,7 +294,7 @@ int km_emotion_stream_update(void* es, float* emotion_dev, uint8_t* valid_dev, u
         if (const int rc = prosody_ragged(e->prosody, e->ring, e->ring_len, e->table, (int)e->max_updates, e->max_nf, e->rec, e->fout, st)) return rc;
         hipLaunchKernelGGL(es_basic_epilogue_kernel, dim3((unsigned)e->max_updates), dim3(64), 0, st, (const EgmSlot*)e->table, (const float*)e->fout,
                            e->st, e->features);
-        hipLaunchKernelGGL(es_basic_output_kernel, dim3((unsigned)((e->n * es::NBASIC + 255) / 256)), dim3(256), 0, st, (int)e->n,
+        hipLaunchKernelGGL((es_output_kernel<es::NBASIC, es::NFEAT>), dim3((unsigned)((e->n * es::NBASIC + 255) / 256)), dim3(256), 0, st, (int)e->n,
                            (const float*)e->features, (const int32_t*)e->st.has_features, (const uint8_t*)e->updated, emotion_dev, valid_dev, updated_dev);
         HIP_TRY(hipGetLastError());
         return KM_OK;
@@ -330,7 +303,7 @@ int km_emotion_stream_update(void* es, float* emotion_dev, uint8_t* valid_dev, u
         return rc;
     hipLaunchKernelGGL(es_epilogue_kernel, dim3((unsigned)e->max_updates), dim3(256), 0, st, (const EgmSlot*)e->table, (const float*)e->fout, e->st,
                        e->features, e->slots, (const float*)e->wt, (const float*)e->bias, e->emotion);
-    hipLaunchKernelGGL(es_output_kernel, dim3((unsigned)((e->n * es::NEMO + 255) / 256)), dim3(256), 0, st, (int)e->n, (const float*)e->emotion,
+    hipLaunchKernelGGL((es_output_kernel<es::NEMO, es::NEMO>), dim3((unsigned)((e->n * es::NEMO + 255) / 256)), dim3(256), 0, st, (int)e->n, (const float*)e->emotion,
                        (const int32_t*)e->st.has_features, (const uint8_t*)e->updated, emotion_dev, valid_dev, updated_dev);
     HIP_TRY(hipGetLastError());
     return KM_OK;
@@ -351,7 +324,7 @@ int km_emotion_stream_features(void* es, float* features_dev, float* slots_dev, 
     EmotionStream* e = static_cast<EmotionStream*>(es);
     if (e->basic) {
         if (slots_dev) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_features: the basic back end has no window slots");
-        hipLaunchKernelGGL(es_basic_output_kernel, dim3((unsigned)((e->n * es::NBASIC + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)e->n,
+        hipLaunchKernelGGL((es_output_kernel<es::NBASIC, es::NFEAT>), dim3((unsigned)((e->n * es::NBASIC + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (int)e->n,
                            (const float*)e->features, (const int32_t*)e->st.has_features, (const uint8_t*)e->updated, features_dev,
                            (uint8_t*)nullptr, (uint8_t*)nullptr);
         HIP_TRY(hipGetLastError());

@@ -15,7 +15,7 @@ import torch
 from .. import _lib
 from .._lib import check
 from ..engine import _ptr, _stream_ptr
-from ..streaming import emotion_stream_shape
+from ..streaming import _create_emotion_backend, emotion_stream_shape
 
 
 class ClipEmotion:
@@ -48,29 +48,11 @@ class ClipEmotion:
         if not torch.cuda.is_available():
             raise _lib.KoeMorphError(_lib.KM_ERR_HIP, "no GPU visible: the clip emotion track has no CPU fallback")
         self.context_window, self.update_interval, self.max_slots = context_window, update_interval, max_slots
-        self.device = torch.device(device if device not in (None, "cpu", "auto") else "cuda")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
         self._lib = _lib.load()
-        self._h = C.c_void_p()
-        if backend == "basic":
-            self.compression_layer = None
-            self.emotion_dim = 9
-            with torch.cuda.device(self.device):
-                check(self._lib.km_emotion_clip_create_basic(C.byref(self._h), context_window, update_interval, max_slots))
-        else:
-            if compression_layer is None:
-                compression_layer = torch.nn.Linear(264, 256)
-            if tuple(compression_layer.weight.shape) != (256, 264):
-                raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
-            self.compression_layer = compression_layer
-            self.emotion_dim = 256
-            with torch.cuda.device(self.device):
-                check(self._lib.km_emotion_clip_create(C.byref(self._h), context_window, update_interval, max_slots))
-                w = compression_layer.weight.detach().to(self.device, torch.float32).contiguous()
-                b = compression_layer.bias.detach().to(self.device, torch.float32).contiguous()
-                check(self._lib.km_emotion_clip_set_compression(self._h, _ptr(w), _ptr(b), _stream_ptr(self.device)))
-                torch.cuda.current_stream(self.device).synchronize()      # w and b may go once the copy is done
+        create = self._lib.km_emotion_clip_create_basic if backend == "basic" else self._lib.km_emotion_clip_create
+        self.device, self._h, self.compression_layer, self.emotion_dim, _ = _create_emotion_backend(
+            backend, compression_layer, device, lambda h: create(h, context_window, update_interval, max_slots),
+            self._lib.km_emotion_clip_set_compression)
         self._tracks: Dict[Hashable, Tuple[torch.Tensor, int]] = {}
         self.builds = 0                                                   # calls of build() / build_batch(), track_for's misses included
 

@@ -416,6 +416,32 @@ def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 
                 min_samples=int(0.5 * sample_rate), max_frames=max_frames)
 
 
+def _create_emotion_backend(backend: str, compression_layer: Optional[torch.nn.Module], device, create, set_compression):
+    """What ``StreamEmotion`` and ``ClipEmotion`` do with their back end: ``create(handle_ref)`` on the resolved device (``"cpu"``,
+    ``"auto"`` and None mean the current GPU), and for eGeMAPS the ``Linear(264, 256)`` -- torch's default when absent -- copied
+    into the object with ``set_compression(handle, w, b, stream)``.  Returns (device, handle, the layer kept, emotion_dim,
+    feature_dim); the basic back end keeps no layer and both widths are 9."""
+    device = torch.device(device if device not in (None, "cpu", "auto") else "cuda")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    h = C.c_void_p()
+    if backend == "basic":
+        with torch.cuda.device(device):
+            check(create(C.byref(h)))
+        return device, h, None, 9, 9
+    if compression_layer is None:
+        compression_layer = torch.nn.Linear(264, 256)
+    if tuple(compression_layer.weight.shape) != (256, 264):
+        raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
+    with torch.cuda.device(device):
+        check(create(C.byref(h)))
+        w = compression_layer.weight.detach().to(device, torch.float32).contiguous()
+        b = compression_layer.bias.detach().to(device, torch.float32).contiguous()
+        check(set_compression(h, _ptr(w), _ptr(b), _stream_ptr(device)))
+        torch.cuda.current_stream(device).synchronize()                   # w and b may go once the copy is done
+    return device, h, compression_layer, 256, 88
+
+
 class StreamEmotion:
     """The emotion input of ``n_streams`` streams, computed on the device from the audio pushed into it: per stream the reference's
     ``AudioBuffer``, the update rule of ``process_audio_frame``, the three window slots and ``Linear(264, 256)``
@@ -449,29 +475,11 @@ class StreamEmotion:
         self.n_streams, self.max_updates = n_streams, max_updates
         self.context_window, self.update_interval = context_window, update_interval
         self.ring_len = self.shape["ring_len"]
-        self.device = torch.device(device if device not in (None, "cpu", "auto") else "cuda")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
         self._lib = _lib.load()
-        self._h = C.c_void_p()
-        if backend == "basic":
-            self.compression_layer = None
-            self.emotion_dim = self.feature_dim = 9
-            with torch.cuda.device(self.device):
-                check(self._lib.km_emotion_stream_create_basic(C.byref(self._h), n_streams, context_window, update_interval, max_updates))
-        else:
-            if compression_layer is None:
-                compression_layer = torch.nn.Linear(264, 256)
-            if tuple(compression_layer.weight.shape) != (256, 264):
-                raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
-            self.compression_layer = compression_layer
-            self.emotion_dim, self.feature_dim = 256, 88
-            with torch.cuda.device(self.device):
-                check(self._lib.km_emotion_stream_create(C.byref(self._h), n_streams, context_window, update_interval, max_updates))
-                w = compression_layer.weight.detach().to(self.device, torch.float32).contiguous()
-                b = compression_layer.bias.detach().to(self.device, torch.float32).contiguous()
-                check(self._lib.km_emotion_stream_set_compression(self._h, _ptr(w), _ptr(b), _stream_ptr(self.device)))
-                torch.cuda.current_stream(self.device).synchronize()          # w and b may go once the copy is done
+        create = self._lib.km_emotion_stream_create_basic if backend == "basic" else self._lib.km_emotion_stream_create
+        self.device, self._h, self.compression_layer, self.emotion_dim, self.feature_dim = _create_emotion_backend(
+            backend, compression_layer, device, lambda h: create(h, n_streams, context_window, update_interval, max_updates),
+            self._lib.km_emotion_stream_set_compression)
         self.emotion = torch.zeros(n_streams, self.emotion_dim, device=self.device)
         self.valid = torch.zeros(n_streams, dtype=torch.uint8, device=self.device)
         self.updated = torch.zeros(n_streams, dtype=torch.uint8, device=self.device)

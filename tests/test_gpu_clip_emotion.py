@@ -115,6 +115,7 @@ def test_emotion_rows_use_the_first_features_in_both_slots():
         worst, worst_stream = max(worst, float((err / bound).max())), max(worst_stream, float((err_stream / bound).max()))
         assert (err <= bound).all(), (k, float((err / bound).max()))
         assert (err_stream <= bound).all(), (k, float((err_stream / bound).max()))
+        assert np.array_equal(bits(emotion[k]), bits(e_stream)), k       # one summation order in both kernels: the same bits
     print(f"clip A: worst error / bound = {worst:.3f} against float64, {worst_stream:.3f} against the stream")
     # the slots matter: with the row's own features in them the rows after the first would be somewhere else
     x_wrong = np.concatenate([features[11]] * 3).astype(np.float64)
@@ -137,6 +138,17 @@ def test_build_without_features_out_and_rebuild_of_another_clip():
     other = dev(0.3 * ec.speechlike(1400, 1.5))
     ce.build(other)
     emotion = torch.empty(12, 256, device="cuda")
+    rc = ce._lib.km_emotion_clip_build(ce._h, clip.data_ptr(), N_A, None, emotion.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert rc == KM_OK
+    torch.cuda.synchronize()
+    assert np.array_equal(bits(emotion.cpu().numpy()), bits(track_a()[0]))
+    ce.close()
+
+
+def test_one_row_per_pass_without_features_out():
+    """max_slots 1 and features_out NULL: every pass after the first takes features[0] from the object's own buffer."""
+    ce = ClipEmotion(CTX_A, ITV_A, max_slots=1, compression_layer=layer())
+    clip, emotion = dev(clip_a()), torch.empty(12, 256, device="cuda")
     rc = ce._lib.km_emotion_clip_build(ce._h, clip.data_ptr(), N_A, None, emotion.data_ptr(), torch.cuda.current_stream().cuda_stream)
     assert rc == KM_OK
     torch.cuda.synchronize()
