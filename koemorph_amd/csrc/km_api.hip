@@ -274,41 +274,32 @@ static int forward_audio(km_handle h, const char* who, const float* audio_dev, i
                     (long long)B, (long long)L);
     MelPlan* plan = c->mel_plans[0];
     const MelSrc src = mel_windows(audio_dev, B, L);
-    if (!c->fused_ok) {     // generic shapes: staged front end, GEMM-chain core, stand-alone EMA
-        if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
-        const bool power_path = (generic_core_takes_power(c) || core128_forward_ok(c, attn_dev != nullptr)) && !c->opt.generic_staged;
-        const bool fuse_emo = power_path && mel_fuses_emotion(c, plan);   // emotion logits inside the front-end kernel
-        if (!fuse_emo)
-            if (int rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, stream)) return rc;
-        if (power_path) {
-            // power-mel -> dB conversion inside the encoder's tile staging: no log-mel image at all
-            if (int rc = launch_mel_power(c, plan, src, stream, fuse_emo ? mel_emotion(emotion_dev, c->ws.zemo) : MelCarry{})) return rc;
-            if (int rc = launch_core_generic_power(c, plan, B, n_frames, c->ws.zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
-        } else if (c->NK == 80 && !c->opt.generic_staged) {
-            // log-mel written straight into the packed encoder input; long + short-term rows in one contraction
-            float* xp = generic_packed_x(c, B);
-            if (int rc = launch_mel_packed(c, plan, src, xp, c->T, (c->KT + 15) / 16 * 16, stream)) return rc;
-            if (int rc = launch_core_generic_packed(c, xp, B, c->ws.zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
-        } else {
-            if (int rc = launch_mel(c, plan, src, 0, c->ws.mel, c->ws.mel_short, stream)) return rc;
-            if (int rc = launch_core_generic(c, c->ws.mel, B, n_frames, c->ws.mel_short, c->ws.zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
-        }
-        if (state_dev) return launch_smooth(c, out_dev, state_dev, B, first, stream);
+    if (!c->fused_ok && !c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
+    if (core_takes_power(c, attn_dev != nullptr)) {
+        // emotion logits (inside the front-end kernel where it can carry them), power-mel + window maxima, then the fused core or
+        // a generic one, either converting to dB as it loads its rows: no log-mel image at all.  Stage events on the fused shape alone
+        hipStream_t st = (hipStream_t)stream;
+        const bool tm = c->fused_ok && c->stage_timing;
+        if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[0], st));
+        if (int rc = launch_mel_power_with_logits(c, plan, src, emotion_dev, c->ws.zemo, stream, tm ? (hipEvent_t)c->stage_ev[1] : nullptr)) return rc;
+        if (tm) { HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[2], st)); HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[3], st)); }
+        if (int rc = launch_core_power(c, plan, B, n_frames, c->ws.zemo, out_dev, stream,
+                                       with_outputs(core_workspace(state_dev, first), raw_dev, attn_dev))) return rc;
+        if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[4], st));
         return KM_OK;
     }
-    // three launches: emotion logits, power-mel + window maxima, fused core (dB conversion on load)
-    hipStream_t st = (hipStream_t)stream;
-    const bool tm = c->stage_timing;
-    const bool fuse_emo = mel_fuses_emotion(c, plan);   // emotion logits computed inside the front-end kernel
-    if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[0], st));
-    if (!fuse_emo)
-        if (int rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, stream)) return rc;
-    if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[1], st));
-    if (int rc = launch_mel_power(c, plan, src, stream, fuse_emo ? mel_emotion(emotion_dev, c->ws.zemo) : MelCarry{})) return rc;
-    if (tm) { HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[2], st)); HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[3], st)); }
-    if (int rc = launch_core_fused_db(c, plan, B, n_frames, c->ws.zemo, out_dev, stream,
-                                      with_outputs(core_workspace(state_dev, first), raw_dev, attn_dev))) return rc;
-    if (tm) HIP_TRY(hipEventRecord((hipEvent_t)c->stage_ev[4], st));
+    // generic shapes without a power path: staged front end, GEMM-chain core, stand-alone EMA
+    if (int rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, stream)) return rc;
+    if (c->NK == 80 && !c->opt.generic_staged) {
+        // log-mel written straight into the packed encoder input; long + short-term rows in one contraction
+        float* xp = generic_packed_x(c, B);
+        if (int rc = launch_mel_packed(c, plan, src, xp, c->T, (c->KT + 15) / 16 * 16, stream)) return rc;
+        if (int rc = launch_core_generic_packed(c, xp, B, c->ws.zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
+    } else {
+        if (int rc = launch_mel(c, plan, src, 0, c->ws.mel, c->ws.mel_short, stream)) return rc;
+        if (int rc = launch_core_generic(c, c->ws.mel, B, n_frames, c->ws.mel_short, c->ws.zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
+    }
+    if (state_dev) return launch_smooth(c, out_dev, state_dev, B, first, stream);
     return KM_OK;
 }
 
@@ -377,17 +368,9 @@ static int forward_clip(km_handle h, const float* clip_dev, int64_t clip_len, co
             if (int rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, stream)) return rc;
         }
         if (int rc = launch_clip_images(c, plan, clip_dev, clip_len, start_frames_dev, B, min_start_frame, n_span, cp.E, stream)) return rc;
-        if (c->melmax_dirty) {
-            HIP_TRY(hipMemsetAsync(c->ws.melmax, 0, (size_t)c->ws.windows * sizeof(unsigned), (hipStream_t)stream));
-            c->melmax_dirty = false;
-        }
+        if (int rc = clear_stale_maxima(c, stream)) return rc;
         if (int rc = launch_clip_assemble(c, start_frames_dev, B, min_start_frame, n_span, cp.E, stream)) return rc;
-        if (c->fused_ok)
-            return launch_core_fused_db(c, plan, B, T + 1, c->ws.zemo, out_dev, stream,
-                                        with_outputs(core_workspace(state_dev, first), raw_dev, attn_dev));
-        if (int rc = launch_core_generic_power(c, plan, B, T + 1, c->ws.zemo, out_dev, raw_dev, attn_dev, stream)) return rc;
-        if (state_dev) return launch_smooth(c, out_dev, state_dev, B, first, stream);
-        return KM_OK;
+        return launch_core_power(c, plan, B, T + 1, c->ws.zemo, out_dev, stream, with_outputs(core_workspace(state_dev, first), raw_dev, attn_dev));
     }
     // grow-only; allocates, so not inside a stream capture
     if (int rc = c->seq.fwd_span.grow(n_span * c->NK, stream, "km_forward_clip: floats of the span image")) return rc;
@@ -493,10 +476,8 @@ int km_forward_audio_pipelined(km_handle h, const float* audio_dev, int64_t B, i
         if (hipEventRecord((hipEvent_t)c->pipe.ev_in[slot], caller) != hipSuccess) { rc = fail(KM_ERR_HIP, "hipEventRecord failed"); break; }
         if (hipStreamWaitEvent(s1, (hipEvent_t)c->pipe.ev_in[slot], 0) != hipSuccess) { rc = fail(KM_ERR_HIP, "hipStreamWaitEvent failed"); break; }
         if (tm) (void)hipEventRecord((hipEvent_t)c->stage_ev[0], s1);
-        const bool fuse_emo = mel_fuses_emotion(c, c->mel_plans[0]);
-        if (!fuse_emo && (rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, s1))) break;
-        if (tm) (void)hipEventRecord((hipEvent_t)c->stage_ev[1], s1);
-        if ((rc = launch_mel_power(c, c->mel_plans[0], mel_windows(audio_dev, B, L), s1, fuse_emo ? mel_emotion(emotion_dev, c->ws.zemo) : MelCarry{}))) break;
+        if ((rc = launch_mel_power_with_logits(c, c->mel_plans[0], mel_windows(audio_dev, B, L), emotion_dev, c->ws.zemo, s1,
+                                               tm ? (hipEvent_t)c->stage_ev[1] : nullptr))) break;
         if (tm) (void)hipEventRecord((hipEvent_t)c->stage_ev[2], s1);
         (void)hipEventRecord((hipEvent_t)c->pipe.ev_mel[slot], s1);
         (void)hipStreamWaitEvent(s2, (hipEvent_t)c->pipe.ev_mel[slot], 0);

@@ -50,9 +50,7 @@ static SeqPlan seq_plan(km_handle h, int64_t B, int64_t L, int32_t stride_frames
     const bool rp = mel_rp_planned(c, plan), dedup = !c->opt.seq_per_window;     // seq_per_window: tests compare the schedules
     const bool sizes_ok = B < lim && p.N < lim && p.nfc < lim;                   // (the products below then fit 64 bits)
     const int64_t total = sizes_ok ? B * p.N : 0;
-    // the power path of km_forward_audio (forward_audio in km_api.hip): the fused core, or a generic core that converts to dB itself
-    const bool power = c->fused_ok || ((generic_core_takes_power(c) || core128_forward_ok(c, with_attention)) && !c->opt.generic_staged);
-    if (c->opt.seq_assemble && dedup && power && rp && m.pad_mode == KM_PAD_CONSTANT && c->NK % 4 == 0 && n_frames >= 2 * p.E &&
+    if (c->opt.seq_assemble && dedup && core_takes_power(c, with_attention) && rp && m.pad_mode == KM_PAD_CONSTANT && c->NK % 4 == 0 && n_frames >= 2 * p.E &&
         L >= (int64_t)c->T * hop && sizes_ok && B * p.nfc < lim / c->NK && total * 3 * p.E < lim / c->NK) {
         p.route = 2;
         p.stft_frames = B * p.nfc + total * 3 * p.E;         // per window E left-edge rows and E launches of 2 rows (row 0 discarded)
@@ -145,8 +143,9 @@ static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int6
         // emotion features ONCE for the entire audio (:88): one logit per clip
         if (int rc = launch_emotion(c, emotion_dev, B, c->ws.zemo, stream)) return rc;
     }
+    SeqAssemble sa{};
+    SeqCore sc{};
     if (assembled) {
-        hipStream_t st = (hipStream_t)stream;
         const int E = sp.E, T = c->T;
         if (int rc = launch_seq_zero_maxima(c->seq.fmax, B * nfc, c->seq.emax, total * edge_rows, stream)) return rc;
         // (1) every clip as one long "window" of nfc frames
@@ -164,31 +163,11 @@ static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int6
             if (int rc = launch_mel_power(c, plan, wins, stream, mel_to_frames(&right_img))) return rc;
         }
         // (3) per tile: the windows' rows and maxima into the workspace, then the core km_forward_audio runs on its power path
-        // (the assemble kernel stores the maxima it needs; the slots of a fresh workspace beyond a short tile are cleared as
+        // (the assemble kernel stores the maxima it needs; the slots of a fresh workspace beyond a short tile are cleared once, as
         // launch_mel_power clears them, because the core launches below declare the maxima clean)
-        if (c->melmax_dirty) {
-            HIP_TRY(hipMemsetAsync(c->ws.melmax, 0, (size_t)c->ws.windows * sizeof(unsigned), st));
-            c->melmax_dirty = false;
-        }
-        const SeqAssemble sa{c->seq.pow, c->seq.fmax, c->seq.edge, c->seq.emax, right, rmax, total, (int)nfc, (int)stride_frames, (int)N, E, T};
-        for (int64_t w0 = 0; w0 < total; w0 += tile) {
-            const int64_t nw = (total - w0) < tile ? (total - w0) : tile;
-            if (int rc = launch_seq_assemble(c, sa, nw, w0, stream)) return rc;
-            if (c->fused_ok) {
-                if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
-                                                  with_outputs(trk ? core_workspace_seq_win(w0) : core_workspace_seq(w0, (int)N), raw_at(w0), attn_at(w0)))) return rc;
-            } else {
-                if (!trk)
-                    if (int rc = launch_gather_clip_logits(c, c->ws.zemo, c->ws.zemo_win, nw, w0, (int)N, stream)) return rc;
-                if (int rc = launch_core_generic_power(c, plan, nw, n_frames, trk ? zemo + w0 : c->ws.zemo_win, out_dev + w0 * c->NB,
-                                                       raw_at(w0), attn_at(w0), stream)) return rc;
-            }
-            if (int rc = stats_take(w0, nw)) return rc;
-        }
-        if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
-        return KM_OK;
-    }
-    if (shared) {
+        if (int rc = clear_stale_maxima(c, stream)) return rc;
+        sa = SeqAssemble{c->seq.pow, c->seq.fmax, c->seq.edge, c->seq.emax, right, rmax, total, (int)nfc, (int)stride_frames, (int)N, E, T};
+    } else if (shared) {
         hipStream_t st = (hipStream_t)stream;
         HIP_TRY(hipMemsetAsync(c->seq.fmax, 0, (size_t)B * nfc * sizeof(unsigned), st));
         HIP_TRY(hipMemsetAsync(c->seq.emax, 0, (size_t)total * 2 * sizeof(unsigned), st));
@@ -199,32 +178,33 @@ static int sequence_forward(km_handle h, const float* audio_dev, int64_t B, int6
         const SeqFrames edge_img{c->seq.edge, c->seq.emax, 2, (int)(n_frames - 1)};
         if (int rc = launch_mel_power(c, plan, mel_clip_windows(audio_dev, L, total, W, step, 0, (int)N), stream, mel_to_frames(&edge_img))) return rc;
         // (3) per tile: window maxima, then the fused core reading rows from both images
-        const SeqCore sc{c->seq.pow, c->seq.edge, (int)nfc, (int)stride_frames, (int)N};
-        for (int64_t w0 = 0; w0 < total; w0 += tile) {
-            const int64_t nw = (total - w0) < tile ? (total - w0) : tile;
-            if (int rc = launch_seq_window_max(c, c->seq.fmax, c->seq.emax, nw, w0, (int)nfc, (int)stride_frames, (int)N,
-                                               (int)n_frames, stream)) return rc;
-            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
-                                              with_outputs(trk ? core_strided_win(&sc, w0) : core_strided(&sc, w0), raw_at(w0), attn_at(w0)))) return rc;
-            if (int rc = stats_take(w0, nw)) return rc;
-        }
-        if (smooth) return launch_ema_scan(c, out_dev, B, N, stream);
-        return KM_OK;
+        sc = SeqCore{c->seq.pow, c->seq.edge, (int)nfc, (int)stride_frames, (int)N};
     }
+    // The tiles.  Ahead of the core, route 2 assembles the tile's rows into the workspace, route 1 takes its window maxima from the
+    // images, route 0 runs the front end per window (which also clears stale maxima); the core reads a logit per window of the
+    // sequence (track) or per clip.  A generic shape on route 0 keeps the staged log-mel and the chain behind it, as
+    // km_core_forward runs it: the one tile that is not the core behind the power-mel.
+    const bool staged = sp.route == 0 && !c->fused_ok;
     for (int64_t w0 = 0; w0 < total; w0 += tile) {
         const int64_t nw = (total - w0) < tile ? (total - w0) : tile;
-        const MelSrc src = mel_clip_windows(audio_dev, L, nw, W, step, w0, (int)N);
-        if (c->fused_ok) {
-            if (int rc = launch_mel_power(c, plan, src, stream)) return rc;
-            if (int rc = launch_core_fused_db(c, plan, nw, n_frames, zemo, out_dev + w0 * c->NB, stream,
-                                              with_outputs(trk ? core_workspace_seq_win(w0) : core_workspace_seq(w0, (int)N), raw_at(w0), attn_at(w0)))) return rc;
+        float* out = out_dev + w0 * c->NB;
+        CoreSrc cs = trk ? core_workspace_seq_win(w0) : core_workspace_seq(w0, (int)N);
+        if (assembled) {
+            if (int rc = launch_seq_assemble(c, sa, nw, w0, stream)) return rc;
+        } else if (shared) {
+            if (int rc = launch_seq_window_max(c, c->seq.fmax, c->seq.emax, nw, w0, (int)nfc, (int)stride_frames, (int)N, (int)n_frames, stream)) return rc;
+            cs = trk ? core_strided_win(&sc, w0) : core_strided(&sc, w0);
         } else {
-            // generic shapes: staged log-mel, per-window logits gathered from the per-clip ones, GEMM-chain core
-            if (int rc = launch_mel(c, plan, src, 0, c->ws.mel, c->ws.mel_short, stream)) return rc;
+            const MelSrc src = mel_clip_windows(audio_dev, L, nw, W, step, w0, (int)N);
+            if (int rc = staged ? launch_mel(c, plan, src, 0, c->ws.mel, c->ws.mel_short, stream) : launch_mel_power(c, plan, src, stream)) return rc;
+        }
+        if (staged) {     // per-window logits gathered from the per-clip ones, GEMM-chain core
             if (!trk)
                 if (int rc = launch_gather_clip_logits(c, c->ws.zemo, c->ws.zemo_win, nw, w0, (int)N, stream)) return rc;
-            if (int rc = launch_core_generic(c, c->ws.mel, nw, n_frames, c->ws.mel_short, trk ? zemo + w0 : c->ws.zemo_win, out_dev + w0 * c->NB,
-                                             raw_at(w0), attn_at(w0), stream)) return rc;
+            if (int rc = launch_core_generic(c, c->ws.mel, nw, n_frames, c->ws.mel_short, trk ? zemo + w0 : c->ws.zemo_win, out, raw_at(w0),
+                                             attn_at(w0), stream)) return rc;
+        } else {
+            if (int rc = launch_core_power(c, plan, nw, n_frames, zemo, out, stream, with_outputs(cs, raw_at(w0), attn_at(w0)))) return rc;
         }
         if (int rc = stats_take(w0, nw)) return rc;
     }

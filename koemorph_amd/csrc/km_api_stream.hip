@@ -95,17 +95,8 @@ static int stream_outputs_ok(Context* c, const float* attn_dev) {
 static int stream_launches(Context* c, const unsigned char* gate, const float* emotion_dev, float* out_dev, float* raw_dev, float* attn_dev,
                            void* stream) {
     const int64_t S = c->st.n_streams, n_frames = 1 + c->st.ring_len / c->st.plan->cfg.hop_length;
-    const bool fuse_emo = mel_fuses_emotion(c, c->st.plan);
-    if (!fuse_emo)
-        if (int rc = launch_emotion(c, emotion_dev, S, c->ws.zemo, stream)) return rc;
-    if (int rc = launch_mel_power(c, c->st.plan, mel_rings(c, gate), stream, fuse_emo ? mel_emotion(emotion_dev, c->ws.zemo) : MelCarry{})) return rc;
-    if (c->fused_ok)
-        return launch_core_fused_db(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, with_outputs(core_stream(c, gate), raw_dev, attn_dev));
-    if (core256w_stream_ok(c))
-        return launch_core256w_stream(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, gate, raw_dev, attn_dev);
-    if (core128_stream_ok(c))
-        return launch_core128_stream(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, gate, raw_dev, attn_dev);
-    return launch_core512_stream(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, gate, raw_dev, attn_dev);
+    if (int rc = launch_mel_power_with_logits(c, c->st.plan, mel_rings(c, gate), emotion_dev, c->ws.zemo, stream)) return rc;
+    return launch_core_power(c, c->st.plan, S, n_frames, c->ws.zemo, out_dev, stream, with_outputs(core_stream(c, gate), raw_dev, attn_dev));
 }
 
 static int stream_tick(km_handle h, const float* emotion_dev, float* out_dev, uint8_t* ready_dev, float* raw_dev, float* attn_dev, void* stream) {

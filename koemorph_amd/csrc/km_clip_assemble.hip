@@ -52,9 +52,8 @@ ClipPlan clip_plan(Context* c, int64_t B, int64_t min_start, int64_t max_start, 
         base = clip_packs_planned(c, plan) && T >= 2 && m.n_mels <= 128;
     } else {
         today = c->fused_ok && c->opt.core_split != 3 && c->opt.core_split != 6 && rp && shared;
-        // the power path of km_forward_audio: the fused core, or a generic core that converts to dB itself
-        base = c->fused_ok ? (c->opt.core_split != 3 && c->opt.core_split != 6)
-                           : ((generic_core_takes_power(c) || core128_forward_ok(c, with_attention)) && !c->opt.generic_staged);
+        // the power path of km_forward_audio (the split-bf16 variants of the fused core apart)
+        base = c->fused_ok ? (c->opt.core_split != 3 && c->opt.core_split != 6) : core_takes_power(c, with_attention);
     }
     const int64_t Ls = (2 * (int64_t)p.E - 1) * hop;
     const bool sizes_ok = B <= 32767 && p.n_span < lim / c->NK && B * 4 * p.E < lim / c->NK && B * 2 * (Ls + 3) < lim;

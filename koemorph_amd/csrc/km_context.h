@@ -379,28 +379,23 @@ int launch_seq_track_logits(Context* c, const float* ztrack, float* zwin, int64_
 int launch_core_generic_packed(Context* c, const float* xp, int64_t B, const float* zemo, float* out, float* raw, float* attn,
                                void* stream);
 float* generic_packed_x(Context* c, int64_t B);
-bool generic_core_takes_power(Context* c);
 int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_frames, const float* zemo, float* out,
                               float* raw, float* attn, void* stream);
 int launch_core_generic(Context* c, const float* mel, int64_t B, int64_t T_in, const float* mel_short, const float* zemo,
                         float* out, float* raw, float* attn, void* stream);
-// km_stream_tick on the d_model 512 shapes (8 or 16 heads, window 512): core512's streaming kernel over the rings' power-mel
-bool core512_stream_ok(Context* c);
-// raw (S, 52) / attn (S, 28, 80, 16-byte aligned) or null: the pre-weight sigmoid values and the head-averaged map of the computed streams
-int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
-                          const unsigned char* gate = nullptr, float* raw = nullptr, float* attn = nullptr);
-// ... and on d_model 256 / 8 heads / window 512 (the shape of the 60 fps recipe): core256w's streaming kernel, same contract
-bool core256w_stream_ok(Context* c);
-int launch_core256w_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
-                           const unsigned char* gate = nullptr, float* raw = nullptr, float* attn = nullptr);
-// ... and on d_model 128 / 4 heads / window 128 or 256 (the reference's `fast` and `basic` variants): core128's streaming kernel
-bool core128_stream_ok(Context* c);
-int launch_core128_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
-                          const unsigned char* gate = nullptr, float* raw = nullptr, float* attn = nullptr);
-// the forward calls take core128_kernel at those shapes: option core128 is set and no map is asked for
-bool core128_forward_ok(Context* c, bool with_attention);
-// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or one of the three above
+// the streams on the shapes with a one-launch generic core (d_model 512 / 8 or 16 heads; 256 / 8 heads / window 512; 128 / 4 heads /
+// window 128 or 256): the shape's streaming kernel over the rings' power-mel.  raw (S, 52) / attn (S, 28, 80, 16-byte aligned) or
+// null: the pre-weight sigmoid values and the head-averaged map of the computed streams
+int launch_core_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
+                       const unsigned char* gate = nullptr, float* raw = nullptr, float* attn = nullptr);
+// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or one of those
 bool stream_core_ok(Context* c);
+// the forward calls have a power path: the fused core, or a generic core that reads the power-mel workspace and converts to dB itself
+bool core_takes_power(Context* c, bool with_attention);
+// ... and the core on it, for the B windows whose rows and maxima are in the workspace: the fused core with `src` as it is; on the
+// generic shapes the logits src.win0 / src.zemo_div names (gathered into ws.zemo_win unless the divisor is 1), then the streaming
+// core for a stream source, else launch_core_generic_power with src.raw / src.attn and launch_smooth where src.state is set
+int launch_core_power(Context* c, MelPlan* plan, int64_t B, int64_t n_frames, const float* zemo, float* out, void* stream, const CoreSrc& src);
 // km_core_route: 0 fused d_model 256 core, 1 core512_kernel, 2 core256w_kernel, 3 the launch-per-product chain, 4 core128_kernel
 int core_route(Context* c, bool with_attention);
 
@@ -450,6 +445,12 @@ int launch_mel_clip_span(Context* c, MelPlan* p, const float* clip, int64_t clip
 int launch_train_clip_pack(Context* c, MelPlan* p, const float* span, const float* edge, const int* start_frames, int64_t B,
                            int min_start, int64_t n_span, int T, int KP, float* xt, void* stream);
 bool mel_fuses_emotion(Context* c, MelPlan* p);
+// the windows' emotion logits and their power-mel: one launch with the rider where mel_fuses_emotion holds, else launch_emotion and
+// the plain front end.  emo_done: recorded between the two (stage timing of the fused shape), or null
+int launch_mel_power_with_logits(Context* c, MelPlan* p, const MelSrc& src, const float* emotion, float* zemo, void* stream,
+                                 hipEvent_t emo_done = nullptr);
+// ws.melmax all-zero ahead of launches that raise or store maxima in a freshly (re)allocated workspace (melmax_dirty)
+int clear_stale_maxima(Context* c, void* stream);
 
 // km_seq_assemble.hip
 // Sequence mode, assembled route: windows win0 .. win0 + nw - 1 of `total` (n_per_clip per clip, `stride` frames apart) written into

@@ -1,6 +1,7 @@
 // The one-launch core of d_model 128 / 4 heads / 80 mel channels / decoder hidden 64 at window 128 or 256 -- the reference's `fast`
-// and `basic` variants (kernels and their launches; the dispatch is km_generic.hip's: core128_ok, launch_core128,
-// launch_core128_stream).  A translation unit of its own: the kernels of every other unit are compiled exactly as before.
+// and `basic` variants (kernels and their launches; the dispatch is km_generic.hip's: its row of kOneLaunchCores,
+// launch_core_generic_packed / _power, launch_core_stream).  A translation unit of its own: the kernels of every other unit are
+// compiled exactly as before.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

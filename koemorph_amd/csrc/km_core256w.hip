@@ -1,6 +1,6 @@
 // The one-launch core of d_model 256 / 8 heads / 80 mel channels / decoder hidden 128 at window 512 (kernels and their launches; the
-// dispatch is km_generic.hip's: core256w_ok, launch_core256w, launch_core256w_stream).  A translation unit of its own: the
-// kernels of km_generic.hip are compiled exactly as before.
+// dispatch is km_generic.hip's: its row of kOneLaunchCores, launch_core_generic_packed / _power, launch_core_stream).  A
+// translation unit of its own: the kernels of km_generic.hip are compiled exactly as before.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

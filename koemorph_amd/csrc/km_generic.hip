@@ -609,70 +609,86 @@ __global__ __launch_bounds__(512) void core512_stream_kernel(Core512StreamArgs s
     attn_out_vr_body<512, HPW, true>(a.S, a.Y, a.wv_bg, a.wf_pg, a.bf, a.w2, a.b2, a.zemo, a.wsum, a.out, a.raw, b, gsm, sa.st);
 }
 
-static bool core512_merge_ok(Context* c, bool with_attn) {
-    return c->d == 512 && c->NK == 80 && c->DH == 256 && (c->H == 8 || c->H == 16) && !with_attn && !c->opt.no_ln_fusion &&
-           !c->opt.no_score_fusion && !c->opt.no_out_fusion && !c->opt.no_v_fusion && !c->opt.no_core_merge && c->packed.count("qk_pg") &&
-           c->packed.count("wf_pg") && c->packed.count("wv_bg");
-}
-
 constexpr int kCore512Lds = (2 * 16 * 81 * 4 + 32 * (512 + 8) + 8 * 32) * (int)sizeof(float);   // dynamic LDS of the last stage
 
+// core512_kernel's launchers in the form the other two one-launch cores have (km_core_args.h); 8 or 16 heads by the score rows
 template <bool FUSE_DB>
-static int launch_core512(Context* c, int64_t B, const float* xp, int KP, const EncSrc& src, const float* zemo, float* out, float* raw,
-                          hipStream_t st) {
-    const int d = c->d, H = c->H, NKk = c->NK;
-    float* Y = c->ws.generic;
-    float* S = Y + 2 * B * NKk * d;
-    Core512Args a{xp, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), S, H * 28,
-                  dv(c, "wv_bg"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw};
-    constexpr int lds = kCore512Lds;
+static int launch_core512_t(const Core512Args& a, int64_t B, int device, hipStream_t st) {
     static PerDeviceOnce once;
-    if (once.first(c->device)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_kernel<2, 1, FUSE_DB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_kernel<4, 2, FUSE_DB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    if (once.first(device)) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_kernel<2, 1, FUSE_DB>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_kernel<4, 2, FUSE_DB>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
     }
-    if (H == 8) hipLaunchKernelGGL((core512_kernel<2, 1, FUSE_DB>), dim3((unsigned)B), dim3(512), lds, st, a);
-    else hipLaunchKernelGGL((core512_kernel<4, 2, FUSE_DB>), dim3((unsigned)B), dim3(512), lds, st, a);
+    if (a.rows == 8 * 28) hipLaunchKernelGGL((core512_kernel<2, 1, FUSE_DB>), dim3((unsigned)B), dim3(512), kCore512Lds, st, a);
+    else hipLaunchKernelGGL((core512_kernel<4, 2, FUSE_DB>), dim3((unsigned)B), dim3(512), kCore512Lds, st, a);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+static int launch_core512_kernel(const Core512Args& a, bool fuse_db, int64_t B, int device, hipStream_t st) {
+    return fuse_db ? launch_core512_t<true>(a, B, device, st) : launch_core512_t<false>(a, B, device, st);
+}
+static int launch_core512_stream_kernel(const Core512StreamArgs& sa, int64_t S, int device, hipStream_t st) {
+    static PerDeviceOnce once;
+    if (once.first(device)) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_stream_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_stream_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
+    }
+    if (sa.c.rows == 8 * 28) hipLaunchKernelGGL((core512_stream_kernel<2, 1>), dim3((unsigned)S), dim3(512), kCore512Lds, st, sa);
+    else hipLaunchKernelGGL((core512_stream_kernel<4, 2>), dim3((unsigned)S), dim3(512), kCore512Lds, st, sa);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
 
-// core256w_kernel (km_core256w.hip), the one-launch core of d_model 256 / 8 heads / decoder hidden 128 at window 512 -- the shape the
-// reference's frame_rate=60 recipe trains.  T is restricted on purpose: every other d_model 256 window keeps the launches it has
-// (encoder_ln_kernel<8, 2> + the chain)
-static bool core256w_ok(Context* c, bool with_attn) {
-    return c->d == 256 && c->H == 8 && c->NK == 80 && c->DH == 128 && c->T == 512 && !with_attn && !c->opt.no_ln_fusion &&
-           !c->opt.no_score_fusion && !c->opt.no_out_fusion && !c->opt.no_v_fusion && !c->opt.no_core_merge && c->packed.count("qk_pg") &&
-           c->packed.count("wf_pg") && c->packed.count("wv_bg32") && c->packed.count("wce_pg");
+// the chain's encoder_ln_kernel converts the front end's power-mel to dB itself (shapes with an instantiation, both fusions on)
+static bool generic_core_takes_power(Context* c) {
+    return c->NK == 80 && (c->d == 512 || c->d == 256 || c->d == 64) && !c->opt.no_ln_fusion && !c->opt.no_db_fusion;
 }
 
-// ... and its launch (the kernels: km_core256w.hip); fuse_db: rows from the power-mel of `src` instead of the packed image xp
-static int launch_core256w(Context* c, bool fuse_db, int64_t B, const float* xp, int KP, const EncSrc& src, const float* zemo, float* out,
-                           float* raw, hipStream_t st) {
+// The one-launch cores of the generic shapes, a row each: core512_kernel (above) at d_model 512 / 8 or 16 heads; core256w_kernel
+// (km_core256w.hip) at d_model 256 / 8 heads / window 512, the shape the reference's frame_rate=60 recipe trains -- every other
+// d_model 256 window keeps the launches it has; core128_kernel (km_core128.hip) at d_model 128 / 4 heads / windows 128 and 256, the
+// reference's `fast` and `basic` variants.  d_model and the window tell the shapes apart, so at most one row serves a handle and the
+// order of the rows means nothing.
+struct OneLaunchCore {
+    int route;                            // what km_core_route answers
+    bool (*shape)(const Context* c);
+    const char *wce, *wv, *wf;            // its encoder, value and fold images (km_host.cpp)
+    bool encoder_ln_power;                // it reads the power-mel as encoder_ln_kernel does: only where generic_core_takes_power
+    bool forward_opt_in;                  // the forward calls take it under option core128 (and not generic_staged); the streams either way
+    CoreLaunch launch;
+    CoreStreamLaunch launch_stream;
+};
+static const OneLaunchCore kOneLaunchCores[] = {
+    {1, [](const Context* c) { return c->d == 512 && (c->H == 8 || c->H == 16) && c->NK == 80 && c->DH == 256; },
+     "wce_pg", "wv_bg", "wf_pg", true, false, launch_core512_kernel, launch_core512_stream_kernel},
+    {2, [](const Context* c) { return c->d == 256 && c->H == 8 && c->NK == 80 && c->DH == 128 && c->T == 512; },
+     "wce_pg", "wv_bg32", "wf_pg", true, false, launch_core256w_kernel, launch_core256w_stream_kernel},
+    // (no_db_fusion switches core128 off altogether: its first stage is written for the power-mel)
+    {4, [](const Context* c) { return c->d == 128 && c->H == 4 && c->NK == 80 && c->DH == 64 && (c->T == 128 || c->T == 256) && !c->opt.no_db_fusion; },
+     "wce_pg128", "wv_bg128", "wf_pg128", false, true, launch_core128_kernel, launch_core128_stream_kernel},
+};
+
+// the row that serves the handle's forward calls (with_attn: a map is asked for, which the chain alone writes) or its streams (whose
+// maps come from stream_head_mean_kernel after the launch, so they never ask here), or null
+enum CoreUse { kForward, kStream };
+static const OneLaunchCore* one_launch_core(Context* c, CoreUse use, bool with_attn = false) {
+    if (with_attn || c->opt.no_ln_fusion || c->opt.no_score_fusion || c->opt.no_out_fusion || c->opt.no_v_fusion || c->opt.no_core_merge) return nullptr;
+    for (const OneLaunchCore& r : kOneLaunchCores) {
+        if (!r.shape(c)) continue;
+        if (!c->packed.count("qk_pg") || !c->packed.count(r.wce) || !c->packed.count(r.wv) || !c->packed.count(r.wf)) return nullptr;
+        if (use == kForward) return !r.forward_opt_in || (c->opt.core128 && !c->opt.generic_staged) ? &r : nullptr;
+        return !r.encoder_ln_power || generic_core_takes_power(c) ? &r : nullptr;
+    }
+    return nullptr;
+}
+
+// a row's kernel arguments for B windows: rows from the packed image xp, or (xp null) from the power-mel of `src`
+static Core512Args one_launch_args(Context* c, const OneLaunchCore& r, int64_t B, const float* xp, const EncSrc& src, const float* zemo,
+                                   float* out, float* raw) {
     float* Y = c->ws.generic;
     float* S = Y + 2 * B * c->NK * c->d;      // where the chain keeps its scores
-    Core512Args a{xp, dv(c, "wce_pg"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), S, c->H * 28,
-                  dv(c, "wv_bg32"), dv(c, "wf_pg"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw};
-    return launch_core256w_kernel(a, fuse_db, B, c->device, st);
-}
-
-// core128_kernel (km_core128.hip), the one-launch core of d_model 128 / 4 heads / decoder hidden 64 at windows 128 and 256 -- the
-// reference's `fast` and `basic` variants.  The streams at these shapes take it; the forward calls take it under option core128
-// (core128_forward_ok) and keep the launch-per-product chain otherwise
-static bool core128_ok(Context* c, bool with_attn) {
-    return c->d == 128 && c->H == 4 && c->NK == 80 && c->DH == 64 && (c->T == 128 || c->T == 256) && !with_attn && !c->opt.no_ln_fusion &&
-           !c->opt.no_score_fusion && !c->opt.no_out_fusion && !c->opt.no_v_fusion && !c->opt.no_core_merge && !c->opt.no_db_fusion &&
-           c->packed.count("qk_pg") && c->packed.count("wce_pg128") && c->packed.count("wv_bg128") && c->packed.count("wf_pg128");
-}
-bool core128_forward_ok(Context* c, bool with_attention) { return c->opt.core128 && !c->opt.generic_staged && core128_ok(c, with_attention); }
-
-static int launch_core128(Context* c, bool fuse_db, int64_t B, const float* xp, int KP, const EncSrc& src, const float* zemo, float* out,
-                          float* raw, hipStream_t st) {
-    float* Y = c->ws.generic;
-    float* S = Y + 2 * B * c->NK * c->d;      // where the chain keeps its scores
-    Core512Args a{xp, dv(c, "wce_pg128"), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), S, c->H * 28,
-                  dv(c, "wv_bg128"), dv(c, "wf_pg128"), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw};
-    return launch_core128_kernel(a, fuse_db, B, c->device, st);
+    return {xp, dv(c, r.wce), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, (c->KT + 15) / 16 * 16, src, dv(c, "qk_pg"), S, c->H * 28,
+            dv(c, r.wv), dv(c, r.wf), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw};
 }
 
 // d_model -> (waves, column tiles per wave) of the fused encoder + LayerNorm kernel
@@ -698,9 +714,8 @@ int launch_core_generic_packed(Context* c, const float* xp, int64_t B, const flo
     const bool fuse_ln = !c->opt.no_ln_fusion;
     hipStream_t st = (hipStream_t)stream;
     bool ln_done = fuse_ln;
-    if (core512_merge_ok(c, attn != nullptr)) return launch_core512<false>(c, B, xp, KP, EncSrc{}, zemo, out, raw, st);
-    if (core256w_ok(c, attn != nullptr)) return launch_core256w(c, false, B, xp, KP, EncSrc{}, zemo, out, raw, st);
-    if (core128_forward_ok(c, attn != nullptr)) return launch_core128(c, false, B, xp, KP, EncSrc{}, zemo, out, raw, st);
+    if (const OneLaunchCore* r = one_launch_core(c, kForward, attn != nullptr))
+        return r->launch(one_launch_args(c, *r, B, xp, EncSrc{}, zemo, out, raw), false, B, c->device, st);
     if (fuse_ln && (d == 512 || d == 256 || d == 64)) {
         if (int rc = launch_encoder_ln_for<false>(c, B, st, xp, KP, EncSrc{})) return rc;
     } else {
@@ -712,59 +727,43 @@ int launch_core_generic_packed(Context* c, const float* xp, int64_t B, const flo
     return core_generic_after_encoder(c, B, zemo, out, raw, attn, stream, ln_done);
 }
 
-// the generic core fed directly by the front end's power-mel workspace (dB conversion inside the encoder kernel);
-// returns KM_ERR_UNSUPPORTED for shapes without an encoder_ln_kernel instantiation (callers then use the packed image)
-bool generic_core_takes_power(Context* c) {
-    return c->NK == 80 && (c->d == 512 || c->d == 256 || c->d == 64) && !c->opt.no_ln_fusion && !c->opt.no_db_fusion;
-}
-
 LogParams plan_log_params(MelPlan* p);
 
-int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_frames, const float* zemo, float* out,
-                              float* raw, float* attn, void* stream) {
-    const bool core128 = core128_forward_ok(c, attn != nullptr);      // d_model 128 has no encoder_ln_kernel: the power-mel feeds this route alone
-    if (!core128 && !generic_core_takes_power(c)) return fail(KM_ERR_UNSUPPORTED, "no fused encoder for d_model=%d", c->d);
-    const int KP = (c->KT + 15) / 16 * 16;
-    hipStream_t st = (hipStream_t)stream;
-    EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
-    if (core128) {
-        if (int rc = launch_core128(c, true, B, nullptr, KP, src, zemo, out, raw, st)) return rc;
-        c->melmax_dirty = false;
-        return KM_OK;
-    }
-    if (core512_merge_ok(c, attn != nullptr)) {
-        if (int rc = launch_core512<true>(c, B, nullptr, KP, src, zemo, out, raw, st)) return rc;
-        c->melmax_dirty = false;
-        return KM_OK;
-    }
-    if (core256w_ok(c, attn != nullptr)) {
-        if (int rc = launch_core256w(c, true, B, nullptr, KP, src, zemo, out, raw, st)) return rc;
-        c->melmax_dirty = false;
-        return KM_OK;
-    }
-    if (int rc = launch_encoder_ln_for<true>(c, B, st, nullptr, KP, src)) return rc;
-    c->melmax_dirty = false;     // every slot the encoder read was just written by the front end and is re-zeroed by the encoder
-    return core_generic_after_encoder(c, B, zemo, out, raw, attn, stream, true);
+// a generic core that converts the power-mel to dB itself: the chain's encoder_ln_kernel, or row r where it brings a first stage of
+// its own (core128: d_model 128 has no encoder_ln_kernel)
+static bool generic_power_ok(Context* c, const OneLaunchCore* r) { return generic_core_takes_power(c) || (r && !r->encoder_ln_power); }
+
+// the forward calls have a core behind the power-mel workspace (the power path of km_forward_audio, which sequence mode and the
+// resident-clip calls plan with): the fused core, or such a generic one unless the staged image is asked for
+bool core_takes_power(Context* c, bool with_attention) {
+    return c->fused_ok || (generic_power_ok(c, one_launch_core(c, kForward, with_attention)) && !c->opt.generic_staged);
 }
 
-// km_stream_tick on the d_model 512 shapes: the front end has written the power-mel of every ready stream's ring
-bool core512_stream_ok(Context* c) { return core512_merge_ok(c, false) && generic_core_takes_power(c); }
-// ... and on d_model 256 / 8 heads / window 512 (core256w_stream_kernel)
-bool core256w_stream_ok(Context* c) { return core256w_ok(c, false) && generic_core_takes_power(c); }
-// ... and on d_model 128 / 4 heads / window 128 or 256 (core128_stream_kernel; the predicate holds no_db_fusion already)
-bool core128_stream_ok(Context* c) { return core128_ok(c, false); }
-// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or one of the three above
-bool stream_core_ok(Context* c) { return c->fused_ok || core512_stream_ok(c) || core256w_stream_ok(c) || core128_stream_ok(c); }
+// the generic core fed directly by the front end's power-mel workspace (dB conversion inside the encoder stage): the shape's
+// one-launch core, else encoder_ln_kernel + the chain
+int launch_core_generic_power(Context* c, MelPlan* plan, int64_t B, int64_t n_frames, const float* zemo, float* out,
+                              float* raw, float* attn, void* stream) {
+    const OneLaunchCore* r = one_launch_core(c, kForward, attn != nullptr);
+    if (!generic_power_ok(c, r)) return fail(KM_ERR_UNSUPPORTED, "no fused encoder for d_model=%d", c->d);
+    hipStream_t st = (hipStream_t)stream;
+    EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
+    if (r) {
+        if (int rc = r->launch(one_launch_args(c, *r, B, nullptr, src, zemo, out, raw), true, B, c->device, st)) return rc;
+    } else if (int rc = launch_encoder_ln_for<true>(c, B, st, nullptr, (c->KT + 15) / 16 * 16, src)) return rc;
+    c->melmax_dirty = false;     // every slot the encoder read was just written by the front end and is re-zeroed by the encoder
+    return r ? KM_OK : core_generic_after_encoder(c, B, zemo, out, raw, attn, stream, true);
+}
+
+// the handle's shape has a streaming core: the fused one (d_model 256, 8 heads, window 256) or a row of the table
+bool stream_core_ok(Context* c) { return c->fused_ok || one_launch_core(c, kStream) != nullptr; }
 
 // km_core_route: the kernel the forward calls take behind the packed image or the power-mel (km_core_forward, km_forward_audio,
 // the generic branch of km_sequence_forward*); host only
 int core_route(Context* c, bool with_attention) {
     if (c->fused_ok) return 0;
     if (c->opt.generic_staged) return 3;
-    if (core512_merge_ok(c, with_attention)) return 1;
-    if (core256w_ok(c, with_attention)) return 2;
-    if (core128_forward_ok(c, with_attention)) return 4;
-    return 3;
+    const OneLaunchCore* r = one_launch_core(c, kForward, with_attention);
+    return r ? r->route : 3;
 }
 
 // The head-averaged map of every stream that core512_stream_kernel just computed (km_stream_tick_attn / _step_attn): the kernel
@@ -789,24 +788,19 @@ __global__ __launch_bounds__(kStreamMapThreads) void stream_head_mean_kernel(con
     reinterpret_cast<float4*>(attn)[(int64_t)b * per4 + i] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
 }
 
-// the arguments of a streaming core launch over the rings' power-mel (wv: the value image of the shape's last stage; wce, wf: the
-// encoder and fold images, under names of their own at d_model 128)
-static Core512StreamArgs stream_core_args(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out,
-                                          const unsigned char* gate, float* raw, const char* wv, const char* wce = "wce_pg",
-                                          const char* wf = "wf_pg") {
-    const int KP = (c->KT + 15) / 16 * 16;
-    float* Y = c->ws.generic;
-    float* Sc = Y + 2 * S * c->NK * c->d;
+// km_stream_tick / _step on the shapes of the table: the front end has written the power-mel of every stream whose gate flag is set
+// (null: is_full); the row's streaming kernel over the rings, then, where asked for, the maps.  raw (S, 52) / attn (S, 28, 80,
+// 16-byte aligned) or null
+int launch_core_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
+                       const unsigned char* gate, float* raw, float* attn) {
+    const OneLaunchCore* r = one_launch_core(c, kStream);
+    if (!r) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
+    if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
     const EncSrc src{c->ws.melpow, c->ws.melmax, (int)n_frames, c->T, plan_log_params(plan)};
-    return {{nullptr, dv(c, wce), dv(c, "bce"), dv(c, "ln_g"), dv(c, "ln_b"), Y, KP, src, dv(c, "qk_pg"), Sc, c->H * 28,
-             dv(c, wv), dv(c, wf), dv(c, "bf"), dv(c, "w2"), dv(c, "b2"), zemo, dv(c, "wsum"), out, raw},
-            {(int)(c->st.out_frames > 0 ? c->st.out_frames : n_frames), gate ? gate : c->st.ring_ready, c->st.ring_started,
-             c->st.ring_state, c->alpha}};
-}
-
-// what follows a streaming core launch: the window maxima are clean again; the maps, where asked for
-static int stream_core_done(Context* c, const Core512StreamArgs& sa, int64_t S, float* attn, void* stream) {
-    HIP_TRY(hipGetLastError());
+    const Core512StreamArgs sa{one_launch_args(c, *r, S, nullptr, src, zemo, out, raw),
+                               {(int)(c->st.out_frames > 0 ? c->st.out_frames : n_frames), gate ? gate : c->st.ring_ready, c->st.ring_started,
+                                c->st.ring_state, c->alpha}};
+    if (int rc = r->launch_stream(sa, S, c->device, (hipStream_t)stream)) return rc;
     c->melmax_dirty = false;     // as in launch_core_generic_power: the slots the front end wrote are re-zeroed by the encoder stage
     if (attn) {
         const int per4 = 28 * c->NK / 4;
@@ -817,37 +811,22 @@ static int stream_core_done(Context* c, const Core512StreamArgs& sa, int64_t S, 
     return KM_OK;
 }
 
-int launch_core512_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
-                          const unsigned char* gate, float* raw, float* attn) {
-    if (!core512_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
-    if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
-    const Core512StreamArgs sa = stream_core_args(c, plan, S, n_frames, zemo, out, gate, raw, "wv_bg");
-    static PerDeviceOnce once;
-    if (once.first(c->device)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_stream_kernel<2, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&core512_stream_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, kCore512Lds));
+// The core behind the power-mel workspace, whatever the shape: what every forward path launches once the rows and window maxima of
+// its B windows are there.  The fused core takes `src` as it is.  The generic cores read one logit per window, so a divisor other
+// than 1 is resolved by a gather first; a stream source (src.ready) then goes to the streaming kernels, which smooth themselves,
+// every other one to launch_core_generic_power and the stand-alone EMA.  Strided images and start-frame tables (src.seq, src.tab)
+// exist on the fused shape alone: their callers refuse the generic shapes before any launch.
+int launch_core_power(Context* c, MelPlan* plan, int64_t B, int64_t n_frames, const float* zemo, float* out, void* stream, const CoreSrc& src) {
+    if (c->fused_ok) return launch_core_fused_db(c, plan, B, n_frames, zemo, out, stream, src);
+    const float* z = zemo + src.win0;
+    if (src.zemo_div != 1) {
+        if (int rc = launch_gather_clip_logits(c, zemo, c->ws.zemo_win, B, src.win0, src.zemo_div, stream)) return rc;
+        z = c->ws.zemo_win;
     }
-    if (c->H == 8) hipLaunchKernelGGL((core512_stream_kernel<2, 1>), dim3((unsigned)S), dim3(512), kCore512Lds, (hipStream_t)stream, sa);
-    else hipLaunchKernelGGL((core512_stream_kernel<4, 2>), dim3((unsigned)S), dim3(512), kCore512Lds, (hipStream_t)stream, sa);
-    return stream_core_done(c, sa, S, attn, stream);
-}
-
-int launch_core256w_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
-                           const unsigned char* gate, float* raw, float* attn) {
-    if (!core256w_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
-    if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
-    const Core512StreamArgs sa = stream_core_args(c, plan, S, n_frames, zemo, out, gate, raw, "wv_bg32");
-    if (int rc = launch_core256w_stream_kernel(sa, S, c->device, (hipStream_t)stream)) return rc;
-    return stream_core_done(c, sa, S, attn, stream);
-}
-
-int launch_core128_stream(Context* c, MelPlan* plan, int64_t S, int64_t n_frames, const float* zemo, float* out, void* stream,
-                          const unsigned char* gate, float* raw, float* attn) {
-    if (!core128_stream_ok(c)) return fail(KM_ERR_UNSUPPORTED, "no kernel for d_model=%d, mel_sequence_length=%d, heads=%d", c->d, c->T, c->H);
-    if (!c->ws.generic) return fail(KM_ERR_WORKSPACE, "generic workspace missing: call km_reserve after km_finalize");
-    const Core512StreamArgs sa = stream_core_args(c, plan, S, n_frames, zemo, out, gate, raw, "wv_bg128", "wce_pg128", "wf_pg128");
-    if (int rc = launch_core128_stream_kernel(sa, S, c->device, (hipStream_t)stream)) return rc;
-    return stream_core_done(c, sa, S, attn, stream);
+    if (src.ready) return launch_core_stream(c, plan, B, n_frames, z, out, stream, src.ready, src.raw, src.attn);
+    if (int rc = launch_core_generic_power(c, plan, B, n_frames, z, out, src.raw, src.attn, stream)) return rc;
+    if (src.state) return launch_smooth(c, out, src.state, B, src.first, stream);
+    return KM_OK;
 }
 
 float* generic_packed_x(Context* c, int64_t B) {     // the packed-X slot behind the other intermediates of B windows

@@ -1313,6 +1313,22 @@ static void mel_plan_args(MelPlan* p, MelArgs& a) {
     a.fbg_gid = p->d_fbg_gid; a.fbg_desc = p->d_fbg_desc; a.fbg_weight = p->d_fbg_weight; a.fbg_nw = (int)p->fbg_weight.size();
 }
 
+int clear_stale_maxima(Context* c, void* stream) {
+    if (c->melmax_dirty) {
+        HIP_TRY(hipMemsetAsync(c->ws.melmax, 0, (size_t)c->ws.windows * sizeof(unsigned), (hipStream_t)stream));
+        c->melmax_dirty = false;
+    }
+    return KM_OK;
+}
+
+int launch_mel_power_with_logits(Context* c, MelPlan* p, const MelSrc& src, const float* emotion, float* zemo, void* stream, hipEvent_t emo_done) {
+    const bool rider = mel_fuses_emotion(c, p);
+    if (!rider)
+        if (int rc = launch_emotion(c, emotion, src.B, zemo, stream)) return rc;
+    if (emo_done) HIP_TRY(hipEventRecord(emo_done, (hipStream_t)stream));
+    return launch_mel_power(c, p, src, stream, rider ? mel_emotion(emotion, zemo) : MelCarry{});
+}
+
 // power-mel (B, n_frames, n_mels) + per-window max into the workspace (or what `carry` says)
 int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, const MelCarry& carry) {
     const km_mel_config& m = p->cfg;
@@ -1348,10 +1364,8 @@ int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, co
     // entries they consume, and the stand-alone log kernels below are followed by a memset of theirs -- so a step recorded
     // into a hipGraph needs no memset node and stays correct whatever ran between two replays.  The flag only covers a
     // freshly (re)allocated workspace.
-    if (!seq && c->melmax_dirty) {
-        HIP_TRY(hipMemsetAsync(c->ws.melmax, 0, (size_t)c->ws.windows * sizeof(unsigned), st));
-        c->melmax_dirty = false;
-    }
+    if (!seq)
+        if (int rc = clear_stale_maxima(c, stream)) return rc;
     MelArgs a;
     mel_plan_args(p, a);
     a.audio = src.audio; a.L = L; a.clip_len = src.clip_len; a.win_step = src.win_step; a.win0 = src.win0;
