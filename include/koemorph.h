@@ -710,6 +710,11 @@ int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_
  * 2 <4,2,true> (128 x 64), 3 <4,4,true> (128 x 128, K <= 256), 4 <4,4,false> (128 x 128, K > 256).  -1 for a bad argument.
  * Host only, no device needed: the tests name the kernel a product ran on with it. */
 int km_gemm_kernel_choice(int64_t M, int64_t N, int64_t K, int64_t batch);
+/* What the workgroups with linear ids 0 .. n_ids - 1 of a 1024-point front-end launch do, as the kernel itself derives it:
+ * `windows` windows, per_window workgroups each, and -- group > 0 -- one emotion group workgroup per `group` windows in front of
+ * them.  out (n_ids, 3) int32, on the host: kind (0 nothing: the surplus of the rounded-up grid, 1 the emotion logits of windows
+ * [group b, group b + group), 2 front-end workgroup bx of window b), b, bx.  Host only, no device needed: the tests walk the mapping. */
+int km_mel_role_table(int64_t windows, int32_t per_window, int32_t group, int64_t n_ids, int32_t* out);
 
 /* ---- emotion vectors of many streams, from the pushed audio, resident on the device ------------------------------
  * An object of its own (not tied to a km_handle), on the current device.  Replaces, for n_streams speakers at once, one
@@ -1003,7 +1008,9 @@ int km_resample_clip(void* rs, const float* clip_dev, int64_t n_in, float* out_d
  * "seq_per_window", "seq_assemble" (default 0; 1: sequence mode shares each clip's STFT frames at every shape and hop whose forward
  * call has a power path, assembling the windows into the workspace: km_sequence_plan route 2), "clip_assemble" (default 0; 1:
  * km_train_step_clip / km_forward_clip / km_forward_clip_attn also run on the handles they refuse by default, from a span image and
- * E edge rows a side per window: km_clip_plan route 2; a handle they accept keeps its launches and bits), "generic_staged", "mel_two_frame", "emotion_separate", "no_ln_fusion", "no_db_fusion",
+ * E edge rows a side per window: km_clip_plan route 2; a handle they accept keeps its launches and bits), "generic_staged", "mel_two_frame", "emotion_separate",
+ * "emotion_rider" (default 0; 1: at d_model 256 the front-end launch computes each window's emotion logit inside one of that window's
+ * workgroups, as it does at the other shapes, instead of in group workgroups at the head of the launch that read the weights once per group of windows; same bits), "no_ln_fusion", "no_db_fusion",
  * "no_score_fusion", "no_out_fusion", "no_v_fusion",
  * "no_core_merge" (the one-launch cores of d_model 512 and of d_model 256 / window 512 as the launches they replaced: km_core_route),
  * "core128" (default 0; 1: the forward calls at d_model 128 / 4 heads / window 128 or 256 run core128_kernel, route 4, instead of the

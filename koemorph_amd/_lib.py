@@ -216,6 +216,7 @@ SIGNATURES = {
     "km_loss_terms_compute": (C.c_int, [_p, _p, _p]),
     "km_linear": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p]),
     "km_gemm_kernel_choice": (C.c_int, [_i64, _i64, _i64, _i64]),
+    "km_mel_role_table": (C.c_int, [_i64, _i32, _i32, _i64, _p]),
     "km_emotion_stream_create": (C.c_int, [C.POINTER(_p), _i64, C.c_double, C.c_double, _i64]),
     "km_emotion_stream_destroy": (C.c_int, [_p]),
     "km_emotion_stream_set_compression": (C.c_int, [_p, _p, _p, _p]),

@@ -182,6 +182,10 @@ int km_gemm_kernel_choice(int64_t M, int64_t N, int64_t K, int64_t batch) {
     return gemm_kernel_choice(linear_args(nullptr, nullptr, nullptr, M, K, N, nullptr), (int)batch);
 }
 
+int km_mel_role_table(int64_t windows, int32_t per_window, int32_t group, int64_t n_ids, int32_t* out) {
+    return mel_role_table(windows, per_window, group, n_ids, out);
+}
+
 int km_audio_energy(const float* features_dev, int64_t B, int64_t T, int64_t D, float* energy_dev, void* stream) {
     if (!features_dev || !energy_dev || B <= 0 || T <= 0 || D <= 0) return fail(KM_ERR_INVALID_ARG, "km_audio_energy: bad argument");
     return launch_audio_energy(features_dev, B, T, D, energy_dev, stream);

@@ -29,8 +29,12 @@ struct Packed {
     DevBuf<float> dev;
 };
 
+#ifndef KM_EMO_GROUP
+#define KM_EMO_GROUP 2              /* A/B builds: -DKM_EMO_GROUP=1 .. 12 (measured: profiles/emotion_groups.txt) */
+#endif
 constexpr int kMelRpWaves = 8;      // waves per workgroup of mel_power_rp_kernel
 constexpr int kMelRpGroups = 4;     // filter groups a wave can hold (8 x 4 x 4 = up to 128 filters)
+constexpr int kMelEmoGroup = KM_EMO_GROUP;   // windows per emotion group workgroup of mel_power_rp_kernel (emotion_group_d256; 1, 2, 3, 4, 8 and 12 measured, 2 the fastest step: profiles/emotion_groups.txt)
 constexpr int kMelRpRow = 580;      // power-row stride in dwords (4 mod 64: see the mel stage), >= fbg_extent
 
 // Sparse triangular mel filterbank + window for one front-end configuration.
@@ -68,6 +72,7 @@ struct Options {
     int generic_staged = 0;        // 1: generic core from a staged log-mel image instead of the power-mel workspace
     int mel_two_frame = 0;         // 1: two-frames-per-wave front end (A/B baseline)
     int emotion_separate = 0;      // 1: emotion logits in their own kernel
+    int emotion_rider = 0;         // 1: d_model 256: the front end's per-window emotion rider instead of its group workgroups (A/B, and the tests' bit-identity witness)
     int no_ln_fusion = 0, no_db_fusion = 0, no_score_fusion = 0, no_out_fusion = 0, no_v_fusion = 0;   // generic chain A/B
     int legacy_no_merge = 0;       // 1: the legacy model's attention and tail as two launches instead of one (legacy_attn_tail_kernel)
     int no_core_merge = 0;         // 1: the d_model 512 core as its three launches (encoder + LayerNorm, scores, output) instead of one workgroup per window walking the three stages (core512_kernel); d_model 256 / window 512: the launch-per-product chain instead of core256w_kernel
@@ -424,12 +429,14 @@ inline MelSrc mel_clip_windows(const float* clips, int64_t clip_len, int64_t B, 
 inline MelSrc mel_rings(Context* c, const unsigned char* gate = nullptr) {
     return {c->st.ring, c->st.n_streams, c->st.ring_len, c->st.ring_len, 0, 0, 1, c->st.ring_wptr, gate ? gate : c->st.ring_ready};
 }
-// What a launch may carry, at most one of: the emotion rider (the windows' logits from the same kernel: mel_fuses_emotion, one window
-// per clip), rows into a SeqFrames image instead of the workspace (mel_rp_ok, no rings), the packed training input (mel_packs, a plain batch)
-struct MelCarry { const float* emotion = nullptr; float* zemo = nullptr; const SeqFrames* seq = nullptr; const MelPack* pack = nullptr; };
-inline MelCarry mel_emotion(const float* emotion, float* zemo) { return {emotion, zemo, nullptr, nullptr}; }
-inline MelCarry mel_to_frames(const SeqFrames* seq) { return {nullptr, nullptr, seq, nullptr}; }
-inline MelCarry mel_to_pack(const MelPack* pack) { return {nullptr, nullptr, nullptr, pack}; }
+// What a launch may carry, at most one of: the windows' emotion logits from the same kernel (mel_fuses_emotion, one window per clip)
+// -- emo_group = 0: the per-window rider inside the last workgroup of each window; emo_group = kMelEmoGroup (d_model 256 / hidden
+// 128 only: mel_emotion_grouped): ceil(B / emo_group) extra workgroups in front of the grid, one per group of windows --, rows into a
+// SeqFrames image instead of the workspace (mel_rp_ok, no rings), the packed training input (mel_packs, a plain batch)
+struct MelCarry { const float* emotion = nullptr; float* zemo = nullptr; const SeqFrames* seq = nullptr; const MelPack* pack = nullptr; int emo_group = 0; };
+inline MelCarry mel_emotion(const float* emotion, float* zemo, int emo_group = 0) { return {emotion, zemo, nullptr, nullptr, emo_group}; }
+inline MelCarry mel_to_frames(const SeqFrames* seq) { return {nullptr, nullptr, seq, nullptr, 0}; }
+inline MelCarry mel_to_pack(const MelPack* pack) { return {nullptr, nullptr, nullptr, pack, 0}; }
 int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, const MelCarry& carry = {});
 // true when launch_mel_power launches mel_power_rp_kernel, the row-parallel 1024-point kernel
 bool mel_rp_ok(Context* c, MelPlan* p);
@@ -445,8 +452,11 @@ int launch_mel_clip_span(Context* c, MelPlan* p, const float* clip, int64_t clip
 int launch_train_clip_pack(Context* c, MelPlan* p, const float* span, const float* edge, const int* start_frames, int64_t B,
                            int min_start, int64_t n_span, int T, int KP, float* xt, void* stream);
 bool mel_fuses_emotion(Context* c, MelPlan* p);
-// the windows' emotion logits and their power-mel: one launch with the rider where mel_fuses_emotion holds, else launch_emotion and
-// the plain front end.  emo_done: recorded between the two (stage timing of the fused shape), or null
+// true when that launch carries the logits in group workgroups (d_model 256 / hidden 128, unless the option emotion_rider asks for the rider)
+bool mel_emotion_grouped(Context* c, MelPlan* p);
+int mel_role_table(int64_t windows, int per_window, int group, int64_t n_ids, int32_t* out);   // km_mel_role_table
+// the windows' emotion logits and their power-mel: one launch with the group workgroups or the rider where mel_fuses_emotion holds, else
+// launch_emotion and the plain front end.  emo_done: recorded between the two (stage timing of the fused shape), or null
 int launch_mel_power_with_logits(Context* c, MelPlan* p, const MelSrc& src, const float* emotion, float* zemo, void* stream,
                                  hipEvent_t emo_done = nullptr);
 // ws.melmax all-zero ahead of launches that raise or store maxima in a freshly (re)allocated workspace (melmax_dirty)

@@ -212,6 +212,152 @@ __device__ __forceinline__ void emotion_window_d256(const EmoArgs& e, int64_t b,
     __syncthreads();   // scratch is free again
 }
 
+// The grouped form: one 512-thread workgroup computes the logits of the ng <= G consecutive windows b0 .. b0 + ng - 1, so
+// the layer-1 and layer-2 images (384 KB through L2) are read once per group instead of once per window.  Per window the
+// thread mapping, the fmaf chains (each from 0, against that window's row in LDS) and the order in which the partials are
+// combined are those of emotion_window_d256: a thread keeps the 64 (32) weights of a k-quarter (k-eighth) in registers and
+// runs the chain once per window.  LayerNorm and the ReLU / w2 tail: one wave per window, wave w takes windows w, w + 8, ...
+// Bit-identical to emotion_window_d256 and emotion_kernel_d256.  A window whose ready[] byte is 0 (ready: per window of
+// the launch, or null) is computed like the others and not stored.  Window b reads row win0 + b of emo and writes zemo[win0 + b].
+// scratch: G x 1536 floats of LDS.  Must be called by all 512 threads of the workgroup (contains barriers).
+template <int G>
+__device__ __forceinline__ void emotion_group_d256(const EmoArgs& e, int64_t win0, int b0, int ng, const unsigned char* ready, float* scratch) {
+    constexpr int d = 256, DH = 128, WS = 1536;   // per window: emo_s [256], e1 [256], part [4][256] then [8][128]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = tid & 255, h1 = __builtin_amdgcn_readfirstlane(tid >> 8);   // layer 1: column n, k-quarters 2 h1 and 2 h1 + 1
+    const int m = tid & 127, h2 = tid >> 7;                                    // layer 2: hidden unit m, k-eighths 2 h2 and 2 h2 + 1 (two h2 per wave)
+    // Everything that does not depend on a barrier is requested up front -- the small vectors here, a layer's first block of
+    // weights ahead of the barrier in front of that layer -- so a group pays four memory round trips in a row, not nine (the
+    // workgroup holds a slot that a front-end workgroup is waiting for; most of its time, though, is the FMAs on a VALU it shares
+    // with an FFT workgroup: profiles/emotion_groups.txt).
+    const float bee_n = e.bee[n];
+    float lg[4], lb[4], be2v[2], w2v[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { lg[i] = e.lg[lane + 64 * i]; lb[i] = e.lb[lane + 64 * i]; }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { be2v[i] = e.be2[lane + 64 * i]; w2v[i] = e.w2[lane + 64 * i]; }
+    const float b2 = e.b2[0];
+    auto load1 = [&](int q, float (&w)[64]) {
+        const float* wp = e.wee_t + (size_t)64 * q * d + n;
+#pragma unroll
+        for (int u = 0; u < 64; ++u) w[u] = wp[u * d];
+    };
+    auto run1 = [&](int q, const float (&w)[64]) {   // the chain of emotion_window_d256, once per window of the group
+#pragma unroll 1
+        for (int g = 0; g < ng; ++g) {
+            const float* emo_s = scratch + g * WS;
+            float acc = 0.f;
+#pragma unroll
+            for (int u = 0; u < 64; u += 4) {
+                const float4 x = *reinterpret_cast<const float4*>(emo_s + 64 * q + u);
+                acc = fmaf(x.x, w[u], acc);
+                acc = fmaf(x.y, w[u + 1], acc);
+                acc = fmaf(x.z, w[u + 2], acc);
+                acc = fmaf(x.w, w[u + 3], acc);
+            }
+            scratch[g * WS + 512 + q * d + n] = acc;
+        }
+    };
+    auto load2 = [&](int q, float (&w)[32]) {
+        const float* wp = e.we2 + (size_t)32 * q * DH + m;
+#pragma unroll
+        for (int u = 0; u < 32; ++u) w[u] = wp[u * DH];
+    };
+    auto run2 = [&](int q, const float (&w)[32]) {
+#pragma unroll 1
+        for (int g = 0; g < ng; ++g) {
+            const float* e1 = scratch + g * WS + 256;
+            float acc = 0.f;
+#pragma unroll
+            for (int u = 0; u < 32; u += 4) {
+                const float4 x = *reinterpret_cast<const float4*>(e1 + 32 * q + u);
+                acc = fmaf(x.x, w[u], acc);
+                acc = fmaf(x.y, w[u + 1], acc);
+                acc = fmaf(x.z, w[u + 2], acc);
+                acc = fmaf(x.w, w[u + 3], acc);
+            }
+            scratch[g * WS + 512 + q * DH + m] = acc;
+        }
+    };
+    {
+        float w[64];
+        load1(2 * h1, w);
+        for (int i = tid; i < ng * d; i += 512) {
+            const int g = i >> 8, k = i & 255;
+            scratch[g * WS + k] = k < e.ED ? e.emo[(win0 + b0 + g) * e.ED + k] : 0.f;
+        }
+        __syncthreads();
+        run1(2 * h1, w);
+        load1(2 * h1 + 1, w);
+        run1(2 * h1 + 1, w);
+    }
+    float w2r[32];
+    load2(2 * h2, w2r);
+    __syncthreads();
+    for (int i = tid; i < ng * d; i += 512) {      // (i & 255 == n)
+        const int g = i >> 8;
+        const float* part = scratch + g * WS + 512;
+        float s = bee_n;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += part[q * d + n];
+        scratch[g * WS + 256 + n] = s;
+    }
+    __syncthreads();
+    for (int g = wave; g < ng; g += 8) {   // LayerNorm (eps 1e-5), two-pass, one wave per window
+        float* e1 = scratch + g * WS + 256;
+        float x[4], s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { x[i] = e1[lane + 64 * i]; s += x[i]; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        const float mean = s * (1.0f / d);
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const float t = x[i] - mean; v += t * t; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        const float rstd = 1.0f / sqrtf(v * (1.0f / d) + 1e-5f);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = lane + 64 * i;
+            e1[c] = (x[i] - mean) * rstd * lg[i] + lb[i];
+        }
+    }
+    __syncthreads();
+    run2(2 * h2, w2r);
+    load2(2 * h2 + 1, w2r);
+    run2(2 * h2 + 1, w2r);
+    __syncthreads();
+    for (int g = wave; g < ng; g += 8) {   // ReLU, dot with w2: one wave per window
+        const float* part = scratch + g * WS + 512;
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int mm = lane + 64 * i;
+            float hsum = be2v[i];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) hsum += part[q * DH + mm];
+            s += fmaxf(hsum, 0.f) * w2v[i];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0 && (!ready || ready[b0 + g])) e.zemo[win0 + b0 + g] = s + b2;
+    }
+}
+
+// Which work a workgroup of the front-end launch does, from its linear id: ids 0 .. groups - 1 compute the emotion logits of
+// windows [G id, G id + G) (emotion_group_d256; groups = 0 where the launch carries none), ids groups .. groups + per_window x
+// windows - 1 are the front end proper, windows counting fastest (the workgroups of one window are `windows` ids apart), and
+// whatever the rounded-up grid has beyond that does nothing.
+struct MelRole { int kind, b, bx; };   // kind 0: none; 1: emotion group b; 2: front end, workgroup bx of window b
+__host__ __device__ inline MelRole mel_role(unsigned lin, int windows, int per_window, int groups) {
+    if (lin < (unsigned)groups) return {1, (int)lin, 0};
+    const unsigned r = lin - (unsigned)groups;
+    if (r >= (unsigned)windows * (unsigned)per_window) return {0, 0, 0};
+    return {2, (int)(r % (unsigned)windows), (int)(r / (unsigned)windows)};
+}
+
 // The same stream for the other shapes (d_model, decoder hidden: powers of two in [64, 1024]; emotion_dim <= 256), again
 // for a 512-thread workgroup.  Both layers read their weights as float4 (four adjacent output columns per thread) with
 // the contraction index split over 512 / (columns / 4) thread groups, 16 independent 16-byte loads in flight per thread;

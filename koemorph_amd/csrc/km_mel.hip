@@ -115,7 +115,10 @@ struct MelArgs {
     int fbg_nw;           // floats in fbg_weight
     float* melpow;        // (B, n_frames, n_mels)
     unsigned* melmax;     // (B) float bits, zero-initialised
-    EmoArgs emo;          // optional: the window's emotion logit, computed by the last workgroup of each window
+    EmoArgs emo;          // optional: the window's emotion logit, computed by the last workgroup of each window ...
+    // ... or, emo_groups > 0 (mel_power_rp_kernel at d_model 256), by the launch's first emo_groups workgroups, kMelEmoGroup windows
+    // each (mel_role, emotion_group_d256).  n_windows: the windows of the launch, from which a workgroup derives its role
+    int n_windows, emo_groups;
     // shared-frame sequence mode (km_sequence_forward): output row r of a window is STFT frame r * frame_mul, and the
     // maxima go per row into frame_max[(window, row)] instead of per window into melmax
     int frame_mul;
@@ -391,6 +394,7 @@ __global__ __launch_bounds__(256) void mel_power_kernel(MelArgs a) {
 #ifdef KM_MEL_STAMP
 #define KM_ASM asm volatile      /* keeps the arithmetic blocks between their stamps */
 __device__ unsigned long long km_mel_stamps[1024 * 8 * 24];
+__device__ unsigned long long km_mel_group_stamps[2 * 128];      // emotion group workgroups: real-time clock at entry and at exit
 #define KM_STAMP(i)                                                  \
     do {                                                             \
         const unsigned long long now_ = __builtin_readcyclecounter(); \
@@ -795,10 +799,35 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // Workgroup -> (window, chunk phase).  KM_MEL_REMAP: the linear workgroup id counts windows fastest, so the workgroups of
     // one window are gridDim.y ids apart instead of adjacent (tools/micro: which workgroups share a CU / an XCD's L2).
+    // The role comes from the linear id and the launch's window count (mel_role, km_device.h): the first a.emo_groups ids are the
+    // emotion group workgroups, and the grid is rounded up to whole rows, so its last ids may have no role at all.
 #if KM_MEL_REMAP
     const unsigned lin_ = blockIdx.x + gridDim.x * blockIdx.y;
-    const int b = TAB ? ((int)blockIdx.x < a.tab_span_wgs ? 0 : 1 + (int)blockIdx.x - a.tab_span_wgs) : (int)(lin_ % gridDim.y);
-    const int bx = TAB ? (b == 0 ? (int)blockIdx.x : 0) : (int)(lin_ / gridDim.y);
+    const MelRole role = TAB ? MelRole{2, 0, 0} : mel_role(lin_, a.n_windows, (int)gridDim.x, PACK ? 0 : a.emo_groups);
+    if (!TAB && role.kind == 0) return;
+    if constexpr (!PACK && !TAB) {
+        if (role.kind == 1) {
+            // Emotion logits of windows [G role.b, + G): no FFT, so the whole dynamic LDS is this workgroup's scratch.  It writes
+            // zemo and ends; the kernel boundary in front of the core publishes the values.  No workgroup waits for another:
+            // the low ids only make it likely that these start first and the front-end workgroups fill in behind them.
+            static_assert(kMelEmoGroup * 1536 <= WAVES * FFT_BUF * 2 + FPB * NFS, "the group scratch has to fit the launch's dynamic LDS");
+#ifdef KM_MEL_STAMP
+            const unsigned long long g_rt0 = __builtin_amdgcn_s_memrealtime();
+#endif
+            const int g0 = role.b * kMelEmoGroup;
+            const int ng = a.n_windows - g0 < kMelEmoGroup ? a.n_windows - g0 : kMelEmoGroup;
+            if (!(KM_MEL_SKIP & 16)) emotion_group_d256<kMelEmoGroup>(a.emo, a.win0, g0, ng, a.ready, smem);
+#ifdef KM_MEL_STAMP
+            if (tid == 0 && role.b < 128) {
+                km_mel_group_stamps[2 * role.b] = g_rt0;
+                km_mel_group_stamps[2 * role.b + 1] = __builtin_amdgcn_s_memrealtime();
+            }
+#endif
+            return;
+        }
+    }
+    const int b = TAB ? ((int)blockIdx.x < a.tab_span_wgs ? 0 : 1 + (int)blockIdx.x - a.tab_span_wgs) : role.b;
+    const int bx = TAB ? (b == 0 ? (int)blockIdx.x : 0) : role.bx;
 #else
     const int b = blockIdx.y, bx = (int)blockIdx.x;
     static_assert(!TAB, "the clip-span launch is laid out for KM_MEL_REMAP");
@@ -836,11 +865,14 @@ __global__ __launch_bounds__(512, 4) void mel_power_rp_kernel(MelArgs a) {
             zn_ok = true;
         } else if (bx * FPB + wave < n_frames) zn_ok = load_frame_rp_fast<RING>(x, Lv, rs, a.hop, (bx * FPB + wave) * fmul, lane, zn);
     };
-    // The emotion stream of this window (0.2 MFLOP, latency bound, independent of the audio) rides in the last workgroup of
-    // the window: no separate launch, and the chunk hand-out below lets that workgroup take correspondingly fewer chunks.
-    // (It requests its first frame after the rider: the rider's weight loads need the registers.)  The packing and the
-    // clip-span launches never carry one (launch_mel_power refuses the combination, launch_mel_clip_span sets none).
-    if (!PACK && !TAB && !(KM_MEL_SKIP & 16) && a.emo.emo && bx == (int)gx - 1) {
+    // The emotion logits come from the same launch.  At d_model 256 the group workgroups above compute them (the weights are the
+    // same for every window: 384 KB through L2 once per kMelEmoGroup windows, not once per window) and both workgroups of a window
+    // request their first frame right here.  At the other shapes, and at d_model 256 under the option emotion_rider
+    // (a.emo_groups == 0), the stream of this window (0.2 MFLOP, latency bound, independent of the audio) rides in the last
+    // workgroup of the window: the chunk hand-out below lets that workgroup take correspondingly fewer chunks.  (It requests its
+    // first frame after the rider: the rider's weight loads need the registers.)  The packing and the clip-span launches never
+    // carry either (launch_mel_power refuses the combination, launch_mel_clip_span sets none).
+    if (!PACK && !TAB && !(KM_MEL_SKIP & 16) && a.emo.emo && a.emo_groups == 0 && bx == (int)gx - 1) {
         if (a.emo.d == 256 && a.emo.DH == 128) emotion_window_d256(a.emo, gw, pw);
         else emotion_window_generic(a.emo, EmoShape{a.emo.d, a.emo.DH}, gw, pw);
         first_frame();
@@ -1321,12 +1353,31 @@ int clear_stale_maxima(Context* c, void* stream) {
     return KM_OK;
 }
 
+// ... in group workgroups rather than per-window riders: the production shape, whose two weight images (384 KB) every rider
+// would read again through L2 (256 windows: 100 MB a launch).  The option emotion_rider keeps the rider there (A/B; same bits).
+bool mel_emotion_grouped(Context* c, MelPlan* p) {
+    return KM_MEL_REMAP && mel_fuses_emotion(c, p) && c->d == 256 && c->DH == 128 && !c->opt.emotion_rider;
+}
+
 int launch_mel_power_with_logits(Context* c, MelPlan* p, const MelSrc& src, const float* emotion, float* zemo, void* stream, hipEvent_t emo_done) {
-    const bool rider = mel_fuses_emotion(c, p);
-    if (!rider)
+    const bool fused = mel_fuses_emotion(c, p);
+    if (!fused)
         if (int rc = launch_emotion(c, emotion, src.B, zemo, stream)) return rc;
     if (emo_done) HIP_TRY(hipEventRecord(emo_done, (hipStream_t)stream));
-    return launch_mel_power(c, p, src, stream, rider ? mel_emotion(emotion, zemo) : MelCarry{});
+    return launch_mel_power(c, p, src, stream, fused ? mel_emotion(emotion, zemo, mel_emotion_grouped(c, p) ? kMelEmoGroup : 0) : MelCarry{});
+}
+
+// mel_role (km_device.h) for the ids 0 .. n_ids - 1 of a launch of `windows` windows, per_window workgroups each, with an
+// emotion group workgroup per `group` windows (0: none): out (n_ids, 3) = kind, b, bx.  Host only; the tests walk it.
+int mel_role_table(int64_t windows, int per_window, int group, int64_t n_ids, int32_t* out) {
+    if (windows <= 0 || windows > 65535 || per_window <= 0 || per_window > 512 || group < 0 || n_ids < 0 || !out)
+        return fail(KM_ERR_INVALID_ARG, "mel_role_table: bad argument");
+    const int groups = group > 0 ? (int)((windows + group - 1) / group) : 0;
+    for (int64_t i = 0; i < n_ids; ++i) {
+        const MelRole r = mel_role((unsigned)i, (int)windows, per_window, groups);
+        out[3 * i] = r.kind; out[3 * i + 1] = r.b; out[3 * i + 2] = r.bx;
+    }
+    return KM_OK;
 }
 
 // power-mel (B, n_frames, n_mels) + per-window max into the workspace (or what `carry` says)
@@ -1346,8 +1397,9 @@ int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, co
     const bool ring = src.ring_start != nullptr, plain = !ring && src.wins_per_clip <= 1;
     if ((carry.emotion != nullptr) + (seq != nullptr) + (carry.pack != nullptr) > 1 || (seq && !(mel_rp_ok(c, p) && !ring)) ||
         (carry.pack && !(plain && mel_packs(c, p, n_frames, carry.pack->T) && carry.pack->KP >= carry.pack->T + 3)) ||
-        (carry.emotion && !(mel_fuses_emotion(c, p) && carry.zemo && src.wins_per_clip <= 1)))
-        return fail(KM_ERR_UNSUPPORTED, "launch_mel_power: emotion rider, frame image or packed output requested for an unsupported configuration");
+        (carry.emotion && !(mel_fuses_emotion(c, p) && carry.zemo && src.wins_per_clip <= 1)) ||
+        (carry.emo_group && !(carry.emotion && carry.emo_group == kMelEmoGroup && KM_MEL_REMAP && c->d == 256 && c->DH == 128)))
+        return fail(KM_ERR_UNSUPPORTED, "launch_mel_power: emotion logits (rider or groups), frame image or packed output requested for an unsupported configuration");
     if (!p->uploaded) return fail(KM_ERR_NOT_FINALIZED, "mel plan not uploaded (km_finalize / km_reserve first)");
     static PerDeviceOnce once;
     if (once.first(c->device)) {
@@ -1373,6 +1425,7 @@ int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, co
     a.ring_start = src.ring_start; a.ready = src.ready;
     a.melpow = c->ws.melpow; a.melmax = c->ws.melmax;
     a.frame_mul = 1; a.frame_max = nullptr; a.chunk_ctr = c->ws_chunkctr;
+    a.n_windows = (int)B; a.emo_groups = carry.emo_group ? (int)((B + carry.emo_group - 1) / carry.emo_group) : 0;
     a.pack_xt = nullptr; a.pack_T = a.pack_KP = 0; a.pack_amin = m.amin;
     a.tab_start = nullptr; a.tab_edge = nullptr; a.tab_min = a.tab_T = a.tab_span_wgs = 0;
     if (carry.pack) { a.pack_xt = carry.pack->xt; a.pack_T = carry.pack->T; a.pack_KP = carry.pack->KP; }
@@ -1390,7 +1443,8 @@ int launch_mel_power(Context* c, MelPlan* p, const MelSrc& src, void* stream, co
     int per_window = (int)((512 + B / 2) / B);
     if (per_window > n_chunks) per_window = n_chunks;
     if (per_window < 1) per_window = 1;
-    const dim3 grid((unsigned)per_window, (unsigned)B);
+    // (the group workgroups take the first ids of the grid: whole rows of per_window ids more, the surplus ids do nothing)
+    const dim3 grid((unsigned)per_window, (unsigned)(B + (a.emo_groups + per_window - 1) / per_window));
     if (mel_rp_ok(c, p)) {
         const size_t ldsrp = melrp_lds_bytes(a.fbg_nw);      // 74 KB: two workgroups per CU
         if (carry.pack) hipLaunchKernelGGL((mel_power_rp_kernel<false, true>), grid, dim3(melrp::NT), ldsrp, st, a);
@@ -1629,6 +1683,9 @@ LogParams plan_log_params(MelPlan* p) { return log_params(p->cfg); }
 #ifdef KM_MEL_STAMP
 extern "C" __attribute__((visibility("default"))) int km_debug_mel_stamps(unsigned long long* out, int n) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(km_mel_stamps), (size_t)n * sizeof(unsigned long long));
+}
+extern "C" __attribute__((visibility("default"))) int km_debug_mel_group_stamps(unsigned long long* out, int n) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(km_mel_group_stamps), (size_t)n * sizeof(unsigned long long));
 }
 #endif
 

@@ -1,6 +1,8 @@
 """Where a wave of mel_power_rp_kernel spends its cycles at the C2 shape: by part of the frame loop, by workgroup role, and
 for the frames off the fast path -- the wait at the loop top for an edge frame against an ordinary one, the lone 17th turn
-against a full one, and when the two workgroups of a window end.  Needs a library built with -DKM_MEL_STAMP
+against a full one, when the two workgroups of a window end, and -- where the launch carries them -- when the emotion group
+workgroups (the first ids of the grid) start and how long one takes.  KM_EMOTION_RIDER=1 in the environment puts the per-window
+rider back (role 1 then carries it).  Needs a library built with -DKM_MEL_STAMP
 (tools/micro/mel_xchg.sh with EXTRA=-DKM_MEL_STAMP):  KM_LIBRARY=tools/micro/bin/libkm_xchg0.so python tools/micro/mel_stamp.py"""
 import ctypes as C
 import os
@@ -41,12 +43,20 @@ def main():
     rc = lib.km_debug_mel_stamps(buf, n)
     assert rc == 0, rc
     st = np.frombuffer(buf, dtype=np.uint64).reshape(512, 8, 24).astype(np.float64)
+    # emotion group workgroups: real-time clock at entry and exit of each (all zero where the rider ran; absent in older libraries)
+    grp = np.zeros((0, 2))
+    if hasattr(lib, "km_debug_mel_group_stamps"):
+        gbuf = (C.c_ulonglong * 256)()
+        assert lib.km_debug_mel_group_stamps(gbuf, 256) == 0
+        grp = np.frombuffer(gbuf, dtype=np.uint64).reshape(128, 2).astype(np.float64)
+        grp = grp[grp[:, 0] > 0]
+    role1 = "8 chunks" if len(grp) else "8 chunks + emotion rider"
     total = st[:, :, 12]
     print(f"waves: {st.shape[0] * 8}; cycles per wave (first to last stamp): mean {total.mean():.0f}  min {total.min():.0f}  max {total.max():.0f}")
     for even in (0, 1):
         sel = st[even::2]
         tot = sel[:, :, 12].mean()
-        print(f"-- workgroups with blockIdx.x = {even} ({'9 chunks' if even == 0 else '8 chunks + emotion rider'}): {tot:.0f} cycles per wave")
+        print(f"-- workgroups with blockIdx.x = {even} ({'9 chunks' if even == 0 else role1}): {tot:.0f} cycles per wave")
         for i, name in enumerate(PARTS):
             v = sel[:, :, i].mean()
             print(f"   {name:34s} {v:9.0f} cycles  {100 * v / tot:5.1f} %")
@@ -55,6 +65,16 @@ def main():
     span_rt = rt1.max() - rt0.min()
     ghz = np.median((end - ent) / np.maximum(rt1 - rt0, 1)) / 10.0
     print(f"kernel span (real-time clock): {span_rt / 100:.2f} us; shader-clock counter runs at {ghz:.3f} GHz")
+    if len(grp):
+        t0 = min(rt0.min(), grp[:, 0].min())
+        dur = grp[:, 1] - grp[:, 0]
+        print(f"   emotion groups: {len(grp)} workgroups; start {np.mean(grp[:, 0] - t0) / 100:6.2f} us after the first wave of the launch (max "
+              f"{np.max(grp[:, 0] - t0) / 100:.2f}); one takes {dur.mean() / 100:6.2f} us (min {dur.min() / 100:.2f}, max {dur.max() / 100:.2f}); the last ends at "
+              f"{np.max(grp[:, 1] - t0) / 100:6.2f} us; first front-end wave {(rt0.min() - t0) / 100:.2f} us after the first group; "
+              f"kernel span with the groups {(max(rt1.max(), grp[:, 1].max()) - t0) / 100:.2f} us")
+        late = np.sort(rt0.min(axis=1) - rt0.min())[::-1]
+        print(f"   front-end workgroups by start: the latest 40 begin {late[:40].mean() / 100:6.2f} us after the first (max {late[0] / 100:.2f}), "
+              f"the rest {late[40:].mean() / 100:6.2f} us; {int((late > 100).sum())} start more than 1 us late")
     for role in (0, 1):
         sel = slice(role, None, 2)
         print(f"   role {role}: starts {np.mean(rt0[sel] - rt0.min()) / 100:6.2f} us after the first wave (max {np.max(rt0[sel] - rt0.min()) / 100:.2f}); "
