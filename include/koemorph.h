@@ -702,6 +702,20 @@ int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_
 int km_egemaps_records(const float* work_dev, int64_t B, int64_t L, float* rec_host, void* stream);
 int km_egemaps_track_from_records(float* rec_dev, int64_t B, int64_t nf, void* stream);
 int km_egemaps_functionals_from_records(const float* rec_dev, int64_t B, int64_t nf, float* out_dev, void* stream);
+/* Windows beyond 2048 frames (20.5 s), opt-in: up to 2^20 samples (65.5 s, 6548 frames), the window limit of the `basic` back end.
+ * The reference's long_context variant extracts eGeMAPS over 30 s (2995 frames).  The three per-frame kernels take any frame count;
+ * the two per-window kernels (pitch track, functionals) have a second form that holds a long window in dynamic LDS and gives, on the
+ * same records, the bits of the first form at every frame count up to 2048.
+ *   km_egemaps_functionals_long              the contract of km_egemaps_functionals for L <= 2^20 (KM_ERR_UNSUPPORTED beyond: "a
+ *                                            window of L samples, at most 1048576 (65.5 s)"); workspace from
+ *                                            km_egemaps_workspace_floats, records by km_egemaps_records.  At 2048 frames or fewer it
+ *                                            launches what km_egemaps_functionals launches
+ *   km_egemaps_track_from_records_long       km_egemaps_track_from_records / _functionals_from_records for 1 <= nf <= 6548, ALWAYS
+ *   km_egemaps_functionals_from_records_long on the long form of the kernel (tests: the equal-bits law) */
+int km_egemaps_functionals_long(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
+                                int64_t work_floats, float* out_dev, void* stream);
+int km_egemaps_track_from_records_long(float* rec_dev, int64_t B, int64_t nf, void* stream);
+int km_egemaps_functionals_from_records_long(const float* rec_dev, int64_t B, int64_t nf, float* out_dev, void* stream);
 /* out (B, N) = x (B, K) w^T + b with w stored (N, K) like nn.Linear: the 264 -> 256 compression of the three concatenated
  * eGeMAPS windows (OpenSMILEeGeMAPSExtractor.get_concatenated_features, opensmile_extractor.py:575-590).  b may be NULL. */
 int km_linear(const float* x_dev, const float* w_dev, const float* b_dev, int64_t B, int64_t K, int64_t N, float* out_dev, void* stream);
@@ -858,6 +872,15 @@ int km_emotion_clip_rows(void* ec, const float* emotion_track_dev, int64_t K, in
  * and, as above, none of them allocates, synchronises or reads back. */
 int km_emotion_clip_create_basic(void** ec, double context_window_s, double update_interval_s, int64_t max_slots);
 int km_emotion_clip_width(void* ec);
+/* The eGeMAPS objects (km_emotion_stream_create, km_emotion_clip_create) with the window limit of km_egemaps_functionals_long: C <=
+ * 2^20 samples, else KM_ERR_UNSUPPORTED "a window of C samples, at most 1048576 (65.5 s)".  Every other check, its text (under the
+ * entry point's own name) and the order in which the refusals win are those of the plain entry points; all refusals come before any
+ * device call and leave a null handle.  An object whose window has at most 2048 frames IS the plain object.  Beyond that every
+ * call on the object is unchanged (push, update, set_compression, reset_streams, features; build, build_batch, rows; capture and
+ * replay); the frame records take slots x frames x 36 floats of the object's one allocation (0.94 MB per slot at the limit), and
+ * the per-window kernels of every slot, short windows included, are the long form. */
+int km_emotion_stream_create_long(void** es, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates);
+int km_emotion_clip_create_long(void** ec, double context_window_s, double update_interval_s, int64_t max_slots);
 
 /* ---- evaluation metrics: a streaming accumulator in device memory ------------------------------------------------
  * Replaces BlendshapeMetrics (src/model/losses.py:421-521) and compute_lip_sync_metrics (:524-583).  The reference

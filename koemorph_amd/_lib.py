@@ -192,6 +192,9 @@ SIGNATURES = {
     "km_egemaps_records": (C.c_int, [_p, _i64, _i64, _p, _p]),
     "km_egemaps_track_from_records": (C.c_int, [_p, _i64, _i64, _p]),
     "km_egemaps_functionals_from_records": (C.c_int, [_p, _i64, _i64, _p, _p]),
+    "km_egemaps_functionals_long": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _i64, _p, _p]),
+    "km_egemaps_track_from_records_long": (C.c_int, [_p, _i64, _i64, _p]),
+    "km_egemaps_functionals_from_records_long": (C.c_int, [_p, _i64, _i64, _p, _p]),
     "km_metrics_create": (C.c_int, [C.POINTER(_p)]),
     "km_metrics_destroy": (C.c_int, [_p]),
     "km_metrics_reset": (C.c_int, [_p, _p]),
@@ -233,6 +236,8 @@ SIGNATURES = {
     "km_prosody_windows": (C.c_int, [_p, _p, _i64, _p, _i64, _i64, _p, _i64, _p, _p]),
     "km_emotion_clip_create": (C.c_int, [C.POINTER(_p), C.c_double, C.c_double, _i64]),
     "km_emotion_clip_create_basic": (C.c_int, [C.POINTER(_p), C.c_double, C.c_double, _i64]),
+    "km_emotion_stream_create_long": (C.c_int, [C.POINTER(_p), _i64, C.c_double, C.c_double, _i64]),
+    "km_emotion_clip_create_long": (C.c_int, [C.POINTER(_p), C.c_double, C.c_double, _i64]),
     "km_emotion_clip_width": (C.c_int, [_p]),
     "km_emotion_clip_destroy": (C.c_int, [_p]),
     "km_emotion_clip_set_compression": (C.c_int, [_p, _p, _p, _p]),

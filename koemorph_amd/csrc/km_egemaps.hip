@@ -29,6 +29,7 @@
 #include <memory>
 
 #include "km_context.h"
+#include "km_egemaps_long.h"
 #include "km_egemaps_ragged.h"
 
 namespace km {
@@ -42,6 +43,7 @@ constexpr int MAXF = 2048;              // frames per window the functional kern
 enum Rec { R_LOUD = 0, R_ALPHA, R_HAMM, R_SL0, R_SL1, R_FLUX, R_MFCC, R_RMS = 10, R_CF = 11, R_CS = 14, R_VOI = 17, R_F = 18, R_BW = 21,
            R_F0 = 24, R_JIT, R_SHIM, R_HNR, R_H1H2, R_H1A3, R_FAMP = 30 };
 constexpr float VOICING_CUTOFF = 0.55f, RMS_FLOOR = 0.001f;   // on the autocorrelation measure (oracle/egemaps.py acf_strength)
+static_assert(REC == egml::REC && MAXF == egml::MAXF_SHORT, "km_egemaps_long.hip reads these records");
 }  // namespace egm
 
 struct EgmPlan {
@@ -951,19 +953,28 @@ static EgmArgs egm_args(const EgmPlan* p, const float* audio, int64_t L, int nf,
 }
 
 // The five kernels over ragged windows that live in stream rings (km_emotion_stream.hip): fixed grids of max_nf frames x
-// n_slots windows, everything else from the slot table on the device.
+// n_slots windows, everything else from the slot table on the device.  long_windows: the object was made for windows beyond MAXF
+// frames (km_emotion_*_create_long): max_nf up to 6548, and the two per-window kernels are those of km_egemaps_long.hip for every slot.
 int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
-                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st) {
+                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st, bool long_windows) {
     using namespace egm;
-    if (!plan || !rings_dev || !slots_dev || !scale_dev || !rec_dev || !out_dev || n_slots < 1 || n_slots > 65535 || max_nf < 1 || max_nf > MAXF ||
-        ring_len < 1 || ring_len > (1 << 30))
+    if (!plan || !rings_dev || !slots_dev || !scale_dev || !rec_dev || !out_dev || n_slots < 1 || n_slots > 65535 || max_nf < 1 ||
+        max_nf > (long_windows ? egml::MAXF : MAXF) || ring_len < 1 || ring_len > (1 << 30))
         return fail(KM_ERR_INVALID_ARG, "egm_ragged_functionals: bad argument");
     EgmArgs a = egm_args(static_cast<EgmPlan*>(plan), rings_dev, 0, 0, scale_dev, rec_dev);
     a.rec_frames = max_nf; a.slots = slots_dev; a.ring_len = (int)ring_len;
     hipLaunchKernelGGL(egm_peak_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, rings_dev, (int64_t)0, slots_dev, (int)ring_len, scale_dev);
     hipLaunchKernelGGL(egm_frame_kernel<true>, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(egm_viterbi_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, rec_dev, 0, max_nf, slots_dev);
+    if (long_windows) {
+        HIP_TRY(hipGetLastError());
+        if (const int rc = egm_long_track(rec_dev, 0, max_nf, slots_dev, n_slots, st)) return rc;
+    } else
+        hipLaunchKernelGGL(egm_viterbi_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, rec_dev, 0, max_nf, slots_dev);
     hipLaunchKernelGGL(egm_voiced_kernel<true>, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
+    if (long_windows) {
+        HIP_TRY(hipGetLastError());
+        return egm_long_functional(rec_dev, 0, max_nf, slots_dev, n_slots, out_dev, st);
+    }
     hipLaunchKernelGGL(egm_functional_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, (const float*)rec_dev, 0, max_nf, slots_dev, out_dev);
     HIP_TRY(hipGetLastError());
     return KM_OK;
@@ -997,15 +1008,21 @@ int64_t km_egemaps_workspace_floats(int64_t B, int64_t L) {
     return B * (km_egemaps_num_frames(L) * egm::REC + 4);
 }
 
-int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
-                           int64_t work_floats, float* out_dev, void* stream) {
+// km_egemaps_functionals and km_egemaps_functionals_long (`who` is the name the texts carry).  The latter takes windows of up to 2^20
+// samples: beyond MAXF frames the two per-window kernels of km_egemaps_long.hip run between the same per-frame kernels; up to MAXF
+// frames it launches what the former launches
+static int egm_functionals(const char* who, bool long_windows, void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize,
+                           float* work_dev, int64_t work_floats, float* out_dev, void* stream) {
     using namespace egm;
-    if (!plan || !audio_dev || !work_dev || !out_dev || B <= 0 || L <= 0) return fail(KM_ERR_INVALID_ARG, "km_egemaps_functionals: bad argument");
+    if (!plan || !audio_dev || !work_dev || !out_dev || B <= 0 || L <= 0) return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
     const int64_t nf = km_egemaps_num_frames(L);
-    if (nf < 1) return fail(KM_ERR_INVALID_ARG, "km_egemaps_functionals: the window is shorter than one 60 ms frame (%lld samples)", (long long)L);
-    if (nf > MAXF) return fail(KM_ERR_UNSUPPORTED, "km_egemaps_functionals: %lld frames per window, at most %d (20.5 s)", (long long)nf, MAXF);
-    if (work_floats < km_egemaps_workspace_floats(B, L)) return fail(KM_ERR_WORKSPACE, "km_egemaps_functionals: workspace too small");
-    if (B > 65535) return fail(KM_ERR_UNSUPPORTED, "km_egemaps_functionals: at most 65535 windows per call");
+    if (nf < 1) return fail(KM_ERR_INVALID_ARG, "%s: the window is shorter than one 60 ms frame (%lld samples)", who, (long long)L);
+    if (long_windows && L > egml::MAX_WINDOW)
+        return fail(KM_ERR_UNSUPPORTED, "%s: a window of %lld samples, at most %lld (65.5 s)", who, (long long)L, (long long)egml::MAX_WINDOW);
+    if (!long_windows && nf > MAXF) return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (20.5 s)", who, (long long)nf, MAXF);
+    if (work_floats < km_egemaps_workspace_floats(B, L)) return fail(KM_ERR_WORKSPACE, "%s: workspace too small", who);
+    if (B > 65535) return fail(KM_ERR_UNSUPPORTED, "%s: at most 65535 windows per call", who);
+    const bool lng = nf > MAXF;
     EgmPlan* p = static_cast<EgmPlan*>(plan);
     hipStream_t st = (hipStream_t)stream;
     float* scale = work_dev;                       // (B), padded to 4 B floats
@@ -1016,11 +1033,29 @@ int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_
     }
     const EgmArgs a = egm_args(p, audio_dev, L, (int)nf, normalize ? scale : nullptr, rec);
     hipLaunchKernelGGL(egm_frame_kernel<false>, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(egm_viterbi_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, rec, (int)nf, (int)nf, (const EgmSlot*)nullptr);
+    if (lng) {
+        HIP_TRY(hipGetLastError());
+        if (const int rc = egm_long_track(rec, (int)nf, (int)nf, nullptr, (int)B, st)) return rc;
+    } else
+        hipLaunchKernelGGL(egm_viterbi_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, rec, (int)nf, (int)nf, (const EgmSlot*)nullptr);
     hipLaunchKernelGGL(egm_voiced_kernel<false>, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
+    if (lng) {
+        HIP_TRY(hipGetLastError());
+        return egm_long_functional(rec, (int)nf, (int)nf, nullptr, (int)B, out_dev, st);
+    }
     hipLaunchKernelGGL(egm_functional_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, (const float*)rec, (int)nf, (int)nf, (const EgmSlot*)nullptr, out_dev);
     HIP_TRY(hipGetLastError());
     return KM_OK;
+}
+
+int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
+                           int64_t work_floats, float* out_dev, void* stream) {
+    return egm_functionals("km_egemaps_functionals", false, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev, stream);
+}
+
+int km_egemaps_functionals_long(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
+                                int64_t work_floats, float* out_dev, void* stream) {
+    return egm_functionals("km_egemaps_functionals_long", true, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev, stream);
 }
 
 // The two kernels that are pure functions of the record array, on records the caller wrote (tests): the same kernels, the

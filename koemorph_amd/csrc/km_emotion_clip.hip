@@ -23,6 +23,7 @@
 #include <memory>
 
 #include "km_context.h"
+#include "km_egemaps_long.h"
 #include "km_egemaps_ragged.h"
 #include "km_emotion_common.h"
 #include "km_prosody_ragged.h"
@@ -51,6 +52,7 @@ struct EmotionClip : EmoTiming {
     float* bias = nullptr;     // (256)
     bool has_compression = false;
     bool basic = false;        // the `basic` back end: rows of 9, rec is (max_slots, max_nf, 4), no scale / fout / f0 / w / bias
+    bool long_windows = false; // km_emotion_clip_create_long with more than 2048 frames per window: the per-window kernels of km_egemaps_long.hip
     void* prosody = nullptr;
     ~EmotionClip() { (void)km_egemaps_plan_destroy(plan); (void)km_prosody_plan_destroy(prosody); }
 };
@@ -150,7 +152,8 @@ __global__ __launch_bounds__(256) void ec_rows_kernel(const float* __restrict__ 
     if (valid && c == 0) valid[b] = K > 0 ? 1 : 0;
 }
 
-static int ec_create(const char* fn, void** ec_out, double context_window_s, double update_interval_s, int64_t max_slots, bool basic) {
+static int ec_create(const char* fn, void** ec_out, double context_window_s, double update_interval_s, int64_t max_slots, bool basic,
+                     bool long_windows = false) {
     using namespace ec;
     if (!ec_out) return fail(KM_ERR_INVALID_ARG, "%s: NULL argument", fn);
     *ec_out = nullptr;
@@ -158,8 +161,11 @@ static int ec_create(const char* fn, void** ec_out, double context_window_s, dou
     if (max_slots < 1 || max_slots > 65535) return fail(KM_ERR_INVALID_ARG, "%s: max_slots %lld, 1 .. 65535", fn, (long long)max_slots);
     std::unique_ptr<EmotionClip> e(new (std::nothrow) EmotionClip());
     if (!e) return fail(KM_ERR_HIP, "%s: out of host memory", fn);
-    if (const int rc = emo_timing(fn, context_window_s, update_interval_s, basic, e.get())) return rc;
+    if (const int rc = emo_timing(fn, context_window_s, update_interval_s, basic, e.get(), long_windows)) return rc;
     e->max_slots = max_slots; e->basic = basic;
+    e->long_windows = long_windows && e->max_nf > MAXF;                         // up to 2048 frames it is the plain object
+    if (e->long_windows)
+        if (const int rc = egm_long_prepare()) return rc;
     if (const int rc = basic ? km_prosody_plan_create(&e->prosody) : km_egemaps_plan_create(&e->plan)) return rc;
     const int64_t ms = max_slots, nf = e->max_nf;
     auto layout = [&](char* base) {
@@ -194,7 +200,8 @@ static int ec_build(EmotionClip* e, const float* clips_dev, int64_t B, int64_t L
             if (const int rc = prosody_ragged(e->prosody, clips_dev, L, e->table, ms, e->max_nf, e->rec, emotion_out + g0 * ec::NBASIC, st)) return rc;
             continue;
         }
-        if (const int rc = egm_ragged_functionals(e->plan, clips_dev, L, e->table, ms, e->max_nf, e->scale, e->rec, e->fout, st)) return rc;
+        if (const int rc = egm_ragged_functionals(e->plan, clips_dev, L, e->table, ms, e->max_nf, e->scale, e->rec, e->fout, st, e->long_windows))
+            return rc;
         hipLaunchKernelGGL(ec_epilogue_kernel, dim3(ec::NEMO / ec::TN), dim3(256), 0, st, (const float*)e->fout, (int)(G - g0 < ms ? G - g0 : ms), g0, K,
                            e->f0, (const float*)e->w, (const float*)e->bias, features_out, emotion_out);
         HIP_TRY(hipGetLastError());
@@ -210,6 +217,10 @@ extern "C" {
 
 int km_emotion_clip_create(void** ec_out, double context_window_s, double update_interval_s, int64_t max_slots) {
     return ec_create("km_emotion_clip_create", ec_out, context_window_s, update_interval_s, max_slots, false);
+}
+
+int km_emotion_clip_create_long(void** ec_out, double context_window_s, double update_interval_s, int64_t max_slots) {
+    return ec_create("km_emotion_clip_create_long", ec_out, context_window_s, update_interval_s, max_slots, false, true);
 }
 
 int km_emotion_clip_create_basic(void** ec_out, double context_window_s, double update_interval_s, int64_t max_slots) {

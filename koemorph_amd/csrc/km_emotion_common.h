@@ -35,15 +35,16 @@ inline int emo_check_seconds(const char* fn, double context_window_s, double upd
     return KM_OK;
 }
 
-// The law in samples for checked seconds, or the refusal of what the kernels of the back end cannot hold.
-inline int emo_timing(const char* fn, double context_window_s, double update_interval_s, bool basic, EmoTiming* t) {
+// The law in samples for checked seconds, or the refusal of what the kernels of the back end cannot hold.  long_windows (eGeMAPS
+// only, km_emotion_*_create_long): the window limit of the basic back end takes the place of the 2048 frames.
+inline int emo_timing(const char* fn, double context_window_s, double update_interval_s, bool basic, EmoTiming* t, bool long_windows = false) {
     using namespace emo;
     if (context_window_s > 3600.0) return fail(KM_ERR_UNSUPPORTED, "%s: context window of %g s", fn, context_window_s);
     const int64_t R = (int64_t)((context_window_s + 2.0) * SR), Cw = (int64_t)(context_window_s * SR), C = Cw < R ? Cw : R;
     const int64_t nf = basic ? 1 + C / BASIC_HOP : km_egemaps_num_frames(C);          // 32 ms or 10 ms frames
-    if (basic && C > BASIC_MAX_WINDOW)
+    if ((basic || long_windows) && C > BASIC_MAX_WINDOW)
         return fail(KM_ERR_UNSUPPORTED, "%s: a window of %lld samples, at most %d (65.5 s)", fn, (long long)C, BASIC_MAX_WINDOW);
-    if (!basic && nf > MAXF) return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (20.5 s)", fn, (long long)nf, MAXF);
+    if (!basic && !long_windows && nf > MAXF) return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (20.5 s)", fn, (long long)nf, MAXF);
     t->ring_len = (int)R; t->window_len = (int)C; t->update_samples = (int)(update_interval_s * SR); t->min_samples = SR / 2; t->max_nf = (int)nf;
     return KM_OK;
 }

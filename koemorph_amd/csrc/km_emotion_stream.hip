@@ -23,6 +23,7 @@
 #include <memory>
 
 #include "km_context.h"
+#include "km_egemaps_long.h"
 #include "km_egemaps_ragged.h"
 #include "km_emotion_common.h"
 #include "km_prosody_ragged.h"
@@ -63,6 +64,7 @@ struct EmotionStream : EmoTiming {
     float* bias = nullptr;     // (256)
     bool has_compression = false;
     bool basic = false;        // the `basic` back end: features holds 9 values per stream (row stride 88), no slots, no emotion layer
+    bool long_windows = false; // km_emotion_stream_create_long with more than 2048 frames per window: the per-window kernels of km_egemaps_long.hip
     void* prosody = nullptr;
     ~EmotionStream() { (void)km_egemaps_plan_destroy(plan); (void)km_prosody_plan_destroy(prosody); }
 };
@@ -199,9 +201,9 @@ __global__ __launch_bounds__(256) void es_transpose_kernel(const float* __restri
     if (i < es::NEMO * es::NCAT) { const int o = i / es::NCAT, k = i % es::NCAT; wt[k * es::NEMO + o] = w[i]; }
 }
 
-static int es_create(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates, bool basic) {
+static int es_create(const char* fn, void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates,
+                     bool basic, bool long_windows = false) {
     using namespace es;
-    const char* fn = "km_emotion_stream_create";                                // the name both entry points say
     if (!es_out) return fail(KM_ERR_INVALID_ARG, "%s: NULL argument", fn);
     *es_out = nullptr;
     if (n_streams < 1 || n_streams > MAX_STREAMS) return fail(KM_ERR_INVALID_ARG, "%s: n_streams %lld, 1 .. %d", fn, (long long)n_streams, MAX_STREAMS);
@@ -210,8 +212,11 @@ static int es_create(void** es_out, int64_t n_streams, double context_window_s, 
         return fail(KM_ERR_INVALID_ARG, "%s: max_updates %lld, 1 .. n_streams (%lld)", fn, (long long)max_updates, (long long)n_streams);
     std::unique_ptr<EmotionStream> e(new (std::nothrow) EmotionStream());
     if (!e) return fail(KM_ERR_HIP, "%s: out of host memory", fn);
-    if (const int rc = emo_timing(fn, context_window_s, update_interval_s, basic, e.get())) return rc;
+    if (const int rc = emo_timing(fn, context_window_s, update_interval_s, basic, e.get(), long_windows)) return rc;
     e->n = n_streams; e->max_updates = max_updates; e->basic = basic;
+    e->long_windows = long_windows && e->max_nf > MAXF;                         // up to 2048 frames it is the plain object
+    if (e->long_windows)
+        if (const int rc = egm_long_prepare()) return rc;
     if (const int rc = basic ? km_prosody_plan_create(&e->prosody) : km_egemaps_plan_create(&e->plan)) return rc;
     const int64_t n = n_streams, mu = max_updates, R = e->ring_len, nf = e->max_nf;
     auto layout = [&](char* base) {
@@ -243,11 +248,15 @@ using namespace km;
 extern "C" {
 
 int km_emotion_stream_create(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates) {
-    return es_create(es_out, n_streams, context_window_s, update_interval_s, max_updates, false);
+    return es_create("km_emotion_stream_create", es_out, n_streams, context_window_s, update_interval_s, max_updates, false);
+}
+
+int km_emotion_stream_create_long(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates) {
+    return es_create("km_emotion_stream_create_long", es_out, n_streams, context_window_s, update_interval_s, max_updates, false, true);
 }
 
 int km_emotion_stream_create_basic(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates) {
-    return es_create(es_out, n_streams, context_window_s, update_interval_s, max_updates, true);
+    return es_create("km_emotion_stream_create", es_out, n_streams, context_window_s, update_interval_s, max_updates, true);   // the name both say
 }
 
 int km_emotion_stream_destroy(void* es) {
@@ -299,7 +308,8 @@ int km_emotion_stream_update(void* es, float* emotion_dev, uint8_t* valid_dev, u
         HIP_TRY(hipGetLastError());
         return KM_OK;
     }
-    if (const int rc = egm_ragged_functionals(e->plan, e->ring, e->ring_len, e->table, (int)e->max_updates, e->max_nf, e->scale, e->rec, e->fout, st))
+    if (const int rc = egm_ragged_functionals(e->plan, e->ring, e->ring_len, e->table, (int)e->max_updates, e->max_nf, e->scale, e->rec, e->fout, st,
+                                              e->long_windows))
         return rc;
     hipLaunchKernelGGL(es_epilogue_kernel, dim3((unsigned)e->max_updates), dim3(256), 0, st, (const EgmSlot*)e->table, (const float*)e->fout, e->st,
                        e->features, e->slots, (const float*)e->wt, (const float*)e->bias, e->emotion);

@@ -35,12 +35,16 @@ class ClipEmotion:
     stream holds after that many samples, and bit for bit ``BasicEmotion()(window[None])[0]``.  ``emotion_dim`` is 9, the input of a
     model with ``emotion_dim`` 9; ``build`` -> ``(emotion (K, 9), None)``, ``build_batch`` -> ``((B, K, 9), None)``, ``rows`` takes and
     returns width 9.  There is no compression layer (passing one raises ``ValueError``); the window may hold up to 2**20 samples and
-    the scratch is ``max_slots`` x ``(1 + window_len // 512)`` x 4 floats."""
+    the scratch is ``max_slots`` x ``(1 + window_len // 512)`` x 4 floats.
+
+    ``long_windows=True`` (km_emotion_clip_create_long): eGeMAPS windows of up to 2**20 samples (65.5 s) instead of 2048 frames --
+    ``ClipEmotion(30.0, 0.2, long_windows=True)`` is the track of the reference's ``long_context`` variant, bit for bit the rows of a
+    ``StreamEmotion(1, 30.0, 0.2, long_windows=True)`` stream.  The scratch grows with the window: 0.43 MB per slot at 30 s."""
 
     def __init__(self, context_window: float = 20.0, update_interval: float = 0.3, max_slots: int = 64,
-                 compression_layer: Optional[torch.nn.Module] = None, device="cuda", backend: str = "egemaps"):
-        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend)
-        self.backend = backend
+                 compression_layer: Optional[torch.nn.Module] = None, device="cuda", backend: str = "egemaps", long_windows: bool = False):
+        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend, long_windows=long_windows)
+        self.backend, self.long_windows = backend, long_windows
         if backend == "basic" and compression_layer is not None:
             raise ValueError("the basic back end has no compression layer: its nine features are the emotion input as they are")
         if not 1 <= max_slots <= 65535:
@@ -49,7 +53,8 @@ class ClipEmotion:
             raise _lib.KoeMorphError(_lib.KM_ERR_HIP, "no GPU visible: the clip emotion track has no CPU fallback")
         self.context_window, self.update_interval, self.max_slots = context_window, update_interval, max_slots
         self._lib = _lib.load()
-        create = self._lib.km_emotion_clip_create_basic if backend == "basic" else self._lib.km_emotion_clip_create
+        create = (self._lib.km_emotion_clip_create_basic if backend == "basic" else
+                  self._lib.km_emotion_clip_create_long if long_windows else self._lib.km_emotion_clip_create)
         self.device, self._h, self.compression_layer, self.emotion_dim, _ = _create_emotion_backend(
             backend, compression_layer, device, lambda h: create(h, context_window, update_interval, max_slots),
             self._lib.km_emotion_clip_set_compression)

@@ -125,8 +125,10 @@ class EGeMAPSEngine:
     def num_frames(self, L: int) -> int:
         return int(self._lib.km_egemaps_num_frames(L))
 
-    def functionals(self, audio, normalize: bool = True):
-        """audio (B, L) fp32 on the device -> (B, 88) eGeMAPSv02 functionals."""
+    def functionals(self, audio, normalize: bool = True, long_windows: bool = False):
+        """audio (B, L) fp32 on the device -> (B, 88) eGeMAPSv02 functionals.  Windows of more than 2048 frames (20.5 s) are
+        refused unless ``long_windows`` (km_egemaps_functionals_long: up to 2**20 samples, 65.5 s); a window of at most 2048 frames
+        runs the same launches either way."""
         torch = self._torch
         audio = audio.to(self.device, torch.float32).contiguous()
         if audio.dim() != 2:
@@ -137,9 +139,10 @@ class EGeMAPSEngine:
             self._work = torch.empty(need, device=self.device)
         self._work_for = (B, L)
         out = torch.empty(B, EGEMAPS_DIM, device=self.device)
+        call = self._lib.km_egemaps_functionals_long if long_windows else self._lib.km_egemaps_functionals
         with torch.cuda.device(self.device):
-            check(self._lib.km_egemaps_functionals(self._plan, audio.data_ptr(), B, L, 1 if normalize else 0, self._work.data_ptr(),
-                                                   self._work.numel(), out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+            check(call(self._plan, audio.data_ptr(), B, L, 1 if normalize else 0, self._work.data_ptr(), self._work.numel(), out.data_ptr(),
+                       torch.cuda.current_stream(self.device).cuda_stream))
         return out
 
     def records(self) -> np.ndarray:
@@ -160,24 +163,27 @@ class EGeMAPSEngine:
             raise ValueError(f"Expected records (B, frames, 36), got {tuple(rec.shape)}")
         return rec
 
-    def track_from_records(self, rec):
-        """records (B, frames, 36) -> a copy on the device whose F0 column the pitch-track kernel has rewritten (tests)."""
+    def track_from_records(self, rec, long_windows: bool = False):
+        """records (B, frames, 36) -> a copy on the device whose F0 column the pitch-track kernel has rewritten (tests).
+        ``long_windows``: the kernel for up to 6548 frames (km_egemaps_track_from_records_long), at any frame count."""
         torch = self._torch
         rec = self._records_on_device(rec).clone()
         B, nf, _ = rec.shape
         with torch.cuda.device(self.device):
-            check(self._lib.km_egemaps_track_from_records(rec.data_ptr(), B, nf, torch.cuda.current_stream(self.device).cuda_stream))
+            call = self._lib.km_egemaps_track_from_records_long if long_windows else self._lib.km_egemaps_track_from_records
+            check(call(rec.data_ptr(), B, nf, torch.cuda.current_stream(self.device).cuda_stream))
         return rec
 
-    def functionals_from_records(self, rec):
-        """records (B, frames, 36) -> (B, 88): the functionals kernel alone (tests)."""
+    def functionals_from_records(self, rec, long_windows: bool = False):
+        """records (B, frames, 36) -> (B, 88): the functionals kernel alone (tests).  ``long_windows``: the kernel for up to 6548
+        frames (km_egemaps_functionals_from_records_long), at any frame count."""
         torch = self._torch
         rec = self._records_on_device(rec)
         B, nf, _ = rec.shape
         out = torch.empty(B, EGEMAPS_DIM, device=self.device)
         with torch.cuda.device(self.device):
-            check(self._lib.km_egemaps_functionals_from_records(rec.data_ptr(), B, nf, out.data_ptr(),
-                                                                torch.cuda.current_stream(self.device).cuda_stream))
+            call = self._lib.km_egemaps_functionals_from_records_long if long_windows else self._lib.km_egemaps_functionals_from_records
+            check(call(rec.data_ptr(), B, nf, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
         return out
 
 
@@ -187,7 +193,7 @@ class OpenSMILEeGeMAPSExtractor:
     def __init__(self, sample_rate: int = 16000, context_window: float = 20.0, update_interval: float = 0.3,
                  feature_set: str = "eGeMAPSv02", feature_level: str = "Functionals", enable_caching: bool = True,
                  cache_dir: Optional[str] = None, device: str = "cpu", temporal_history_frames: int = 30,
-                 use_concatenation: bool = False, clock=time.time):
+                 use_concatenation: bool = False, clock=time.time, long_windows: bool = False):
         if sample_rate != 16000:
             raise ValueError("the GPU eGeMAPS extractor is built for 16 kHz audio")
         if context_window < 1.0:
@@ -205,6 +211,7 @@ class OpenSMILEeGeMAPSExtractor:
         self.device = device
         self.temporal_history_frames, self.use_concatenation = temporal_history_frames, use_concatenation
         self._clock = clock
+        self.long_windows = long_windows                     # windows beyond 2048 frames (20.5 s): the long_context variant's 30 s
         self.engine = EGeMAPSEngine(device)
         self.feature_dim = EGEMAPS_DIM
         self.audio_buffer = AudioBuffer(max_duration=context_window + 2.0, sample_rate=sample_rate)
@@ -229,7 +236,7 @@ class OpenSMILEeGeMAPSExtractor:
         import torch
         if isinstance(audio, np.ndarray):
             audio = torch.from_numpy(np.ascontiguousarray(audio, np.float32))
-        return self.engine.functionals(audio, normalize)
+        return self.engine.functionals(audio, normalize, long_windows=self.long_windows)
 
     def _extract_features_from_audio(self, audio: np.ndarray) -> Optional[np.ndarray]:
         """One window -> (88,) float32 (reference :427-454: float32, peak normalisation, NaN / Inf -> 0)."""
@@ -439,4 +446,5 @@ def create_opensmile_extractor(config: Dict) -> OpenSMILEeGeMAPSExtractor:
         update_interval=config.get("update_interval", 0.3), feature_set=config.get("feature_set", "eGeMAPSv02"),
         feature_level=config.get("feature_level", "Functionals"), enable_caching=config.get("enable_caching", True),
         cache_dir=config.get("cache_dir"), device=config.get("device", "cpu"),
-        temporal_history_frames=config.get("temporal_history_frames", 30), use_concatenation=config.get("use_concatenation", False))
+        temporal_history_frames=config.get("temporal_history_frames", 30), use_concatenation=config.get("use_concatenation", False),
+        long_windows=config.get("long_windows", False))

@@ -2,7 +2,7 @@
 
     python -m koemorph_amd.scripts.render_sequential --model_path ckpt.pth --input_audio a.wav --output_json out.jsonl
                                                      [--stride 1] [--emotion egemaps|basic|noise] [--attention-summary summary.json]
-                                                     [--share-frames]
+                                                     [--share-frames] [--emotion-context-window S] [--emotion-update-interval S]
 
 The clip goes through ``SequentialDualStreamModel.forward`` (one output frame per window position, EMA along the clip) and every
 frame is written as one ``{"timestamp", "blendshapes"}`` line, encoded by ``koemorph_amd.wire`` as the streaming scripts encode
@@ -14,7 +14,10 @@ checkpoints trained with ``--variant basic --emotion basic``; ``noise`` is the r
 ``--attention-summary`` writes what the reference's AttentionVisualizer reduces the clip's attention maps to (``AttentionStats``:
 mean map, mean entropy and peak histogram per mouth query, mean and share per frequency band) as one JSON object; the maps are
 reduced on the device tile by tile, no (frames, 28, 80) array is made.  ``--share-frames`` computes the clip's STFT once at every
-model shape and hop (``SequentialDualStreamModel(share_frames=True)``).
+model shape and hop (``SequentialDualStreamModel(share_frames=True)``).  The emotion track's context window and update interval are
+the checkpoint's (``model_config["emotion_context_window"]`` / ``["emotion_update_interval"]``, written by ``train_sequential`` when
+its flags of the same names were given), else 20.0 s / 0.3 s; the two flags here set them for a checkpoint that carries none and are
+refused where they contradict the checkpoint.
 """
 from __future__ import annotations
 
@@ -53,10 +56,31 @@ def compression_layer(ckpt: dict) -> "tuple[torch.nn.Linear, str]":
     return layer, f"default initialisation, seed {COMPRESSION_SEED}"
 
 
-def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: str = "cuda",
-               share_frames: bool = False) -> SequentialDualStreamModel:
+class EmotionTimingError(ValueError):
+    """A timing flag that contradicts the checkpoint, or one given without an emotion track (a usage error on the command line)."""
+
+
+def emotion_timing(cfg: dict, context_window: Optional[float], update_interval: Optional[float]) -> "Optional[tuple[float, float]]":
+    """(context window, update interval) of the emotion track, or None for the 20.0 s / 0.3 s object as ever: the checkpoint's
+    values where it carries them, else the flags; a flag that contradicts the checkpoint is a ValueError."""
+    saved = (cfg.get("emotion_context_window"), cfg.get("emotion_update_interval"))
+    for name, flag, have in (("--emotion-context-window", context_window, saved[0]), ("--emotion-update-interval", update_interval, saved[1])):
+        if flag is not None and have is not None and float(flag) != float(have):
+            raise EmotionTimingError(f"{name} {flag:g} contradicts the checkpoint, which was trained with {float(have):g}")
+    cw = saved[0] if saved[0] is not None else context_window
+    ui = saved[1] if saved[1] is not None else update_interval
+    if cw is None and ui is None:
+        return None
+    return float(20.0 if cw is None else cw), float(0.3 if ui is None else ui)
+
+
+def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: str = "cuda", share_frames: bool = False,
+               emotion_context_window: Optional[float] = None, emotion_update_interval: Optional[float] = None) -> SequentialDualStreamModel:
     ckpt = torch.load(model_path, map_location="cpu", weights_only=True)
     cfg = dict(ckpt.get("model_config") or {})
+    timing = emotion_timing(cfg, emotion_context_window, emotion_update_interval)
+    if timing is not None and emotion == "noise":
+        raise EmotionTimingError("the emotion track's context window and update interval need --emotion egemaps or basic")
     emotion_dim = int(cfg.get("emotion_dim", 256))
     width = {"egemaps": 256, "basic": 9}.get(emotion)
     if width is not None and width != emotion_dim:
@@ -65,10 +89,11 @@ def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: st
     if emotion == "egemaps":
         layer, source = compression_layer(ckpt)
         logger.info("emotion track: eGeMAPS, compression layer from the %s", source)
-        clip_emotion = ClipEmotion(compression_layer=layer, device=device)
+        clip_emotion = (ClipEmotion(compression_layer=layer, device=device) if timing is None else
+                        ClipEmotion(*timing, compression_layer=layer, device=device, long_windows=True))
     elif emotion == "basic":
         logger.info("emotion track: the nine basic prosodic values per row")
-        clip_emotion = ClipEmotion(device=device, backend="basic")
+        clip_emotion = ClipEmotion(device=device, backend="basic") if timing is None else ClipEmotion(*timing, device=device, backend="basic")
     model = SequentialDualStreamModel(d_model=int(cfg.get("d_model", 256)), num_heads=int(cfg.get("num_heads", 8)),
                                       mel_sequence_length=int(cfg.get("mel_sequence_length", 256)), stride_frames=stride,
                                       emotion_config={"emotion_dim": emotion_dim, "backend": "basic" if emotion_dim == 9 else "opensmile"},
@@ -137,6 +162,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="upload the file at its own rate and convert it to the model's rate on the device")
     p.add_argument("--share-frames", dest="share_frames", action="store_true",
                    help="compute the clip's STFT once and assemble the windows on the device (engine option seq_assemble)")
+    p.add_argument("--emotion-context-window", dest="emotion_context_window", type=float, default=None, metavar="SECONDS",
+                   help="seconds of audio behind a row of the emotion track, for a checkpoint that does not say (default 20.0; "
+                        "configs/model/dual_stream.yaml: fast 10, long_context 30); refused where it contradicts the checkpoint")
+    p.add_argument("--emotion-update-interval", dest="emotion_update_interval", type=float, default=None, metavar="SECONDS",
+                   help="seconds between two rows of the emotion track (default 0.3; fast 0.5, long_context 0.2); as above")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -144,7 +174,11 @@ def build_parser() -> argparse.ArgumentParser:
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
-    model = load_model(args.model_path, args.stride, args.emotion, args.device, args.share_frames)
+    try:
+        model = load_model(args.model_path, args.stride, args.emotion, args.device, args.share_frames, args.emotion_context_window,
+                           args.emotion_update_interval)
+    except EmotionTimingError as exc:
+        build_parser().error(str(exc))
     if args.device_resample:
         audio = load_audio_device_resample(args.input_audio, model.sample_rate, next(model.parameters()).device)
     else:

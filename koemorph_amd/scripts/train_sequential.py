@@ -45,7 +45,8 @@ class SequentialTrainer:
                  device: str = "cuda", learning_rate: float = 1e-4, weight_decay: float = 1e-5, gradient_clip: float = 1.0,
                  mse_weight: float = 1.0, l1_weight: float = 0.0, extra_loss_terms: Optional[Dict[str, float]] = None,
                  emotion_provider: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, dropout: float = 0.1, seed: int = 0,
-                 from_clip: bool = False, clip_emotion: Optional[ClipEmotion] = None, clip_assemble: bool = False):
+                 from_clip: bool = False, clip_emotion: Optional[ClipEmotion] = None, clip_assemble: bool = False,
+                 record_emotion_timing: bool = False):
         """``from_clip``: batches that name their windows inside the resident clip (``resident_windows=True`` data sets) go
         through ``Trainer.step_clip`` -- no window copy, shared STFT frames; same losses and weights, bit for bit.  An
         ``emotion_provider`` is handed window audio, so with one installed the trainer stays on the gathered path.
@@ -68,6 +69,8 @@ class SequentialTrainer:
                              f"the engine's emotion_dim is {engine.emotion_dim}")
         self.emotion_provider = emotion_provider
         self.clip_emotion = clip_emotion
+        # the track's context window and update interval go into the checkpoint's model_config (render_sequential builds the same track)
+        self.record_emotion_timing = record_emotion_timing and clip_emotion is not None
         self.from_clip = from_clip
         if clip_assemble:
             engine.set_option("clip_assemble", 1)
@@ -305,6 +308,9 @@ class SequentialTrainer:
                                  "mel_sequence_length": self.engine.mel_sequence_length, "emotion_dim": self.engine.emotion_dim,
                                  "emotion_backend": self.clip_emotion.backend if self.clip_emotion is not None else
                                  ("provider" if self.emotion_provider is not None else "noise")}}
+        if self.record_emotion_timing:
+            ckpt["model_config"].update(emotion_context_window=float(self.clip_emotion.context_window),
+                                        emotion_update_interval=float(self.clip_emotion.update_interval))
         if self.rank == 0:
             torch.save(ckpt, path)
             if is_best:
@@ -364,6 +370,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "(ClipEmotion; implies resident batches, what a StreamEmotion serves at inference); basic = the same track "
                         "of nine prosodic values per row (ClipEmotion(backend='basic'), what StreamEmotion(backend='basic') serves; "
                         "needs an emotion_dim of 9: --variant basic)")
+    p.add_argument("--emotion-context-window", dest="emotion_context_window", type=float, default=None, metavar="SECONDS",
+                   help="seconds of audio behind a row of the emotion track (default 20.0).  configs/model/dual_stream.yaml: fast 10, "
+                        "long_context 30.  Given, the eGeMAPS track takes windows beyond 20.5 s (ClipEmotion(long_windows=True), up to "
+                        "65.5 s) and both values are written into the checkpoint's model_config")
+    p.add_argument("--emotion-update-interval", dest="emotion_update_interval", type=float, default=None, metavar="SECONDS",
+                   help="seconds between two rows of the emotion track (default 0.3).  configs/model/dual_stream.yaml: fast 0.5, "
+                        "long_context 0.2.  Given, as --emotion-context-window")
     p.add_argument("--variant", choices=tuple(VARIANTS), default="default",
                    help="the model shape, as configs/model/dual_stream.yaml names its variants: d_model, heads, emotion_dim and the "
                         "default of --window_frames")
@@ -393,7 +406,22 @@ def parse_args(argv=None) -> argparse.Namespace:
                 "use --variant basic")
     if args.emotion == "egemaps" and args.emotion_dim != 256:
         p.error(f"--emotion egemaps produces 256 values per window, the emotion_dim of --variant {args.variant} is {args.emotion_dim}")
+    args.emotion_timing_given = args.emotion_context_window is not None or args.emotion_update_interval is not None
+    if args.emotion_timing_given and args.emotion == "noise":
+        p.error("--emotion-context-window / --emotion-update-interval shape the emotion track: use --emotion egemaps or basic")
     return args
+
+
+def clip_emotion_from_args(args, device) -> Optional[ClipEmotion]:
+    """The ClipEmotion of the command line: none for noise; without the two timing flags the 20.0 s / 0.3 s object as ever; with
+    either, that timing and -- eGeMAPS -- windows beyond 2048 frames (the basic back end takes them as it is)."""
+    if args.emotion not in ("egemaps", "basic"):
+        return None
+    if not args.emotion_timing_given:
+        return ClipEmotion(device=device, backend=args.emotion)
+    return ClipEmotion(20.0 if args.emotion_context_window is None else args.emotion_context_window,
+                       0.3 if args.emotion_update_interval is None else args.emotion_update_interval,
+                       device=device, backend=args.emotion, long_windows=args.emotion == "egemaps")
 
 
 def main(argv=None):
@@ -415,8 +443,8 @@ def main(argv=None):
     st = SequentialTrainer(eng, train, val, device=device, learning_rate=args.learning_rate, weight_decay=args.weight_decay,
                            gradient_clip=args.gradient_clip, l1_weight=args.l1_weight, dropout=args.dropout, seed=args.seed,
                            from_clip=args.resident_clip,
-                           clip_emotion=ClipEmotion(device=device, backend=args.emotion) if track else None,
-                           clip_assemble=args.clip_assemble)
+                           clip_emotion=clip_emotion_from_args(args, device), clip_assemble=args.clip_assemble,
+                           record_emotion_timing=args.emotion_timing_given)
     if args.resume:
         st.load_checkpoint(args.resume)
     for _ in range(st.epoch, args.epochs):

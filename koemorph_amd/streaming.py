@@ -384,16 +384,20 @@ class LegacyStreamEngine:
 
 
 def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 0.3, sample_rate: int = 16000,
-                         backend: str = "egemaps") -> dict:
+                         backend: str = "egemaps", long_windows: bool = False) -> dict:
     """The arithmetic of the reference's OpenSMILEeGeMAPSExtractor in samples, which km_emotion_stream_create follows: the
     AudioBuffer of ``context_window + 2`` seconds (opensmile_extractor.py:245-248), the window ``get_window(context_window)`` returns
     once that much audio has arrived, the samples between two updates of a stream, the half second below which nothing is extracted
     (:388-389) and the 10 ms frames of a full window.  ValueError where km_emotion_stream_create refuses: the constructor's own
     checks (:204-209) and a window of more than 2048 frames (20.5 s), which the functionals kernel cannot hold.
     ``backend="basic"`` (km_emotion_stream_create_basic): the same rings and rule; ``max_frames`` counts the 32 ms frames of the
-    prosodic features, ``1 + window_len // 512``, and the window may hold up to 2**20 samples (65.5 s)."""
+    prosodic features, ``1 + window_len // 512``, and the window may hold up to 2**20 samples (65.5 s).
+    ``long_windows=True`` (eGeMAPS only; km_emotion_stream_create_long): the window limit is the basic back end's, 2**20 samples or
+    6548 frames, instead of 2048 frames -- the reference's ``long_context`` variant has 30 s / 0.2 s, 2995 frames."""
     if backend not in ("egemaps", "basic"):
         raise ValueError(f"backend must be 'egemaps' or 'basic', got {backend!r}")
+    if long_windows and backend != "egemaps":
+        raise ValueError("long_windows is the eGeMAPS back end's switch: the basic back end takes windows of 2**20 samples as it is")
     if sample_rate != 16000:
         raise ValueError("the GPU eGeMAPS extractor is built for 16 kHz audio")
     if not context_window >= 1.0:
@@ -410,7 +414,9 @@ def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 
             raise ValueError(f"a window of {window_len} samples, at most {1 << 20} (65.5 s)")
     else:
         max_frames = (window_len - 960) // 160 + 1
-        if max_frames > 2048:
+        if long_windows and window_len > 1 << 20:
+            raise ValueError(f"a window of {window_len} samples, at most {1 << 20} (65.5 s)")
+        if not long_windows and max_frames > 2048:
             raise ValueError(f"{max_frames} frames per window, at most 2048 (20.5 s)")
     return dict(ring_len=ring_len, window_len=window_len, update_samples=int(update_interval * sample_rate),
                 min_samples=int(0.5 * sample_rate), max_frames=max_frames)
@@ -458,12 +464,17 @@ class StreamEmotion:
     stream's row is the nine raw prosodic values of its window -- bit for bit ``BasicEmotion()(window[None])[0]``
     (koemorph_amd.features.basic_emotion: EmotionExtractor._extract_basic).  ``emotion`` and ``features`` are ``(n_streams, 9)``,
     the input of a model with ``emotion_dim`` 9; there is no peak normalisation, no slots (``slots`` raises) and no compression
-    layer (passing one raises ``ValueError``)."""
+    layer (passing one raises ``ValueError``).
+
+    ``long_windows=True`` (km_emotion_stream_create_long): eGeMAPS windows of up to 2**20 samples (65.5 s) instead of 2048 frames
+    (20.5 s) -- ``StreamEmotion(n, 30.0, 0.2, long_windows=True)`` is the reference's ``long_context`` variant.  Every call is
+    unchanged; an object whose window has at most 2048 frames is the plain object."""
 
     def __init__(self, n_streams: int, context_window: float = 20.0, update_interval: float = 0.3, max_updates: Optional[int] = None,
-                 compression_layer: Optional[torch.nn.Module] = None, device="cuda", backend: str = "egemaps"):
-        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend)
-        self.backend = backend
+                 compression_layer: Optional[torch.nn.Module] = None, device="cuda", backend: str = "egemaps",
+                 long_windows: bool = False):
+        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend, long_windows=long_windows)
+        self.backend, self.long_windows = backend, long_windows
         if backend == "basic" and compression_layer is not None:
             raise ValueError("the basic back end has no compression layer: its nine features are the emotion input as they are")
         if max_updates is None:
@@ -476,7 +487,8 @@ class StreamEmotion:
         self.context_window, self.update_interval = context_window, update_interval
         self.ring_len = self.shape["ring_len"]
         self._lib = _lib.load()
-        create = self._lib.km_emotion_stream_create_basic if backend == "basic" else self._lib.km_emotion_stream_create
+        create = (self._lib.km_emotion_stream_create_basic if backend == "basic" else
+                  self._lib.km_emotion_stream_create_long if long_windows else self._lib.km_emotion_stream_create)
         self.device, self._h, self.compression_layer, self.emotion_dim, self.feature_dim = _create_emotion_backend(
             backend, compression_layer, device, lambda h: create(h, n_streams, context_window, update_interval, max_updates),
             self._lib.km_emotion_stream_set_compression)

@@ -44,7 +44,17 @@ def cycle(i):
     track, _ = ce.build(clip)
     ce.rows(track, clip.shape[0], torch.tensor([0, 1, 2, 9], dtype=torch.int32, device="cuda"), 266, 32)
     ce.close()
-    del ctr, c, clip, ce, track
+    # one long eGeMAPS track (a 21 s window has 2095 frames, beyond the 2048 of the plain object) and one long stream update: the
+    # plan and the frame records behind the per-window kernels for long windows
+    from koemorph_amd.streaming import StreamEmotion
+    long_clip = audio[:4].reshape(-1)[:22 * 16000].contiguous()
+    lce = ClipEmotion(21.0, 10.0, max_slots=2, long_windows=True)
+    ltrack, _ = lce.build(long_clip)
+    lce.rows(ltrack, long_clip.shape[0], torch.tensor([0, 1, 2, 9], dtype=torch.int32, device="cuda"), 266, 32)
+    lce.close()
+    lse = StreamEmotion(1, 21.0, 10.0, long_windows=True)
+    lse.push(long_clip[None]); lse.update(); lse.close()
+    del ctr, c, clip, ce, track, long_clip, lce, ltrack, lse
     m = KoeMorphModel(d_model=64, d_query=64, num_heads=4, num_encoder_layers=1, num_attention_layers=1, decoder_hidden_dim=32, emotion_dim=8).cuda().eval()
     with torch.no_grad():
         m(torch.randn(2, 12, 80, device="cuda"), torch.randn(2, 12, 8, device="cuda"))
