@@ -13,11 +13,11 @@
 //   egm_peak_kernel        per window: 1 / max |x|                                   (opensmile_extractor.py:431-433)
 //   egm_frame_kernel       per 10 ms frame: 60 ms Gaussian + 20 ms Hamming frames as ONE 1024-point complex FFT in LDS,
 //                          spectral descriptors, loudness, MFCC 1-4, sub-harmonic-summation pitch candidates, LPC formants
-//   egm_viterbi_kernel     per window: pitch track over the candidates (sequential dynamic programme, 4 states)
+//   egm_viterbi_kernel     per window: pitch track over the candidates (sequential dynamic programme, 4 states); km_egemaps_window.hip
 //   egm_voiced_kernel      per voiced frame: HNR (autocorrelation), jitter / shimmer (pitch periods marked in the
 //                          waveform), harmonic differences and formant amplitudes
 //   egm_functional_kernel  per window: 3-frame smoothing, means / normalised deviations / percentiles (bitonic sort in
-//                          LDS) / slopes of rising and falling parts over voiced, unvoiced or all frames
+//                          LDS) / slopes of rising and falling parts over voiced, unvoiced or all frames; km_egemaps_window.hip
 // Each kernel has two instantiations: over a dense (B, L) array of windows (km_egemaps_*), and over ragged windows that are read
 // in place from stream rings through a slot table written on the device (egm_ragged_functionals, for km_emotion_stream.hip).
 #include <hip/hip_runtime.h>
@@ -29,21 +29,16 @@
 #include <memory>
 
 #include "km_context.h"
-#include "km_egemaps_long.h"
+#include "km_egemaps_dev.h"
 #include "km_egemaps_ragged.h"
+#include "km_egemaps_window.h"
 
 namespace km {
 
 
-namespace egm {
-constexpr int SR = 16000, HOP = 160, N60 = 960, N20 = 320, NFFT = 1024, NB = NFFT / 2 + 1, OFF20 = (N60 - N20) / 2;
+namespace egm {                         // SR, HOP, the record layout and the voicing thresholds: km_egemaps_dev.h
+constexpr int N60 = 960, N20 = 320, NFFT = 1024, NB = NFFT / 2 + 1, OFF20 = (N60 - N20) / 2;
 constexpr int NBANDS = 26, LPC = 11, NCAND = 3, PPO = 48, NHARM = 15;
-constexpr int REC = 36;                 // floats per frame record (layout below)
-constexpr int MAXF = 2048;              // frames per window the functional kernel holds in LDS (20.5 s)
-enum Rec { R_LOUD = 0, R_ALPHA, R_HAMM, R_SL0, R_SL1, R_FLUX, R_MFCC, R_RMS = 10, R_CF = 11, R_CS = 14, R_VOI = 17, R_F = 18, R_BW = 21,
-           R_F0 = 24, R_JIT, R_SHIM, R_HNR, R_H1H2, R_H1A3, R_FAMP = 30 };
-constexpr float VOICING_CUTOFF = 0.55f, RMS_FLOOR = 0.001f;   // on the autocorrelation measure (oracle/egemaps.py acf_strength)
-static_assert(REC == egml::REC && MAXF == egml::MAXF_SHORT, "km_egemaps_long.hip reads these records");
 }  // namespace egm
 
 struct EgmPlan {
@@ -218,24 +213,11 @@ __global__ __launch_bounds__(256) void egm_peak_kernel(const float* __restrict__
     if (threadIdx.x == 0) scale[blockIdx.x] = red[0] > 0.f ? 1.0f / red[0] : 1.0f;
 }
 
-// block-wide reductions (256 threads = 4 waves), fixed order: an xor butterfly inside each wave, then the four wave results
-// in wave order through 4 floats of LDS scratch -- two barriers instead of the ten of a 256-element LDS tree
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+// block-wide maximum, as block_sum (km_egemaps_dev.h): a butterfly inside each wave, then the four wave results in wave order
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 __device__ __forceinline__ float block_max(float v, float* red) {
     v = wave_max(v);
@@ -545,81 +527,6 @@ __global__ __launch_bounds__(256, 6) void egm_frame_kernel(EgmArgs a) {
     }
 }
 
-// pitch track over the candidates: states 0..2 = candidate, 3 = unvoiced.  One thread per window walks the frames; the
-// back pointers live in the bp LDS array (two bits per state), which the backtrack then overwrites with the chosen state.
-template <bool RAGGED>
-__global__ __launch_bounds__(256) void egm_viterbi_kernel(float* __restrict__ recs, int nf, int rec_frames, const EgmSlot* __restrict__ slots) {
-    using namespace egm;
-    // The recursion itself is sequential (thread 0), but its inputs are not: all threads first gather the seven numbers a
-    // step needs -- voicing flag, log2 of the three candidate frequencies, their strengths -- into LDS, so that the walk
-    // reads LDS instead of paying a global round trip per frame (2.7 ms -> 0.2 ms per call), and write the chosen F0 back
-    // together at the end.  Same arithmetic in the same order as before.
-    __shared__ float in[7 * MAXF];            // [0] voiced-ok, [1..3] log2 f (or -1: no candidate), [4..6] strength
-    __shared__ unsigned char bp[MAXF];        // back pointers (two bits per state), then the chosen state
-    if constexpr (RAGGED) {
-        const EgmSlot sl = slots[blockIdx.x];
-        if (sl.stream < 0) return;
-        nf = sl.nf;
-    }
-    float* rec = recs + (int64_t)blockIdx.x * rec_frames * REC;
-    for (int t = threadIdx.x; t < nf; t += 256) {
-        const float* r = rec + (int64_t)t * REC;
-        in[t] = (r[R_VOI] >= VOICING_CUTOFF && r[R_RMS] >= RMS_FLOOR) ? 1.f : 0.f;
-        for (int c = 0; c < 3; ++c) {
-            const float f = r[R_CF + c];
-            in[(1 + c) * MAXF + t] = f > 0.f ? log2f(f) : -1.f;       // candidates are >= 25 Hz: log2 > 0
-            in[(4 + c) * MAXF + t] = r[R_CS + c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float w_local = 2.0f, w_vv = 10.0f, w_vuv = 10.0f / 8.0f, w_thr = 4.0f, INF = 1e30f;
-        float cost[4], lf_prev[3] = {0.f, 0.f, 0.f};
-        for (int t = 0; t < nf; ++t) {
-            const bool vok = in[t] != 0.f;
-            float loc[4], lf[3];
-            for (int c = 0; c < 3; ++c) {
-                const float l2 = in[(1 + c) * MAXF + t];
-                const bool has = l2 >= 0.f;
-                lf[c] = has ? l2 : 0.f;
-                loc[c] = has ? w_local * (1.0f - in[(4 + c) * MAXF + t]) + (vok ? 0.f : w_thr) : INF;
-            }
-            loc[3] = vok ? w_thr : 0.f;
-            float nc[4];
-            int packed = 0;                                   // back pointers: two bits per state
-            for (int s = 0; s < 4; ++s) {
-                if (t == 0) { nc[s] = loc[s]; continue; }
-                if (loc[s] >= INF) { nc[s] = INF; continue; }
-                float best = INF; int arg = 0;
-                for (int p = 0; p < 4; ++p) {
-                    if (cost[p] >= INF) continue;
-                    const float tr = (s < 3 && p < 3) ? w_vv * fabsf(lf[s] - lf_prev[p]) : ((s == 3 && p == 3) ? 0.f : w_vuv);
-                    const float v = cost[p] + tr;
-                    if (v < best) { best = v; arg = p; }
-                }
-                nc[s] = best + loc[s];
-                packed |= arg << (2 * s);
-            }
-            bp[t] = (unsigned char)packed;
-            for (int s = 0; s < 4; ++s) cost[s] = nc[s];
-            for (int c = 0; c < 3; ++c) lf_prev[c] = lf[c];
-        }
-        int s = 0;
-        for (int q = 1; q < 4; ++q) if (cost[q] < cost[s]) s = q;
-        for (int t = nf - 1; t >= 0; --t) {
-            const int packed = bp[t];
-            bp[t] = (unsigned char)s;                         // the state chosen for frame t
-            s = (packed >> (2 * s)) & 3;
-        }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < nf; t += 256) {
-        float* r = rec + (int64_t)t * REC;
-        const int st = bp[t];
-        r[R_F0] = st < 3 ? r[R_CF + st] : 0.f;
-    }
-}
-
 template <bool RAGGED>
 __global__ __launch_bounds__(256) void egm_voiced_kernel(EgmArgs a) {
     using namespace egm;
@@ -749,196 +656,6 @@ __global__ __launch_bounds__(256) void egm_voiced_kernel(EgmArgs a) {
     }
 }
 
-// ---- functionals: one workgroup per window ---------------------------------------------------------------------------
-struct FuncScratch {
-    float* v;       // [MAXF] contour (smoothed)
-    float* s;       // [MAXF] sort buffer
-    float* red;     // [256]
-};
-
-__device__ __forceinline__ void bitonic_sort(float* s, int n2) {      // ascending, n2 a power of two, padding = +inf
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < n2; i += 256) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const bool up = (i & k) == 0;
-                    const float x = s[i], y = s[ixj];
-                    if ((x > y) == up) { s[i] = y; s[ixj] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-template <bool RAGGED>
-__global__ __launch_bounds__(256) void egm_functional_kernel(const float* __restrict__ recs, int nf, int rec_frames, const EgmSlot* __restrict__ slots,
-                                                             float* __restrict__ out) {
-    using namespace egm;
-    __shared__ float v[MAXF], s[MAXF], f0s[MAXF], red[256], res[16];
-    __shared__ int cnt_s[4];
-    const int tid = threadIdx.x;
-    if constexpr (RAGGED) {
-        const EgmSlot sl = slots[blockIdx.x];
-        if (sl.stream < 0) return;
-        nf = sl.nf;
-    }
-    const float* rec = recs + (int64_t)blockIdx.x * rec_frames * REC;
-    float* o = out + (int64_t)blockIdx.x * 88;
-    auto raw = [&](int t, int field) { return rec[(int64_t)t * REC + field]; };
-    // smoothed F0 (non-zero smoothing) defines the voiced frames
-    for (int t = tid; t < nf; t += 256) {
-        const float c = raw(t, R_F0);
-        float acc = 0.f; int n = 0;
-        if (c != 0.f)
-            for (int q = (t > 0 ? t - 1 : 0); q <= (t + 1 < nf ? t + 1 : nf - 1); ++q) { const float x = raw(q, R_F0); if (x != 0.f) { acc += x; ++n; } }
-        f0s[t] = n ? acc / n : 0.f;
-    }
-    __syncthreads();
-    // load a contour: mode 0 plain 3-frame average, 1 non-zero average of the values masked to voiced frames, 2 semitone of f0s
-    auto load = [&](int field, int mode) {
-        for (int t = tid; t < nf; t += 256) {
-            float r = 0.f;
-            if (mode == 2) r = f0s[t] > 0.f ? 12.0f * log2f(f0s[t] / 27.5f) : 0.f;
-            else if (mode == 0) {
-                float acc = 0.f; int n = 0;
-                for (int q = (t > 0 ? t - 1 : 0); q <= (t + 1 < nf ? t + 1 : nf - 1); ++q) { acc += raw(q, field); ++n; }
-                r = acc / n;
-            } else {
-                const float c = f0s[t] > 0.f ? raw(t, field) : 0.f;
-                if (c != 0.f) {
-                    float acc = 0.f; int n = 0;
-                    for (int q = (t > 0 ? t - 1 : 0); q <= (t + 1 < nf ? t + 1 : nf - 1); ++q) {
-                        const float x = f0s[q] > 0.f ? raw(q, field) : 0.f;
-                        if (x != 0.f) { acc += x; ++n; }
-                    }
-                    r = acc / n;
-                }
-            }
-            v[t] = r;
-        }
-        __syncthreads();
-    };
-    // mean and normalised standard deviation over frames selected by sel: 0 all, 1 voiced, 2 unvoiced
-    auto mean_sn = [&](int sel, float& m, float& sn) {
-        float a0 = 0.f; int n0 = 0;
-        for (int t = tid; t < nf; t += 256) { const bool vo = f0s[t] > 0.f; if (sel == 0 || (sel == 1) == vo) { a0 += v[t]; ++n0; } }
-        const float sum = block_sum(a0, red);
-        const int n = (int)block_sum((float)n0, red);
-        m = n ? sum / n : 0.f;
-        float a1 = 0.f;
-        for (int t = tid; t < nf; t += 256) { const bool vo = f0s[t] > 0.f; if (sel == 0 || (sel == 1) == vo) { const float dd = v[t] - m; a1 += dd * dd; } }
-        const float var = block_sum(a1, red);
-        sn = (n && m != 0.f) ? sqrtf(var / n) / fabsf(m) : 0.f;
-    };
-    // the ten functionals of a contour over the selected frames -> o[base .. base + 9]
-    auto ten = [&](int sel, int base) {
-        float m, sn;
-        mean_sn(sel, m, sn);
-        // compact the selected values (order preserved) into s by thread 0 -- also the scan for slopes
-        if (tid == 0) {
-            int n = 0;
-            for (int t = 0; t < nf; ++t) { const bool vo = f0s[t] > 0.f; if (sel == 0 || (sel == 1) == vo) s[n++] = v[t]; }
-            cnt_s[0] = n;
-            // slopes of the rising / falling parts (cut at local extrema).  Their spread is accumulated as a running mean and
-            // a running sum of squared deviations (Welford): E[x^2] - E[x]^2 in float32 leaves the rounding of x^2 behind, and
-            // its square root is 2e-4 of the slope where the true deviation is zero (a single part, equal parts)
-            float rs = 0.f, rm = 0.f, rq = 0.f, fs = 0.f, fm = 0.f, fq = 0.f; int rn = 0, fn = 0;
-            if (n >= 2) {
-                int start = 0;
-                for (int t = 1; t < n; ++t) {
-                    const bool last = t == n - 1;
-                    const bool turn = !last && ((s[t] - s[t - 1]) * (s[t + 1] - s[t]) < 0.f);
-                    if (turn || last) {
-                        const float dv = s[t] - s[start];
-                        const float sl = dv / ((t - start) * (float)HOP / SR);
-                        if (dv > 0.f) { rs += sl; ++rn; const float d = sl - rm; rm += d / rn; rq += d * (sl - rm); }
-                        else if (dv < 0.f) { fs += sl; ++fn; const float d = sl - fm; fm += d / fn; fq += d * (sl - fm); }
-                        start = t;
-                    }
-                }
-            }
-            res[0] = rn ? rs / rn : 0.f; res[1] = rn ? sqrtf(fmaxf(rq / rn, 0.f)) : 0.f;
-            res[2] = fn ? fs / fn : 0.f; res[3] = fn ? sqrtf(fmaxf(fq / fn, 0.f)) : 0.f;
-        }
-        __syncthreads();
-        const int n = cnt_s[0];
-        int n2 = 1;
-        while (n2 < n) n2 <<= 1;
-        for (int i = n + tid; i < n2; i += 256) s[i] = INFINITY;
-        __syncthreads();
-        if (n2 > 1) bitonic_sort(s, n2);
-        if (tid == 0) {
-            auto pct = [&](float p) {
-                if (n == 0) return 0.f;
-                const float pos = p * (n - 1);
-                const int i = (int)floorf(pos); const float fr = pos - i;
-                return i + 1 >= n ? s[i] : s[i] * (1.f - fr) + s[i + 1] * fr;
-            };
-            const float p20 = pct(0.2f), p50 = pct(0.5f), p80 = pct(0.8f);
-            o[base] = m; o[base + 1] = sn; o[base + 2] = p20; o[base + 3] = p50; o[base + 4] = p80; o[base + 5] = p80 - p20;
-            o[base + 6] = res[0]; o[base + 7] = res[1]; o[base + 8] = res[2]; o[base + 9] = res[3];
-        }
-        __syncthreads();
-    };
-    float m, sn;
-    load(R_F0, 2); ten(1, 0);
-    load(R_LOUD, 0); ten(0, 10);
-    // loudness peaks (local maxima of the smoothed contour)
-    {
-        float pk = 0.f;
-        for (int t = 1 + tid; t + 1 < nf; t += 256) if (v[t] > v[t - 1] && v[t] >= v[t + 1]) pk += 1.f;
-        const float npk = block_sum(pk, red);
-        if (tid == 0) o[81] = npk / (nf * (float)HOP / SR);
-    }
-    load(R_FLUX, 0);
-    mean_sn(0, m, sn); if (tid == 0) { o[20] = m; o[21] = sn; }
-    mean_sn(1, m, sn); if (tid == 0) { o[66] = m; o[67] = sn; }
-    mean_sn(2, m, sn); if (tid == 0) o[80] = m;
-    for (int i = 0; i < 4; ++i) {
-        load(R_MFCC + i, 0);
-        mean_sn(0, m, sn); if (tid == 0) { o[22 + 2 * i] = m; o[23 + 2 * i] = sn; }
-        mean_sn(1, m, sn); if (tid == 0) { o[68 + 2 * i] = m; o[69 + 2 * i] = sn; }
-    }
-    {
-        const int fields[14] = {R_JIT, R_SHIM, R_HNR, R_H1H2, R_H1A3, R_F, R_BW, R_FAMP, R_F + 1, R_BW + 1, R_FAMP + 1, R_F + 2, R_BW + 2, R_FAMP + 2};
-        for (int i = 0; i < 14; ++i) {
-            load(fields[i], 1);
-            mean_sn(1, m, sn); if (tid == 0) { o[30 + 2 * i] = m; o[31 + 2 * i] = sn; }
-        }
-        const int spec[4] = {R_ALPHA, R_HAMM, R_SL0, R_SL1};
-        for (int i = 0; i < 4; ++i) {
-            load(spec[i], 0);
-            mean_sn(1, m, sn); if (tid == 0) { o[58 + 2 * i] = m; o[59 + 2 * i] = sn; }
-            mean_sn(2, m, sn); if (tid == 0) o[76 + i] = m;
-        }
-    }
-    // voiced / unvoiced segments and the equivalent sound level
-    {
-        float e2 = 0.f;
-        for (int t = tid; t < nf; t += 256) { const float r = raw(t, R_RMS); e2 += r * r; }
-        const float es = block_sum(e2, red);
-        if (tid == 0) {
-            float vs = 0.f, vq = 0.f, us = 0.f, uq = 0.f; int vn = 0, un = 0, run = 0; bool cur = false;
-            for (int t = 0; t <= nf; ++t) {
-                const bool vo = t < nf && f0s[t] > 0.f;
-                if (t == nf || (run && vo != cur)) {
-                    if (run) { const float len = (float)run; if (cur) { vs += len; vq += len * len; ++vn; } else { us += len; uq += len * len; ++un; } }
-                    run = 0;
-                }
-                if (t < nf) { cur = vo; ++run; }
-            }
-            const float dur = nf * (float)HOP / SR, fr = (float)HOP / SR;
-            o[82] = vn / dur;
-            o[83] = vn ? vs / vn * fr : 0.f;
-            o[84] = vn ? sqrtf(fmaxf(vq / vn - (vs / vn) * (vs / vn), 0.f)) * fr : 0.f;
-            o[85] = un ? us / un * fr : 0.f;
-            o[86] = un ? sqrtf(fmaxf(uq / un - (us / un) * (us / un), 0.f)) * fr : 0.f;
-            o[87] = 10.0f * log10f(fmaxf(es / nf, 1e-12f));
-        }
-    }
-}
-
 static EgmArgs egm_args(const EgmPlan* p, const float* audio, int64_t L, int nf, const float* scale, float* rec) {
     EgmArgs a{};
     a.audio = audio; a.L = L; a.nf = nf; a.scale = scale; a.tab = p->d; a.rec = rec; a.rec_frames = nf; a.slots = nullptr; a.ring_len = 0;
@@ -953,31 +670,21 @@ static EgmArgs egm_args(const EgmPlan* p, const float* audio, int64_t L, int nf,
 }
 
 // The five kernels over ragged windows that live in stream rings (km_emotion_stream.hip): fixed grids of max_nf frames x
-// n_slots windows, everything else from the slot table on the device.  long_windows: the object was made for windows beyond MAXF
-// frames (km_emotion_*_create_long): max_nf up to 6548, and the two per-window kernels are those of km_egemaps_long.hip for every slot.
+// n_slots windows, everything else from the slot table on the device.  long_windows: the object was made for windows beyond 2048
+// frames (km_emotion_*_create_long): max_nf up to 6548, and the two per-window kernels run at their long tier for every slot.
 int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
                            float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st, bool long_windows) {
     using namespace egm;
     if (!plan || !rings_dev || !slots_dev || !scale_dev || !rec_dev || !out_dev || n_slots < 1 || n_slots > 65535 || max_nf < 1 ||
-        max_nf > (long_windows ? egml::MAXF : MAXF) || ring_len < 1 || ring_len > (1 << 30))
+        max_nf > (long_windows ? LongTier::MAXF : ShortTier::MAXF) || ring_len < 1 || ring_len > (1 << 30))
         return fail(KM_ERR_INVALID_ARG, "egm_ragged_functionals: bad argument");
     EgmArgs a = egm_args(static_cast<EgmPlan*>(plan), rings_dev, 0, 0, scale_dev, rec_dev);
     a.rec_frames = max_nf; a.slots = slots_dev; a.ring_len = (int)ring_len;
     hipLaunchKernelGGL(egm_peak_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, rings_dev, (int64_t)0, slots_dev, (int)ring_len, scale_dev);
     hipLaunchKernelGGL(egm_frame_kernel<true>, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
-    if (long_windows) {
-        HIP_TRY(hipGetLastError());
-        if (const int rc = egm_long_track(rec_dev, 0, max_nf, slots_dev, n_slots, st)) return rc;
-    } else
-        hipLaunchKernelGGL(egm_viterbi_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, rec_dev, 0, max_nf, slots_dev);
+    if (const int rc = egm_track(rec_dev, 0, max_nf, slots_dev, n_slots, long_windows, st)) return rc;
     hipLaunchKernelGGL(egm_voiced_kernel<true>, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
-    if (long_windows) {
-        HIP_TRY(hipGetLastError());
-        return egm_long_functional(rec_dev, 0, max_nf, slots_dev, n_slots, out_dev, st);
-    }
-    hipLaunchKernelGGL(egm_functional_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, (const float*)rec_dev, 0, max_nf, slots_dev, out_dev);
-    HIP_TRY(hipGetLastError());
-    return KM_OK;
+    return egm_functional(rec_dev, 0, max_nf, slots_dev, n_slots, out_dev, long_windows, st);
 }
 
 }  // namespace km
@@ -1009,7 +716,7 @@ int64_t km_egemaps_workspace_floats(int64_t B, int64_t L) {
 }
 
 // km_egemaps_functionals and km_egemaps_functionals_long (`who` is the name the texts carry).  The latter takes windows of up to 2^20
-// samples: beyond MAXF frames the two per-window kernels of km_egemaps_long.hip run between the same per-frame kernels; up to MAXF
+// samples: beyond 2048 frames the two per-window kernels run at their long tier between the same per-frame kernels; up to 2048
 // frames it launches what the former launches
 static int egm_functionals(const char* who, bool long_windows, void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize,
                            float* work_dev, int64_t work_floats, float* out_dev, void* stream) {
@@ -1017,12 +724,13 @@ static int egm_functionals(const char* who, bool long_windows, void* plan, const
     if (!plan || !audio_dev || !work_dev || !out_dev || B <= 0 || L <= 0) return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
     const int64_t nf = km_egemaps_num_frames(L);
     if (nf < 1) return fail(KM_ERR_INVALID_ARG, "%s: the window is shorter than one 60 ms frame (%lld samples)", who, (long long)L);
-    if (long_windows && L > egml::MAX_WINDOW)
-        return fail(KM_ERR_UNSUPPORTED, "%s: a window of %lld samples, at most %lld (65.5 s)", who, (long long)L, (long long)egml::MAX_WINDOW);
-    if (!long_windows && nf > MAXF) return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (20.5 s)", who, (long long)nf, MAXF);
+    if (long_windows && L > MAX_WINDOW)
+        return fail(KM_ERR_UNSUPPORTED, "%s: a window of %lld samples, at most %lld (65.5 s)", who, (long long)L, (long long)MAX_WINDOW);
+    if (!long_windows && nf > ShortTier::MAXF)
+        return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (20.5 s)", who, (long long)nf, ShortTier::MAXF);
     if (work_floats < km_egemaps_workspace_floats(B, L)) return fail(KM_ERR_WORKSPACE, "%s: workspace too small", who);
     if (B > 65535) return fail(KM_ERR_UNSUPPORTED, "%s: at most 65535 windows per call", who);
-    const bool lng = nf > MAXF;
+    const bool long_tier = nf > ShortTier::MAXF;
     EgmPlan* p = static_cast<EgmPlan*>(plan);
     hipStream_t st = (hipStream_t)stream;
     float* scale = work_dev;                       // (B), padded to 4 B floats
@@ -1033,19 +741,9 @@ static int egm_functionals(const char* who, bool long_windows, void* plan, const
     }
     const EgmArgs a = egm_args(p, audio_dev, L, (int)nf, normalize ? scale : nullptr, rec);
     hipLaunchKernelGGL(egm_frame_kernel<false>, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
-    if (lng) {
-        HIP_TRY(hipGetLastError());
-        if (const int rc = egm_long_track(rec, (int)nf, (int)nf, nullptr, (int)B, st)) return rc;
-    } else
-        hipLaunchKernelGGL(egm_viterbi_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, rec, (int)nf, (int)nf, (const EgmSlot*)nullptr);
+    if (const int rc = egm_track(rec, (int)nf, (int)nf, nullptr, (int)B, long_tier, st)) return rc;
     hipLaunchKernelGGL(egm_voiced_kernel<false>, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
-    if (lng) {
-        HIP_TRY(hipGetLastError());
-        return egm_long_functional(rec, (int)nf, (int)nf, nullptr, (int)B, out_dev, st);
-    }
-    hipLaunchKernelGGL(egm_functional_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, (const float*)rec, (int)nf, (int)nf, (const EgmSlot*)nullptr, out_dev);
-    HIP_TRY(hipGetLastError());
-    return KM_OK;
+    return egm_functional(rec, (int)nf, (int)nf, nullptr, (int)B, out_dev, long_tier, st);
 }
 
 int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
@@ -1056,31 +754,6 @@ int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_
 int km_egemaps_functionals_long(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
                                 int64_t work_floats, float* out_dev, void* stream) {
     return egm_functionals("km_egemaps_functionals_long", true, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev, stream);
-}
-
-// The two kernels that are pure functions of the record array, on records the caller wrote (tests): the same kernels, the
-// same launch shape as in km_egemaps_functionals, no copy.
-static int check_records(const char* who, const void* rec, const void* out, int64_t B, int64_t nf) {
-    using namespace egm;
-    if (!rec || !out || B <= 0) return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
-    if (nf < 1) return fail(KM_ERR_INVALID_ARG, "%s: %lld frames per window, at least 1", who, (long long)nf);
-    if (nf > MAXF) return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (20.5 s)", who, (long long)nf, MAXF);
-    if (B > 65535) return fail(KM_ERR_UNSUPPORTED, "%s: at most 65535 windows per call", who);
-    return KM_OK;
-}
-
-int km_egemaps_track_from_records(float* rec_dev, int64_t B, int64_t nf, void* stream) {
-    if (const int rc = check_records("km_egemaps_track_from_records", rec_dev, rec_dev, B, nf)) return rc;
-    hipLaunchKernelGGL(egm_viterbi_kernel<false>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, rec_dev, (int)nf, (int)nf, (const EgmSlot*)nullptr);
-    HIP_TRY(hipGetLastError());
-    return KM_OK;
-}
-
-int km_egemaps_functionals_from_records(const float* rec_dev, int64_t B, int64_t nf, float* out_dev, void* stream) {
-    if (const int rc = check_records("km_egemaps_functionals_from_records", rec_dev, out_dev, B, nf)) return rc;
-    hipLaunchKernelGGL(egm_functional_kernel<false>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, rec_dev, (int)nf, (int)nf, (const EgmSlot*)nullptr, out_dev);
-    HIP_TRY(hipGetLastError());
-    return KM_OK;
 }
 
 // per-frame records of the most recent call on this workspace, for the tests: (B, nf, 36) floats

@@ -1,54 +1,32 @@
-// eGeMAPS windows beyond 2048 frames (20.5 s): the two per-window kernels of km_egemaps.hip -- pitch track and functionals -- for up
-// to 6548 frames, a window of 2^20 samples (65.5 s), the limit of the `basic` back end.  The long_context variant of the reference
-// (configs/model/dual_stream.yaml: 30 s context, 0.2 s updates) has 2995 frames per window.
+// The two eGeMAPS kernels that hold a whole window in LDS -- pitch track and functionals -- written once and compiled for two capacity
+// tiers (km_egemaps_window.h).  The other three kernels (peak, frame, voiced: km_egemaps.hip) work per frame and take any frame count.
 //
-// The other three kernels (peak, frame, voiced) work per frame and take any frame count; only these two hold a window in LDS.  Here
-// the window lives in DYNAMIC LDS (gfx950: 160 KB per workgroup):
-//   egm_long_viterbi_kernel     the recursion of egm_viterbi_kernel statement for statement.  The seven inputs of a step for 6548
-//                               frames would be 183 KB, so they are staged in chunks of 4096 frames (112 KB): all threads gather a
-//                               chunk, thread 0 walks it out of LDS, repeat; costs and the previous frame's log-frequencies stay in
-//                               thread 0's registers across chunks.  The back pointers of the WHOLE window stay in LDS, a byte per
-//                               frame, for the backtrack.  118 KB.
-//   egm_long_functional_kernel  egm_functional_kernel's arithmetic in its fixed orders (256-stride partial sums through block_sum,
-//                               serial compaction and slope scan, segment scan) on three contours of 6548 floats, the sort padded
-//                               to 8192.  83 KB.  One statement differs beyond 2048 frames: the position of a percentile is an exact
-//                               quotient there, not a float32 product (see pct).
-// At any frame count up to 2048 both give, on the same records, the bits of the kernels they restate (tests/test_gpu_egemaps_long.py);
-// a translation unit of their own keeps the register allocation of the five existing kernels where it is.
+//   ShortTier   2048 frames (20.5 s): every plain entry point and object.  59 KB (track) and 24 KB (functionals) of LDS.
+//   LongTier    6548 frames, a window of 2^20 samples (65.5 s), the limit of the `basic` back end: the `_long` entry points and objects.
+//               The long_context variant of the reference (configs/model/dual_stream.yaml: 30 s context, 0.2 s updates) has 2995
+//               frames per window.  118 KB and 83 KB (gfx950: 160 KB per workgroup).
+// The window lives in DYNAMIC LDS carved at constexpr offsets; only the long tier is beyond 64 KB and needs the function attribute.
+//
+//   egm_viterbi_kernel     per window: pitch track over the candidates (sequential dynamic programme, 4 states).  The seven inputs of
+//                          a step are staged in chunks of Tier::CHUNK frames -- for 6548 frames they would be 183 KB, a chunk of 4096
+//                          is 112 KB; the short tier's chunk is its whole window, a single pass.  The back pointers of the WHOLE
+//                          window stay in LDS, a byte per frame, for the backtrack.
+//   egm_functional_kernel  per window: 3-frame smoothing, means / normalised deviations / percentiles (bitonic sort in LDS) / slopes of
+//                          rising and falling parts over voiced, unvoiced or all frames, in fixed orders: 256-stride partial sums
+//                          through block_sum, serial compaction and slope scan, segment scan.  Three arrays of Tier::MAXF floats, the
+//                          sort buffer padded to Tier::SORT_MAX.
+// The order of the float32 operations is the contract (the tests pin bits).  Nothing in the arithmetic depends on the tier: at any frame
+// count up to 2048 the long tier gives, on the same records, the short tier's bits (tests/test_gpu_egemaps_long.py) -- chunking and the
+// sort's capacity are where they differ.
 #include <hip/hip_runtime.h>
 
 #include "km_context.h"
-#include "km_egemaps_long.h"
+#include "km_egemaps_dev.h"
+#include "km_egemaps_window.h"
 
 namespace km {
 
-namespace egml {
-constexpr int SR = 16000, HOP = 160;
-enum Rec { R_LOUD = 0, R_ALPHA, R_HAMM, R_SL0, R_SL1, R_FLUX, R_MFCC, R_RMS = 10, R_CF = 11, R_CS = 14, R_VOI = 17, R_F = 18, R_BW = 21,
-           R_F0 = 24, R_JIT, R_SHIM, R_HNR, R_H1H2, R_H1A3, R_FAMP = 30 };                 // egm::Rec (km_egemaps.hip)
-constexpr float VOICING_CUTOFF = 0.55f, RMS_FLOOR = 0.001f;
-constexpr int BP_BYTES = (MAXF + 15) / 16 * 16;
-constexpr int TRACK_LDS = 7 * CHUNK * (int)sizeof(float) + BP_BYTES;
-constexpr int FUNC_LDS = (2 * MAXF + SORT_MAX) * (int)sizeof(float);
-static_assert(TRACK_LDS <= 160 * 1024 && FUNC_LDS <= 160 * 1024, "gfx950: 160 KB of LDS per workgroup");
-static_assert(MAXF <= SORT_MAX && MAXF == 6548, "the sort buffer holds every frame of the longest window");
-}  // namespace egml
-
-// block_sum of km_egemaps.hip: an xor butterfly inside each wave, then the four wave results in wave order
-__device__ __forceinline__ float egml_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float egml_block_sum(float v, float* red) {
-    v = egml_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__device__ __forceinline__ void egml_bitonic_sort(float* s, int n2) {      // ascending, n2 a power of two, padding = +inf
+__device__ __forceinline__ void bitonic_sort(float* s, int n2) {      // ascending, n2 a power of two, padding = +inf
     for (int k = 2; k <= n2; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int i = threadIdx.x; i < n2; i += 256) {
@@ -63,10 +41,18 @@ __device__ __forceinline__ void egml_bitonic_sort(float* s, int n2) {      // as
         }
 }
 
-// pitch track over the candidates: states 0..2 = candidate, 3 = unvoiced (egm_viterbi_kernel)
-template <bool RAGGED>
-__global__ __launch_bounds__(256) void egm_long_viterbi_kernel(float* __restrict__ recs, int nf, int rec_frames, const EgmSlot* __restrict__ slots) {
-    using namespace egml;
+// pitch track over the candidates: states 0..2 = candidate, 3 = unvoiced.  One thread per window walks the frames; the back pointers
+// live in the bp LDS array (two bits per state), which the backtrack then overwrites with the chosen state.
+template <bool RAGGED, class Tier>
+__global__ __launch_bounds__(256) void egm_viterbi_kernel(float* __restrict__ recs, int nf, int rec_frames, const EgmSlot* __restrict__ slots) {
+    using namespace egm;
+    constexpr int MAXF = Tier::MAXF, CHUNK = Tier::CHUNK;
+    static_assert(track_lds<Tier>() <= 160 * 1024, "gfx950: 160 KB of LDS per workgroup");
+    // The recursion itself is sequential (thread 0), but its inputs are not: all threads first gather the seven numbers a step needs --
+    // voicing flag, log2 of the three candidate frequencies, their strengths -- into LDS, so that the walk reads LDS instead of paying
+    // a global round trip per frame (2.7 ms -> 0.2 ms per call), and write the chosen F0 back together at the end.  Beyond CHUNK frames:
+    // all threads gather a chunk, thread 0 walks it out of LDS, repeat; costs and the previous frame's log-frequencies stay in thread
+    // 0's registers across chunks.
     extern __shared__ float dyn[];
     float* in = dyn;                                                     // [7][CHUNK]: [0] voiced-ok, [1..3] log2 f (or -1), [4..6] strength
     unsigned char* bp = reinterpret_cast<unsigned char*>(dyn + 7 * CHUNK);   // [MAXF] back pointers (two bits per state), then the chosen state
@@ -142,11 +128,14 @@ __global__ __launch_bounds__(256) void egm_long_viterbi_kernel(float* __restrict
     }
 }
 
-// functionals: one workgroup per window (egm_functional_kernel)
-template <bool RAGGED>
-__global__ __launch_bounds__(256) void egm_long_functional_kernel(const float* __restrict__ recs, int nf, int rec_frames,
-                                                                  const EgmSlot* __restrict__ slots, float* __restrict__ out) {
-    using namespace egml;
+// functionals: one workgroup per window
+template <bool RAGGED, class Tier>
+__global__ __launch_bounds__(256) void egm_functional_kernel(const float* __restrict__ recs, int nf, int rec_frames, const EgmSlot* __restrict__ slots,
+                                                             float* __restrict__ out) {
+    using namespace egm;
+    constexpr int MAXF = Tier::MAXF, SORT_MAX = Tier::SORT_MAX;
+    static_assert(func_lds<Tier>() <= 160 * 1024, "gfx950: 160 KB of LDS per workgroup");
+    static_assert(MAXF <= SORT_MAX && (SORT_MAX & (SORT_MAX - 1)) == 0, "the sort buffer holds every frame of the longest window");
     extern __shared__ float dyn[];
     float* v = dyn;                       // [MAXF] contour (smoothed)
     float* f0s = dyn + MAXF;              // [MAXF] smoothed F0
@@ -200,12 +189,12 @@ __global__ __launch_bounds__(256) void egm_long_functional_kernel(const float* _
     auto mean_sn = [&](int sel, float& m, float& sn) {
         float a0 = 0.f; int n0 = 0;
         for (int t = tid; t < nf; t += 256) { const bool vo = f0s[t] > 0.f; if (sel == 0 || (sel == 1) == vo) { a0 += v[t]; ++n0; } }
-        const float sum = egml_block_sum(a0, red);
-        const int n = (int)egml_block_sum((float)n0, red);
+        const float sum = block_sum(a0, red);
+        const int n = (int)block_sum((float)n0, red);
         m = n ? sum / n : 0.f;
         float a1 = 0.f;
         for (int t = tid; t < nf; t += 256) { const bool vo = f0s[t] > 0.f; if (sel == 0 || (sel == 1) == vo) { const float dd = v[t] - m; a1 += dd * dd; } }
-        const float var = egml_block_sum(a1, red);
+        const float var = block_sum(a1, red);
         sn = (n && m != 0.f) ? sqrtf(var / n) / fabsf(m) : 0.f;
     };
     // the ten functionals of a contour over the selected frames -> o[base .. base + 9]
@@ -217,8 +206,9 @@ __global__ __launch_bounds__(256) void egm_long_functional_kernel(const float* _
             int n = 0;
             for (int t = 0; t < nf; ++t) { const bool vo = f0s[t] > 0.f; if (sel == 0 || (sel == 1) == vo) s[n++] = v[t]; }
             cnt_s[0] = n;
-            // slopes of the rising / falling parts (cut at local extrema), their spread as a running mean and a running sum of
-            // squared deviations (Welford), as egm_functional_kernel says why
+            // slopes of the rising / falling parts (cut at local extrema).  Their spread is accumulated as a running mean and
+            // a running sum of squared deviations (Welford): E[x^2] - E[x]^2 in float32 leaves the rounding of x^2 behind, and
+            // its square root is 2e-4 of the slope where the true deviation is zero (a single part, equal parts)
             float rs = 0.f, rm = 0.f, rq = 0.f, fs = 0.f, fm = 0.f, fq = 0.f; int rn = 0, fn = 0;
             if (n >= 2) {
                 int start = 0;
@@ -243,13 +233,14 @@ __global__ __launch_bounds__(256) void egm_long_functional_kernel(const float* _
         while (n2 < n) n2 <<= 1;
         for (int i = n + tid; i < n2; i += 256) s[i] = INFINITY;
         __syncthreads();
-        if (n2 > 1) egml_bitonic_sort(s, n2);
+        if (n2 > 1) bitonic_sort(s, n2);
         if (tid == 0) {
-            // percentile p = pn / pd at position p (n - 1).  Up to 2048 frames the position is egm_functional_kernel's float32 product
-            // (equal bits).  Beyond, float32 numbers near the position are 2.4e-4 to 4.9e-4 apart, and that times the gap between two
-            // sorted neighbours -- 7 loudness units between the clusters of a speech-like window of 30 s -- was 4.7 times the tolerance
-            // of the class: there the position is the exact quotient, integer part and remainder
-            auto pct = [&](float p) {                               // egm_functional_kernel's
+            // percentile p = pn / pd at position p (n - 1).  Up to 2048 frames the position is the float32 product.  Beyond, float32
+            // numbers near the position are 2.4e-4 to 4.9e-4 apart, and that times the gap between two sorted neighbours -- 7 loudness
+            // units between the clusters of a speech-like window of 30 s -- was 4.7 times the tolerance of the class: there the
+            // position is the exact quotient, integer part and remainder.  A condition on the window, not on the tier: the long tier
+            // at 2048 frames or fewer keeps giving the short tier's bits
+            auto pct = [&](float p) {
                 if (n == 0) return 0.f;
                 const float pos = p * (n - 1);
                 const int i = (int)floorf(pos); const float fr = pos - i;
@@ -262,7 +253,7 @@ __global__ __launch_bounds__(256) void egm_long_functional_kernel(const float* _
                 return i + 1 >= n ? s[i] : s[i] * (1.f - fr) + s[i + 1] * fr;
             };
             float p20, p50, p80;
-            if (nf > MAXF_SHORT) { p20 = pct_exact(1, 5); p50 = pct_exact(1, 2); p80 = pct_exact(4, 5); }
+            if (nf > ShortTier::MAXF) { p20 = pct_exact(1, 5); p50 = pct_exact(1, 2); p80 = pct_exact(4, 5); }
             else { p20 = pct(0.2f); p50 = pct(0.5f); p80 = pct(0.8f); }
             o[base] = m; o[base + 1] = sn; o[base + 2] = p20; o[base + 3] = p50; o[base + 4] = p80; o[base + 5] = p80 - p20;
             o[base + 6] = res[0]; o[base + 7] = res[1]; o[base + 8] = res[2]; o[base + 9] = res[3];
@@ -276,7 +267,7 @@ __global__ __launch_bounds__(256) void egm_long_functional_kernel(const float* _
     {
         float pk = 0.f;
         for (int t = 1 + tid; t + 1 < nf; t += 256) if (v[t] > v[t - 1] && v[t] >= v[t + 1]) pk += 1.f;
-        const float npk = egml_block_sum(pk, red);
+        const float npk = block_sum(pk, red);
         if (tid == 0) o[81] = npk / (nf * (float)HOP / SR);
     }
     load(R_FLUX, 0);
@@ -305,7 +296,7 @@ __global__ __launch_bounds__(256) void egm_long_functional_kernel(const float* _
     {
         float e2 = 0.f;
         for (int t = tid; t < nf; t += 256) { const float r = raw(t, R_RMS); e2 += r * r; }
-        const float es = egml_block_sum(e2, red);
+        const float es = block_sum(e2, red);
         if (tid == 0) {
             float vs = 0.f, vq = 0.f, us = 0.f, uq = 0.f; int vn = 0, un = 0, run = 0; bool cur = false;
             for (int t = 0; t <= nf; ++t) {
@@ -327,41 +318,54 @@ __global__ __launch_bounds__(256) void egm_long_functional_kernel(const float* _
     }
 }
 
-int egm_long_prepare() {
-    using namespace egml;
+int egm_window_prepare() {
+    using namespace egm;
     static PerDeviceOnce once;
     int device = -1;
     HIP_TRY(hipGetDevice(&device));
     if (!once.first(device)) return KM_OK;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_long_viterbi_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, TRACK_LDS));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_long_viterbi_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TRACK_LDS));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_long_functional_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FUNC_LDS));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_long_functional_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, FUNC_LDS));
+    constexpr hipFuncAttribute attr = hipFuncAttributeMaxDynamicSharedMemorySize;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_viterbi_kernel<false, LongTier>), attr, track_lds<LongTier>()));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_viterbi_kernel<true, LongTier>), attr, track_lds<LongTier>()));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_functional_kernel<false, LongTier>), attr, func_lds<LongTier>()));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_functional_kernel<true, LongTier>), attr, func_lds<LongTier>()));
     return KM_OK;
 }
 
-static int egm_long_check(const char* who, const void* rec, const void* out, int nf, int rec_frames, const EgmSlot* slots, int n) {
-    using namespace egml;
-    if (!rec || !out || n < 1 || n > 65535 || rec_frames < 1 || rec_frames > MAXF || (!slots && (nf < 1 || nf > rec_frames)))
+static int window_check(const char* who, const void* rec, const void* out, int nf, int rec_frames, const EgmSlot* slots, int n, bool long_tier) {
+    using namespace egm;
+    if (!rec || !out || n < 1 || n > 65535 || rec_frames < 1 || rec_frames > (long_tier ? LongTier::MAXF : ShortTier::MAXF) ||
+        (!slots && (nf < 1 || nf > rec_frames)))
         return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
-    return egm_long_prepare();
+    return long_tier ? egm_window_prepare() : KM_OK;
 }
 
-int egm_long_track(float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, hipStream_t st) {
-    if (const int rc = egm_long_check("egm_long_track", rec_dev, rec_dev, nf, rec_frames, slots_dev, n)) return rc;
-    if (slots_dev) hipLaunchKernelGGL(egm_long_viterbi_kernel<true>, dim3((unsigned)n), dim3(256), egml::TRACK_LDS, st, rec_dev, 0, rec_frames, slots_dev);
-    else hipLaunchKernelGGL(egm_long_viterbi_kernel<false>, dim3((unsigned)n), dim3(256), egml::TRACK_LDS, st, rec_dev, nf, rec_frames, (const EgmSlot*)nullptr);
+template <class Tier>
+static void launch_track(float* rec, int nf, int rec_frames, const EgmSlot* slots, int n, hipStream_t st) {
+    constexpr int lds = egm::track_lds<Tier>();
+    if (slots) hipLaunchKernelGGL((egm_viterbi_kernel<true, Tier>), dim3((unsigned)n), dim3(256), lds, st, rec, 0, rec_frames, slots);
+    else hipLaunchKernelGGL((egm_viterbi_kernel<false, Tier>), dim3((unsigned)n), dim3(256), lds, st, rec, nf, rec_frames, (const EgmSlot*)nullptr);
+}
+
+template <class Tier>
+static void launch_functional(const float* rec, int nf, int rec_frames, const EgmSlot* slots, int n, float* out, hipStream_t st) {
+    constexpr int lds = egm::func_lds<Tier>();
+    if (slots) hipLaunchKernelGGL((egm_functional_kernel<true, Tier>), dim3((unsigned)n), dim3(256), lds, st, rec, 0, rec_frames, slots, out);
+    else hipLaunchKernelGGL((egm_functional_kernel<false, Tier>), dim3((unsigned)n), dim3(256), lds, st, rec, nf, rec_frames, (const EgmSlot*)nullptr, out);
+}
+
+int egm_track(float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, bool long_tier, hipStream_t st) {
+    if (const int rc = window_check("egm_track", rec_dev, rec_dev, nf, rec_frames, slots_dev, n, long_tier)) return rc;
+    if (long_tier) launch_track<egm::LongTier>(rec_dev, nf, rec_frames, slots_dev, n, st);
+    else launch_track<egm::ShortTier>(rec_dev, nf, rec_frames, slots_dev, n, st);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
 
-int egm_long_functional(const float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, float* out_dev, hipStream_t st) {
-    if (const int rc = egm_long_check("egm_long_functional", rec_dev, out_dev, nf, rec_frames, slots_dev, n)) return rc;
-    if (slots_dev)
-        hipLaunchKernelGGL(egm_long_functional_kernel<true>, dim3((unsigned)n), dim3(256), egml::FUNC_LDS, st, rec_dev, 0, rec_frames, slots_dev, out_dev);
-    else
-        hipLaunchKernelGGL(egm_long_functional_kernel<false>, dim3((unsigned)n), dim3(256), egml::FUNC_LDS, st, rec_dev, nf, rec_frames,
-                           (const EgmSlot*)nullptr, out_dev);
+int egm_functional(const float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, float* out_dev, bool long_tier, hipStream_t st) {
+    if (const int rc = window_check("egm_functional", rec_dev, out_dev, nf, rec_frames, slots_dev, n, long_tier)) return rc;
+    if (long_tier) launch_functional<egm::LongTier>(rec_dev, nf, rec_frames, slots_dev, n, out_dev, st);
+    else launch_functional<egm::ShortTier>(rec_dev, nf, rec_frames, slots_dev, n, out_dev, st);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
@@ -372,24 +376,35 @@ using namespace km;
 
 extern "C" {
 
-// The test hooks of km_egemaps_track_from_records / km_egemaps_functionals_from_records: ALWAYS the kernels of this file, at 1 to 6548
-// frames, so that their bits can be held against the existing kernels' up to 2048.
-static int check_records_long(const char* who, const void* rec, const void* out, int64_t B, int64_t nf) {
+// The two kernels that are pure functions of the record array, on records the caller wrote (tests): the same kernels, the same launch
+// shape as in km_egemaps_functionals, no copy.  The plain hooks run the short tier; the `_long` hooks ALWAYS the long tier, at 1 to
+// 6548 frames, so that its bits can be held against the short tier's up to 2048.
+static int check_records(const char* who, const void* rec, const void* out, int64_t B, int64_t nf, int cap, const char* seconds_text) {
     if (!rec || !out || B <= 0) return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
     if (nf < 1) return fail(KM_ERR_INVALID_ARG, "%s: %lld frames per window, at least 1", who, (long long)nf);
-    if (nf > egml::MAXF) return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (65.5 s)", who, (long long)nf, egml::MAXF);
+    if (nf > cap) return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (%s)", who, (long long)nf, cap, seconds_text);
     if (B > 65535) return fail(KM_ERR_UNSUPPORTED, "%s: at most 65535 windows per call", who);
     return KM_OK;
 }
 
+int km_egemaps_track_from_records(float* rec_dev, int64_t B, int64_t nf, void* stream) {
+    if (const int rc = check_records("km_egemaps_track_from_records", rec_dev, rec_dev, B, nf, egm::ShortTier::MAXF, "20.5 s")) return rc;
+    return egm_track(rec_dev, (int)nf, (int)nf, nullptr, (int)B, false, (hipStream_t)stream);
+}
+
+int km_egemaps_functionals_from_records(const float* rec_dev, int64_t B, int64_t nf, float* out_dev, void* stream) {
+    if (const int rc = check_records("km_egemaps_functionals_from_records", rec_dev, out_dev, B, nf, egm::ShortTier::MAXF, "20.5 s")) return rc;
+    return egm_functional(rec_dev, (int)nf, (int)nf, nullptr, (int)B, out_dev, false, (hipStream_t)stream);
+}
+
 int km_egemaps_track_from_records_long(float* rec_dev, int64_t B, int64_t nf, void* stream) {
-    if (const int rc = check_records_long("km_egemaps_track_from_records_long", rec_dev, rec_dev, B, nf)) return rc;
-    return egm_long_track(rec_dev, (int)nf, (int)nf, nullptr, (int)B, (hipStream_t)stream);
+    if (const int rc = check_records("km_egemaps_track_from_records_long", rec_dev, rec_dev, B, nf, egm::LongTier::MAXF, "65.5 s")) return rc;
+    return egm_track(rec_dev, (int)nf, (int)nf, nullptr, (int)B, true, (hipStream_t)stream);
 }
 
 int km_egemaps_functionals_from_records_long(const float* rec_dev, int64_t B, int64_t nf, float* out_dev, void* stream) {
-    if (const int rc = check_records_long("km_egemaps_functionals_from_records_long", rec_dev, out_dev, B, nf)) return rc;
-    return egm_long_functional(rec_dev, (int)nf, (int)nf, nullptr, (int)B, out_dev, (hipStream_t)stream);
+    if (const int rc = check_records("km_egemaps_functionals_from_records_long", rec_dev, out_dev, B, nf, egm::LongTier::MAXF, "65.5 s")) return rc;
+    return egm_functional(rec_dev, (int)nf, (int)nf, nullptr, (int)B, out_dev, true, (hipStream_t)stream);
 }
 
 }  // extern "C"

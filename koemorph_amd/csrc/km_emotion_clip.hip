@@ -23,7 +23,7 @@
 #include <memory>
 
 #include "km_context.h"
-#include "km_egemaps_long.h"
+#include "km_egemaps_window.h"
 #include "km_egemaps_ragged.h"
 #include "km_emotion_common.h"
 #include "km_prosody_ragged.h"
@@ -52,7 +52,7 @@ struct EmotionClip : EmoTiming {
     float* bias = nullptr;     // (256)
     bool has_compression = false;
     bool basic = false;        // the `basic` back end: rows of 9, rec is (max_slots, max_nf, 4), no scale / fout / f0 / w / bias
-    bool long_windows = false; // km_emotion_clip_create_long with more than 2048 frames per window: the per-window kernels of km_egemaps_long.hip
+    bool long_windows = false; // km_emotion_clip_create_long with more than 2048 frames per window: the long tier of the per-window kernels (km_egemaps_window.hip)
     void* prosody = nullptr;
     ~EmotionClip() { (void)km_egemaps_plan_destroy(plan); (void)km_prosody_plan_destroy(prosody); }
 };
@@ -165,7 +165,7 @@ static int ec_create(const char* fn, void** ec_out, double context_window_s, dou
     e->max_slots = max_slots; e->basic = basic;
     e->long_windows = long_windows && e->max_nf > MAXF;                         // up to 2048 frames it is the plain object
     if (e->long_windows)
-        if (const int rc = egm_long_prepare()) return rc;
+        if (const int rc = egm_window_prepare()) return rc;
     if (const int rc = basic ? km_prosody_plan_create(&e->prosody) : km_egemaps_plan_create(&e->plan)) return rc;
     const int64_t ms = max_slots, nf = e->max_nf;
     auto layout = [&](char* base) {

@@ -23,7 +23,7 @@
 #include <memory>
 
 #include "km_context.h"
-#include "km_egemaps_long.h"
+#include "km_egemaps_window.h"
 #include "km_egemaps_ragged.h"
 #include "km_emotion_common.h"
 #include "km_prosody_ragged.h"
@@ -64,7 +64,7 @@ struct EmotionStream : EmoTiming {
     float* bias = nullptr;     // (256)
     bool has_compression = false;
     bool basic = false;        // the `basic` back end: features holds 9 values per stream (row stride 88), no slots, no emotion layer
-    bool long_windows = false; // km_emotion_stream_create_long with more than 2048 frames per window: the per-window kernels of km_egemaps_long.hip
+    bool long_windows = false; // km_emotion_stream_create_long with more than 2048 frames per window: the long tier of the per-window kernels (km_egemaps_window.hip)
     void* prosody = nullptr;
     ~EmotionStream() { (void)km_egemaps_plan_destroy(plan); (void)km_prosody_plan_destroy(prosody); }
 };
@@ -216,7 +216,7 @@ static int es_create(const char* fn, void** es_out, int64_t n_streams, double co
     e->n = n_streams; e->max_updates = max_updates; e->basic = basic;
     e->long_windows = long_windows && e->max_nf > MAXF;                         // up to 2048 frames it is the plain object
     if (e->long_windows)
-        if (const int rc = egm_long_prepare()) return rc;
+        if (const int rc = egm_window_prepare()) return rc;
     if (const int rc = basic ? km_prosody_plan_create(&e->prosody) : km_egemaps_plan_create(&e->plan)) return rc;
     const int64_t n = n_streams, mu = max_updates, R = e->ring_len, nf = e->max_nf;
     auto layout = [&](char* base) {

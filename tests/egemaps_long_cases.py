@@ -1,15 +1,15 @@
 """Shared by tests/test_egemaps_long_host.py and tests/test_gpu_egemaps_long.py: the frame counts, tolerances and track bound of
-the eGeMAPS kernels for windows beyond 2048 frames (koemorph_amd/csrc/km_egemaps_long.hip).  The records, references and error
-classes are those of tests/egemaps_cases.py, unchanged; only the frame counts are new."""
+the long tier of the per-window eGeMAPS kernels, windows beyond 2048 frames (koemorph_amd/csrc/km_egemaps_window.hip).  The records,
+references and error classes are those of tests/egemaps_cases.py, unchanged; only the frame counts are new."""
 import numpy as np
 
 import egemaps_cases as ec
 
-MAXF_SHORT, MAXF_LONG = 2048, 6548                 # egm::MAXF; (2**20 - 960) // 160 + 1
-TRACK_CHUNK = 4096                                 # egml::CHUNK: frames of pitch-track inputs staged in LDS at a time (the host test reads the header)
+MAXF_SHORT, MAXF_LONG = 2048, 6548                 # ShortTier::MAXF; LongTier::MAXF = (2**20 - 960) // 160 + 1
+TRACK_CHUNK = 4096                                 # LongTier::CHUNK: frames of pitch-track inputs staged in LDS at a time (the host test reads the header)
 SORT_DOUBLES = 4096                                # the functionals' sort is padded to 4096 up to here and to 8192 beyond
 
-# equal bits with the existing kernels: one frame, fewer than a wave, one past the 256-thread stride, their limit
+# equal bits with the short tier: one frame, fewer than a wave, one past the 256-thread stride, their limit
 EQUAL_NF = (1, 3, 257, 2048)
 # against float64: one past the old limit; one below, at and one above the sort's doubling and every chunk boundary of the track
 # kernel's staging (both 4096: the only boundary below the cap); the cap

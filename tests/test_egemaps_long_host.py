@@ -103,9 +103,10 @@ def test_header_signatures_and_sources_name_the_new_entry_points():
     for name in NEW_EXPORTS:
         assert re.search(r"\bint %s\s*\(" % name, text) and name in _lib.SIGNATURES and hasattr(lib, name), name
     # the constants the frame counts of these tests are chosen around
-    hdr = open(os.path.join(ROOT, "koemorph_amd", "csrc", "km_egemaps_long.h")).read()
-    assert re.search(r"\bCHUNK = %d;" % lc.TRACK_CHUNK, hdr) and re.search(r"\bSORT_MAX = 8192;", hdr)
-    assert "km_egemaps_long.hip" in open(os.path.join(ROOT, "koemorph_amd", "build.py")).read()
+    hdr = open(os.path.join(ROOT, "koemorph_amd", "csrc", "km_egemaps_window.h")).read()
+    long_tier = re.search(r"struct LongTier \{(.*?)\};", hdr, re.S).group(1)
+    assert re.search(r"\bCHUNK = %d;" % lc.TRACK_CHUNK, long_tier) and re.search(r"\bSORT_MAX = 8192;", long_tier)
+    assert '"km_egemaps_window.hip"' in open(os.path.join(ROOT, "koemorph_amd", "build.py")).read()
 
 
 @pytest.mark.parametrize("nf", lc.LONG_NF)

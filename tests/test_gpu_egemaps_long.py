@@ -1,5 +1,5 @@
-"""The eGeMAPS kernels for windows beyond 2048 frames (koemorph_amd/csrc/km_egemaps_long.hip: egm_long_viterbi_kernel,
-egm_long_functional_kernel) on the crafted records of tests/egemaps_cases.py, no audio in the way:
+"""The long tier of the per-window eGeMAPS kernels, for windows beyond 2048 frames (koemorph_amd/csrc/km_egemaps_window.hip:
+egm_viterbi_kernel and egm_functional_kernel at LongTier) on the crafted records of tests/egemaps_cases.py, no audio in the way:
 
 1. EQUAL BITS.  At 1, 3, 257 and 2048 frames the ``_long`` hooks give, on the same records, the bits of the existing hooks: all 88
    functionals and the whole record array behind the pitch track.
