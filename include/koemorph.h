@@ -881,6 +881,43 @@ int km_emotion_clip_width(void* ec);
  * the per-window kernels of every slot, short windows included, are the long form. */
 int km_emotion_stream_create_long(void** es, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates);
 int km_emotion_clip_create_long(void** ec, double context_window_s, double update_interval_s, int64_t max_slots);
+/* ---- the GeMAPS feature set: the emotion input of the reference's `fast` variant (configs/model/dual_stream.yaml: 10 s / 0.5 s,
+ * feature_set "GeMAPS") ----
+ * The 62 functionals of GeMAPS v01b are the 88 of eGeMAPSv02 without the spectral flux (5 values), MFCC 1-4 (16), the bandwidths of F2
+ * and F3 (4) and the equivalent sound level (1): columns 20-29, 48, 49, 54, 55, 66-75, 80 and 87 removed, the other 62 in the order
+ * the 88 have.  PARITY with openSMILE's own GeMAPSv01b -- values, and that its column order is this one -- is UNPINNED, as for the
+ * whole eGeMAPS back end.  What is pinned: value j of a GeMAPS call IS, bit for bit, the value of the j-th kept column of the eGeMAPS
+ * call on the same samples.  The frame kernel's GeMAPS form leaves out the previous frame's transform, the flux sum and the four DCT
+ * sums and writes 0 to fields 5-9 of a frame record (36 floats, same layout); the functionals kernel's skips the seven contours and
+ * the RMS sum nobody reads.  An unknown feature set is KM_ERR_INVALID_ARG everywhere.
+ *   km_feature_set_width                     88 / 62, -1 for an unknown set
+ *   km_egemaps_functionals_set               km_egemaps_functionals (long_windows 0) or km_egemaps_functionals_long (non-zero) with
+ *                                            out_dev (B, width): their workspace, their refusals under this name; with set 0 their
+ *                                            launches
+ *   km_egemaps_functionals_from_records_set  the test hooks km_egemaps_functionals_from_records / _long (long_windows non-zero
+ *                                            ALWAYS runs the long form) with out_dev (B, width)
+ *   km_emotion_stream_create_set             km_emotion_stream_create / _create_long for a feature set; with set 0 exactly their object
+ *   km_emotion_clip_create_set               km_emotion_clip_create / _create_long likewise
+ *   km_emotion_stream_feature_width          88 / 62 / 9: the row width of `features` (host only; 0 for a NULL object)
+ *   km_emotion_clip_feature_width
+ * On a GeMAPS object set_compression takes w (256, 186) -- three windows of 62, concatenated as the 88 are; the reference hard-codes
+ * Linear(264, 256) and so never compresses GeMAPS features, a deliberate deviation -- `features` is (n, 62), the slots (n, 2, 62),
+ * build / build_batch write features_out (K, 62).  The sum over k is the sequential chain of the 88-value objects with the 78 terms of
+ * the removed columns left out: an eGeMAPS object whose layer holds those weights in the kept columns and 0 elsewhere gives equal
+ * emotion bits.  Every other call (rows, push, update, reset_streams, capture and replay) is unchanged. */
+#define KM_FEATURE_SET_EGEMAPS 0
+#define KM_FEATURE_SET_GEMAPS 1
+int km_feature_set_width(int32_t feature_set);
+int km_egemaps_functionals_set(void* plan, int32_t feature_set, int32_t long_windows, const float* audio_dev, int64_t B, int64_t L,
+                               int32_t normalize, float* work_dev, int64_t work_floats, float* out_dev, void* stream);
+int km_egemaps_functionals_from_records_set(int32_t feature_set, int32_t long_windows, const float* rec_dev, int64_t B, int64_t nf,
+                                            float* out_dev, void* stream);
+int km_emotion_stream_create_set(void** es, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates,
+                                 int32_t feature_set, int32_t long_windows);
+int km_emotion_clip_create_set(void** ec, double context_window_s, double update_interval_s, int64_t max_slots, int32_t feature_set,
+                               int32_t long_windows);
+int km_emotion_stream_feature_width(void* es);
+int km_emotion_clip_feature_width(void* ec);
 
 /* ---- evaluation metrics: a streaming accumulator in device memory ------------------------------------------------
  * Replaces BlendshapeMetrics (src/model/losses.py:421-521) and compute_lip_sync_metrics (:524-583).  The reference

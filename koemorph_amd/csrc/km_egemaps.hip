@@ -18,6 +18,8 @@
 //                          waveform), harmonic differences and formant amplitudes
 //   egm_functional_kernel  per window: 3-frame smoothing, means / normalised deviations / percentiles (bitonic sort in
 //                          LDS) / slopes of rising and falling parts over voiced, unvoiced or all frames; km_egemaps_window.hip
+// The frame and functional kernels also take the feature set (km_egemaps_dev.h): eGeMAPS, or the 62 functionals of GeMAPS, which leave
+// out the work only the other 26 need.
 // Each kernel has two instantiations: over a dense (B, L) array of windows (km_egemaps_*), and over ragged windows that are read
 // in place from stream rings through a slot table written on the device (egm_ragged_functionals, for km_emotion_stream.hip).
 #include <hip/hip_runtime.h>
@@ -287,9 +289,13 @@ __device__ __forceinline__ void frame_spectra(const EgmArgs& a, const Src& xw, f
     __syncthreads();
 }
 
-template <bool RAGGED>
+// SET (km_egemaps_window.h): the GeMAPS instantiations leave out what only the spectral flux and the MFCCs need -- the previous
+// frame's transform and Mp, the flux sum, the four DCT sums -- and write 0 to those five fields.  Every other statement is the same,
+// in the same order: every other field of a record has the eGeMAPS instantiation's bits.
+template <bool RAGGED, int SET>
 __global__ __launch_bounds__(256, 6) void egm_frame_kernel(EgmArgs a) {
     using namespace egm;
+    constexpr bool FULL = SET == SET_EGEMAPS;
     __shared__ float2 zb[NFFT];
     __shared__ float2 tw[NFFT / 2];
     __shared__ float M60[NB + 3], M20[NB + 3], Mp[NB + 3], red[256], E[32], slog[512], shs[256], misc[64], sw[N60], rl[128];
@@ -301,7 +307,7 @@ __global__ __launch_bounds__(256, 6) void egm_frame_kernel(EgmArgs a) {
     for (int k = tid; k < NFFT / 2; k += 256) tw[k] = reinterpret_cast<const float2*>(a.tab + a.o_tw)[k];
     __syncthreads();
     // previous frame's 20 ms spectrum (for the spectral flux): the imaginary slot of a transform whose real slot is unused
-    if (t > 0) {
+    if (FULL && t > 0) {
         const float* ham = a.tab + a.o_ham;
         for (int n = tid; n < NFFT; n += 256) zb[bitrev10(n)] = make_float2(n < N20 ? ham[n] * xw[HOP * (t - 1) + OFF20 + n] * sc : 0.f, 0.f);
         __syncthreads();
@@ -330,9 +336,11 @@ __global__ __launch_bounds__(256, 6) void egm_frame_kernel(EgmArgs a) {
         const float ej = on ? E[tid] : 0.f;
         const float loud = wave_sum(on ? powf(ej * a.tab[a.o_eql + tid], 0.33f) : 0.f);
         const float le = on ? logf(fmaxf(ej, 1e-8f)) : 0.f;
-        float c[4];
+        float c[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (FULL) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) c[i] = wave_sum(on ? le * a.tab[a.o_dct + i * NBANDS + tid] : 0.f);
+            for (int i = 0; i < 4; ++i) c[i] = wave_sum(on ? le * a.tab[a.o_dct + i * NBANDS + tid] : 0.f);
+        }
         if (tid == 0) {
             rec[R_LOUD] = loud;
 #pragma unroll
@@ -352,15 +360,15 @@ __global__ __launch_bounds__(256, 6) void egm_frame_kernel(EgmArgs a) {
             const float ldb = 10.0f * log10f(pw + 1e-12f);
             if (k >= a.b_sl0[0] && k < a.b_sl0[1]) s0 = fmaf(ldb, a.tab[a.o_sl0 + k - a.b_sl0[0]], s0);
             if (k >= a.b_sl1[0] && k < a.b_sl1[1]) s1 = fmaf(ldb, a.tab[a.o_sl1 + k - a.b_sl1[0]], s1);
-            if (t > 0) { const float dm = M20[k] - Mp[k]; fl += dm * dm; }
+            if (FULL && t > 0) { const float dm = M20[k] - Mp[k]; fl += dm * dm; }
         }
         const float LO = block_sum(lo, red), HI = block_sum(hi, red), PL = block_max(pl, red), PH = block_max(ph, red);
-        const float S0 = block_sum(s0, red), S1 = block_sum(s1, red), FL = block_sum(fl, red);
+        const float S0 = block_sum(s0, red), S1 = block_sum(s1, red), FL = FULL ? block_sum(fl, red) : 0.f;
         if (tid == 0) {
             rec[R_ALPHA] = 10.0f * log10f((LO + 1e-12f) / (HI + 1e-12f));
             rec[R_HAMM] = 10.0f * log10f((PL + 1e-12f) / (PH + 1e-12f));
             rec[R_SL0] = S0; rec[R_SL1] = S1;
-            rec[R_FLUX] = t > 0 ? sqrtf(FL / NB) : 0.f;
+            rec[R_FLUX] = FULL && t > 0 ? sqrtf(FL / NB) : 0.f;
         }
     }
     // ---- sub-harmonic summation on the log2-frequency axis ----
@@ -673,18 +681,20 @@ static EgmArgs egm_args(const EgmPlan* p, const float* audio, int64_t L, int nf,
 // n_slots windows, everything else from the slot table on the device.  long_windows: the object was made for windows beyond 2048
 // frames (km_emotion_*_create_long): max_nf up to 6548, and the two per-window kernels run at their long tier for every slot.
 int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
-                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st, bool long_windows) {
+                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st, bool long_windows, int feature_set) {
     using namespace egm;
+    if (!set_known(feature_set)) return fail(KM_ERR_INVALID_ARG, "egm_ragged_functionals: feature set %d", feature_set);
     if (!plan || !rings_dev || !slots_dev || !scale_dev || !rec_dev || !out_dev || n_slots < 1 || n_slots > 65535 || max_nf < 1 ||
         max_nf > (long_windows ? LongTier::MAXF : ShortTier::MAXF) || ring_len < 1 || ring_len > (1 << 30))
         return fail(KM_ERR_INVALID_ARG, "egm_ragged_functionals: bad argument");
     EgmArgs a = egm_args(static_cast<EgmPlan*>(plan), rings_dev, 0, 0, scale_dev, rec_dev);
     a.rec_frames = max_nf; a.slots = slots_dev; a.ring_len = (int)ring_len;
     hipLaunchKernelGGL(egm_peak_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, rings_dev, (int64_t)0, slots_dev, (int)ring_len, scale_dev);
-    hipLaunchKernelGGL(egm_frame_kernel<true>, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
+    const auto frame_kernel = feature_set == SET_GEMAPS ? egm_frame_kernel<true, SET_GEMAPS> : egm_frame_kernel<true, SET_EGEMAPS>;
+    hipLaunchKernelGGL(frame_kernel, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
     if (const int rc = egm_track(rec_dev, 0, max_nf, slots_dev, n_slots, long_windows, st)) return rc;
     hipLaunchKernelGGL(egm_voiced_kernel<true>, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
-    return egm_functional(rec_dev, 0, max_nf, slots_dev, n_slots, out_dev, long_windows, st);
+    return egm_functional(rec_dev, 0, max_nf, slots_dev, n_slots, out_dev, long_windows, st, feature_set);
 }
 
 }  // namespace km
@@ -718,7 +728,7 @@ int64_t km_egemaps_workspace_floats(int64_t B, int64_t L) {
 // km_egemaps_functionals and km_egemaps_functionals_long (`who` is the name the texts carry).  The latter takes windows of up to 2^20
 // samples: beyond 2048 frames the two per-window kernels run at their long tier between the same per-frame kernels; up to 2048
 // frames it launches what the former launches
-static int egm_functionals(const char* who, bool long_windows, void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize,
+static int egm_functionals(const char* who, int feature_set, bool long_windows, void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize,
                            float* work_dev, int64_t work_floats, float* out_dev, void* stream) {
     using namespace egm;
     if (!plan || !audio_dev || !work_dev || !out_dev || B <= 0 || L <= 0) return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
@@ -740,20 +750,30 @@ static int egm_functionals(const char* who, bool long_windows, void* plan, const
         HIP_TRY(hipGetLastError());
     }
     const EgmArgs a = egm_args(p, audio_dev, L, (int)nf, normalize ? scale : nullptr, rec);
-    hipLaunchKernelGGL(egm_frame_kernel<false>, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
+    const auto frame_kernel = feature_set == SET_GEMAPS ? egm_frame_kernel<false, SET_GEMAPS> : egm_frame_kernel<false, SET_EGEMAPS>;
+    hipLaunchKernelGGL(frame_kernel, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
     if (const int rc = egm_track(rec, (int)nf, (int)nf, nullptr, (int)B, long_tier, st)) return rc;
     hipLaunchKernelGGL(egm_voiced_kernel<false>, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
-    return egm_functional(rec, (int)nf, (int)nf, nullptr, (int)B, out_dev, long_tier, st);
+    return egm_functional(rec, (int)nf, (int)nf, nullptr, (int)B, out_dev, long_tier, st, feature_set);
 }
 
 int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
                            int64_t work_floats, float* out_dev, void* stream) {
-    return egm_functionals("km_egemaps_functionals", false, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev, stream);
+    return egm_functionals("km_egemaps_functionals", egm::SET_EGEMAPS, false, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev, stream);
 }
 
 int km_egemaps_functionals_long(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
                                 int64_t work_floats, float* out_dev, void* stream) {
-    return egm_functionals("km_egemaps_functionals_long", true, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev, stream);
+    return egm_functionals("km_egemaps_functionals_long", egm::SET_EGEMAPS, true, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev, stream);
+}
+
+// either call above for either feature set: out_dev is (B, km_feature_set_width(feature_set)).  With set 0 the launches are theirs
+int km_egemaps_functionals_set(void* plan, int32_t feature_set, int32_t long_windows, const float* audio_dev, int64_t B, int64_t L, int32_t normalize,
+                               float* work_dev, int64_t work_floats, float* out_dev, void* stream) {
+    if (!egm::set_known(feature_set))
+        return fail(KM_ERR_INVALID_ARG, "km_egemaps_functionals_set: feature set %d, 0 (eGeMAPS) or 1 (GeMAPS)", (int)feature_set);
+    return egm_functionals("km_egemaps_functionals_set", feature_set, long_windows != 0, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev,
+                           stream);
 }
 
 // per-frame records of the most recent call on this workspace, for the tests: (B, nf, 36) floats

@@ -19,8 +19,9 @@ struct EgmSlot {
 // peak, frame, pitch-track, voiced and functional kernels for n_slots slots: grids of max_nf x n_slots (per frame) and n_slots (per
 // window) whatever the table holds.  scale_dev (n_slots), rec_dev (n_slots, max_nf, 36), out_dev (n_slots, 88): rows of empty slots
 // are not written.  No allocation, no synchronisation.  max_nf <= 2048; with long_windows max_nf <= 6548 and the two per-window kernels
-// (km_egemaps_window.hip) run at their long tier for every slot (equal bits on equal records up to 2048 frames).
+// (km_egemaps_window.hip) run at their long tier for every slot (equal bits on equal records up to 2048 frames).  feature_set 1 (GeMAPS,
+// km_egemaps_dev.h): the frame and functional kernels' GeMAPS instantiations, out_dev is (n_slots, 62).
 int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
-                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st, bool long_windows = false);
+                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st, bool long_windows = false, int feature_set = 0);
 
 }  // namespace km

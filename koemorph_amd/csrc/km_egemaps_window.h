@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "km_egemaps_dev.h"
 #include "km_egemaps_ragged.h"
 
 namespace km {
@@ -36,10 +37,11 @@ template <class Tier> constexpr int func_lds() { return (2 * Tier::MAXF + Tier::
 // so that nothing but launches is left for a stream capture.
 int egm_window_prepare();
 
-// Pitch track (writes the F0 column of the records) and functionals (88 floats per window) of n windows, dense (slots null: every
+// Pitch track (writes the F0 column of the records) and functionals (88 floats per window, 62 for the GeMAPS feature set) of n windows, dense (slots null: every
 // window has nf frames, records rec_frames apart) or ragged (the frame count of window i is slots[i].nf, empty slots are skipped).
 // rec_frames is at most the tier's MAXF.  One launch of n workgroups of 256 threads each.
 int egm_track(float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, bool long_tier, hipStream_t st);
-int egm_functional(const float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, float* out_dev, bool long_tier, hipStream_t st);
+int egm_functional(const float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, float* out_dev, bool long_tier, hipStream_t st,
+                   int feature_set = egm::SET_EGEMAPS);
 
 }  // namespace km

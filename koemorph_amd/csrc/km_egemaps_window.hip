@@ -128,12 +128,15 @@ __global__ __launch_bounds__(256) void egm_viterbi_kernel(float* __restrict__ re
     }
 }
 
-// functionals: one workgroup per window
-template <bool RAGGED, class Tier>
+// functionals: one workgroup per window.  SET (km_egemaps_dev.h): the GeMAPS instantiations skip the seven contours none of their 62
+// values reads (flux, MFCC 1-4, the bandwidths of F2 and F3) and the RMS sum of the sound level, and write the values they keep at
+// stride 62, at the place out_col gives; each value is computed by the statements that compute it among the 88.
+template <bool RAGGED, class Tier, int SET>
 __global__ __launch_bounds__(256) void egm_functional_kernel(const float* __restrict__ recs, int nf, int rec_frames, const EgmSlot* __restrict__ slots,
                                                              float* __restrict__ out) {
     using namespace egm;
     constexpr int MAXF = Tier::MAXF, SORT_MAX = Tier::SORT_MAX;
+    constexpr bool FULL = SET == SET_EGEMAPS;
     static_assert(func_lds<Tier>() <= 160 * 1024, "gfx950: 160 KB of LDS per workgroup");
     static_assert(MAXF <= SORT_MAX && (SORT_MAX & (SORT_MAX - 1)) == 0, "the sort buffer holds every frame of the longest window");
     extern __shared__ float dyn[];
@@ -150,7 +153,8 @@ __global__ __launch_bounds__(256) void egm_functional_kernel(const float* __rest
     }
     if (nf > MAXF) return;                                               // refused on the host; never index past the LDS arrays
     const float* rec = recs + (int64_t)blockIdx.x * rec_frames * REC;
-    float* o = out + (int64_t)blockIdx.x * 88;
+    float* o = out + (int64_t)blockIdx.x * set_width(SET);
+    auto col = [](int c) { return FULL ? c : gemaps_pos(c); };           // where eGeMAPS column c is written
     auto raw = [&](int t, int field) { return rec[(int64_t)t * REC + field]; };
     // smoothed F0 (non-zero smoothing) defines the voiced frames
     for (int t = tid; t < nf; t += 256) {
@@ -268,35 +272,41 @@ __global__ __launch_bounds__(256) void egm_functional_kernel(const float* __rest
         float pk = 0.f;
         for (int t = 1 + tid; t + 1 < nf; t += 256) if (v[t] > v[t - 1] && v[t] >= v[t + 1]) pk += 1.f;
         const float npk = block_sum(pk, red);
-        if (tid == 0) o[81] = npk / (nf * (float)HOP / SR);
+        if (tid == 0) o[col(81)] = npk / (nf * (float)HOP / SR);
     }
-    load(R_FLUX, 0);
-    mean_sn(0, m, sn); if (tid == 0) { o[20] = m; o[21] = sn; }
-    mean_sn(1, m, sn); if (tid == 0) { o[66] = m; o[67] = sn; }
-    mean_sn(2, m, sn); if (tid == 0) o[80] = m;
-    for (int i = 0; i < 4; ++i) {
-        load(R_MFCC + i, 0);
-        mean_sn(0, m, sn); if (tid == 0) { o[22 + 2 * i] = m; o[23 + 2 * i] = sn; }
-        mean_sn(1, m, sn); if (tid == 0) { o[68 + 2 * i] = m; o[69 + 2 * i] = sn; }
+    if constexpr (FULL) {
+        load(R_FLUX, 0);
+        mean_sn(0, m, sn); if (tid == 0) { o[20] = m; o[21] = sn; }
+        mean_sn(1, m, sn); if (tid == 0) { o[66] = m; o[67] = sn; }
+        mean_sn(2, m, sn); if (tid == 0) o[80] = m;
+        for (int i = 0; i < 4; ++i) {
+            load(R_MFCC + i, 0);
+            mean_sn(0, m, sn); if (tid == 0) { o[22 + 2 * i] = m; o[23 + 2 * i] = sn; }
+            mean_sn(1, m, sn); if (tid == 0) { o[68 + 2 * i] = m; o[69 + 2 * i] = sn; }
+        }
     }
     {
         const int fields[14] = {R_JIT, R_SHIM, R_HNR, R_H1H2, R_H1A3, R_F, R_BW, R_FAMP, R_F + 1, R_BW + 1, R_FAMP + 1, R_F + 2, R_BW + 2, R_FAMP + 2};
         for (int i = 0; i < 14; ++i) {
+            if (!FULL && (fields[i] == R_BW + 1 || fields[i] == R_BW + 2)) continue;
             load(fields[i], 1);
-            mean_sn(1, m, sn); if (tid == 0) { o[30 + 2 * i] = m; o[31 + 2 * i] = sn; }
+            mean_sn(1, m, sn); if (tid == 0) { o[col(30 + 2 * i)] = m; o[col(31 + 2 * i)] = sn; }
         }
         const int spec[4] = {R_ALPHA, R_HAMM, R_SL0, R_SL1};
         for (int i = 0; i < 4; ++i) {
             load(spec[i], 0);
-            mean_sn(1, m, sn); if (tid == 0) { o[58 + 2 * i] = m; o[59 + 2 * i] = sn; }
-            mean_sn(2, m, sn); if (tid == 0) o[76 + i] = m;
+            mean_sn(1, m, sn); if (tid == 0) { o[col(58 + 2 * i)] = m; o[col(59 + 2 * i)] = sn; }
+            mean_sn(2, m, sn); if (tid == 0) o[col(76 + i)] = m;
         }
     }
     // voiced / unvoiced segments and the equivalent sound level
     {
-        float e2 = 0.f;
-        for (int t = tid; t < nf; t += 256) { const float r = raw(t, R_RMS); e2 += r * r; }
-        const float es = block_sum(e2, red);
+        float es = 0.f;
+        if constexpr (FULL) {
+            float e2 = 0.f;
+            for (int t = tid; t < nf; t += 256) { const float r = raw(t, R_RMS); e2 += r * r; }
+            es = block_sum(e2, red);
+        }
         if (tid == 0) {
             float vs = 0.f, vq = 0.f, us = 0.f, uq = 0.f; int vn = 0, un = 0, run = 0; bool cur = false;
             for (int t = 0; t <= nf; ++t) {
@@ -308,12 +318,12 @@ __global__ __launch_bounds__(256) void egm_functional_kernel(const float* __rest
                 if (t < nf) { cur = vo; ++run; }
             }
             const float dur = nf * (float)HOP / SR, fr = (float)HOP / SR;
-            o[82] = vn / dur;
-            o[83] = vn ? vs / vn * fr : 0.f;
-            o[84] = vn ? sqrtf(fmaxf(vq / vn - (vs / vn) * (vs / vn), 0.f)) * fr : 0.f;
-            o[85] = un ? us / un * fr : 0.f;
-            o[86] = un ? sqrtf(fmaxf(uq / un - (us / un) * (us / un), 0.f)) * fr : 0.f;
-            o[87] = 10.0f * log10f(fmaxf(es / nf, 1e-12f));
+            o[col(82)] = vn / dur;
+            o[col(83)] = vn ? vs / vn * fr : 0.f;
+            o[col(84)] = vn ? sqrtf(fmaxf(vq / vn - (vs / vn) * (vs / vn), 0.f)) * fr : 0.f;
+            o[col(85)] = un ? us / un * fr : 0.f;
+            o[col(86)] = un ? sqrtf(fmaxf(uq / un - (us / un) * (us / un), 0.f)) * fr : 0.f;
+            if constexpr (FULL) o[87] = 10.0f * log10f(fmaxf(es / nf, 1e-12f));
         }
     }
 }
@@ -327,8 +337,10 @@ int egm_window_prepare() {
     constexpr hipFuncAttribute attr = hipFuncAttributeMaxDynamicSharedMemorySize;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_viterbi_kernel<false, LongTier>), attr, track_lds<LongTier>()));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_viterbi_kernel<true, LongTier>), attr, track_lds<LongTier>()));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_functional_kernel<false, LongTier>), attr, func_lds<LongTier>()));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_functional_kernel<true, LongTier>), attr, func_lds<LongTier>()));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_functional_kernel<false, LongTier, SET_EGEMAPS>), attr, func_lds<LongTier>()));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_functional_kernel<true, LongTier, SET_EGEMAPS>), attr, func_lds<LongTier>()));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_functional_kernel<false, LongTier, SET_GEMAPS>), attr, func_lds<LongTier>()));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&egm_functional_kernel<true, LongTier, SET_GEMAPS>), attr, func_lds<LongTier>()));
     return KM_OK;
 }
 
@@ -347,11 +359,11 @@ static void launch_track(float* rec, int nf, int rec_frames, const EgmSlot* slot
     else hipLaunchKernelGGL((egm_viterbi_kernel<false, Tier>), dim3((unsigned)n), dim3(256), lds, st, rec, nf, rec_frames, (const EgmSlot*)nullptr);
 }
 
-template <class Tier>
+template <class Tier, int SET>
 static void launch_functional(const float* rec, int nf, int rec_frames, const EgmSlot* slots, int n, float* out, hipStream_t st) {
     constexpr int lds = egm::func_lds<Tier>();
-    if (slots) hipLaunchKernelGGL((egm_functional_kernel<true, Tier>), dim3((unsigned)n), dim3(256), lds, st, rec, 0, rec_frames, slots, out);
-    else hipLaunchKernelGGL((egm_functional_kernel<false, Tier>), dim3((unsigned)n), dim3(256), lds, st, rec, nf, rec_frames, (const EgmSlot*)nullptr, out);
+    if (slots) hipLaunchKernelGGL((egm_functional_kernel<true, Tier, SET>), dim3((unsigned)n), dim3(256), lds, st, rec, 0, rec_frames, slots, out);
+    else hipLaunchKernelGGL((egm_functional_kernel<false, Tier, SET>), dim3((unsigned)n), dim3(256), lds, st, rec, nf, rec_frames, (const EgmSlot*)nullptr, out);
 }
 
 int egm_track(float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, bool long_tier, hipStream_t st) {
@@ -362,10 +374,16 @@ int egm_track(float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, 
     return KM_OK;
 }
 
-int egm_functional(const float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, float* out_dev, bool long_tier, hipStream_t st) {
+int egm_functional(const float* rec_dev, int nf, int rec_frames, const EgmSlot* slots_dev, int n, float* out_dev, bool long_tier, hipStream_t st,
+                   int feature_set) {
+    using namespace egm;
+    if (!set_known(feature_set)) return fail(KM_ERR_INVALID_ARG, "egm_functional: feature set %d", feature_set);
     if (const int rc = window_check("egm_functional", rec_dev, out_dev, nf, rec_frames, slots_dev, n, long_tier)) return rc;
-    if (long_tier) launch_functional<egm::LongTier>(rec_dev, nf, rec_frames, slots_dev, n, out_dev, st);
-    else launch_functional<egm::ShortTier>(rec_dev, nf, rec_frames, slots_dev, n, out_dev, st);
+    if (feature_set == SET_GEMAPS) {
+        if (long_tier) launch_functional<LongTier, SET_GEMAPS>(rec_dev, nf, rec_frames, slots_dev, n, out_dev, st);
+        else launch_functional<ShortTier, SET_GEMAPS>(rec_dev, nf, rec_frames, slots_dev, n, out_dev, st);
+    } else if (long_tier) launch_functional<LongTier, SET_EGEMAPS>(rec_dev, nf, rec_frames, slots_dev, n, out_dev, st);
+    else launch_functional<ShortTier, SET_EGEMAPS>(rec_dev, nf, rec_frames, slots_dev, n, out_dev, st);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }
@@ -405,6 +423,19 @@ int km_egemaps_track_from_records_long(float* rec_dev, int64_t B, int64_t nf, vo
 int km_egemaps_functionals_from_records_long(const float* rec_dev, int64_t B, int64_t nf, float* out_dev, void* stream) {
     if (const int rc = check_records("km_egemaps_functionals_from_records_long", rec_dev, out_dev, B, nf, egm::LongTier::MAXF, "65.5 s")) return rc;
     return egm_functional(rec_dev, (int)nf, (int)nf, nullptr, (int)B, out_dev, true, (hipStream_t)stream);
+}
+
+int km_feature_set_width(int32_t feature_set) { return egm::set_width(feature_set); }
+
+// either hook above for either feature set: out_dev is (B, km_feature_set_width); long_windows != 0 ALWAYS runs the long tier
+int km_egemaps_functionals_from_records_set(int32_t feature_set, int32_t long_windows, const float* rec_dev, int64_t B, int64_t nf, float* out_dev,
+                                            void* stream) {
+    const char* who = "km_egemaps_functionals_from_records_set";
+    if (!egm::set_known(feature_set)) return fail(KM_ERR_INVALID_ARG, "%s: feature set %d, 0 (eGeMAPS) or 1 (GeMAPS)", who, (int)feature_set);
+    if (const int rc = long_windows ? check_records(who, rec_dev, out_dev, B, nf, egm::LongTier::MAXF, "65.5 s")
+                                    : check_records(who, rec_dev, out_dev, B, nf, egm::ShortTier::MAXF, "20.5 s"))
+        return rc;
+    return egm_functional(rec_dev, (int)nf, (int)nf, nullptr, (int)B, out_dev, long_windows != 0, (hipStream_t)stream, feature_set);
 }
 
 }  // extern "C"

@@ -34,7 +34,8 @@ namespace km {
 namespace ec {
 using namespace emo;
 constexpr int TN = 16, TM = 16;          // the epilogue's tile: output columns per workgroup, rows per turn (TN * TM = 256 threads)
-constexpr int WS = NCAT + 1;             // LDS stride of a weight row: 265 is odd, so the 16 columns of a half wave hit 16 banks
+constexpr int ws(int nf) { return 3 * nf + 1; }    // LDS stride of a weight row: 265 (187 for the 62 of GeMAPS) is odd, so the 16 columns of a half wave hit 16 banks
+static_assert(ws(NFEAT) % 2 == 1 && ws(62) % 2 == 1, "odd strides");
 constexpr int64_t MAX_CLIP = (int64_t)1 << 30;     // egm_ragged_functionals' ring limit; EgmSlot.start is an int32
 constexpr int RW = 16;                   // rows at width 9: the lanes a window takes, so 256 / 16 windows per workgroup
 }  // namespace ec
@@ -52,6 +53,8 @@ struct EmotionClip : EmoTiming {
     float* bias = nullptr;     // (256)
     bool has_compression = false;
     bool basic = false;        // the `basic` back end: rows of 9, rec is (max_slots, max_nf, 4), no scale / fout / f0 / w / bias
+    int feature_set = 0;       // KM_FEATURE_SET_*; nfeat = 88 or 62: fout (max_slots, nfeat), f0 (nfeat), w (256, 3 nfeat)
+    int nfeat = emo::NFEAT;
     bool long_windows = false; // km_emotion_clip_create_long with more than 2048 frames per window: the long tier of the per-window kernels (km_egemaps_window.hip)
     void* prosody = nullptr;
     ~EmotionClip() { (void)km_egemaps_plan_destroy(plan); (void)km_prosody_plan_destroy(prosody); }
@@ -85,11 +88,14 @@ __global__ __launch_bounds__(256) void ec_plan_kernel(int64_t g0, int64_t G, int
 // the pass, 16 rows per turn (thread = column x row).  Row (c, 0) is slot c K - g0 of this pass when c K >= g0; otherwise an earlier
 // pass wrote features[c K] (every workgroup reads it, none of this launch writes it).  Without `features` (one clip, so c = 0) the
 // object's f0 stands in for features[0]: block 0 of the pass that holds row 0 stores it, later passes read it.  A row's sum is one
-// fmaf chain over k = 0 .. 263 from zero, then + bias: the order of es_epilogue_kernel, whatever the pass holds. ----
+// fmaf chain over k = 0 .. 263 from zero, then + bias: the order of es_epilogue_kernel, whatever the pass holds.  NF = 62 (GeMAPS): the
+// same at 62 features a row and 186 weights a column. ----
+template <int NF>
 __global__ __launch_bounds__(256) void ec_epilogue_kernel(const float* __restrict__ fout, int rows, int64_t g0, int64_t K, float* __restrict__ f0,
                                                           const float* __restrict__ w, const float* __restrict__ bias,
                                                           float* __restrict__ features, float* __restrict__ emotion) {
     using namespace ec;
+    constexpr int NFEAT = NF, NCAT = 3 * NF, WS = ws(NF);
     __shared__ float wl[TN * WS];
     __shared__ float xl[TM * NFEAT];
     __shared__ float f0l[TM * NFEAT];
@@ -153,27 +159,29 @@ __global__ __launch_bounds__(256) void ec_rows_kernel(const float* __restrict__ 
 }
 
 static int ec_create(const char* fn, void** ec_out, double context_window_s, double update_interval_s, int64_t max_slots, bool basic,
-                     bool long_windows = false) {
+                     bool long_windows = false, int feature_set = 0) {
     using namespace ec;
     if (!ec_out) return fail(KM_ERR_INVALID_ARG, "%s: NULL argument", fn);
     *ec_out = nullptr;
+    if (!egm::set_known(feature_set)) return fail(KM_ERR_INVALID_ARG, "%s: feature set %d, 0 (eGeMAPS) or 1 (GeMAPS)", fn, feature_set);
     if (const int rc = emo_check_seconds(fn, context_window_s, update_interval_s)) return rc;
     if (max_slots < 1 || max_slots > 65535) return fail(KM_ERR_INVALID_ARG, "%s: max_slots %lld, 1 .. 65535", fn, (long long)max_slots);
     std::unique_ptr<EmotionClip> e(new (std::nothrow) EmotionClip());
     if (!e) return fail(KM_ERR_HIP, "%s: out of host memory", fn);
     if (const int rc = emo_timing(fn, context_window_s, update_interval_s, basic, e.get(), long_windows)) return rc;
     e->max_slots = max_slots; e->basic = basic;
+    e->feature_set = feature_set; e->nfeat = egm::set_width(feature_set);
     e->long_windows = long_windows && e->max_nf > MAXF;                         // up to 2048 frames it is the plain object
     if (e->long_windows)
         if (const int rc = egm_window_prepare()) return rc;
     if (const int rc = basic ? km_prosody_plan_create(&e->prosody) : km_egemaps_plan_create(&e->plan)) return rc;
-    const int64_t ms = max_slots, nf = e->max_nf;
+    const int64_t ms = max_slots, nf = e->max_nf, NF = e->nfeat;
     auto layout = [&](char* base) {
         EmoCarver c{base};
         e->table = c.take<EgmSlot>(ms); e->rec = c.take<float>(ms * nf * (basic ? BASIC_REC : REC));
         if (!basic) {
-            e->scale = c.take<float>(ms); e->fout = c.take<float>(ms * NFEAT); e->f0 = c.take<float>(NFEAT);
-            e->w = c.take<float>((int64_t)NEMO * NCAT); e->bias = c.take<float>(NEMO);
+            e->scale = c.take<float>(ms); e->fout = c.take<float>(ms * NF); e->f0 = c.take<float>(NF);
+            e->w = c.take<float>(NEMO * 3 * NF); e->bias = c.take<float>(NEMO);
         }
         return c.at;
     };
@@ -200,9 +208,11 @@ static int ec_build(EmotionClip* e, const float* clips_dev, int64_t B, int64_t L
             if (const int rc = prosody_ragged(e->prosody, clips_dev, L, e->table, ms, e->max_nf, e->rec, emotion_out + g0 * ec::NBASIC, st)) return rc;
             continue;
         }
-        if (const int rc = egm_ragged_functionals(e->plan, clips_dev, L, e->table, ms, e->max_nf, e->scale, e->rec, e->fout, st, e->long_windows))
+        if (const int rc = egm_ragged_functionals(e->plan, clips_dev, L, e->table, ms, e->max_nf, e->scale, e->rec, e->fout, st, e->long_windows,
+                                                  e->feature_set))
             return rc;
-        hipLaunchKernelGGL(ec_epilogue_kernel, dim3(ec::NEMO / ec::TN), dim3(256), 0, st, (const float*)e->fout, (int)(G - g0 < ms ? G - g0 : ms), g0, K,
+        const auto epilogue = e->nfeat == egm::NFEAT_GEMAPS ? ec_epilogue_kernel<egm::NFEAT_GEMAPS> : ec_epilogue_kernel<ec::NFEAT>;
+        hipLaunchKernelGGL(epilogue, dim3(ec::NEMO / ec::TN), dim3(256), 0, st, (const float*)e->fout, (int)(G - g0 < ms ? G - g0 : ms), g0, K,
                            e->f0, (const float*)e->w, (const float*)e->bias, features_out, emotion_out);
         HIP_TRY(hipGetLastError());
     }
@@ -227,6 +237,17 @@ int km_emotion_clip_create_basic(void** ec_out, double context_window_s, double 
     return ec_create("km_emotion_clip_create_basic", ec_out, context_window_s, update_interval_s, max_slots, true);
 }
 
+int km_emotion_clip_create_set(void** ec_out, double context_window_s, double update_interval_s, int64_t max_slots, int32_t feature_set,
+                               int32_t long_windows) {
+    return ec_create("km_emotion_clip_create_set", ec_out, context_window_s, update_interval_s, max_slots, false, long_windows != 0, feature_set);
+}
+
+int km_emotion_clip_feature_width(void* ec) {
+    if (!ec) return 0;
+    const EmotionClip* e = static_cast<EmotionClip*>(ec);
+    return e->basic ? ec::NBASIC : e->nfeat;
+}
+
 int km_emotion_clip_width(void* ec) {
     if (!ec) return 0;
     return static_cast<EmotionClip*>(ec)->basic ? ec::NBASIC : ec::NEMO;
@@ -243,7 +264,7 @@ int km_emotion_clip_set_compression(void* ec, const float* w_dev, const float* b
     EmotionClip* e = static_cast<EmotionClip*>(ec);
     if (e->basic) return fail(KM_ERR_INVALID_ARG, "km_emotion_clip_set_compression: the basic back end has no compression layer");
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(e->w, w_dev, (size_t)ec::NEMO * ec::NCAT * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->w, w_dev, (size_t)ec::NEMO * 3 * e->nfeat * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(e->bias, b_dev, ec::NEMO * sizeof(float), hipMemcpyDeviceToDevice, st));
     e->has_compression = true;
     return KM_OK;

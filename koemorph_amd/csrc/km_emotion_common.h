@@ -12,7 +12,7 @@
 namespace km {
 
 namespace emo {
-constexpr int SR = 16000, NFEAT = 88, NCAT = 3 * NFEAT, NEMO = 256, REC = 36, MAXF = 2048;
+constexpr int SR = 16000, NFEAT = 88, NEMO = 256, REC = 36, MAXF = 2048;   // NFEAT: eGeMAPS; a GeMAPS object has egm::NFEAT_GEMAPS = 62 (km_egemaps_dev.h)
 constexpr int NBASIC = 9, BASIC_REC = 4, BASIC_HOP = 512, BASIC_MAX_WINDOW = 1 << 20;   // the `basic` back end (km_prosody.hip)
 }  // namespace emo
 

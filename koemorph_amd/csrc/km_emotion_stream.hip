@@ -12,6 +12,10 @@
 // stream's features are the nine raw values of EmotionExtractor._extract_basic on its window (km_prosody.hip over the same slot
 // table), kept in the first 9 of the stream's 88 feature floats; no peak normalisation, no slots, no Linear(264, 256).
 //
+// A second feature set on the eGeMAPS back end (km_emotion_stream_create_set, KM_FEATURE_SET_GEMAPS): the 62 functionals of GeMAPS, the
+// emotion input of the reference's `fast` variant.  The epilogue, the reset and the transpose are templates on the feature count NF, 88
+// or 62: features (n, NF), slots (n, 2, NF), Linear(3 NF, 256) -- the same sequential chain over k with the removed columns' terms left out.
+//
 // Time is audio time: a stream is due when `update_samples` samples have arrived since its last update (the reference asks
 // time.time()), so every result is a function of the call sequence.  Nothing here allocates, synchronises or reads back after
 // creation and every grid is fixed by (n_streams, max_updates): push + update capture into a hipGraph as one linear chain.
@@ -52,7 +56,7 @@ struct EmotionStream : EmoTiming {
     DevBuf<char> blob;         // one allocation, carved below
     float* ring = nullptr;     // (n, ring_len)
     EsState st{};
-    float* features = nullptr; // (n, 88)
+    float* features = nullptr; // (n, nfeat): (n, 88), or (n, 62) for GeMAPS; slots, fout and wt likewise
     float* slots = nullptr;    // (n, 2, 88)
     float* emotion = nullptr;  // (n, 256)
     uint8_t* updated = nullptr;// (n)
@@ -64,6 +68,8 @@ struct EmotionStream : EmoTiming {
     float* bias = nullptr;     // (256)
     bool has_compression = false;
     bool basic = false;        // the `basic` back end: features holds 9 values per stream (row stride 88), no slots, no emotion layer
+    int feature_set = 0;       // KM_FEATURE_SET_*; nfeat = 88 or 62 (the basic back end keeps its 9 values at the stride of 88)
+    int nfeat = emo::NFEAT;
     bool long_windows = false; // km_emotion_stream_create_long with more than 2048 frames per window: the long tier of the per-window kernels (km_egemaps_window.hip)
     void* prosody = nullptr;
     ~EmotionStream() { (void)km_egemaps_plan_destroy(plan); (void)km_prosody_plan_destroy(prosody); }
@@ -127,11 +133,13 @@ __global__ __launch_bounds__(es::SEL_THREADS) void es_select_kernel(int n, int m
     }
 }
 
-// ---- per selected stream: scrub, slots, bookkeeping, Linear(264, 256) ----
+// ---- per selected stream: scrub, slots, bookkeeping, Linear(3 NF, 256) ----
+template <int NF>
 __global__ __launch_bounds__(256) void es_epilogue_kernel(const EgmSlot* __restrict__ table, const float* __restrict__ fout, EsState st,
                                                           float* __restrict__ features, float* __restrict__ slots,
                                                           const float* __restrict__ wt, const float* __restrict__ bias, float* __restrict__ emotion) {
     using namespace es;
+    constexpr int NFEAT = NF, NCAT = 3 * NF;
     __shared__ float x[NCAT];
     const int tid = threadIdx.x;
     const EgmSlot sl = table[blockIdx.x];
@@ -178,10 +186,12 @@ __global__ __launch_bounds__(64) void es_basic_epilogue_kernel(const EgmSlot* __
 }
 
 // ---- OpenSMILEeGeMAPSExtractor.reset, per stream ----
+template <int NF>
 __global__ __launch_bounds__(256) void es_reset_kernel(const uint8_t* __restrict__ mask, float* __restrict__ ring, int ring_len, EsState st,
                                                        float* __restrict__ features, float* __restrict__ slots, float* __restrict__ emotion,
                                                        uint8_t* __restrict__ updated) {
     using namespace es;
+    constexpr int NFEAT = NF;
     const int s = blockIdx.y;
     if (mask && !mask[s]) return;
     float* r = ring + (int64_t)s * ring_len;
@@ -196,16 +206,19 @@ __global__ __launch_bounds__(256) void es_reset_kernel(const uint8_t* __restrict
     }
 }
 
-__global__ __launch_bounds__(256) void es_transpose_kernel(const float* __restrict__ w, float* __restrict__ wt) {    // (256, 264) -> (264, 256)
+template <int NF>
+__global__ __launch_bounds__(256) void es_transpose_kernel(const float* __restrict__ w, float* __restrict__ wt) {    // (256, 3 NF) -> (3 NF, 256)
+    constexpr int NCAT = 3 * NF;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < es::NEMO * es::NCAT) { const int o = i / es::NCAT, k = i % es::NCAT; wt[k * es::NEMO + o] = w[i]; }
+    if (i < es::NEMO * NCAT) { const int o = i / NCAT, k = i % NCAT; wt[k * es::NEMO + o] = w[i]; }
 }
 
 static int es_create(const char* fn, void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates,
-                     bool basic, bool long_windows = false) {
+                     bool basic, bool long_windows = false, int feature_set = 0) {
     using namespace es;
     if (!es_out) return fail(KM_ERR_INVALID_ARG, "%s: NULL argument", fn);
     *es_out = nullptr;
+    if (!egm::set_known(feature_set)) return fail(KM_ERR_INVALID_ARG, "%s: feature set %d, 0 (eGeMAPS) or 1 (GeMAPS)", fn, feature_set);
     if (n_streams < 1 || n_streams > MAX_STREAMS) return fail(KM_ERR_INVALID_ARG, "%s: n_streams %lld, 1 .. %d", fn, (long long)n_streams, MAX_STREAMS);
     if (const int rc = emo_check_seconds(fn, context_window_s, update_interval_s)) return rc;
     if (max_updates < 1 || max_updates > n_streams)
@@ -214,22 +227,23 @@ static int es_create(const char* fn, void** es_out, int64_t n_streams, double co
     if (!e) return fail(KM_ERR_HIP, "%s: out of host memory", fn);
     if (const int rc = emo_timing(fn, context_window_s, update_interval_s, basic, e.get(), long_windows)) return rc;
     e->n = n_streams; e->max_updates = max_updates; e->basic = basic;
+    e->feature_set = feature_set; e->nfeat = egm::set_width(feature_set);
     e->long_windows = long_windows && e->max_nf > MAXF;                         // up to 2048 frames it is the plain object
     if (e->long_windows)
         if (const int rc = egm_window_prepare()) return rc;
     if (const int rc = basic ? km_prosody_plan_create(&e->prosody) : km_egemaps_plan_create(&e->plan)) return rc;
-    const int64_t n = n_streams, mu = max_updates, R = e->ring_len, nf = e->max_nf;
+    const int64_t n = n_streams, mu = max_updates, R = e->ring_len, nf = e->max_nf, NF = e->nfeat;
     auto layout = [&](char* base) {
         EmoCarver c{base};
         e->ring = c.take<float>(n * R);
         e->st.write_pos = c.take<int32_t>(n); e->st.is_full = c.take<int32_t>(n);
         e->st.total = c.take<int64_t>(n); e->st.last_total = c.take<int64_t>(n);
         e->st.has_features = c.take<int32_t>(n); e->st.slots_filled = c.take<int32_t>(n);
-        e->features = c.take<float>(n * NFEAT); e->slots = c.take<float>(n * 2 * NFEAT);
+        e->features = c.take<float>(n * NF); e->slots = c.take<float>(n * 2 * NF);
         e->emotion = c.take<float>(n * NEMO); e->updated = c.take<uint8_t>(n);
         e->table = c.take<EgmSlot>(mu); e->scale = c.take<float>(mu);
-        e->rec = c.take<float>(mu * nf * (basic ? BASIC_REC : REC)); e->fout = c.take<float>(mu * (basic ? NBASIC : NFEAT));
-        e->wt = c.take<float>((int64_t)NCAT * NEMO); e->bias = c.take<float>(NEMO);
+        e->rec = c.take<float>(mu * nf * (basic ? BASIC_REC : REC)); e->fout = c.take<float>(mu * (basic ? NBASIC : NF));
+        e->wt = c.take<float>(3 * NF * NEMO); e->bias = c.take<float>(NEMO);
         return c.at;
     };
     const int64_t bytes = layout(nullptr);
@@ -259,6 +273,18 @@ int km_emotion_stream_create_basic(void** es_out, int64_t n_streams, double cont
     return es_create("km_emotion_stream_create", es_out, n_streams, context_window_s, update_interval_s, max_updates, true);   // the name both say
 }
 
+int km_emotion_stream_create_set(void** es_out, int64_t n_streams, double context_window_s, double update_interval_s, int64_t max_updates,
+                                 int32_t feature_set, int32_t long_windows) {
+    return es_create("km_emotion_stream_create_set", es_out, n_streams, context_window_s, update_interval_s, max_updates, false, long_windows != 0,
+                     feature_set);
+}
+
+int km_emotion_stream_feature_width(void* es) {
+    if (!es) return 0;
+    const EmotionStream* e = static_cast<EmotionStream*>(es);
+    return e->basic ? es::NBASIC : e->nfeat;
+}
+
 int km_emotion_stream_destroy(void* es) {
     if (!es) return KM_OK;
     delete static_cast<EmotionStream*>(es);
@@ -270,7 +296,8 @@ int km_emotion_stream_set_compression(void* es, const float* w_dev, const float*
     EmotionStream* e = static_cast<EmotionStream*>(es);
     if (e->basic) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_set_compression: the basic back end has no compression layer");
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(es_transpose_kernel, dim3((es::NEMO * es::NCAT + 255) / 256), dim3(256), 0, st, w_dev, e->wt);
+    const auto transpose = e->nfeat == egm::NFEAT_GEMAPS ? es_transpose_kernel<egm::NFEAT_GEMAPS> : es_transpose_kernel<es::NFEAT>;
+    hipLaunchKernelGGL(transpose, dim3((unsigned)((es::NEMO * 3 * e->nfeat + 255) / 256)), dim3(256), 0, st, w_dev, e->wt);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(e->bias, b_dev, es::NEMO * sizeof(float), hipMemcpyDeviceToDevice, st));
     e->has_compression = true;
@@ -309,9 +336,10 @@ int km_emotion_stream_update(void* es, float* emotion_dev, uint8_t* valid_dev, u
         return KM_OK;
     }
     if (const int rc = egm_ragged_functionals(e->plan, e->ring, e->ring_len, e->table, (int)e->max_updates, e->max_nf, e->scale, e->rec, e->fout, st,
-                                              e->long_windows))
+                                              e->long_windows, e->feature_set))
         return rc;
-    hipLaunchKernelGGL(es_epilogue_kernel, dim3((unsigned)e->max_updates), dim3(256), 0, st, (const EgmSlot*)e->table, (const float*)e->fout, e->st,
+    const auto epilogue = e->nfeat == egm::NFEAT_GEMAPS ? es_epilogue_kernel<egm::NFEAT_GEMAPS> : es_epilogue_kernel<es::NFEAT>;
+    hipLaunchKernelGGL(epilogue, dim3((unsigned)e->max_updates), dim3(256), 0, st, (const EgmSlot*)e->table, (const float*)e->fout, e->st,
                        e->features, e->slots, (const float*)e->wt, (const float*)e->bias, e->emotion);
     hipLaunchKernelGGL((es_output_kernel<es::NEMO, es::NEMO>), dim3((unsigned)((e->n * es::NEMO + 255) / 256)), dim3(256), 0, st, (int)e->n, (const float*)e->emotion,
                        (const int32_t*)e->st.has_features, (const uint8_t*)e->updated, emotion_dev, valid_dev, updated_dev);
@@ -323,7 +351,8 @@ int km_emotion_stream_reset_streams(void* es, const uint8_t* mask_dev, void* str
     if (!es) return fail(KM_ERR_INVALID_ARG, "km_emotion_stream_reset_streams: NULL argument");
     EmotionStream* e = static_cast<EmotionStream*>(es);
     const int bx = (e->ring_len + 256 * 8 - 1) / (256 * 8);
-    hipLaunchKernelGGL(es_reset_kernel, dim3((unsigned)(bx < 256 ? bx : 256), (unsigned)e->n), dim3(256), 0, (hipStream_t)stream, mask_dev, e->ring,
+    const auto reset = e->nfeat == egm::NFEAT_GEMAPS ? es_reset_kernel<egm::NFEAT_GEMAPS> : es_reset_kernel<es::NFEAT>;
+    hipLaunchKernelGGL(reset, dim3((unsigned)(bx < 256 ? bx : 256), (unsigned)e->n), dim3(256), 0, (hipStream_t)stream, mask_dev, e->ring,
                        e->ring_len, e->st, e->features, e->slots, e->emotion, e->updated);
     HIP_TRY(hipGetLastError());
     return KM_OK;
@@ -340,9 +369,9 @@ int km_emotion_stream_features(void* es, float* features_dev, float* slots_dev, 
         HIP_TRY(hipGetLastError());
         return KM_OK;
     }
-    HIP_TRY(hipMemcpyAsync(features_dev, e->features, (size_t)e->n * es::NFEAT * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(features_dev, e->features, (size_t)e->n * e->nfeat * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (slots_dev)
-        HIP_TRY(hipMemcpyAsync(slots_dev, e->slots, (size_t)e->n * 2 * es::NFEAT * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        HIP_TRY(hipMemcpyAsync(slots_dev, e->slots, (size_t)e->n * 2 * e->nfeat * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return KM_OK;
 }
 

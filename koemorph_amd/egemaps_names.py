@@ -20,3 +20,29 @@ FEATURE_NAMES: List[str] = (
     ["loudnessPeaksPerSec", "VoicedSegmentsPerSec", "MeanVoicedSegmentLengthSec", "StddevVoicedSegmentLengthSec",
      "MeanUnvoicedSegmentLength", "StddevUnvoicedSegmentLength", "equivalentSoundLevel_dBp"])
 assert len(FEATURE_NAMES) == 88
+
+# GeMAPS v01b as it is defined here: the 88 without the spectral flux, MFCC 1-4, the bandwidths of F2 and F3 and the equivalent
+# sound level, in the order the 88 have (KM_FEATURE_SET_GEMAPS writes these columns).  That openSMILE's own GeMAPSv01b has these
+# values in this order is UNPINNED, as the whole back end is.
+GEMAPS_REMOVED = ("spectralFlux", "mfcc", "F2bandwidth", "F3bandwidth", "equivalentSoundLevel")
+GEMAPS_COLUMNS: List[int] = [i for i, n in enumerate(FEATURE_NAMES) if not any(r in n for r in GEMAPS_REMOVED)]
+GEMAPS_FEATURE_NAMES: List[str] = [FEATURE_NAMES[i] for i in GEMAPS_COLUMNS]
+assert len(GEMAPS_COLUMNS) == 62
+
+FEATURE_SETS = {"eGeMAPSv02": 0, "GeMAPS": 1}         # the reference's spellings -> KM_FEATURE_SET_*
+FEATURE_SET_DIMS = {"eGeMAPSv02": 88, "GeMAPS": 62}
+
+
+def feature_set_code(feature_set: str) -> int:
+    """KM_FEATURE_SET_* of a feature set's name; any other string is refused with the reference's text."""
+    if feature_set not in FEATURE_SETS:
+        raise ValueError(f"Unsupported feature set: {feature_set}")
+    return FEATURE_SETS[feature_set]
+
+
+def check_compression_shape(layer, feature_set: str = "eGeMAPSv02") -> None:
+    """The compression layer of a feature set is a Linear(3 * dim, 256) -- three windows concatenated: Linear(264, 256), or
+    Linear(186, 256) for GeMAPS (where the reference hard-codes 264 and so never compresses; a deliberate deviation)."""
+    n_in = 3 * FEATURE_SET_DIMS[feature_set]
+    if tuple(layer.weight.shape) != (256, n_in):
+        raise ValueError(f"compression_layer must be a Linear({n_in}, 256), got weight {tuple(layer.weight.shape)}")

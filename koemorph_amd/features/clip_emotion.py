@@ -14,6 +14,7 @@ import torch
 
 from .. import _lib
 from .._lib import check
+from ..egemaps_names import feature_set_code
 from ..engine import _ptr, _stream_ptr
 from ..streaming import _create_emotion_backend, emotion_stream_shape
 
@@ -39,12 +40,17 @@ class ClipEmotion:
 
     ``long_windows=True`` (km_emotion_clip_create_long): eGeMAPS windows of up to 2**20 samples (65.5 s) instead of 2048 frames --
     ``ClipEmotion(30.0, 0.2, long_windows=True)`` is the track of the reference's ``long_context`` variant, bit for bit the rows of a
-    ``StreamEmotion(1, 30.0, 0.2, long_windows=True)`` stream.  The scratch grows with the window: 0.43 MB per slot at 30 s."""
+    ``StreamEmotion(1, 30.0, 0.2, long_windows=True)`` stream.  The scratch grows with the window: 0.43 MB per slot at 30 s.
+
+    ``feature_set="GeMAPS"`` (km_emotion_clip_create_set): the 62 functionals of GeMAPS -- ``ClipEmotion(10.0, 0.5,
+    feature_set="GeMAPS")`` is the track of the reference's ``fast`` variant.  ``feature_dim`` is 62, ``build`` -> ``(emotion (K, 256),
+    features (K, 62))``, the layer a ``Linear(186, 256)``; ``StreamEmotion``'s notes on the set apply."""
 
     def __init__(self, context_window: float = 20.0, update_interval: float = 0.3, max_slots: int = 64,
-                 compression_layer: Optional[torch.nn.Module] = None, device="cuda", backend: str = "egemaps", long_windows: bool = False):
-        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend, long_windows=long_windows)
-        self.backend, self.long_windows = backend, long_windows
+                 compression_layer: Optional[torch.nn.Module] = None, device="cuda", backend: str = "egemaps", long_windows: bool = False,
+                 feature_set: str = "eGeMAPSv02"):
+        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend, long_windows=long_windows, feature_set=feature_set)
+        self.backend, self.long_windows, self.feature_set = backend, long_windows, feature_set
         if backend == "basic" and compression_layer is not None:
             raise ValueError("the basic back end has no compression layer: its nine features are the emotion input as they are")
         if not 1 <= max_slots <= 65535:
@@ -55,9 +61,12 @@ class ClipEmotion:
         self._lib = _lib.load()
         create = (self._lib.km_emotion_clip_create_basic if backend == "basic" else
                   self._lib.km_emotion_clip_create_long if long_windows else self._lib.km_emotion_clip_create)
-        self.device, self._h, self.compression_layer, self.emotion_dim, _ = _create_emotion_backend(
-            backend, compression_layer, device, lambda h: create(h, context_window, update_interval, max_slots),
-            self._lib.km_emotion_clip_set_compression)
+        make = lambda h: create(h, context_window, update_interval, max_slots)
+        if feature_set_code(feature_set):
+            make = lambda h: self._lib.km_emotion_clip_create_set(h, context_window, update_interval, max_slots, feature_set_code(feature_set),
+                                                                  1 if long_windows else 0)
+        self.device, self._h, self.compression_layer, self.emotion_dim, self.feature_dim = _create_emotion_backend(
+            backend, compression_layer, device, make, self._lib.km_emotion_clip_set_compression, feature_set)
         self._tracks: Dict[Hashable, Tuple[torch.Tensor, int]] = {}
         self.builds = 0                                                   # calls of build() / build_batch(), track_for's misses included
 
@@ -88,7 +97,7 @@ class ClipEmotion:
         n = clip.shape[0]
         K = self.num_rows(n)
         emotion = torch.empty(K, self.emotion_dim, device=clip.device)
-        features = torch.empty(K, 88, device=clip.device) if self.backend != "basic" else None
+        features = torch.empty(K, self.feature_dim, device=clip.device) if self.backend != "basic" else None
         with torch.cuda.device(clip.device):
             check(self._lib.km_emotion_clip_build(self._h, _ptr(clip), n, _ptr(features) if features is not None else None, _ptr(emotion),
                                                   _stream_ptr(clip.device)))
@@ -105,7 +114,7 @@ class ClipEmotion:
         B, L = clips.shape
         K = self.num_rows(L)
         emotion = torch.empty(B, K, self.emotion_dim, device=clips.device)
-        features = torch.empty(B, K, 88, device=clips.device) if self.backend != "basic" else None
+        features = torch.empty(B, K, self.feature_dim, device=clips.device) if self.backend != "basic" else None
         with torch.cuda.device(clips.device):
             check(self._lib.km_emotion_clip_build_batch(self._h, _ptr(clips), B, L, _ptr(features) if features is not None else None,
                                                         _ptr(emotion), _stream_ptr(clips.device)))

@@ -6,6 +6,10 @@ eGeMAPSv02 functionals: the reference hands each 20 s window to the third-party 
 (:227-235, :439), here the window goes to ``km_egemaps_functionals`` (koemorph_amd/csrc/km_egemaps.hip) -- and
 ``extract_batch`` does it for any number of windows at once, which is what 1 024 concurrent speaker streams need.
 
+``feature_set="GeMAPS"`` (the reference's other choice, its ``fast`` variant): the 62 functionals that are the 88 without the spectral
+flux, MFCC 1-4, the bandwidths of F2 and F3 and the equivalent sound level (``koemorph_amd.egemaps_names.GEMAPS_COLUMNS``), and a
+``Linear(186, 256)`` where the reference's hard-coded ``Linear(264, 256)`` fails.
+
 PARITY UNPINNED for the feature values (openSMILE is neither vendored nor pinned by the reference and is not installed here;
 see oracle/egemaps.py for the published definitions that are implemented).  The buffering / update / 3-window concatenation
 logic is the reference's own and is tested against a restatement (oracle/buffers.py).
@@ -23,6 +27,7 @@ import numpy as np
 
 from .. import _lib
 from .._lib import check
+from ..egemaps_names import FEATURE_SET_DIMS, check_compression_shape, feature_set_code
 
 logger = logging.getLogger(__name__)
 
@@ -125,11 +130,13 @@ class EGeMAPSEngine:
     def num_frames(self, L: int) -> int:
         return int(self._lib.km_egemaps_num_frames(L))
 
-    def functionals(self, audio, normalize: bool = True, long_windows: bool = False):
+    def functionals(self, audio, normalize: bool = True, long_windows: bool = False, feature_set: str = "eGeMAPSv02"):
         """audio (B, L) fp32 on the device -> (B, 88) eGeMAPSv02 functionals.  Windows of more than 2048 frames (20.5 s) are
         refused unless ``long_windows`` (km_egemaps_functionals_long: up to 2**20 samples, 65.5 s); a window of at most 2048 frames
-        runs the same launches either way."""
+        runs the same launches either way.  ``feature_set="GeMAPS"``: (B, 62), the columns GEMAPS_COLUMNS of the 88 bit for bit,
+        from kernels that leave out what only the other 26 need (km_egemaps_functionals_set)."""
         torch = self._torch
+        code = feature_set_code(feature_set)
         audio = audio.to(self.device, torch.float32).contiguous()
         if audio.dim() != 2:
             raise ValueError(f"Expected 2D audio (B, L), got {audio.dim()}D")
@@ -138,11 +145,15 @@ class EGeMAPSEngine:
         if self._work is None or self._work.numel() < need:
             self._work = torch.empty(need, device=self.device)
         self._work_for = (B, L)
-        out = torch.empty(B, EGEMAPS_DIM, device=self.device)
+        out = torch.empty(B, FEATURE_SET_DIMS[feature_set], device=self.device)
         call = self._lib.km_egemaps_functionals_long if long_windows else self._lib.km_egemaps_functionals
+        args = (audio.data_ptr(), B, L, 1 if normalize else 0, self._work.data_ptr(), self._work.numel(), out.data_ptr(),
+                torch.cuda.current_stream(self.device).cuda_stream)
         with torch.cuda.device(self.device):
-            check(call(self._plan, audio.data_ptr(), B, L, 1 if normalize else 0, self._work.data_ptr(), self._work.numel(), out.data_ptr(),
-                       torch.cuda.current_stream(self.device).cuda_stream))
+            if code:
+                check(self._lib.km_egemaps_functionals_set(self._plan, code, 1 if long_windows else 0, *args))
+            else:
+                check(call(self._plan, *args))
         return out
 
     def records(self) -> np.ndarray:
@@ -174,16 +185,18 @@ class EGeMAPSEngine:
             check(call(rec.data_ptr(), B, nf, torch.cuda.current_stream(self.device).cuda_stream))
         return rec
 
-    def functionals_from_records(self, rec, long_windows: bool = False):
+    def functionals_from_records(self, rec, long_windows: bool = False, feature_set: str = "eGeMAPSv02"):
         """records (B, frames, 36) -> (B, 88): the functionals kernel alone (tests).  ``long_windows``: the kernel for up to 6548
-        frames (km_egemaps_functionals_from_records_long), at any frame count."""
+        frames (km_egemaps_functionals_from_records_long), at any frame count.  ``feature_set="GeMAPS"``: (B, 62)."""
         torch = self._torch
+        code = feature_set_code(feature_set)
         rec = self._records_on_device(rec)
         B, nf, _ = rec.shape
-        out = torch.empty(B, EGEMAPS_DIM, device=self.device)
+        out = torch.empty(B, FEATURE_SET_DIMS[feature_set], device=self.device)
         with torch.cuda.device(self.device):
             call = self._lib.km_egemaps_functionals_from_records_long if long_windows else self._lib.km_egemaps_functionals_from_records
-            check(call(rec.data_ptr(), B, nf, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream))
+            args = (rec.data_ptr(), B, nf, out.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+            check(self._lib.km_egemaps_functionals_from_records_set(code, 1 if long_windows else 0, *args) if code else call(*args))
         return out
 
 
@@ -202,8 +215,7 @@ class OpenSMILEeGeMAPSExtractor:
             raise ValueError("Update interval must be at least 0.1 seconds")
         if update_interval > context_window:
             raise ValueError("Update interval cannot be larger than context window")
-        if feature_set != "eGeMAPSv02":
-            raise ValueError(f"Unsupported feature set: {feature_set}")       # the reference also offers GeMAPS (:214-215)
+        feature_set_code(feature_set)                        # "eGeMAPSv02" or "GeMAPS" (:214-215); "Unsupported feature set: X" otherwise
         if feature_level != "Functionals":
             raise ValueError(f"Unsupported feature level: {feature_level}")
         self.sample_rate, self.context_window, self.update_interval = sample_rate, context_window, update_interval
@@ -213,7 +225,8 @@ class OpenSMILEeGeMAPSExtractor:
         self._clock = clock
         self.long_windows = long_windows                     # windows beyond 2048 frames (20.5 s): the long_context variant's 30 s
         self.engine = EGeMAPSEngine(device)
-        self.feature_dim = EGEMAPS_DIM
+        self.feature_set = feature_set
+        self.feature_dim = FEATURE_SET_DIMS[feature_set]     # 88, or the 62 of GeMAPS
         self.audio_buffer = AudioBuffer(max_duration=context_window + 2.0, sample_rate=sample_rate)
         self.last_update_time = 0.0
         self.current_features: Optional[np.ndarray] = None
@@ -232,11 +245,11 @@ class OpenSMILEeGeMAPSExtractor:
 
     # ---- the part openSMILE did -------------------------------------------------------------------------------------
     def extract_batch(self, audio, normalize: bool = True):
-        """(B, L) windows (numpy or tensor) -> (B, 88) tensor on the device: every window in one call."""
+        """(B, L) windows (numpy or tensor) -> (B, 88) tensor on the device ((B, 62) for GeMAPS): every window in one call."""
         import torch
         if isinstance(audio, np.ndarray):
             audio = torch.from_numpy(np.ascontiguousarray(audio, np.float32))
-        return self.engine.functionals(audio, normalize, long_windows=self.long_windows)
+        return self.engine.functionals(audio, normalize, long_windows=self.long_windows, feature_set=self.feature_set)
 
     def _extract_features_from_audio(self, audio: np.ndarray) -> Optional[np.ndarray]:
         """One window -> (88,) float32 (reference :427-454: float32, peak normalisation, NaN / Inf -> 0)."""
@@ -334,7 +347,9 @@ class OpenSMILEeGeMAPSExtractor:
 
     def get_concatenated_features(self) -> Optional[np.ndarray]:
         """3 windows x 88 -> 264 -> Linear(264, 256) (reference :559-592; the layer is created on first use with torch's
-        default initialisation and is not trained there either).  The product runs on the GPU (km_linear)."""
+        default initialisation and is not trained there either).  The product runs on the GPU (km_linear).  GeMAPS: 3 x 62 ->
+        Linear(186, 256) -- a deliberate deviation: the reference hard-codes Linear(264, 256), its product raises on 186 inputs
+        inside the try and it returns None, so its `fast` variant never gets a compressed vector."""
         if not self.use_concatenation:
             logger.warning("get_concatenated_features() called but use_concatenation=False")
             return None
@@ -344,16 +359,14 @@ class OpenSMILEeGeMAPSExtractor:
         parts = [self.window_features[i] if self.window_features[i] is not None else np.zeros(self.feature_dim, np.float32)
                  for i in self.window_intervals]
         concatenated = np.concatenate(parts)
-        if self.compression_layer is None:
-            self.compression_layer = torch.nn.Linear(264, 256)
+        layer = self._compression()
         dev = self.engine.device
-        layer = self.compression_layer
         x = torch.from_numpy(concatenated.astype(np.float32)).to(dev).unsqueeze(0).contiguous()
         w = layer.weight.detach().to(dev, torch.float32).contiguous()
         b = layer.bias.detach().to(dev, torch.float32).contiguous()
         out = torch.empty(1, 256, device=dev)
         with torch.cuda.device(dev):
-            check(self.engine._lib.km_linear(x.data_ptr(), w.data_ptr(), b.data_ptr(), 1, 264, 256, out.data_ptr(),
+            check(self.engine._lib.km_linear(x.data_ptr(), w.data_ptr(), b.data_ptr(), 1, 3 * self.feature_dim, 256, out.data_ptr(),
                                              torch.cuda.current_stream(dev).cuda_stream))
         return out[0].cpu().numpy().astype(np.float32)
 
@@ -387,25 +400,34 @@ class OpenSMILEeGeMAPSExtractor:
         dev = self.engine.device
         past = torch.from_numpy(np.concatenate([self.window_features[0.3], self.window_features[0.6]])).to(dev)
         cat = torch.cat([current, past.unsqueeze(0).expand(B, -1)], dim=1).contiguous()  # (B, 264)
-        if self.compression_layer is None:
-            self.compression_layer = torch.nn.Linear(264, 256)
-        w = self.compression_layer.weight.detach().to(dev, torch.float32).contiguous()
-        b = self.compression_layer.bias.detach().to(dev, torch.float32).contiguous()
+        layer = self._compression()
+        w = layer.weight.detach().to(dev, torch.float32).contiguous()
+        b = layer.bias.detach().to(dev, torch.float32).contiguous()
         out = torch.empty(B, 256, device=dev)
         with torch.cuda.device(dev):
-            check(self.engine._lib.km_linear(cat.data_ptr(), w.data_ptr(), b.data_ptr(), B, 264, 256, out.data_ptr(),
+            check(self.engine._lib.km_linear(cat.data_ptr(), w.data_ptr(), b.data_ptr(), B, 3 * self.feature_dim, 256, out.data_ptr(),
                                              torch.cuda.current_stream(dev).cuda_stream))
         return out
 
+    def _compression(self):
+        """The Linear(3 * feature_dim, 256) of both concatenation paths: created on first use, refused if one of another shape was set."""
+        import torch
+        n_in = 3 * self.feature_dim
+        if self.compression_layer is None:
+            self.compression_layer = torch.nn.Linear(n_in, 256)
+        check_compression_shape(self.compression_layer, self.feature_set)
+        return self.compression_layer
+
     def get_feature_names(self) -> List[str]:
-        from ..egemaps_names import FEATURE_NAMES
-        return list(FEATURE_NAMES)
+        from ..egemaps_names import FEATURE_NAMES, GEMAPS_FEATURE_NAMES
+        return list(GEMAPS_FEATURE_NAMES if self.feature_set == "GeMAPS" else FEATURE_NAMES)
 
     def get_stats(self) -> Dict[str, object]:
         return {"total_updates": self.total_updates, "failed_extractions": self.failed_extractions,
                 "success_rate": self.total_updates / max(self.total_updates + self.failed_extractions, 1),
                 "avg_extraction_time": np.mean(self.extraction_times) if self.extraction_times else 0.0,
                 "context_window": self.context_window, "update_interval": self.update_interval, "feature_dim": self.feature_dim,
+                "feature_set": self.feature_set,
                 "temporal_history_frames": self.temporal_history_frames, "temporal_features_ready": self.temporal_features_ready,
                 "history_length": len(self.feature_history), "use_concatenation": self.use_concatenation,
                 "concatenated_features_ready": getattr(self, "concatenated_features_ready", False),

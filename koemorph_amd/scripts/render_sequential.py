@@ -41,18 +41,18 @@ logger = logging.getLogger(__name__)
 COMPRESSION_SEED = 0          # the Linear(264, 256) of a checkpoint that carries none: torch's default initialisation under this seed
 
 
-def compression_layer(ckpt: dict) -> "tuple[torch.nn.Linear, str]":
+def compression_layer(ckpt: dict, n_in: int = 264) -> "tuple[torch.nn.Linear, str]":
     """The 264 -> 256 layer behind the emotion track and where it came from: ``ckpt["emotion_compression"]`` (``weight`` (256, 264),
-    ``bias`` (256)) when the checkpoint carries one, else a seeded default initialisation."""
+    ``bias`` (256)) when the checkpoint carries one, else a seeded default initialisation.  ``n_in`` 186: the layer of a GeMAPS track."""
     saved = ckpt.get("emotion_compression")
     if saved is not None:
-        layer = torch.nn.Linear(264, 256)
+        layer = torch.nn.Linear(n_in, 256)
         layer.load_state_dict({"weight": torch.as_tensor(saved["weight"], dtype=torch.float32),
                                "bias": torch.as_tensor(saved["bias"], dtype=torch.float32)})
         return layer, "checkpoint"
     with torch.random.fork_rng(devices=[]):                # the caller's generator is left as it was
         torch.manual_seed(COMPRESSION_SEED)
-        layer = torch.nn.Linear(264, 256)
+        layer = torch.nn.Linear(n_in, 256)
     return layer, f"default initialisation, seed {COMPRESSION_SEED}"
 
 
@@ -74,15 +74,27 @@ def emotion_timing(cfg: dict, context_window: Optional[float], update_interval: 
     return float(20.0 if cw is None else cw), float(0.3 if ui is None else ui)
 
 
+def emotion_feature_set(cfg: dict, emotion: str) -> str:
+    """The feature set of the eGeMAPS track, from the checkpoint; ``--emotion egemaps`` on a checkpoint trained with ``--emotion gemaps``
+    (``model_config["emotion_feature_set"] == "GeMAPS"``) and the reverse are refused with a text that names both."""
+    saved = "gemaps" if cfg.get("emotion_feature_set", "eGeMAPSv02") == "GeMAPS" else "egemaps"
+    if emotion in ("egemaps", "gemaps") and emotion != saved:
+        names = {"egemaps": "eGeMAPSv02, 88 functionals", "gemaps": "GeMAPS, 62 functionals"}
+        raise EmotionTimingError(f"--emotion {emotion} ({names[emotion]}) contradicts the checkpoint, which was trained with "
+                                 f"--emotion {saved} ({names[saved]})")
+    return "GeMAPS" if emotion == "gemaps" else "eGeMAPSv02"
+
+
 def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: str = "cuda", share_frames: bool = False,
                emotion_context_window: Optional[float] = None, emotion_update_interval: Optional[float] = None) -> SequentialDualStreamModel:
     ckpt = torch.load(model_path, map_location="cpu", weights_only=True)
     cfg = dict(ckpt.get("model_config") or {})
     timing = emotion_timing(cfg, emotion_context_window, emotion_update_interval)
+    feature_set = emotion_feature_set(cfg, emotion)
     if timing is not None and emotion == "noise":
         raise EmotionTimingError("the emotion track's context window and update interval need --emotion egemaps or basic")
     emotion_dim = int(cfg.get("emotion_dim", 256))
-    width = {"egemaps": 256, "basic": 9}.get(emotion)
+    width = {"egemaps": 256, "gemaps": 256, "basic": 9}.get(emotion)
     if width is not None and width != emotion_dim:
         raise ValueError(f"--emotion {emotion} produces {width} values per window, the checkpoint's emotion_dim is {emotion_dim}")
     clip_emotion: Optional[ClipEmotion] = None
@@ -91,6 +103,11 @@ def load_model(model_path, stride: int = 1, emotion: str = "egemaps", device: st
         logger.info("emotion track: eGeMAPS, compression layer from the %s", source)
         clip_emotion = (ClipEmotion(compression_layer=layer, device=device) if timing is None else
                         ClipEmotion(*timing, compression_layer=layer, device=device, long_windows=True))
+    elif emotion == "gemaps":
+        layer, source = compression_layer(ckpt, 186)
+        logger.info("emotion track: GeMAPS (62 functionals), compression layer from the %s", source)
+        clip_emotion = (ClipEmotion(compression_layer=layer, device=device, feature_set=feature_set) if timing is None else
+                        ClipEmotion(*timing, compression_layer=layer, device=device, long_windows=True, feature_set=feature_set))
     elif emotion == "basic":
         logger.info("emotion track: the nine basic prosodic values per row")
         clip_emotion = ClipEmotion(device=device, backend="basic") if timing is None else ClipEmotion(*timing, device=device, backend="basic")
@@ -153,8 +170,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--input_audio", required=True)
     p.add_argument("--output_json", required=True)
     p.add_argument("--stride", type=int, default=1, help="frames between two window positions")
-    p.add_argument("--emotion", choices=("egemaps", "noise", "basic"), default="egemaps",
-                   help="basic: the clip's track of nine prosodic values per row, for checkpoints of train_sequential --variant basic "
+    p.add_argument("--emotion", choices=("egemaps", "noise", "basic", "gemaps"), default="egemaps",
+                   help="gemaps: the track of the 62 GeMAPS functionals, for checkpoints of train_sequential --emotion gemaps (the feature "
+                        "set and the Linear(186, 256) are the checkpoint's; egemaps on such a checkpoint, and gemaps on any other, is "
+                        "refused); basic: the clip's track of nine prosodic values per row, for checkpoints of train_sequential --variant basic "
                         "--emotion basic (emotion_dim 9); a back end whose width is not the checkpoint's emotion_dim is refused")
     p.add_argument("--attention-summary", default=None, metavar="PATH",
                    help="write the clip's attention statistics (AttentionStats.compute()) as JSON")

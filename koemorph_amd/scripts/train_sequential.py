@@ -13,7 +13,9 @@ The reference's ``MultiTaskLoss`` does not exist in its ``src/model/losses.py``;
 vector is an input of the model: a ``ClipEmotion`` (``--emotion egemaps``) gives every window the row of its clip's eGeMAPS
 emotion track that a live stream would hold when the window ends, gathered by start frame, so the step stays on the resident
 clip; ``--variant basic --emotion basic`` is the same at the ``basic`` shape (d_model 128, 4 heads, emotion_dim 9) with the track of
-nine prosodic values per row (``ClipEmotion(backend="basic")``); ``emotion_provider(audio) -> (B, emotion_dim)`` is handed window
+nine prosodic values per row (``ClipEmotion(backend="basic")``); ``--variant fast --emotion gemaps --emotion-context-window 10
+--emotion-update-interval 0.5`` is the reference's ``fast`` recipe, the track of the 62 GeMAPS functionals through a ``Linear(186, 256)``
+that goes into the checkpoint (``ClipEmotion(feature_set="GeMAPS")``); ``emotion_provider(audio) -> (B, emotion_dim)`` is handed window
 audio instead; without either the reference's own failure fallback is used (``randn * 0.1`` of the engine's emotion width,
 simplified_dual_stream_model.py:250-267), seeded per window for reproducibility.
 No hydra / TensorBoard dependency: plain argparse, metrics to the log.
@@ -308,6 +310,11 @@ class SequentialTrainer:
                                  "mel_sequence_length": self.engine.mel_sequence_length, "emotion_dim": self.engine.emotion_dim,
                                  "emotion_backend": self.clip_emotion.backend if self.clip_emotion is not None else
                                  ("provider" if self.emotion_provider is not None else "noise")}}
+        if self.clip_emotion is not None and getattr(self.clip_emotion, "feature_set", "eGeMAPSv02") == "GeMAPS":
+            # render_sequential --emotion gemaps reads both: the set, and the Linear(186, 256) the track went through
+            layer = self.clip_emotion.compression_layer
+            ckpt["model_config"]["emotion_feature_set"] = "GeMAPS"
+            ckpt["emotion_compression"] = {"weight": layer.weight.detach().cpu().clone(), "bias": layer.bias.detach().cpu().clone()}
         if self.record_emotion_timing:
             ckpt["model_config"].update(emotion_context_window=float(self.clip_emotion.context_window),
                                         emotion_update_interval=float(self.clip_emotion.update_interval))
@@ -364,12 +371,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loss-components", dest="loss_components", action="store_true",
                    help="validation reports the loss by component (LossTerms) and per-sequence loss / smoothness; with "
                         "--resident-clip the validation forward runs from the resident clip (Engine.forward_clip)")
-    p.add_argument("--emotion", choices=("noise", "egemaps", "basic"), default="noise",
+    p.add_argument("--emotion", choices=("noise", "egemaps", "basic", "gemaps"), default="noise",
                    help="the model's emotion input: noise = the reference's extraction-failure fallback (randn * 0.1 per window); "
                         "egemaps = each clip's eGeMAPS emotion track, computed once on the device and gathered by start frame "
                         "(ClipEmotion; implies resident batches, what a StreamEmotion serves at inference); basic = the same track "
                         "of nine prosodic values per row (ClipEmotion(backend='basic'), what StreamEmotion(backend='basic') serves; "
-                        "needs an emotion_dim of 9: --variant basic)")
+                        "needs an emotion_dim of 9: --variant basic); gemaps = the eGeMAPS track's kernels at the 62 functionals of "
+                        "GeMAPS through a Linear(186, 256) that is saved with the checkpoint (ClipEmotion(feature_set='GeMAPS'); with "
+                        "--variant fast --emotion-context-window 10 --emotion-update-interval 0.5 the reference's `fast` recipe)")
     p.add_argument("--emotion-context-window", dest="emotion_context_window", type=float, default=None, metavar="SECONDS",
                    help="seconds of audio behind a row of the emotion track (default 20.0).  configs/model/dual_stream.yaml: fast 10, "
                         "long_context 30.  Given, the eGeMAPS track takes windows beyond 20.5 s (ClipEmotion(long_windows=True), up to "
@@ -404,24 +413,37 @@ def parse_args(argv=None) -> argparse.Namespace:
     if args.emotion == "basic" and args.emotion_dim != 9:
         p.error(f"--emotion basic produces 9 values per window, the emotion_dim of --variant {args.variant} is {args.emotion_dim}: "
                 "use --variant basic")
-    if args.emotion == "egemaps" and args.emotion_dim != 256:
-        p.error(f"--emotion egemaps produces 256 values per window, the emotion_dim of --variant {args.variant} is {args.emotion_dim}")
+    if args.emotion in ("egemaps", "gemaps") and args.emotion_dim != 256:
+        p.error(f"--emotion {args.emotion} produces 256 values per window, the emotion_dim of --variant {args.variant} is {args.emotion_dim}")
     args.emotion_timing_given = args.emotion_context_window is not None or args.emotion_update_interval is not None
     if args.emotion_timing_given and args.emotion == "noise":
         p.error("--emotion-context-window / --emotion-update-interval shape the emotion track: use --emotion egemaps or basic")
     return args
 
 
+GEMAPS_COMPRESSION_SEED = 0   # the Linear(186, 256) of --emotion gemaps: torch's default initialisation under this seed, saved with the checkpoint
+
+
+def gemaps_compression_layer() -> torch.nn.Linear:
+    with torch.random.fork_rng(devices=[]):                # the caller's generator is left as it was
+        torch.manual_seed(GEMAPS_COMPRESSION_SEED)
+        return torch.nn.Linear(186, 256)
+
+
 def clip_emotion_from_args(args, device) -> Optional[ClipEmotion]:
     """The ClipEmotion of the command line: none for noise; without the two timing flags the 20.0 s / 0.3 s object as ever; with
-    either, that timing and -- eGeMAPS -- windows beyond 2048 frames (the basic back end takes them as it is)."""
-    if args.emotion not in ("egemaps", "basic"):
+    either, that timing and -- eGeMAPS -- windows beyond 2048 frames (the basic back end takes them as it is).  gemaps: the eGeMAPS
+    back end at the GeMAPS feature set, with a seeded Linear(186, 256)."""
+    if args.emotion not in ("egemaps", "basic", "gemaps"):
         return None
+    kw = dict(device=device, backend=args.emotion)
+    if args.emotion == "gemaps":
+        kw = dict(device=device, backend="egemaps", feature_set="GeMAPS", compression_layer=gemaps_compression_layer())
     if not args.emotion_timing_given:
-        return ClipEmotion(device=device, backend=args.emotion)
+        return ClipEmotion(**kw)
     return ClipEmotion(20.0 if args.emotion_context_window is None else args.emotion_context_window,
                        0.3 if args.emotion_update_interval is None else args.emotion_update_interval,
-                       device=device, backend=args.emotion, long_windows=args.emotion == "egemaps")
+                       long_windows=args.emotion != "basic", **kw)
 
 
 def main(argv=None):
@@ -436,7 +458,7 @@ def main(argv=None):
     eng.finalize(device)
     kw = dict(window_frames=args.window_frames, stride_frames=args.stride_frames, shuffle_files=False, loop_dataset=False,
               batch_size=args.batch_size, device=device, max_files=args.max_files, device_resample=args.device_resample)
-    track = args.emotion in ("egemaps", "basic")         # the track is read from the resident clip: every batch must name it
+    track = args.emotion in ("egemaps", "basic", "gemaps")       # the track is read from the resident clip: every batch must name it
     train = SequentialKoeMorphDataset(args.data_dir, resident_windows=args.resident_clip or track, **kw)
     val = SequentialKoeMorphDataset(args.val_dir, resident_windows=(args.resident_clip and args.loss_components) or track, **kw) \
         if args.val_dir else None

@@ -39,6 +39,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .egemaps_names import FEATURE_SET_DIMS, check_compression_shape, feature_set_code
 from .engine import Engine, MelConfig, _ptr, _stream_ptr
 
 
@@ -384,7 +385,7 @@ class LegacyStreamEngine:
 
 
 def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 0.3, sample_rate: int = 16000,
-                         backend: str = "egemaps", long_windows: bool = False) -> dict:
+                         backend: str = "egemaps", long_windows: bool = False, feature_set: str = "eGeMAPSv02") -> dict:
     """The arithmetic of the reference's OpenSMILEeGeMAPSExtractor in samples, which km_emotion_stream_create follows: the
     AudioBuffer of ``context_window + 2`` seconds (opensmile_extractor.py:245-248), the window ``get_window(context_window)`` returns
     once that much audio has arrived, the samples between two updates of a stream, the half second below which nothing is extracted
@@ -393,9 +394,13 @@ def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 
     ``backend="basic"`` (km_emotion_stream_create_basic): the same rings and rule; ``max_frames`` counts the 32 ms frames of the
     prosodic features, ``1 + window_len // 512``, and the window may hold up to 2**20 samples (65.5 s).
     ``long_windows=True`` (eGeMAPS only; km_emotion_stream_create_long): the window limit is the basic back end's, 2**20 samples or
-    6548 frames, instead of 2048 frames -- the reference's ``long_context`` variant has 30 s / 0.2 s, 2995 frames."""
+    6548 frames, instead of 2048 frames -- the reference's ``long_context`` variant has 30 s / 0.2 s, 2995 frames.
+    ``feature_set`` ("eGeMAPSv02" or "GeMAPS", eGeMAPS back end only) is checked and changes none of the five numbers: the feature
+    count is the object's ``feature_dim``."""
     if backend not in ("egemaps", "basic"):
         raise ValueError(f"backend must be 'egemaps' or 'basic', got {backend!r}")
+    if feature_set_code(feature_set) and backend != "egemaps":
+        raise ValueError("feature_set is the eGeMAPS back end's choice: the basic back end has its nine prosodic values")
     if long_windows and backend != "egemaps":
         raise ValueError("long_windows is the eGeMAPS back end's switch: the basic back end takes windows of 2**20 samples as it is")
     if sample_rate != 16000:
@@ -422,11 +427,13 @@ def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 
                 min_samples=int(0.5 * sample_rate), max_frames=max_frames)
 
 
-def _create_emotion_backend(backend: str, compression_layer: Optional[torch.nn.Module], device, create, set_compression):
+def _create_emotion_backend(backend: str, compression_layer: Optional[torch.nn.Module], device, create, set_compression,
+                            feature_set: str = "eGeMAPSv02"):
     """What ``StreamEmotion`` and ``ClipEmotion`` do with their back end: ``create(handle_ref)`` on the resolved device (``"cpu"``,
     ``"auto"`` and None mean the current GPU), and for eGeMAPS the ``Linear(264, 256)`` -- torch's default when absent -- copied
     into the object with ``set_compression(handle, w, b, stream)``.  Returns (device, handle, the layer kept, emotion_dim,
-    feature_dim); the basic back end keeps no layer and both widths are 9."""
+    feature_dim); the basic back end keeps no layer and both widths are 9.  ``feature_set="GeMAPS"``: 62 features and a
+    ``Linear(186, 256)``."""
     device = torch.device(device if device not in (None, "cpu", "auto") else "cuda")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -435,17 +442,17 @@ def _create_emotion_backend(backend: str, compression_layer: Optional[torch.nn.M
         with torch.cuda.device(device):
             check(create(C.byref(h)))
         return device, h, None, 9, 9
+    feature_dim = FEATURE_SET_DIMS[feature_set]
     if compression_layer is None:
-        compression_layer = torch.nn.Linear(264, 256)
-    if tuple(compression_layer.weight.shape) != (256, 264):
-        raise ValueError(f"compression_layer must be a Linear(264, 256), got weight {tuple(compression_layer.weight.shape)}")
+        compression_layer = torch.nn.Linear(3 * feature_dim, 256)
+    check_compression_shape(compression_layer, feature_set)
     with torch.cuda.device(device):
         check(create(C.byref(h)))
         w = compression_layer.weight.detach().to(device, torch.float32).contiguous()
         b = compression_layer.bias.detach().to(device, torch.float32).contiguous()
         check(set_compression(h, _ptr(w), _ptr(b), _stream_ptr(device)))
         torch.cuda.current_stream(device).synchronize()                   # w and b may go once the copy is done
-    return device, h, compression_layer, 256, 88
+    return device, h, compression_layer, 256, feature_dim
 
 
 class StreamEmotion:
@@ -468,13 +475,20 @@ class StreamEmotion:
 
     ``long_windows=True`` (km_emotion_stream_create_long): eGeMAPS windows of up to 2**20 samples (65.5 s) instead of 2048 frames
     (20.5 s) -- ``StreamEmotion(n, 30.0, 0.2, long_windows=True)`` is the reference's ``long_context`` variant.  Every call is
-    unchanged; an object whose window has at most 2048 frames is the plain object."""
+    unchanged; an object whose window has at most 2048 frames is the plain object.
+
+    ``feature_set="GeMAPS"`` (km_emotion_stream_create_set): the 62 functionals of GeMAPS instead of the 88 --
+    ``StreamEmotion(n, 10.0, 0.5, feature_set="GeMAPS")`` is the reference's ``fast`` variant.  ``features`` is ``(n_streams, 62)``,
+    ``slots`` ``(n_streams, 2, 62)``, the layer a ``Linear(186, 256)`` (a deliberate deviation: the reference's hard-coded
+    ``Linear(264, 256)`` never compresses GeMAPS features).  Feature j is feature ``GEMAPS_COLUMNS[j]`` of the eGeMAPS object on the
+    same pushes, bit for bit; parity with openSMILE's own GeMAPSv01b is UNPINNED."""
 
     def __init__(self, n_streams: int, context_window: float = 20.0, update_interval: float = 0.3, max_updates: Optional[int] = None,
                  compression_layer: Optional[torch.nn.Module] = None, device="cuda", backend: str = "egemaps",
-                 long_windows: bool = False):
-        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend, long_windows=long_windows)
-        self.backend, self.long_windows = backend, long_windows
+                 long_windows: bool = False, feature_set: str = "eGeMAPSv02"):
+        self.shape = emotion_stream_shape(context_window, update_interval, backend=backend, long_windows=long_windows,
+                                          feature_set=feature_set)
+        self.backend, self.long_windows, self.feature_set = backend, long_windows, feature_set
         if backend == "basic" and compression_layer is not None:
             raise ValueError("the basic back end has no compression layer: its nine features are the emotion input as they are")
         if max_updates is None:
@@ -489,9 +503,12 @@ class StreamEmotion:
         self._lib = _lib.load()
         create = (self._lib.km_emotion_stream_create_basic if backend == "basic" else
                   self._lib.km_emotion_stream_create_long if long_windows else self._lib.km_emotion_stream_create)
+        make = lambda h: create(h, n_streams, context_window, update_interval, max_updates)
+        if feature_set_code(feature_set):
+            make = lambda h: self._lib.km_emotion_stream_create_set(h, n_streams, context_window, update_interval, max_updates,
+                                                                    feature_set_code(feature_set), 1 if long_windows else 0)
         self.device, self._h, self.compression_layer, self.emotion_dim, self.feature_dim = _create_emotion_backend(
-            backend, compression_layer, device, lambda h: create(h, n_streams, context_window, update_interval, max_updates),
-            self._lib.km_emotion_stream_set_compression)
+            backend, compression_layer, device, make, self._lib.km_emotion_stream_set_compression, feature_set)
         self.emotion = torch.zeros(n_streams, self.emotion_dim, device=self.device)
         self.valid = torch.zeros(n_streams, dtype=torch.uint8, device=self.device)
         self.updated = torch.zeros(n_streams, dtype=torch.uint8, device=self.device)
@@ -540,8 +557,8 @@ class StreamEmotion:
         """(n_streams, 2, 88): the 300 ms and 600 ms window slots, i.e. the first features of each stream's current life; a copy."""
         if self.backend == "basic":
             raise AttributeError("the basic back end has no window slots")
-        feats = torch.empty(self.n_streams, 88, device=self.device)
-        out = torch.empty(self.n_streams, 2, 88, device=self.device)
+        feats = torch.empty(self.n_streams, self.feature_dim, device=self.device)
+        out = torch.empty(self.n_streams, 2, self.feature_dim, device=self.device)
         check(self._lib.km_emotion_stream_features(self._h, _ptr(feats), _ptr(out), _stream_ptr(self.device)))
         return out
 

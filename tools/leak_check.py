@@ -54,6 +54,14 @@ def cycle(i):
     lce.close()
     lse = StreamEmotion(1, 21.0, 10.0, long_windows=True)
     lse.push(long_clip[None]); lse.update(); lse.close()
+    # one GeMAPS stream update and one GeMAPS clip track (feature_set="GeMAPS": 62 functionals, a Linear(186, 256))
+    gse = StreamEmotion(2, 1.0, 0.1, feature_set="GeMAPS")
+    gse.push(audio[:2, :16000].contiguous()); gse.update(); gse.close()
+    gce = ClipEmotion(1.0, 0.1, max_slots=4, feature_set="GeMAPS")
+    gtrack, _ = gce.build(clip)
+    gce.rows(gtrack, clip.shape[0], torch.tensor([0, 1, 2, 9], dtype=torch.int32, device="cuda"), 266, 32)
+    gce.close()
+    del gse, gce, gtrack
     del ctr, c, clip, ce, track, long_clip, lce, ltrack, lse
     m = KoeMorphModel(d_model=64, d_query=64, num_heads=4, num_encoder_layers=1, num_attention_layers=1, decoder_hidden_dim=32, emotion_dim=8).cuda().eval()
     with torch.no_grad():
