@@ -918,6 +918,33 @@ int km_emotion_clip_create_set(void** ec, double context_window_s, double update
                                int32_t long_windows);
 int km_emotion_stream_feature_width(void* es);
 int km_emotion_clip_feature_width(void* ec);
+/* ---- eGeMAPS low-level descriptors per frame: the reference extractor's feature_level="LowLevelDescriptors"
+ * (src/features/opensmile_extractor.py:220-225), and a per-frame emotion input on the model's frame grid ----
+ * The 25 smoothed contours behind the 88 functionals, one row per frame, from the frame records of the calls above: columns 0-9 the
+ * 3-frame average of loudness, alpha ratio, Hammarberg index, the two spectral slopes, spectral flux and MFCC 1-4; column 10 the
+ * semitone (from 27.5 Hz) of the non-zero-smoothed F0, 0 in unvoiced frames; columns 11-24 jitter, shimmer, HNR, H1-H2, H1-A3 and
+ * frequency, bandwidth, amplitude of F1, F2, F3, masked to voiced frames and smoothed over non-zero values, 0 in unvoiced frames.
+ * GeMAPS: the 18 columns left without 5-9, 20 and 23.  The float32 statements are those of the functionals kernel.  PARITY of names,
+ * order and values with openSMILE's own LowLevelDescriptors level is UNPINNED, as for the whole eGeMAPS back end.
+ * Frame grid: fps == 0 gives the native rows, one per 10 ms frame.  Otherwise fps must be finite and within 1 .. 400
+ * (KM_ERR_INVALID_ARG), there are int(L / 16000 * fps) rows (float64, in that order: the mel extractor's frame count), and row k sits
+ * at frame coordinate p = k * 100.0 / fps, j = floor(p), w = p - j: the last frame for j >= nf - 1, frame j for w == 0, otherwise
+ * fmaf((float)w, b - a, a) between frames j and j + 1 -- but columns 10-24 blend only where both are non-zero and else take the nearer
+ * frame's value (the earlier at w == 0.5): a descriptor is never mixed with an unvoiced frame's 0.
+ *   km_egemaps_lld_width          25 / 18, -1 for an unknown set
+ *   km_egemaps_lld_frames         rows of the grid for a window of L samples; fps == 0: km_egemaps_num_frames(L); -1 for a bad fps
+ *   km_egemaps_llds               audio_dev (B, L) -> out_dev (B, rows, width).  The checks, limits and refusal texts of
+ *                                 km_egemaps_functionals_set under this name, its workspace (km_egemaps_workspace_floats; records by
+ *                                 km_egemaps_records) and its launches up to the records, then one launch of the descriptor kernel.
+ *                                 Launches only: no allocation, no synchronisation, capturable.  A grid of 0 rows launches nothing.
+ *   km_egemaps_llds_from_records  the descriptor kernel alone on caller-written records rec_dev (B, nf, 36), 1 <= nf <= 6548 (tests);
+ *                                 L_for_grid lays the grid (ignored with fps == 0, at most 2^20) */
+int km_egemaps_lld_width(int32_t feature_set);
+int64_t km_egemaps_lld_frames(int64_t L, double fps);
+int km_egemaps_llds(void* plan, int32_t feature_set, int32_t long_windows, const float* audio_dev, int64_t B, int64_t L, int32_t normalize,
+                    float* work_dev, int64_t work_floats, double fps, float* out_dev, void* stream);
+int km_egemaps_llds_from_records(int32_t feature_set, const float* rec_dev, int64_t B, int64_t nf, int64_t L_for_grid, double fps,
+                                 float* out_dev, void* stream);
 
 /* ---- evaluation metrics: a streaming accumulator in device memory ------------------------------------------------
  * Replaces BlendshapeMetrics (src/model/losses.py:421-521) and compute_lip_sync_metrics (:524-583).  The reference

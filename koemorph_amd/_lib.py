@@ -245,6 +245,10 @@ SIGNATURES = {
     "km_emotion_clip_create_set": (C.c_int, [C.POINTER(_p), C.c_double, C.c_double, _i64, _i32, _i32]),
     "km_emotion_stream_feature_width": (C.c_int, [_p]),
     "km_emotion_clip_feature_width": (C.c_int, [_p]),
+    "km_egemaps_lld_width": (C.c_int, [_i32]),
+    "km_egemaps_lld_frames": (_i64, [_i64, C.c_double]),
+    "km_egemaps_llds": (C.c_int, [_p, _i32, _i32, _p, _i64, _i64, _i32, _p, _i64, C.c_double, _p, _p]),
+    "km_egemaps_llds_from_records": (C.c_int, [_i32, _p, _i64, _i64, _i64, C.c_double, _p, _p]),
     "km_emotion_clip_width": (C.c_int, [_p]),
     "km_emotion_clip_destroy": (C.c_int, [_p]),
     "km_emotion_clip_set_compression": (C.c_int, [_p, _p, _p, _p]),

@@ -33,6 +33,7 @@
 #include "km_context.h"
 #include "km_egemaps_dev.h"
 #include "km_egemaps_ragged.h"
+#include "km_egemaps_lld.h"
 #include "km_egemaps_window.h"
 
 namespace km {
@@ -728,8 +729,11 @@ int64_t km_egemaps_workspace_floats(int64_t B, int64_t L) {
 // km_egemaps_functionals and km_egemaps_functionals_long (`who` is the name the texts carry).  The latter takes windows of up to 2^20
 // samples: beyond 2048 frames the two per-window kernels run at their long tier between the same per-frame kernels; up to 2048
 // frames it launches what the former launches
-static int egm_functionals(const char* who, int feature_set, bool long_windows, void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize,
-                           float* work_dev, int64_t work_floats, float* out_dev, void* stream) {
+// Its checks and its launches up to the frame records (peak, frame, track, voiced) are egm_window_records, which km_egemaps_llds shares:
+// *rec_out is where the records of the B windows lie in the workspace, *nf_out their frame count, *long_tier_out the per-window tier
+static int egm_window_records(const char* who, int feature_set, bool long_windows, void* plan, const float* audio_dev, int64_t B, int64_t L,
+                              int32_t normalize, float* work_dev, int64_t work_floats, const float* out_dev, void* stream, float** rec_out,
+                              int64_t* nf_out, bool* long_tier_out, bool launch = true) {
     using namespace egm;
     if (!plan || !audio_dev || !work_dev || !out_dev || B <= 0 || L <= 0) return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
     const int64_t nf = km_egemaps_num_frames(L);
@@ -740,6 +744,7 @@ static int egm_functionals(const char* who, int feature_set, bool long_windows, 
         return fail(KM_ERR_UNSUPPORTED, "%s: %lld frames per window, at most %d (20.5 s)", who, (long long)nf, ShortTier::MAXF);
     if (work_floats < km_egemaps_workspace_floats(B, L)) return fail(KM_ERR_WORKSPACE, "%s: workspace too small", who);
     if (B > 65535) return fail(KM_ERR_UNSUPPORTED, "%s: at most 65535 windows per call", who);
+    if (!launch) return KM_OK;                     // km_egemaps_llds with an empty frame grid: the checks alone
     const bool long_tier = nf > ShortTier::MAXF;
     EgmPlan* p = static_cast<EgmPlan*>(plan);
     hipStream_t st = (hipStream_t)stream;
@@ -754,7 +759,18 @@ static int egm_functionals(const char* who, int feature_set, bool long_windows, 
     hipLaunchKernelGGL(frame_kernel, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
     if (const int rc = egm_track(rec, (int)nf, (int)nf, nullptr, (int)B, long_tier, st)) return rc;
     hipLaunchKernelGGL(egm_voiced_kernel<false>, dim3((unsigned)nf, (unsigned)B), dim3(256), 0, st, a);
-    return egm_functional(rec, (int)nf, (int)nf, nullptr, (int)B, out_dev, long_tier, st, feature_set);
+    HIP_TRY(hipGetLastError());
+    *rec_out = rec; *nf_out = nf; *long_tier_out = long_tier;
+    return KM_OK;
+}
+
+static int egm_functionals(const char* who, int feature_set, bool long_windows, void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize,
+                           float* work_dev, int64_t work_floats, float* out_dev, void* stream) {
+    float* rec = nullptr; int64_t nf = 0; bool long_tier = false;
+    if (const int rc = egm_window_records(who, feature_set, long_windows, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev, stream, &rec,
+                                          &nf, &long_tier))
+        return rc;
+    return egm_functional(rec, (int)nf, (int)nf, nullptr, (int)B, out_dev, long_tier, (hipStream_t)stream, feature_set);
 }
 
 int km_egemaps_functionals(void* plan, const float* audio_dev, int64_t B, int64_t L, int32_t normalize, float* work_dev,
@@ -774,6 +790,23 @@ int km_egemaps_functionals_set(void* plan, int32_t feature_set, int32_t long_win
         return fail(KM_ERR_INVALID_ARG, "km_egemaps_functionals_set: feature set %d, 0 (eGeMAPS) or 1 (GeMAPS)", (int)feature_set);
     return egm_functionals("km_egemaps_functionals_set", feature_set, long_windows != 0, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev,
                            stream);
+}
+
+// The low-level descriptors per frame, out_dev (B, km_egemaps_lld_frames(L, fps), km_egemaps_lld_width(feature_set)): the checks and
+// the launches of km_egemaps_functionals_set up to the records, then egm_lld_kernel where that has the functionals (km_egemaps_lld.hip)
+int km_egemaps_llds(void* plan, int32_t feature_set, int32_t long_windows, const float* audio_dev, int64_t B, int64_t L, int32_t normalize,
+                    float* work_dev, int64_t work_floats, double fps, float* out_dev, void* stream) {
+    const char* who = "km_egemaps_llds";
+    if (!egm::set_known(feature_set)) return fail(KM_ERR_INVALID_ARG, "%s: feature set %d, 0 (eGeMAPS) or 1 (GeMAPS)", who, (int)feature_set);
+    if (fps != 0.0 && egm_lld_frames(0, fps) < 0)
+        return fail(KM_ERR_INVALID_ARG, "%s: fps %g, finite and within 1 .. 400 (0: the native 100 Hz)", who, fps);
+    const int64_t T_out = egm_lld_frames(L, fps);
+    float* rec = nullptr; int64_t nf = 0; bool long_tier = false;
+    if (const int rc = egm_window_records(who, feature_set, long_windows != 0, plan, audio_dev, B, L, normalize, work_dev, work_floats, out_dev, stream,
+                                          &rec, &nf, &long_tier, T_out != 0))
+        return rc;
+    if (T_out == 0) return KM_OK;                  // less than one row of the grid: nothing was launched
+    return egm_lld(rec, (int)nf, (int)nf, (int)B, T_out, fps, out_dev, (hipStream_t)stream, feature_set);
 }
 
 // per-frame records of the most recent call on this workspace, for the tests: (B, nf, 36) floats

@@ -27,7 +27,7 @@ import numpy as np
 
 from .. import _lib
 from .._lib import check
-from ..egemaps_names import FEATURE_SET_DIMS, check_compression_shape, feature_set_code
+from ..egemaps_names import FEATURE_SET_DIMS, LLD_DIMS, check_compression_shape, feature_set_code, lld_fps_value
 
 logger = logging.getLogger(__name__)
 
@@ -156,6 +156,52 @@ class EGeMAPSEngine:
                 check(call(self._plan, *args))
         return out
 
+    def llds(self, audio, normalize: bool = True, feature_set: str = "eGeMAPSv02", long_windows: bool = False, fps=None):
+        """audio (B, L) fp32 on the device -> (B, T, 25) low-level descriptors per frame ((B, T, 18) for GeMAPS; the columns
+        egemaps_names.LLD_NAMES): the smoothed contours behind the functionals, from the same frame records (km_egemaps_llds).
+        ``fps=None``: the T native 10 ms frames.  Otherwise T = int(L / 16000 * fps) rows on the frame grid of a model running at
+        ``fps`` (1 .. 400), linearly interpolated -- never between a voiced descriptor and an unvoiced frame's 0.  Windows beyond
+        2048 frames need ``long_windows`` as for ``functionals``.  A grid of 0 rows returns an empty tensor and launches nothing."""
+        torch = self._torch
+        code = feature_set_code(feature_set)
+        rate = lld_fps_value(fps)
+        audio = audio.to(self.device, torch.float32).contiguous()
+        if audio.dim() != 2:
+            raise ValueError(f"Expected 2D audio (B, L), got {audio.dim()}D")
+        B, L = audio.shape
+        T = int(self._lib.km_egemaps_lld_frames(L, rate))
+        if T == 0 and self.num_frames(L) >= 1:
+            return torch.empty(B, 0, LLD_DIMS[feature_set], device=self.device)
+        need = int(self._lib.km_egemaps_workspace_floats(B, L))
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, device=self.device)
+        self._work_for = (B, L)
+        out = torch.empty(B, max(T, 1), LLD_DIMS[feature_set], device=self.device)[:, :T]     # a row even for a window the call refuses
+        with torch.cuda.device(self.device):
+            check(self._lib.km_egemaps_llds(self._plan, code, 1 if long_windows else 0, audio.data_ptr(), B, L, 1 if normalize else 0,
+                                            self._work.data_ptr(), self._work.numel(), rate, out.data_ptr(),
+                                            torch.cuda.current_stream(self.device).cuda_stream))
+        return out
+
+    def llds_from_records(self, rec, feature_set: str = "eGeMAPSv02", fps=None, length=None):
+        """records (B, frames, 36) -> (B, T, 25 | 18): the descriptor kernel alone, at any frame count up to 6548 (tests).  ``length``
+        is the window's sample count, which lays the frame grid: required when ``fps`` is given."""
+        torch = self._torch
+        code = feature_set_code(feature_set)
+        rate = lld_fps_value(fps)
+        if fps is not None and length is None:
+            raise ValueError("llds_from_records: `length` (the window's sample count) is required when fps is given")
+        rec = self._records_on_device(rec)
+        B, nf, _ = rec.shape
+        T = nf if fps is None else int(self._lib.km_egemaps_lld_frames(int(length), rate))
+        out = torch.empty(B, max(T, 0), LLD_DIMS[feature_set], device=self.device)
+        if T == 0:
+            return out
+        with torch.cuda.device(self.device):
+            check(self._lib.km_egemaps_llds_from_records(code, rec.data_ptr(), B, nf, 0 if fps is None else int(length), rate, out.data_ptr(),
+                                                         torch.cuda.current_stream(self.device).cuda_stream))
+        return out
+
     def records(self) -> np.ndarray:
         """Per-frame low-level descriptors of the most recent call, (B, frames, 36) -- see km_egemaps.hip (tests)."""
         B, L = self._work_for
@@ -216,8 +262,12 @@ class OpenSMILEeGeMAPSExtractor:
         if update_interval > context_window:
             raise ValueError("Update interval cannot be larger than context window")
         feature_set_code(feature_set)                        # "eGeMAPSv02" or "GeMAPS" (:214-215); "Unsupported feature set: X" otherwise
-        if feature_level != "Functionals":
+        if feature_level not in ("Functionals", "LowLevelDescriptors"):
             raise ValueError(f"Unsupported feature level: {feature_level}")
+        if feature_level == "LowLevelDescriptors" and use_concatenation:
+            # a deliberate deviation: the reference accepts the pair and fails later, in the Linear(264, 256) of three windows of 88
+            raise ValueError("feature_level='LowLevelDescriptors' cannot be combined with use_concatenation: the compression layer "
+                             "takes three windows of functionals")
         self.sample_rate, self.context_window, self.update_interval = sample_rate, context_window, update_interval
         self.enable_caching = enable_caching
         self.device = device
@@ -226,7 +276,9 @@ class OpenSMILEeGeMAPSExtractor:
         self.long_windows = long_windows                     # windows beyond 2048 frames (20.5 s): the long_context variant's 30 s
         self.engine = EGeMAPSEngine(device)
         self.feature_set = feature_set
-        self.feature_dim = FEATURE_SET_DIMS[feature_set]     # 88, or the 62 of GeMAPS
+        self.feature_level = feature_level
+        # 88, or the 62 of GeMAPS; at the descriptor level the width of a frame's row, 25 or 18
+        self.feature_dim = LLD_DIMS[feature_set] if feature_level == "LowLevelDescriptors" else FEATURE_SET_DIMS[feature_set]
         self.audio_buffer = AudioBuffer(max_duration=context_window + 2.0, sample_rate=sample_rate)
         self.last_update_time = 0.0
         self.current_features: Optional[np.ndarray] = None
@@ -244,21 +296,27 @@ class OpenSMILEeGeMAPSExtractor:
         self.feature_cache = {} if enable_caching else None
 
     # ---- the part openSMILE did -------------------------------------------------------------------------------------
-    def extract_batch(self, audio, normalize: bool = True):
-        """(B, L) windows (numpy or tensor) -> (B, 88) tensor on the device ((B, 62) for GeMAPS): every window in one call."""
+    def extract_batch(self, audio, normalize: bool = True, fps=None):
+        """(B, L) windows (numpy or tensor) -> (B, 88) tensor on the device ((B, 62) for GeMAPS): every window in one call.
+        feature_level="LowLevelDescriptors": (B, T, 25) ((B, T, 18)), a row per 10 ms frame, or per frame of a model at ``fps``."""
         import torch
         if isinstance(audio, np.ndarray):
             audio = torch.from_numpy(np.ascontiguousarray(audio, np.float32))
+        if self.feature_level == "LowLevelDescriptors":
+            return self.engine.llds(audio, normalize, feature_set=self.feature_set, long_windows=self.long_windows, fps=fps)
+        if fps is not None:
+            raise ValueError("fps applies to feature_level='LowLevelDescriptors' only")
         return self.engine.functionals(audio, normalize, long_windows=self.long_windows, feature_set=self.feature_set)
 
     def _extract_features_from_audio(self, audio: np.ndarray) -> Optional[np.ndarray]:
-        """One window -> (88,) float32 (reference :427-454: float32, peak normalisation, NaN / Inf -> 0)."""
+        """One window -> (88,) float32 (reference :427-454: float32, peak normalisation, NaN / Inf -> 0).  At the descriptor level
+        the (T, W) rows flattened to (T * W,), as the reference's ``.values.flatten()`` gives them."""
         try:
             audio = np.asarray(audio, np.float32)
             if self.engine.num_frames(len(audio)) < 1:
                 logger.warning("Window shorter than one analysis frame")
                 return None
-            feats = self.extract_batch(audio[None, :], normalize=True)[0].cpu().numpy()
+            feats = self.extract_batch(audio[None, :], normalize=True)[0].cpu().numpy().reshape(-1)
             if np.any(np.isnan(feats)) or np.any(np.isinf(feats)):
                 logger.warning("Invalid features detected (NaN/Inf)")
                 feats = np.nan_to_num(feats, nan=0.0, posinf=0.0, neginf=0.0)
@@ -419,7 +477,9 @@ class OpenSMILEeGeMAPSExtractor:
         return self.compression_layer
 
     def get_feature_names(self) -> List[str]:
-        from ..egemaps_names import FEATURE_NAMES, GEMAPS_FEATURE_NAMES
+        from ..egemaps_names import FEATURE_NAMES, GEMAPS_FEATURE_NAMES, GEMAPS_LLD_NAMES, LLD_NAMES
+        if self.feature_level == "LowLevelDescriptors":
+            return list(GEMAPS_LLD_NAMES if self.feature_set == "GeMAPS" else LLD_NAMES)
         return list(GEMAPS_FEATURE_NAMES if self.feature_set == "GeMAPS" else FEATURE_NAMES)
 
     def get_stats(self) -> Dict[str, object]:
