@@ -549,6 +549,39 @@ int km_koemorph_forward(km_handle h, const float* mel_dev, const float* emotion_
                         const uint8_t* audio_mask_dev, const float* prev_dev, float* smoother_state_dev,
                         int32_t apply_constraints, float* out_dev, float* raw_dev, float* attn_dev, void* stream);
 
+/* ---- KoeMorphModel: autoregressive rollout of whole clips on the device ---------------------------------
+ * The model is autoregressive: frame i's output is frame i + 1's prev_blendshapes, and the smoother carries state.  One call renders
+ * frames first_frame .. F - 1 of B clips from their per-frame rows mel_dev (B, F, mel_dim) and emotion_dev (B, F, emotion_dim)
+ * (same F for every clip).  THE LAW: for i = first_frame .. F - 1 in order, T_i = min(i + 1, T), row i - first_frame of out_dev /
+ * raw_dev (B, F - first_frame, 52) is km_koemorph_forward on the dense window of rows i - T_i + 1 .. i of every clip, B, T_i, no
+ * audio mask, prev = the previous rendered frame's out (prev0_dev (B, 52) for i == first_frame; NULL: that one frame runs without
+ * conditioning), smoother_state_dev (km_koemorph_forward's layouts; NULL = no smoothing) updated by every frame in turn and
+ * left as the loop leaves it.  A clip's first T - 1 frames see SHORTER windows, not padded ones (the causal mask lets query q
+ * see keys 0 .. q: a left-padded window would leave query 0 without a key).  first_frame > 0 continues a stream: pass the last
+ * T - 1 rows already rendered as context, the previous call's last out as prev0_dev and the state; two calls give the bits of one.
+ *   km_koemorph_rollout_reserve  workspace (a buffer group of its own; km_koemorph_forward's workspace grows to max_clips x
+ *                        max_context as well) for calls of up to max_clips clips and T <= max_context, and the chunk length of
+ *                        route 1.  Grow-only; it allocates, so not inside a stream capture
+ *   km_koemorph_rollout  route 1 (the width of the fused kernels, T <= 32, option "kmm_no_fuse" off, 16-byte aligned row pointers):
+ *                        frames with a short window (i < T - 1) as four launches each (window gather, encoder, decode, row scatter);
+ *                        the others in chunks of chunk_frames as three launches per chunk: a gather of the chunk's B x frames
+ *                        overlapping windows into a dense staging buffer, ONE encoder launch over all of them, ONE
+ *                        kmmf_rollout_kernel launch (a workgroup per clip walks the serial chain with prev and the state in LDS).
+ *                        Route 0 (any other width, T > 32, emotion_dim % 16 != 0, "kmm_no_fuse", misaligned rows): per frame a
+ *                        window gather, the launches of km_koemorph_forward and a row scatter.  Launches on `stream` only: capturable.
+ *                        KM_ERR_INVALID_ARG (the text names the entry point and the value): NULL mel_dev / emotion_dev / out_dev,
+ *                        B, F or T < 1, first_frame outside 0 .. F - 1, a handle of another kind; KM_ERR_WORKSPACE: not reserved,
+ *                        or reserved for fewer clips or a shorter context
+ *   km_koemorph_rollout_plan  host only (after km_finalize_host), the function the call itself runs: out[0] route, out[1] chunks
+ *                        (route 1), out[2] rendered frames with a short window, out[3] launches of the call (route 0 on the chain:
+ *                        counted with prev0 given; without it the first frame makes two fewer), out[4] workspace floats of the
+ *                        rollout group.  With the reserved chunk_frames, or 256 before any reserve; row pointers taken as aligned */
+int km_koemorph_rollout_reserve(km_handle h, int64_t max_clips, int64_t max_context, int64_t chunk_frames);
+int km_koemorph_rollout(km_handle h, const float* mel_dev, const float* emotion_dev, int64_t B, int64_t F, int64_t T, int64_t first_frame,
+                        const float* prev0_dev, float* smoother_state_dev, int32_t apply_constraints, float* out_dev, float* raw_dev,
+                        void* stream);
+int km_koemorph_rollout_plan(km_handle h, int64_t B, int64_t F, int64_t T, int64_t first_frame, int64_t out[5]);
+
 /* ---- streaming: many concurrent speaker streams, state resident on the device -------------------------
  * Replaces, for all streams of this GPU at once, MelAudioBuffer.add_audio_frame / get_current_audio
  * (src/features/mel_sliding_window.py:70-140), MelSlidingWindowExtractor.process_audio_frame (:252-324) and

@@ -14,6 +14,19 @@
 
 using namespace km;
 
+namespace km {
+
+int reserve_koemorph(Context* c, int64_t max_batch, int64_t max_frames) {
+    if (max_batch <= c->kmm_batch && max_frames <= c->kmm_frames) return KM_OK;
+    const int64_t Bm = max_batch > c->kmm_batch ? max_batch : c->kmm_batch, Tm = max_frames > c->kmm_frames ? max_frames : c->kmm_frames;
+    c->kmm_batch = c->kmm_frames = 0;
+    if (int rc = c->ws.generic.alloc(Bm * koemorph_ws_floats(c, Tm), "km_koemorph_reserve")) return rc;
+    c->kmm_batch = Bm; c->kmm_frames = Tm;
+    return KM_OK;
+}
+
+}  // namespace km
+
 extern "C" {
 
 
@@ -207,12 +220,7 @@ int km_koemorph_reserve(km_handle h, int64_t max_batch, int64_t max_frames) {
     Context* c = h;
     if (c->kind != 2) return fail(KM_ERR_INVALID_ARG, "not a KoeMorphModel handle (km_koemorph_create)");
     if (max_batch <= 0 || max_frames <= 0) return fail(KM_ERR_INVALID_ARG, "km_koemorph_reserve: bad argument");
-    if (max_batch <= c->kmm_batch && max_frames <= c->kmm_frames) return KM_OK;
-    const int64_t Bm = max_batch > c->kmm_batch ? max_batch : c->kmm_batch, Tm = max_frames > c->kmm_frames ? max_frames : c->kmm_frames;
-    c->kmm_batch = c->kmm_frames = 0;
-    if (int rc = c->ws.generic.alloc(Bm * koemorph_ws_floats(c, Tm), "km_koemorph_reserve")) return rc;
-    c->kmm_batch = Bm; c->kmm_frames = Tm;
-    return KM_OK;
+    return reserve_koemorph(c, max_batch, max_frames);
 }
 
 int km_koemorph_forward(km_handle h, const float* mel_dev, const float* emotion_dev, int64_t B, int64_t T,

@@ -213,6 +213,12 @@ struct ClipAsmBufs {
     DevBuf<float> edge; DevBuf<unsigned> emax;   // (2 windows, 2 E, NK) the snippets' frames and their per-row maxima
 };
 
+// km_koemorph_rollout_reserve: workspace of km_koemorph_rollout (km_koemorph_rollout.hip carves it), one allocation
+struct RolloutBufs {
+    int64_t clips = 0, context = 0, chunk = 0;   // what it was sized for; clips == 0 until reserved
+    DevBuf<float> ws;
+};
+
 // two-deep pipeline across calls (km_forward_audio_pipelined)
 struct PipeSlot {
     DevBuf<float> melpow; DevBuf<unsigned> melmax; DevBuf<float> zemo;
@@ -261,6 +267,7 @@ struct Context {
     SeqBufs seq;                                 // km_sequence_forward*, km_forward_clip
     ClipAsmBufs clipasm;                         // km_train_step_clip / km_forward_clip with option clip_assemble
     Pipeline pipe;                               // km_forward_audio_pipelined
+    RolloutBufs ro;                              // kind 2: km_koemorph_rollout
     bool stage_timing = false;
     DevEvent stage_ev[6];                        // emo b/e, mel e, core b/e
     bool melmax_dirty = true;      // ws.melmax may hold stale maxima (see launch_mel_power)
@@ -371,6 +378,7 @@ int64_t legacy_ws_floats(Context* c, int64_t frames);
 int finalize_host_legacy(Context* c);
 int finalize_host_koemorph(Context* c);
 int64_t koemorph_ws_floats(Context* c, int64_t T);
+int reserve_koemorph(Context* c, int64_t max_batch, int64_t max_frames);     // km_api.hip: what km_koemorph_reserve does behind its guards
 int launch_koemorph(Context* c, const float* mel, const float* emo, int64_t B, int64_t T, const unsigned char* kvalid, const float* prev,
                     float* state, int apply_constraints, float* out, float* raw, float* attn, void* stream);
 struct LegacyPowSrc { const float* melpow; unsigned* melmax; const LogParams* lp; };      // the front end's power-mel as the legacy model's input

@@ -8,6 +8,8 @@
 //                         transformer layer with the rows resident in LDS.
 //   kmmf_decode_kernel    average of the two encodings, query embeddings (+ conditioning net), every cross-attention layer,
 //                         BlendshapeDecoder and the output tail: one workgroup per window, the 52 query rows resident in LDS.
+//   kmmf_rollout_kernel   the decode kernel's body (decode_window, shared) in a loop over consecutive frames of a clip, one workgroup
+//                         per clip, the previous frame's output and the smoother state resident in LDS (km_koemorph_rollout).
 //
 // All products are exact-fp32 v_mfma_f32_16x16x4_f32.  Activations are the A operand out of an LDS image [row][264] (one
 // ds_read_b128 = the operand of four MFMAs, stride 264 = 8 mod 64 dwords: conflict-free for the instruction's lane groups);
@@ -624,19 +626,23 @@ struct DecArgs {
     KmmTail tail;
 };
 
-__global__ __launch_bounds__(512) void kmmf_decode_kernel(DecArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+// One window, start to finish: the body of kmmf_decode_kernel and of every iteration of kmmf_rollout_kernel.
+//   b: the window's batch element for the key padding mask and the attention maps; row0: its first row in a.xm / a.xe;
+//   prev: ITS 52 previous coefficients or null (a.prev is not read here); tail / tb: the output tail's pointers and the
+//   element they are indexed with (km_kmm_tail.h).  Ends behind the tail's last store, with no barrier after it.
+__device__ __forceinline__ void decode_window(const DecArgs& a, int b, int64_t row0, const float* prev, const KmmTail& tail, int64_t tb,
+                                              float* smem, const int tid) {
     float* X = smem;
     float* Y = smem + QIMG;
     float* A = smem + 2 * QIMG;
     float* red = A + TMAX * XS;
     float* ys = red + RED;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, j = lane & 15;
-    const int b = blockIdx.x, T = a.T;
+    const int T = a.T;
     const int col0 = 32 * wave;
 
-    const unsigned kmask = (unsigned)__ballot(lane < T && (!a.kvalid || a.kvalid[(int64_t)b * T + lane]));
+    const unsigned kmask = (unsigned)__ballot(lane < T && (!a.kvalid || a.kvalid[row0 + lane]));
 #ifdef KM_KMMF_STAMP
     unsigned st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long st_last = __builtin_readcyclecounter();
@@ -646,19 +652,19 @@ __global__ __launch_bounds__(512) void kmmf_decode_kernel(DecArgs a) {
         const int t = i >> 6, c4 = i & 63;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (t < T) {
-            const float4 m = *reinterpret_cast<const float4*>(a.xm + ((int64_t)b * T + t) * D + 4 * c4);
-            const float4 e = *reinterpret_cast<const float4*>(a.xe + ((int64_t)b * T + t) * D + 4 * c4);
+            const float4 m = *reinterpret_cast<const float4*>(a.xm + (row0 + t) * D + 4 * c4);
+            const float4 e = *reinterpret_cast<const float4*>(a.xe + (row0 + t) * D + 4 * c4);
             v = make_float4((m.x + e.x) / 2.0f, (m.y + e.y) / 2.0f, (m.z + e.z) / 2.0f, (m.w + e.w) / 2.0f);
         }
         *reinterpret_cast<float4*>(A + t * XS + 4 * c4) = v;
     }
     // ---- conditioning (attention.py:500-512): cond = W3 relu(W0 prev + b0) + b3, through `red`; four lanes per hidden
     //      unit (13 of the 52 inputs each), then two lanes per output (64 of the 128 hidden units each) ----
-    if (a.prev) {
+    if (prev) {
         {
             const int o = tid >> 2, part = tid & 3;
             const float* w = a.cw0 + o * NQ + 13 * part;
-            const float* p = a.prev + (int64_t)b * NQ + 13 * part;
+            const float* p = prev + 13 * part;
             float s = 0.f;
 #pragma unroll
             for (int k = 0; k < 13; ++k) s = fmaf(w[k], p[k], s);
@@ -690,7 +696,7 @@ __global__ __launch_bounds__(512) void kmmf_decode_kernel(DecArgs a) {
     for (int i = tid; i < NQ * 64; i += NTH) {
         const int q = i >> 6, c4 = i & 63;
         float4 v = *reinterpret_cast<const float4*>(a.emb + q * D + 4 * c4);
-        if (a.prev) {
+        if (prev) {
             const float4 cv = *reinterpret_cast<const float4*>(red + 128 + 4 * c4);
             v.x += cv.x; v.y += cv.y; v.z += cv.z; v.w += cv.w;
         }
@@ -797,7 +803,7 @@ __global__ __launch_bounds__(512) void kmmf_decode_kernel(DecArgs a) {
         float s = 0.f;
         if (q < NQ) {
             const float4* hr = reinterpret_cast<const float4*>(cur + q * XS + 16 * part);
-            const float4* wr = reinterpret_cast<const float4*>(a.tail.wout + q * HID + 16 * part);
+            const float4* wr = reinterpret_cast<const float4*>(tail.wout + q * HID + 16 * part);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float4 hv = hr[k], wv = wr[k];
@@ -807,12 +813,12 @@ __global__ __launch_bounds__(512) void kmmf_decode_kernel(DecArgs a) {
         s += __shfl_xor(s, 1);
         s += __shfl_xor(s, 2);
         s += __shfl_xor(s, 4);
-        if (q < NQ && part == 0) ys[q] = s + a.tail.bout[q];
+        if (q < NQ && part == 0) ys[q] = s + tail.bout[q];
     }
     __syncthreads();
     const float z = tid < NQ ? ys[tid] : 0.f;
     __syncthreads();
-    kmm_tail_dev(a.tail, b, tid, z, ys);
+    kmm_tail_dev(tail, tb, tid, z, ys);
 #ifdef KM_KMMF_STAMP
     KF_STAMP(7);
     if (lane == 0 && blockIdx.x < 1024) {
@@ -821,6 +827,64 @@ __global__ __launch_bounds__(512) void kmmf_decode_kernel(DecArgs a) {
         for (int i = 0; i < 16; ++i) o[i] = st_acc[i];
     }
 #endif
+}
+
+__global__ __launch_bounds__(512) void kmmf_decode_kernel(DecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int b = blockIdx.x;
+    decode_window(a, b, (int64_t)b * a.T, a.prev ? a.prev + (int64_t)b * NQ : nullptr, a.tail, b, smem, threadIdx.x);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// kmmf_rollout_kernel: the autoregressive chain of ONE clip over the frames of a chunk, one workgroup per clip.  Iteration k is
+// decode_window on window (clip, k) of the chunk's encodings (d.xm / d.xe: (clips, frames, T, 256), no key padding, no maps);
+// its `out` is the next iteration's `prev`.  `prev` (52 floats) and the clip's smoother state (up to 16 x 52 + 1 floats) live in
+// LDS behind the decode images for the length of the chunk -- the tail reads and writes them there, so no wave ever reads from
+// memory what another wave stored an iteration earlier; `out` / `raw` go to memory per frame, the state and the last `out`
+// (prev_io, the next chunk's prev) once at the end.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int ROLL_STATE = 16 * NQ + 4;          // 16 ring slots + the slot pointer, rounded up
+constexpr int ROLL_LDS_FLOATS = DEC_LDS_FLOATS + 64 + ROLL_STATE;
+
+struct RollArgs {
+    DecArgs d;                 // d.prev: (clips, 52) before the chunk's first frame, or null: that one frame runs unconditioned;
+                               // d.tail.state: the caller's state (all clips); d.tail.out / raw: row of the chunk's first frame of clip 0
+    int frames;                // frames of the chunk
+    int64_t out_stride;        // floats from one clip's rows of out / raw to the next clip's
+    int state_floats;          // per clip: 52 (exponential) or window * 52 + 1
+    float* prev_io;            // (clips, 52): the chunk's last out
+};
+
+__global__ __launch_bounds__(512) void kmmf_rollout_kernel(RollArgs r) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* pv = smem + DEC_LDS_FLOATS;
+    float* stl = pv + 64;
+    const int tid = threadIdx.x;
+    const int64_t clip = blockIdx.x;
+    const bool smooth = r.d.tail.smooth >= 0;
+    if (smooth)
+        for (int i = tid; i < r.state_floats; i += NTH) stl[i] = r.d.tail.state[clip * r.state_floats + i];
+    if (r.d.prev && tid < NQ) pv[tid] = r.d.prev[clip * NQ + tid];
+    __syncthreads();
+    KmmTail t = r.d.tail;
+    t.state = stl; t.out = pv;
+    float* out = r.d.tail.out + clip * r.out_stride;
+    float* raw = r.d.tail.raw ? r.d.tail.raw + clip * r.out_stride : nullptr;
+    for (int k = 0; k < r.frames; ++k) {
+        const float* prev = (k > 0 || r.d.prev) ? pv : nullptr;      // only a call's first rendered frame can be without one
+        t.prev = prev;
+        t.raw = raw ? raw + (int64_t)k * NQ : nullptr;
+        // the thread index is opaque to the optimiser in every iteration: per-lane weight addresses computed once for the whole
+        // loop would cost more registers than the body has to spare (scratch)
+        int tk = tid;
+        asm volatile("" : "+v"(tk));
+        decode_window(r.d, 0, (clip * r.frames + k) * r.d.T, prev, t, 0, smem, tk);
+        if (tid < NQ) out[(int64_t)k * NQ + tid] = pv[tid];          // thread q stored pv[q] itself
+        __syncthreads();                                             // pv, the state and the images before the next frame's readers
+    }
+    if (smooth)
+        for (int i = tid; i < r.state_floats; i += NTH) r.d.tail.state[clip * r.state_floats + i] = stl[i];
+    if (tid < NQ && r.frames > 0) r.prev_io[clip * NQ + tid] = pv[tid];
 }
 
 
@@ -1229,6 +1293,35 @@ int launch_kmmf_decode(Context* c, const float* xm, const float* xe, int64_t B, 
     a.kvalid = kvalid; a.causal = k.causal; a.window = k.window_size; a.attn = attn; a.B = (int)B; a.T = (int)T;
     a.tail = tail;
     hipLaunchKernelGGL(kf::kmmf_decode_kernel, dim3((unsigned)B), dim3(kf::NTH), kf::DEC_LDS_FLOATS * 4, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+// the serial chain of `frames` consecutive frames of every clip behind ONE encoder launch over their windows: xm, xe (clips, frames,
+// T, 256); tail.out / tail.raw: the first of those frames' row of clip 0, out_stride floats from clip to clip; prev (clips, 52) or
+// null; prev_io (clips, 52) receives the last frame's out (it may be `prev`)
+int launch_kmmf_rollout(Context* c, const float* xm, const float* xe, int64_t clips, int64_t frames, int64_t T, const float* prev,
+                        const KmmTail& tail, int64_t out_stride, float* prev_io, void* stream) {
+    static PerDeviceOnce once;
+    if (once.first(c->device))
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&kf::kmmf_rollout_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    kf::ROLL_LDS_FLOATS * 4));
+    const km_koemorph_config& k = c->kmm;
+    kf::RollArgs r{};
+    kf::DecArgs& a = r.d;
+    a.xm = xm; a.xe = xe; a.emb = dvp(c, "query_embeddings.query_embeddings");
+    a.cw0 = dvp(c, "query_embeddings.conditioning_net.0.weight"); a.cb0 = dvp(c, "query_embeddings.conditioning_net.0.bias");
+    a.cw3 = dvp(c, "query_embeddings.conditioning_net.3.weight"); a.cb3 = dvp(c, "query_embeddings.conditioning_net.3.bias");
+    a.prev = prev; a.cross = dvp(c, "kmf_cross"); a.cross_layers = k.num_attention_layers;
+    a.dec = dvp(c, "kmf_dec"); a.dec_layers = k.decoder_layers;
+    a.act = k.decoder_activation == 0 ? 1 : (k.decoder_activation == 1 ? 2 : (k.decoder_activation == 2 ? 3 : 4));
+    a.kvalid = nullptr; a.causal = k.causal; a.window = k.window_size; a.attn = nullptr; a.B = (int)(clips * frames); a.T = (int)T;
+    a.tail = tail;
+    r.frames = (int)frames; r.out_stride = out_stride; r.prev_io = prev_io;
+    r.state_floats = tail.smooth == 0 ? tail.NB : tail.window * tail.NB + 1;
+    if (tail.smooth > 0 && r.state_floats > kf::ROLL_STATE)
+        return fail(KM_ERR_UNSUPPORTED, "rollout kernel: smoothing window %d, at most 16", tail.window);
+    hipLaunchKernelGGL(kf::kmmf_rollout_kernel, dim3((unsigned)clips), dim3(kf::NTH), kf::ROLL_LDS_FLOATS * 4, (hipStream_t)stream, r);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

@@ -203,6 +203,19 @@ static int encode_stream(Context* c, const char* stream, const float* in, int in
     return KM_OK;
 }
 
+// the output tail's arguments (km_kmm_tail.h) of one forward; `h` is the chain's to fill in
+KmmTail koemorph_tail(Context* c, const float* prev, float* state, int apply_constraints, float* out, float* raw) {
+    const km_koemorph_config& k = c->kmm;
+    const bool smooth = state != nullptr && k.use_temporal_smoothing;
+    KmmTail ta{};
+    ta.hid = k.decoder_hidden_dim; ta.NB = c->NB; ta.wout = dv(c, "decoder.output_proj.weight"); ta.bout = dv(c, "decoder.output_proj.bias");
+    ta.prev = prev; ta.out_act = k.output_activation; ta.smooth = smooth ? k.smoothing_method : -1; ta.window = k.smoothing_window;
+    ta.sm_param = !smooth ? nullptr : (k.smoothing_method == 0 ? dv(c, "temporal_smoother.alpha")
+                                       : (k.smoothing_method == 1 ? dv(c, "temporal_smoother.gaussian_weights") : nullptr));
+    ta.state = smooth ? state : nullptr; ta.constraints = (apply_constraints && k.use_constraints) ? 1 : 0; ta.out = out; ta.raw = raw;
+    return ta;
+}
+
 int launch_koemorph(Context* c, const float* mel, const float* emo, int64_t B, int64_t T, const unsigned char* kvalid, const float* prev,
                     float* state, int apply_constraints, float* out, float* raw, float* attn, void* stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -232,13 +245,7 @@ int launch_koemorph(Context* c, const float* mel, const float* emo, int64_t B, i
         if (int rc = encode_stream(c, "mel", mel, k.mel_dim, B, T, kvalid, xm, qkv, S, O, ffn, st)) return rc;
         if (int rc = encode_stream(c, "emotion", emo, k.emotion_dim, B, T, kvalid, xe, qkv, S, O, ffn, st)) return rc;
     }
-    const bool smooth = state != nullptr && k.use_temporal_smoothing;
-    KmmTail ta{};
-    ta.hid = hid; ta.NB = NB; ta.wout = dv(c, "decoder.output_proj.weight"); ta.bout = dv(c, "decoder.output_proj.bias");
-    ta.prev = prev; ta.out_act = k.output_activation; ta.smooth = smooth ? k.smoothing_method : -1; ta.window = k.smoothing_window;
-    ta.sm_param = !smooth ? nullptr : (k.smoothing_method == 0 ? dv(c, "temporal_smoother.alpha")
-                                       : (k.smoothing_method == 1 ? dv(c, "temporal_smoother.gaussian_weights") : nullptr));
-    ta.state = smooth ? state : nullptr; ta.constraints = (apply_constraints && k.use_constraints) ? 1 : 0; ta.out = out; ta.raw = raw;
+    KmmTail ta = koemorph_tail(c, prev, state, apply_constraints, out, raw);
     if (fused) return launch_kmmf_decode(c, xm, xe, B, T, kvalid, prev, attn, ta, stream);
     hipLaunchKernelGGL(kmm_avg_kernel, dim3((unsigned)((R * d + 255) / 256)), dim3(256), 0, st, xm, xe, xm, R * d);
     // ---- queries (attention.py:481-514) ----

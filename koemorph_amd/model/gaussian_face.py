@@ -171,6 +171,9 @@ class KoeMorphModel(nn.Module):
         self._sig = None
         self._reserved = (0, 0)
         self._smoother_state: Optional[torch.Tensor] = None
+        self._rollout_reserved = (0, 0, 0)               # clips, context frames, chunk frames of km_koemorph_rollout_reserve
+        object.__setattr__(self, "_render_mel", None)    # render()'s extractors, built on first use (kept out of the module tree)
+        self._render_egemaps = None
 
     # ---- handle plumbing ------------------------------------------------------------------------
     def _c_config(self) -> KMKoeMorphConfig:
@@ -214,6 +217,24 @@ class KoeMorphModel(nn.Module):
         except Exception:
             pass
 
+    def _ensure_smoother_state(self, B: int, dev) -> None:
+        """``self._smoother_state`` for a batch of B, by the reference's rules (forward and rollout share them)."""
+        nb = self.num_blendshapes
+        if self.smoothing_method != "exponential" and (self._smoother_state is None or self._smoother_state.shape[0] != B):
+            # gaussian / median: every batch element's history ring (window, 52) + its slot pointer (include/koemorph.h).  A
+            # new batch size continues from batch element 0's history, as decoder.py:333-337 expands history[:, :1, :]
+            W = self.temporal_smoother.window_size
+            first = torch.zeros(1, W * nb + 1, device=dev) if self._smoother_state is None else self._smoother_state[:1]
+            self._smoother_state = first.expand(B, -1).contiguous()
+        if self.smoothing_method == "exponential" and (self._smoother_state is None or self._smoother_state.shape[0] != B):
+            # decoder.py:282-283: the (1, 52) state is expanded to the batch (zeros after a reset); a state that already
+            # holds another batch size cannot be expanded -- torch raises there, and so does this mirror
+            if self._smoother_state is not None and self._smoother_state.shape[0] != 1:
+                raise RuntimeError(f"temporal smoother holds state for batch {self._smoother_state.shape[0]}, got batch {B}: "
+                                   "call reset_temporal_state() between sequences (the reference's expand() fails the same way)")
+            first = torch.zeros(1, nb, device=dev) if self._smoother_state is None else self._smoother_state
+            self._smoother_state = first.expand(B, -1).contiguous()
+
     # ---- reference API --------------------------------------------------------------------------
     def forward(self, mel_features: torch.Tensor, emotion_features: torch.Tensor, audio_mask: Optional[torch.Tensor] = None,
                 prev_blendshapes: Optional[torch.Tensor] = None, apply_smoothing: bool = True, apply_constraints: bool = True,
@@ -239,20 +260,8 @@ class KoeMorphModel(nn.Module):
                 raise ValueError(f"audio_mask must be (B, T) = {(B, T)}, got {tuple(audio_mask.shape)}")
             valid = audio_mask.to(device=dev, dtype=torch.uint8).contiguous()
         smooth = apply_smoothing and self.use_temporal_smoothing
-        if smooth and self.smoothing_method != "exponential" and (self._smoother_state is None or self._smoother_state.shape[0] != B):
-            # gaussian / median: every batch element's history ring (window, 52) + its slot pointer (include/koemorph.h).  A
-            # new batch size continues from batch element 0's history, as decoder.py:333-337 expands history[:, :1, :]
-            W = self.temporal_smoother.window_size
-            first = torch.zeros(1, W * nb + 1, device=dev) if self._smoother_state is None else self._smoother_state[:1]
-            self._smoother_state = first.expand(B, -1).contiguous()
-        if smooth and self.smoothing_method == "exponential" and (self._smoother_state is None or self._smoother_state.shape[0] != B):
-            # decoder.py:282-283: the (1, 52) state is expanded to the batch (zeros after a reset); a state that already
-            # holds another batch size cannot be expanded -- torch raises there, and so does this mirror
-            if self._smoother_state is not None and self._smoother_state.shape[0] != 1:
-                raise RuntimeError(f"temporal smoother holds state for batch {self._smoother_state.shape[0]}, got batch {B}: "
-                                   "call reset_temporal_state() between sequences (the reference's expand() fails the same way)")
-            first = torch.zeros(1, nb, device=dev) if self._smoother_state is None else self._smoother_state
-            self._smoother_state = first.expand(B, -1).contiguous()
+        if smooth:
+            self._ensure_smoother_state(B, dev)
         out = torch.empty(B, nb, device=dev)
         raw = torch.empty(B, nb, device=dev)
         L = len(self.cross_attention_layers)
@@ -266,6 +275,108 @@ class KoeMorphModel(nn.Module):
         if attn is not None:
             output["attention_weights"] = [attn[i] for i in range(L)]
         return output
+
+    # ---- whole clips: the autoregressive loop on the device ----------------------------------------
+    DEFAULT_CHUNK_FRAMES = 256       # README "KoeMorphModel rollout": read from the measured table
+
+    def _context(self, context_frames: Optional[int]) -> int:
+        if context_frames is not None:
+            return int(context_frames)
+        return int(self.window_size) if self.window_size is not None else 30
+
+    def rollout_plan(self, B: int, F: int, context_frames: Optional[int] = None, first_frame: int = 0) -> Dict[str, int]:
+        """What ``rollout`` would run for B clips of F rows (km_koemorph_rollout_plan; host only)."""
+        lib, h, _ = self._handle()
+        out = (C.c_int64 * 5)()
+        check(lib.km_koemorph_rollout_plan(h, B, F, self._context(context_frames), first_frame, out))
+        return dict(zip(("route", "chunks", "short_frames", "launches", "workspace_floats"), (int(v) for v in out)))
+
+    def rollout(self, mel_rows: torch.Tensor, emotion_rows: torch.Tensor, context_frames: Optional[int] = None, first_frame: int = 0,
+                prev_blendshapes: Optional[torch.Tensor] = None, apply_smoothing: bool = True, apply_constraints: bool = True,
+                chunk_frames: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Render frames ``first_frame ..`` of B clips from their per-frame rows (B, F, mel_dim) / (B, F, emotion_dim) in one call
+        (km_koemorph_rollout): frame i is ``forward`` on the window of its last ``min(i + 1, context_frames)`` rows with the
+        previous frame's output as ``prev_blendshapes`` (``prev_blendshapes`` here feeds the first rendered frame), the smoother
+        state carried as ``forward`` carries it.  ``first_frame > 0`` continues a stream: rows before it are context only."""
+        if self.training and torch.is_grad_enabled():
+            raise RuntimeError("the HIP forward implements eval-mode arithmetic; call .eval() or torch.no_grad()")
+        if mel_rows.dim() != 3 or emotion_rows.dim() != 3 or mel_rows.shape[:2] != emotion_rows.shape[:2]:
+            raise ValueError(f"expected (B, F, mel_dim) and (B, F, emotion_dim), got {tuple(mel_rows.shape)} and {tuple(emotion_rows.shape)}")
+        if mel_rows.shape[2] != self.mel_dim or emotion_rows.shape[2] != self.emotion_dim:
+            raise ValueError(f"expected rows of {self.mel_dim} and {self.emotion_dim} features, got {mel_rows.shape[2]} and {emotion_rows.shape[2]}")
+        if not 0 <= int(first_frame) < mel_rows.shape[1]:
+            raise ValueError(f"first_frame {first_frame} outside 0 .. {mel_rows.shape[1] - 1}")
+        lib, h, dev = self._handle()
+        mel = mel_rows.float().contiguous()
+        emo = emotion_rows.float().contiguous()
+        B, F, _ = mel.shape
+        T = self._context(context_frames)
+        chunk = int(chunk_frames) if chunk_frames is not None else self.DEFAULT_CHUNK_FRAMES
+        res = self._rollout_reserved
+        if B > res[0] or T > res[1] or chunk != res[2]:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.KoeMorphError(_lib.KM_ERR_WORKSPACE, f"km_koemorph_rollout_reserve: {B} clips x {T} context frames in chunks of "
+                                         f"{chunk} exceed the reserved {res} during a stream capture: run one call of this size first")
+            want = (max(B, res[0]), max(T, res[1]), chunk)
+            with torch.cuda.device(dev):
+                torch.cuda.synchronize(dev)
+                check(lib.km_koemorph_rollout_reserve(h, *want))
+            self._rollout_reserved = want
+            self._reserved = (max(want[0], self._reserved[0]), max(want[1], self._reserved[1]))
+        nb = self.num_blendshapes
+        prev = None if prev_blendshapes is None else prev_blendshapes.float().contiguous()
+        if prev is not None and tuple(prev.shape) != (B, nb):
+            raise ValueError(f"prev_blendshapes must be (B, {nb}) = {(B, nb)}, got {tuple(prev.shape)}")
+        smooth = apply_smoothing and self.use_temporal_smoothing
+        if smooth:
+            self._ensure_smoother_state(B, dev)
+        rows = F - int(first_frame)
+        out = torch.empty(B, rows, nb, device=dev)
+        raw = torch.empty(B, rows, nb, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.km_koemorph_rollout(h, _ptr(mel), _ptr(emo), B, F, T, int(first_frame), _ptr(prev) if prev is not None else None,
+                                          _ptr(self._smoother_state) if smooth else None, 1 if apply_constraints else 0,
+                                          _ptr(out), _ptr(raw), _stream_ptr(dev)))
+        return {"blendshapes": out, "raw_blendshapes": raw}
+
+    def render(self, audio: torch.Tensor, fps: float = 30.0, context_frames: Optional[int] = None,
+               emotion_rows: Optional[torch.Tensor] = None, feature_set: str = "eGeMAPSv02", long_windows: bool = False,
+               **rollout_kwargs) -> Dict[str, torch.Tensor]:
+        """audio (B, L) at 16 kHz on the device -> the clip's blendshape track: mel rows from ``MelSpectrogramExtractor(target_fps=fps)``,
+        emotion rows from ``EGeMAPSEngine.llds(audio, fps=fps)`` (or ``emotion_rows``), zero-padded on the right to ``emotion_dim``,
+        then ``rollout``."""
+        if self.training and torch.is_grad_enabled():
+            raise RuntimeError("the HIP forward implements eval-mode arithmetic; call .eval() or torch.no_grad()")
+        if audio.dim() == 1:
+            audio = audio.unsqueeze(0)
+        expected = int(audio.shape[1] / 16000 * fps)               # rows of both extractors for L samples
+        if emotion_rows is not None:                               # the caller's rows are judged before anything is computed
+            emotion_rows = self._pad_emotion_rows(emotion_rows, self.emotion_dim)
+            if emotion_rows.shape[1] != expected:
+                raise ValueError(f"{expected} mel rows but {emotion_rows.shape[1]} emotion rows: the two tracks must lie on one frame grid")
+        if self._render_mel is None or self._render_mel.target_fps != fps:
+            from ..features.stft import MelSpectrogramExtractor
+            object.__setattr__(self, "_render_mel", MelSpectrogramExtractor(target_fps=fps, n_mels=self.mel_dim))   # not a submodule
+        mel = self._render_mel(audio)
+        if emotion_rows is None:
+            if self._render_egemaps is None:
+                from ..features.opensmile_extractor import EGeMAPSEngine
+                self._render_egemaps = EGeMAPSEngine(audio.device)
+            emotion_rows = self._render_egemaps.llds(audio.float().contiguous(), feature_set=feature_set, long_windows=long_windows, fps=fps)
+        emo = self._pad_emotion_rows(emotion_rows, self.emotion_dim)
+        if emo.shape[1] != mel.shape[1]:
+            raise ValueError(f"{mel.shape[1]} mel rows but {emo.shape[1]} emotion rows: the two tracks must lie on one frame grid")
+        return self.rollout(mel, emo, context_frames=context_frames, **rollout_kwargs)
+
+    @staticmethod
+    def _pad_emotion_rows(rows: torch.Tensor, emotion_dim: int) -> torch.Tensor:
+        """(B, F, n) descriptor rows -> (B, F, emotion_dim), zeros on the right; wider rows are an error."""
+        if rows.dim() != 3:
+            raise ValueError(f"expected emotion rows (B, F, n), got {tuple(rows.shape)}")
+        n = rows.shape[2]
+        if n > emotion_dim:
+            raise ValueError(f"emotion rows are {n} wide, the model's emotion_dim is {emotion_dim}")
+        return rows if n == emotion_dim else torch.nn.functional.pad(rows, (0, emotion_dim - n))
 
     def reset_temporal_state(self):
         """New sequence: the smoother starts from zeros again (gaussian_face.py:270-276)."""

@@ -69,6 +69,12 @@ def cycle(i):
     mf = KoeMorphModel(d_query=256).cuda().eval()       # default width: the two fused kernels and their weight blobs
     with torch.no_grad():
         mf(torch.randn(3, 30, 80, device="cuda"), torch.randn(3, 30, 256, device="cuda"))
+        # one rollout on each route: the rollout workspace group (per-frame launches at d_model 64; gather, encoder and rollout kernel
+        # in chunks at the default width)
+        m.reset_temporal_state(); mf.reset_temporal_state()
+        assert m.rollout_plan(2, 12, 5)["route"] == 0 and mf.rollout_plan(2, 20, 9)["route"] == 1
+        m.rollout(torch.randn(2, 12, 80, device="cuda"), torch.randn(2, 12, 8, device="cuda"), context_frames=5)
+        mf.rollout(torch.randn(2, 20, 80, device="cuda"), torch.randn(2, 20, 256, device="cuda"), context_frames=9, chunk_frames=4)
     del tr, eng, g, m, mf, audio, emo
     gc.collect(); torch.cuda.empty_cache()
 
