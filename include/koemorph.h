@@ -582,6 +582,48 @@ int km_koemorph_rollout(km_handle h, const float* mel_dev, const float* emotion_
                         void* stream);
 int km_koemorph_rollout_plan(km_handle h, int64_t B, int64_t F, int64_t T, int64_t first_frame, int64_t out[5]);
 
+/* ---- KoeMorphModel: live streams with their last rows resident on the device -----------------------------
+ * n_streams independent streams, out of phase.  THE LAW: stream s has a frame counter c_s, 0 after creation and after a reset of
+ * that stream.  A step that gives it n_s new rows (0 <= n_s <= max_rows) renders n_s frames, in order; frame i = c_s + j is
+ * km_koemorph_forward at B = 1 on the dense window of the stream's rows i - T_i + 1 .. i, T_i = min(i + 1, context_frames), no audio
+ * mask, prev = the stream's previous rendered frame (frame 0 has none and runs unconditioned), the stream's OWN smoother state
+ * (zeros after a reset, km_koemorph_forward's layouts for B = 1) updated by every frame.  Short windows are shorter windows, never
+ * padded ones (the rollout's law).  Streams share nothing; a stream with n_s = 0 keeps ring, counter, previous frame and state, and
+ * its rows of out_dev / raw_dev are not written.  The results are those of the per-stream km_koemorph_forward loop, bit for bit.
+ * Served: the width of the fused kernels (d_model 256, 8 heads, 52 blendshapes, decoder width 128, mel_dim and emotion_dim multiples
+ * of 16, at least one attention layer), context_frames <= 32, smoothing window <= 16, option "kmm_no_fuse" off (rollout route 1);
+ * anything else is KM_ERR_UNSUPPORTED at creation, the text naming the entry point and the value.
+ *   km_koemorph_stream_plan    host only (after km_finalize_host), the function create itself uses: out[0] 1 supported / 0 not (the
+ *                        reason is km_last_error's text; the other values are 0), out[1] ring rows per stream = context_frames - 1 +
+ *                        max_rows, out[2] launches per step (4), out[3] device memory of the engine in 4-byte units, out[4] LDS
+ *                        bytes of the chain kernel, out[5] smoother-state floats per stream
+ *   km_koemorph_stream_create  a buffer group of its own (rings, counters, previous frames, states, window table, encodings).
+ *                        Allocates and synchronises the device: call it outside any stream capture.  A second create replaces the
+ *                        first; km_destroy frees the group.  apply_smoothing / apply_constraints: km_koemorph_forward's switches
+ *   km_koemorph_stream_step    mel_dev (n_streams, max_rows, mel_dim), emotion_dev (n_streams, max_rows, emotion_dim), both 16-byte
+ *                        aligned; counts_dev (n_streams) int32 or NULL = max_rows for every stream, each clamped to 0 .. max_rows:
+ *                        stream s brings rows 0 .. n_s - 1 of its block.  out_dev / raw_dev (or NULL) (n_streams, max_rows, 52): row
+ *                        (s, j) = frame c_s + j for j < n_s, the others untouched; rendered_dev (n_streams) int32 or NULL receives
+ *                        n_s.  FOUR launches on `stream` whatever the sizes and phases (row advance + window table, the encoder for
+ *                        windows of <= 16 and of 17 .. 32 rows, the per-stream chains); no allocation, synchronisation or readback:
+ *                        capturable
+ *   km_koemorph_stream_reset   one launch: the streams with mask_dev[s] != 0 (NULL: all) become freshly created ones
+ *   km_koemorph_stream_destroy frees the group and leaves the handle as it was before create (km_destroy does the same on its way)
+ *   km_koemorph_stream_frames  frames_dev (n_streams) int64 <- the counters
+ *   km_koemorph_stream_state   state_dev (n_streams, out[5]) and / or prev_dev (n_streams, 52), either may be NULL <- the smoother
+ *                        states and the last rendered frames
+ * KM_ERR_INVALID_ARG: NULL handle, a handle of another kind, n_streams / context_frames / max_rows < 1, no engine created, NULL or
+ * misaligned row pointers. */
+int km_koemorph_stream_plan(km_handle h, int64_t n_streams, int64_t context_frames, int64_t max_rows, int64_t out[6]);
+int km_koemorph_stream_create(km_handle h, int64_t n_streams, int64_t context_frames, int64_t max_rows, int32_t apply_smoothing,
+                              int32_t apply_constraints);
+int km_koemorph_stream_step(km_handle h, const float* mel_dev, const float* emotion_dev, const int32_t* counts_dev, float* out_dev,
+                            float* raw_dev, int32_t* rendered_dev, void* stream);
+int km_koemorph_stream_reset(km_handle h, const uint8_t* mask_dev, void* stream);
+int km_koemorph_stream_destroy(km_handle h);
+int km_koemorph_stream_frames(km_handle h, int64_t* frames_dev, void* stream);
+int km_koemorph_stream_state(km_handle h, float* state_dev, float* prev_dev, void* stream);
+
 /* ---- streaming: many concurrent speaker streams, state resident on the device -------------------------
  * Replaces, for all streams of this GPU at once, MelAudioBuffer.add_audio_frame / get_current_audio
  * (src/features/mel_sliding_window.py:70-140), MelSlidingWindowExtractor.process_audio_frame (:252-324) and

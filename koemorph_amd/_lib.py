@@ -172,6 +172,13 @@ SIGNATURES = {
     "km_koemorph_rollout_reserve": (C.c_int, [_h, _i64, _i64, _i64]),
     "km_koemorph_rollout": (C.c_int, [_h, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _i32, _p, _p, _p]),
     "km_koemorph_rollout_plan": (C.c_int, [_h, _i64, _i64, _i64, _i64, C.POINTER(_i64)]),
+    "km_koemorph_stream_plan": (C.c_int, [_h, _i64, _i64, _i64, C.POINTER(_i64)]),
+    "km_koemorph_stream_create": (C.c_int, [_h, _i64, _i64, _i64, _i32, _i32]),
+    "km_koemorph_stream_step": (C.c_int, [_h, _p, _p, _p, _p, _p, _p, _p]),
+    "km_koemorph_stream_reset": (C.c_int, [_h, _p, _p]),
+    "km_koemorph_stream_destroy": (C.c_int, [_h]),
+    "km_koemorph_stream_frames": (C.c_int, [_h, _p, _p]),
+    "km_koemorph_stream_state": (C.c_int, [_h, _p, _p, _p]),
     "km_stream_create": (C.c_int, [_h, _i64, C.c_double, C.c_double, C.POINTER(KMMelConfig)]),
     "km_stream_push": (C.c_int, [_h, _p, _i64, _p]),
     "km_stream_tick": (C.c_int, [_h, _p, _p, _p, _p]),

@@ -219,6 +219,18 @@ struct RolloutBufs {
     DevBuf<float> ws;
 };
 
+// km_koemorph_stream_create: the stream engine of a KoeMorphModel handle (km_koemorph_stream.hip); streams == 0 until created
+struct KoeMorphStreams {
+    int64_t streams = 0, context = 0, max_rows = 0, cap = 0, state_floats = 0;
+    int smoothing = 0, constraints = 0;
+    DevBuf<float> ring_mel, ring_emo;    // (streams, cap, mel_dim / emotion_dim) the last cap = context - 1 + max_rows rows, positions wrap
+    DevBuf<long long> counter;           // (streams) frames since the stream's reset
+    DevBuf<int> nstep;                   // (streams) frames of the current step
+    DevBuf<float> prev, state;           // (streams, 52) the last rendered frame; (streams, state_floats) the smoother state
+    DevBuf<int> table;                   // (streams * max_rows, 4) the step's window table (KmsWindow, km_kmmf.hip)
+    DevBuf<float> xm, xe;                // (streams * max_rows, context, 256) encodings of the step's windows
+};
+
 // two-deep pipeline across calls (km_forward_audio_pipelined)
 struct PipeSlot {
     DevBuf<float> melpow; DevBuf<unsigned> melmax; DevBuf<float> zemo;
@@ -268,6 +280,7 @@ struct Context {
     ClipAsmBufs clipasm;                         // km_train_step_clip / km_forward_clip with option clip_assemble
     Pipeline pipe;                               // km_forward_audio_pipelined
     RolloutBufs ro;                              // kind 2: km_koemorph_rollout
+    KoeMorphStreams ks;                          // kind 2: km_koemorph_stream_*
     bool stage_timing = false;
     DevEvent stage_ev[6];                        // emo b/e, mel e, core b/e
     bool melmax_dirty = true;      // ws.melmax may hold stale maxima (see launch_mel_power)

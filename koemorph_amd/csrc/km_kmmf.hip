@@ -10,6 +10,9 @@
 //                         BlendshapeDecoder and the output tail: one workgroup per window, the 52 query rows resident in LDS.
 //   kmmf_rollout_kernel   the decode kernel's body (decode_window, shared) in a loop over consecutive frames of a clip, one workgroup
 //                         per clip, the previous frame's output and the smoother state resident in LDS (km_koemorph_rollout).
+//   kmmf_encoder_kernel<., true> / kmmf_chain_kernel   the same two bodies for streams that are out of phase (km_koemorph_stream_step):
+//                         one window per encoder workgroup with its length read from the step's window table and its rows from the
+//                         stream's ring; one workgroup per stream that walks the frames the step gave it.
 //
 // All products are exact-fp32 v_mfma_f32_16x16x4_f32.  Activations are the A operand out of an LDS image [row][264] (one
 // ds_read_b128 = the operand of four MFMAs, stride 264 = 8 mod 64 dwords: conflict-free for the instruction's lane groups);
@@ -24,6 +27,7 @@
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 
 #include "km_context.h"
 #include "km_device.h"
@@ -433,17 +437,44 @@ struct EncArgs {
     int slot_log2;                            // a window owns 1 << slot_log2 rows of the 32 (the power of two >= T): 1 .. 32 windows per workgroup
 };
 
-template <bool SMALL>     // SMALL: windows of <= 16 frames (slots of 1 .. 16 rows), else one window of 17 - 32 frames
-__global__ __launch_bounds__(256) void kmmf_encoder_kernel(EncArgs a) {
+// The step's window table of the stream engine (km_koemorph_stream.hip), one entry per (stream, frame slot): x = stream, y = frame
+// slot j, z = T_i (0: the slot holds no frame), w = ring position of the window's first row.
+typedef int4 KmsWindow;
+
+// a.in0 / a.in1: the streams' rings (streams, cap, in_dim); a.out0 / a.out1: (entries, a.T, 256); a.B: entries; a.kvalid null
+struct EncRagArgs : EncArgs { const KmsWindow* table; int cap; };
+
+// Raggedness is a template parameter; the dense instantiations are the statements they were.
+//   RAGGED = false: a.B dense windows of a.T frames each, 32 >> a.slot_log2 of them per workgroup.
+//   RAGGED = true (km_koemorph_stream_step): ONE window per workgroup, the window of table entry blockIdx.x >> 1, laid out as a
+//   forward call at B = 1 lays it out:
+//   its T_i rows at the head of the image in a slot of the power of two >= T_i, every other row without a frame.  T_i and the slot
+//   are workgroup-uniform values read from the table; the rows come from the stream's ring (cap rows, positions wrap) -- read in
+//   place, not staged: a window is read by exactly one workgroup per stream, so a staging image would add a write and a read of
+//   every row to save nothing but the wrap, which is one compare per 16-byte move -- and go to rows (entry, 0 .. T_i - 1) of
+//   out0 / out1 (entries, a.T, 256).  A workgroup whose slot is empty or whose class (T_i <= 16: SMALL) is the other instantiation's
+//   returns at once: the two launches cover all entries each, and a step's grid does not depend on the streams' phases.
+template <bool SMALL, bool RAGGED = false>     // SMALL: windows of <= 16 frames (slots of 1 .. 16 rows), else one window of 17 - 32 frames
+__global__ __launch_bounds__(256) void kmmf_encoder_kernel(std::conditional_t<RAGGED, EncRagArgs, EncArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* X = smem;
     float* Y = smem + EIMG;
     float* red = smem + 2 * EIMG;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, j = lane & 15;
-    const int T = a.T, lg = a.slot_log2;
+    int rT = 0, rlg = 0, pos0 = 0, cap = 0; int64_t ring0 = 0;     // RAGGED: the window's length, slot and first ring position, the stream's first ring row
+    if constexpr (RAGGED) {
+        cap = a.cap;
+        const KmsWindow e = a.table[blockIdx.x >> 1];
+        rT = __builtin_amdgcn_readfirstlane(e.z);
+        if (rT == 0 || (rT <= 16) != SMALL) return;
+        while ((1 << rlg) < rT) ++rlg;
+        ring0 = (int64_t)__builtin_amdgcn_readfirstlane(e.x) * cap; pos0 = __builtin_amdgcn_readfirstlane(e.w);
+    }
+    const int T = RAGGED ? rT : a.T, lg = RAGGED ? rlg : a.slot_log2;
     const int stream = blockIdx.x & 1, widx = blockIdx.x >> 1;
-    const int w0 = widx * (EROWS >> lg);                // first window of this workgroup
+    const int w0 = RAGGED ? 0 : widx * (EROWS >> lg);   // first window of this workgroup
+    constexpr int RB = 1;                               // RAGGED: windows of the workgroup
     const float* in = stream ? a.in1 : a.in0;
     const int in_dim = stream ? a.in_dim1 : a.in_dim0;
     float* out = stream ? a.out1 : a.out0;
@@ -459,13 +490,18 @@ __global__ __launch_bounds__(256) void kmmf_encoder_kernel(EncArgs a) {
     unsigned rowmask;
     {
         const int b = w0 + (lane >> lg), t = lane & ((1 << lg) - 1);
-        rowmask = (unsigned)__ballot(lane < EROWS && b < a.B && t < T && (!a.kvalid || a.kvalid[(int64_t)b * T + t]));
+        rowmask = (unsigned)__ballot(lane < EROWS && (RAGGED ? b < RB : b < a.B) && t < T && (!a.kvalid || a.kvalid[(int64_t)b * T + t]));
     }
     // ---- input rows -> X (columns >= in_dim and rows without a frame are zero) ----
     for (int i = tid; i < EROWS * 64; i += ENTH) {
         const int r = i >> 6, c4 = i & 63, b = w0 + (r >> lg), t = r & ((1 << lg) - 1);
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (b < a.B && t < T && 4 * c4 < in_dim) v = *reinterpret_cast<const float4*>(in + ((int64_t)b * T + t) * in_dim + 4 * c4);
+        if constexpr (RAGGED) {
+            const int p = pos0 + t;                     // both below cap
+            if (b < RB && t < T && 4 * c4 < in_dim) v = *reinterpret_cast<const float4*>(in + (ring0 + (p >= cap ? p - cap : p)) * in_dim + 4 * c4);
+        } else {
+            if (b < a.B && t < T && 4 * c4 < in_dim) v = *reinterpret_cast<const float4*>(in + ((int64_t)b * T + t) * in_dim + 4 * c4);
+        }
         *reinterpret_cast<float4*>(X + r * XS + 4 * c4) = v;
     }
     __syncthreads();
@@ -592,7 +628,11 @@ __global__ __launch_bounds__(256) void kmmf_encoder_kernel(EncArgs a) {
     // ---- rows -> (B, T, 256) ----
     for (int i = tid; i < EROWS * 64; i += ENTH) {
         const int r = i >> 6, c4 = i & 63, b = w0 + (r >> lg), t = r & ((1 << lg) - 1);
-        if (b < a.B && t < T) *reinterpret_cast<float4*>(out + ((int64_t)b * T + t) * D + 4 * c4) = *reinterpret_cast<const float4*>(xc + r * XS + 4 * c4);
+        if constexpr (RAGGED) {
+            if (b < RB && t < T) *reinterpret_cast<float4*>(out + ((int64_t)widx * a.T + t) * D + 4 * c4) = *reinterpret_cast<const float4*>(xc + r * XS + 4 * c4);
+        } else {
+            if (b < a.B && t < T) *reinterpret_cast<float4*>(out + ((int64_t)b * T + t) * D + 4 * c4) = *reinterpret_cast<const float4*>(xc + r * XS + 4 * c4);
+        }
     }
 #ifdef KM_KMMF_STAMP
     KF_STAMP(12);
@@ -629,9 +669,10 @@ struct DecArgs {
 // One window, start to finish: the body of kmmf_decode_kernel and of every iteration of kmmf_rollout_kernel.
 //   b: the window's batch element for the key padding mask and the attention maps; row0: its first row in a.xm / a.xe;
 //   prev: ITS 52 previous coefficients or null (a.prev is not read here); tail / tb: the output tail's pointers and the
-//   element they are indexed with (km_kmm_tail.h).  Ends behind the tail's last store, with no barrier after it.
+//   element they are indexed with (km_kmm_tail.h); T: the window's frames (a.T is not read here: the chain kernel's windows differ in
+//   length).  Ends behind the tail's last store, with no barrier after it.
 __device__ __forceinline__ void decode_window(const DecArgs& a, int b, int64_t row0, const float* prev, const KmmTail& tail, int64_t tb,
-                                              float* smem, const int tid) {
+                                              float* smem, const int tid, const int T) {
     float* X = smem;
     float* Y = smem + QIMG;
     float* A = smem + 2 * QIMG;
@@ -639,7 +680,6 @@ __device__ __forceinline__ void decode_window(const DecArgs& a, int b, int64_t r
     float* ys = red + RED;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, j = lane & 15;
-    const int T = a.T;
     const int col0 = 32 * wave;
 
     const unsigned kmask = (unsigned)__ballot(lane < T && (!a.kvalid || a.kvalid[row0 + lane]));
@@ -832,7 +872,7 @@ __device__ __forceinline__ void decode_window(const DecArgs& a, int b, int64_t r
 __global__ __launch_bounds__(512) void kmmf_decode_kernel(DecArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = blockIdx.x;
-    decode_window(a, b, (int64_t)b * a.T, a.prev ? a.prev + (int64_t)b * NQ : nullptr, a.tail, b, smem, threadIdx.x);
+    decode_window(a, b, (int64_t)b * a.T, a.prev ? a.prev + (int64_t)b * NQ : nullptr, a.tail, b, smem, threadIdx.x, a.T);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -878,13 +918,66 @@ __global__ __launch_bounds__(512) void kmmf_rollout_kernel(RollArgs r) {
         // loop would cost more registers than the body has to spare (scratch)
         int tk = tid;
         asm volatile("" : "+v"(tk));
-        decode_window(r.d, 0, (clip * r.frames + k) * r.d.T, prev, t, 0, smem, tk);
+        decode_window(r.d, 0, (clip * r.frames + k) * r.d.T, prev, t, 0, smem, tk, r.d.T);
         if (tid < NQ) out[(int64_t)k * NQ + tid] = pv[tid];          // thread q stored pv[q] itself
         __syncthreads();                                             // pv, the state and the images before the next frame's readers
     }
     if (smooth)
         for (int i = tid; i < r.state_floats; i += NTH) r.d.tail.state[clip * r.state_floats + i] = stl[i];
     if (tid < NQ && r.frames > 0) r.prev_io[clip * NQ + tid] = pv[tid];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// kmmf_chain_kernel: kmmf_rollout_kernel for streams that are out of phase (km_koemorph_stream_step): one workgroup per STREAM walks
+// the n_s frames the step gave it.  Frame j is frame i = c_s + j of the stream's life, its window has T_i = min(i + 1, context) rows
+// at slot (stream, j) of the ragged encoder launches' output, and it runs unconditioned exactly when i == 0.  The stream's previous
+// frame and smoother state sit in LDS for the step: loaded from the engine's per-stream buffers, stored back once.  A stream that
+// was given no frame returns before it touches anything.
+// ---------------------------------------------------------------------------------------------------------
+struct ChainArgs {
+    DecArgs d;                 // d.xm / d.xe: (streams * max_rows, d.T, 256), d.T = the context; d.prev is not read; d.tail.state:
+                               // (streams, state_floats); d.tail.out / raw: (streams, max_rows, 52)
+    int max_rows, state_floats;
+    const int* nstep;          // (streams) frames of this step
+    const long long* counter;  // (streams) frames since the stream's reset, this step's included
+    float* prev;               // (streams, 52) the last rendered frame
+};
+
+__global__ __launch_bounds__(512) void kmmf_chain_kernel(ChainArgs r) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* pv = smem + DEC_LDS_FLOATS;
+    float* stl = pv + 64;
+    const int tid = threadIdx.x;
+    const int64_t s = blockIdx.x;
+    int n = r.nstep[s];
+    if (n <= 0) return;
+    n = n < r.max_rows ? n : r.max_rows;
+    const long long c0 = r.counter[s] - n;
+    const bool smooth = r.d.tail.smooth >= 0;
+    if (smooth)
+        for (int i = tid; i < r.state_floats; i += NTH) stl[i] = r.d.tail.state[s * r.state_floats + i];
+    if (tid < NQ) pv[tid] = r.prev[s * NQ + tid];                    // not read by frame 0 of a life
+    __syncthreads();
+    KmmTail t = r.d.tail;
+    t.state = stl; t.out = pv;
+    float* out = r.d.tail.out + s * r.max_rows * NQ;
+    float* raw = r.d.tail.raw ? r.d.tail.raw + s * r.max_rows * NQ : nullptr;
+    for (int k = 0; k < n; ++k) {
+        const long long i = c0 + k;
+        const int Ti = i + 1 < (long long)r.d.T ? (int)(i + 1) : r.d.T;
+        const float* prev = i > 0 ? pv : nullptr;
+        t.prev = prev;
+        t.raw = raw ? raw + (int64_t)k * NQ : nullptr;
+        // the opaque thread index of kmmf_rollout_kernel, for its reason: without it this kernel spills as that one did
+        int tk = tid;
+        asm volatile("" : "+v"(tk));
+        decode_window(r.d, 0, (s * r.max_rows + k) * r.d.T, prev, t, 0, smem, tk, Ti);
+        if (tid < NQ) out[(int64_t)k * NQ + tid] = pv[tid];          // thread q stored pv[q] itself
+        __syncthreads();
+    }
+    if (smooth)
+        for (int i = tid; i < r.state_floats; i += NTH) r.d.tail.state[s * r.state_floats + i] = stl[i];
+    if (tid < NQ) r.prev[s * NQ + tid] = pv[tid];
 }
 
 
@@ -1322,6 +1415,63 @@ int launch_kmmf_rollout(Context* c, const float* xm, const float* xe, int64_t cl
     if (tail.smooth > 0 && r.state_floats > kf::ROLL_STATE)
         return fail(KM_ERR_UNSUPPORTED, "rollout kernel: smoothing window %d, at most 16", tail.window);
     hipLaunchKernelGGL(kf::kmmf_rollout_kernel, dim3((unsigned)clips), dim3(kf::NTH), kf::ROLL_LDS_FLOATS * 4, (hipStream_t)stream, r);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+// ---- the stream engine's launches (km_koemorph_stream.hip) ----
+int64_t kmmf_chain_lds_bytes() { return (int64_t)kf::ROLL_LDS_FLOATS * 4; }
+
+// the attributes of the three kernels of a step, set at creation: a capture never sees them being set
+int kmmf_stream_prepare(Context* c) {
+    static PerDeviceOnce once;
+    if (!once.first(c->device)) return KM_OK;
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&kf::kmmf_encoder_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kf::ENC_LDS_FLOATS * 4));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&kf::kmmf_encoder_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kf::ENC_LDS_FLOATS * 4));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&kf::kmmf_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kf::ROLL_LDS_FLOATS * 4));
+    return KM_OK;
+}
+
+// both streams of DualStreamEncoder for the windows of a step's table: TWO launches over all `entries` each (T_i <= 16, then 17 ..
+// 32), whatever the table holds.  ring_mel / ring_emo (streams, cap, dim); xm, xe (entries, T, 256)
+int launch_kmmf_encoder_ragged(Context* c, const float* ring_mel, const float* ring_emo, const int4* table, int64_t entries, int64_t T,
+                               int64_t cap, float* xm, float* xe, void* stream) {
+    kf::EncRagArgs r{};
+    kf::EncArgs& a = r;
+    a.in0 = ring_mel; a.in1 = ring_emo; a.in_dim0 = c->kmm.mel_dim; a.in_dim1 = c->kmm.emotion_dim;
+    a.blob = dvp(c, "kmf_enc"); a.stream_floats = kmmf::enc_stream_floats(c->kmm.num_encoder_layers); a.layers = c->kmm.num_encoder_layers;
+    a.kvalid = nullptr; a.out0 = xm; a.out1 = xe; a.B = (int)entries; a.T = (int)T; a.groups = (int)entries;
+    r.table = table; r.cap = (int)cap;
+    const dim3 grid((unsigned)(2 * entries));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(kf::kmmf_encoder_kernel<true, true>), grid, dim3(kf::ENTH), kf::ENC_LDS_FLOATS * 4, (hipStream_t)stream, r);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(kf::kmmf_encoder_kernel<false, true>), grid, dim3(kf::ENTH), kf::ENC_LDS_FLOATS * 4, (hipStream_t)stream, r);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+// the serial chains of a step, one workgroup per stream: tail.state (streams, state_floats) or null, tail.out / tail.raw (streams,
+// max_rows, 52); nstep, counter and prev are the engine's per-stream buffers
+int launch_kmmf_chain(Context* c, const float* xm, const float* xe, int64_t streams, int64_t max_rows, int64_t T, const KmmTail& tail,
+                      const int* nstep, const long long* counter, float* prev, void* stream) {
+    const km_koemorph_config& k = c->kmm;
+    kf::ChainArgs r{};
+    kf::DecArgs& a = r.d;
+    a.xm = xm; a.xe = xe; a.emb = dvp(c, "query_embeddings.query_embeddings");
+    a.cw0 = dvp(c, "query_embeddings.conditioning_net.0.weight"); a.cb0 = dvp(c, "query_embeddings.conditioning_net.0.bias");
+    a.cw3 = dvp(c, "query_embeddings.conditioning_net.3.weight"); a.cb3 = dvp(c, "query_embeddings.conditioning_net.3.bias");
+    a.prev = nullptr; a.cross = dvp(c, "kmf_cross"); a.cross_layers = k.num_attention_layers;
+    a.dec = dvp(c, "kmf_dec"); a.dec_layers = k.decoder_layers;
+    a.act = k.decoder_activation == 0 ? 1 : (k.decoder_activation == 1 ? 2 : (k.decoder_activation == 2 ? 3 : 4));
+    a.kvalid = nullptr; a.causal = k.causal; a.window = k.window_size; a.attn = nullptr; a.B = (int)(streams * max_rows); a.T = (int)T;
+    a.tail = tail;
+    r.max_rows = (int)max_rows; r.nstep = nstep; r.counter = counter; r.prev = prev;
+    r.state_floats = tail.smooth < 0 ? 0 : (tail.smooth == 0 ? tail.NB : tail.window * tail.NB + 1);
+    if (r.state_floats > kf::ROLL_STATE)
+        return fail(KM_ERR_UNSUPPORTED, "stream chain kernel: smoothing window %d, at most 16", tail.window);
+    hipLaunchKernelGGL(kf::kmmf_chain_kernel, dim3((unsigned)streams), dim3(kf::NTH), kf::ROLL_LDS_FLOATS * 4, (hipStream_t)stream, r);
     HIP_TRY(hipGetLastError());
     return KM_OK;
 }

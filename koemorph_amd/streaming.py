@@ -29,10 +29,14 @@ its ``emotion`` matrix is what ``tick`` / ``step`` read (km_emotion_stream_*).
 
 ``LegacyStreamEngine`` is the counterpart for ``SimplifiedKoeMorphModel``: the reference's consuming FIFO
 (scripts/rt_simplified.py:46-97) per stream instead of a sliding ring, no EMA, no emotion input (km_legacy_stream_*).
+
+``KoeMorphStreams`` serves the multi-layer ``KoeMorphModel`` at the row level: per stream the last rows of both feature tracks, the
+frame counter, the previous frame and the smoother state on the device, one ragged four-launch ``step`` per tick (km_koemorph_stream_*).
 """
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from typing import Optional, Tuple
 
 import torch
@@ -382,6 +386,202 @@ class LegacyStreamEngine:
             self._g_counts_full = True
         self._graph.replay()
         return self.out, self.ready
+
+
+class KoeMorphStreams:
+    """Live streams of a ``KoeMorphModel`` (km_koemorph_stream_*): ``n_streams`` independent streams, out of phase, each with its
+    last ``context_frames - 1 + max_rows`` feature rows, its frame counter, its previous rendered frame and its own smoother state
+    resident on the device.
+
+    The law: a ``step`` that gives stream s ``n_s`` new rows (0 .. ``max_rows``) renders ``n_s`` frames for it, in order.  Frame i,
+    counted since the stream's last reset, is ``model.forward`` at B = 1 on the stream's rows ``i - T_i + 1 .. i``,
+    ``T_i = min(i + 1, context_frames)`` (a dense window, no ``audio_mask``), ``prev_blendshapes`` = the stream's previous frame
+    (frame 0 has none and runs as ``inference_step(prev=None)``), with the stream's own smoother state -- bit for bit.  Streams share
+    nothing; a stream with ``n_s = 0`` keeps everything and its rows of the outputs keep what they held.  The model's own
+    ``_smoother_state`` is neither read nor written.
+
+    One ``step`` is four launches whatever the sizes and phases are, allocates nothing in the library and reads nothing back, so it
+    can be captured (``capture`` / ``replay``).  The model's current weights are used: a changed parameter is uploaded by the next
+    ``step`` (not by ``replay``) and every stream keeps its rows, counter, previous frame and state.
+
+    Served: the fused width (d_model 256, 8 heads, decoder width 128, ``mel_dim`` / ``emotion_dim`` multiples of 16, at least one
+    attention layer), ``context_frames <= 32``; anything else raises ``KoeMorphError`` (KM_ERR_UNSUPPORTED) here."""
+
+    def __init__(self, model, n_streams: int, context_frames: Optional[int] = None, max_rows: int = 1, apply_smoothing: bool = True,
+                 apply_constraints: bool = True):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise _lib.KoeMorphError(_lib.KM_ERR_WORKSPACE, "km_koemorph_stream_create: allocates, so not inside a stream capture: "
+                                     "create the engine first")
+        lib, h, dev = model._handle()
+        self.model, self.n_streams, self.max_rows = model, int(n_streams), int(max_rows)
+        self.context_frames = model._context(context_frames)
+        self.apply_smoothing, self.apply_constraints = bool(apply_smoothing), bool(apply_constraints)
+        self._lib, self._h, self.device = lib, h, dev
+        with torch.cuda.device(dev):
+            check(lib.km_koemorph_stream_create(h, self.n_streams, self.context_frames, self.max_rows, 1 if apply_smoothing else 0,
+                                                1 if apply_constraints else 0))
+        self.plan = koemorph_stream_plan(lib, h, self.n_streams, self.context_frames, self.max_rows)
+        nb = model.num_blendshapes
+        self.out = torch.zeros(self.n_streams, self.max_rows, nb, device=dev)
+        self.raw = torch.zeros(self.n_streams, self.max_rows, nb, device=dev)
+        self.rendered = torch.zeros(self.n_streams, dtype=torch.int32, device=dev)
+        self._graph = None
+        self._g_mel = self._g_emo = self._g_counts = None
+        self._open = True
+        model._stream_engine = weakref.ref(self)           # a handle holds ONE engine: a later one on this model replaces this one
+
+    def _live(self) -> None:
+        owner = getattr(self.model, "_stream_engine", None)
+        if not self._open or owner is None or owner() is not self:
+            raise RuntimeError("this KoeMorphStreams was closed, or replaced by a later one on the same model")
+
+    def close(self) -> None:
+        """Free the engine's device memory; the model and its handle stay."""
+        if not getattr(self, "_open", False):
+            return
+        self._open = False
+        self._graph = None
+        owner = getattr(self.model, "_stream_engine", None)
+        if owner is not None and owner() is self:              # a replaced engine's memory went with the second create
+            self.model._stream_engine = None
+            with torch.cuda.device(self.device):
+                torch.cuda.synchronize(self.device)
+                check(self._lib.km_koemorph_stream_destroy(self._h))
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def check_rows(n_streams: int, max_rows: int, mel_dim: int, emotion_dim: int, mel_rows: torch.Tensor, emotion_rows: torch.Tensor,
+                   counts: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """What ``step`` accepts, judged before any device work: (N, r, mel_dim) and (N, r, n <= emotion_dim) rows with 1 <= r <=
+        ``max_rows`` -- (N, dim) is one row per stream -- and (N,) int32 counts.  Returns the two as 3-d tensors; ValueError otherwise."""
+        if mel_rows.dim() == 2:
+            mel_rows = mel_rows.unsqueeze(1)
+        if emotion_rows.dim() == 2:
+            emotion_rows = emotion_rows.unsqueeze(1)
+        if mel_rows.dim() != 3 or emotion_rows.dim() != 3 or mel_rows.shape[:2] != emotion_rows.shape[:2]:
+            raise ValueError(f"expected (N, rows, mel_dim) and (N, rows, emotion_dim), got {tuple(mel_rows.shape)} and {tuple(emotion_rows.shape)}")
+        if mel_rows.shape[0] != n_streams:
+            raise ValueError(f"expected rows of {n_streams} streams, got {mel_rows.shape[0]}")
+        if not 1 <= mel_rows.shape[1] <= max_rows:
+            raise ValueError(f"{mel_rows.shape[1]} rows per stream, the engine takes 1 .. {max_rows} per step")
+        if mel_rows.shape[2] != mel_dim:
+            raise ValueError(f"mel rows are {mel_rows.shape[2]} wide, the model's mel_dim is {mel_dim}")
+        if emotion_rows.shape[2] > emotion_dim:
+            raise ValueError(f"emotion rows are {emotion_rows.shape[2]} wide, the model's emotion_dim is {emotion_dim}")
+        if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (n_streams,)):
+            raise ValueError(f"expected ({n_streams},) int32 counts")
+        return mel_rows, emotion_rows
+
+    def _prepare(self, mel_rows, emotion_rows, counts):
+        """-> (N, max_rows, dim) float32 contiguous rows on the device and the counts (None: every stream brings every row)."""
+        m = self.model
+        mel, emo = self.check_rows(self.n_streams, self.max_rows, m.mel_dim, m.emotion_dim, mel_rows, emotion_rows, counts)
+        r = mel.shape[1]
+        mel = mel.to(self.device, torch.float32)
+        emo = m._pad_emotion_rows(emo.to(self.device, torch.float32), m.emotion_dim)
+        if r < self.max_rows:
+            mel = torch.nn.functional.pad(mel, (0, 0, 0, self.max_rows - r))
+            emo = torch.nn.functional.pad(emo, (0, 0, 0, self.max_rows - r))
+            counts = (torch.full((self.n_streams,), r, dtype=torch.int32, device=self.device) if counts is None
+                      else counts.to(self.device).clamp(max=r))
+        elif counts is not None:
+            counts = counts.to(self.device)
+        return mel.contiguous(), emo.contiguous(), None if counts is None else counts.contiguous()
+
+    def _result(self):
+        return {"blendshapes": self.out, "raw_blendshapes": self.raw, "rendered": self.rendered}
+
+    def step(self, mel_rows: torch.Tensor, emotion_rows: torch.Tensor, counts: Optional[torch.Tensor] = None):
+        """mel_rows (N, r, mel_dim), emotion_rows (N, r, n <= emotion_dim; zero-padded on the right as ``render`` pads), r <= max_rows
+        -- (N, dim): one row per stream --, counts (N,) int32 on the device: how many of its r rows each stream brings (default all)
+        -> {"blendshapes": (N, max_rows, 52), "raw_blendshapes": ..., "rendered": (N,) int32}, owned by the engine: row (s, j) is
+        stream s's j-th new frame for j < rendered[s]; the other rows keep what they held."""
+        mel, emo, cnt = self._prepare(mel_rows, emotion_rows, counts)
+        self._live()
+        self.model._handle()                                     # uploads changed weights; the streams' state is kept
+        with torch.cuda.device(self.device):
+            check(self._lib.km_koemorph_stream_step(self._h, _ptr(mel), _ptr(emo), _ptr(cnt) if cnt is not None else None, _ptr(self.out),
+                                                    _ptr(self.raw), _ptr(self.rendered), _stream_ptr(self.device)))
+        return self._result()
+
+    def reset_streams(self, mask: torch.Tensor) -> None:
+        """mask (N,) bool or uint8: those streams become freshly created ones (counter 0, no previous frame, zero state)."""
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (self.n_streams,):
+            raise ValueError(f"expected a ({self.n_streams},) bool or uint8 mask")
+        self._live()
+        m8 = mask.to(self.device, torch.uint8).contiguous()
+        check(self._lib.km_koemorph_stream_reset(self._h, _ptr(m8), _stream_ptr(self.device)))
+
+    def reset(self) -> None:
+        self._live()
+        check(self._lib.km_koemorph_stream_reset(self._h, None, _stream_ptr(self.device)))
+
+    def frames(self) -> torch.Tensor:
+        """(N,) int64: every stream's frames since its last reset; a copy."""
+        self._live()
+        out = torch.empty(self.n_streams, dtype=torch.int64, device=self.device)
+        check(self._lib.km_koemorph_stream_frames(self._h, _ptr(out), _stream_ptr(self.device)))
+        return out
+
+    def smoother_state(self) -> Optional[torch.Tensor]:
+        """(N, state floats per stream): the streams' smoother states in ``forward``'s layout for B = 1; None without smoothing."""
+        if not self.plan["state_floats"] or not self.apply_smoothing:
+            return None
+        self._live()
+        out = torch.empty(self.n_streams, self.plan["state_floats"], device=self.device)
+        check(self._lib.km_koemorph_stream_state(self._h, _ptr(out), None, _stream_ptr(self.device)))
+        return out
+
+    # ---- hipGraph replay ------------------------------------------------------------------------
+    def capture(self, max_rows: Optional[int] = None) -> None:
+        """Record one step with per-stream counts on static input buffers of ``max_rows`` (default: the engine's) rows per stream."""
+        r = self.max_rows if max_rows is None else int(max_rows)
+        if not 1 <= r <= self.max_rows:
+            raise ValueError(f"max_rows {r} outside 1 .. {self.max_rows}")
+        self._live()
+        dev, m = self.device, self.model
+        self.model._handle()
+        self._g_rows = r
+        self._g_mel = torch.zeros(self.n_streams, self.max_rows, m.mel_dim, device=dev)
+        self._g_emo = torch.zeros(self.n_streams, self.max_rows, m.emotion_dim, device=dev)
+        self._g_counts = torch.zeros(self.n_streams, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            check(self._lib.km_koemorph_stream_step(self._h, _ptr(self._g_mel), _ptr(self._g_emo), _ptr(self._g_counts), _ptr(self.out),
+                                                    _ptr(self.raw), _ptr(self.rendered), _stream_ptr(dev)))
+        self._graph = g
+
+    def replay(self, mel_rows: torch.Tensor, emotion_rows: torch.Tensor, counts: Optional[torch.Tensor] = None):
+        """One captured step; counts None: every stream brings all its rows."""
+        if self._graph is None:
+            raise RuntimeError("capture() first")
+        self._live()
+        m = self.model
+        mel, emo = self.check_rows(self.n_streams, self._g_rows, m.mel_dim, m.emotion_dim, mel_rows, emotion_rows, counts)
+        r, n = mel.shape[1], emo.shape[2]
+        self._g_mel[:, :r].copy_(mel, non_blocking=True)
+        if n < m.emotion_dim:
+            self._g_emo[:, :r, n:].zero_()
+        self._g_emo[:, :r, :n].copy_(emo, non_blocking=True)
+        if counts is not None:
+            self._g_counts.copy_(counts.clamp(max=r), non_blocking=True)
+        else:
+            self._g_counts.fill_(r)
+        self._graph.replay()
+        return self._result()
+
+
+def koemorph_stream_plan(lib, h, n_streams: int, context_frames: int, max_rows: int) -> dict:
+    """km_koemorph_stream_plan as a dict (host only)."""
+    out = (C.c_int64 * 6)()
+    check(lib.km_koemorph_stream_plan(h, n_streams, context_frames, max_rows, out))
+    return dict(zip(("supported", "ring_rows", "launches", "device_floats", "chain_lds_bytes", "state_floats"), (int(v) for v in out)))
 
 
 def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 0.3, sample_rate: int = 16000,

@@ -75,6 +75,13 @@ def cycle(i):
         assert m.rollout_plan(2, 12, 5)["route"] == 0 and mf.rollout_plan(2, 20, 9)["route"] == 1
         m.rollout(torch.randn(2, 12, 80, device="cuda"), torch.randn(2, 12, 8, device="cuda"), context_frames=5)
         mf.rollout(torch.randn(2, 20, 80, device="cuda"), torch.randn(2, 20, 256, device="cuda"), context_frames=9, chunk_frames=4)
+    # one stream engine on the default width: create, one step, reset; the handle's km_destroy frees the group (no close())
+    from koemorph_amd.streaming import KoeMorphStreams
+    ks = KoeMorphStreams(mf, 3, context_frames=9, max_rows=2)
+    ks.step(torch.randn(3, 2, 80, device="cuda"), torch.randn(3, 2, 256, device="cuda"))
+    ks.reset()
+    ks._open = False                                       # the engine object is dropped without close(): km_destroy frees its group
+    del ks
     del tr, eng, g, m, mf, audio, emo
     gc.collect(); torch.cuda.empty_cache()
 
