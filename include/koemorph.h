@@ -624,6 +624,59 @@ int km_koemorph_stream_destroy(km_handle h);
 int km_koemorph_stream_frames(km_handle h, int64_t* frames_dev, void* stream);
 int km_koemorph_stream_state(km_handle h, float* state_dev, float* prev_dev, void* stream);
 
+/* ---- KoeMorphModel: the rows of the streams from pushed audio -------------------------------------------
+ * The audio front of the engine above: 16 kHz samples are pushed per stream and the mel and emotion rows km_koemorph_stream_step takes
+ * come out with their per-stream counts; samples, counters and rows stay on the device.  THE LAW.
+ *   Clock     hop = int(16000 / fps) (float64).  Stream s has received n_s samples since creation or its last reset; frame k is due as
+ *             soon as n_s >= (k + 1) * hop.  After a push the stream has K = n_s / hop frames; the push renders frames c_s .. K - 1, in
+ *             order (c_s: the count before it).  Integer arithmetic: the two tracks never drift apart or behind the audio.  Supported:
+ *             hop >= 257 and fps >= 10 (30 fps: 533, 60 fps: 266); anything else is KM_ERR_UNSUPPORTED at creation.  max_rows =
+ *             max_samples / hop + 1 bounds the frames of a push.
+ *   Mel row k the row of the STFT frame centred on sample k * hop of the stream, in the configuration of MelSpectrogramExtractor
+ *             (16000 Hz, 512 points, mel_dim HTK filters 80 .. 8000 Hz, "window" normalisation, log(mel + 1e-8)), reflected at the
+ *             stream's first sample only: with hop >= 257 every frame has its 512 samples when it is due.  A function of the stream's
+ *             samples alone -- not of the pushes they came in, of the other streams or of where the ring wraps.
+ *   Emotion row k  a push that leaves stream s with new frames sets the window: a0 = the smallest multiple of 160 >= n_s - W (0 while
+ *             n_s <= W, W = int(emotion_window_s * 16000)), len = n_s - a0, m = a0 / 160, nf = (len - 960) / 160 + 1 (0 for len < 960).
+ *             The window's descriptors are the rows of km_egemaps_llds(samples a0 .. n_s - 1, normalize 1, fps 0).  Row k sits at
+ *             p = (double)(k * hop) / 160.0, j = floor(p) - m, w = p - floor(p): frame 0 for j < 0 (creation rules it out), the last
+ *             frame for j >= nf - 1, frame j for w == 0, otherwise fmaf((float)w, b - a, a) between frames j and j + 1, with
+ *             km_egemaps_llds's exception for columns 10-24.  The row is emotion_dim wide, the descriptors first, zeros to the right;
+ *             a window without a frame gives a row of zeros.  Emotion rows depend on the push schedule: the window ends where the push ends.
+ *   km_koemorph_audio_plan      host only, the function create itself uses: out[0] 1 supported / 0 not (the reason is km_last_error's
+ *                        text; the other values are 0), out[1] hop, out[2] max_rows, out[3] ring samples per stream (W + max_samples),
+ *                        out[4] W, out[5] frames of a full window, out[6] launches of a push (7), out[7] bytes of the engine's
+ *                        state on the device (rings, counters, tables, frame records; the two constant plans come on top)
+ *   km_koemorph_audio_schedule  host only, the arithmetic of the advance kernel for one stream: samples before, samples pushed, the life's
+ *                        origin in the ring -> out[0]
+ *                        first new frame, out[1] new frames, out[2] a0, out[3] len, out[4] nf, out[5] m, out[6] samples after, out[7..9]
+ *                        the window's slot for the ragged eGeMAPS kernels: stream (-1: nothing to compute), ring index of a0, nf
+ *   km_koemorph_audio_create    a buffer group of its own on the handle, with a mel plan and an eGeMAPS plan.  Allocates and synchronises:
+ *                        outside any stream capture.  A second create replaces the first; km_destroy frees the group.  Checks, each
+ *                        refusal naming the entry point and the value: n_streams >= 1, a known feature set, W >= max_samples + hop +
+ *                        1120 (KM_ERR_INVALID_ARG); a window of at most 2048 frames, emotion_dim at least the descriptor count
+ *                        (KM_ERR_UNSUPPORTED)
+ *   km_koemorph_audio_rows      samples_dev (n_streams, M), 1 <= M <= max_samples; counts_dev (n_streams) int32 or NULL = M, clamped to
+ *                        0 .. M -> mel_rows_dev (n_streams, max_rows, mel_dim), emotion_rows_dev (n_streams, max_rows, emotion_dim),
+ *                        row_counts_dev (n_streams) int32: row (s, j) is frame c_s + j for j < row_counts[s], the others untouched.
+ *                        SEVEN launches on `stream`, one linear chain (advance, mel rows, the four record kernels of the ragged
+ *                        eGeMAPS chain, descriptor rows); no allocation, synchronisation or readback: capturable, also in front of
+ *                        km_koemorph_stream_step on the same three buffers
+ *   km_koemorph_audio_reset     one launch: the streams with mask_dev[s] != 0 (NULL: all) start again at sample 0; the ring's write position
+ *                        stays where it stands and becomes the new life's origin (sample i of a life at (origin + i) mod ring)
+ *   km_koemorph_audio_samples   totals_dev (n_streams) int64 <- n_s
+ *   km_koemorph_audio_destroy   frees the group (km_destroy does the same on its way) */
+int km_koemorph_audio_plan(km_handle h, int64_t n_streams, double fps, double emotion_window_s, int64_t max_samples, int32_t feature_set,
+                           int64_t out[8]);
+int km_koemorph_audio_schedule(int64_t samples_before, int64_t pushed, int32_t hop, int64_t window_samples, int64_t ring_len, int64_t origin,
+                               int32_t stream, int64_t out[10]);
+int km_koemorph_audio_create(km_handle h, int64_t n_streams, double fps, double emotion_window_s, int64_t max_samples, int32_t feature_set);
+int km_koemorph_audio_rows(km_handle h, const float* samples_dev, int64_t M, const int32_t* counts_dev, float* mel_rows_dev,
+                           float* emotion_rows_dev, int32_t* row_counts_dev, void* stream);
+int km_koemorph_audio_reset(km_handle h, const uint8_t* mask_dev, void* stream);
+int km_koemorph_audio_samples(km_handle h, int64_t* totals_dev, void* stream);
+int km_koemorph_audio_destroy(km_handle h);
+
 /* ---- streaming: many concurrent speaker streams, state resident on the device -------------------------
  * Replaces, for all streams of this GPU at once, MelAudioBuffer.add_audio_frame / get_current_audio
  * (src/features/mel_sliding_window.py:70-140), MelSlidingWindowExtractor.process_audio_frame (:252-324) and

@@ -179,6 +179,13 @@ SIGNATURES = {
     "km_koemorph_stream_destroy": (C.c_int, [_h]),
     "km_koemorph_stream_frames": (C.c_int, [_h, _p, _p]),
     "km_koemorph_stream_state": (C.c_int, [_h, _p, _p, _p]),
+    "km_koemorph_audio_plan": (C.c_int, [_h, _i64, C.c_double, C.c_double, _i64, _i32, C.POINTER(_i64)]),
+    "km_koemorph_audio_schedule": (C.c_int, [_i64, _i64, _i32, _i64, _i64, _i64, _i32, C.POINTER(_i64)]),
+    "km_koemorph_audio_create": (C.c_int, [_h, _i64, C.c_double, C.c_double, _i64, _i32]),
+    "km_koemorph_audio_rows": (C.c_int, [_h, _p, _i64, _p, _p, _p, _p, _p]),
+    "km_koemorph_audio_reset": (C.c_int, [_h, _p, _p]),
+    "km_koemorph_audio_samples": (C.c_int, [_h, _p, _p]),
+    "km_koemorph_audio_destroy": (C.c_int, [_h]),
     "km_stream_create": (C.c_int, [_h, _i64, C.c_double, C.c_double, C.POINTER(KMMelConfig)]),
     "km_stream_push": (C.c_int, [_h, _p, _i64, _p]),
     "km_stream_tick": (C.c_int, [_h, _p, _p, _p, _p]),

@@ -24,7 +24,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 LIB_PATH = os.path.join(LIB_DIR, "libkoemorph_hip.so")
-SOURCES = ["km_host.cpp", "km_wire.cpp", "km_core.hip", "km_mel.hip", "km_generic.hip", "km_core256w.hip", "km_core128.hip", "km_koemorph.hip", "km_koemorph_rollout.hip", "km_koemorph_stream.hip", "km_kmmf.hip", "km_train.hip", "km_trainp.hip", "km_legacy_train.hip", "km_legacy_stream.hip", "km_egemaps.hip", "km_egemaps_window.hip", "km_egemaps_lld.hip", "km_prosody.hip", "km_emotion_stream.hip", "km_emotion_clip.hip", "km_data.hip", "km_metrics.hip", "km_attn_stats.hip", "km_loss_terms.hip", "km_resample.hip", "km_api.hip", "km_api_train.hip", "km_api_stream.hip", "km_api_seq.hip", "km_seq_assemble.hip", "km_clip_assemble.hip"]
+SOURCES = ["km_host.cpp", "km_wire.cpp", "km_core.hip", "km_mel.hip", "km_generic.hip", "km_core256w.hip", "km_core128.hip", "km_koemorph.hip", "km_koemorph_rollout.hip", "km_koemorph_stream.hip", "km_koemorph_audio.hip", "km_kmmf.hip", "km_train.hip", "km_trainp.hip", "km_legacy_train.hip", "km_legacy_stream.hip", "km_egemaps.hip", "km_egemaps_window.hip", "km_egemaps_lld.hip", "km_prosody.hip", "km_emotion_stream.hip", "km_emotion_clip.hip", "km_data.hip", "km_metrics.hip", "km_attn_stats.hip", "km_loss_terms.hip", "km_resample.hip", "km_api.hip", "km_api_train.hip", "km_api_stream.hip", "km_api_seq.hip", "km_seq_assemble.hip", "km_clip_assemble.hip"]
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "koemorph.h")]
 
 

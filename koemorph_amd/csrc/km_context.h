@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -231,6 +232,20 @@ struct KoeMorphStreams {
     DevBuf<float> xm, xe;                // (streams * max_rows, context, 256) encodings of the step's windows
 };
 
+// km_koemorph_audio_create: the audio front of the stream engine (km_koemorph_audio.hip); streams == 0 until created
+struct EgmPlanDelete { void operator()(void* p) const; };   // km_egemaps_plan_destroy
+struct KoeMorphAudio {
+    int64_t streams = 0, max_samples = 0, ring_len = 0, W = 0, max_nf = 0, max_rows = 0;
+    int hop = 0, rows_tile = 0, feature_set = 0;
+    std::unique_ptr<MelPlan> mel;                // the 512-point plan of the stream's frame rate: owned here, so destroy frees its mirrors
+    std::unique_ptr<void, EgmPlanDelete> egm;    // km_egemaps_plan_create
+    DevBuf<float> ring;                          // (streams, ring_len) sample i of a life at i mod ring_len
+    DevBuf<long long> total;                     // (streams) samples since the stream's reset
+    DevBuf<int> origin;                          // (streams) ring index of the life's sample 0
+    DevBuf<char> table, slots;                   // (streams) KmaEntry / EgmSlot of the push (km_koemorph_audio.h)
+    DevBuf<float> scale, rec;                    // (streams), (streams, max_nf, 36): the ragged eGeMAPS kernels' peak scales and frame records
+};
+
 // two-deep pipeline across calls (km_forward_audio_pipelined)
 struct PipeSlot {
     DevBuf<float> melpow; DevBuf<unsigned> melmax; DevBuf<float> zemo;
@@ -281,6 +296,7 @@ struct Context {
     Pipeline pipe;                               // km_forward_audio_pipelined
     RolloutBufs ro;                              // kind 2: km_koemorph_rollout
     KoeMorphStreams ks;                          // kind 2: km_koemorph_stream_*
+    KoeMorphAudio ka;                            // kind 2: km_koemorph_audio_*
     bool stage_timing = false;
     DevEvent stage_ev[6];                        // emo b/e, mel e, core b/e
     bool melmax_dirty = true;      // ws.melmax may hold stale maxima (see launch_mel_power)

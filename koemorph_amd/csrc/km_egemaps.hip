@@ -681,13 +681,14 @@ static EgmArgs egm_args(const EgmPlan* p, const float* audio, int64_t L, int nf,
 // The five kernels over ragged windows that live in stream rings (km_emotion_stream.hip): fixed grids of max_nf frames x
 // n_slots windows, everything else from the slot table on the device.  long_windows: the object was made for windows beyond 2048
 // frames (km_emotion_*_create_long): max_nf up to 6548, and the two per-window kernels run at their long tier for every slot.
-int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
-                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st, bool long_windows, int feature_set) {
+// The first four of them -- peak, frame, pitch track, voiced -- under the caller's name: the frame records of every slot's window
+static int ragged_records(const char* who, void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
+                          float* scale_dev, float* rec_dev, hipStream_t st, bool long_windows, int feature_set) {
     using namespace egm;
-    if (!set_known(feature_set)) return fail(KM_ERR_INVALID_ARG, "egm_ragged_functionals: feature set %d", feature_set);
-    if (!plan || !rings_dev || !slots_dev || !scale_dev || !rec_dev || !out_dev || n_slots < 1 || n_slots > 65535 || max_nf < 1 ||
+    if (!set_known(feature_set)) return fail(KM_ERR_INVALID_ARG, "%s: feature set %d", who, feature_set);
+    if (!plan || !rings_dev || !slots_dev || !scale_dev || !rec_dev || n_slots < 1 || n_slots > 65535 || max_nf < 1 ||
         max_nf > (long_windows ? LongTier::MAXF : ShortTier::MAXF) || ring_len < 1 || ring_len > (1 << 30))
-        return fail(KM_ERR_INVALID_ARG, "egm_ragged_functionals: bad argument");
+        return fail(KM_ERR_INVALID_ARG, "%s: bad argument", who);
     EgmArgs a = egm_args(static_cast<EgmPlan*>(plan), rings_dev, 0, 0, scale_dev, rec_dev);
     a.rec_frames = max_nf; a.slots = slots_dev; a.ring_len = (int)ring_len;
     hipLaunchKernelGGL(egm_peak_kernel<true>, dim3((unsigned)n_slots), dim3(256), 0, st, rings_dev, (int64_t)0, slots_dev, (int)ring_len, scale_dev);
@@ -695,6 +696,21 @@ int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len,
     hipLaunchKernelGGL(frame_kernel, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
     if (const int rc = egm_track(rec_dev, 0, max_nf, slots_dev, n_slots, long_windows, st)) return rc;
     hipLaunchKernelGGL(egm_voiced_kernel<true>, dim3((unsigned)max_nf, (unsigned)n_slots), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return KM_OK;
+}
+
+int egm_ragged_records(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf, float* scale_dev,
+                       float* rec_dev, hipStream_t st, bool long_windows, int feature_set) {
+    return ragged_records("egm_ragged_records", plan, rings_dev, ring_len, slots_dev, n_slots, max_nf, scale_dev, rec_dev, st, long_windows, feature_set);
+}
+
+int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
+                           float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st, bool long_windows, int feature_set) {
+    if (!out_dev) return fail(KM_ERR_INVALID_ARG, "egm_ragged_functionals: bad argument");
+    if (const int rc = ragged_records("egm_ragged_functionals", plan, rings_dev, ring_len, slots_dev, n_slots, max_nf, scale_dev, rec_dev, st,
+                                      long_windows, feature_set))
+        return rc;
     return egm_functional(rec_dev, 0, max_nf, slots_dev, n_slots, out_dev, long_windows, st, feature_set);
 }
 

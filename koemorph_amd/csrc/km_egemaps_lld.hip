@@ -26,17 +26,7 @@
 namespace km {
 
 namespace egm {
-constexpr int LLD_CORE = 128;                 // frames a tile smooths
-constexpr int LLD_STAGE = LLD_CORE + 4;       // ... and stages: two frames of halo a side
-constexpr int LLD_FIRST_NZ = 10;              // eGeMAPS columns 0-9: plain average; 10: semitone of the smoothed F0; 11-24: masked non-zero average
-
-// eGeMAPS column of column c of the set, and the record field an eGeMAPS column is smoothed from (10: the F0 itself)
-template <int SET> __host__ __device__ constexpr int lld_ecol(int c) {
-    return SET == SET_EGEMAPS ? c : c < 5 ? c : c < 15 ? c + 5 : c == 15 ? 21 : c == 16 ? 22 : 24;
-}
-__host__ __device__ constexpr int lld_field(int e) {
-    return e < LLD_FIRST_NZ ? e : e == 10 ? (int)R_F0 : e < 16 ? R_JIT + (e - 11) : ((e - 16) % 3 == 0 ? R_F : (e - 16) % 3 == 1 ? R_BW : R_FAMP) + (e - 16) / 3;
-}
+// (the tile sizes, lld_ecol and lld_field: km_egemaps_lld.h, shared with the stream rows of km_koemorph_audio.hip)
 constexpr bool lld_gemaps_drops(int e) { return (e >= 5 && e <= 9) || e == 20 || e == 23; }
 constexpr bool lld_columns_agree() {
     int n = 0;

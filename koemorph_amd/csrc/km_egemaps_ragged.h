@@ -24,4 +24,9 @@ struct EgmSlot {
 int egm_ragged_functionals(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf,
                            float* scale_dev, float* rec_dev, float* out_dev, hipStream_t st, bool long_windows = false, int feature_set = 0);
 
+// Its first four launches alone (peak, frame, pitch track, voiced): the frame records of every slot's window in rec_dev, for a caller
+// that reduces them itself (km_koemorph_audio.hip writes descriptor rows).  egm_ragged_functionals is this call plus the functional kernel.
+int egm_ragged_records(void* plan, const float* rings_dev, int64_t ring_len, const EgmSlot* slots_dev, int n_slots, int max_nf, float* scale_dev,
+                       float* rec_dev, hipStream_t st, bool long_windows = false, int feature_set = 0);
+
 }  // namespace km

@@ -32,6 +32,10 @@ its ``emotion`` matrix is what ``tick`` / ``step`` read (km_emotion_stream_*).
 
 ``KoeMorphStreams`` serves the multi-layer ``KoeMorphModel`` at the row level: per stream the last rows of both feature tracks, the
 frame counter, the previous frame and the smoother state on the device, one ragged four-launch ``step`` per tick (km_koemorph_stream_*).
+
+``AudioRowStreams`` produces those rows from pushed 16 kHz audio -- per stream a ring of samples and a sample counter on the device, a
+seven-launch ``push`` that gives the mel and eGeMAPS descriptor rows of the frames that became due -- and ``KoeMorphAudioStreams`` puts
+it in front of a ``KoeMorphStreams``: audio in, blendshape frames out (km_koemorph_audio_*).
 """
 from __future__ import annotations
 
@@ -582,6 +586,215 @@ def koemorph_stream_plan(lib, h, n_streams: int, context_frames: int, max_rows: 
     out = (C.c_int64 * 6)()
     check(lib.km_koemorph_stream_plan(h, n_streams, context_frames, max_rows, out))
     return dict(zip(("supported", "ring_rows", "launches", "device_floats", "chain_lds_bytes", "state_floats"), (int(v) for v in out)))
+
+
+def koemorph_audio_plan(lib, h, n_streams: int, fps: float, emotion_window: float, max_samples: int, feature_set: str = "eGeMAPSv02") -> dict:
+    """km_koemorph_audio_plan as a dict (host only): ``supported`` 0 leaves the reason in ``km_last_error``."""
+    out = (C.c_int64 * 8)()
+    check(lib.km_koemorph_audio_plan(h, int(n_streams), float(fps), float(emotion_window), int(max_samples), feature_set_code(feature_set), out))
+    return dict(zip(("supported", "hop", "max_rows", "ring_len", "window_samples", "window_frames", "launches", "device_bytes"),
+                    (int(v) for v in out)))
+
+
+def check_samples(n_streams: int, max_samples: int, samples: torch.Tensor, counts: Optional[torch.Tensor] = None) -> None:
+    """What ``push`` accepts, judged before any device work: (N, M) samples with 1 <= M <= max_samples and (N,) int32 counts."""
+    if samples.dim() != 2 or samples.shape[0] != n_streams:
+        raise ValueError(f"expected ({n_streams}, M) samples, got {tuple(samples.shape)}")
+    if not 1 <= samples.shape[1] <= max_samples:
+        raise ValueError(f"{samples.shape[1]} samples per stream, the engine takes 1 .. {max_samples} per push")
+    if counts is not None and (counts.dtype != torch.int32 or tuple(counts.shape) != (n_streams,)):
+        raise ValueError(f"expected ({n_streams},) int32 counts")
+
+
+class AudioRowStreams:
+    """The rows of ``KoeMorphStreams.step`` from pushed 16 kHz audio (km_koemorph_audio_*): per stream a ring of samples and a sample
+    counter on the device; a ``push`` is seven launches and gives the mel and emotion rows of the frames that became due, and their counts.
+
+    The law: ``hop = int(16000 / fps)``; frame k of a stream is due as soon as the stream holds ``(k + 1) * hop`` samples, so a push that
+    takes it from ``n0`` to ``n`` samples renders frames ``n0 // hop .. n // hop - 1``.  Mel row k is the row of the STFT frame centred on
+    sample ``k * hop`` in ``MelSpectrogramExtractor``'s configuration, reflected at the stream's first sample only -- a function of the
+    stream's samples alone.  Emotion row k is read, at ``p = k * hop / 160``, from the eGeMAPS descriptors of the stream's last
+    ``emotion_window`` seconds as they stand at the end of the push (tests/koemorph_audio_cases.py restates the window and the grid), so it
+    depends on where the pushes end.  ``emotion_window`` = 2 s is a choice nobody has measured for quality.
+
+    Served: ``hop >= 257`` and ``fps >= 10``, ``int(emotion_window * 16000) >= max_samples + hop + 1120``, a window of at most 2048
+    frames (20.5 s); anything else raises ``KoeMorphError`` here.  A handle holds one: a later one on the same model replaces this one."""
+
+    def __init__(self, model, n_streams: int, fps: float = 30.0, emotion_window: float = 2.0, max_samples: int = 1600,
+                 feature_set: str = "eGeMAPSv02"):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise _lib.KoeMorphError(_lib.KM_ERR_WORKSPACE, "km_koemorph_audio_create: allocates, so not inside a stream capture: "
+                                     "create the engine first")
+        lib, h, dev = model._handle()
+        self.model, self.n_streams, self.fps, self.max_samples = model, int(n_streams), float(fps), int(max_samples)
+        self.emotion_window, self.feature_set = float(emotion_window), feature_set
+        self._lib, self._h, self.device = lib, h, dev
+        code = feature_set_code(feature_set)
+        with torch.cuda.device(dev):
+            check(lib.km_koemorph_audio_create(h, self.n_streams, self.fps, self.emotion_window, self.max_samples, code))
+        self.plan = koemorph_audio_plan(lib, h, self.n_streams, self.fps, self.emotion_window, self.max_samples, feature_set)
+        self.hop, self.max_rows = self.plan["hop"], self.plan["max_rows"]
+        self.mel_rows = torch.zeros(self.n_streams, self.max_rows, model.mel_dim, device=dev)
+        self.emotion_rows = torch.zeros(self.n_streams, self.max_rows, model.emotion_dim, device=dev)
+        self.row_counts = torch.zeros(self.n_streams, dtype=torch.int32, device=dev)
+        self._open = True
+        model._audio_engine = weakref.ref(self)
+
+    def _live(self) -> None:
+        owner = getattr(self.model, "_audio_engine", None)
+        if not self._open or owner is None or owner() is not self:
+            raise RuntimeError("this AudioRowStreams was closed, or replaced by a later one on the same model")
+
+    def close(self) -> None:
+        """Free the engine's device memory; the model and its handle stay."""
+        if not getattr(self, "_open", False):
+            return
+        self._open = False
+        owner = getattr(self.model, "_audio_engine", None)
+        if owner is not None and owner() is self:              # a replaced engine's memory went with the second create
+            self.model._audio_engine = None
+            with torch.cuda.device(self.device):
+                torch.cuda.synchronize(self.device)
+                check(self._lib.km_koemorph_audio_destroy(self._h))
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _prepare(self, samples, counts):
+        check_samples(self.n_streams, self.max_samples, samples, counts)
+        x = samples.to(self.device, torch.float32).contiguous()
+        return x, None if counts is None else counts.to(self.device).contiguous()
+
+    def _launch(self, x, cnt) -> None:
+        check(self._lib.km_koemorph_audio_rows(self._h, _ptr(x), x.shape[1], _ptr(cnt) if cnt is not None else None, _ptr(self.mel_rows),
+                                               _ptr(self.emotion_rows), _ptr(self.row_counts), _stream_ptr(self.device)))
+
+    def push(self, samples: torch.Tensor, counts: Optional[torch.Tensor] = None):
+        """samples (N, M <= max_samples), counts (N,) int32 on the device: how many of its M samples each stream brings (default all,
+        clamped to 0 .. M) -> (mel_rows (N, max_rows, mel_dim), emotion_rows (N, max_rows, emotion_dim), row_counts (N,) int32), owned
+        by the object: row (s, j) is stream s's j-th new frame for j < row_counts[s]; the other rows keep what they held."""
+        x, cnt = self._prepare(samples, counts)
+        self._live()
+        with torch.cuda.device(self.device):
+            self._launch(x, cnt)
+        return self.mel_rows, self.emotion_rows, self.row_counts
+
+    def reset_streams(self, mask: torch.Tensor) -> None:
+        """mask (N,) bool or uint8: those streams start again at sample 0."""
+        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (self.n_streams,):
+            raise ValueError(f"expected a ({self.n_streams},) bool or uint8 mask")
+        self._live()
+        m8 = mask.to(self.device, torch.uint8).contiguous()
+        check(self._lib.km_koemorph_audio_reset(self._h, _ptr(m8), _stream_ptr(self.device)))
+
+    def reset(self) -> None:
+        self._live()
+        check(self._lib.km_koemorph_audio_reset(self._h, None, _stream_ptr(self.device)))
+
+    def samples(self) -> torch.Tensor:
+        """(N,) int64: every stream's samples since its last reset; a copy."""
+        self._live()
+        out = torch.empty(self.n_streams, dtype=torch.int64, device=self.device)
+        check(self._lib.km_koemorph_audio_samples(self._h, _ptr(out), _stream_ptr(self.device)))
+        return out
+
+
+class KoeMorphAudioStreams:
+    """``KoeMorphModel`` streams from pushed audio: an ``AudioRowStreams`` in front of a ``KoeMorphStreams(max_rows = the plan's)`` on
+    one model.  ``push`` is the seven launches of the rows and the four of the step on the same device buffers -- exactly
+    ``KoeMorphStreams.step(mel_rows, emotion_rows, row_counts)``, that engine's law unchanged -- with no allocation, synchronisation
+    or readback, so it can be captured (``capture`` / ``replay``)."""
+
+    def __init__(self, model, n_streams: int, fps: float = 30.0, context_frames: Optional[int] = None, emotion_window: float = 2.0,
+                 max_samples: int = 1600, feature_set: str = "eGeMAPSv02", apply_smoothing: bool = True, apply_constraints: bool = True):
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise _lib.KoeMorphError(_lib.KM_ERR_WORKSPACE, "km_koemorph_audio_create: allocates, so not inside a stream capture: "
+                                     "create the engine first")
+        self.rows = AudioRowStreams(model, n_streams, fps, emotion_window, max_samples, feature_set)
+        try:
+            self.frames_engine = KoeMorphStreams(model, n_streams, context_frames=context_frames, max_rows=self.rows.max_rows,
+                                                 apply_smoothing=apply_smoothing, apply_constraints=apply_constraints)
+        except Exception:
+            self.rows.close()
+            raise
+        self.model, self.n_streams, self.fps, self.hop = model, int(n_streams), float(fps), self.rows.hop
+        self.max_samples, self.max_rows, self.device = self.rows.max_samples, self.rows.max_rows, self.rows.device
+        self._graph = None
+        self._g_samples = self._g_counts = None
+
+    def close(self) -> None:
+        self._graph = None
+        self.frames_engine.close()
+        self.rows.close()
+
+    def _launch(self, x, cnt) -> None:
+        r, f = self.rows, self.frames_engine
+        r._launch(x, cnt)
+        check(f._lib.km_koemorph_stream_step(f._h, _ptr(r.mel_rows), _ptr(r.emotion_rows), _ptr(r.row_counts), _ptr(f.out), _ptr(f.raw),
+                                             _ptr(f.rendered), _stream_ptr(self.device)))
+
+    def push(self, samples: torch.Tensor, counts: Optional[torch.Tensor] = None):
+        """samples (N, M <= max_samples), counts (N,) int32 (default: all M) -> ``KoeMorphStreams.step``'s dict, owned by the engine:
+        ``rendered[s]`` is the frames this push gave stream s, ``blendshapes[s, j]`` its j-th new frame for j < rendered[s]."""
+        x, cnt = self.rows._prepare(samples, counts)
+        self.rows._live()
+        self.frames_engine._live()
+        self.model._handle()                                     # uploads changed weights; the streams' state is kept
+        with torch.cuda.device(self.device):
+            self._launch(x, cnt)
+        return self.frames_engine._result()
+
+    def reset_streams(self, mask: torch.Tensor) -> None:
+        self.rows.reset_streams(mask)
+        self.frames_engine.reset_streams(mask)
+
+    def reset(self) -> None:
+        self.rows.reset()
+        self.frames_engine.reset()
+
+    def frames(self) -> torch.Tensor:
+        """(N,) int64: every stream's frames since its last reset; a copy."""
+        return self.frames_engine.frames()
+
+    def smoother_state(self) -> Optional[torch.Tensor]:
+        return self.frames_engine.smoother_state()
+
+    # ---- hipGraph replay ------------------------------------------------------------------------
+    def capture(self, n_per_stream: Optional[int] = None) -> None:
+        """Record one push of ``n_per_stream`` (default ``max_samples``) samples per stream with per-stream counts on static inputs."""
+        m = self.max_samples if n_per_stream is None else int(n_per_stream)
+        if not 1 <= m <= self.max_samples:
+            raise ValueError(f"{m} samples per stream outside 1 .. {self.max_samples}")
+        self.rows._live()
+        self.frames_engine._live()
+        self.model._handle()
+        dev = self.device
+        self._g_samples = torch.zeros(self.n_streams, m, device=dev)
+        self._g_counts = torch.zeros(self.n_streams, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._launch(self._g_samples, self._g_counts)
+        self._graph = g
+
+    def replay(self, samples: torch.Tensor, counts: Optional[torch.Tensor] = None):
+        """One captured push; samples (N, M <= the captured width), counts None: every stream brings all M."""
+        if self._graph is None:
+            raise RuntimeError("capture() first")
+        self.rows._live()
+        self.frames_engine._live()
+        check_samples(self.n_streams, self._g_samples.shape[1], samples, counts)
+        m = samples.shape[1]
+        self._g_samples[:, :m].copy_(samples, non_blocking=True)
+        if counts is not None:
+            self._g_counts.copy_(counts.clamp(max=m), non_blocking=True)
+        else:
+            self._g_counts.fill_(m)
+        self._graph.replay()
+        return self.frames_engine._result()
 
 
 def emotion_stream_shape(context_window: float = 20.0, update_interval: float = 0.3, sample_rate: int = 16000,

@@ -82,6 +82,14 @@ def cycle(i):
     ks.reset()
     ks._open = False                                       # the engine object is dropped without close(): km_destroy frees its group
     del ks
+    # one audio engine in front of a stream engine: create, pushes, reset; km_destroy frees both groups and the two plans
+    from koemorph_amd.streaming import KoeMorphAudioStreams
+    ka = KoeMorphAudioStreams(mf, 3, context_frames=9, emotion_window=0.5)
+    ka.push(audio[:3, :1600].contiguous()); ka.push(audio[:3, 1600:2133].contiguous())
+    ka.reset()
+    ka.push(audio[:3, :533].contiguous())
+    ka.rows._open = ka.frames_engine._open = False
+    del ka
     del tr, eng, g, m, mf, audio, emo
     gc.collect(); torch.cuda.empty_cache()
 
